@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- neighbor-group SpMM aggregation (GNNAdvisor `SAG`) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path -- `gnna_sag_f32` through the C ABI (prologue + the
 aggregation kernel's column-phase launches) -- over the whole synthetic graph, inputs already
@@ -15,20 +15,28 @@ auto mode (`--manual` = the reference's manual mode, partSize 32, single pass).
 weak-scaling leg -- every rank owns a Reddit-sized block of destination rows whose sources are drawn from all
 ranks' nodes; each step exchanges source features over RCCL/xGMI (only the referenced remote rows when that is
 clearly less than the whole blocks, `--exchange`) and aggregates locally (gnnadvisor_osdi21_amd/dist.py) -- so that
-N = 1 is the single-GPU workload.  `--scaling strong,config5` (default) adds, inside `config.values` (detail file: `config.legs`),
-the strong-scaling leg (the SAME Reddit-like graph as the single-GPU line, split into N nnz-balanced destination
-blocks) and, at 8 ranks (or with --config5-leg), BASELINE config 5 (papers100M-like, D = 128, exchange chosen
-collectively), each verified on every rank.
+N = 1 is the single-GPU workload.  With `--full`, `--scaling strong,config5` (default) adds, inside `config.values` (detail
+file: `config.legs`), the strong-scaling leg (the SAME Reddit-like graph as the single-GPU line, split into N nnz-balanced
+destination blocks) and, at 8 ranks (or with --config5-leg, with or without `--full`), BASELINE config 5 (papers100M-like,
+D = 128, exchange chosen collectively), each verified on every rank.
+
+A plain run (no `--full`) does what its headline figure needs and nothing else: it sets up the workload, runs W warm-up
+steps, times exactly K steps (`ms_per_step` = their wall time / K), writes the outputs of the last timed step when
+`--dump-outputs DIR` is given (dump_outputs: DIR/aggregated.npy on one GPU; the inputs are seeded, so the same arguments give
+the same inputs), and prints the line.  `--full` (implied by `--detail`) adds everything below: four more blocks of K steps
+for the spread, the verification, the floor probe, the reference-style timing, the other modes, the PMC child passes, the
+CPU baseline and the detail file.
 
 Rank 0 prints ONE compact JSON line (< 8 KB, normally ~2 KB: `compact_single` / `compact_sharded`; the driver keeps an 8 KB
-tail of stdout): the contract's keys, `config` as flat scalars, `roofline` and `cpu_baseline` as numbers.  `value` = total
-aggregated edges per second over all ranks.  The FULL record -- verification detail, the other modes, the reference-style
-wall-clock timing, the PMC detail, and with `--detail` the secondary legs (config 4's GIN widths, the HBM-resident graph,
-the node-order legs, config 5's per-rank shape, the prepared lifecycle) -- goes to `gpurun_out/bench_detail[_nN].json`
-(`--detail-file`) and a one-line summary to stderr.  Copies of the detail file are kept under profiles/.
+tail of stdout): the contract's keys, `config` as flat scalars, `roofline` (its PMC and floor terms with `--full`) and, with
+`--full`, `cpu_baseline` as numbers.  `value` = total aggregated edges per second over all ranks.  With `--full` the FULL
+record -- verification detail, the other modes, the reference-style wall-clock timing, the PMC detail, and with `--detail`
+the secondary legs (config 4's GIN widths, the HBM-resident graph, the node-order legs, config 5's per-rank shape, the
+prepared lifecycle) -- goes to the detail file (`--detail-file`; by default bench_detail[_nN].json in the run's output
+folder) and a one-line summary to stderr.  Copies of the detail file are kept under profiles/.
 
-`verified`: after the timed loop the timed configuration itself is checked -- X = ones must give the
-exact row nnz in every column (the reference's own known-answer test, unitest.py:54-63), and 256
+`verified` (`--full`; not in the line of a plain single-GPU run): after the timed loop the timed configuration itself is checked --
+X = ones must give the exact row nnz in every column (the reference's own known-answer test, unitest.py:54-63), and 256
 sampled rows of the timed randn output are compared with an fp64 gather-sum.
 
 `roofline` (definition frozen in round 5, tests/test_bench_cpu.py): `achieved` = SURVEY.md 8(d) ALGORITHMIC bytes per launch
@@ -146,11 +154,19 @@ def parse_args(argv=None):
     ap.add_argument("--config", default="reddit-like")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the graph (debug only)")
     ap.add_argument("--locality", type=float, default=0.0)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, measure and check everything else: the spread over more blocks of steps, the "
+                         "verification, the floor probe, the reference-style timing, the other modes, the PMC passes, the CPU "
+                         "baseline and the detail file (N ranks: the strong-scaling and config-5 legs, the single-GPU comparison)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (float32, at most 64 MB "
+                         "in all; a seeded sample of rows beyond that)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 PMC child passes (traffic = null)")
     ap.add_argument("--detail", action="store_true",
                     help="also run the secondary legs (config 4 GIN widths, the HBM-resident graph, the node-order legs, config 5's "
-                         "per-rank shape, the prepared lifecycle); their records go to the detail file, never into the line")
+                         "per-rank shape, the prepared lifecycle); their records go to the detail file, never into the line; "
+                         "implies --full")
     ap.add_argument("--detail-file", default="",
                     help="where the full record goes (default gpurun_out/bench_detail[_nN].json under the repo)")
     ap.add_argument("--no-secondary", action="store_true", help="with --detail: skip the HBM-resident second workload and the node-order legs")
@@ -1054,6 +1070,32 @@ def other_modes(w, steps: int = 10):
     return res
 
 
+# ---------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000     # all files of one --dump-outputs together
+DUMP_SAMPLE_SEED = 20211104
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """What the timed path returned in its last step -> `out_dir`/<name>.npy, float32, rows as they came back.  An array
+    larger than its share of `limit` is written as a fixed, seeded sample of its rows (the same rows for the same shape),
+    with the sampled row ids beside it as <name>_rows.npy (float64), so that two builds can be compared row for row."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = limit // max(1, len(arrays)) - 4096                          # (room for the .npy headers)
+    for name, t in arrays.items():
+        t = t.detach()
+        rows = t.shape[0] if t.dim() else 1
+        row_bytes = max(1, t.numel() // max(1, rows)) * 4
+        if rows * row_bytes <= share:
+            np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+            continue
+        k = max(1, share // (row_bytes + 8))
+        ids = torch.randperm(rows, generator=torch.Generator().manual_seed(DUMP_SAMPLE_SEED))[:k].sort().values
+        np.save(os.path.join(out_dir, name + ".npy"), t[ids.to(t.device)].float().cpu().numpy())
+        np.save(os.path.join(out_dir, name + "_rows.npy"), ids.numpy().astype(np.float64))
+
+
 # ---------------------------------------------------------------------------------------------- the line
 LINE_LIMIT = 8000       # the driver keeps an 8 KB tail of stdout: a longer line cannot be parsed (round 5's was 34.7 KB)
 LINE_TARGET = 4096
@@ -1159,16 +1201,18 @@ def compact_sharded(rec, detail_file=None):
 
 
 def emit(rec, result_fd, compact, args, suffix=""):
-    """Full record -> the detail file (and a short summary on stderr); the compact line -> the saved stdout."""
+    """Full record -> the detail file (with --full or --detail-file; and a short summary on stderr); the compact line -> the
+    saved stdout."""
     path = args.detail_file or os.path.join(ROOT, "gpurun_out", "bench_detail%s.json" % suffix)
     shown = None
-    try:
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump(_clean(rec, 9), f, indent=1)
-        shown = os.path.relpath(path, ROOT)
-    except OSError as exc:                                   # (a read-only tree must not cost the line)
-        print(f"# bench.py: detail file not written ({exc})", file=sys.stderr)
+    if args.detail_file or args.full:
+        try:
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            with open(path, "w") as f:
+                json.dump(_clean(rec, 9), f, indent=1)
+            shown = os.path.relpath(path, ROOT)
+        except OSError as exc:                               # (a read-only tree must not cost the line)
+            print(f"# bench.py: detail file not written ({exc})", file=sys.stderr)
     line = compact(rec, shown)
     text = json.dumps(line, allow_nan=False, separators=(",", ":"))
     if len(text) >= LINE_LIMIT:                              # never print a line the driver cannot read: shed the optional keys
@@ -1216,6 +1260,8 @@ def run_single(args, result_fd):
         world5, form5 = args.config[len("rank-of-"):].split("/")
         w5 = RankOf8Workload(dev, args.dim, form=form5, world=int(world5), scale=args.scale, manual=args.manual)
         e5, p5 = w5.time(args.steps, args.warmup)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"aggregated": w5.out})
         rec = {"metric": "aggregated edges/sec, config 5 per-rank shape", "value": w5.g.nnz * args.steps / e5, "unit": "edges/s",
                "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": e5 * 1e3 / args.steps,
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -1223,9 +1269,8 @@ def run_single(args, result_fd):
                "roofline": roofline_record(w5, p5["main_ms"], p5["prologue_ms"], None)}
         emit(rec, result_fd, compact_single, args, "_rank_of")
         return
-    extras = not args.headline_only
+    extras = args.full and not args.headline_only     # a plain run: set-up, warm-up, the timed steps, the line
     detail = extras and args.detail
-    tmpdir = tempfile.mkdtemp(prefix="gnna_bench_", dir="/tmp")
 
     def free():
         gc.collect()
@@ -1234,8 +1279,11 @@ def run_single(args, result_fd):
     # ---- the headline: BASELINE config 3 as a caller of the reference API runs it (lifecycle "dropin"; --prepared times
     # the build's own lifecycle extension instead, for profiling) --------------------------------------------------------
     w = Workload(args.config, args.dim, dev, scale=args.scale, locality=args.locality, manual=args.manual,
-                 part_size=args.partSize, lifecycle="prepared" if args.prepared else "dropin", calibrate=extras)
-    elapsed, prof = w.time(args.steps, args.warmup)
+                 part_size=args.partSize, lifecycle="prepared" if args.prepared else "dropin", calibrate=not args.headline_only)
+    elapsed, prof = w.time(args.steps, args.warmup, blocks=5 if extras else 1)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"aggregated": w.out})
+    tmpdir = tempfile.mkdtemp(prefix="gnna_bench_", dir="/tmp") if detail else None
     g = w.g
     kern_ms, pro_ms = prof["main_ms"], prof["prologue_ms"]
     check = w.verify() if extras else {"verified": None}
@@ -1417,7 +1465,8 @@ def run_single(args, result_fd):
         rec["roofline"]["other_workloads"] = others
     if extras and not args.no_cpu_baseline:
         rec["cpu_baseline"] = cpu_baseline(g.to("cpu"), w.Xc.cpu(), w.pp, w.p2n, args.dim)
-    shutil.rmtree(tmpdir, ignore_errors=True)
+    if tmpdir:
+        shutil.rmtree(tmpdir, ignore_errors=True)
     emit(rec, result_fd, compact_single, args)
 
 
@@ -1486,6 +1535,8 @@ def sharded_leg(args, dev, world, rank, name, rp, ci, bounds, D, feat, avg_span,
     sync_all()
     elapsed = time.perf_counter() - t0
     prof = _lib.profile_end()
+    if args.dump_outputs and name == "weak":              # (the headline leg: every rank writes its own block of rows)
+        dump_outputs(args.dump_outputs, {f"aggregated_rank{rank}": out}, limit=DUMP_LIMIT_BYTES // world)
     calls_per_step = prof["calls"] / max(1, steps)
     kern_ms = prof["main_ms"] * calls_per_step
     phases_last = _lib.last_num_phases()
@@ -1614,7 +1665,7 @@ def run_sharded(args, result_fd, world, rank, local_rank):
                                (1.0 - args.locality) * n_global / 3.0, args.steps, args.warmup, dist, args.exchange)
     del rp, ci
     single = None
-    if world == 1 and not args.headline_only:
+    if world == 1 and args.full and not args.headline_only:
         # the sharded path with one rank must be the single-GPU workload: the reference caller's line (lifecycle "dropin") is
         # timed beside it, and a sharded value more than 3 % below it fails the run (VERDICT r4 task 6b)
         w1 = Workload(args.config, D, dev, scale=args.scale, locality=args.locality, manual=args.manual, part_size=args.partSize)
@@ -1629,7 +1680,7 @@ def run_sharded(args, result_fd, world, rank, local_rank):
             raise RuntimeError("the one-rank sharded path reaches %.3f of the single-GPU value (%.1f vs %.1f G edges/s): more than 3 %% "
                                "below it" % (single["sharded_over_single"], legs["weak"]["value"] / 1e9, single["value"] / 1e9))
 
-    want = [v for v in args.scaling.split(",") if v]
+    want = [v for v in args.scaling.split(",") if v] if args.full else []      # (the extra legs run with --full)
     failed = {}
     # ---- strong scaling: the SAME graph as the single-GPU line, split into `world` nnz-balanced destination blocks
     if "strong" in want and world > 1:
@@ -1731,6 +1782,7 @@ def run_sharded(args, result_fd, world, rank, local_rank):
 def main():
     process_env()
     args = parse_args()
+    args.full = args.full or args.detail
     if args.pmc_child:
         import torch  # noqa: F401
         return pmc_child(args)

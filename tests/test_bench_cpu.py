@@ -16,8 +16,35 @@ def test_defaults_follow_the_driver_contract():
     assert a.gpus == 1 and a.steps > 0 and a.warmup > 0 and a.dim == 64 and a.config == "reddit-like"
     a = bench.parse_args(["--gpus", "8", "--steps", "5", "--warmup", "2"])
     assert (a.gpus, a.steps, a.warmup) == (8, 5, 2) and a.backend == "nccl" and a.exchange == "auto"
-    # N-rank line: the weak-scaling headline plus the strong-scaling and (at 8 ranks) config-5 legs by default
+    # N-rank line: the weak-scaling headline plus (with --full) the strong-scaling and (at 8 ranks) config-5 legs by default
     assert a.scaling == "strong,config5" and not a.config5_leg and a.config5_scale == 1.0
+    # a plain run measures the headline only and writes no outputs; --full adds the rest
+    assert not a.full and not a.detail and a.dump_outputs == ""
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_float32_whole_or_a_seeded_sample_of_rows(tmp_path):
+    import numpy as np
+    import torch
+    small = torch.arange(12 * 4, dtype=torch.float32).reshape(12, 4)
+    bench.dump_outputs(str(tmp_path / "a"), {"aggregated": small})
+    assert sorted(os.listdir(tmp_path / "a")) == ["aggregated.npy"]
+    got = np.load(tmp_path / "a" / "aggregated.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy())
+    # larger than the limit: a fixed sample of rows (the same for the same shape) and the row ids beside it
+    big = torch.randn(50000, 64, generator=torch.Generator().manual_seed(3))
+    limit = 1 << 20
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"aggregated": big}, limit=limit)
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["aggregated.npy", "aggregated_rows.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= limit
+    rows, vals = np.load(tmp_path / "b" / "aggregated_rows.npy"), np.load(tmp_path / "b" / "aggregated.npy")
+    assert rows.dtype == np.float64 and vals.dtype == np.float32 and len(rows) == len(vals) > 1000
+    assert np.all(np.diff(rows) > 0) and rows[-1] < 50000
+    assert np.array_equal(vals, big.numpy()[rows.astype(np.int64)])
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "aggregated_rows.npy"))
 
 
 def test_kernel_labels_name_what_ran():
@@ -180,6 +207,17 @@ def test_emit_writes_the_detail_file_and_one_line(tmp_path, capfd):
     full = json.load(open(A.detail_file))
     assert "other_workloads" in full["roofline"] and len(full["roofline"]["other_workloads"]) >= 9
     assert "line" in capfd.readouterr().err
+
+
+def test_a_plain_run_writes_no_detail_file(tmp_path, monkeypatch):
+    import json
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path))           # (where the default detail file would go)
+    rd, wr = os.pipe()
+    bench.emit(_canned(), wr, bench.compact_single, bench.parse_args(["--steps", "20", "--warmup", "5"]))
+    os.close(wr)
+    line = json.loads(os.read(rd, 1 << 16).decode())
+    os.close(rd)
+    assert os.listdir(tmp_path) == [] and "detail_file" not in line["config"]
 
 
 def test_the_n_rank_line_is_short_too():

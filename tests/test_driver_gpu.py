@@ -127,7 +127,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     detail = str(tmp_path / "detail_n2.json")
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu",
                           "--steps", "3", "--warmup", "1", "--scale", "0.05", "--config5-leg", "--config5-scale", "0.01",
-                          "--detail-file", detail],
+                          "--detail-file", detail, "--full"],
                          cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
@@ -153,6 +153,39 @@ def test_bench_launches_its_own_ranks(tmp_path):
     assert len(full["config"]["ranks"]) == 2
     assert len(full["config"]["exchange_only_ms_per_rank"]) == 2 and len(full["config"]["aggregate_only_ms_per_rank"]) == 2
     assert set(full["roofline"]["per_leg_kernels"]) == {"weak", "strong", "config5"}
+
+
+def test_plain_bench_run_times_its_steps_and_dumps_what_the_last_step_returned(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: one line whose ms_per_step is the wall time of
+    exactly K steps, no extra checks or measurements (no `verified`, no CPU baseline, no detail file), and DIR holds the
+    output of the last timed step -- equal to an fp64 CSR sum over the same seeded graph and features."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    import oracle
+    from gnnadvisor_osdi21_amd import graph
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = tmp_path / "outputs"
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "2", "--scale", "0.05",
+                          "--dump-outputs", str(out_dir)], cwd=root, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [l for l in res.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, res.stdout
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["warmup"] == 2 and rec["ms_per_step"] > 0 and rec["unit"] == "edges/s"
+    assert rec["value"] == pytest.approx(rec["config"]["nnz"] / (rec["ms_per_step"] * 1e-3), rel=1e-5)
+    assert "verified" not in rec and "cpu_baseline" not in rec and "detail_file" not in rec["config"]
+    assert sorted(os.listdir(out_dir)) == ["aggregated.npy"]
+    got = np.load(out_dir / "aggregated.npy")
+    dev = torch.device("cuda", 0)
+    g = graph.make_config_graph("reddit-like", device=dev, scale=0.05)
+    X = torch.randn(g.num_nodes, 64, device=dev, generator=torch.Generator(device=dev).manual_seed(1234)).cpu().numpy()
+    rp, ci = g.row_pointers.cpu().numpy(), g.column_index.cpu().numpy()
+    assert got.dtype == np.float32 and got.shape == (g.num_nodes, 64) and rec["config"]["nnz"] == g.nnz
+    ref = oracle.csr_f64(0, X, rp, ci)
+    scale = np.maximum(1.0, oracle.csr_f64(0, np.abs(X), rp, ci))
+    assert float((np.abs(got - ref) / scale).max()) <= 1e-4
 
 
 def test_drop_in_call_sequence_is_as_fast_as_the_tuned_path():
