@@ -47,7 +47,8 @@ EXPORTS = ("gnna_version", "gnna_build_id", "gnna_last_error", "gnna_count_parts
            "gnna_last_num_launches", "gnna_reorder_community_i32", "gnna_prepare_graph", "gnna_release_graph",
            "gnna_runtime_counters", "gnna_row_counts_i64", "gnna_row_splits_i64", "gnna_csr_from_edges_range_i32",
            "gnna_forget_graph", "gnna_agg_ld_f32", "gnna_preferred_ld", "gnna_device_cus", "gnna_host_threads",
-           "gnna_reorder_community_csr_i32", "gnna_relabel_edges_i32", "gnna_relabel_csr_i32", "gnna_runtime_counters_ex", "gnna_forget_plans")
+           "gnna_reorder_community_csr_i32", "gnna_relabel_edges_i32", "gnna_relabel_csr_i32", "gnna_runtime_counters_ex", "gnna_forget_plans",
+           "gnna_debug_untrusted_copies")
 
 
 def load() -> ctypes.CDLL:
@@ -151,6 +152,8 @@ def load() -> ctypes.CDLL:
     L.gnna_runtime_counters.argtypes = [ctypes.POINTER(ctypes.c_int64)]
     L.gnna_runtime_counters_ex.restype = ctypes.c_int
     L.gnna_runtime_counters_ex.argtypes = [ctypes.POINTER(ctypes.c_int64), ctypes.c_int]
+    L.gnna_debug_untrusted_copies.restype = ctypes.c_int
+    L.gnna_debug_untrusted_copies.argtypes = [ctypes.c_void_p]
     L.gnna_profile_begin.restype = ctypes.c_int
     L.gnna_profile_begin.argtypes = [ctypes.c_int]
     L.gnna_profile_end.restype = ctypes.c_int
@@ -200,7 +203,7 @@ def host_threads() -> int:
 
 
 def build_id() -> str:
-    """"0.6.0+<source hash>" of the loaded libgnna.so (gnna_build_id)."""
+    """"0.6.1+<source hash>" of the loaded libgnna.so (gnna_build_id)."""
     return load().gnna_build_id().decode()
 
 
@@ -562,8 +565,15 @@ def runtime_counters() -> dict:
     out = (ctypes.c_int64 * 16)()
     n = load().gnna_runtime_counters_ex(out, 16)
     names = ("plan_builds", "launch_syncs", "launch_frees", "launch_mallocs", "backoff_skips", "sweep_launches",
-             "pack_builds", "packed_launches", "full_hashes")
+             "pack_builds", "packed_launches", "full_hashes", "capture_scratch")
     return {name: int(out[i]) for i, name in enumerate(names) if i < n}
+
+
+def debug_untrusted_copies(column_index) -> int:
+    """For tests: how many packed id copies of this graph a full hash has marked "never trust again" (synchronises)."""
+    n = load().gnna_debug_untrusted_copies(column_index.data_ptr())
+    _check(min(n, 0))
+    return n
 
 
 def set_graph_phases(column_index, dim: int, column_phases: int) -> None:

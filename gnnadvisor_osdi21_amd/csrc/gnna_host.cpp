@@ -75,7 +75,7 @@ void apply_env()
         else if (!std::strcmp(tok, "PAD")) g_tuning.pad_rows = v;
         else if (!std::strcmp(tok, "ZERO")) g_tuning.zero_fill = v;
         else if (!std::strcmp(tok, "SWEEP")) g_tuning.sweep = v;
-        else if (!std::strcmp(tok, "CHECK")) g_tuning.ids_check_every = v;
+        else if (!std::strcmp(tok, "CHECK")) { if (v > 0) g_tuning.ids_check_every = v; }   // (<= 0: the built-in, as in gnna_set_tuning)
         else if (!std::strcmp(tok, "SLACK")) g_tuning.sweep_slack = v;
         else if (!std::strcmp(tok, "DET")) g_tuning.deterministic = v;
         else if (!std::strcmp(tok, "PACK")) g_tuning.pack_ids = v;
@@ -199,7 +199,7 @@ int gnna_version(void) { return GNNA_VERSION; }
 #ifndef GNNA_SOURCE_HASH
 #define GNNA_SOURCE_HASH "unhashed"        /* (built by hand, not by gnnadvisor_osdi21_amd/build.py) */
 #endif
-const char *gnna_build_id(void) { return "0.6.0+" GNNA_SOURCE_HASH; }
+const char *gnna_build_id(void) { return "0.6.1+" GNNA_SOURCE_HASH; }
 
 const char *gnna_last_error(void) { return t_error; }
 

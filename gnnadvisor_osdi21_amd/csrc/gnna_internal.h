@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <map>
 #include <utility>
+#include <vector>
 
 #include "gnna.h"
 
@@ -32,7 +33,20 @@ void apply_graph_hints(const void *column_index, int dim, gnna_tuning *tune);
 struct Workspace {
     void *ptr = nullptr;
     size_t bytes = 0;
-    bool captured = false;     // handed to a call that was being captured: a graph points at it, it is never freed
+};
+// Scratch of a call that is being captured: keyed by the capture (hipStreamGetCaptureInfo's id), the stream and the slot.  A
+// graph runs whenever and wherever it is replayed -- next to any eager call and any other graph -- so these buffers are handed
+// to the calls of that one capture on that one stream only, and are never freed.
+struct CaptureKey {
+    unsigned long long capture_id;
+    hipStream_t stream;
+    int slot;
+    bool operator<(const CaptureKey &o) const
+    {
+        if (capture_id != o.capture_id) return capture_id < o.capture_id;
+        if (stream != o.stream) return stream < o.stream;
+        return slot < o.slot;
+    }
 };
 struct DeviceState {
     std::atomic<bool> init{false};
@@ -44,8 +58,10 @@ struct DeviceState {
     uint32_t *sweep_sync = nullptr;  // kCallBlocks counter blocks for the sweep kernel's soft barrier (call_block_of)
     std::map<hipStream_t, int> stream_block;   // streams that own one of the first kStreamBlocks call blocks
     int captured_blocks = 0;                   // call blocks handed to captured calls so far (never returned)
-    std::map<std::pair<hipStream_t, int>, Workspace> ws;  // per stream: slot 1 staged / pre-scaled X, slot 2 partial rows of the
-                                                          // deterministic schedule / slabs of the weight-gradient kernel
+    std::map<std::pair<hipStream_t, int>, Workspace> ws;  // eager calls, per stream: slot 1 staged / pre-scaled X, slot 2 partial
+                                                          // rows of the deterministic schedule / slabs of the weight-gradient kernel
+    std::map<CaptureKey, Workspace> capture_ws;           // captured calls: the same slots, per capture and stream (never freed)
+    std::vector<void *> capture_outgrown;                 // buffers a capture outgrew: earlier calls of its graph still point at them
 };
 constexpr int kFlagSlots = 1024;
 // per-call lists of long runs of rows without edges that the sparse prologue leaves to a grid-wide pass
@@ -65,7 +81,8 @@ static_assert(kCallBlocks <= kFlagSlots && kStreamBlocks + kCapturedBlocks < kCa
 
 // State of the current device (lazily created: CU count, flag ring).
 int get_device_state(DeviceState **out);
-// Grow-only scratch buffer `slot` of `stream`.
+// Scratch buffer `slot` of `stream` for an eager call (grow-only, shared by the eager calls on that stream), or -- while `stream`
+// is being captured -- of that capture on that stream (allocated at capture time, never freed, never handed to another call).
 int get_workspace(DeviceState *ds, hipStream_t stream, int slot, size_t bytes, void **out);
 // Fresh non-zero sequence number of an aggregation call on `stream` and its slot among the flags (the call block's index).
 int32_t next_call_seq(DeviceState *ds, hipStream_t stream, int32_t **flag_slot);
@@ -136,7 +153,8 @@ int choose_slices(const SlicePlanStats &st, size_t x_bytes, int S, uint32_t slic
                   bool square, bool hinted_scattered);
 // Events on the launch path that the contract promises not to happen after gnna_prepare_graph (gnna_runtime_counters).
 enum { CTR_PLAN_BUILDS = 0, CTR_LAUNCH_SYNCS = 1, CTR_LAUNCH_FREES = 2, CTR_LAUNCH_MALLOCS = 3, CTR_BACKOFF_SKIPS = 4,
-       CTR_SWEEP_LAUNCHES = 5, CTR_PACK_BUILDS = 6, CTR_PACKED_LAUNCHES = 7, CTR_FULL_HASHES = 8, CTR_COUNT = 9 };
+       CTR_SWEEP_LAUNCHES = 5, CTR_PACK_BUILDS = 6, CTR_PACKED_LAUNCHES = 7, CTR_FULL_HASHES = 8, CTR_CAPTURE_SCRATCH = 9,
+       CTR_COUNT = 10 };
 void count_event(int which);
 
 struct StreamLaunch {

@@ -56,32 +56,57 @@ int get_device_state(DeviceState **out)
     return GNNA_OK;
 }
 
-// Grow-only scratch buffer for `stream` (work on one stream is ordered, so one buffer per
-// stream is enough).  hipFree of the old buffer synchronises the device, which makes the
-// replacement safe; steady state performs no allocation.
+// Scratch buffer `slot` for a call on `stream`.
+//   * Eager calls: one grow-only buffer per (stream, slot) -- work on one stream is ordered, so the calls on it can share it.
+//     hipFree of the old buffer synchronises the device, which makes the replacement safe; steady state allocates nothing.
+//   * A call that is being captured gets a buffer of its capture: keyed by (capture id, stream, slot), allocated here at capture
+//     time and never freed (the graph may be replayed at any time).  No eager call and no other capture is ever handed it: a
+//     graph is replayed whenever and wherever its caller likes -- next to eager calls on the capture stream and next to other
+//     graphs captured on that stream (torch.cuda.graph captures every graph on one side stream).  Calls of one capture on one
+//     stream are ordered in the graph, so they may share it; when a later one needs more, the outgrown buffer is kept too.
 int get_workspace(DeviceState *ds, hipStream_t stream, int slot, size_t bytes, void **out)
 {
-    std::lock_guard<std::mutex> lock(g_dev_mutex);
-    Workspace &w = ds->ws[std::make_pair(stream, slot)];
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cap) != hipSuccess) (void)hipGetLastError();
+    unsigned long long capture_id = 0;
+    if (hipStreamGetCaptureInfo(stream, &cap, &capture_id) != hipSuccess) {
+        (void)hipGetLastError();
+        cap = hipStreamCaptureStatusNone;
+    }
+    std::lock_guard<std::mutex> lock(g_dev_mutex);
+    if (cap != hipStreamCaptureStatusNone) {
+        if (cap != hipStreamCaptureStatusActive)
+            return fail(GNNA_ERR_HIP, "library scratch: the capture of this stream has been invalidated");
+        Workspace &w = ds->capture_ws[CaptureKey{capture_id, stream, slot}];
+        if (w.bytes < bytes) {
+            if (w.ptr) ds->capture_outgrown.push_back(w.ptr);
+            w.ptr = nullptr;
+            w.bytes = 0;
+            // (hipMalloc is not captured; relaxed mode lets it run while this thread, or another one, captures in global
+            // mode -- as PyTorch's caching allocator does)
+            hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+            (void)hipThreadExchangeStreamCaptureMode(&mode);
+            hipError_t e = hipMalloc(&w.ptr, bytes);
+            (void)hipThreadExchangeStreamCaptureMode(&mode);
+            if (e != hipSuccess) {
+                w.ptr = nullptr;
+                return fail(GNNA_ERR_HIP, "hipMalloc(scratch of a captured call, %zu B): %s", bytes, hipGetErrorString(e));
+            }
+            w.bytes = bytes;
+            count_event(CTR_CAPTURE_SCRATCH);
+        }
+        *out = w.ptr;
+        return GNNA_OK;
+    }
+    Workspace &w = ds->ws[std::make_pair(stream, slot)];
     if (w.bytes < bytes) {
-        // growing means hipFree + hipMalloc: illegal inside a stream capture -- refuse instead (warm the path up before
-        // capturing on this stream)
-        if (cap != hipStreamCaptureStatusNone)
-            return fail(GNNA_ERR_UNSUPPORTED, "library scratch (%zu B) would have to grow during stream capture: "
-                        "run the same call once on this stream before capturing", bytes);
-        // a buffer some captured graph points at stays allocated for good (the graph may be replayed at any time)
-        if (w.ptr && !w.captured) (void)hipFree(w.ptr);
+        if (w.ptr) (void)hipFree(w.ptr);
         w.ptr = nullptr;
         w.bytes = 0;
-        w.captured = false;
         const size_t want = bytes + bytes / 4;
         hipError_t e = hipMalloc(&w.ptr, want);
         if (e != hipSuccess) return fail(GNNA_ERR_HIP, "hipMalloc(workspace %zu B): %s", want, hipGetErrorString(e));
         w.bytes = want;
     }
-    if (cap != hipStreamCaptureStatusNone) w.captured = true;
     *out = w.ptr;
     return GNNA_OK;
 }

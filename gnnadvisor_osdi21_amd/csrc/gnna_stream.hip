@@ -912,6 +912,8 @@ struct Plan {
         int64_t num_ids = 0;
         hipEvent_t ready = nullptr;
         hipStream_t made_on = nullptr;
+        hipEvent_t hashed = nullptr;     // recorded behind the latest full hash of the copy: the next one, from whichever stream, waits
+                                         // for it (the hashes share the accumulator words of the state: two at once mix their sums)
         uint64_t stamp = 0;              // value of the plan's lookup counter at the last use
     };
     std::vector<Packed> packed;
@@ -1053,6 +1055,7 @@ int get_slice_plan(DeviceState *ds, hipStream_t stream, const int32_t *column_in
         for (auto &pk : pl->packed) {
             if (pk.ids) { (void)hipFree(pk.ids); count_event(CTR_LAUNCH_FREES); }
             if (pk.ready) (void)hipEventDestroy(pk.ready);
+            if (pk.hashed) (void)hipEventDestroy(pk.hashed);
         }
         pl->packed.clear();
         pl->col = column_index; pl->pp = part_pointers; pl->p2n = part2Node; pl->P = num_parts; pl->slice_rows = slice_rows;
@@ -1117,6 +1120,7 @@ int release_slice_plans(const void *column_index, bool deferred)
         for (auto &pk : pl->packed) {
             if (pk.ids) g_dead.push_back(pk.ids);
             if (pk.ready) (void)hipEventDestroy(pk.ready);
+            if (pk.hashed) (void)hipEventDestroy(pk.hashed);
         }
         delete pl;
         g_plans.erase(g_plans.begin() + (long)i);
@@ -1150,13 +1154,18 @@ int launch_ids_sample_check(hipStream_t stream, const int32_t *col, int64_t n, c
     return e == hipSuccess ? GNNA_OK : fail(GNNA_ERR_HIP, "packed ids check launch: %s", hipGetErrorString(e));
 }
 
-static void launch_full_hash(DeviceState *ds, hipStream_t stream, const Plan *pl, int64_t nnz, unsigned long long *state, int store,
+// The full hash of copy `pk` on `stream`, ordered after the copy's previous hash on any stream (caller holds g_plan_mutex, so
+// the hashes of one copy are enqueued one after the other: each waits for the event the one before recorded).
+static void launch_full_hash(DeviceState *ds, hipStream_t stream, const Plan *pl, Plan::Packed &pk, int64_t nnz, int store,
                              int32_t *stale_flag, int32_t seq)
 {
+    if (!pk.hashed) (void)hipEventCreateWithFlags(&pk.hashed, hipEventDisableTiming);
+    else (void)hipStreamWaitEvent(stream, pk.hashed, 0);
     const int64_t work = (nnz + 3) / 4 + pl->P + 1;
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((work + kBlock - 1) / kBlock, (int64_t)ds->num_cus * 8));
     hipLaunchKernelGGL(ids_full_hash_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, static_cast<const int32_t *>(pl->col), nnz,
-                       static_cast<const int32_t *>(pl->pp), pl->P, state, store, stale_flag, seq);
+                       static_cast<const int32_t *>(pl->pp), pl->P, pk.checksum, store, stale_flag, seq);
+    (void)hipEventRecord(pk.hashed, stream);
 }
 
 // Packed ids of a plan for (B phases, G groups per chunk): looked up, or -- with may_build, outside a stream
@@ -1186,7 +1195,7 @@ int get_packed_ids(DeviceState *ds, hipStream_t stream, void *plan_handle, int B
             // aggregation (not while capturing: a replayed graph would either always or never pay for it)
             if (stale_flag && check_every > 0 && check_every < (1 << 30) && cap == hipStreamCaptureStatusNone &&
                 ++pk.hits % (uint64_t)check_every == 0) {
-                launch_full_hash(ds, stream, pl, pk.num_ids, pk.checksum, 0, stale_flag, seq);
+                launch_full_hash(ds, stream, pl, pk, pk.num_ids, 0, stale_flag, seq);
                 count_event(CTR_FULL_HASHES);
             }
             *ids = pk.ids; *item_off = pk.item_off;
@@ -1240,6 +1249,7 @@ int get_packed_ids(DeviceState *ds, hipStream_t stream, void *plan_handle, int B
         (void)hipGetLastError();
         slot->ids = nullptr; slot->item_off = nullptr; slot->B = 0; slot->G = 0;
         if (slot->ready) { (void)hipEventDestroy(slot->ready); slot->ready = nullptr; }
+        if (slot->hashed) { (void)hipEventDestroy(slot->hashed); slot->hashed = nullptr; }
         if (slot == &pl->packed.back()) pl->packed.pop_back();
         else slot->stamp = pl->pack_lookups;
         pl->pack_no_memory_until = pl->pack_lookups + kPackedNoMemoryBackoff;
@@ -1259,7 +1269,7 @@ int get_packed_ids(DeviceState *ds, hipStream_t stream, void *plan_handle, int B
     hipLaunchKernelGGL(ids_checksum_kernel, dim3(1), dim3(kWave), 0, stream, static_cast<const int32_t *>(pl->col), nnz,
                        static_cast<const int32_t *>(pl->pp), pl->P, slot->checksum);
     (void)hipMemsetAsync(slot->checksum + 1, 0, 7 * sizeof(unsigned long long), stream);
-    launch_full_hash(ds, stream, pl, nnz, slot->checksum, 1, nullptr, 0);
+    launch_full_hash(ds, stream, pl, *slot, nnz, 1, nullptr, 0);
     slot->hits = 0;
     e = hipGetLastError();
     if (e != hipSuccess) return fail(GNNA_ERR_HIP, "packed ids launch: %s", hipGetErrorString(e));
@@ -1357,6 +1367,24 @@ int gnna_runtime_counters_ex(int64_t *out, int capacity)
 {
     for (int i = 0; i < capacity && i < gnna::CTR_COUNT; i++) out[i] = (int64_t)gnna::g_counters[i].load();
     return gnna::CTR_COUNT;
+}
+int gnna_debug_untrusted_copies(const int32_t *column_index)
+{
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return gnna::fail(GNNA_ERR_HIP, "hipDeviceSynchronize: %s", hipGetErrorString(e));
+    std::lock_guard<std::mutex> lock(gnna::g_plan_mutex);
+    int untrusted = 0;
+    for (gnna::Plan *pl : gnna::g_plans) {
+        if (pl->col != column_index) continue;
+        for (auto &pk : pl->packed) {
+            if (!pk.ids || !pk.checksum) continue;
+            unsigned long long mark = 0;
+            e = hipMemcpy(&mark, pk.checksum + 4, sizeof(mark), hipMemcpyDeviceToHost);
+            if (e != hipSuccess) return gnna::fail(GNNA_ERR_HIP, "reading a packed copy's state: %s", hipGetErrorString(e));
+            if (mark != 0ull) untrusted++;
+        }
+    }
+    return untrusted;
 }
 #pragma GCC visibility pop
 }

@@ -31,13 +31,22 @@
  *     enqueue work.  One exception: the first aggregation on a partition the library has not
  *     seen yet (and that is large enough to be worth slicing) runs a counting pass over the
  *     column ids and synchronises `stream` once to read its statistics; never while the stream
- *     is being captured.  Library scratch is allocated on first use and never grown during capture
- *     (GNNA_ERR_UNSUPPORTED instead): warm a path up once before capturing it -- or call
- *     gnna_prepare_graph() once per graph: after it no aggregation on that graph synchronises,
- *     allocates or frees, and a captured call takes the same schedule as an eager one.  Captured calls keep a block of
- *     per-call device scratch (step counters, lists) of their own for good, so graphs may be replayed concurrently; the
- *     library holds 160 such blocks per device -- graphs whose calls were captured after those are used up share a ring and
- *     must not be replayed concurrently with each other.
+ *     is being captured.  Library scratch (the staged or pre-scaled copy of the gathered rows, the
+ *     deterministic schedule's partial rows, the weight-gradient slabs) is allocated on first use:
+ *     eager calls share one grow-only buffer per (stream, slot).  A call that is being captured
+ *     gets buffers of its own capture instead, keyed by (capture id, stream, slot), allocated with
+ *     hipMalloc at capture time (in relaxed capture mode, so a global-mode capture accepts it) and
+ *     never freed: each captured graph keeps its scratch -- up to the size of the staged input
+ *     matrix per aggregation width, plus the partial rows or slabs -- for the life of the process,
+ *     and no eager call and no other capture is ever handed it.  So a path needs no warm-up on the
+ *     capture stream (torch.cuda.make_graphed_callables captures with none), and graphs captured on
+ *     one stream may be replayed concurrently with each other and with eager calls on that stream.
+ *     gnna_runtime_counters_ex [9] counts these allocations.  gnna_prepare_graph() once per graph:
+ *     after it no eager aggregation on that graph synchronises, allocates or frees, and a captured
+ *     call takes the same schedule as an eager one.  Captured calls also keep a block of per-call
+ *     device scratch (step counters, lists) of their own for good; the library holds 160 such
+ *     blocks per device -- graphs whose calls were captured after those are used up share a ring
+ *     and must not be replayed concurrently with each other.
  *   - return value: GNNA_OK or a negative gnna_status; gnna_last_error() gives the
  *     message for the calling thread.  (The reference printf()s and exit(-1)s on launch
  *     failure, .cu:177-181; this library reports instead.)
@@ -55,7 +64,7 @@
 extern "C" {
 #endif
 
-#define GNNA_VERSION 600 /* 0.6.0: gnna_tuning.ids_check_every (full hash of the ids behind a packed copy), gnna_device_cus, gnna_host_threads; 0.5.0: gnna_tuning opens with struct_size (checked by gnna_set_tuning, which now returns a status), gnna_build_id; 0.4.1: gnna_sddmm_ld_f32 (leading dimensions for both SDDMM sides); 0.4.0: gnna_agg_ld_f32 (leading dimensions, ReLU epilogue), gnna_forget_graph, chunk-walk kernel retired; 0.3.1: gnna_tuning grew (pack_ids); 0.3.0: sweep, sweep_slack, graph lifecycle, 64-bit CSR builder */
+#define GNNA_VERSION 601 /* 0.6.1: per-capture library scratch, full hashes of a packed copy ordered across streams, gnna_debug_untrusted_copies, counter [9]; 0.6.0: gnna_tuning.ids_check_every (full hash of the ids behind a packed copy), gnna_device_cus, gnna_host_threads; 0.5.0: gnna_tuning opens with struct_size (checked by gnna_set_tuning, which now returns a status), gnna_build_id; 0.4.1: gnna_sddmm_ld_f32 (leading dimensions for both SDDMM sides); 0.4.0: gnna_agg_ld_f32 (leading dimensions, ReLU epilogue), gnna_forget_graph, chunk-walk kernel retired; 0.3.1: gnna_tuning grew (pack_ids); 0.3.0: sweep, sweep_slack, graph lifecycle, 64-bit CSR builder */
 #define GNNA_API __attribute__((visibility("default")))
 
 typedef enum gnna_status {
@@ -404,8 +413,14 @@ GNNA_API int gnna_forget_plans(const int32_t *column_index);
  *   read packed ids. */
 GNNA_API void gnna_runtime_counters(int64_t out[8]);
 /* The same list, open-ended: fills out[0 .. min(capacity, count)) and returns the number of counters this library keeps.
- *   [8] full hashes of the ids behind a packed copy run at a launch (gnna_tuning.ids_check_every). */
+ *   [8] full hashes of the ids behind a packed copy run at a launch (gnna_tuning.ids_check_every), [9] scratch buffers
+ *   allocated for calls that were being captured (kept for good: see "stream" under Conventions). */
 GNNA_API int gnna_runtime_counters_ex(int64_t *out, int capacity);
+/* For tests: waits for the device, then returns how many packed id copies of the graph whose column_index starts at this
+ * device address are marked "never trust again" by a full hash (gnna_tuning.ids_check_every), or a negative gnna_status.
+ * The full hashes of one copy run one after the other, whichever streams the calls come from, so only a column_index that
+ * really changed marks its copy. */
+GNNA_API int gnna_debug_untrusted_copies(const int32_t *column_index);
 
 /* Number of column phases the calling thread's most recent aggregation call used (>= 1). */
 GNNA_API int gnna_last_num_phases(void);

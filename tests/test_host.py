@@ -17,7 +17,7 @@ from gnnadvisor_osdi21_amd import _lib, decider, graph, load_extension
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_exports_every_declared_symbol_of_version_601():
     header = open(os.path.join(ROOT, "include", "gnna.h")).read()
     declared = set(re.findall(r"GNNA_API\s+[\w\s\*]+?\b(gnna_\w+)\s*\(", header))
     assert declared, "no GNNA_API declarations found"
@@ -25,16 +25,19 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in gnna.h but not exported by libgnna.so"
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
-    assert lib.gnna_version() == 600
+    assert lib.gnna_version() == 601
+    assert re.search(r"#define GNNA_VERSION 601\b", header)
 
 
-def test_binaries_carry_the_hash_of_the_sources_beside_them():
+def test_binaries_carry_version_0_6_1_and_the_hash_of_the_sources_beside_them():
     """gnna_build_id() / GNNAdvisor.build_id(): the loaded binaries were compiled from this tree's sources."""
+    import gnnadvisor_osdi21_amd
+    assert gnnadvisor_osdi21_amd.__version__ == "0.6.1"
     from gnnadvisor_osdi21_amd import build as gbuild
     want = gbuild.source_hash()
     assert re.fullmatch(r"[0-9a-f]{16}", want)
-    assert _lib.build_id() == "0.6.0+" + want
-    assert load_extension().build_id() == f"module {want}, library 0.6.0+{want}"
+    assert _lib.build_id() == "0.6.1+" + want
+    assert load_extension().build_id() == f"module {want}, library 0.6.1+{want}"
 
 
 def test_set_tuning_refuses_another_struct_layout():
@@ -145,6 +148,20 @@ def test_tuning_roundtrip():
     finally:
         _lib.reset_tuning()
     assert _lib.get_tuning()["groups_per_chunk"] == 16
+
+
+def test_tune_env_check_keeps_the_builtin_for_values_up_to_zero():
+    """GNNA_TUNE=CHECK=n sets ids_check_every; n <= 0 means "built-in" (64), never "stale-id guard off"."""
+    import subprocess
+    import sys
+    code = "from gnnadvisor_osdi21_amd import _lib; print(_lib.get_tuning()['ids_check_every'])"
+    for value, want in (("0", 64), ("-3", 64), ("5", 5)):
+        env = {k: v for k, v in os.environ.items() if k not in ("GNNA_TUNE", "GNNA_DEBUG_FULL_CHECKSUM")}
+        env["GNNA_TUNE"] = f"CHECK={value}"
+        env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
+        res = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=120)
+        assert res.returncode == 0, res.stderr
+        assert int(res.stdout.strip().splitlines()[-1]) == want, (value, res.stdout)
 
 
 class _DS:
