@@ -48,7 +48,8 @@ EXPORTS = ("gnna_version", "gnna_build_id", "gnna_last_error", "gnna_count_parts
            "gnna_runtime_counters", "gnna_row_counts_i64", "gnna_row_splits_i64", "gnna_csr_from_edges_range_i32",
            "gnna_forget_graph", "gnna_agg_ld_f32", "gnna_preferred_ld", "gnna_device_cus", "gnna_host_threads",
            "gnna_reorder_community_csr_i32", "gnna_relabel_edges_i32", "gnna_relabel_csr_i32", "gnna_runtime_counters_ex", "gnna_forget_plans",
-           "gnna_debug_untrusted_copies")
+           "gnna_debug_untrusted_copies", "gnna_agg_edge_ld_f32", "gnna_edge_softmax_f32", "gnna_edge_softmax_backward_f32",
+           "gnna_reverse_edges_i32")
 
 
 def load() -> ctypes.CDLL:
@@ -159,6 +160,17 @@ def load() -> ctypes.CDLL:
     L.gnna_profile_end.restype = ctypes.c_int
     L.gnna_profile_end.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                    ctypes.POINTER(ctypes.c_int)]
+    L.gnna_agg_edge_ld_f32.restype = ctypes.c_int
+    L.gnna_agg_edge_ld_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 5 + [
+        ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p]
+    L.gnna_edge_softmax_f32.restype = ctypes.c_int
+    L.gnna_edge_softmax_f32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                        ctypes.c_void_p, ctypes.c_void_p]
+    L.gnna_edge_softmax_backward_f32.restype = ctypes.c_int
+    L.gnna_edge_softmax_backward_f32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                 ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    L.gnna_reverse_edges_i32.restype = ctypes.c_int
+    L.gnna_reverse_edges_i32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
     _lib = L
     return L
 
@@ -619,3 +631,58 @@ def sddmm(dst_feat, src_feat, column_index, part_pointers, part2Node, partSize=3
                                             part2Node.data_ptr(), out.data_ptr(), n_out, n_in, dim, part2Node.numel(),
                                             int(partSize), _stream(dst_feat.device)))
     return out
+
+
+def agg_edge(X, column_index, edge_weight, part_pointers, part2Node, num_out_rows, partSize=32, out=None,
+             accumulate=False, relu=False):
+    """gnna_agg_edge_ld_f32: out[i] (+)= sum_e w[e] * X[column_index[e]] with caller-supplied edge weights `edge_weight`
+    ([nnz] float32, indexed like column_index).  Strided X / out as in agg_ld."""
+    if not X.is_cuda:
+        raise GnnaError("aggregation needs device tensors: there is no CPU path in libgnna")
+    assert edge_weight.dtype == torch.float32 and edge_weight.is_contiguous() and edge_weight.numel() == column_index.numel(), \
+        "edge_weight must be a contiguous float32 tensor indexed like column_index"
+    xp, n_in, dim, ld_in = _rows_view(X, "X")
+    if out is None:
+        assert not accumulate, "accumulate needs an existing `out`"
+        out = _fresh_output((num_out_rows, dim), X.device)
+    yp, n_out, dim_o, ld_out = _rows_view(out, "out")
+    assert n_out == int(num_out_rows) and dim_o == dim and out.device == X.device
+    flags = (ACCUMULATE if accumulate else 0) | (EPILOGUE_RELU if relu else 0)
+    with torch.cuda.device(X.device):
+        _check(load().gnna_agg_edge_ld_f32(xp, ld_in, n_in, column_index.data_ptr(), edge_weight.data_ptr(),
+                                           part_pointers.data_ptr(), part2Node.data_ptr(), yp, ld_out, int(num_out_rows), dim,
+                                           part2Node.numel(), int(partSize), flags, _stream(X.device)))
+    return out
+
+
+def edge_softmax(scores, row_pointers, out=None):
+    """gnna_edge_softmax_f32: softmax over every row's edges; scores [nnz] or head-major [heads, nnz] (contiguous)."""
+    assert scores.is_cuda and scores.dtype == torch.float32 and scores.is_contiguous() and scores.dim() in (1, 2)
+    heads, nnz = (1, scores.numel()) if scores.dim() == 1 else scores.shape
+    out = torch.empty_like(scores) if out is None else out
+    with torch.cuda.device(scores.device):
+        _check(load().gnna_edge_softmax_f32(scores.data_ptr(), row_pointers.data_ptr(), row_pointers.numel() - 1, nnz, heads,
+                                            out.data_ptr(), _stream(scores.device)))
+    return out
+
+
+def edge_softmax_backward(probs, grad_probs, row_pointers, out=None):
+    """gnna_edge_softmax_backward_f32: grad_scores = probs * (grad_probs - sum_row probs * grad_probs)."""
+    assert probs.is_cuda and probs.dtype == torch.float32 and probs.is_contiguous() and probs.dim() in (1, 2)
+    assert grad_probs.shape == probs.shape and grad_probs.dtype == torch.float32 and grad_probs.is_contiguous()
+    heads, nnz = (1, probs.numel()) if probs.dim() == 1 else probs.shape
+    out = torch.empty_like(probs) if out is None else out
+    with torch.cuda.device(probs.device):
+        _check(load().gnna_edge_softmax_backward_f32(probs.data_ptr(), grad_probs.data_ptr(), row_pointers.data_ptr(),
+                                                     row_pointers.numel() - 1, nnz, heads, out.data_ptr(),
+                                                     _stream(probs.device)))
+    return out
+
+
+def reverse_edges(row_pointers, column_index) -> torch.Tensor:
+    """gnna_reverse_edges_i32 (host): rev[e] = position of the edge col(e) -> row(e) matching e, int32 [nnz] on the CPU.
+    Raises GnnaError, naming the first unmatched edge, when the graph's structure is not symmetric."""
+    rp, ci = _host_i32(row_pointers), _host_i32(column_index)
+    rev = torch.empty(ci.numel(), dtype=torch.int32)
+    _check(load().gnna_reverse_edges_i32(rp.data_ptr(), ci.data_ptr(), rp.numel() - 1, rev.data_ptr()))
+    return rev

@@ -411,6 +411,18 @@ int sweep_auto_phases(const gnna_tuning &t, int mode, int dim, size_t x_bytes, i
     return std::max(2, std::min(std::min(16, 2 * B), std::max(2, part_size / 4)));
 }
 
+// Phases of the sweep kernel for an unweighted call at this width on a prepared graph (0 or 1: the streaming kernel runs): the
+// sweep's packed copy (Bs phases, 64 groups per chunk) is the one gnna_prepare_graph makes.  MODE_EDGE, which the sweep does
+// not run, takes the streaming kernel on those phases and chunks, so that it reads the same copy.
+int sweep_phases_of_width(const gnna_tuning &t, int dim, size_t foot_bytes, size_t x_bytes, int64_t num_out_rows,
+                          int64_t num_in_rows, const SlicePlanStats &st, int B, int num_cus, int partSize, int S)
+{
+    int Bs = sweep_auto_phases(t, MODE_SAG, dim, foot_bytes, num_out_rows, num_in_rows, st, B, num_cus, t.deterministic == 1, partSize);
+    if (t.sweep == 1 && t.deterministic != 1 && sweep_supports(MODE_SAG, dim, x_bytes))
+        Bs = t.column_phases >= 2 ? B : std::max(2, std::min(std::min(16, 2 * B), std::max(2, partSize / 4)));
+    return std::min(Bs, S);
+}
+
 int choose_slices(const SlicePlanStats &st, size_t x_bytes, int S, uint32_t slice_rows, int64_t num_out_rows,
                   bool square, bool hinted_scattered)
 {
@@ -479,6 +491,7 @@ namespace {
 
 // One aggregation call.  ld_in / ld_out: row strides of `input` / `out` in floats (>= dim).  flags: GNNA_ACCUMULATE,
 // GNNA_EPILOGUE_RELU.  num_windows > 1: the call is one of a windowed sequence and covers source windows [win_begin, win_end).
+// (MODE_EDGE: `degrees_in` carries the caller's edge weights, indexed like column_index; `degrees` is unused)
 int launch_agg(int mode, const float *input, int64_t ld_in, int64_t num_in_rows, const int32_t *column_index,
                const float *degrees, const float *degrees_in, float epsilon, const int32_t *part_pointers,
                const int32_t *part2Node, float *out, int64_t ld_out, int64_t num_nodes, int dim, int64_t num_parts,
@@ -564,6 +577,8 @@ int launch_agg(int mode, const float *input, int64_t ld_in, int64_t num_in_rows,
         return fail(GNNA_ERR_INVALID_ARGUMENT, "null index pointer");
     if (mode == MODE_GCN && (!degrees || !degrees_in))
         return fail(GNNA_ERR_INVALID_ARGUMENT, "null degrees pointer");
+    if (mode == MODE_EDGE && num_parts > 0 && !degrees_in)
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "null edge_weight pointer");
     if (out == input) return fail(GNNA_ERR_INVALID_ARGUMENT, "out must not alias input");
 
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
@@ -737,7 +752,8 @@ int launch_agg(int mode, const float *input, int64_t ld_in, int64_t num_in_rows,
     const int auto_Bs = (cnt && !windowed && plan.stats.valid)
                             ? sweep_auto_phases(tune, mode, dim, foot_bytes, num_nodes, num_in_rows, plan.stats, B, ds->num_cus,
                                                 tune.deterministic == 1, partSize) : 0;
-    if (cnt && !windowed && dim >= 4 && (tune.sweep == 1 || auto_Bs > 0) && tune.deterministic != 1 && sweep_supports(mode, dim, x_bytes)) {
+    if (mode != MODE_EDGE && cnt && !windowed && dim >= 4 && (tune.sweep == 1 || auto_Bs > 0) && tune.deterministic != 1 &&
+        sweep_supports(mode, dim, x_bytes)) {
         int Bs = B;
         if (auto_Bs > 0) {
             Bs = std::min(auto_Bs, S);
@@ -776,13 +792,23 @@ int launch_agg(int mode, const float *input, int64_t ld_in, int64_t num_in_rows,
     }
 
     // ---- streaming kernel (gnna_stream.hip) -----------------------------------------------------------------------
+    // a work item is (chunk, slice): keep its edge count about what `groups_per_chunk` groups are in one pass
+    int G = std::min(64, tune.groups_per_chunk * B);
+    if (mode == MODE_EDGE && cnt && !windowed && plan.handle && plan.pinned && (plan.stats.valid || tune.sweep == 1) &&
+        tune.xcd_remap != 0) {
+        // a prepared width the unweighted call sweeps: the sweep's phases and chunks (and so its packed copy)
+        const int Bs = sweep_phases_of_width(tune, dim, foot_bytes, x_bytes, num_nodes, num_in_rows, plan.stats, B, ds->num_cus,
+                                             partSize, S);
+        if (Bs >= 2) { B = Bs; G = kWave; }
+    }
     t_last_phases = B;
     StreamLaunch a;
     a.mode = mode; a.X = X; a.col = column_index; a.pp = part_pointers; a.p2n = part2Node; a.Y = out;
-    a.cnt = cnt; a.row_scale = row_scale; a.deg_row = degrees; a.deg_col = degrees_in; a.flag = flag; a.seq = seq;
+    a.cnt = cnt; a.row_scale = row_scale; a.flag = flag; a.seq = seq;
+    if (mode == MODE_EDGE) { a.deg_row = nullptr; a.deg_col = nullptr; a.edge_w = degrees_in; }
+    else { a.deg_row = degrees; a.deg_col = degrees_in; }
     a.trust = tune.trust_canonical ? 1 : 0; a.P = num_parts;
-    // a work item is (chunk, slice): keep its edge count about what `groups_per_chunk` groups are in one pass
-    a.D = dim; a.ldx = ldx; a.ldy = ldy; a.G = std::min(64, tune.groups_per_chunk * B); a.U = tune.loads_in_flight; a.S = S; a.B = B;
+    a.D = dim; a.ldx = ldx; a.ldy = ldy; a.G = G; a.U = tune.loads_in_flight; a.S = S; a.B = B;
     a.win_lo = win_lo; a.win_hi = win_hi; a.relu = relu; a.num_out_rows = num_nodes;
     t_last_launches = 1;
     a.wide = wide; a.plain_ok = (B == 1 && !accumulate_into_out && !windowed); a.xcd_remap = tune.xcd_remap != 0;
@@ -900,6 +926,15 @@ int gnna_agg_rect_windows_f32(int mode, const float *input, int64_t num_in_rows,
                       accumulate != 0 ? GNNA_ACCUMULATE : 0u, num_windows, window_begin, window_end);
 }
 
+int gnna_agg_edge_ld_f32(const float *input, int64_t ld_in, int64_t num_in_rows, const int32_t *column_index,
+                         const float *edge_weight, const int32_t *part_pointers, const int32_t *part2Node, float *out,
+                         int64_t ld_out, int64_t num_out_rows, int dim, int64_t num_parts, int partSize, unsigned flags,
+                         void *stream)
+{
+    return launch_agg(MODE_EDGE, input, ld_in, num_in_rows, column_index, nullptr, edge_weight, 1.f, part_pointers,
+                      part2Node, out, ld_out, num_out_rows, dim, num_parts, partSize, 32, 4, stream, flags);
+}
+
 int64_t gnna_preferred_ld(int dim, int64_t num_in_rows, int64_t num_edges)
 {
     if (dim <= 0 || num_in_rows <= 0) return dim > 0 ? dim : 0;
@@ -977,11 +1012,8 @@ int gnna_prepare_graph(const int32_t *column_index, const int32_t *part_pointers
             // the kernel that will run at this width: the sweep (its own phase count, 64 groups per chunk) for the unweighted
             // and pre-scaled calls where the library picks it, the streaming kernel for everything else -- and for the
             // per-edge GCN form (gcn_prescale = 2) at any width, which the sweep does not run
-            int Bs = sweep_auto_phases(t, MODE_SAG, dim, foot_bytes, num_out_rows, num_in_rows, plan.stats, B, ds->num_cus,
-                                       t.deterministic == 1, partSize);
-            if (t.sweep == 1 && t.deterministic != 1 && sweep_supports(MODE_SAG, dim, x_bytes))
-                Bs = t.column_phases >= 2 ? B : std::max(2, std::min(std::min(16, 2 * B), std::max(2, partSize / 4)));
-            Bs = std::min(Bs, plan.S);
+            const int Bs = sweep_phases_of_width(t, dim, foot_bytes, x_bytes, num_out_rows, num_in_rows, plan.stats, B, ds->num_cus,
+                                                 partSize, plan.S);
             const bool swept = Bs >= 2 && t.xcd_remap != 0;
             if (swept) rc = get_packed_ids(ds, stream, plan.handle, Bs, kWave, true, true, &ids, &off);
             if (rc == GNNA_OK && (!swept || t.gcn_prescale == 2))

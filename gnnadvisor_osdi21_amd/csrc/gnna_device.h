@@ -16,7 +16,8 @@ constexpr int kBlock = 256;
 constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kXcds = 8;
 
-enum { MODE_SAG = 0, MODE_GCN = 1, MODE_GIN = 2, MODE_SDDMM = 3 };
+// MODE_EDGE: per-edge weights supplied by the caller (w[e], indexed like column_index)
+enum { MODE_SAG = 0, MODE_GCN = 1, MODE_GIN = 2, MODE_SDDMM = 3, MODE_EDGE = 4 };
 
 // T: register type; M: the same vector as it sits in memory.  Feature rows are only 4-byte
 // aligned in general (row stride = D floats, D arbitrary), and gfx950 global_load/store_dwordx4

@@ -340,6 +340,83 @@ int gnna_build_part_i32(int partSize, const int32_t *indptr, int64_t num_nodes,
     return GNNA_OK;
 }
 
+// ---- reverse-edge map -----------------------------------------------------------------------
+// Every row's positions sorted by (column id, position); the t-th position of the run of column j in row i then pairs
+// with the t-th position of the run of column i in row j.  Rows are sorted and matched independently (parallel_rows),
+// and the first unmatched edge is the smallest one over all threads: nothing depends on the thread count.
+
+int gnna_reverse_edges_i32(const int32_t *row_pointers, const int32_t *column_index, int64_t num_nodes, int32_t *rev)
+{
+    if (num_nodes < 0 || !row_pointers) return gnna::fail(GNNA_ERR_INVALID_ARGUMENT, "gnna_reverse_edges_i32: bad argument");
+    if (num_nodes >= 0x7fffffffLL) return gnna::fail(GNNA_ERR_UNSUPPORTED, "gnna_reverse_edges_i32: more than 2^31-2 nodes");
+    if (row_pointers[0] != 0) return gnna::fail(GNNA_ERR_INVALID_ARGUMENT, "row_pointers[0] = %d, expected 0", row_pointers[0]);
+    for (int64_t i = 0; i < num_nodes; i++)
+        if (row_pointers[i + 1] < row_pointers[i])
+            return gnna::fail(GNNA_ERR_INVALID_ARGUMENT, "row_pointers decrease at row %lld", (long long)i);
+    const int64_t nnz = row_pointers[num_nodes];
+    if (nnz == 0) return GNNA_OK;
+    if (!column_index || !rev) return gnna::fail(GNNA_ERR_INVALID_ARGUMENT, "gnna_reverse_edges_i32: null pointer");
+    std::atomic<int64_t> bad_id{nnz};
+    parallel_rows(nnz, [&](int64_t lo, int64_t hi) {
+        for (int64_t e = lo; e < hi; e++)
+            if (column_index[e] < 0 || column_index[e] >= num_nodes) {
+                int64_t cur = bad_id.load();
+                while (e < cur && !bad_id.compare_exchange_weak(cur, e)) {}
+                return;
+            }
+    });
+    if (bad_id.load() < nnz)
+        return gnna::fail(GNNA_ERR_INVALID_ARGUMENT, "column_index[%lld] = %d is not a node id (num_nodes = %lld)",
+                          (long long)bad_id.load(), column_index[bad_id.load()], (long long)num_nodes);
+    std::vector<int32_t> order((size_t)nnz);
+    parallel_rows(num_nodes, [&](int64_t lo, int64_t hi) {
+        for (int64_t i = lo; i < hi; i++) {
+            int32_t *o = order.data() + row_pointers[i];
+            const int32_t n = row_pointers[i + 1] - row_pointers[i];
+            for (int32_t k = 0; k < n; k++) o[k] = row_pointers[i] + k;
+            std::sort(o, o + n, [&](int32_t a, int32_t b) {
+                return column_index[a] != column_index[b] ? column_index[a] < column_index[b] : a < b;
+            });
+        }
+    });
+    // run of column `j` in row `i`: [first, last) of order[] (binary search over the sorted row)
+    auto run_of = [&](int64_t i, int32_t j, int64_t *first) -> int64_t {
+        const int32_t *b = order.data() + row_pointers[i], *e = order.data() + row_pointers[i + 1];
+        const int32_t *f = std::lower_bound(b, e, j, [&](int32_t pos, int32_t v) { return column_index[pos] < v; });
+        const int32_t *l = std::upper_bound(f, e, j, [&](int32_t v, int32_t pos) { return v < column_index[pos]; });
+        *first = f - order.data();
+        return l - f;
+    };
+    std::atomic<int64_t> unmatched{nnz};
+    parallel_rows(num_nodes, [&](int64_t lo, int64_t hi) {
+        int64_t mine = nnz;
+        for (int64_t i = lo; i < hi; i++) {
+            const int64_t end = row_pointers[i + 1];
+            for (int64_t a = row_pointers[i]; a < end;) {
+                const int32_t j = column_index[order[a]];
+                int64_t b = a + 1;
+                while (b < end && column_index[order[b]] == j) b++;
+                int64_t other = 0;
+                const int64_t m = run_of(j, (int32_t)i, &other);
+                for (int64_t t = 0; t < b - a; t++) {
+                    if (t < m) rev[order[a + t]] = order[other + t];
+                    else mine = std::min<int64_t>(mine, order[a + t]);   // (positions of a run increase: the first is at t = m)
+                }
+                a = b;
+            }
+        }
+        int64_t cur = unmatched.load();
+        while (mine < cur && !unmatched.compare_exchange_weak(cur, mine)) {}
+    });
+    const int64_t u = unmatched.load();
+    if (u < nnz) {
+        const int64_t row = std::upper_bound(row_pointers, row_pointers + num_nodes + 1, (int32_t)u) - row_pointers - 1;
+        return gnna::fail(GNNA_ERR_INVALID_ARGUMENT, "the graph's structure is not symmetric: edge %lld (%lld -> %d) has no "
+                          "matching reverse edge", (long long)u, (long long)row, column_index[u]);
+    }
+    return GNNA_OK;
+}
+
 // ---- graph inputs --------------------------------------------------------------------------
 
 

@@ -158,12 +158,13 @@ enum { CTR_PLAN_BUILDS = 0, CTR_LAUNCH_SYNCS = 1, CTR_LAUNCH_FREES = 2, CTR_LAUN
 void count_event(int which);
 
 struct StreamLaunch {
-    int mode;                 // MODE_SAG, MODE_GIN (also the pre-scaled GCN form: GIN + row_scale) or MODE_GCN (per-edge)
+    int mode;                 // MODE_SAG, MODE_GIN (also the pre-scaled GCN form: GIN + row_scale), MODE_GCN (per-edge) or MODE_EDGE
     const float *X; const int32_t *col; const int32_t *pp; const int32_t *p2n; float *Y;
     const uint8_t *cnt;       // slice counts or nullptr (single phase)
     const float *row_scale;
     const float *deg_row; const float *deg_col;   // MODE_GCN
     const float *A = nullptr;                      // MODE_SDDMM: destination-side features (Y = edge_out)
+    const float *edge_w = nullptr;                 // MODE_EDGE: per-edge weights, indexed like column_index
     const int32_t *flag; int32_t seq; int32_t trust;
     int64_t P;
     int D, ldx, G, U, S, B;

@@ -62,7 +62,7 @@ constexpr int kIdSlots = 512;    // at most this many column ids parked in LDS p
 // like every other width -- Reddit-like D = 16: 0.900 -> 0.860 ms, D = 8: 0.857 -> 0.810 ms.  Not for the modes that
 // park a second per-slot array in LDS: 3 x 16 KiB per block would cost occupancy)
 template <int LPR, int MODE>
-constexpr int id_slots() { return (LPR == 4 && MODE != MODE_GCN && MODE != MODE_SDDMM) ? GNNA_NARROW_SLOTS : kIdSlots; }
+constexpr int id_slots() { return (LPR == 4 && MODE != MODE_GCN && MODE != MODE_EDGE && MODE != MODE_SDDMM) ? GNNA_NARROW_SLOTS : kIdSlots; }
 
 struct StreamParams {
     const float *X;
@@ -74,6 +74,7 @@ struct StreamParams {
     const float *row_scale;    // MODE_GIN: optional per-destination-row factor on top of eps
     const float *deg_row;      // MODE_GCN (per-edge coefficients): degree norm per destination row ...
     const float *deg_col;      // ... and per source row
+    const float *edge_w;       // MODE_EDGE: the caller's per-edge weights, indexed like column_index
     const float *A;            // MODE_SDDMM: destination-side features [num_out_rows, D]; Y is then edge_out [nnz]
     const int32_t *flag;       // *flag == seq  <=>  partition is NOT canonical
     int64_t P;
@@ -278,8 +279,9 @@ stream_kernel(const StreamParams p)
     static_assert(RL % U == 0, "a round is a whole number of batches");
     // per wavefront: the round's list slots as row offsets into X (bytes; row index when X > 4 GiB)
     __shared__ uint32_t s_off[kSWaves][RL * RPI];
-    // MODE_GCN: the per-edge coefficient round(deg_i * deg_j) of every list slot (reference .cu:355,389)
-    __shared__ float s_cf[kSWaves][MODE == MODE_GCN ? RL * RPI : 1];
+    // MODE_GCN: the per-edge coefficient round(deg_i * deg_j) of every list slot (reference .cu:355,389); MODE_EDGE: w[e]
+    constexpr bool PER_EDGE = MODE == MODE_GCN || MODE == MODE_EDGE;
+    __shared__ __attribute__((aligned(16))) float s_cf[kSWaves][PER_EDGE ? RL * RPI : 1];
     // folded rows waiting to be written: the float atomics of the sliced schedule are memory-side round
     // trips that sit in the same in-order vmcnt queue as the row loads, so a flush in the middle of the
     // stream would stall the ring until it retires.  Rows are parked here (2 KiB per wavefront) and
@@ -359,7 +361,9 @@ stream_kernel(const StreamParams p)
     const int up_end = __shfl_up(pa + end, 1), up_n = __shfl_up(n_own, 1);
     // (MODE_SDDMM writes edge_out at the edges' ORIGINAL positions: its pieces merge only where those are adjacent too -- which,
     // with sorted ids, is wherever the aggregation's merge)
-    const bool cont = n_own > 0 && !seg_start && up_n > 0 && ((packed && MODE != MODE_SDDMM) || up_end == pa + beg);
+    // (MODE_EDGE reads w at the original positions as well)
+    constexpr bool ORIG_POS = MODE == MODE_SDDMM || MODE == MODE_EDGE;
+    const bool cont = n_own > 0 && !seg_start && up_n > 0 && ((packed && !ORIG_POS) || up_end == pa + beg);
     const unsigned long long NE = __ballot(n_own > 0 && !cont);        // piece heads
     const int n_cum = wave_inclusive_scan(n_own);
     const int own_beg = packed ? (int)item_base + (n_cum - n_own) : pa + beg;    // first edge of this group's part
@@ -385,7 +389,10 @@ stream_kernel(const StreamParams p)
     const int dst = (n > 0 ? rank : 63) << 2;       // empty pieces all land on lane 63 (unused unless R == 64, then none is empty)
     const int c_pbeg = __builtin_amdgcn_ds_permute(dst, own_beg);
     // MODE_SDDMM with packed ids: where the piece's edges sit in column_index / edge_out (own_beg is its place in the copy)
-    const int c_obeg = MODE == MODE_SDDMM ? __builtin_amdgcn_ds_permute(dst, pa + beg) : 0;
+    const int c_obeg = ORIG_POS ? __builtin_amdgcn_ds_permute(dst, pa + beg) : 0;
+    // (MODE_EDGE keeps the pieces' original positions in LDS: one VGPR less for the whole stream, the per-edge GCN form's count)
+    __shared__ int s_obeg[kSWaves][MODE == MODE_EDGE ? kWave : 1];
+    if constexpr (MODE == MODE_EDGE) s_obeg[wib][lane] = c_obeg;
     const int t_n = __builtin_amdgcn_ds_permute(dst, n);   // (executed by every lane: the senders are not the receivers)
     const int c_n = lane < R ? t_n : 0;
     const int c_meta = __builtin_amdgcn_ds_permute(dst, (my_row << 2) | (last_in_seg ? 2 : 0) | use_atomic_l);
@@ -445,8 +452,9 @@ stream_kernel(const StreamParams p)
             const bool active = J < L && lane < RL;
             const int i = J - k_offX;
             const int e_j = k_pbeg + i * RPI;
-            int o_j = e_j;                                   // MODE_SDDMM: position of the load's first edge in edge_out
+            int o_j = e_j;                                   // MODE_SDDMM / MODE_EDGE: original position of the load's first edge
             if constexpr (MODE == MODE_SDDMM) o_j = __shfl(c_obeg, k) + i * RPI;
+            if constexpr (MODE == MODE_EDGE) o_j = s_obeg[wib][k & (kWave - 1)] + i * RPI;   // (k = R for the unused loads)
             int v_j = active ? k_n - i * RPI : 0;
             const bool fl_j = active && (k_meta & 2) && v_j <= RPI;   // last load of the last piece of its row
             v_j = v_j > RPI ? RPI : v_j;
@@ -460,6 +468,23 @@ stream_kernel(const StreamParams p)
             // non-temporal load costs several times a normal one on this chip -- nt id loads were 3-6 % of the kernel --
             // and the id lines other phases come back for now stay in the L2.)
             if (lane < RL) {
+                if constexpr (MODE == MODE_EDGE) {
+                    // the weights of a load are contiguous (original positions o_j ..): straight into LDS, one vector
+                    // load per 4 slots when the load is full, like the ids; a padded slot gets 0
+                    bool done = false;
+                    if constexpr (RPI >= 4) {
+                        if (v_j == RPI) {
+#pragma unroll
+                            for (int s4 = 0; s4 < RPI; s4 += 4)
+                                *reinterpret_cast<VT *>(cfs + lane * RPI + s4) = *reinterpret_cast<const MT *>(p.edge_w + o_j + s4);
+                            done = true;
+                        }
+                    }
+                    if (!done) {
+#pragma unroll
+                        for (int s = 0; s < RPI; s++) cfs[lane * RPI + s] = s < v_j ? p.edge_w[o_j + s] : 0.f;
+                    }
+                }
                 uint32_t o[RPI];
                 // (plain loads up to 128-float rows; rows of 129-256 floats -- one id per wave-wide load, 1 KiB of L2
                 // per row -- do better when the ids leave the L2 first: D = 256: 7.13 ms with nt ids, 7.44 plain)
@@ -606,7 +631,7 @@ stream_kernel(const StreamParams p)
                     const int vj = __builtin_amdgcn_readlane(v_j, j);
                     if (slot >= vj) v[u] = vzero<4>();
                 }
-                if constexpr (MODE == MODE_GCN) {
+                if constexpr (PER_EDGE) {
                     // the reference rounds coef * x and the accumulation separately (__fmaf_rn(c, x, 0) then +=,
                     // .cu:405); this file is built with -ffp-contract=off
                     const VT tmp = v[u] * cfs[j * RPI + slot];
@@ -1304,7 +1329,7 @@ int launch_stream(const StreamLaunch &a, hipStream_t stream)
 {
     StreamParams p;
     p.X = a.X; p.col = a.col; p.pp = a.pp; p.p2n = a.p2n; p.Y = a.Y; p.cnt = a.cnt; p.row_scale = a.row_scale;
-    p.deg_row = a.deg_row; p.deg_col = a.deg_col; p.A = a.A;
+    p.deg_row = a.deg_row; p.deg_col = a.deg_col; p.edge_w = a.edge_w; p.A = a.A;
     p.flag = a.flag; p.P = a.P; p.seq = a.seq; p.trust = a.trust; p.D = a.D; p.ldx = a.ldx;
     p.DL = std::max(a.D, 4); p.ldy = a.ldy > 0 ? a.ldy : a.D; p.lda = a.lda > 0 ? a.lda : a.D;
     p.G = std::max(1, std::min(a.G, kWave));
@@ -1329,7 +1354,8 @@ int launch_stream(const StreamLaunch &a, hipStream_t stream)
     while (lpr < 64 && lpr < pieces) lpr <<= 1;
     StreamKernel k = a.mode == MODE_GIN ? pick_stream_lpr<MODE_GIN>(lpr, a.wide, a.U)
                      : (a.mode == MODE_GCN ? pick_stream_lpr<MODE_GCN>(lpr, a.wide, a.U)
-                     : (a.mode == MODE_SDDMM ? pick_stream_lpr<MODE_SDDMM>(lpr, a.wide, a.U) : pick_stream_lpr<MODE_SAG>(lpr, a.wide, a.U)));
+                     : (a.mode == MODE_EDGE ? pick_stream_lpr<MODE_EDGE>(lpr, a.wide, a.U)
+                     : (a.mode == MODE_SDDMM ? pick_stream_lpr<MODE_SDDMM>(lpr, a.wide, a.U) : pick_stream_lpr<MODE_SAG>(lpr, a.wide, a.U))));
     p.det = 0; p.det_part = nullptr; p.det_stamp = nullptr; p.stamp = 0;
     p.ids_packed = !a.packed_stale ? nullptr : a.ids_packed; p.item_off = a.item_off;
     p.packed_stale = a.packed_stale;

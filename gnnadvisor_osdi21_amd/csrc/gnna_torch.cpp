@@ -284,6 +284,109 @@ torch::Tensor aggregate_general(int mode, const torch::Tensor &input, const torc
     return out;
 }
 
+// Edge-weighted aggregation (gnna_agg_edge_ld_f32): out[i] (+)= sum_e w[e] X[column_index[e]], strided X / out as aggregate_ld.
+torch::Tensor aggregate_edge(const torch::Tensor &input, const torch::Tensor &column_index, const torch::Tensor &edge_weight,
+                             const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize,
+                             c10::optional<torch::Tensor> out_opt, bool accumulate, bool relu)
+{
+    CHECK_CUDA(input);
+    TORCH_CHECK(input.dim() == 2, "input must be 2-D [num_nodes, dim]");
+    CHECK_F32(input);
+    CHECK_INPUT(column_index); CHECK_I32(column_index);
+    CHECK_INPUT(edge_weight); CHECK_F32(edge_weight);
+    CHECK_INPUT(part_pointers); CHECK_I32(part_pointers);
+    CHECK_INPUT(part2Node); CHECK_I32(part2Node);
+    TORCH_CHECK(edge_weight.dim() == 1 && edge_weight.size(0) == column_index.numel(),
+                "edge_weight must be [nnz], indexed like column_index");
+    TORCH_CHECK(edge_weight.device() == input.device() && column_index.device() == input.device(),
+                "input, column_index and edge_weight must be on one device");
+    TORCH_CHECK(input.size(1) <= 1 || input.stride(1) == 1, "input: the floats of a row must be contiguous (stride(1) == 1)");
+    const int64_t n = input.size(0);
+    const int64_t dim = input.size(1);
+    auto ld_of = [&](const torch::Tensor &t) { return t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(t.size(1), t.stride(0)); };
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(input.device());
+    static const bool poison = std::getenv("GNNA_DEBUG_POISON") && std::atoi(std::getenv("GNNA_DEBUG_POISON")) != 0;
+    torch::Tensor out;
+    if (out_opt.has_value()) {
+        out = *out_opt;
+        CHECK_CUDA(out); CHECK_F32(out);
+        TORCH_CHECK(out.dim() == 2 && out.size(0) == n && out.size(1) == dim, "out must be [num_nodes, dim] like input");
+        TORCH_CHECK(dim <= 1 || out.stride(1) == 1, "out: the floats of a row must be contiguous (stride(1) == 1)");
+    } else {
+        TORCH_CHECK(!accumulate, "accumulate needs an existing `out`");
+        out = poison ? torch::full({n, dim}, std::numeric_limits<float>::quiet_NaN(), input.options()) : torch::empty({n, dim}, input.options());
+    }
+    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+    const unsigned flags = (accumulate ? GNNA_ACCUMULATE : 0u) | (relu ? GNNA_EPILOGUE_RELU : 0u);
+    int rc = gnna_agg_edge_ld_f32(input.data_ptr<float>(), ld_of(input), n, column_index.data_ptr<int32_t>(),
+                                  edge_weight.data_ptr<float>(), part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(),
+                                  out.data_ptr<float>(), ld_of(out), n, (int)dim, part2Node.size(0), partSize, flags, stream);
+    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+    return out;
+}
+
+// Edge softmax and its backward: scores [nnz] or head-major [heads, nnz] over the rows of row_pointers.
+torch::Tensor edge_softmax(const torch::Tensor &scores, const torch::Tensor &row_pointers)
+{
+    CHECK_INPUT(scores); CHECK_F32(scores);
+    CHECK_INPUT(row_pointers); CHECK_I32(row_pointers);
+    TORCH_CHECK(scores.dim() == 1 || scores.dim() == 2, "scores must be [nnz] or [heads, nnz]");
+    TORCH_CHECK(row_pointers.dim() == 1 && row_pointers.size(0) >= 1, "row_pointers must be [num_rows + 1]");
+    TORCH_CHECK(row_pointers.device() == scores.device(), "scores and row_pointers must be on one device");
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(scores.device());
+    auto probs = torch::empty_like(scores);
+    const int heads = scores.dim() == 2 ? (int)scores.size(0) : 1;
+    const int64_t nnz = scores.size(scores.dim() - 1);
+    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+    int rc = gnna_edge_softmax_f32(scores.data_ptr<float>(), row_pointers.data_ptr<int32_t>(), row_pointers.size(0) - 1, nnz, heads,
+                                   probs.data_ptr<float>(), stream);
+    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+    return probs;
+}
+
+torch::Tensor edge_softmax_backward(const torch::Tensor &probs, const torch::Tensor &grad, const torch::Tensor &row_pointers)
+{
+    CHECK_INPUT(probs); CHECK_F32(probs);
+    CHECK_INPUT(grad); CHECK_F32(grad);
+    CHECK_INPUT(row_pointers); CHECK_I32(row_pointers);
+    TORCH_CHECK(probs.dim() == 1 || probs.dim() == 2, "probs must be [nnz] or [heads, nnz]");
+    TORCH_CHECK(grad.sizes() == probs.sizes(), "grad must have the shape of probs");
+    TORCH_CHECK(row_pointers.dim() == 1 && row_pointers.size(0) >= 1, "row_pointers must be [num_rows + 1]");
+    TORCH_CHECK(grad.device() == probs.device() && row_pointers.device() == probs.device(), "probs, grad and row_pointers must be on one device");
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(probs.device());
+    auto gs = torch::empty_like(probs);
+    const int heads = probs.dim() == 2 ? (int)probs.size(0) : 1;
+    const int64_t nnz = probs.size(probs.dim() - 1);
+    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+    int rc = gnna_edge_softmax_backward_f32(probs.data_ptr<float>(), grad.data_ptr<float>(), row_pointers.data_ptr<int32_t>(),
+                                            row_pointers.size(0) - 1, nnz, heads, gs.data_ptr<float>(), stream);
+    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+    return gs;
+}
+
+// SDDMM (gnna_sddmm_ld_f32): edge_out[e] = <A[row(e)], B[column_index[e]]>; A and B may be row-strided views.
+torch::Tensor sddmm(const torch::Tensor &A, const torch::Tensor &B, const torch::Tensor &column_index,
+                    const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize)
+{
+    CHECK_CUDA(A); CHECK_CUDA(B); CHECK_F32(A); CHECK_F32(B);
+    CHECK_INPUT(column_index); CHECK_I32(column_index);
+    CHECK_INPUT(part_pointers); CHECK_I32(part_pointers);
+    CHECK_INPUT(part2Node); CHECK_I32(part2Node);
+    TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.size(1) == B.size(1), "A [rows, dim] and B [num_nodes, dim] expected");
+    TORCH_CHECK(A.device() == B.device() && column_index.device() == A.device(), "A, B and column_index must be on one device");
+    TORCH_CHECK(A.size(1) <= 1 || (A.stride(1) == 1 && B.stride(1) == 1), "the floats of a row must be contiguous (stride(1) == 1)");
+    auto ld_of = [&](const torch::Tensor &t) { return t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(t.size(1), t.stride(0)); };
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(A.device());
+    // (edges of rows without a neighbor-group -- none in a partition of the full CSR -- stay zero)
+    auto out = torch::zeros({column_index.numel()}, A.options());
+    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+    int rc = gnna_sddmm_ld_f32(A.data_ptr<float>(), ld_of(A), B.data_ptr<float>(), ld_of(B), column_index.data_ptr<int32_t>(),
+                               part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), out.data_ptr<float>(),
+                               A.size(0), B.size(0), (int)A.size(1), part2Node.size(0), partSize, stream);
+    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+    return out;
+}
+
 }  // namespace
 
 // ---- host launchers: reference names (GNNAdvisor_kernel.cu:110,267,422,559,696) -------------
@@ -534,6 +637,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           pybind11::arg("mode"), pybind11::arg("input"), pybind11::arg("column_index"), pybind11::arg("degrees"),
           pybind11::arg("epsilon"), pybind11::arg("part_pointers"), pybind11::arg("part2Node"), pybind11::arg("partSize"),
           pybind11::arg("out") = pybind11::none(), pybind11::arg("accumulate") = false, pybind11::arg("relu") = false);
+    m.def("aggregate_edge", &aggregate_edge,
+          "edge-weighted aggregation (extension): out[i] (+)= sum_e edge_weight[e] * X[column_index[e]], edge_weight indexed like "
+          "column_index; X and out may be row-strided views",
+          pybind11::arg("X"), pybind11::arg("column_index"), pybind11::arg("edge_weight"), pybind11::arg("partPtr"),
+          pybind11::arg("part2Node"), pybind11::arg("partSize"), pybind11::arg("out") = pybind11::none(),
+          pybind11::arg("accumulate") = false, pybind11::arg("relu") = false);
+    m.def("edge_softmax", &edge_softmax, "softmax over every row's edges; scores [nnz] or [heads, nnz] (extension)",
+          pybind11::arg("scores"), pybind11::arg("row_pointers"));
+    m.def("edge_softmax_backward", &edge_softmax_backward, "gradient of edge_softmax: probs * (grad - sum_row probs * grad) (extension)",
+          pybind11::arg("probs"), pybind11::arg("grad"), pybind11::arg("row_pointers"));
+    m.def("sddmm", &sddmm, "edge_out[e] = <A[row(e)], B[column_index[e]]> over the neighbor-group partition (extension)",
+          pybind11::arg("A"), pybind11::arg("B"), pybind11::arg("column_index"), pybind11::arg("partPtr"), pybind11::arg("part2Node"),
+          pybind11::arg("partSize"));
     m.def("build_part", &build_part, "GNNAdvisor neighbor-group partitioner (CPU)", pybind11::arg("partSize"),
           pybind11::arg("indptr"), pybind11::arg("float_compat") = false);
 #ifndef GNNA_SOURCE_HASH

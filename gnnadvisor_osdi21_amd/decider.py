@@ -171,12 +171,16 @@ REORDER_S_PER_NODE = 3.9e-7
 REFERENCE_EPOCHS = 200 + 10          # GNNA_main.py:25 (--num_epoches) + the 10 dry runs (:188-189)
 
 
-def expected_aggregations(model, in_dim, hidden, classes, epochs=REFERENCE_EPOCHS):
+def expected_aggregations(model, in_dim, hidden, classes, epochs=REFERENCE_EPOCHS, heads=1):
     """[(feature width, aggregations at that width)] of a whole training run of the reference's models (GNNA_main.py:143-171):
     GCN aggregates X W, i.e. at each layer's OUTPUT width, forward and backward; GIN aggregates at each layer's input width
-    (forward; backward too unless it is the first layer) or, evaluated update-first (ops.GINConv), at the output width."""
+    (forward; backward too unless it is the first layer) or, evaluated update-first (ops.GINConv), at the output width.
+    GAT (main.py --model gat) aggregates every head of H = X W at the head's width, forward and backward (the weighted
+    gather of dY): `heads` per step on the hidden layer, one on the output layer."""
     units = lambda w: (int(w) + 63) // 64
     out = []
+    if model == "gat":
+        return [(hidden, 2 * heads * epochs), (classes, 2 * epochs)]
     if model == "gin":
         dims = [in_dim] + [hidden] * 4 + [classes]
         for i, (a, b) in enumerate(zip(dims[:-1], dims[1:])):
@@ -445,6 +449,34 @@ class inputProperty(object):
     def set_hidden(self):
         """... and every other layer the hidden-layer knobs (param.py:133-141)."""
         return self._activate("hidden")
+
+    # ------------------------------------------------------------------ per-edge arrays (edge-valued aggregation, GAT)
+    def _edge_arrays(self):
+        """The cache of reverse_edges / edge_rows, emptied when `column_index` is another object than the one it was built
+        from (a renumbered CSR)."""
+        cache = getattr(self, "_edge_cache", None)
+        if cache is None or cache["column_index"] is not self.column_index:
+            cache = self._edge_cache = {"column_index": self.column_index}
+        return cache
+
+    def reverse_edges(self):
+        """int32 [nnz] on the graph's device: rev[e] = position of the edge col(e) -> row(e) matching e (libgnna,
+        gnna_reverse_edges_i32; built once per column_index).  Raises when the graph's structure is not symmetric."""
+        cache = self._edge_arrays()
+        if "rev" not in cache:
+            from . import _lib
+            cache["rev"] = _lib.reverse_edges(self.row_pointers, self.column_index).to(self.column_index.device)
+        return cache["rev"]
+
+    def edge_rows(self):
+        """int32 [nnz] on the graph's device: the destination row of every edge (built once per column_index)."""
+        cache = self._edge_arrays()
+        if "rows" not in cache:
+            import torch
+            rp = self.row_pointers.to(self.column_index.device).long()
+            n = rp.numel() - 1
+            cache["rows"] = torch.repeat_interleave(torch.arange(n, dtype=torch.int32, device=rp.device), rp[1:] - rp[:-1])
+        return cache["rows"]
 
     def apply_tuning(self):
         """Push the scheduler knobs and graph hints chosen by the mi355x policy into libgnna.

@@ -205,3 +205,114 @@ class GINConv(_NeighborConv):
             return GNNAFunction_GIN_UpdateFirst.apply(X, self.weights, inputInfo, self.eplison, relu)
         Y = GNNAFunction_GIN.apply(X, self.weights, inputInfo, self.eplison)
         return torch.relu(Y) if relu else Y
+
+
+# ---- edge-valued aggregation, edge softmax, GAT ----------------------------------------------------------------------
+
+def _heads_of(w):
+    """[heads, nnz] view of per-edge values given as [nnz] or [heads, nnz]."""
+    return w.view(1, -1) if w.dim() == 1 else w
+
+
+def _sddmm_at_least_4(A, B, ci, pp, p2n, partSize):
+    """<A[row(e)], B[col(e)]> for every edge; the kernel takes rows of >= 4 floats, narrower ones are zero-padded."""
+    if A.shape[1] < 4:
+        A = torch.nn.functional.pad(A, (0, 4 - A.shape[1]))
+        B = torch.nn.functional.pad(B, (0, 4 - B.shape[1]))
+    return GNNA.sddmm(A, B, ci, pp, p2n, partSize)
+
+
+class EdgeWeightedAggregate(Function):
+    """Y = A_w X with caller-supplied edge values: Y[i] = sum_e w[e] X[column_index[e]] (libgnna gnna_agg_edge_ld_f32).
+    Multi-head: X is [N, heads * F] and w is [heads, nnz]; head h aggregates the column block X[:, h F : (h + 1) F] with w[h]
+    into the same block of Y (the strided forms: no copies).  Backward on a graph whose structure is symmetric:
+    dX = A_{w[rev]} dY (the same partition, weights read through the reverse-edge map) and dw = sddmm(dY, X)."""
+
+    @staticmethod
+    def forward(ctx, X, w, inputInfo):
+        wh = _heads_of(w)
+        heads = wh.shape[0]
+        assert X.dim() == 2 and X.shape[1] % heads == 0, "X must be [num_nodes, heads * F]"
+        assert wh.shape[1] == inputInfo.column_index.numel(), "w must be indexed like column_index"
+        ctx.info, ctx.w_shape = inputInfo, w.shape
+        wh = wh.contiguous()
+        ctx.save_for_backward(X, wh)
+        return _edge_aggregate(X, wh, inputInfo)
+
+    @staticmethod
+    def backward(ctx, dY):
+        X, wh = ctx.saved_tensors
+        info = ctx.info
+        dY = dY.contiguous()
+        heads, F = wh.shape[0], X.shape[1] // wh.shape[0]
+        dX = dw = None
+        if ctx.needs_input_grad[0]:
+            dX = _edge_aggregate(dY, wh.index_select(1, info.reverse_edges()).contiguous(), info)
+        if ctx.needs_input_grad[1]:
+            dw = torch.stack([_sddmm_at_least_4(dY[:, h * F:(h + 1) * F], X[:, h * F:(h + 1) * F], info.column_index,
+                                                info.partPtr, info.part2Node, info.partSize) for h in range(heads)])
+            dw = dw.view(ctx.w_shape)
+        return dX, dw, None
+
+
+def _edge_aggregate(X, wh, info):
+    heads = wh.shape[0]
+    F = X.shape[1] // heads
+    if heads == 1:
+        return GNNA.aggregate_edge(X, info.column_index, wh[0], info.partPtr, info.part2Node, info.partSize)
+    Y = torch.empty(X.shape[0], X.shape[1], dtype=X.dtype, device=X.device)
+    for h in range(heads):
+        GNNA.aggregate_edge(X[:, h * F:(h + 1) * F], info.column_index, wh[h], info.partPtr, info.part2Node, info.partSize,
+                            out=Y[:, h * F:(h + 1) * F])
+    return Y
+
+
+class EdgeSoftmax(Function):
+    """Softmax of per-edge scores ([nnz] or head-major [heads, nnz]) over the edges of every destination row."""
+
+    @staticmethod
+    def forward(ctx, scores, row_pointers):
+        p = GNNA.edge_softmax(scores.contiguous(), row_pointers)
+        ctx.save_for_backward(p, row_pointers)
+        return p
+
+    @staticmethod
+    def backward(ctx, dp):
+        p, rp = ctx.saved_tensors
+        return GNNA.edge_softmax_backward(p, dp.contiguous(), rp), None
+
+
+class GATConv(Module):
+    """Additive graph attention (GAT): H = X W; per head h, s[e] = leaky_relu(<H_h[row(e)], a_l[h]> + <H_h[col(e)], a_r[h]>),
+    alpha = edge softmax of s over every row, Y_h = A_alpha H_h.  Heads are concatenated (concat=True, [N, heads * out]) or
+    averaged ([N, out]).  The scores are nnz-sized elementwise torch work; softmax and aggregation are libgnna kernels.
+    Needs the graph's structure to be symmetric (the backward gathers through the reverse-edge map)."""
+
+    def __init__(self, input_dim, output_dim, heads=1, concat=True, negative_slope=0.2):
+        super().__init__()
+        self.heads, self.out_dim, self.concat, self.negative_slope = int(heads), int(output_dim), bool(concat), float(negative_slope)
+        self.weights = Parameter(torch.empty(input_dim, self.heads * self.out_dim))
+        self.att_l = Parameter(torch.empty(self.heads, self.out_dim))
+        self.att_r = Parameter(torch.empty(self.heads, self.out_dim))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        bound = 1.0 / math.sqrt(self.out_dim)
+        with torch.no_grad():
+            self.weights.uniform_(-bound, bound)
+            self.att_l.uniform_(-bound, bound)
+            self.att_r.uniform_(-bound, bound)
+
+    def forward(self, X, inputInfo):
+        n = X.shape[0]
+        H = torch.mm(X, self.weights)
+        Hh = H.view(n, self.heads, self.out_dim)
+        el = (Hh * self.att_l).sum(-1)          # [N, heads]: destination side
+        er = (Hh * self.att_r).sum(-1)          # source side
+        rows, ci = inputInfo.edge_rows(), inputInfo.column_index
+        s = torch.nn.functional.leaky_relu(el.index_select(0, rows) + er.index_select(0, ci), self.negative_slope)
+        alpha = EdgeSoftmax.apply(s.t().contiguous(), inputInfo.row_pointers)      # [heads, nnz]
+        Y = EdgeWeightedAggregate.apply(H, alpha, inputInfo)
+        if self.concat or self.heads == 1:
+            return Y
+        return Y.view(n, self.heads, self.out_dim).mean(1)

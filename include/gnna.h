@@ -64,7 +64,7 @@
 extern "C" {
 #endif
 
-#define GNNA_VERSION 601 /* 0.6.1: per-capture library scratch, full hashes of a packed copy ordered across streams, gnna_debug_untrusted_copies, counter [9]; 0.6.0: gnna_tuning.ids_check_every (full hash of the ids behind a packed copy), gnna_device_cus, gnna_host_threads; 0.5.0: gnna_tuning opens with struct_size (checked by gnna_set_tuning, which now returns a status), gnna_build_id; 0.4.1: gnna_sddmm_ld_f32 (leading dimensions for both SDDMM sides); 0.4.0: gnna_agg_ld_f32 (leading dimensions, ReLU epilogue), gnna_forget_graph, chunk-walk kernel retired; 0.3.1: gnna_tuning grew (pack_ids); 0.3.0: sweep, sweep_slack, graph lifecycle, 64-bit CSR builder */
+#define GNNA_VERSION 601 /* 0.6.1: gnna_agg_edge_ld_f32 (caller-supplied edge weights), gnna_edge_softmax_f32, gnna_edge_softmax_backward_f32, gnna_reverse_edges_i32; per-capture library scratch, full hashes of a packed copy ordered across streams, gnna_debug_untrusted_copies, counter [9]; 0.6.0: gnna_tuning.ids_check_every (full hash of the ids behind a packed copy), gnna_device_cus, gnna_host_threads; 0.5.0: gnna_tuning opens with struct_size (checked by gnna_set_tuning, which now returns a status), gnna_build_id; 0.4.1: gnna_sddmm_ld_f32 (leading dimensions for both SDDMM sides); 0.4.0: gnna_agg_ld_f32 (leading dimensions, ReLU epilogue), gnna_forget_graph, chunk-walk kernel retired; 0.3.1: gnna_tuning grew (pack_ids); 0.3.0: sweep, sweep_slack, graph lifecycle, 64-bit CSR builder */
 #define GNNA_API __attribute__((visibility("default")))
 
 typedef enum gnna_status {
@@ -231,6 +231,35 @@ GNNA_API int gnna_agg_ld_f32(int mode, const float *input, int64_t ld_in, int64_
                       float epsilon, const int32_t *part_pointers, const int32_t *part2Node,
                       float *out, int64_t ld_out, int64_t num_out_rows, int dim, int64_t num_parts, int partSize,
                       unsigned flags, void *stream);
+
+/* Edge-weighted aggregation: out[i, :] (+)= sum over the neighbor-groups p of row i of sum_{e in p} w[e] * input[column_index[e], :],
+ * with `edge_weight` [nnz] indexed like column_index (attention coefficients, learned edge weights, a normalised adjacency).
+ * Arguments, limits, flags (GNNA_ACCUMULATE | GNNA_EPILOGUE_RELU), leading dimensions and the prepared-graph contract are those
+ * of gnna_agg_ld_f32: on a graph prepared for `dim` the call neither synchronises nor allocates.  A column-blocked call applies
+ * the same weights to every block.  Runs on the streaming kernel (never the sweep kernel), per-edge like MODE_GCN.
+ * Backward on a graph whose structure is symmetric: dX = the same call on dY with the weights w[rev] (gnna_reverse_edges_i32),
+ * dw = gnna_sddmm_ld_f32(dY, X). */
+GNNA_API int gnna_agg_edge_ld_f32(const float *input, int64_t ld_in, int64_t num_in_rows,
+        const int32_t *column_index, const float *edge_weight /* [nnz], indexed like column_index */,
+        const int32_t *part_pointers, const int32_t *part2Node, float *out, int64_t ld_out,
+        int64_t num_out_rows, int dim, int64_t num_parts, int partSize, unsigned flags, void *stream);
+
+/* Edge softmax over the edges of every destination row, per head; scores are head-major [num_heads, num_edges]:
+ *   probs[h, e] = exp(s[h, e] - max_row) / sum_row exp(s - max_row),  e in [row_pointers[i], row_pointers[i + 1]).
+ * Backward: grad_scores[h, e] = probs[h, e] * (grad_probs[h, e] - sum_row probs * grad_probs).
+ * Empty rows write nothing.  No atomics: the same inputs give the same bits whatever the launch order.  Device pointers. */
+GNNA_API int gnna_edge_softmax_f32(const float *scores, const int32_t *row_pointers, int64_t num_rows,
+        int64_t num_edges, int num_heads, float *probs, void *stream);
+GNNA_API int gnna_edge_softmax_backward_f32(const float *probs, const float *grad_probs,
+        const int32_t *row_pointers, int64_t num_rows, int64_t num_edges, int num_heads,
+        float *grad_scores, void *stream);
+
+/* Reverse-edge map of a CSR whose structure is symmetric (host pointers): rev[e] is the position of the edge col(e) -> row(e)
+ * that matches e; the k-th (i, j) of row i pairs with the k-th (j, i) of row j (positions in increasing order), a self loop
+ * may pair with itself, rows need not be sorted.  gnna_host_threads() threads; the result does not depend on their number.
+ * GNNA_ERR_INVALID_ARGUMENT, naming the first unmatched edge, when the structure is not symmetric. */
+GNNA_API int gnna_reverse_edges_i32(const int32_t *row_pointers, const int32_t *column_index,
+        int64_t num_nodes, int32_t *rev);
 
 /* The row stride (in floats, >= dim) the library would stage `dim`-float source rows into before gathering them
  * `num_edges` times from `num_in_rows` rows -- dim itself when it would gather from the contiguous layout.  A producer
