@@ -49,7 +49,7 @@ EXPORTS = ("gnna_version", "gnna_build_id", "gnna_last_error", "gnna_count_parts
            "gnna_forget_graph", "gnna_agg_ld_f32", "gnna_preferred_ld", "gnna_device_cus", "gnna_host_threads",
            "gnna_reorder_community_csr_i32", "gnna_relabel_edges_i32", "gnna_relabel_csr_i32", "gnna_runtime_counters_ex", "gnna_forget_plans",
            "gnna_debug_untrusted_copies", "gnna_agg_edge_ld_f32", "gnna_edge_softmax_f32", "gnna_edge_softmax_backward_f32",
-           "gnna_reverse_edges_i32")
+           "gnna_reverse_edges_i32", "gnna_agg_ld_x16", "gnna_prepare_x16")
 
 
 def load() -> ctypes.CDLL:
@@ -87,6 +87,13 @@ def load() -> ctypes.CDLL:
                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
                                     ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    L.gnna_agg_ld_x16.restype = ctypes.c_int
+    L.gnna_agg_ld_x16.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                                  ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                  ctypes.c_int, ctypes.c_uint, ctypes.c_void_p]
+    L.gnna_prepare_x16.restype = ctypes.c_int
+    L.gnna_prepare_x16.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
     L.gnna_agg_ld_f32.restype = ctypes.c_int
     L.gnna_agg_ld_f32.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
@@ -527,6 +534,66 @@ def agg_ld(mode, X, column_index, part_pointers, part2Node, num_out_rows, partSi
                                       yp, ld_out, int(num_out_rows), dim, part2Node.numel(), int(partSize), flags,
                                       _stream(X.device)))
     return out
+
+
+F32, BF16, F16 = 0, 1, 2        # GNNA_F32 / GNNA_BF16 / GNNA_F16
+_X16_TYPES = {torch.bfloat16: BF16, torch.float16: F16}
+
+
+def _rows_view_any(t: torch.Tensor, what: str):
+    """_rows_view for any element type: the leading dimension is counted in elements."""
+    assert t.dim() == 2, f"{what} must be a 2-D tensor"
+    if t.shape[1] > 1 and t.stride(1) != 1:
+        raise GnnaError(f"{what}: the elements of a row must be contiguous (stride(1) == 1)")
+    ld = t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0))
+    if ld < t.shape[1]:
+        raise GnnaError(f"{what}: rows overlap (stride(0) = {t.stride(0)} < {t.shape[1]})")
+    return t.data_ptr(), t.shape[0], t.shape[1], ld
+
+
+def agg_ld_x16(mode, X, column_index, part_pointers, part2Node, num_out_rows, partSize=32, degrees_out=None,
+               degrees_in=None, epsilon=1.0, out=None, out_dtype=None, accumulate=False, relu=False):
+    """gnna_agg_ld_x16: agg_ld over bfloat16 / float16 `X`, accumulated in fp32.  The result is float32 or has X's dtype
+    (`out_dtype`, default X's; or the dtype of a given `out`), rounded once.  Degrees stay float32.  accumulate needs a
+    float32 `out`.  float16 results beyond +-65504 are +-inf (GCN coefficients get large: prefer bfloat16 / float32)."""
+    if not X.is_cuda:
+        raise GnnaError("aggregation needs device tensors: there is no CPU path in libgnna")
+    if X.dtype not in _X16_TYPES:
+        raise GnnaError(f"agg_ld_x16 takes bfloat16 or float16 features (got {X.dtype}); float32 goes through agg_ld")
+    xp, n_in, dim, ld_in = _rows_view_any(X, "X")
+    if out is None:
+        assert not accumulate, "accumulate needs an existing `out`"
+        out_dtype = X.dtype if out_dtype is None else out_dtype
+        if os.environ.get("GNNA_DEBUG_POISON", "0") not in ("", "0"):
+            out = torch.full((int(num_out_rows), dim), float("nan"), dtype=out_dtype, device=X.device)
+        else:
+            out = torch.empty((int(num_out_rows), dim), dtype=out_dtype, device=X.device)
+    elif out_dtype is not None and out.dtype != out_dtype:
+        raise GnnaError(f"out is {out.dtype}, out_dtype says {out_dtype}")
+    if out.dtype != torch.float32 and out.dtype != X.dtype:
+        raise GnnaError(f"the output is float32 or has the input's dtype {X.dtype} (got {out.dtype})")
+    out_type = F32 if out.dtype == torch.float32 else _X16_TYPES[out.dtype]
+    yp, n_out, dim_o, ld_out = _rows_view_any(out, "out")
+    assert n_out == int(num_out_rows) and dim_o == dim and out.device == X.device
+    for t in (degrees_out, degrees_in):
+        assert t is None or t.dtype == torch.float32, "degrees stay float32"
+    flags = (ACCUMULATE if accumulate else 0) | (EPILOGUE_RELU if relu else 0)
+    with torch.cuda.device(X.device):
+        _check(load().gnna_agg_ld_x16(int(mode), _X16_TYPES[X.dtype], xp, ld_in, n_in, column_index.data_ptr(),
+                                      _ptr(degrees_out), _ptr(degrees_in), float(epsilon), part_pointers.data_ptr(),
+                                      part2Node.data_ptr(), yp, out_type, ld_out, int(num_out_rows), dim,
+                                      part2Node.numel(), int(partSize), flags, _stream(X.device)))
+    return out
+
+
+def prepare_x16(num_in_rows: int, num_out_rows: int, dims, device=None) -> None:
+    """gnna_prepare_x16: sizes the current stream's scratch of the 16-bit path for these widths, so that later eager
+    agg_ld_x16 calls of those shapes on this stream neither allocate nor free."""
+    dims = [int(d) for d in dims]
+    arr = (ctypes.c_int * max(1, len(dims)))(*dims)
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    with torch.cuda.device(device):
+        _check(load().gnna_prepare_x16(int(num_in_rows), int(num_out_rows), arr, len(dims), _stream(device)))
 
 
 def preferred_ld(dim: int, num_in_rows: int, num_edges: int) -> int:

@@ -487,6 +487,19 @@ int choose_slices(const SlicePlanStats &st, size_t x_bytes, int S, uint32_t slic
     return std::max(b, 1);
 }
 
+int launch_zero_fill(DeviceState *ds, hipStream_t stream, float *out, int64_t rows, int dim, int64_t ld)
+{
+    const size_t n_floats = (size_t)rows * (size_t)dim;
+    if (n_floats == 0) return GNNA_OK;
+    int64_t blocks = (int64_t)((n_floats / 4 + kBlock - 1) / kBlock);
+    blocks = std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)ds->num_cus * 8));
+    hipLaunchKernelGGL(prologue_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, out, n_floats, dim, (int)ld, nullptr, nullptr,
+                       (int64_t)0, nullptr, 0, /*validate=*/0, /*zero_fill=*/1, nullptr, (int64_t)0, nullptr, nullptr, nullptr, 0);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "zero-fill launch: %s", hipGetErrorString(e));
+    return GNNA_OK;
+}
+
 namespace {
 
 // One aggregation call.  ld_in / ld_out: row strides of `input` / `out` in floats (>= dim).  flags: GNNA_ACCUMULATE,
@@ -933,6 +946,84 @@ int gnna_agg_edge_ld_f32(const float *input, int64_t ld_in, int64_t num_in_rows,
 {
     return launch_agg(MODE_EDGE, input, ld_in, num_in_rows, column_index, nullptr, edge_weight, 1.f, part_pointers,
                       part2Node, out, ld_out, num_out_rows, dim, num_parts, partSize, 32, 4, stream, flags);
+}
+
+int gnna_agg_ld_x16(int mode, int in_type, const void *input, int64_t ld_in, int64_t num_in_rows,
+                    const int32_t *column_index, const float *degrees_out, const float *degrees_in, float epsilon,
+                    const int32_t *part_pointers, const int32_t *part2Node, void *out, int out_type, int64_t ld_out,
+                    int64_t num_out_rows, int dim, int64_t num_parts, int partSize, unsigned flags, void *stream_v)
+{
+    if (mode != MODE_SAG && mode != MODE_GCN && mode != MODE_GIN)
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "unknown mode %d", mode);
+    if (in_type != GNNA_BF16 && in_type != GNNA_F16)
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "in_type must be GNNA_BF16 or GNNA_F16 (got %d)", in_type);
+    if (out_type != GNNA_F32 && out_type != in_type)
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "out_type must be GNNA_F32 or the input's type (in_type=%d out_type=%d)", in_type, out_type);
+    if (flags & ~(unsigned)(GNNA_ACCUMULATE | GNNA_EPILOGUE_RELU))
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "unknown flag bits 0x%x", flags);
+    if (num_out_rows < 0 || dim < 0 || num_parts < 0 || num_in_rows < 0)
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "negative size (num_out_rows=%lld dim=%d num_parts=%lld)",
+                    (long long)num_out_rows, dim, (long long)num_parts);
+    if (partSize <= 0) return fail(GNNA_ERR_INVALID_ARGUMENT, "partSize must be positive (got %d)", partSize);
+    if ((flags & GNNA_ACCUMULATE) && out_type != GNNA_F32)
+        return fail(GNNA_ERR_UNSUPPORTED, "GNNA_ACCUMULATE with a 16-bit output would round the sum twice: accumulate into an fp32 output");
+    if (num_out_rows >= ((int64_t)1 << 29))
+        return fail(GNNA_ERR_UNSUPPORTED, "%lld destination rows in one call (at most 536870911): shard the rows", (long long)num_out_rows);
+    if (num_out_rows == 0 || dim == 0) return GNNA_OK;
+    if (ld_in < dim || ld_out < dim || ld_in >= ((int64_t)1 << 29) || ld_out >= ((int64_t)1 << 29))
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "row strides must be >= dim and < 2^29 elements (ld_in=%lld ld_out=%lld dim=%d)",
+                    (long long)ld_in, (long long)ld_out, dim);
+    if (!out || !input) return fail(GNNA_ERR_INVALID_ARGUMENT, "null feature pointer");
+    if ((reinterpret_cast<uintptr_t>(input) & 1) || (reinterpret_cast<uintptr_t>(out) & (out_type == GNNA_F32 ? 3 : 1)))
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "feature pointers must be aligned to their element size");
+    if (num_parts > 0 && (!column_index || !part_pointers || !part2Node))
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "null index pointer");
+    if (mode == MODE_GCN && (!degrees_out || !degrees_in)) return fail(GNNA_ERR_INVALID_ARGUMENT, "null degrees pointer");
+    if (out == input) return fail(GNNA_ERR_INVALID_ARGUMENT, "out must not alias input");
+    gnna_tuning tune;
+    gnna_get_tuning(&tune);
+    // every row is added with float atomics (gnna_x16.hip): the order of the additions is not fixed
+    if (tune.deterministic == 1)
+        return fail(GNNA_ERR_UNSUPPORTED, "gnna_agg_ld_x16 has no deterministic schedule (gnna_tuning.deterministic = 1): its rows meet "
+                                          "in fp32 through float atomics; use gnna_agg_ld_f32 on fp32 features");
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    DeviceState *ds = nullptr;
+    int rc = get_device_state(&ds);
+    if (rc != GNNA_OK) return rc;
+    X16Launch c;
+    c.mode = mode; c.in_type = in_type; c.out_type = out_type; c.input = input; c.ld_in = ld_in; c.num_in_rows = num_in_rows;
+    c.column_index = column_index; c.degrees_out = degrees_out; c.degrees_in = degrees_in; c.epsilon = epsilon;
+    c.part_pointers = part_pointers; c.part2Node = part2Node; c.out = out; c.ld_out = ld_out; c.num_out_rows = num_out_rows;
+    c.dim = dim; c.num_parts = num_parts; c.partSize = partSize;
+    c.accumulate = (flags & GNNA_ACCUMULATE) != 0; c.relu = (flags & GNNA_EPILOGUE_RELU) != 0; c.xcd_remap = tune.xcd_remap != 0;
+    c.prof_call = profile_acquire_call(num_parts > 0);
+    profile_record(c.prof_call, 0, stream);
+    t_last_phases = 1;
+    t_last_launches = 1;
+    rc = launch_x16(ds, stream, c);
+    if (rc != GNNA_OK) return rc;
+    profile_record(c.prof_call, 2, stream);
+    return GNNA_OK;
+}
+
+int gnna_prepare_x16(int64_t num_in_rows, int64_t num_out_rows, const int *dims, int num_dims, void *stream_v)
+{
+    if (num_in_rows < 0 || num_out_rows < 0 || num_dims < 0 || (num_dims > 0 && !dims))
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "gnna_prepare_x16: bad argument");
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(stream, &cap);
+    if (cap != hipStreamCaptureStatusNone)
+        return fail(GNNA_ERR_UNSUPPORTED, "gnna_prepare_x16 allocates: call it before the capture");
+    DeviceState *ds = nullptr;
+    int rc = get_device_state(&ds);
+    if (rc != GNNA_OK) return rc;
+    for (int i = 0; i < num_dims; i++) {
+        if (dims[i] <= 0) return fail(GNNA_ERR_INVALID_ARGUMENT, "gnna_prepare_x16: dims[%d] = %d", i, dims[i]);
+        rc = reserve_x16(ds, stream, num_in_rows, num_out_rows, dims[i]);
+        if (rc != GNNA_OK) return rc;
+    }
+    return GNNA_OK;
 }
 
 int64_t gnna_preferred_ld(int dim, int64_t num_in_rows, int64_t num_edges)

@@ -217,6 +217,24 @@ int sweep_auto_phases(const gnna_tuning &t, int mode, int dim, size_t x_bytes, i
 constexpr int kSweepListCap = 1023;    // list of row ranges the kernel did not store once: [count][overflow][(first, rows) ...]
 constexpr int kSweepSlotWords = 8 * 16 + 2 + 2 * kSweepListCap;
 
+// ---- 16-bit storage, fp32 accumulation (gnna_x16.hip) ----------------------------------------------------------
+struct X16Launch {
+    int mode;                 // MODE_SAG, MODE_GCN (per-edge fp32 source degree, fp32 destination degree at the flush) or MODE_GIN
+    int in_type, out_type;    // GNNA_BF16 / GNNA_F16; out_type may also be GNNA_F32
+    const void *input; int64_t ld_in, num_in_rows;          // leading dimensions in ELEMENTS
+    const int32_t *column_index; const float *degrees_out; const float *degrees_in; float epsilon;
+    const int32_t *part_pointers; const int32_t *part2Node;
+    void *out; int64_t ld_out, num_out_rows;
+    int dim; int64_t num_parts; int partSize;
+    bool accumulate, relu, xcd_remap;
+    int prof_call = -1;
+};
+int launch_x16(DeviceState *ds, hipStream_t stream, const X16Launch &c);
+// Sizes the stream's scratch of the 16-bit path for one width (staged source rows, fp32 sums of a 16-bit output).
+int reserve_x16(DeviceState *ds, hipStream_t stream, int64_t num_in_rows, int64_t num_out_rows, int dim);
+// out[r, 0:dim] = 0 for every row (rows `ld` floats apart): the dense prologue without its validation (gnna_agg.hip).
+int launch_zero_fill(DeviceState *ds, hipStream_t stream, float *out, int64_t rows, int dim, int64_t ld);
+
 // ---- optional per-call kernel timing (gnna_profile_begin/end) ---------------------------------------
 // Returns the index of this call in the active profile (-1 when not profiling).
 int profile_acquire_call(bool has_work);

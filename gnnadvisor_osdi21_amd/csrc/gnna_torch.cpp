@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <limits>
 #include <torch/extension.h>
+#include <torch/csrc/Dtype.h>
 
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
@@ -244,11 +245,20 @@ torch::Tensor aggregate(AggKind kind, const torch::Tensor &input, const torch::T
 torch::Tensor aggregate_general(int mode, const torch::Tensor &input, const torch::Tensor &column_index,
                                 const c10::optional<torch::Tensor> &degrees, double epsilon,
                                 const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize,
-                                c10::optional<torch::Tensor> out_opt, bool accumulate, bool relu)
+                                c10::optional<torch::Tensor> out_opt, bool accumulate, bool relu, pybind11::object out_dtype_obj)
 {
     CHECK_CUDA(input);
     TORCH_CHECK(input.dim() == 2, "input must be 2-D [num_nodes, dim]");
-    CHECK_F32(input);
+    const bool x16 = input.scalar_type() == at::kBFloat16 || input.scalar_type() == at::kHalf;
+    TORCH_CHECK(x16 || input.scalar_type() == at::kFloat, "input must be float32, bfloat16 or float16 (got ", input.scalar_type(), ")");
+    // out_dtype (bf16 / fp16 input only): float32 or the input's dtype; default: the input's dtype
+    at::ScalarType out_dtype = input.scalar_type();
+    if (!out_dtype_obj.is_none()) {
+        TORCH_CHECK(THPDtype_Check(out_dtype_obj.ptr()), "out_dtype must be a torch.dtype");
+        out_dtype = reinterpret_cast<THPDtype *>(out_dtype_obj.ptr())->scalar_type;
+        TORCH_CHECK(out_dtype == input.scalar_type() || (x16 && out_dtype == at::kFloat),
+                    "out_dtype must be float32 or the input's dtype ", input.scalar_type(), " (got ", out_dtype, ")");
+    }
     CHECK_INPUT(column_index); CHECK_I32(column_index);
     CHECK_INPUT(part_pointers); CHECK_I32(part_pointers);
     CHECK_INPUT(part2Node); CHECK_I32(part2Node);
@@ -267,16 +277,35 @@ torch::Tensor aggregate_general(int mode, const torch::Tensor &input, const torc
     torch::Tensor out;
     if (out_opt.has_value()) {
         out = *out_opt;
-        CHECK_CUDA(out); CHECK_F32(out);
+        CHECK_CUDA(out);
+        if (x16) {
+            TORCH_CHECK(out.scalar_type() == at::kFloat || out.scalar_type() == input.scalar_type(),
+                        "out must be float32 or have the input's dtype ", input.scalar_type(), " (got ", out.scalar_type(), ")");
+            TORCH_CHECK(out_dtype_obj.is_none() || out.scalar_type() == out_dtype, "out is ", out.scalar_type(), ", out_dtype says ", out_dtype);
+        } else {
+            CHECK_F32(out);
+        }
         TORCH_CHECK(out.dim() == 2 && out.size(0) == n && out.size(1) == dim, "out must be [num_nodes, dim] like input");
         TORCH_CHECK(dim <= 1 || out.stride(1) == 1, "out: the floats of a row must be contiguous (stride(1) == 1)");
     } else {
         TORCH_CHECK(!accumulate, "accumulate needs an existing `out`");
-        out = poison ? torch::full({n, dim}, std::numeric_limits<float>::quiet_NaN(), input.options()) : torch::empty({n, dim}, input.options());
+        // (the poison covers the 16-bit outputs as well: an element the library leaves unwritten is NaN in every float type)
+        const auto opts = input.options().dtype(out_dtype);
+        out = poison ? torch::full({n, dim}, std::numeric_limits<float>::quiet_NaN(), opts) : torch::empty({n, dim}, opts);
     }
     void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
     const float *deg = degrees.has_value() ? degrees->data_ptr<float>() : nullptr;
     const unsigned flags = (accumulate ? GNNA_ACCUMULATE : 0u) | (relu ? GNNA_EPILOGUE_RELU : 0u);
+    if (x16) {
+        // features stored in 16 bits, accumulated in fp32 (gnna_agg_ld_x16); the degrees stay fp32
+        const int in_type = input.scalar_type() == at::kBFloat16 ? GNNA_BF16 : GNNA_F16;
+        const int out_type = out.scalar_type() == at::kFloat ? GNNA_F32 : in_type;
+        int rc = gnna_agg_ld_x16(mode, in_type, input.data_ptr(), ld_of(input), n, column_index.data_ptr<int32_t>(), deg, deg,
+                                 (float)epsilon, part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(),
+                                 out.data_ptr(), out_type, ld_of(out), n, (int)dim, part2Node.size(0), partSize, flags, stream);
+        TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+        return out;
+    }
     int rc = gnna_agg_ld_f32(mode, input.data_ptr<float>(), ld_of(input), n, column_index.data_ptr<int32_t>(), deg, deg,
                              (float)epsilon, part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(),
                              out.data_ptr<float>(), ld_of(out), n, (int)dim, part2Node.size(0), partSize, flags, stream);
@@ -633,10 +662,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("backward_gin", &spmm_backward_gin, "GNNAdvisor backward GIN (HIP, gfx950)");
     m.def("aggregate_ld", &aggregate_general,
           "general aggregation (extension): mode 0 sag / 1 gcn / 2 gin; input and out may be row-strided views; "
-          "accumulate adds into out; relu clamps the result at zero in the same call",
+          "accumulate adds into out; relu clamps the result at zero in the same call.  bfloat16 / float16 input is accumulated "
+          "in fp32 (degrees stay float32) and returned as out_dtype: float32 or the input's dtype (the default)",
           pybind11::arg("mode"), pybind11::arg("input"), pybind11::arg("column_index"), pybind11::arg("degrees"),
           pybind11::arg("epsilon"), pybind11::arg("part_pointers"), pybind11::arg("part2Node"), pybind11::arg("partSize"),
-          pybind11::arg("out") = pybind11::none(), pybind11::arg("accumulate") = false, pybind11::arg("relu") = false);
+          pybind11::arg("out") = pybind11::none(), pybind11::arg("accumulate") = false, pybind11::arg("relu") = false,
+          pybind11::arg("out_dtype") = pybind11::none());
     m.def("aggregate_edge", &aggregate_edge,
           "edge-weighted aggregation (extension): out[i] (+)= sum_e edge_weight[e] * X[column_index[e]], edge_weight indexed like "
           "column_index; X and out may be row-strided views",

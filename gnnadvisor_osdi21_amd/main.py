@@ -44,6 +44,9 @@ def build_parser():
     p.add_argument('--scale', type=float, default=1.0, help="shrink the synthetic graph")
     p.add_argument('--locality', type=float, default=0.0, help="synthetic graph: share of the edges within +-4096 ids of a hidden order")
     p.add_argument('--scramble', default='False', **tf, help="synthetic graph: relabel the nodes at random (hides the locality)")
+    p.add_argument('--dtype', type=str, default='float32', choices=['float32', 'bfloat16', 'float16'],
+                   help="element type of the features and the model (gcn, gin): bfloat16 / float16 are aggregated with fp32 "
+                        "accumulation (libgnna gnna_agg_ld_x16); float16 GCN outputs can overflow on hub rows, prefer bfloat16")
     p.add_argument('--hip_graph', default='False', **tf,
                    help="True: capture one training epoch (forward, backward, Adam) into a HIP graph and replay it "
                         "(MI355X addition; pays on small, launch-bound graphs)")
@@ -70,6 +73,13 @@ def main(argv=None, capture=None):
     if args.model == 'gat' and flag(args.hip_graph):
         # (the attention layers build their per-edge arrays and the SDDMM's id copies at first use: not captured yet)
         raise SystemExit("--model gat does not support --hip_graph True: run it with --hip_graph False")
+    if args.dtype != 'float32' and args.model == 'gat':
+        raise SystemExit("--dtype %s: the attention layers (edge-weighted aggregation, SDDMM, edge softmax) are float32 only; "
+                         "run --model gat with --dtype float32" % args.dtype)
+    if args.dtype != 'float32' and flag(args.hip_graph):
+        raise SystemExit("--dtype %s does not support --hip_graph True yet: run it with --hip_graph False" % args.dtype)
+    if args.dtype != 'float32' and (flag(args.single_spmm) or flag(args.verify_spmm)):
+        raise SystemExit("--single_spmm / --verify_spmm run the float32 entry: use --dtype float32")
     if args.heads < 1:
         raise SystemExit("--heads must be >= 1")
     assert torch.cuda.is_available(), "requires an MI355X GPU: there is no CPU path"
@@ -180,7 +190,7 @@ def main(argv=None, capture=None):
             def forward(self):
                 x = self.conv1(dataset.x, inputInfo.set_input(), relu=True)   # F.relu(conv1(...)), fused (GNNA_main.py:151)
                 x = self.conv2(x, inputInfo.set_hidden())
-                return F.log_softmax(x, dim=1)
+                return F.log_softmax(x.float(), dim=1)
     elif args.model == 'gat':
         class Net(torch.nn.Module):
             def __init__(self):
@@ -204,9 +214,14 @@ def main(argv=None, capture=None):
                 for i, conv in enumerate(self.convs):
                     # F.relu after every layer but the last (GNNA_main.py:166-169), fused where the aggregation ends the layer
                     x = conv(x, inputInfo.set_input() if i == 0 else inputInfo.set_hidden(), relu=i + 1 < len(self.convs))
-                return F.log_softmax(x, dim=1)
+                return F.log_softmax(x.float(), dim=1)
 
     model = Net().to(device)
+    if args.dtype != 'float32':
+        # features and parameters stored in 16 bits; every aggregation accumulates in fp32 and rounds its result once
+        dataset.x = dataset.x.to(getattr(torch, args.dtype))
+        model = model.to(getattr(torch, args.dtype))
+        _gnna_lib.prepare_x16(dataset.num_nodes, dataset.num_nodes, _prep_widths, device=device)
     if capture is not None:
         capture.update(dataset=dataset, inputInfo=inputInfo, model=model, args=args)
     if verbose_mode:

@@ -28,16 +28,90 @@ def _knobs(info):
     return (info.partSize, info.dimWorker, info.warpPerBlock)
 
 
+# ---- features stored in bfloat16 / float16 (libgnna gnna_agg_ld_x16: fp32 accumulation, one rounding of the result) ------
+_X16 = (torch.bfloat16, torch.float16)
+
+
+def _x16_dtype(X):
+    """The 16-bit dtype a layer computes in: X's own when the model was cast, the autocast dtype inside
+    torch.autocast("cuda", dtype=bfloat16 / float16), else None (the fp32 path, unchanged)."""
+    if X.dtype in _X16:
+        return X.dtype
+    if X.is_cuda and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") in _X16:
+        return torch.get_autocast_dtype("cuda")
+    return None
+
+
+def _aggregate_x16(mode, X, graph, partSize, epsilon=1.0, relu=False):
+    """mode 0 sag / 1 gcn / 2 gin over 16-bit X -> the same dtype; the degrees stay fp32."""
+    _rp, ci, deg, pp, p2n = graph
+    if X.dim() == 2 and X.shape[1] > 1 and X.stride(1) != 1:
+        X = X.contiguous()
+    return GNNA.aggregate_ld(mode, X, ci, deg if mode == 1 else None, float(epsilon), pp, p2n, partSize, None, False, bool(relu))
+
+
+class GNNAFunction_X16(Function):
+    """A GCN (mode 1) or GIN (mode 2) layer on 16-bit features, update-first -- Y = agg(X W), the GCN order -- or
+    aggregate-first -- Y = agg(X) W.  Both aggregations (forward, and backward on the 16-bit gradient: the structure is
+    assumed symmetric, as everywhere in this file) run on gnna_agg_ld_x16 and return the compute dtype; the dense products
+    (X W, G W^T, X^T G) are torch.mm on 16-bit operands.  X and the weights may be fp32 (torch.autocast) or 16-bit (a cast
+    model): their gradients come back in their own dtype."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda")
+    def forward(ctx, X, weight, inputInfo, mode, epsilon, update_first, relu, dtype):
+        ctx.graph, ctx.partSize = _graph_args(inputInfo), inputInfo.partSize
+        ctx.mode, ctx.eps, ctx.update_first, ctx.relu, ctx.dtype = int(mode), float(epsilon), bool(update_first), bool(relu), dtype
+        ctx.in_dtypes = (X.dtype, weight.dtype)
+        Xh, Wh = X.to(dtype), weight.to(dtype)
+        if ctx.update_first:
+            Y = _aggregate_x16(ctx.mode, torch.mm(Xh, Wh), ctx.graph, ctx.partSize, ctx.eps, ctx.relu)
+            ctx.save_for_backward(Xh, Wh, *((Y,) if ctx.relu else ()))
+        else:
+            T = _aggregate_x16(ctx.mode, Xh, ctx.graph, ctx.partSize, ctx.eps)
+            Y = torch.mm(T, Wh)
+            if ctx.relu:
+                Y = torch.relu(Y)
+            ctx.save_for_backward(T, Wh, *((Y,) if ctx.relu else ()))
+        return Y
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, d_output):
+        saved, Wh = ctx.saved_tensors[0], ctx.saved_tensors[1]
+        dY = d_output.to(ctx.dtype)
+        if ctx.relu:
+            dY = dY * (ctx.saved_tensors[2] > 0)
+        dY = dY.contiguous()
+        d_input = None
+        if ctx.update_first:
+            G = _aggregate_x16(ctx.mode, dY, ctx.graph, ctx.partSize, ctx.eps)
+            d_weight = torch.mm(saved.t(), G)
+            if ctx.needs_input_grad[0]:
+                d_input = torch.mm(G, Wh.t())
+        else:
+            d_weight = torch.mm(saved.t(), dY)
+            if ctx.needs_input_grad[0]:
+                d_input = _aggregate_x16(ctx.mode, torch.mm(dY, Wh.t()), ctx.graph, ctx.partSize, ctx.eps)
+        if d_input is not None:
+            d_input = d_input.to(ctx.in_dtypes[0])
+        return d_input, d_weight.to(ctx.in_dtypes[1]), None, None, None, None, None, None
+
+
 class ScatterAndGather(Function):
     """Y = A X (unweighted neighbor sum).  A is assumed symmetric, so backward is the same op."""
 
     @staticmethod
     def forward(ctx, X, inputInfo):
         ctx.graph, ctx.knobs = _graph_args(inputInfo), _knobs(inputInfo)
+        if X.dtype in _X16:
+            return _aggregate_x16(0, X, ctx.graph, ctx.knobs[0])
         return GNNA.SAG(X, *ctx.graph, *ctx.knobs)
 
     @staticmethod
     def backward(ctx, d_output):
+        if d_output.dtype in _X16:
+            return _aggregate_x16(0, d_output, ctx.graph, ctx.knobs[0]), None
         return GNNA.SAG(d_output.contiguous(), *ctx.graph, *ctx.knobs), None
 
 
@@ -178,6 +252,9 @@ class GCNConv(_NeighborConv):
         """X: [num_nodes, input_dim]; inputInfo: decider.inputProperty holding the CSR, the
         sqrt-degree vector and the neighbor-group partition on X's device.  relu=True returns relu(layer) with the
         clamp fused into the aggregation (same values as F.relu(conv(X, inputInfo)))."""
+        dt = _x16_dtype(X)
+        if dt is not None:      # bfloat16 / float16 features (a cast model, or torch.autocast): fp32 accumulation, 16-bit result
+            return GNNAFunction_X16.apply(X, self.weights, inputInfo, 1, 1.0, True, relu, dt)
         return (GNNAFunction_ReLU if relu else GNNAFunction).apply(X, self.weights, inputInfo)
 
 
@@ -201,6 +278,9 @@ class GINConv(_NeighborConv):
     def forward(self, X, inputInfo, relu=False):
         """relu=True returns relu(layer): fused into the aggregation when the layer runs update-first (the aggregation is
         its last step), an ordinary F.relu behind the dense update otherwise."""
+        dt = _x16_dtype(X)
+        if dt is not None:
+            return GNNAFunction_X16.apply(X, self.weights, inputInfo, 2, self.eplison, self._use_update_first(X), relu, dt)
         if self._use_update_first(X):
             return GNNAFunction_GIN_UpdateFirst.apply(X, self.weights, inputInfo, self.eplison, relu)
         Y = GNNAFunction_GIN.apply(X, self.weights, inputInfo, self.eplison)

@@ -64,7 +64,7 @@
 extern "C" {
 #endif
 
-#define GNNA_VERSION 601 /* 0.6.1: gnna_agg_edge_ld_f32 (caller-supplied edge weights), gnna_edge_softmax_f32, gnna_edge_softmax_backward_f32, gnna_reverse_edges_i32; per-capture library scratch, full hashes of a packed copy ordered across streams, gnna_debug_untrusted_copies, counter [9]; 0.6.0: gnna_tuning.ids_check_every (full hash of the ids behind a packed copy), gnna_device_cus, gnna_host_threads; 0.5.0: gnna_tuning opens with struct_size (checked by gnna_set_tuning, which now returns a status), gnna_build_id; 0.4.1: gnna_sddmm_ld_f32 (leading dimensions for both SDDMM sides); 0.4.0: gnna_agg_ld_f32 (leading dimensions, ReLU epilogue), gnna_forget_graph, chunk-walk kernel retired; 0.3.1: gnna_tuning grew (pack_ids); 0.3.0: sweep, sweep_slack, graph lifecycle, 64-bit CSR builder */
+#define GNNA_VERSION 601 /* 0.6.1: gnna_agg_ld_x16 + gnna_prepare_x16 (bf16 / fp16 storage, fp32 accumulation; GNNA_F32 / GNNA_BF16 / GNNA_F16), gnna_agg_edge_ld_f32 (caller-supplied edge weights), gnna_edge_softmax_f32, gnna_edge_softmax_backward_f32, gnna_reverse_edges_i32; per-capture library scratch, full hashes of a packed copy ordered across streams, gnna_debug_untrusted_copies, counter [9]; 0.6.0: gnna_tuning.ids_check_every (full hash of the ids behind a packed copy), gnna_device_cus, gnna_host_threads; 0.5.0: gnna_tuning opens with struct_size (checked by gnna_set_tuning, which now returns a status), gnna_build_id; 0.4.1: gnna_sddmm_ld_f32 (leading dimensions for both SDDMM sides); 0.4.0: gnna_agg_ld_f32 (leading dimensions, ReLU epilogue), gnna_forget_graph, chunk-walk kernel retired; 0.3.1: gnna_tuning grew (pack_ids); 0.3.0: sweep, sweep_slack, graph lifecycle, 64-bit CSR builder */
 #define GNNA_API __attribute__((visibility("default")))
 
 typedef enum gnna_status {
@@ -243,6 +243,35 @@ GNNA_API int gnna_agg_edge_ld_f32(const float *input, int64_t ld_in, int64_t num
         const int32_t *column_index, const float *edge_weight /* [nnz], indexed like column_index */,
         const int32_t *part_pointers, const int32_t *part2Node, float *out, int64_t ld_out,
         int64_t num_out_rows, int dim, int64_t num_parts, int partSize, unsigned flags, void *stream);
+
+/* 16-bit storage, fp32 arithmetic: gnna_agg_ld_f32 over features STORED as bfloat16 or IEEE half and ACCUMULATED in fp32.
+ *   in_type:  GNNA_BF16 or GNNA_F16 -- the element type of `input`;
+ *   out_type: GNNA_F32 (`out` is float) or in_type (`out` has the input's type); anything else: GNNA_ERR_INVALID_ARGUMENT;
+ *   ld_in / ld_out: ELEMENTS between the starts of consecutive rows (>= dim).  Source rows that can be read 16 bytes at a time
+ *     -- base 16-byte aligned, ld_in and dim multiples of 8 -- are gathered in place; any other layout (dim 1, 3, 7, 41, 100 ...)
+ *     is first copied into library scratch with the width padded to a multiple of 8;
+ *   degrees_out / degrees_in / epsilon: fp32, as for gnna_agg_ld_f32.  GCN is deg_out[i] * sum_j deg_in[j] * float(x[j]): every
+ *     product and every sum is fp32 and the library never makes a pre-scaled 16-bit copy of `input`;
+ *   a 16-bit output element is rounded exactly once, to nearest-even, after its whole sum (row factor and ReLU included) is
+ *     known: the sums meet in fp32 library scratch (num_out_rows x dim floats; a captured call gets its capture's own) and a small
+ *     epilogue converts them.  fp16 output beyond +-65504 becomes +-inf, as IEEE rounding says -- the GCN coefficients are
+ *     products of sqrt-degrees and reach 1e3 - 1e5 on hub rows, so take GNNA_BF16 or GNNA_F32 output for GCN;
+ *   flags: GNNA_EPILOGUE_RELU with both output types; GNNA_ACCUMULATE with fp32 output only (GNNA_ERR_UNSUPPORTED with a 16-bit
+ *     output: adding into it would round twice).
+ * Correct for every partition gnna_agg_ld_f32 accepts (every row is added with float atomics: no validation pass, no plan, no
+ * synchronisation).  For the same reason there is no deterministic schedule: with gnna_tuning.deterministic = 1 the call returns
+ * GNNA_ERR_UNSUPPORTED.  Limits of one call as for gnna_agg_ld_f32.  Scratch is allocated on first use like every other library
+ * scratch; gnna_prepare_x16 sizes it up front for the given widths on `stream` (not inside a capture), after which eager calls
+ * of those widths from num_in_rows source rows into num_out_rows destination rows on that stream never allocate or free. */
+#define GNNA_F32 0   /* output only */
+#define GNNA_BF16 1
+#define GNNA_F16 2
+GNNA_API int gnna_agg_ld_x16(int mode, int in_type, const void *input, int64_t ld_in, int64_t num_in_rows,
+        const int32_t *column_index, const float *degrees_out, const float *degrees_in, float epsilon,
+        const int32_t *part_pointers, const int32_t *part2Node,
+        void *out, int out_type, int64_t ld_out, int64_t num_out_rows, int dim, int64_t num_parts, int partSize,
+        unsigned flags, void *stream);
+GNNA_API int gnna_prepare_x16(int64_t num_in_rows, int64_t num_out_rows, const int *dims, int num_dims, void *stream);
 
 /* Edge softmax over the edges of every destination row, per head; scores are head-major [num_heads, num_edges]:
  *   probs[h, e] = exp(s[h, e] - max_row) / sum_row exp(s - max_row),  e in [row_pointers[i], row_pointers[i + 1]).
