@@ -49,7 +49,7 @@ EXPORTS = ("gnna_version", "gnna_build_id", "gnna_last_error", "gnna_count_parts
            "gnna_forget_graph", "gnna_agg_ld_f32", "gnna_preferred_ld", "gnna_device_cus", "gnna_host_threads",
            "gnna_reorder_community_csr_i32", "gnna_relabel_edges_i32", "gnna_relabel_csr_i32", "gnna_runtime_counters_ex", "gnna_forget_plans",
            "gnna_debug_untrusted_copies", "gnna_agg_edge_ld_f32", "gnna_edge_softmax_f32", "gnna_edge_softmax_backward_f32",
-           "gnna_reverse_edges_i32", "gnna_agg_ld_x16", "gnna_prepare_x16")
+           "gnna_reverse_edges_i32", "gnna_agg_ld_x16", "gnna_prepare_x16", "gnna_agg_reduce_ld_f32", "gnna_scatter_arg_ld_f32")
 
 
 def load() -> ctypes.CDLL:
@@ -178,6 +178,14 @@ def load() -> ctypes.CDLL:
                                                  ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     L.gnna_reverse_edges_i32.restype = ctypes.c_int
     L.gnna_reverse_edges_i32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+    L.gnna_agg_reduce_ld_f32.restype = ctypes.c_int
+    L.gnna_agg_reduce_ld_f32.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 4 + [
+        ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_uint,
+        ctypes.c_void_p]
+    L.gnna_scatter_arg_ld_f32.restype = ctypes.c_int
+    L.gnna_scatter_arg_ld_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                          ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                          ctypes.c_uint, ctypes.c_void_p]
     _lib = L
     return L
 
@@ -753,3 +761,65 @@ def reverse_edges(row_pointers, column_index) -> torch.Tensor:
     rev = torch.empty(ci.numel(), dtype=torch.int32)
     _check(load().gnna_reverse_edges_i32(rp.data_ptr(), ci.data_ptr(), rp.numel() - 1, rev.data_ptr()))
     return rev
+
+
+REDUCE_MAX, REDUCE_MIN = 0, 1   # GNNA_REDUCE_MAX / GNNA_REDUCE_MIN
+
+
+def _arg_view(t: torch.Tensor, rows: int, dim: int, what: str):
+    """(data pointer, leading dimension) of a 2-D int32 device tensor [rows, dim] whose rows are contiguous."""
+    assert t.dtype == torch.int32 and t.dim() == 2 and tuple(t.shape) == (rows, dim), f"{what} must be int32 [{rows}, {dim}]"
+    if dim > 1 and t.stride(1) != 1:
+        raise GnnaError(f"{what}: the elements of a row must be contiguous (stride(1) == 1)")
+    ld = t.stride(0) if rows > 1 else max(dim, t.stride(0))
+    if ld < dim:
+        raise GnnaError(f"{what}: rows overlap (stride(0) = {t.stride(0)} < {dim})")
+    return t.data_ptr(), ld
+
+
+def agg_reduce_ld(op, X, column_index, part_pointers, part2Node, partSize=32, *, num_out_rows=None, out=None, want_arg=True,
+                  relu=False, arg=None):
+    """gnna_agg_reduce_ld_f32: out[i, f] = max / min (op = REDUCE_MAX / REDUCE_MIN) over the edges e of row i of
+    X[column_index[e], f] and arg[i, f] = the smallest such position e (int32; -1 and out = 0 for rows without edges).
+    -> (out, arg); arg is None with want_arg=False.  `X`, `out` and a caller's `arg` may be row-strided views (stride(1) == 1):
+    they are passed with their leading dimension, no copy.  relu: out = max(out, 0), arg unchanged."""
+    if not X.is_cuda:
+        raise GnnaError("aggregation needs device tensors: there is no CPU path in libgnna")
+    xp, n_in, dim, ld_in = _rows_view(X, "X")
+    n_out = n_in if num_out_rows is None else int(num_out_rows)
+    if out is None:
+        out = _fresh_output((n_out, dim), X.device)
+    yp, rows_o, dim_o, ld_out = _rows_view(out, "out")
+    assert rows_o == n_out and dim_o == dim and out.device == X.device
+    ap, ld_arg = None, dim
+    if arg is not None or want_arg:
+        if arg is None:
+            # (poisoned like a fresh `out`: a position the library fails to write cannot pass for one it wrote)
+            poison = os.environ.get("GNNA_DEBUG_POISON", "0") not in ("", "0")
+            arg = (torch.full((n_out, dim), -(2 ** 31), dtype=torch.int32, device=X.device) if poison
+                   else torch.empty((n_out, dim), dtype=torch.int32, device=X.device))
+        assert arg.device == X.device
+        ap, ld_arg = _arg_view(arg, n_out, dim, "arg")
+    with torch.cuda.device(X.device):
+        _check(load().gnna_agg_reduce_ld_f32(int(op), xp, ld_in, n_in, column_index.data_ptr(), part_pointers.data_ptr(),
+                                             part2Node.data_ptr(), yp, ld_out, ap, ld_arg, n_out, dim, part2Node.numel(),
+                                             int(partSize), EPILOGUE_RELU if relu else 0, _stream(X.device)))
+    return out, arg
+
+
+def scatter_arg_ld(grad_out, arg, column_index, num_in_rows, out=None, accumulate=False):
+    """gnna_scatter_arg_ld_f32, the backward of agg_reduce_ld: out[column_index[arg[i, f]], f] += grad_out[i, f] for every
+    arg[i, f] >= 0; `out` [num_in_rows, dim] is cleared first unless accumulate.  Strided views as in agg_reduce_ld."""
+    if not grad_out.is_cuda:
+        raise GnnaError("scatter_arg needs device tensors: there is no CPU path in libgnna")
+    gp, n_out, dim, ld_go = _rows_view(grad_out, "grad_out")
+    ap, ld_arg = _arg_view(arg, n_out, dim, "arg")
+    if out is None:
+        assert not accumulate, "accumulate needs an existing `out`"
+        out = _fresh_output((int(num_in_rows), dim), grad_out.device)
+    op_, rows_i, dim_i, ld_gi = _rows_view(out, "out")
+    assert rows_i == int(num_in_rows) and dim_i == dim and out.device == grad_out.device and arg.device == grad_out.device
+    with torch.cuda.device(grad_out.device):
+        _check(load().gnna_scatter_arg_ld_f32(gp, ld_go, ap, ld_arg, column_index.data_ptr(), n_out, op_, ld_gi, int(num_in_rows),
+                                              dim, ACCUMULATE if accumulate else 0, _stream(grad_out.device)))
+    return out

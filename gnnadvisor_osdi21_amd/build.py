@@ -26,7 +26,7 @@ EXT = os.path.join(PKG, "GNNAdvisor.so")
 ARCH = "gfx950"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-LIB_SOURCES = [os.path.join(CSRC, f) for f in ("gnna_agg.hip", "gnna_stream.hip", "gnna_sweep.hip", "gnna_x16.hip", "gnna_sddmm.hip", "gnna_edge.hip",
+LIB_SOURCES = [os.path.join(CSRC, f) for f in ("gnna_agg.hip", "gnna_stream.hip", "gnna_sweep.hip", "gnna_x16.hip", "gnna_reduce.hip", "gnna_sddmm.hip", "gnna_edge.hip",
                                                 "gnna_gemm.hip", "gnna_runtime.hip", "gnna_host.cpp", "gnna_reorder.cpp")]
 LIB_DEPS = LIB_SOURCES + [os.path.join(CSRC, "gnna_internal.h"), os.path.join(CSRC, "gnna_device.h"),
                            os.path.join(INCLUDE, "gnna.h")]
@@ -68,6 +68,9 @@ def build_lib(force: bool = False, verbose: bool = False) -> str:
     digest = source_hash()
     stamp = os.path.join(objdir, "source_hash.txt")
     stamped = open(stamp).read().strip() if os.path.exists(stamp) else ""
+    if not force and stamped == digest and os.path.exists(LIB) and not _stale(LIB, LIB_DEPS):
+        # the library carries the stamp of exactly these sources (a tree that was shipped without its object files): keep it
+        return LIB
     for src in LIB_SOURCES:
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         objs.append(obj)

@@ -354,6 +354,80 @@ torch::Tensor aggregate_edge(const torch::Tensor &input, const torch::Tensor &co
     return out;
 }
 
+// Element-wise max / min over every row's neighbours (gnna_agg_reduce_ld_f32) -> (out, arg); strided X / out as aggregate_ld.
+// arg [num_nodes, dim] int32: the position in column_index that supplied each element (-1: the row has no edge); an undefined
+// tensor (None in Python) with want_arg = false.
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>>
+aggregate_reduce(int op, const torch::Tensor &input, const torch::Tensor &column_index, const torch::Tensor &part_pointers,
+                 const torch::Tensor &part2Node, int partSize, c10::optional<torch::Tensor> out_opt, bool want_arg, bool relu)
+{
+    CHECK_CUDA(input);
+    TORCH_CHECK(input.dim() == 2, "input must be 2-D [num_nodes, dim]");
+    CHECK_F32(input);
+    CHECK_INPUT(column_index); CHECK_I32(column_index);
+    CHECK_INPUT(part_pointers); CHECK_I32(part_pointers);
+    CHECK_INPUT(part2Node); CHECK_I32(part2Node);
+    TORCH_CHECK(op == GNNA_REDUCE_MAX || op == GNNA_REDUCE_MIN, "op must be 0 (max) or 1 (min)");
+    TORCH_CHECK(column_index.device() == input.device(), "input and column_index must be on one device");
+    TORCH_CHECK(input.size(1) >= 1, "input must have at least one column");
+    TORCH_CHECK(input.size(1) <= 1 || input.stride(1) == 1, "input: the floats of a row must be contiguous (stride(1) == 1)");
+    const int64_t n = input.size(0);
+    const int64_t dim = input.size(1);
+    auto ld_of = [&](const torch::Tensor &t) { return t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(t.size(1), t.stride(0)); };
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(input.device());
+    static const bool poison = std::getenv("GNNA_DEBUG_POISON") && std::atoi(std::getenv("GNNA_DEBUG_POISON")) != 0;
+    torch::Tensor out;
+    if (out_opt.has_value()) {
+        out = *out_opt;
+        CHECK_CUDA(out); CHECK_F32(out);
+        TORCH_CHECK(out.dim() == 2 && out.size(0) == n && out.size(1) == dim, "out must be [num_nodes, dim] like input");
+        TORCH_CHECK(dim <= 1 || out.stride(1) == 1, "out: the floats of a row must be contiguous (stride(1) == 1)");
+    } else {
+        out = poison ? torch::full({n, dim}, std::numeric_limits<float>::quiet_NaN(), input.options()) : torch::empty({n, dim}, input.options());
+    }
+    c10::optional<torch::Tensor> arg;
+    if (want_arg) {
+        const auto opts = input.options().dtype(at::kInt);
+        arg = poison ? torch::full({n, dim}, std::numeric_limits<int32_t>::min(), opts) : torch::empty({n, dim}, opts);
+    }
+    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+    int rc = gnna_agg_reduce_ld_f32(op, input.data_ptr<float>(), ld_of(input), n, column_index.data_ptr<int32_t>(),
+                                    part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), out.data_ptr<float>(),
+                                    ld_of(out), arg.has_value() ? arg->data_ptr<int32_t>() : nullptr, dim, n, (int)dim,
+                                    part2Node.size(0), partSize, relu ? GNNA_EPILOGUE_RELU : 0u, stream);
+    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+    return std::make_tuple(out, arg);
+}
+
+// Backward of aggregate_reduce (gnna_scatter_arg_ld_f32): grad_in[column_index[arg[i, f]], f] += grad_out[i, f], arg >= 0.
+torch::Tensor scatter_arg(const torch::Tensor &grad_out, const torch::Tensor &arg, const torch::Tensor &column_index,
+                          int64_t num_in_rows)
+{
+    CHECK_CUDA(grad_out);
+    TORCH_CHECK(grad_out.dim() == 2, "grad_out must be 2-D [num_nodes, dim]");
+    CHECK_F32(grad_out);
+    CHECK_INPUT(arg); CHECK_I32(arg);
+    CHECK_INPUT(column_index); CHECK_I32(column_index);
+    TORCH_CHECK(arg.dim() == 2 && arg.size(0) == grad_out.size(0) && arg.size(1) == grad_out.size(1), "arg must be [num_nodes, dim] like grad_out");
+    TORCH_CHECK(arg.device() == grad_out.device() && column_index.device() == grad_out.device(),
+                "grad_out, arg and column_index must be on one device");
+    TORCH_CHECK(grad_out.size(1) >= 1, "grad_out must have at least one column");
+    TORCH_CHECK(grad_out.size(1) <= 1 || grad_out.stride(1) == 1, "grad_out: the floats of a row must be contiguous (stride(1) == 1)");
+    TORCH_CHECK(num_in_rows >= 0, "num_in_rows must not be negative");
+    const int64_t n = grad_out.size(0);
+    const int64_t dim = grad_out.size(1);
+    auto ld_of = [&](const torch::Tensor &t) { return t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(t.size(1), t.stride(0)); };
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(grad_out.device());
+    static const bool poison = std::getenv("GNNA_DEBUG_POISON") && std::atoi(std::getenv("GNNA_DEBUG_POISON")) != 0;
+    auto out = poison ? torch::full({num_in_rows, dim}, std::numeric_limits<float>::quiet_NaN(), grad_out.options())
+                      : torch::empty({num_in_rows, dim}, grad_out.options());
+    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+    int rc = gnna_scatter_arg_ld_f32(grad_out.data_ptr<float>(), ld_of(grad_out), arg.data_ptr<int32_t>(), dim,
+                                     column_index.data_ptr<int32_t>(), n, out.data_ptr<float>(), dim, num_in_rows, (int)dim, 0u, stream);
+    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+    return out;
+}
+
 // Edge softmax and its backward: scores [nnz] or head-major [heads, nnz] over the rows of row_pointers.
 torch::Tensor edge_softmax(const torch::Tensor &scores, const torch::Tensor &row_pointers)
 {
@@ -674,6 +748,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           pybind11::arg("X"), pybind11::arg("column_index"), pybind11::arg("edge_weight"), pybind11::arg("partPtr"),
           pybind11::arg("part2Node"), pybind11::arg("partSize"), pybind11::arg("out") = pybind11::none(),
           pybind11::arg("accumulate") = false, pybind11::arg("relu") = false);
+    m.def("aggregate_reduce", &aggregate_reduce,
+          "element-wise max (op 0) / min (op 1) over every row's neighbours (extension) -> (out, arg): arg[i, f] is the position in "
+          "column_index that supplied out[i, f], the smallest one among ties; rows without edges give 0 and -1",
+          pybind11::arg("op"), pybind11::arg("X"), pybind11::arg("column_index"), pybind11::arg("partPtr"),
+          pybind11::arg("part2Node"), pybind11::arg("partSize"), pybind11::arg("out") = pybind11::none(),
+          pybind11::arg("want_arg") = true, pybind11::arg("relu") = false);
+    m.def("scatter_arg", &scatter_arg,
+          "backward of aggregate_reduce (extension): grad_in[column_index[arg[i, f]], f] += grad_out[i, f] for arg >= 0",
+          pybind11::arg("grad_out"), pybind11::arg("arg"), pybind11::arg("column_index"), pybind11::arg("num_in_rows"));
     m.def("edge_softmax", &edge_softmax, "softmax over every row's edges; scores [nnz] or [heads, nnz] (extension)",
           pybind11::arg("scores"), pybind11::arg("row_pointers"));
     m.def("edge_softmax_backward", &edge_softmax_backward, "gradient of edge_softmax: probs * (grad - sum_row probs * grad) (extension)",

@@ -171,14 +171,28 @@ REORDER_S_PER_NODE = 3.9e-7
 REFERENCE_EPOCHS = 200 + 10          # GNNA_main.py:25 (--num_epoches) + the 10 dry runs (:188-189)
 
 
-def expected_aggregations(model, in_dim, hidden, classes, epochs=REFERENCE_EPOCHS, heads=1):
+def expected_aggregations(model, in_dim, hidden, classes, epochs=REFERENCE_EPOCHS, heads=1, aggregator="mean"):
     """[(feature width, aggregations at that width)] of a whole training run of the reference's models (GNNA_main.py:143-171):
     GCN aggregates X W, i.e. at each layer's OUTPUT width, forward and backward; GIN aggregates at each layer's input width
     (forward; backward too unless it is the first layer) or, evaluated update-first (ops.GINConv), at the output width.
     GAT (main.py --model gat) aggregates every head of H = X W at the head's width, forward and backward (the weighted
-    gather of dY): `heads` per step on the hidden layer, one on the output layer."""
+    gather of dY): `heads` per step on the hidden layer, one on the output layer.
+    GraphSAGE (main.py --model sage, two ops.SAGEConv layers): the mean aggregator follows GIN's rule per layer (the neighbor
+    weights commute with the mean); max / min gather once per layer and step at the layer's INPUT width -- their backward
+    (scatter_arg) is num_nodes x width work, not a gather, and the first layer's features need no gradient."""
     units = lambda w: (int(w) + 63) // 64
     out = []
+    if model == "sage":
+        dims = [in_dim, hidden, classes]
+        for i, (a, b) in enumerate(zip(dims[:-1], dims[1:])):
+            needs_dx = i > 0
+            if aggregator != "mean":
+                out.append((a, epochs))
+            elif 2 * units(b) < (2 * units(a) if needs_dx else units(a)):
+                out.append((b, 2 * epochs))
+            else:
+                out.append((a, (2 if needs_dx else 1) * epochs))
+        return out
     if model == "gat":
         return [(hidden, 2 * heads * epochs), (classes, 2 * epochs)]
     if model == "gin":
@@ -477,6 +491,15 @@ class inputProperty(object):
             n = rp.numel() - 1
             cache["rows"] = torch.repeat_interleave(torch.arange(n, dtype=torch.int32, device=rp.device), rp[1:] - rp[:-1])
         return cache["rows"]
+
+    def inv_row_counts(self):
+        """float32 [num_nodes] on the graph's device: 1 / max(edges of the row, 1), from row_pointers (`degrees` holds square
+        roots).  The row factor of a neighbor mean; a row without edges keeps the factor 1.  Built once per column_index."""
+        cache = self._edge_arrays()
+        if "inv_counts" not in cache:
+            rp = self.row_pointers.to(self.column_index.device).long()
+            cache["inv_counts"] = 1.0 / (rp[1:] - rp[:-1]).clamp(min=1).float()
+        return cache["inv_counts"]
 
     def apply_tuning(self):
         """Push the scheduler knobs and graph hints chosen by the mi355x policy into libgnna.

@@ -26,7 +26,9 @@ def build_parser():
     p.add_argument("--dim", type=int, default=96, help="input embedding dimension size")
     p.add_argument("--hidden", type=int, default=16, help="hidden dimension size")
     p.add_argument("--classes", type=int, default=22, help="output classes size")
-    p.add_argument('--model', type=str, default='gcn', choices=['gcn', 'gin', 'gat'], help="GCN, GIN or GAT")
+    p.add_argument('--model', type=str, default='gcn', choices=['gcn', 'gin', 'gat', 'sage'], help="GCN, GIN, GAT or GraphSAGE")
+    p.add_argument('--aggregator', type=str, default='mean', choices=['mean', 'max', 'min'],
+                   help="GraphSAGE: how a node's neighbours are reduced (mean, element-wise max or element-wise min)")
     p.add_argument('--heads', type=int, default=1, help="GAT: attention heads of the hidden layer (the output layer has one)")
     p.add_argument("--num_epoches", type=int, default=200, help="number of epoches for training, default=200")
     p.add_argument("--partSize", type=int, default=32, help="neighbor-group size")
@@ -76,6 +78,9 @@ def main(argv=None, capture=None):
     if args.dtype != 'float32' and args.model == 'gat':
         raise SystemExit("--dtype %s: the attention layers (edge-weighted aggregation, SDDMM, edge softmax) are float32 only; "
                          "run --model gat with --dtype float32" % args.dtype)
+    if args.dtype != 'float32' and args.model == 'sage':
+        raise SystemExit("--dtype %s: the GraphSAGE layers (max / min / mean over the neighbours) are float32 only; "
+                         "run --model sage with --dtype float32" % args.dtype)
     if args.dtype != 'float32' and flag(args.hip_graph):
         raise SystemExit("--dtype %s does not support --hip_graph True yet: run it with --hip_graph False" % args.dtype)
     if args.dtype != 'float32' and (flag(args.single_spmm) or flag(args.verify_spmm)):
@@ -96,7 +101,7 @@ def main(argv=None, capture=None):
     from . import load_extension
     from .decider import inputProperty
     from .loader import custom_dataset
-    from .ops import GATConv, GCNConv, GINConv
+    from .ops import GATConv, GCNConv, GINConv, SAGEConv
     GNNA = load_extension()
 
     # ---- loading data --------------------------------------------------------------------
@@ -120,7 +125,7 @@ def main(argv=None, capture=None):
     from .decider import expected_aggregations
     inputInfo.expected_aggregations = [(args.hidden, args.num_epoches)] if (single_spmm or verify_spmm) else \
         expected_aggregations(args.model, dataset.num_features, args.hidden, dataset.num_classes, args.num_epoches + 10,
-                              heads=args.heads)
+                              heads=args.heads, aggregator=args.aggregator)
     inputInfo.force_renumbering = flag(args.force_rabbit)
     inputInfo.decider()
     inputInfo = inputInfo.set_input()
@@ -200,6 +205,19 @@ def main(argv=None, capture=None):
 
             def forward(self):
                 x = F.elu(self.conv1(dataset.x, inputInfo.set_input()))
+                x = self.conv2(x, inputInfo.set_hidden())
+                return F.log_softmax(x, dim=1)
+    elif args.model == 'sage':
+        inputInfo.inv_row_counts()      # (the mean's row factors: built here, not inside a captured epoch)
+
+        class Net(torch.nn.Module):
+            def __init__(self):
+                super().__init__()
+                self.conv1 = SAGEConv(dataset.num_features, args.hidden, aggregator=args.aggregator)
+                self.conv2 = SAGEConv(args.hidden, dataset.num_classes, aggregator=args.aggregator)
+
+            def forward(self):
+                x = self.conv1(dataset.x, inputInfo.set_input(), relu=True)
                 x = self.conv2(x, inputInfo.set_hidden())
                 return F.log_softmax(x, dim=1)
     else:

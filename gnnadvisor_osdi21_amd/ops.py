@@ -287,6 +287,113 @@ class GINConv(_NeighborConv):
         return torch.relu(Y) if relu else Y
 
 
+# ---- max / min / mean over the neighbours, GraphSAGE ------------------------------------------------------------------
+
+def _extreme_forward(op, ctx, X, inputInfo):
+    if X.dtype != torch.float32:
+        raise TypeError(f"neighbor max / min: float32 features only (got {X.dtype})")
+    ci = inputInfo.column_index
+    ctx.num_in_rows = X.shape[0]
+    Y, arg = GNNA.aggregate_reduce(op, X, ci, inputInfo.partPtr, inputInfo.part2Node, inputInfo.partSize)
+    ctx.save_for_backward(arg, ci)
+    return Y
+
+
+def _extreme_backward(ctx, dY):
+    arg, ci = ctx.saved_tensors
+    return GNNA.scatter_arg(dY.contiguous(), arg, ci, ctx.num_in_rows), None
+
+
+class NeighborMax(Function):
+    """Y[i, f] = max over the neighbours j of i of X[j, f] (libgnna gnna_agg_reduce_ld_f32; a row without edges gives 0).
+    The forward records which edge supplied every element -- among equal values the one earliest in column_index -- and the
+    backward sends that element's gradient to that one source row (gnna_scatter_arg_ld_f32).  Unlike every sum operator of
+    this file, this backward does NOT assume that the graph's structure is symmetric."""
+
+    @staticmethod
+    def forward(ctx, X, inputInfo):
+        return _extreme_forward(0, ctx, X, inputInfo)
+
+    backward = staticmethod(_extreme_backward)
+
+
+class NeighborMin(Function):
+    """NeighborMax with the element-wise minimum; the same tie rule and the same backward (no symmetry assumed)."""
+
+    @staticmethod
+    def forward(ctx, X, inputInfo):
+        return _extreme_forward(1, ctx, X, inputInfo)
+
+    backward = staticmethod(_extreme_backward)
+
+
+class NeighborMean(Function):
+    """Y = diag(1 / max(count, 1)) A X: the mean over every row's neighbours (0 for a row without edges), composed from the
+    neighbor sum GNNA.SAG and a row scaling.  A is assumed symmetric, so backward is A (dY / count)."""
+
+    @staticmethod
+    def forward(ctx, X, inputInfo):
+        if X.dtype != torch.float32:
+            raise TypeError(f"NeighborMean: float32 features only (got {X.dtype})")
+        ctx.graph, ctx.knobs = _graph_args(inputInfo), _knobs(inputInfo)
+        inv = inputInfo.inv_row_counts()
+        ctx.save_for_backward(inv)
+        return GNNA.SAG(X.contiguous(), *ctx.graph, *ctx.knobs).mul_(inv.unsqueeze(1))
+
+    @staticmethod
+    def backward(ctx, dY):
+        inv, = ctx.saved_tensors
+        return GNNA.SAG(dY * inv.unsqueeze(1), *ctx.graph, *ctx.knobs), None
+
+
+class SAGEConv(Module):
+    """GraphSAGE layer: Y = X W_self + agg(X) W_neigh (+ b), agg the mean, the element-wise max or the element-wise min over
+    every node's neighbours.  Both weights are drawn like the other layers' (U(-1/sqrt(out), 1/sqrt(out))).
+    mean: when the layer narrows, X W_neigh is aggregated instead of X (the linear map commutes with the mean; the rule is
+    GINConv's).  max / min: the order is fixed -- aggregate, then multiply.  float32 only."""
+
+    _AGG = {"mean": NeighborMean, "max": NeighborMax, "min": NeighborMin}
+
+    def __init__(self, input_dim, output_dim, aggregator="mean", bias=False):
+        super().__init__()
+        if aggregator not in self._AGG:
+            raise ValueError(f"aggregator must be one of {sorted(self._AGG)} (got {aggregator!r})")
+        self.aggregator = aggregator
+        self.weights_self = Parameter(torch.empty(input_dim, output_dim))
+        self.weights_neigh = Parameter(torch.empty(input_dim, output_dim))
+        self.bias = Parameter(torch.empty(output_dim)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        bound = 1.0 / math.sqrt(self.weights_self.size(1))
+        with torch.no_grad():
+            self.weights_self.uniform_(-bound, bound)
+            self.weights_neigh.uniform_(-bound, bound)
+            if self.bias is not None:
+                self.bias.zero_()
+
+    def _update_first(self, X) -> bool:
+        if self.aggregator != "mean":
+            return False
+        fin, fout = _row_units(self.weights_neigh.size(0)), _row_units(self.weights_neigh.size(1))
+        needs_dx = X.requires_grad and torch.is_grad_enabled()
+        return 2 * fout < (2 * fin if needs_dx else fin)
+
+    def forward(self, X, inputInfo, relu=False):
+        if X.dtype != torch.float32 or _x16_dtype(X) is not None:
+            raise TypeError("SAGEConv computes in float32 only: 16-bit features and torch.autocast are not supported "
+                            f"(got {X.dtype}{', inside torch.autocast' if X.dtype == torch.float32 else ''})")
+        agg = self._AGG[self.aggregator]
+        if self._update_first(X):
+            N = agg.apply(torch.mm(X, self.weights_neigh), inputInfo)
+        else:
+            N = torch.mm(agg.apply(X, inputInfo), self.weights_neigh)
+        Y = torch.addmm(N, X, self.weights_self)
+        if self.bias is not None:
+            Y = Y + self.bias
+        return torch.relu(Y) if relu else Y
+
+
 # ---- edge-valued aggregation, edge softmax, GAT ----------------------------------------------------------------------
 
 def _heads_of(w):

@@ -273,6 +273,43 @@ GNNA_API int gnna_agg_ld_x16(int mode, int in_type, const void *input, int64_t l
         unsigned flags, void *stream);
 GNNA_API int gnna_prepare_x16(int64_t num_in_rows, int64_t num_out_rows, const int *dims, int num_dims, void *stream);
 
+/* Element-wise max / min over the neighbours of every destination row, with the edge that supplied each element:
+ *   out[i, f] = max (GNNA_REDUCE_MAX) or min (GNNA_REDUCE_MIN) over the edges e of row i of input[column_index[e], f];
+ *   arg[i, f] = the position e in column_index that supplied it (arg may be NULL: values only).
+ * Values are exact: a max does not round, so `out` is bit-identical to an fp32 reference for every partition, schedule and run.
+ * Ties: arg is the SMALLEST edge position among the edges that hold the extreme value -- with a CSR whose column ids are
+ *   unique and ascending within a row, also the smallest source id.  arg is therefore reproducible too, for every partition,
+ *   and the call works unchanged under gnna_tuning.deterministic = 1.
+ * Rows without edges, and rows that no neighbor-group names: out = 0, arg = -1.  Every element of the `dim` columns of out and
+ *   arg of all num_out_rows rows is written.
+ * Partitions: whatever gnna_agg_ld_f32 accepts -- rows split over many groups, groups in any order, part2Node in any order,
+ *   groups with part_pointers[p + 1] < part_pointers[p] taken as empty, column ids outside [0, num_in_rows) skipped.
+ *   num_in_rows != num_out_rows, any dim >= 1, leading dimensions (elements between row starts) >= dim on input, out and arg.
+ * flags: GNNA_EPILOGUE_RELU gives max(out, 0) and leaves arg as it is; GNNA_ACCUMULATE: GNNA_ERR_UNSUPPORTED.  op other than the
+ *   two above, dim < 1, a leading dimension < dim: GNNA_ERR_INVALID_ARGUMENT.
+ * NaN and signed zero: elements are compared by the TOTAL order of their bit patterns (IEEE totalOrder), not by `<`:
+ *   -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN.  So max prefers +0 to -0 (min the reverse), a NaN with a clear sign bit wins
+ *   every max and loses every min, a NaN with the sign bit set the reverse.  out holds the bits of the selected element
+ *   unchanged and arg points at exactly that element.
+ * No synchronisation, no plan.  The partial rows of different wavefronts meet in library scratch (num_out_rows x dim 64-bit
+ * keys, allocated on first use like every other library scratch; a captured call gets scratch of its capture) through 64-bit
+ * integer atomic maxima, and a small epilogue kernel writes out and arg.  Limits of one call as for gnna_agg_ld_f32. */
+#define GNNA_REDUCE_MAX 0
+#define GNNA_REDUCE_MIN 1
+GNNA_API int gnna_agg_reduce_ld_f32(int op, const float *input, int64_t ld_in, int64_t num_in_rows,
+        const int32_t *column_index, const int32_t *part_pointers, const int32_t *part2Node,
+        float *out, int64_t ld_out, int32_t *arg /* may be NULL */, int64_t ld_arg,
+        int64_t num_out_rows, int dim, int64_t num_parts, int partSize, unsigned flags, void *stream);
+
+/* Backward of the above: grad_in[column_index[arg[i, f]], f] += grad_out[i, f] for every arg[i, f] >= 0 (arg as written by
+ * gnna_agg_reduce_ld_f32 over the same column_index; a position whose column id is outside [0, num_in_rows) is skipped).
+ * grad_in [num_in_rows, dim] is cleared first unless flags has GNNA_ACCUMULATE.  num_out_rows x dim work, one float atomic per
+ * non-negative arg: the sums depend on arrival order, so with gnna_tuning.deterministic = 1 the call returns
+ * GNNA_ERR_UNSUPPORTED (as gnna_agg_ld_x16 does).  Makes no assumption about the structure of the graph. */
+GNNA_API int gnna_scatter_arg_ld_f32(const float *grad_out, int64_t ld_go, const int32_t *arg, int64_t ld_arg,
+        const int32_t *column_index, int64_t num_out_rows, float *grad_in, int64_t ld_gi, int64_t num_in_rows,
+        int dim, unsigned flags, void *stream);
+
 /* Edge softmax over the edges of every destination row, per head; scores are head-major [num_heads, num_edges]:
  *   probs[h, e] = exp(s[h, e] - max_row) / sum_row exp(s - max_row),  e in [row_pointers[i], row_pointers[i + 1]).
  * Backward: grad_scores[h, e] = probs[h, e] * (grad_probs[h, e] - sum_row probs * grad_probs).
