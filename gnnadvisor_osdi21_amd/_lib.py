@@ -49,7 +49,8 @@ EXPORTS = ("gnna_version", "gnna_build_id", "gnna_last_error", "gnna_count_parts
            "gnna_forget_graph", "gnna_agg_ld_f32", "gnna_preferred_ld", "gnna_device_cus", "gnna_host_threads",
            "gnna_reorder_community_csr_i32", "gnna_relabel_edges_i32", "gnna_relabel_csr_i32", "gnna_runtime_counters_ex", "gnna_forget_plans",
            "gnna_debug_untrusted_copies", "gnna_agg_edge_ld_f32", "gnna_edge_softmax_f32", "gnna_edge_softmax_backward_f32",
-           "gnna_reverse_edges_i32", "gnna_agg_ld_x16", "gnna_prepare_x16", "gnna_agg_reduce_ld_f32", "gnna_scatter_arg_ld_f32")
+           "gnna_reverse_edges_i32", "gnna_agg_ld_x16", "gnna_prepare_x16", "gnna_agg_reduce_ld_f32", "gnna_scatter_arg_ld_f32",
+           "gnna_gat_forward_f32", "gnna_gat_backward_f32")
 
 
 def load() -> ctypes.CDLL:
@@ -186,6 +187,15 @@ def load() -> ctypes.CDLL:
     L.gnna_scatter_arg_ld_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                           ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                           ctypes.c_uint, ctypes.c_void_p]
+    L.gnna_gat_forward_f32.restype = ctypes.c_int
+    L.gnna_gat_forward_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 6 + [
+        ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p]
+    L.gnna_gat_backward_f32.restype = ctypes.c_int
+    L.gnna_gat_backward_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4 + [
+        ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p]
     _lib = L
     return L
 
@@ -823,3 +833,59 @@ def scatter_arg_ld(grad_out, arg, column_index, num_in_rows, out=None, accumulat
         _check(load().gnna_scatter_arg_ld_f32(gp, ld_go, ap, ld_arg, column_index.data_ptr(), n_out, op_, ld_gi, int(num_in_rows),
                                               dim, ACCUMULATE if accumulate else 0, _stream(grad_out.device)))
     return out
+
+
+def _node_heads(t, n, what):
+    """[n, heads] contiguous float32 device tensor -> heads."""
+    assert t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == n and t.is_contiguous(), \
+        f"{what} must be a contiguous float32 [num_nodes, heads] tensor"
+    return t.shape[1]
+
+
+def gat_forward(H, el, er, row_pointers, column_index, part_pointers, part2Node, partSize=32, negative_slope=0.2, out=None,
+                lse=None, relu=False):
+    """gnna_gat_forward_f32: fused multi-head GAT attention.  H [N, heads * dim], el / er [N, heads] -> (out, lse) with
+    out[i, h] = sum_e alpha(e, h) H[col(e), h], alpha = exp(leaky_relu(el[i, h] + er[j, h]) - lse[i, h]); no per-edge tensor.
+    `H` and `out` may be row-strided views (stride(1) == 1): they are passed with their leading dimension."""
+    if not H.is_cuda:
+        raise GnnaError("GAT attention needs device tensors: there is no CPU path in libgnna")
+    hp, n, width, ld_h = _rows_view(H, "H")
+    heads = _node_heads(el, n, "el")
+    assert _node_heads(er, n, "er") == heads and heads >= 1 and width % heads == 0, "H must be [num_nodes, heads * dim]"
+    if out is None:
+        out = _fresh_output((n, width), H.device)
+    if lse is None:
+        lse = _fresh_output((n, heads), H.device)
+    op_, n_o, width_o, ld_out = _rows_view(out, "out")
+    assert n_o == n and width_o == width and _node_heads(lse, n, "lse") == heads
+    with torch.cuda.device(H.device):
+        _check(load().gnna_gat_forward_f32(hp, ld_h, el.data_ptr(), er.data_ptr(), row_pointers.data_ptr(), column_index.data_ptr(),
+                                           part_pointers.data_ptr(), part2Node.data_ptr(), float(negative_slope), op_, ld_out,
+                                           lse.data_ptr(), n, heads, width // heads, part2Node.numel(), int(partSize),
+                                           EPILOGUE_RELU if relu else 0, _stream(H.device)))
+    return out, lse
+
+
+def gat_backward(H, el, er, lse, Y, dY, row_pointers, column_index, part_pointers, part2Node, partSize=32, negative_slope=0.2,
+                 dH=None):
+    """gnna_gat_backward_f32: (dH, d_el, d_er) of gat_forward for the gradient dY of its output Y, on a graph whose structure
+    is symmetric (not checked here).  dH is the attention part only (sum alpha dY); strided H / Y / dY / dH as in gat_forward."""
+    if not H.is_cuda:
+        raise GnnaError("GAT attention needs device tensors: there is no CPU path in libgnna")
+    hp, n, width, ld_h = _rows_view(H, "H")
+    yp, n_y, width_y, ld_y = _rows_view(Y, "Y")
+    gp, n_g, width_g, ld_g = _rows_view(dY, "dY")
+    heads = _node_heads(el, n, "el")
+    assert _node_heads(er, n, "er") == heads and _node_heads(lse, n, "lse") == heads and width % heads == 0
+    assert (n_y, width_y) == (n, width) and (n_g, width_g) == (n, width), "Y and dY must have the shape of H"
+    if dH is None:
+        dH = _fresh_output((n, width), H.device)
+    dp, n_d, width_d, ld_d = _rows_view(dH, "dH")
+    assert (n_d, width_d) == (n, width)
+    d_el, d_er = _fresh_output((n, heads), H.device), _fresh_output((n, heads), H.device)
+    with torch.cuda.device(H.device):
+        _check(load().gnna_gat_backward_f32(hp, ld_h, el.data_ptr(), er.data_ptr(), lse.data_ptr(), yp, ld_y, gp, ld_g,
+                                            row_pointers.data_ptr(), column_index.data_ptr(), part_pointers.data_ptr(),
+                                            part2Node.data_ptr(), float(negative_slope), dp, ld_d, d_el.data_ptr(), d_er.data_ptr(),
+                                            n, heads, width // heads, part2Node.numel(), int(partSize), 0, _stream(H.device)))
+    return dH, d_el, d_er

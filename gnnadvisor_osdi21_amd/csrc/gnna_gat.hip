@@ -1,0 +1,591 @@
+// gnna_gat.hip -- fused multi-head GAT attention, forward and backward (gnna_gat_forward_f32 / gnna_gat_backward_f32).
+// CDNA4 / gfx950 only.  No counterpart in the reference (it has no attention layer).
+//
+// With lse[i, h] = logsumexp over the edges of row i of s = leaky_relu(el[i, h] + er[j, h]) known, the attention coefficient of
+// an edge i <- j is a function of node-sized values only,
+//     alpha(i, j, h) = exp(leaky_relu(el[i, h] + er[j, h]) - lse[i, h]),
+// so every pass computes it where it gathers the row and no buffer of the size of the edge list exists anywhere.
+//
+//   forward   (a) gat_lse_kernel: rows of the CSR, a SEG-lane segment of a wavefront per row (the whole block for long rows, after
+//                 the short ones), online (max, sum) per head; reads the column ids once and gathers er[j, 0:heads).  One writer
+//                 per row, fixed order, plain stores: the same bits on every run.
+//             (b) gat_pull_kernel<SIDE_FWD>: out[i] = sum_e alpha * H[col(e)].
+//   backward  gat_pack_kernel: c[i, h] = <dY[i, h, :], Y[i, h, :]> (= sum_e alpha * dalpha of the row), packed with el and lse
+//                 into 16 bytes per (node, head) of library scratch;
+//             gat_pull_kernel<SIDE_BWD_DST>: row i pulls H[j], er[j]:              d_el[i, h] = sum_e dz
+//             gat_pull_kernel<SIDE_BWD_SRC>: row j pulls dY[i], (el, lse, c)[i]:   d_er[j, h] = sum_e dz, dH[j] = sum_e alpha * dY[i]
+//                 (the edges of row j stand for the edges j -> i: the structure must be symmetric)
+//             with dalpha = <dY[i, h, :], H[j, h, :]>, dz = alpha * (dalpha - c[i, h]) * (z > 0 ? 1 : negative_slope).
+//
+// gat_pull_kernel is the gather of gnna_x16.hip with another lane layout: a wavefront takes G consecutive neighbor-groups, merges
+// the groups of one destination row into a run of edges and walks the run 64 edges at a time -- one coalesced load of 64 ids,
+// then LPR wave-wide loads of 16 bytes per lane that bring 64 / LPR whole rows each.  A head of `dim` floats is covered by
+// LPH = next_pow2(ceil(dim / 4)) lanes and a row by LPR = LPH * (heads of a column block) <= 64 lanes, so a lane's head is fixed:
+// it needs one er value (or one 16-byte (el, lse, c) record) per gathered row, and the per-head dot product of the backward is
+// a sum over the LPH lanes of the head (DPP).  Rows wider than one wave-wide load are taken in column blocks of whole heads inside
+// the call.  dim % 4 != 0: the last lane of a head loads its 1..3 floats one by one; nothing is staged.  At the end of a run the
+// 64 / LPR partial rows meet by a butterfly and are ADDED with float atomics (correct for every partition gnna_agg_ld_f32
+// accepts, no validation pass), so the outputs are zero-filled first and there is no deterministic schedule for these passes.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+
+#include "gnna.h"
+#include "gnna_device.h"
+#include "gnna_internal.h"
+
+namespace gnna {
+namespace {
+
+typedef VecOf<4>::T VT;
+typedef VecOf<4>::M MT;
+
+constexpr int kSlotGatPack = 6;   // library scratch: (el, lse, c, 0) per (node, head) of a backward call
+constexpr int kLongIters = 8;     // lse pass: a row of more than SEG * 4 * kLongIters edges goes to the whole block
+constexpr int kMaxDim = 256;      // floats per head (LPH <= 64)
+
+enum { SIDE_FWD = 0, SIDE_BWD_DST = 1, SIDE_BWD_SRC = 2 };
+
+__device__ __forceinline__ float leaky(float z, float slope) { return z > 0.f ? z : z * slope; }
+
+// the first n4 (<= 4) floats at p, the others 0
+__device__ __forceinline__ VT load_piece(const float *__restrict__ p, int n4)
+{
+    if (n4 >= 4) return *reinterpret_cast<const MT *>(p);
+    VT v = (VT)(0.f);
+    if (n4 > 0) v[0] = p[0];
+    if (n4 > 1) v[1] = p[1];
+    if (n4 > 2) v[2] = p[2];
+    return v;
+}
+
+// sum over the LPH consecutive lanes of a head; result in every lane of the head
+template <int LPH>
+__device__ __forceinline__ float head_sum(float v)
+{
+    if constexpr (LPH == 1) return v;
+    else if constexpr (LPH == 2) return v + dpp_move<0xB1>(v);      // quad_perm [1,0,3,2]
+    else return lane_group_sum<LPH>(v);
+}
+
+// sum over the 64 / LPR lanes that share lane % LPR (the partial rows of a wavefront); result in every lane
+template <int LPR>
+__device__ __forceinline__ float slots_sum(float v)
+{
+    v = slot_reduce<LPR>(v);                                        // strides 32 .. 4
+    if constexpr (LPR <= 2) v += dpp_move<0x4E>(v);                 // quad_perm [2,3,0,1]: stride 2
+    if constexpr (LPR <= 1) v += dpp_move<0xB1>(v);                 // quad_perm [1,0,3,2]: stride 1
+    return v;
+}
+
+// ---- (a) lse[i, h] ------------------------------------------------------------------------------------------------------
+
+struct MaxSum { float m, l; };
+
+__device__ __forceinline__ MaxSum ms_merge(MaxSum a, MaxSum b)
+{
+    const float m = fmaxf(a.m, b.m);
+    if (m == -INFINITY) return a;
+    const float fa = a.m == -INFINITY ? 0.f : expf(a.m - m);
+    const float fb = b.m == -INFINITY ? 0.f : expf(b.m - m);
+    return MaxSum{m, a.l * fa + b.l * fb};
+}
+
+// four scores enter together (-inf: no edge): one rescale of the running sum per step
+__device__ __forceinline__ MaxSum ms_add4(MaxSum a, const float x[4])
+{
+    const float mx = fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3]));
+    const float m = fmaxf(a.m, mx);
+    if (m == -INFINITY) return a;
+    float l = a.m == -INFINITY ? 0.f : a.l * expf(a.m - m);
+#pragma unroll
+    for (int k = 0; k < 4; k++) l += x[k] == -INFINITY ? 0.f : expf(x[k] - m);
+    return MaxSum{m, l};
+}
+
+// butterfly over the `w` lanes of a segment (a power of two <= 64)
+__device__ __forceinline__ MaxSum seg_reduce(MaxSum v, int w)
+{
+    for (int d = w >> 1; d > 0; d >>= 1) v = ms_merge(v, MaxSum{__shfl_xor(v.m, d), __shfl_xor(v.l, d)});
+    return v;
+}
+
+// One row [beg, end) swept by `nl` lanes (this one: index t), four edges per lane and step, HB heads from hb0 on.
+template <int HB>
+__device__ __forceinline__ void lse_row(const float *__restrict__ el_row, const float *__restrict__ er,
+                                        const int32_t *__restrict__ col, int64_t beg, int64_t end, int t, int nl, uint32_t N,
+                                        int heads, int hb0, float slope, MaxSum acc[HB])
+{
+    float eli[HB];
+#pragma unroll
+    for (int hh = 0; hh < HB; hh++) {
+        eli[hh] = hb0 + hh < heads ? el_row[hb0 + hh] : 0.f;
+        acc[hh] = MaxSum{-INFINITY, 0.f};
+    }
+    for (int64_t e = beg + t; e < end; e += (int64_t)nl * 4) {
+        int id[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int64_t ee = e + (int64_t)k * nl;
+            id[k] = ee < end ? col[ee] : -1;
+            if ((uint32_t)id[k] >= N) id[k] = -1;                  // an id outside the graph is skipped, in every pass alike
+        }
+#pragma unroll
+        for (int hh = 0; hh < HB; hh++) {
+            if (hb0 + hh < heads) {
+                float x[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+                    x[k] = id[k] >= 0 ? leaky(eli[hh] + er[(size_t)(uint32_t)id[k] * heads + hb0 + hh], slope) : -INFINITY;
+                acc[hh] = ms_add4(acc[hh], x);
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ float lse_of(MaxSum v) { return v.m == -INFINITY ? 0.f : v.m + logf(v.l); }
+
+// blockIdx.y: block of HB heads.  seg: lanes per row (4 .. 64, a power of two).
+template <int HB>
+__global__ void __launch_bounds__(kBlock)
+gat_lse_kernel(const float *__restrict__ el, const float *__restrict__ er, const int32_t *__restrict__ rp,
+               const int32_t *__restrict__ col, int64_t N, int heads, float slope, float *__restrict__ lse, int seg)
+{
+    constexpr int kMaxTile = kWavesPerBlock * (kWave / 4);
+    __shared__ int s_long[kMaxTile];
+    __shared__ int s_nlong;
+    __shared__ float s_red[2][kWavesPerBlock];
+    const int tid = threadIdx.x;
+    const int lane = tid & (kWave - 1);
+    const int wib = tid >> 6;
+    const int rpw = kWave / seg;                      // rows per wavefront
+    const int tile = kWavesPerBlock * rpw;
+    const int long_edges = seg * 4 * kLongIters;
+    const int hb0 = (int)blockIdx.y * HB;
+    if (tid == 0) s_nlong = 0;
+    __syncthreads();
+
+    const int64_t r0 = (int64_t)blockIdx.x * tile;
+    const int local = wib * rpw + lane / seg;
+    const int64_t row = r0 + local;
+    const int t = lane % seg;
+    int64_t beg = 0, end = 0;
+    if (row < N) { beg = rp[row]; end = rp[row + 1]; }
+    const bool is_long = end - beg > long_edges;
+    if (is_long && t == 0) s_long[atomicAdd(&s_nlong, 1)] = local;
+    // short rows (and rows without edges: lse = 0): the segment -- every lane of a segment takes the same branch
+    if (row < N && !is_long) {
+        MaxSum acc[HB];
+        lse_row<HB>(el + (size_t)row * heads, er, col, beg, end, t, seg, (uint32_t)N, heads, hb0, slope, acc);
+#pragma unroll
+        for (int hh = 0; hh < HB; hh++) {
+            const MaxSum v = seg_reduce(acc[hh], seg);
+            if (t == 0 && hb0 + hh < heads) lse[(size_t)row * heads + hb0 + hh] = lse_of(v);
+        }
+    }
+    __syncthreads();
+    // long rows: the whole block, one after the other (the list's order may vary; a row's result does not depend on it)
+    const int nlong = s_nlong;
+    for (int q = 0; q < nlong; q++) {
+        const int64_t rr = r0 + s_long[q];
+        MaxSum acc[HB];
+        lse_row<HB>(el + (size_t)rr * heads, er, col, rp[rr], rp[rr + 1], tid, kBlock, (uint32_t)N, heads, hb0, slope, acc);
+#pragma unroll
+        for (int hh = 0; hh < HB; hh++) {
+            const MaxSum v = seg_reduce(acc[hh], kWave);
+            __syncthreads();
+            if (lane == 0) { s_red[0][wib] = v.m; s_red[1][wib] = v.l; }
+            __syncthreads();
+            MaxSum r{s_red[0][0], s_red[1][0]};
+#pragma unroll
+            for (int w = 1; w < kWavesPerBlock; w++) r = ms_merge(r, MaxSum{s_red[0][w], s_red[1][w]});
+            if (tid == 0 && hb0 + hh < heads) lse[(size_t)rr * heads + hb0 + hh] = lse_of(r);
+        }
+    }
+}
+
+// ---- c[i, h] = <dY[i, h, :], Y[i, h, :]>, packed with el and lse ------------------------------------------------------------
+
+__global__ void __launch_bounds__(kBlock)
+gat_pack_kernel(const float *__restrict__ G, size_t ldg, const float *__restrict__ Y, size_t ldy, const float *__restrict__ el,
+                const float *__restrict__ lse, VT *__restrict__ pack, size_t N, int heads, int dim)
+{
+    const size_t n = N * (size_t)heads;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / (unsigned)heads, h = i - r * (unsigned)heads;
+        const float *g = G + r * ldg + h * (size_t)dim, *y = Y + r * ldy + h * (size_t)dim;
+        float c = 0.f;
+        for (int f = 0; f < dim; f++) c = __builtin_fmaf(g[f], y[f], c);
+        VT v;
+        v[0] = el[i]; v[1] = lse[i]; v[2] = c; v[3] = 0.f;
+        pack[i] = v;
+    }
+}
+
+// ---- the gather ----------------------------------------------------------------------------------------------------------
+
+struct GatArgs {
+    const float *own; size_t ld_own;      // the row's own features: dY (SIDE_BWD_DST), H (SIDE_BWD_SRC); unused forward
+    const float *gat; size_t ld_gat;      // the gathered rows: H (SIDE_FWD, SIDE_BWD_DST), dY (SIDE_BWD_SRC)
+    const float *el, *er, *lse;           // [N, heads]; el and lse: forward only
+    const VT *pack;                       // backward: (el, lse, c, 0) per (node, head)
+    const int32_t *col, *pp, *p2n;
+    float *out; size_t ld_out;            // out (SIDE_FWD), dH (SIDE_BWD_SRC): zero-filled, added to
+    float *dsc;                           // d_el (SIDE_BWD_DST), d_er (SIDE_BWD_SRC): [N, heads], zero-filled, added to
+    float slope;
+    int64_t P;
+    uint32_t N;
+    int heads, dim, G, xcd_remap;
+};
+
+template <int SIDE, int LOG_LPH, int LOG_LPR>
+__global__ void __launch_bounds__(kBlock)
+gat_pull_kernel(const GatArgs p)
+{
+    constexpr int LPH = 1 << LOG_LPH;             // lanes per head
+    constexpr int LPR = 1 << LOG_LPR;             // lanes per row (of a column block)
+    constexpr int HB = LPR / LPH;                 // heads per column block
+    constexpr int R = kWave / LPR;                // rows per wave-wide load
+    constexpr int U = LPR < 8 ? LPR : 8;          // row loads in flight per lane
+    const int lane = threadIdx.x & (kWave - 1);
+    const int sub = lane >> LOG_LPR, cl = lane & (LPR - 1);
+    const int hl = cl >> LOG_LPH, fl = (cl & (LPH - 1)) * 4;
+    // consecutive chunks on one XCD (workgroups go round the 8 XCDs): neighbouring rows share source rows in that L2
+    uint32_t vb = blockIdx.x;
+    if (p.xcd_remap) {
+        const uint32_t nb = gridDim.x, q = nb / kXcds, rem = nb % kXcds, x = vb % kXcds, i = vb / kXcds;
+        vb = x < rem ? x * (q + 1) + i : rem * (q + 1) + (x - rem) * q + i;
+    }
+    const int64_t chunk = (int64_t)vb * kWavesPerBlock + (threadIdx.x >> 6);
+    const int64_t g0 = chunk * p.G;
+    if (g0 >= p.P) return;
+    const int cnt = (int)(p.P - g0 < (int64_t)p.G ? p.P - g0 : (int64_t)p.G);
+    int s = 0, e = 0, r = -1;
+    if (lane < cnt) {
+        s = p.pp[g0 + lane];
+        e = p.pp[g0 + lane + 1];
+        r = p.p2n[g0 + lane];
+    }
+    // a group without edges, with a negative range or with a row outside the graph contributes nothing and ends the run
+    const bool bad = lane >= cnt || e <= s || s < 0 || (uint32_t)r >= p.N;
+    const int prev_r = __shfl_up(r, 1);
+    const int prev_bad = __shfl_up((int)bad, 1);
+    const bool first = lane == 0 || bad || prev_bad != 0 || r != prev_r;
+    unsigned long long starts = __ballot(first);
+    if (cnt < kWave) starts &= (1ull << cnt) - 1ull;
+    const int bad_i = bad ? 1 : 0;
+    const int heads = p.heads;
+
+    while (starts) {
+        const int a = __builtin_ctzll(starts);
+        starts &= starts - 1ull;
+        const int b = starts ? __builtin_ctzll(starts) : cnt;
+        if (__builtin_amdgcn_readlane(bad_i, a)) continue;
+        const int rs = __builtin_amdgcn_readlane(s, a);
+        const int re = __builtin_amdgcn_readlane(e, b - 1);
+        const uint32_t row = (uint32_t)__builtin_amdgcn_readlane(r, a);
+        if (re <= rs) continue;
+        for (int hb0 = 0; hb0 < heads; hb0 += HB) {
+            const int h = hb0 + hl;
+            const int n4 = h < heads ? p.dim - fl : 0;        // floats of this lane's piece (<= 0: the lane idles)
+            const bool ok = n4 > 0;
+            const size_t colf = (size_t)(ok ? h : 0) * p.dim + (ok ? fl : 0);
+            const size_t sidx = (size_t)row * heads + (ok ? h : 0);
+            // what the row itself brings
+            float el_i = 0.f, lse_i = 0.f, c_i = 0.f, er_j = 0.f;
+            VT ownv = (VT)(0.f);
+            if (ok) {
+                if constexpr (SIDE == SIDE_FWD) { el_i = p.el[sidx]; lse_i = p.lse[sidx]; }
+                if constexpr (SIDE == SIDE_BWD_DST) { const VT o = p.pack[sidx]; el_i = o[0]; lse_i = o[1]; c_i = o[2]; }
+                if constexpr (SIDE == SIDE_BWD_SRC) er_j = p.er[sidx];
+                if constexpr (SIDE != SIDE_FWD) ownv = load_piece(p.own + (size_t)row * p.ld_own + colf, n4);
+            }
+            VT acc = (VT)(0.f);
+            float dzs = 0.f;
+            for (int e0 = rs; e0 < re; e0 += kWave) {
+                const int nb = re - e0 < kWave ? re - e0 : kWave;
+                int id = -1;
+                if (lane < nb) {
+                    id = p.col[(int64_t)e0 + lane];
+                    if ((uint32_t)id >= p.N) id = -1;           // (an id outside the graph is skipped, never read)
+                }
+#pragma unroll
+                for (int u0 = 0; u0 < LPR; u0 += U) {
+                    if (u0 * R >= nb) break;
+                    VT v[U];
+                    VT rec[SIDE == SIDE_BWD_SRC ? U : 1];
+                    float sc[U];
+                    bool live[U];
+#pragma unroll
+                    for (int k = 0; k < U; k++) {
+                        const int idj = __shfl(id, (u0 + k) * R + sub);
+                        live[k] = idj >= 0 && ok;
+                        v[k] = (VT)(0.f);
+                        sc[k] = 0.f;
+                        if constexpr (SIDE == SIDE_BWD_SRC) rec[k] = (VT)(0.f);
+                        if (live[k]) {
+                            v[k] = load_piece(p.gat + (size_t)(uint32_t)idj * p.ld_gat + colf, n4);
+                            if constexpr (SIDE == SIDE_BWD_SRC) rec[k] = p.pack[(size_t)(uint32_t)idj * heads + h];
+                            else sc[k] = p.er[(size_t)(uint32_t)idj * heads + h];
+                        }
+                    }
+#pragma unroll
+                    for (int k = 0; k < U; k++) {
+                        float z, lse_e, c_e;
+                        if constexpr (SIDE == SIDE_BWD_SRC) { z = rec[k][0] + er_j; lse_e = rec[k][1]; c_e = rec[k][2]; }
+                        else { z = el_i + sc[k]; lse_e = lse_i; c_e = c_i; }
+                        float alpha = __expf(leaky(z, p.slope) - lse_e);
+                        alpha = live[k] ? alpha : 0.f;
+                        if constexpr (SIDE != SIDE_FWD) {
+                            const float part = (ownv[0] * v[k][0] + ownv[1] * v[k][1]) + (ownv[2] * v[k][2] + ownv[3] * v[k][3]);
+                            const float dalpha = head_sum<LPH>(part);
+                            dzs += alpha * (dalpha - c_e) * (z > 0.f ? 1.f : p.slope);
+                        }
+                        if constexpr (SIDE != SIDE_BWD_DST) {
+#pragma unroll
+                            for (int q = 0; q < 4; q++) acc[q] = __builtin_fmaf(alpha, v[k][q], acc[q]);
+                        }
+                    }
+                }
+            }
+            // ---- the R partial rows of the wavefront meet; the first slot adds them to the output ------------------------
+            if constexpr (SIDE != SIDE_BWD_DST) {
+                VT t;
+#pragma unroll
+                for (int q = 0; q < 4; q++) t[q] = slots_sum<LPR>(acc[q]);
+                if (sub == 0 && ok) {
+                    float *dst = p.out + (size_t)row * p.ld_out + colf;
+#pragma unroll
+                    for (int q = 0; q < 4; q++)
+                        if (q < n4) atomicAdd(dst + q, t[q]);
+                }
+            }
+            if constexpr (SIDE != SIDE_FWD) {
+                const float t = slots_sum<LPR>(dzs);
+                if (sub == 0 && ok && fl == 0) atomicAdd(p.dsc + sidx, t);
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kBlock)
+gat_relu_kernel(float *__restrict__ Y, size_t ld, size_t rows, int D)
+{
+    const size_t n = rows * (size_t)D;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / (unsigned)D, c = i - r * (unsigned)D;
+        if (Y[r * ld + c] < 0.f) Y[r * ld + c] = 0.f;
+    }
+}
+
+template <int SIDE, int LOG_LPH>
+void launch_pull_lpr(int log_lpr, dim3 grid, hipStream_t stream, const GatArgs &a)
+{
+#define GNNA_GAT_CASE(L)                                                                                                  \
+    case L:                                                                                                               \
+        if constexpr (L >= LOG_LPH) hipLaunchKernelGGL((gat_pull_kernel<SIDE, LOG_LPH, L>), grid, dim3(kBlock), 0, stream, a); \
+        break;
+    switch (log_lpr) {
+        GNNA_GAT_CASE(0) GNNA_GAT_CASE(1) GNNA_GAT_CASE(2) GNNA_GAT_CASE(3) GNNA_GAT_CASE(4) GNNA_GAT_CASE(5) GNNA_GAT_CASE(6)
+    }
+#undef GNNA_GAT_CASE
+}
+
+template <int SIDE>
+int launch_pull(DeviceState *ds, hipStream_t stream, GatArgs a, int partSize)
+{
+    if (a.P <= 0) return GNNA_OK;
+    int log_lph = 0;
+    while ((4 << log_lph) < a.dim) log_lph++;
+    int log_lpr = log_lph;
+    while (log_lpr < 6 && (1 << (log_lpr - log_lph)) < a.heads) log_lpr++;
+    // groups per wavefront: 64, fewer while that leaves compute units without a chunk
+    int G = std::max(1, std::min(kWave, 2048 / std::max(1, partSize)));     // about 2048 edges per wavefront at most
+    while (G > 1 && (a.P + G - 1) / G < (int64_t)ds->num_cus * 16) G >>= 1;
+    a.G = G;
+    const int64_t chunks = (a.P + G - 1) / G;
+    const int64_t blocks = (chunks + kWavesPerBlock - 1) / kWavesPerBlock;
+    if (blocks > 0x7fffffffll) return fail(GNNA_ERR_UNSUPPORTED, "GAT attention: %lld neighbor-groups in one call", (long long)a.P);
+    const dim3 grid((unsigned)blocks);
+    switch (log_lph) {
+    case 0: launch_pull_lpr<SIDE, 0>(log_lpr, grid, stream, a); break;
+    case 1: launch_pull_lpr<SIDE, 1>(log_lpr, grid, stream, a); break;
+    case 2: launch_pull_lpr<SIDE, 2>(log_lpr, grid, stream, a); break;
+    case 3: launch_pull_lpr<SIDE, 3>(log_lpr, grid, stream, a); break;
+    case 4: launch_pull_lpr<SIDE, 4>(log_lpr, grid, stream, a); break;
+    case 5: launch_pull_lpr<SIDE, 5>(log_lpr, grid, stream, a); break;
+    default: launch_pull_lpr<SIDE, 6>(log_lpr, grid, stream, a); break;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "GAT attention launch: %s", hipGetErrorString(e));
+    return GNNA_OK;
+}
+
+unsigned grid_for(size_t work_items, int num_cus)
+{
+    const size_t blocks = (work_items + kBlock - 1) / kBlock;
+    return (unsigned)std::max<size_t>(1, std::min<size_t>(blocks, (size_t)num_cus * 8));
+}
+
+int launch_lse(hipStream_t stream, const float *el, const float *er, const int32_t *rp, const int32_t *col, int64_t N,
+               int64_t avg, int heads, float slope, float *lse)
+{
+    // lanes per row: about a quarter of the average degree (every lane reads 4 edges per step), 4 .. 64
+    int seg = 4;
+    while (seg < kWave && (int64_t)seg * 4 < avg) seg <<= 1;
+    const int64_t tile = (int64_t)kWavesPerBlock * (kWave / seg);
+    const int64_t blocks = (N + tile - 1) / tile;
+    int hb = 1;
+    while (hb < 8 && hb < heads) hb <<= 1;
+    const dim3 grid((unsigned)blocks, (unsigned)((heads + hb - 1) / hb));
+    switch (hb) {
+    case 1: hipLaunchKernelGGL(gat_lse_kernel<1>, grid, dim3(kBlock), 0, stream, el, er, rp, col, N, heads, slope, lse, seg); break;
+    case 2: hipLaunchKernelGGL(gat_lse_kernel<2>, grid, dim3(kBlock), 0, stream, el, er, rp, col, N, heads, slope, lse, seg); break;
+    case 4: hipLaunchKernelGGL(gat_lse_kernel<4>, grid, dim3(kBlock), 0, stream, el, er, rp, col, N, heads, slope, lse, seg); break;
+    default: hipLaunchKernelGGL(gat_lse_kernel<8>, grid, dim3(kBlock), 0, stream, el, er, rp, col, N, heads, slope, lse, seg); break;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "GAT lse launch: %s", hipGetErrorString(e));
+    return GNNA_OK;
+}
+
+// what both entry points check alike
+int check_common(const char *what, int64_t num_nodes, int heads, int dim, int64_t num_parts, int partSize, unsigned flags,
+                 unsigned allowed_flags)
+{
+    if (flags & GNNA_ACCUMULATE) return fail(GNNA_ERR_UNSUPPORTED, "%s: GNNA_ACCUMULATE is not supported", what);
+    if (flags & ~allowed_flags) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", what, flags);
+    if (num_nodes < 0 || num_parts < 0 || heads < 1 || dim < 1)
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: bad size (num_nodes=%lld heads=%d dim=%d num_parts=%lld)", what,
+                    (long long)num_nodes, heads, dim, (long long)num_parts);
+    if (partSize <= 0) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: partSize must be positive (got %d)", what, partSize);
+    if (num_nodes >= ((int64_t)1 << 29))
+        return fail(GNNA_ERR_UNSUPPORTED, "%s: %lld rows in one call (at most 536870911): shard the rows", what, (long long)num_nodes);
+    if (dim > kMaxDim) return fail(GNNA_ERR_UNSUPPORTED, "%s: at most %d floats per head (got %d)", what, kMaxDim, dim);
+    if (heads > 64) return fail(GNNA_ERR_UNSUPPORTED, "%s: at most 64 heads (got %d)", what, heads);
+    gnna_tuning tune;
+    gnna_get_tuning(&tune);
+    // the gathered rows are added with float atomics: the order of the additions is not fixed
+    if (tune.deterministic == 1)
+        return fail(GNNA_ERR_UNSUPPORTED, "%s has no deterministic schedule (gnna_tuning.deterministic = 1): its rows are added "
+                                          "with float atomics", what);
+    return GNNA_OK;
+}
+
+bool bad_ld(int64_t ld, int64_t width) { return ld < width || ld >= ((int64_t)1 << 29); }
+
+}  // namespace
+}  // namespace gnna
+
+using namespace gnna;
+
+extern "C" {
+#pragma GCC visibility push(default)
+
+int gnna_gat_forward_f32(const float *H, int64_t ld_h, const float *el, const float *er, const int32_t *row_pointers,
+                         const int32_t *column_index, const int32_t *part_pointers, const int32_t *part2Node,
+                         float negative_slope, float *out, int64_t ld_out, float *lse, int64_t num_nodes, int heads, int dim,
+                         int64_t num_parts, int partSize, unsigned flags, void *stream_v)
+{
+    const char *what = "gnna_gat_forward_f32";
+    int rc = check_common(what, num_nodes, heads, dim, num_parts, partSize, flags, GNNA_ACCUMULATE | GNNA_EPILOGUE_RELU);
+    if (rc != GNNA_OK) return rc;
+    if (num_nodes == 0) return GNNA_OK;
+    const int64_t W = (int64_t)heads * dim;
+    if (bad_ld(ld_h, W) || bad_ld(ld_out, W))
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: row strides must be >= heads * dim and < 2^29 floats (ld_h=%lld ld_out=%lld)",
+                    what, (long long)ld_h, (long long)ld_out);
+    if (!H || !el || !er || !out || !lse || !row_pointers) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
+    if (num_parts > 0 && (!column_index || !part_pointers || !part2Node))
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null index pointer", what);
+    if (out == H || out == el || out == er || out == lse || lse == el || lse == er || lse == H)
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: an output must not alias an input or the other output", what);
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    DeviceState *ds = nullptr;
+    rc = get_device_state(&ds);
+    if (rc != GNNA_OK) return rc;
+    rc = launch_zero_fill(ds, stream, out, num_nodes, (int)W, ld_out);
+    if (rc != GNNA_OK) return rc;
+    if (num_parts == 0) return launch_zero_fill(ds, stream, lse, num_nodes, heads, heads);
+    gnna_tuning tune;
+    gnna_get_tuning(&tune);
+    apply_graph_hints(column_index, (int)W, &tune);
+    // edges per row, for the segment width of the lse pass only: the graph's hint, else what the groups can hold at most
+    const int64_t avg = tune.avg_degree > 0 ? tune.avg_degree : (num_parts * (int64_t)partSize + num_nodes - 1) / num_nodes;
+    rc = launch_lse(stream, el, er, row_pointers, column_index, num_nodes, avg, heads, negative_slope, lse);
+    if (rc != GNNA_OK) return rc;
+    GatArgs a{};
+    a.gat = H; a.ld_gat = (size_t)ld_h; a.el = el; a.er = er; a.lse = lse;
+    a.col = column_index; a.pp = part_pointers; a.p2n = part2Node; a.out = out; a.ld_out = (size_t)ld_out;
+    a.slope = negative_slope; a.P = num_parts; a.N = (uint32_t)num_nodes; a.heads = heads; a.dim = dim;
+    a.xcd_remap = tune.xcd_remap != 0 ? 1 : 0;
+    rc = launch_pull<SIDE_FWD>(ds, stream, a, partSize);
+    if (rc != GNNA_OK) return rc;
+    if (flags & GNNA_EPILOGUE_RELU) {
+        hipLaunchKernelGGL(gat_relu_kernel, dim3(grid_for((size_t)num_nodes * (size_t)W, ds->num_cus)), dim3(kBlock), 0, stream,
+                           out, (size_t)ld_out, (size_t)num_nodes, (int)W);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(GNNA_ERR_HIP, "%s: epilogue launch: %s", what, hipGetErrorString(e));
+    }
+    return GNNA_OK;
+}
+
+int gnna_gat_backward_f32(const float *H, int64_t ld_h, const float *el, const float *er, const float *lse, const float *Y,
+                          int64_t ld_y, const float *dY, int64_t ld_dy, const int32_t *row_pointers,
+                          const int32_t *column_index, const int32_t *part_pointers, const int32_t *part2Node,
+                          float negative_slope, float *dH, int64_t ld_dh, float *d_el, float *d_er, int64_t num_nodes,
+                          int heads, int dim, int64_t num_parts, int partSize, unsigned flags, void *stream_v)
+{
+    const char *what = "gnna_gat_backward_f32";
+    (void)row_pointers;     // both passes walk the neighbor-groups
+    int rc = check_common(what, num_nodes, heads, dim, num_parts, partSize, flags, GNNA_ACCUMULATE);
+    if (rc != GNNA_OK) return rc;
+    if (num_nodes == 0) return GNNA_OK;
+    const int64_t W = (int64_t)heads * dim;
+    if (bad_ld(ld_h, W) || bad_ld(ld_y, W) || bad_ld(ld_dy, W) || bad_ld(ld_dh, W))
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: row strides must be >= heads * dim and < 2^29 floats (ld_h=%lld ld_y=%lld "
+                    "ld_dy=%lld ld_dh=%lld)", what, (long long)ld_h, (long long)ld_y, (long long)ld_dy, (long long)ld_dh);
+    if (!H || !el || !er || !lse || !Y || !dY || !dH || !d_el || !d_er) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
+    if (num_parts > 0 && (!column_index || !part_pointers || !part2Node))
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null index pointer", what);
+    const void *ins[] = {H, el, er, lse, Y, dY};
+    const void *outs[] = {dH, d_el, d_er};
+    for (const void *o : outs)
+        for (const void *i : ins)
+            if (o == i) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: an output must not alias an input", what);
+    if (dH == d_el || dH == d_er || d_el == d_er) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: the outputs must not alias each other", what);
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    DeviceState *ds = nullptr;
+    rc = get_device_state(&ds);
+    if (rc != GNNA_OK) return rc;
+    rc = launch_zero_fill(ds, stream, dH, num_nodes, (int)W, ld_dh);
+    if (rc == GNNA_OK) rc = launch_zero_fill(ds, stream, d_el, num_nodes, heads, heads);
+    if (rc == GNNA_OK) rc = launch_zero_fill(ds, stream, d_er, num_nodes, heads, heads);
+    if (rc != GNNA_OK || num_parts == 0) return rc;
+    void *ws = nullptr;
+    rc = get_workspace(ds, stream, kSlotGatPack, ((size_t)num_nodes * heads * sizeof(VT) + 255) & ~(size_t)255, &ws);
+    if (rc != GNNA_OK) return rc;
+    VT *pack = static_cast<VT *>(ws);
+    hipLaunchKernelGGL(gat_pack_kernel, dim3(grid_for((size_t)num_nodes * heads, ds->num_cus)), dim3(kBlock), 0, stream, dY,
+                       (size_t)ld_dy, Y, (size_t)ld_y, el, lse, pack, (size_t)num_nodes, heads, dim);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "%s: pack launch: %s", what, hipGetErrorString(e));
+    gnna_tuning tune;
+    gnna_get_tuning(&tune);
+    GatArgs a{};
+    a.er = er; a.pack = pack; a.col = column_index; a.pp = part_pointers; a.p2n = part2Node;
+    a.slope = negative_slope; a.P = num_parts; a.N = (uint32_t)num_nodes; a.heads = heads; a.dim = dim;
+    a.xcd_remap = tune.xcd_remap != 0 ? 1 : 0;
+    // destination side: row i pulls H[j], er[j] -> d_el
+    a.own = dY; a.ld_own = (size_t)ld_dy; a.gat = H; a.ld_gat = (size_t)ld_h; a.dsc = d_el;
+    rc = launch_pull<SIDE_BWD_DST>(ds, stream, a, partSize);
+    if (rc != GNNA_OK) return rc;
+    // source side: row j pulls dY[i], (el, lse, c)[i] -> d_er, dH
+    a.own = H; a.ld_own = (size_t)ld_h; a.gat = dY; a.ld_gat = (size_t)ld_dy; a.dsc = d_er; a.out = dH; a.ld_out = (size_t)ld_dh;
+    return launch_pull<SIDE_BWD_SRC>(ds, stream, a, partSize);
+}
+
+#pragma GCC visibility pop
+}  // extern "C"

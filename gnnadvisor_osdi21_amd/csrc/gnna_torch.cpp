@@ -467,6 +467,95 @@ torch::Tensor edge_softmax_backward(const torch::Tensor &probs, const torch::Ten
     return gs;
 }
 
+// Fused multi-head GAT attention (gnna_gat_forward_f32 / gnna_gat_backward_f32): H [N, heads * dim], el / er [N, heads].  No
+// per-edge tensor is made.  H, Y and dY go through their leading dimension (copied only when the inner stride is not 1).
+static torch::Tensor gat_rows(const torch::Tensor &t, const char *what, int64_t n, int64_t width)
+{
+    CHECK_CUDA(t); CHECK_F32(t);
+    TORCH_CHECK(t.dim() == 2 && t.size(0) == n && t.size(1) == width, what, " must be [num_nodes, heads * dim]");
+    const bool rows_ok = (width <= 1 || t.stride(1) == 1) && (n <= 1 || t.stride(0) >= width);
+    return rows_ok ? t : t.contiguous();
+}
+
+static void gat_check_graph(const torch::Tensor &H, const torch::Tensor &row_pointers, const torch::Tensor &column_index,
+                            const torch::Tensor &part_pointers, const torch::Tensor &part2Node)
+{
+    CHECK_INPUT(row_pointers); CHECK_I32(row_pointers);
+    CHECK_INPUT(column_index); CHECK_I32(column_index);
+    CHECK_INPUT(part_pointers); CHECK_I32(part_pointers);
+    CHECK_INPUT(part2Node); CHECK_I32(part2Node);
+    TORCH_CHECK(row_pointers.dim() == 1 && row_pointers.size(0) == H.size(0) + 1, "row_pointers must be [num_nodes + 1]");
+    TORCH_CHECK(part_pointers.numel() == part2Node.numel() + 1, "part_pointers must be [num_parts + 1]");
+    TORCH_CHECK(row_pointers.device() == H.device() && column_index.device() == H.device() &&
+                part_pointers.device() == H.device() && part2Node.device() == H.device(), "H and the graph must be on one device");
+}
+
+static int gat_heads(const torch::Tensor &H, const torch::Tensor &el, const torch::Tensor &er)
+{
+    CHECK_INPUT(el); CHECK_F32(el); CHECK_INPUT(er); CHECK_F32(er);
+    TORCH_CHECK(H.dim() == 2, "H must be 2-D [num_nodes, heads * dim]");
+    TORCH_CHECK(el.dim() == 2 && el.size(0) == H.size(0) && el.size(1) >= 1 && er.sizes() == el.sizes(),
+                "el and er must be [num_nodes, heads]");
+    TORCH_CHECK(H.size(1) >= el.size(1) && H.size(1) % el.size(1) == 0, "H must be [num_nodes, heads * dim]");
+    TORCH_CHECK(el.device() == H.device() && er.device() == H.device(), "H, el and er must be on one device");
+    return (int)el.size(1);
+}
+
+std::tuple<torch::Tensor, torch::Tensor>
+gat_forward(const torch::Tensor &H_in, const torch::Tensor &el, const torch::Tensor &er, const torch::Tensor &row_pointers,
+            const torch::Tensor &column_index, const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize,
+            double negative_slope)
+{
+    const int heads = gat_heads(H_in, el, er);
+    const int64_t n = H_in.size(0), width = H_in.size(1);
+    const torch::Tensor H = gat_rows(H_in, "H", n, width);
+    gat_check_graph(H, row_pointers, column_index, part_pointers, part2Node);
+    auto ld_of = [&](const torch::Tensor &t) { return t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(t.size(1), t.stride(0)); };
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(H.device());
+    static const bool poison = std::getenv("GNNA_DEBUG_POISON") && std::atoi(std::getenv("GNNA_DEBUG_POISON")) != 0;
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    auto Y = poison ? torch::full({n, width}, nan, el.options()) : torch::empty({n, width}, el.options());
+    auto lse = poison ? torch::full({n, (int64_t)heads}, nan, el.options()) : torch::empty({n, (int64_t)heads}, el.options());
+    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+    int rc = gnna_gat_forward_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(),
+                                  row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
+                                  part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), (float)negative_slope,
+                                  Y.data_ptr<float>(), width, lse.data_ptr<float>(), n, heads, (int)(width / heads),
+                                  part2Node.size(0), partSize, 0u, stream);
+    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+    return std::make_tuple(Y, lse);
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
+gat_backward(const torch::Tensor &H_in, const torch::Tensor &el, const torch::Tensor &er, const torch::Tensor &lse,
+             const torch::Tensor &Y_in, const torch::Tensor &dY_in, const torch::Tensor &row_pointers,
+             const torch::Tensor &column_index, const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize,
+             double negative_slope)
+{
+    const int heads = gat_heads(H_in, el, er);
+    const int64_t n = H_in.size(0), width = H_in.size(1);
+    const torch::Tensor H = gat_rows(H_in, "H", n, width), Y = gat_rows(Y_in, "Y", n, width), dY = gat_rows(dY_in, "dY", n, width);
+    CHECK_INPUT(lse); CHECK_F32(lse);
+    TORCH_CHECK(lse.sizes() == el.sizes() && lse.device() == H.device(), "lse must be [num_nodes, heads] on H's device");
+    TORCH_CHECK(Y.device() == H.device() && dY.device() == H.device(), "H, Y and dY must be on one device");
+    gat_check_graph(H, row_pointers, column_index, part_pointers, part2Node);
+    auto ld_of = [&](const torch::Tensor &t) { return t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(t.size(1), t.stride(0)); };
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(H.device());
+    static const bool poison = std::getenv("GNNA_DEBUG_POISON") && std::atoi(std::getenv("GNNA_DEBUG_POISON")) != 0;
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    auto fresh = [&](int64_t cols) { return poison ? torch::full({n, cols}, nan, el.options()) : torch::empty({n, cols}, el.options()); };
+    auto dH = fresh(width), d_el = fresh(heads), d_er = fresh(heads);
+    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+    int rc = gnna_gat_backward_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(), lse.data_ptr<float>(),
+                                   Y.data_ptr<float>(), ld_of(Y), dY.data_ptr<float>(), ld_of(dY),
+                                   row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
+                                   part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), (float)negative_slope,
+                                   dH.data_ptr<float>(), width, d_el.data_ptr<float>(), d_er.data_ptr<float>(), n, heads,
+                                   (int)(width / heads), part2Node.size(0), partSize, 0u, stream);
+    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+    return std::make_tuple(dH, d_el, d_er);
+}
+
 // SDDMM (gnna_sddmm_ld_f32): edge_out[e] = <A[row(e)], B[column_index[e]]>; A and B may be row-strided views.
 torch::Tensor sddmm(const torch::Tensor &A, const torch::Tensor &B, const torch::Tensor &column_index,
                     const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize)
@@ -761,6 +850,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           pybind11::arg("scores"), pybind11::arg("row_pointers"));
     m.def("edge_softmax_backward", &edge_softmax_backward, "gradient of edge_softmax: probs * (grad - sum_row probs * grad) (extension)",
           pybind11::arg("probs"), pybind11::arg("grad"), pybind11::arg("row_pointers"));
+    m.def("gat_forward", &gat_forward,
+          "fused multi-head GAT attention -> (Y, lse): Y[i, h] = sum_e exp(leaky_relu(el[i, h] + er[col(e), h]) - lse[i, h]) H[col(e), h] (extension)",
+          pybind11::arg("H"), pybind11::arg("el"), pybind11::arg("er"), pybind11::arg("row_pointers"), pybind11::arg("column_index"),
+          pybind11::arg("part_pointers"), pybind11::arg("part2Node"), pybind11::arg("partSize"), pybind11::arg("negative_slope") = 0.2);
+    m.def("gat_backward", &gat_backward,
+          "gradient of gat_forward on a graph whose structure is symmetric -> (dH, d_el, d_er); dH is the attention part only (extension)",
+          pybind11::arg("H"), pybind11::arg("el"), pybind11::arg("er"), pybind11::arg("lse"), pybind11::arg("Y"), pybind11::arg("dY"),
+          pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("part_pointers"), pybind11::arg("part2Node"),
+          pybind11::arg("partSize"), pybind11::arg("negative_slope") = 0.2);
     m.def("sddmm", &sddmm, "edge_out[e] = <A[row(e)], B[column_index[e]]> over the neighbor-group partition (extension)",
           pybind11::arg("A"), pybind11::arg("B"), pybind11::arg("column_index"), pybind11::arg("partPtr"), pybind11::arg("part2Node"),
           pybind11::arg("partSize"));

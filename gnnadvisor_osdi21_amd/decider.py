@@ -482,6 +482,18 @@ class inputProperty(object):
             cache["rev"] = _lib.reverse_edges(self.row_pointers, self.column_index).to(self.column_index.device)
         return cache["rev"]
 
+    def require_symmetric(self):
+        """Raises unless the graph's structure is symmetric (every edge i <- j has its j <- i); the answer is kept per
+        column_index.  Checked on the host by gnna_reverse_edges_i32 (a copy of the CSR to the host and one pass over it: about
+        a second at 1e8 edges); the map it builds there is dropped -- nothing of the size of the edge list stays on the device
+        (reverse_edges() keeps such a map, and a graph that has one is known to be symmetric).  Works on any graph bundle with
+        row_pointers and column_index (``inputProperty.require_symmetric(bundle)``)."""
+        cache = inputProperty._edge_arrays(self)
+        if "rev" not in cache and "symmetric" not in cache:
+            from . import _lib
+            _lib.reverse_edges(self.row_pointers, self.column_index)
+            cache["symmetric"] = True
+
     def edge_rows(self):
         """int32 [nnz] on the graph's device: the destination row of every edge (built once per column_index)."""
         cache = self._edge_arrays()

@@ -55,6 +55,9 @@ def build_parser():
     p.add_argument('--tune_gemm', default='False', **tf,
                    help="True: let PyTorch's TunableOp time the rocBLAS / hipBLASLt solutions for the layer GEMMs at "
                         "first use (X W and G W^T run 1.3-2x faster; costs 1-2 minutes of set-up, MI355X addition)")
+    p.add_argument('--fused_attention', default='False', **tf,
+                   help="True: --model gat runs both layers on the fused attention kernels (GATConv(fused=True): alpha is made "
+                        "from node-sized values where the rows are gathered, no per-edge tensor; MI355X addition)")
     p.add_argument('--policy', type=str, default='mi355x', choices=['mi355x', 'compat'], help="Decider policy")
     p.add_argument('--force_rabbit', default='False', **tf,
                    help="True: with --enable_rabbit True in auto mode, renumber even when the mi355x cost gate says the run is "
@@ -87,6 +90,8 @@ def main(argv=None, capture=None):
         raise SystemExit("--single_spmm / --verify_spmm run the float32 entry: use --dtype float32")
     if args.heads < 1:
         raise SystemExit("--heads must be >= 1")
+    if flag(args.fused_attention) and args.model != 'gat':
+        raise SystemExit("--fused_attention True selects the fused GAT attention: run it with --model gat (got --model %s)" % args.model)
     assert torch.cuda.is_available(), "requires an MI355X GPU: there is no CPU path"
     device = torch.device('cuda')
     if flag(args.tune_gemm):
@@ -197,11 +202,13 @@ def main(argv=None, capture=None):
                 x = self.conv2(x, inputInfo.set_hidden())
                 return F.log_softmax(x.float(), dim=1)
     elif args.model == 'gat':
+        fused = flag(args.fused_attention)
+
         class Net(torch.nn.Module):
             def __init__(self):
                 super().__init__()
-                self.conv1 = GATConv(dataset.num_features, args.hidden, heads=args.heads, concat=True)
-                self.conv2 = GATConv(args.hidden * args.heads, dataset.num_classes, heads=1)
+                self.conv1 = GATConv(dataset.num_features, args.hidden, heads=args.heads, concat=True, fused=fused)
+                self.conv2 = GATConv(args.hidden * args.heads, dataset.num_classes, heads=1, fused=fused)
 
             def forward(self):
                 x = F.elu(self.conv1(dataset.x, inputInfo.set_input()))

@@ -469,15 +469,55 @@ class EdgeSoftmax(Function):
         return GNNA.edge_softmax_backward(p, dp.contiguous(), rp), None
 
 
+class GATAttention(Function):
+    """The attention of a GAT layer in one fused call per direction (libgnna gnna_gat_forward_f32 / gnna_gat_backward_f32):
+    ``GATAttention.apply(H, el, er, inputInfo, negative_slope) -> Y`` with H [N, heads * F], el / er [N, heads] and
+    Y[i, h] = sum_e alpha(e, h) H[col(e), h], alpha = softmax over row i of leaky_relu(el[i, h] + er[col(e), h]).  alpha is
+    computed from el, er and the saved log-sum-exp of every row wherever a kernel gathers a row: no [nnz] tensor is made, saved
+    or cached (saved: H, el, er, lse, Y -- all node-sized), and all heads run in one call.  The gradient of H returned here is the
+    attention part (sum alpha dY); the paths through el and er are autograd's.
+
+    The backward reads row j's edges as the edges j -> i, so before its first backward on a graph it establishes that the
+    structure is symmetric and raises otherwise (``decider.inputProperty.require_symmetric``): once per column_index, on the host -- a
+    copy of the CSR to the host and a pass of gnna_reverse_edges_i32 over it, about a second at 1e8 edges; only the answer is
+    kept, nothing of the size of the edge list stays on the device."""
+
+    @staticmethod
+    def forward(ctx, H, el, er, inputInfo, negative_slope):
+        info = inputInfo
+        el, er = el.contiguous(), er.contiguous()
+        Y, lse = GNNA.gat_forward(H, el, er, info.row_pointers, info.column_index, info.partPtr, info.part2Node, info.partSize,
+                                  float(negative_slope))
+        ctx.info, ctx.negative_slope = info, float(negative_slope)
+        ctx.save_for_backward(H, el, er, lse, Y)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        H, el, er, lse, Y = ctx.saved_tensors
+        info = ctx.info
+        if not any(ctx.needs_input_grad[:3]):
+            return None, None, None, None, None
+        from .decider import inputProperty
+        inputProperty.require_symmetric(info)    # raises on a structure that is not symmetric (answer cached per column_index)
+        dH, d_el, d_er = GNNA.gat_backward(H, el, er, lse, Y, dY, info.row_pointers, info.column_index, info.partPtr,
+                                           info.part2Node, info.partSize, ctx.negative_slope)
+        need = ctx.needs_input_grad
+        return (dH if need[0] else None, d_el if need[1] else None, d_er if need[2] else None, None, None)
+
+
 class GATConv(Module):
     """Additive graph attention (GAT): H = X W; per head h, s[e] = leaky_relu(<H_h[row(e)], a_l[h]> + <H_h[col(e)], a_r[h]>),
     alpha = edge softmax of s over every row, Y_h = A_alpha H_h.  Heads are concatenated (concat=True, [N, heads * out]) or
     averaged ([N, out]).  The scores are nnz-sized elementwise torch work; softmax and aggregation are libgnna kernels.
-    Needs the graph's structure to be symmetric (the backward gathers through the reverse-edge map)."""
+    Needs the graph's structure to be symmetric (the backward gathers through the reverse-edge map).
+    fused=True: the attention runs on GATAttention instead -- the same function, with alpha made from node-sized values inside
+    the gathers: no per-edge tensor, one call for all heads."""
 
-    def __init__(self, input_dim, output_dim, heads=1, concat=True, negative_slope=0.2):
+    def __init__(self, input_dim, output_dim, heads=1, concat=True, negative_slope=0.2, fused=False):
         super().__init__()
         self.heads, self.out_dim, self.concat, self.negative_slope = int(heads), int(output_dim), bool(concat), float(negative_slope)
+        self.fused = bool(fused)
         self.weights = Parameter(torch.empty(input_dim, self.heads * self.out_dim))
         self.att_l = Parameter(torch.empty(self.heads, self.out_dim))
         self.att_r = Parameter(torch.empty(self.heads, self.out_dim))
@@ -496,10 +536,13 @@ class GATConv(Module):
         Hh = H.view(n, self.heads, self.out_dim)
         el = (Hh * self.att_l).sum(-1)          # [N, heads]: destination side
         er = (Hh * self.att_r).sum(-1)          # source side
-        rows, ci = inputInfo.edge_rows(), inputInfo.column_index
-        s = torch.nn.functional.leaky_relu(el.index_select(0, rows) + er.index_select(0, ci), self.negative_slope)
-        alpha = EdgeSoftmax.apply(s.t().contiguous(), inputInfo.row_pointers)      # [heads, nnz]
-        Y = EdgeWeightedAggregate.apply(H, alpha, inputInfo)
+        if self.fused:
+            Y = GATAttention.apply(H, el, er, inputInfo, self.negative_slope)
+        else:
+            rows, ci = inputInfo.edge_rows(), inputInfo.column_index
+            s = torch.nn.functional.leaky_relu(el.index_select(0, rows) + er.index_select(0, ci), self.negative_slope)
+            alpha = EdgeSoftmax.apply(s.t().contiguous(), inputInfo.row_pointers)      # [heads, nnz]
+            Y = EdgeWeightedAggregate.apply(H, alpha, inputInfo)
         if self.concat or self.heads == 1:
             return Y
         return Y.view(n, self.heads, self.out_dim).mean(1)

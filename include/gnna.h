@@ -320,6 +320,40 @@ GNNA_API int gnna_edge_softmax_backward_f32(const float *probs, const float *gra
         const int32_t *row_pointers, int64_t num_rows, int64_t num_edges, int num_heads,
         float *grad_scores, void *stream);
 
+/* Fused multi-head GAT attention (gnna_gat.hip): the attention coefficient of an edge i <- j,
+ *   alpha(i, j, h) = exp(leaky_relu(el[i, h] + er[j, h], negative_slope) - lse[i, h]),  lse[i, h] = logsumexp over the edges of row i,
+ * is computed from node-sized values wherever a pass gathers a row: no buffer of the size of the edge list is read, written or
+ * allocated, all heads run in one call and every pass reads column_index once (once per column block of whole heads when
+ * heads * dim exceeds one wave-wide load of 256 floats; the lse pass once per 8 heads).
+ *   H, out, Y, dY, dH: [num_nodes, heads * dim] fp32 with leading dimensions in floats (>= heads * dim); el, er, lse, d_el, d_er:
+ *   contiguous [num_nodes, heads].  Square graph: num_nodes destination = source rows.  The partition arguments are the output of
+ *   gnna_build_part_i32 for row_pointers (the lse pass walks the rows, the gathers walk the neighbor-groups); column ids outside
+ *   [0, num_nodes) are skipped in every pass alike.
+ * forward:  out[i, h dim + f] = sum_{e in row i} alpha(e, h) * H[col(e), h dim + f], and lse.  A row without edges: out = 0, lse = 0.
+ *   The row maximum is subtracted before any exponential: finite inputs give finite outputs.  lse is computed without atomics,
+ *   by one writer per row in a fixed order: the same bits on every run.  flags: GNNA_EPILOGUE_RELU (out = max(out, 0)).
+ * backward (Y = the forward's out, dY = its gradient; the STRUCTURE of the graph must be symmetric -- the edges of row j stand for
+ *   the edges j -> i; the caller checks, gnna_reverse_edges_i32 does): with c[i, h] = <dY[i, h, :], Y[i, h, :]> (computed inside
+ *   the call, library scratch of num_nodes x heads x 16 bytes), z = el[i, h] + er[j, h], dalpha = <dY[i, h, :], H[j, h, :]> and
+ *   dz = alpha * (dalpha - c[i, h]) * (z > 0 ? 1 : negative_slope):
+ *     d_el[i, h] = sum_{j in row i} dz,  d_er[j, h] = sum_{i in row j} dz,  dH[j, h, :] = sum_{i in row j} alpha * dY[i, h, :].
+ *   dH is the attention part only: the terms through el = <H, a_l> and er = <H, a_r> are the caller's (autograd).  A row without
+ *   edges: d_el = d_er = 0, dH = 0.  flags: none.
+ * Both: GNNA_ACCUMULATE: GNNA_ERR_UNSUPPORTED.  The gathered rows are added with float atomics (any partition gnna_agg_ld_f32
+ *   accepts is correct, no validation pass, no plan, no synchronisation), so with gnna_tuning.deterministic = 1 the calls return
+ *   GNNA_ERR_UNSUPPORTED, as gnna_agg_ld_x16 does.  heads <= 64 and dim <= 256 (GNNA_ERR_UNSUPPORTED beyond), otherwise the limits
+ *   of gnna_agg_ld_f32.  Bad sizes, null pointers, outputs that alias an input or each other: GNNA_ERR_INVALID_ARGUMENT.  Scratch is
+ *   allocated on first use like every other library scratch (a captured call gets its capture's own). */
+GNNA_API int gnna_gat_forward_f32(const float *H, int64_t ld_h, const float *el, const float *er,
+        const int32_t *row_pointers, const int32_t *column_index, const int32_t *part_pointers, const int32_t *part2Node,
+        float negative_slope, float *out, int64_t ld_out, float *lse, int64_t num_nodes, int heads, int dim,
+        int64_t num_parts, int partSize, unsigned flags, void *stream);
+GNNA_API int gnna_gat_backward_f32(const float *H, int64_t ld_h, const float *el, const float *er, const float *lse,
+        const float *Y, int64_t ld_y, const float *dY, int64_t ld_dy,
+        const int32_t *row_pointers, const int32_t *column_index, const int32_t *part_pointers, const int32_t *part2Node,
+        float negative_slope, float *dH, int64_t ld_dh, float *d_el, float *d_er, int64_t num_nodes, int heads, int dim,
+        int64_t num_parts, int partSize, unsigned flags, void *stream);
+
 /* Reverse-edge map of a CSR whose structure is symmetric (host pointers): rev[e] is the position of the edge col(e) -> row(e)
  * that matches e; the k-th (i, j) of row i pairs with the k-th (j, i) of row j (positions in increasing order), a self loop
  * may pair with itself, rows need not be sorted.  gnna_host_threads() threads; the result does not depend on their number.
