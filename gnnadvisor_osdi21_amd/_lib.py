@@ -50,7 +50,8 @@ EXPORTS = ("gnna_version", "gnna_build_id", "gnna_last_error", "gnna_count_parts
            "gnna_reorder_community_csr_i32", "gnna_relabel_edges_i32", "gnna_relabel_csr_i32", "gnna_runtime_counters_ex", "gnna_forget_plans",
            "gnna_debug_untrusted_copies", "gnna_agg_edge_ld_f32", "gnna_edge_softmax_f32", "gnna_edge_softmax_backward_f32",
            "gnna_reverse_edges_i32", "gnna_agg_ld_x16", "gnna_prepare_x16", "gnna_agg_reduce_ld_f32", "gnna_scatter_arg_ld_f32",
-           "gnna_gat_forward_f32", "gnna_gat_backward_f32")
+           "gnna_gat_forward_f32", "gnna_gat_backward_f32", "gnna_gat_backward_dir_f32", "gnna_transpose_csr_i32",
+           "gnna_count_parts_device_i32", "gnna_build_part_device_i32")
 
 
 def load() -> ctypes.CDLL:
@@ -196,6 +197,19 @@ def load() -> ctypes.CDLL:
                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4 + [
         ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
         ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p]
+    L.gnna_gat_backward_dir_f32.restype = ctypes.c_int
+    L.gnna_gat_backward_dir_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64] + (
+        [ctypes.c_void_p] * 4 + [ctypes.c_int64]) * 2 + [
+        ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p]
+    L.gnna_transpose_csr_i32.restype = ctypes.c_int
+    L.gnna_transpose_csr_i32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 4
+    L.gnna_count_parts_device_i32.restype = ctypes.c_int64
+    L.gnna_count_parts_device_i32.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+    L.gnna_build_part_device_i32.restype = ctypes.c_int
+    L.gnna_build_part_device_i32.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_int64, ctypes.c_void_p]
     _lib = L
     return L
 
@@ -867,9 +881,11 @@ def gat_forward(H, el, er, row_pointers, column_index, part_pointers, part2Node,
 
 
 def gat_backward(H, el, er, lse, Y, dY, row_pointers, column_index, part_pointers, part2Node, partSize=32, negative_slope=0.2,
-                 dH=None):
+                 dH=None, transposed=None):
     """gnna_gat_backward_f32: (dH, d_el, d_er) of gat_forward for the gradient dY of its output Y, on a graph whose structure
-    is symmetric (not checked here).  dH is the attention part only (sum alpha dY); strided H / Y / dY / dH as in gat_forward."""
+    is symmetric (not checked here).  dH is the attention part only (sum alpha dY); strided H / Y / dY / dH as in gat_forward.
+    transposed = (t_row_pointers, t_column_index, t_part_pointers, t_part2Node) of `transpose_csr` / `build_part_device` at the
+    same partSize: gnna_gat_backward_dir_f32, exact on a directed graph."""
     if not H.is_cuda:
         raise GnnaError("GAT attention needs device tensors: there is no CPU path in libgnna")
     hp, n, width, ld_h = _rows_view(H, "H")
@@ -883,9 +899,78 @@ def gat_backward(H, el, er, lse, Y, dY, row_pointers, column_index, part_pointer
     dp, n_d, width_d, ld_d = _rows_view(dH, "dH")
     assert (n_d, width_d) == (n, width)
     d_el, d_er = _fresh_output((n, heads), H.device), _fresh_output((n, heads), H.device)
+    if transposed is not None:
+        t_rp, t_ci, t_pp, t_p2n = transposed
+        for t in (column_index, part_pointers, part2Node, t_rp, t_ci, t_pp, t_p2n):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.device == H.device, \
+                "the graph and its transpose must be contiguous int32 tensors on H's device"
+        assert t_rp.numel() == n + 1 and t_pp.numel() == t_p2n.numel() + 1, "transposed: [N + 1] row pointers, [P + 1] / [P] partition"
+        with torch.cuda.device(H.device):
+            _check(load().gnna_gat_backward_dir_f32(hp, ld_h, el.data_ptr(), er.data_ptr(), lse.data_ptr(), yp, ld_y, gp, ld_g,
+                                                    row_pointers.data_ptr(), column_index.data_ptr(), part_pointers.data_ptr(),
+                                                    part2Node.data_ptr(), part2Node.numel(), t_rp.data_ptr(), t_ci.data_ptr(),
+                                                    t_pp.data_ptr(), t_p2n.data_ptr(), t_p2n.numel(), float(negative_slope), dp, ld_d,
+                                                    d_el.data_ptr(), d_er.data_ptr(), n, heads, width // heads, int(partSize), 0,
+                                                    _stream(H.device)))
+        return dH, d_el, d_er
     with torch.cuda.device(H.device):
         _check(load().gnna_gat_backward_f32(hp, ld_h, el.data_ptr(), er.data_ptr(), lse.data_ptr(), yp, ld_y, gp, ld_g,
                                             row_pointers.data_ptr(), column_index.data_ptr(), part_pointers.data_ptr(),
                                             part2Node.data_ptr(), float(negative_slope), dp, ld_d, d_el.data_ptr(), d_er.data_ptr(),
                                             n, heads, width // heads, part2Node.numel(), int(partSize), 0, _stream(H.device)))
     return dH, d_el, d_er
+
+
+def _device_i32(t, what):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise GnnaError(f"{what} must be a device tensor: the builder runs on the GPU (the host builders take host tensors)")
+    assert t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous(), f"{what} must be a contiguous 1-D int32 tensor"
+    return t
+
+
+def transpose_csr(row_pointers, column_index, num_in_rows=None, want_perm=True):
+    """gnna_transpose_csr_i32 (device): the CSR of A^T for device row_pointers [num_out_rows + 1] / column_index [nnz] ->
+    (t_row_pointers [num_in_rows + 1], t_column_index [nnz], t_perm [nnz] or None).  Row j lists the rows i of the edges i <- j in
+    increasing position e, t_perm[p] = e (= numpy.argsort(column_index, kind="stable")); ids outside [0, num_in_rows) are dropped:
+    t_row_pointers[-1] edges are kept and both arrays are -1 behind them.  num_in_rows defaults to num_out_rows.  Synchronises
+    the current stream; refuses to run inside a stream capture."""
+    rp, ci = _device_i32(row_pointers, "row_pointers"), _device_i32(column_index, "column_index")
+    assert rp.numel() >= 1 and ci.device == rp.device, "row_pointers must be [num_out_rows + 1], on column_index's device"
+    n_out = rp.numel() - 1
+    n_in = n_out if num_in_rows is None else int(num_in_rows)
+    assert n_in >= 0, "num_in_rows must not be negative"
+    nnz = ci.numel()
+    t_rp = torch.empty(n_in + 1, dtype=torch.int32, device=rp.device)
+    t_ci = torch.empty(nnz, dtype=torch.int32, device=rp.device)
+    t_perm = torch.empty(nnz, dtype=torch.int32, device=rp.device) if want_perm else None
+    with torch.cuda.device(rp.device):
+        # (the library trusts row_pointers[num_out_rows] for the edge count: it must not exceed what column_index holds)
+        if n_out > 0 and int(rp[-1]) != nnz:
+            raise GnnaError(f"row_pointers[-1] = {int(rp[-1])} but column_index holds {nnz} ids")
+        _check(load().gnna_transpose_csr_i32(rp.data_ptr(), _ptr(ci), n_out, n_in, t_rp.data_ptr(), _ptr(t_ci), _ptr(t_perm),
+                                             _stream(rp.device)))
+    return t_rp, t_ci, t_perm
+
+
+def count_parts_device(partSize: int, indptr) -> int:
+    """gnna_count_parts_device_i32: count_parts for device row pointers (reads the count back: synchronises)."""
+    ip = _device_i32(indptr, "indptr")
+    assert ip.numel() >= 1
+    with torch.cuda.device(ip.device):
+        n = load().gnna_count_parts_device_i32(int(partSize), ip.data_ptr(), ip.numel() - 1, _stream(ip.device))
+    if n < 0:
+        _check(int(n))
+    return int(n)
+
+
+def build_part_device(partSize: int, indptr):
+    """gnna_build_part_device_i32: build_part for device row pointers -> (partPtr int32 [P + 1], part2Node int32 [P]) on the
+    same device, element for element what build_part gives for the same row pointers."""
+    ip = _device_i32(indptr, "indptr")
+    P = count_parts_device(partSize, ip)
+    pp = torch.empty(P + 1, dtype=torch.int32, device=ip.device)
+    p2n = torch.empty(P, dtype=torch.int32, device=ip.device)
+    with torch.cuda.device(ip.device):
+        _check(load().gnna_build_part_device_i32(int(partSize), ip.data_ptr(), ip.numel() - 1, pp.data_ptr(), _ptr(p2n), P,
+                                                 _stream(ip.device)))
+    return pp, p2n

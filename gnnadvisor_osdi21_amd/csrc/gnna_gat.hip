@@ -538,17 +538,34 @@ int gnna_gat_backward_f32(const float *H, int64_t ld_h, const float *el, const f
                           float negative_slope, float *dH, int64_t ld_dh, float *d_el, float *d_er, int64_t num_nodes,
                           int heads, int dim, int64_t num_parts, int partSize, unsigned flags, void *stream_v)
 {
+    // a symmetric structure is its own transpose
+    return gnna_gat_backward_dir_f32(H, ld_h, el, er, lse, Y, ld_y, dY, ld_dy, row_pointers, column_index, part_pointers, part2Node,
+                                     num_parts, row_pointers, column_index, part_pointers, part2Node, num_parts, negative_slope,
+                                     dH, ld_dh, d_el, d_er, num_nodes, heads, dim, partSize, flags, stream_v);
+}
+
+int gnna_gat_backward_dir_f32(const float *H, int64_t ld_h, const float *el, const float *er, const float *lse, const float *Y,
+                              int64_t ld_y, const float *dY, int64_t ld_dy, const int32_t *row_pointers,
+                              const int32_t *column_index, const int32_t *part_pointers, const int32_t *part2Node,
+                              int64_t num_parts, const int32_t *t_row_pointers, const int32_t *t_column_index,
+                              const int32_t *t_part_pointers, const int32_t *t_part2Node, int64_t t_num_parts,
+                              float negative_slope, float *dH, int64_t ld_dh, float *d_el, float *d_er, int64_t num_nodes,
+                              int heads, int dim, int partSize, unsigned flags, void *stream_v)
+{
     const char *what = "gnna_gat_backward_f32";
     (void)row_pointers;     // both passes walk the neighbor-groups
+    (void)t_row_pointers;
     int rc = check_common(what, num_nodes, heads, dim, num_parts, partSize, flags, GNNA_ACCUMULATE);
     if (rc != GNNA_OK) return rc;
+    if (t_num_parts < 0) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: bad size (t_num_parts=%lld)", what, (long long)t_num_parts);
     if (num_nodes == 0) return GNNA_OK;
     const int64_t W = (int64_t)heads * dim;
     if (bad_ld(ld_h, W) || bad_ld(ld_y, W) || bad_ld(ld_dy, W) || bad_ld(ld_dh, W))
         return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: row strides must be >= heads * dim and < 2^29 floats (ld_h=%lld ld_y=%lld "
                     "ld_dy=%lld ld_dh=%lld)", what, (long long)ld_h, (long long)ld_y, (long long)ld_dy, (long long)ld_dh);
     if (!H || !el || !er || !lse || !Y || !dY || !dH || !d_el || !d_er) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
-    if (num_parts > 0 && (!column_index || !part_pointers || !part2Node))
+    if ((num_parts > 0 && (!column_index || !part_pointers || !part2Node)) ||
+        (t_num_parts > 0 && (!t_column_index || !t_part_pointers || !t_part2Node)))
         return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null index pointer", what);
     const void *ins[] = {H, el, er, lse, Y, dY};
     const void *outs[] = {dH, d_el, d_er};
@@ -563,7 +580,7 @@ int gnna_gat_backward_f32(const float *H, int64_t ld_h, const float *el, const f
     rc = launch_zero_fill(ds, stream, dH, num_nodes, (int)W, ld_dh);
     if (rc == GNNA_OK) rc = launch_zero_fill(ds, stream, d_el, num_nodes, heads, heads);
     if (rc == GNNA_OK) rc = launch_zero_fill(ds, stream, d_er, num_nodes, heads, heads);
-    if (rc != GNNA_OK || num_parts == 0) return rc;
+    if (rc != GNNA_OK || (num_parts == 0 && t_num_parts == 0)) return rc;
     void *ws = nullptr;
     rc = get_workspace(ds, stream, kSlotGatPack, ((size_t)num_nodes * heads * sizeof(VT) + 255) & ~(size_t)255, &ws);
     if (rc != GNNA_OK) return rc;
@@ -582,7 +599,8 @@ int gnna_gat_backward_f32(const float *H, int64_t ld_h, const float *el, const f
     a.own = dY; a.ld_own = (size_t)ld_dy; a.gat = H; a.ld_gat = (size_t)ld_h; a.dsc = d_el;
     rc = launch_pull<SIDE_BWD_DST>(ds, stream, a, partSize);
     if (rc != GNNA_OK) return rc;
-    // source side: row j pulls dY[i], (el, lse, c)[i] -> d_er, dH
+    // source side: row j pulls dY[i], (el, lse, c)[i] -> d_er, dH -- over the edges j -> i, the rows of the transposed structure
+    a.col = t_column_index; a.pp = t_part_pointers; a.p2n = t_part2Node; a.P = t_num_parts;
     a.own = H; a.ld_own = (size_t)ld_h; a.gat = dY; a.ld_gat = (size_t)ld_dy; a.dsc = d_er; a.out = dH; a.ld_out = (size_t)ld_dh;
     return launch_pull<SIDE_BWD_SRC>(ds, stream, a, partSize);
 }

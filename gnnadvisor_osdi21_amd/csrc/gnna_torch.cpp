@@ -530,11 +530,18 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
 gat_backward(const torch::Tensor &H_in, const torch::Tensor &el, const torch::Tensor &er, const torch::Tensor &lse,
              const torch::Tensor &Y_in, const torch::Tensor &dY_in, const torch::Tensor &row_pointers,
              const torch::Tensor &column_index, const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize,
-             double negative_slope)
+             double negative_slope, const c10::optional<std::vector<torch::Tensor>> &transposed)
 {
     const int heads = gat_heads(H_in, el, er);
     const int64_t n = H_in.size(0), width = H_in.size(1);
     const torch::Tensor H = gat_rows(H_in, "H", n, width), Y = gat_rows(Y_in, "Y", n, width), dY = gat_rows(dY_in, "dY", n, width);
+    // transposed = (t_row_pointers, t_column_index, t_part_pointers, t_part2Node): the source-side pass walks it (directed graphs)
+    const torch::Tensor *t_rp = &row_pointers, *t_ci = &column_index, *t_pp = &part_pointers, *t_p2n = &part2Node;
+    if (transposed.has_value()) {
+        TORCH_CHECK(transposed->size() == 4, "transposed must be (t_row_pointers, t_column_index, t_part_pointers, t_part2Node)");
+        t_rp = &(*transposed)[0]; t_ci = &(*transposed)[1]; t_pp = &(*transposed)[2]; t_p2n = &(*transposed)[3];
+        gat_check_graph(H, *t_rp, *t_ci, *t_pp, *t_p2n);
+    }
     CHECK_INPUT(lse); CHECK_F32(lse);
     TORCH_CHECK(lse.sizes() == el.sizes() && lse.device() == H.device(), "lse must be [num_nodes, heads] on H's device");
     TORCH_CHECK(Y.device() == H.device() && dY.device() == H.device(), "H, Y and dY must be on one device");
@@ -546,12 +553,14 @@ gat_backward(const torch::Tensor &H_in, const torch::Tensor &el, const torch::Te
     auto fresh = [&](int64_t cols) { return poison ? torch::full({n, cols}, nan, el.options()) : torch::empty({n, cols}, el.options()); };
     auto dH = fresh(width), d_el = fresh(heads), d_er = fresh(heads);
     void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-    int rc = gnna_gat_backward_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(), lse.data_ptr<float>(),
-                                   Y.data_ptr<float>(), ld_of(Y), dY.data_ptr<float>(), ld_of(dY),
-                                   row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
-                                   part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), (float)negative_slope,
-                                   dH.data_ptr<float>(), width, d_el.data_ptr<float>(), d_er.data_ptr<float>(), n, heads,
-                                   (int)(width / heads), part2Node.size(0), partSize, 0u, stream);
+    int rc = gnna_gat_backward_dir_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(), lse.data_ptr<float>(),
+                                       Y.data_ptr<float>(), ld_of(Y), dY.data_ptr<float>(), ld_of(dY),
+                                       row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
+                                       part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), part2Node.size(0),
+                                       t_rp->data_ptr<int32_t>(), t_ci->data_ptr<int32_t>(), t_pp->data_ptr<int32_t>(),
+                                       t_p2n->data_ptr<int32_t>(), t_p2n->size(0), (float)negative_slope,
+                                       dH.data_ptr<float>(), width, d_el.data_ptr<float>(), d_er.data_ptr<float>(), n, heads,
+                                       (int)(width / heads), partSize, 0u, stream);
     TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
     return std::make_tuple(dH, d_el, d_er);
 }
@@ -812,6 +821,59 @@ std::vector<torch::Tensor> build_part(int partSize, torch::Tensor indptr, bool f
     return {partPtr, part2Node};
 }
 
+// ---- device builders of a directed graph's backward structure (gnna_transpose.hip) ----------------------------------------
+
+static void check_device_ids(const torch::Tensor &t, const char *what)
+{
+    TORCH_CHECK(t.is_cuda(), what, " must be a CUDA tensor (the builder runs on the device)");
+    TORCH_CHECK(t.is_contiguous() && t.dim() == 1, what, " must be a contiguous 1-D tensor");
+    TORCH_CHECK(t.scalar_type() == at::kInt, what, " must be int32 (got ", t.scalar_type(), ")");
+}
+
+// (t_row_pointers [num_in_rows + 1], t_column_index [nnz], t_perm [nnz]) of A^T; t_perm is omitted with want_perm = false.
+std::vector<torch::Tensor> transpose_csr(const torch::Tensor &row_pointers, const torch::Tensor &column_index,
+                                         c10::optional<int64_t> num_in_rows, bool want_perm)
+{
+    check_device_ids(row_pointers, "row_pointers");
+    check_device_ids(column_index, "column_index");
+    TORCH_CHECK(row_pointers.numel() >= 1 && column_index.device() == row_pointers.device(),
+                "row_pointers must be [num_out_rows + 1], on column_index's device");
+    const int64_t n_out = row_pointers.numel() - 1, n_in = num_in_rows.value_or(n_out), nnz = column_index.numel();
+    TORCH_CHECK(n_in >= 0, "num_in_rows must not be negative");
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(row_pointers.device());
+    // (the library trusts row_pointers[num_out_rows] for the edge count: it must not exceed what column_index holds)
+    if (n_out > 0) TORCH_CHECK(row_pointers[n_out].item<int32_t>() == nnz, "row_pointers[-1] must be column_index.numel()");
+    auto t_rp = torch::empty({n_in + 1}, row_pointers.options());
+    auto t_ci = torch::empty({nnz}, row_pointers.options());
+    torch::Tensor t_perm;
+    if (want_perm) t_perm = torch::empty({nnz}, row_pointers.options());
+    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+    int rc = gnna_transpose_csr_i32(row_pointers.data_ptr<int32_t>(), nnz ? column_index.data_ptr<int32_t>() : nullptr, n_out, n_in,
+                                    t_rp.data_ptr<int32_t>(), nnz ? t_ci.data_ptr<int32_t>() : nullptr,
+                                    want_perm && nnz ? t_perm.data_ptr<int32_t>() : nullptr, stream);
+    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+    if (want_perm) return {t_rp, t_ci, t_perm};
+    return {t_rp, t_ci};
+}
+
+// build_part for device row pointers: (partPtr [P + 1], part2Node [P]) on the same device.
+std::vector<torch::Tensor> build_part_device(int partSize, const torch::Tensor &indptr)
+{
+    check_device_ids(indptr, "indptr");
+    TORCH_CHECK(indptr.numel() >= 1, "indptr must have num_nodes + 1 entries");
+    const int64_t num_nodes = indptr.numel() - 1;
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(indptr.device());
+    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+    const int64_t num_parts = gnna_count_parts_device_i32(partSize, indptr.data_ptr<int32_t>(), num_nodes, stream);
+    TORCH_CHECK(num_parts >= 0, "GNNAdvisor (libgnna) error ", num_parts, ": ", gnna_last_error());
+    auto partPtr = torch::empty({num_parts + 1}, indptr.options());
+    auto part2Node = torch::empty({num_parts}, indptr.options());
+    int rc = gnna_build_part_device_i32(partSize, indptr.data_ptr<int32_t>(), num_nodes, partPtr.data_ptr<int32_t>(),
+                                        num_parts ? part2Node.data_ptr<int32_t>() : nullptr, num_parts, stream);
+    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+    return {partPtr, part2Node};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
 {
     m.def("SAG", &SAG, "GNNAdvisor base Scatter-and-Gather Kernel (HIP, gfx950)");
@@ -855,10 +917,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           pybind11::arg("H"), pybind11::arg("el"), pybind11::arg("er"), pybind11::arg("row_pointers"), pybind11::arg("column_index"),
           pybind11::arg("part_pointers"), pybind11::arg("part2Node"), pybind11::arg("partSize"), pybind11::arg("negative_slope") = 0.2);
     m.def("gat_backward", &gat_backward,
-          "gradient of gat_forward on a graph whose structure is symmetric -> (dH, d_el, d_er); dH is the attention part only (extension)",
+          "gradient of gat_forward -> (dH, d_el, d_er); dH is the attention part only (extension).  The structure must be symmetric "
+          "unless transposed = [t_row_pointers, t_column_index, t_part_pointers, t_part2Node] (transpose_csr, build_part_device) is given",
           pybind11::arg("H"), pybind11::arg("el"), pybind11::arg("er"), pybind11::arg("lse"), pybind11::arg("Y"), pybind11::arg("dY"),
           pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("part_pointers"), pybind11::arg("part2Node"),
-          pybind11::arg("partSize"), pybind11::arg("negative_slope") = 0.2);
+          pybind11::arg("partSize"), pybind11::arg("negative_slope") = 0.2, pybind11::arg("transposed") = pybind11::none());
+    m.def("transpose_csr", &transpose_csr,
+          "device-built CSR of A^T (extension) -> [t_row_pointers, t_column_index, t_perm]: row j lists the rows i of the edges i <- j in "
+          "increasing position e, t_perm[p] = e (a stable argsort of column_index); ids outside [0, num_in_rows) are dropped",
+          pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("num_in_rows") = pybind11::none(),
+          pybind11::arg("want_perm") = true);
+    m.def("build_part_device", &build_part_device, "neighbor-group partitioner for device row pointers (extension): what build_part "
+          "returns, on the device", pybind11::arg("partSize"), pybind11::arg("indptr"));
     m.def("sddmm", &sddmm, "edge_out[e] = <A[row(e)], B[column_index[e]]> over the neighbor-group partition (extension)",
           pybind11::arg("A"), pybind11::arg("B"), pybind11::arg("column_index"), pybind11::arg("partPtr"), pybind11::arg("part2Node"),
           pybind11::arg("partSize"));

@@ -322,6 +322,39 @@ class _Auto:
         ip._say("\n=> AUTO Decider Complete !!!\n")
 
 
+class TransposedGraph(object):
+    """The structure a backward pass on a directed graph runs on (``inputProperty.transposed()``): the CSR of A^T built on the
+    device, its neighbor-group partition at the same ``partSize`` and the forward graph's ``degrees`` (the same vector: D A^T D
+    scales rows and columns alike).  It has the attributes a layer reads from a graph bundle -- ``row_pointers column_index
+    degrees partPtr part2Node partSize`` -- so every kernel runs the backward pass on it unchanged.  ``perm`` (int32 [nnz]:
+    position in the forward column_index of every transposed edge) costs another nnz x 4 bytes and is built at its first use,
+    which only the edge-valued operators make."""
+
+    def __init__(self, row_pointers, column_index, owner, partSize, source, perm=None):
+        from . import _lib
+        self._owner = owner                           # the forward profile: `degrees` is its vector, whatever it is set to
+        self._source = source                         # the forward (row_pointers, column_index): what perm is built from
+        self.row_pointers, self.column_index = row_pointers, column_index
+        self.partSize = int(partSize)
+        self.partPtr, self.part2Node = _lib.build_part_device(self.partSize, row_pointers)
+        self._perm = perm
+
+    @property
+    def degrees(self):
+        return self._owner.degrees
+
+    @property
+    def perm(self):
+        if self._perm is None:
+            from . import _lib
+            # (the builder gives the same bits on every run: this second pass orders the edges exactly as the first did)
+            perm = _lib.transpose_csr(*self._source, num_in_rows=self.row_pointers.numel() - 1)[2]
+            # edges dropped for an id outside the graph sit behind every row and are read by nobody; as an index they must
+            # still be one
+            self._perm = perm.clamp_(min=0)
+        return self._perm
+
+
 class inputProperty(object):
     """Graph profile + launch knobs handed to every layer (reference: param.py:4-164; read by
     gnn_conv.py:17-25,44,67 and GNNA_main.py:101-110).  Public surface kept: constructor arguments, the
@@ -369,6 +402,9 @@ class inputProperty(object):
         # libgnna scheduler knobs / graph hints chosen by the mi355x policy (None = library default)
         self.groups_per_chunk = self.loads_in_flight = None
         self.avg_degree_hint = self.nonlocal_ids_hint = None
+        # False: the structure is taken to be symmetric and every backward pass reuses the forward graph (the reference's
+        # assumption).  True: the backward passes run on `transposed()` -- exact on a directed graph
+        self.directed = False
 
     # ---- views ----------------------------------------------------------------------------------------
     def _say(self, text):
@@ -494,6 +530,34 @@ class inputProperty(object):
             _lib.reverse_edges(self.row_pointers, self.column_index)
             cache["symmetric"] = True
 
+    def transposed(self):
+        """The ``TransposedGraph`` of this graph -- what the backward passes use when ``directed`` is true.  Built on the device
+        (libgnna gnna_transpose_csr_i32 + gnna_build_part_device_i32: nothing is copied to the host), once per column_index and
+        ``partSize``; the graph hints of ``apply_tuning`` are registered for the transposed ids too.  The builders synchronise
+        and cannot run inside a stream capture: call this once before capturing a training step."""
+        cache = self._edge_arrays()
+        t = cache.get("transposed")
+        if t is None or t.partSize != int(self.partSize):
+            from . import _lib
+            ci = self.column_index
+            if not getattr(ci, "is_cuda", False):
+                raise ValueError("transposed() is built on the device: move row_pointers and column_index to the GPU first")
+            rp = self.row_pointers.to(ci.device)
+            if t is None:
+                t_rp, t_ci, _ = _lib.transpose_csr(rp, ci, want_perm=False)
+                t = TransposedGraph(t_rp, t_ci, self, self.partSize, (rp, ci))
+                hints = getattr(self, "_graph_hints", None)           # what apply_tuning registered for the forward ids
+                if hints is not None:
+                    _lib.set_graph_hints(t_ci, *hints)
+            else:                                                      # another partSize: only the partition changes
+                t = TransposedGraph(t.row_pointers, t.column_index, self, self.partSize, (rp, ci), perm=t._perm)
+            cache["transposed"] = t
+        return t
+
+    def backward_graph(self):
+        """The graph bundle a backward pass runs on: ``transposed()`` when ``directed``, else this graph itself."""
+        return self.transposed() if self.directed else self
+
     def edge_rows(self):
         """int32 [nnz] on the graph's device: the destination row of every edge (built once per column_index)."""
         cache = self._edge_arrays()
@@ -534,6 +598,11 @@ class inputProperty(object):
         ci = self.column_index
         if ci is not None and getattr(ci, "is_cuda", False):
             _lib.set_graph_hints(ci, self.avg_degree_hint, bool(nonlocal_ids))
+            # the transposed ids (directed graphs) are as scattered as these and have the same average row
+            self._graph_hints = (self.avg_degree_hint, bool(nonlocal_ids))
+            t = self._edge_arrays().get("transposed")
+            if t is not None:
+                _lib.set_graph_hints(t.column_index, *self._graph_hints)
         else:
             _lib.set_tuning(avg_degree=self.avg_degree_hint, nonlocal_ids=-1 if nonlocal_ids is None else nonlocal_ids)
 

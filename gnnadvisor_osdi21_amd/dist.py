@@ -178,7 +178,11 @@ class ShardedAggregator:
                  overlap: bool = True, force_overlap: bool = False,
                  hint_fn: Optional[Callable] = None, scattered_sources: bool = True,
                  pipeline_chunks: int = 0, exchange: str = "allgather", emulate: Optional[tuple] = None,
-                 force_collectives: bool = False):
+                 force_collectives: bool = False, directed: bool = False):
+        if directed:
+            raise NotImplementedError("ShardedAggregator(directed=True): the sharded layers aggregate their gradients over the "
+                                      "forward shard (the structure is taken to be symmetric); transposed shards are not built. "
+                                      "Directed graphs run on one GPU (decider.inputProperty.directed)")
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0

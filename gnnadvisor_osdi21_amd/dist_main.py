@@ -48,11 +48,18 @@ def build_parser():
     p.add_argument("--backend", default="nccl", help="debug: gloo")
     p.add_argument("--share_gpu", action="store_true", help="debug: every rank on cuda:0 (with --backend gloo)")
     p.add_argument("--verbose_mode", default="False", choices=["True", "False"])
+    p.add_argument("--directed", default="False", choices=["True", "False"],
+                   help="False only: the sharded backward pass reuses every rank's forward shard, i.e. it takes the structure "
+                        "to be symmetric (directed graphs: the single-GPU driver, main.py --directed True)")
     return p
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.directed == "True":
+        raise SystemExit("--directed True is not supported by the sharded driver: its backward pass aggregates over every rank's "
+                         "forward shard (the structure is taken to be symmetric) and no transposed shards are built; train a "
+                         "directed graph on one GPU with `python -m gnnadvisor_osdi21_amd.main --directed True`")
     verbose = args.verbose_mode == "True"
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))

@@ -58,6 +58,10 @@ def build_parser():
     p.add_argument('--fused_attention', default='False', **tf,
                    help="True: --model gat runs both layers on the fused attention kernels (GATConv(fused=True): alpha is made "
                         "from node-sized values where the rows are gathered, no per-edge tensor; MI355X addition)")
+    p.add_argument('--directed', default='False', **tf,
+                   help="True: the graph is directed -- every backward pass aggregates over the transposed structure, built on "
+                        "the device right after the partition (False: the structure is taken to be symmetric, as the "
+                        "reference does, and the backward passes reuse the forward graph)")
     p.add_argument('--policy', type=str, default='mi355x', choices=['mi355x', 'compat'], help="Decider policy")
     p.add_argument('--force_rabbit', default='False', **tf,
                    help="True: with --enable_rabbit True in auto mode, renumber even when the mi355x cost gate says the run is "
@@ -170,6 +174,25 @@ def main(argv=None, capture=None):
         # the measured schedule may use other phase counts than the rule's: make their packed id copies now, not in an epoch
         _gnna_lib.prepare_graph(inputInfo.column_index, inputInfo.partPtr, inputInfo.part2Node, dataset.num_nodes,
                                 dataset.num_nodes, inputInfo.partSize, _prep_widths)
+    inputInfo.directed = flag(args.directed)
+    if inputInfo.directed:
+        # the backward passes' structure: built (and prepared like the forward graph) here, never inside a captured epoch
+        start = time.perf_counter()
+        t_graph = inputInfo.transposed()
+        if args.model == 'gat' and not flag(args.fused_attention):
+            t_graph.perm                  # (edge-valued backward: the weights are read through the permutation)
+        torch.cuda.synchronize()
+        if verbose_mode:
+            print("# Build transposed graph on the device (s): {:.3f}".format(time.perf_counter() - start))
+        _gnna_lib.prepare_graph(t_graph.column_index, t_graph.partPtr, t_graph.part2Node, dataset.num_nodes,
+                                dataset.num_nodes, inputInfo.partSize, _prep_widths)
+        if not manual_mode and not (verify_spmm or single_spmm):
+            # the measured schedule, for the transposed ids' own layout
+            from .decider import calibrate_phases
+            calibrate_phases(t_graph.column_index, t_graph.partPtr, t_graph.part2Node, dataset.num_nodes, inputInfo.partSize,
+                             widths, verbose=verbose_mode)
+            _gnna_lib.prepare_graph(t_graph.column_index, t_graph.partPtr, t_graph.part2Node, dataset.num_nodes,
+                                    dataset.num_nodes, inputInfo.partSize, _prep_widths)
     degrees = inputInfo.degrees
     if capture is not None:
         capture.update(dataset=dataset, inputInfo=inputInfo, args=args)

@@ -28,6 +28,23 @@ def _knobs(info):
     return (info.partSize, info.dimWorker, info.warpPerBlock)
 
 
+def _is_directed(info):
+    return bool(getattr(info, "directed", False))
+
+
+def _remember_graph(ctx, info):
+    """Forward: the graph the layer ran on, and the profile its backward pass may have to ask for the transposed one."""
+    ctx.graph, ctx.info, ctx.directed = _graph_args(info), info, _is_directed(info)
+
+
+def _backward_graph(ctx):
+    """Backward: (row_pointers, column_index, degrees, partPtr, part2Node) to aggregate the gradient over.  A sum over the
+    edges i <- j sends row i's gradient to row j, i.e. it aggregates over A^T: the transposed structure of a directed graph
+    (decider.inputProperty.transposed, built on the device and cached), the forward graph itself when the structure is
+    symmetric (``directed`` false: the reference's assumption and this package's default)."""
+    return _graph_args(ctx.info.transposed()) if ctx.directed else ctx.graph
+
+
 # ---- features stored in bfloat16 / float16 (libgnna gnna_agg_ld_x16: fp32 accumulation, one rounding of the result) ------
 _X16 = (torch.bfloat16, torch.float16)
 
@@ -52,15 +69,16 @@ def _aggregate_x16(mode, X, graph, partSize, epsilon=1.0, relu=False):
 
 class GNNAFunction_X16(Function):
     """A GCN (mode 1) or GIN (mode 2) layer on 16-bit features, update-first -- Y = agg(X W), the GCN order -- or
-    aggregate-first -- Y = agg(X) W.  Both aggregations (forward, and backward on the 16-bit gradient: the structure is
-    assumed symmetric, as everywhere in this file) run on gnna_agg_ld_x16 and return the compute dtype; the dense products
+    aggregate-first -- Y = agg(X) W.  Both aggregations (forward, and backward on the 16-bit gradient, over the transposed
+    structure when the graph is ``directed``) run on gnna_agg_ld_x16 and return the compute dtype; the dense products
     (X W, G W^T, X^T G) are torch.mm on 16-bit operands.  X and the weights may be fp32 (torch.autocast) or 16-bit (a cast
     model): their gradients come back in their own dtype."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda")
     def forward(ctx, X, weight, inputInfo, mode, epsilon, update_first, relu, dtype):
-        ctx.graph, ctx.partSize = _graph_args(inputInfo), inputInfo.partSize
+        _remember_graph(ctx, inputInfo)
+        ctx.partSize = inputInfo.partSize
         ctx.mode, ctx.eps, ctx.update_first, ctx.relu, ctx.dtype = int(mode), float(epsilon), bool(update_first), bool(relu), dtype
         ctx.in_dtypes = (X.dtype, weight.dtype)
         Xh, Wh = X.to(dtype), weight.to(dtype)
@@ -84,35 +102,39 @@ class GNNAFunction_X16(Function):
             dY = dY * (ctx.saved_tensors[2] > 0)
         dY = dY.contiguous()
         d_input = None
+        bgraph = _backward_graph(ctx)
         if ctx.update_first:
-            G = _aggregate_x16(ctx.mode, dY, ctx.graph, ctx.partSize, ctx.eps)
+            G = _aggregate_x16(ctx.mode, dY, bgraph, ctx.partSize, ctx.eps)
             d_weight = torch.mm(saved.t(), G)
             if ctx.needs_input_grad[0]:
                 d_input = torch.mm(G, Wh.t())
         else:
             d_weight = torch.mm(saved.t(), dY)
             if ctx.needs_input_grad[0]:
-                d_input = _aggregate_x16(ctx.mode, torch.mm(dY, Wh.t()), ctx.graph, ctx.partSize, ctx.eps)
+                d_input = _aggregate_x16(ctx.mode, torch.mm(dY, Wh.t()), bgraph, ctx.partSize, ctx.eps)
         if d_input is not None:
             d_input = d_input.to(ctx.in_dtypes[0])
         return d_input, d_weight.to(ctx.in_dtypes[1]), None, None, None, None, None, None
 
 
 class ScatterAndGather(Function):
-    """Y = A X (unweighted neighbor sum).  A is assumed symmetric, so backward is the same op."""
+    """Y = A X (unweighted neighbor sum).  Backward is A^T dY: the same op on the same graph when the structure is symmetric,
+    on the transposed structure when ``inputInfo.directed``."""
 
     @staticmethod
     def forward(ctx, X, inputInfo):
-        ctx.graph, ctx.knobs = _graph_args(inputInfo), _knobs(inputInfo)
+        _remember_graph(ctx, inputInfo)
+        ctx.knobs = _knobs(inputInfo)
         if X.dtype in _X16:
             return _aggregate_x16(0, X, ctx.graph, ctx.knobs[0])
         return GNNA.SAG(X, *ctx.graph, *ctx.knobs)
 
     @staticmethod
     def backward(ctx, d_output):
+        bgraph = _backward_graph(ctx)
         if d_output.dtype in _X16:
-            return _aggregate_x16(0, d_output, ctx.graph, ctx.knobs[0]), None
-        return GNNA.SAG(d_output.contiguous(), *ctx.graph, *ctx.knobs), None
+            return _aggregate_x16(0, d_output, bgraph, ctx.knobs[0]), None
+        return GNNA.SAG(d_output.contiguous(), *bgraph, *ctx.knobs), None
 
 
 class GNNAFunction(Function):
@@ -121,7 +143,8 @@ class GNNAFunction(Function):
     @staticmethod
     def forward(ctx, X, weight, inputInfo):
         ctx.save_for_backward(X, weight)
-        ctx.graph, ctx.knobs = _graph_args(inputInfo), _knobs(inputInfo)
+        _remember_graph(ctx, inputInfo)
+        ctx.knobs = _knobs(inputInfo)
         return GNNA.forward(X, weight, *ctx.graph, *ctx.knobs)[0]
 
     @staticmethod
@@ -131,11 +154,13 @@ class GNNAFunction(Function):
 
 
 def _gcn_backward(ctx, d_output, X, weight):
-    """(d_input, d_weight, None) of a GCN layer from the gradient of its (pre-activation) output."""
+    """(d_input, d_weight, None) of a GCN layer from the gradient of its (pre-activation) output: D A^T D dY, then the two
+    dense products."""
+    bgraph = _backward_graph(ctx)
     if not ctx.needs_input_grad[0]:
         # first layer: the features need no gradient (the reference computes and drops d_input)
-        return None, GNNA.backward_weight(d_output, X, *ctx.graph, *ctx.knobs)[0], None
-    d_input, d_weight = GNNA.backward(d_output, X, weight, *ctx.graph, *ctx.knobs)
+        return None, GNNA.backward_weight(d_output, X, *bgraph, *ctx.knobs)[0], None
+    d_input, d_weight = GNNA.backward(d_output, X, weight, *bgraph, *ctx.knobs)
     return d_input, d_weight, None
 
 
@@ -146,8 +171,9 @@ class GNNAFunction_ReLU(Function):
 
     @staticmethod
     def forward(ctx, X, weight, inputInfo):
-        rp, ci, deg, pp, p2n = _graph_args(inputInfo)
-        ctx.graph, ctx.knobs = (rp, ci, deg, pp, p2n), _knobs(inputInfo)
+        _remember_graph(ctx, inputInfo)
+        rp, ci, deg, pp, p2n = ctx.graph
+        ctx.knobs = _knobs(inputInfo)
         Y = GNNA.aggregate_ld(1, torch.mm(X, weight), ci, deg, 1.0, pp, p2n, inputInfo.partSize, None, False, True)
         ctx.save_for_backward(X, weight, Y)
         return Y
@@ -164,8 +190,9 @@ class GNNAFunction_GIN(Function):
 
     @staticmethod
     def forward(ctx, X, weight, inputInfo, eplison):
-        rp, ci, _deg, pp, p2n = _graph_args(inputInfo)
-        ctx.graph, ctx.knobs, ctx.eplison = (rp, ci, pp, p2n), _knobs(inputInfo), eplison
+        _remember_graph(ctx, inputInfo)
+        rp, ci, _deg, pp, p2n = ctx.graph
+        ctx.knobs, ctx.eplison = _knobs(inputInfo), eplison
         X_prime, X_agg = GNNA.forward_gin(X, weight, rp, ci, eplison, pp, p2n, *ctx.knobs)
         ctx.save_for_backward(X_agg, weight)
         return X_prime
@@ -173,11 +200,11 @@ class GNNAFunction_GIN(Function):
     @staticmethod
     def backward(ctx, d_output):
         X_agg, weight = ctx.saved_tensors
-        rp, ci, pp, p2n = ctx.graph
         if not ctx.needs_input_grad[0]:
             # first layer: d_weight = T^T dY needs no aggregation at all; the reference aggregates
             # dY W^T at the input width (F = 602 on Reddit) and drops the result
             return None, GNNA.xtg(X_agg, d_output.contiguous()), None, None
+        rp, ci, _deg, pp, p2n = _backward_graph(ctx)
         d_input, d_weight = GNNA.backward_gin(d_output.contiguous(), X_agg, weight, rp, ci,
                                               ctx.eplison, pp, p2n, *ctx.knobs)
         return d_input, d_weight, None, None
@@ -210,8 +237,9 @@ class GNNAFunction_GIN_UpdateFirst(Function):
 
     @staticmethod
     def forward(ctx, X, weight, inputInfo, eplison, relu=False):
-        rp, ci, _deg, pp, p2n = _graph_args(inputInfo)
-        ctx.graph, ctx.knobs, ctx.eplison = (rp, ci, pp, p2n), _knobs(inputInfo), eplison
+        _remember_graph(ctx, inputInfo)
+        rp, ci, _deg, pp, p2n = ctx.graph
+        ctx.knobs, ctx.eplison = _knobs(inputInfo), eplison
         ctx.relu = bool(relu)
         with torch.no_grad():
             XW = _mm_for_gather(X, weight, ci)
@@ -225,10 +253,10 @@ class GNNAFunction_GIN_UpdateFirst(Function):
     @staticmethod
     def backward(ctx, d_output):
         X, weight = ctx.saved_tensors[:2]
-        rp, ci, pp, p2n = ctx.graph
+        rp, ci, _deg, pp, p2n = _backward_graph(ctx)
         if ctx.relu:
             d_output = d_output * (ctx.saved_tensors[2] > 0)
-        G = GNNA.aggregate_gin(d_output.contiguous(), rp, ci, ctx.eplison, pp, p2n, *ctx.knobs)   # A symmetric
+        G = GNNA.aggregate_gin(d_output.contiguous(), rp, ci, ctx.eplison, pp, p2n, *ctx.knobs)   # eps A^T dY
         d_input = torch.mm(G, weight.t()) if ctx.needs_input_grad[0] else None
         return d_input, GNNA.xtg(X, G), None, None, None
 
@@ -307,8 +335,8 @@ def _extreme_backward(ctx, dY):
 class NeighborMax(Function):
     """Y[i, f] = max over the neighbours j of i of X[j, f] (libgnna gnna_agg_reduce_ld_f32; a row without edges gives 0).
     The forward records which edge supplied every element -- among equal values the one earliest in column_index -- and the
-    backward sends that element's gradient to that one source row (gnna_scatter_arg_ld_f32).  Unlike every sum operator of
-    this file, this backward does NOT assume that the graph's structure is symmetric."""
+    backward sends that element's gradient to that one source row (gnna_scatter_arg_ld_f32).  This backward needs neither a symmetric
+    structure nor the transposed one: it is exact on any graph, whatever ``directed`` says."""
 
     @staticmethod
     def forward(ctx, X, inputInfo):
@@ -329,13 +357,15 @@ class NeighborMin(Function):
 
 class NeighborMean(Function):
     """Y = diag(1 / max(count, 1)) A X: the mean over every row's neighbours (0 for a row without edges), composed from the
-    neighbor sum GNNA.SAG and a row scaling.  A is assumed symmetric, so backward is A (dY / count)."""
+    neighbor sum GNNA.SAG and a row scaling.  Backward is A^T (dY / count) -- count is the forward graph's; A^T is A itself
+    unless the graph is ``directed``."""
 
     @staticmethod
     def forward(ctx, X, inputInfo):
         if X.dtype != torch.float32:
             raise TypeError(f"NeighborMean: float32 features only (got {X.dtype})")
-        ctx.graph, ctx.knobs = _graph_args(inputInfo), _knobs(inputInfo)
+        _remember_graph(ctx, inputInfo)
+        ctx.knobs = _knobs(inputInfo)
         inv = inputInfo.inv_row_counts()
         ctx.save_for_backward(inv)
         return GNNA.SAG(X.contiguous(), *ctx.graph, *ctx.knobs).mul_(inv.unsqueeze(1))
@@ -343,7 +373,7 @@ class NeighborMean(Function):
     @staticmethod
     def backward(ctx, dY):
         inv, = ctx.saved_tensors
-        return GNNA.SAG(dY * inv.unsqueeze(1), *ctx.graph, *ctx.knobs), None
+        return GNNA.SAG(dY * inv.unsqueeze(1), *_backward_graph(ctx), *ctx.knobs), None
 
 
 class SAGEConv(Module):
@@ -413,7 +443,9 @@ class EdgeWeightedAggregate(Function):
     """Y = A_w X with caller-supplied edge values: Y[i] = sum_e w[e] X[column_index[e]] (libgnna gnna_agg_edge_ld_f32).
     Multi-head: X is [N, heads * F] and w is [heads, nnz]; head h aggregates the column block X[:, h F : (h + 1) F] with w[h]
     into the same block of Y (the strided forms: no copies).  Backward on a graph whose structure is symmetric:
-    dX = A_{w[rev]} dY (the same partition, weights read through the reverse-edge map) and dw = sddmm(dY, X)."""
+    dX = A_{w[rev]} dY (the same partition, weights read through the reverse-edge map) and dw = sddmm(dY, X).  On a ``directed``
+    graph dX is the aggregation of dY over the transposed structure with the weights w[:, perm] (perm: the forward position of
+    every transposed edge); dw is the same."""
 
     @staticmethod
     def forward(ctx, X, w, inputInfo):
@@ -434,7 +466,11 @@ class EdgeWeightedAggregate(Function):
         heads, F = wh.shape[0], X.shape[1] // wh.shape[0]
         dX = dw = None
         if ctx.needs_input_grad[0]:
-            dX = _edge_aggregate(dY, wh.index_select(1, info.reverse_edges()).contiguous(), info)
+            if _is_directed(info):
+                t = info.transposed()
+                dX = _edge_aggregate(dY, wh.index_select(1, t.perm).contiguous(), t)
+            else:
+                dX = _edge_aggregate(dY, wh.index_select(1, info.reverse_edges()).contiguous(), info)
         if ctx.needs_input_grad[1]:
             dw = torch.stack([_sddmm_at_least_4(dY[:, h * F:(h + 1) * F], X[:, h * F:(h + 1) * F], info.column_index,
                                                 info.partPtr, info.part2Node, info.partSize) for h in range(heads)])
@@ -477,8 +513,9 @@ class GATAttention(Function):
     or cached (saved: H, el, er, lse, Y -- all node-sized), and all heads run in one call.  The gradient of H returned here is the
     attention part (sum alpha dY); the paths through el and er are autograd's.
 
-    The backward reads row j's edges as the edges j -> i, so before its first backward on a graph it establishes that the
-    structure is symmetric and raises otherwise (``decider.inputProperty.require_symmetric``): once per column_index, on the host -- a
+    On a ``directed`` graph the backward's source-side pass walks the transposed structure (decider.inputProperty.transposed:
+    nnz x 4 bytes of ids and a partition stay on the device) and nothing is assumed.  Otherwise the backward reads row j's edges
+    as the edges j -> i, so before its first backward on a graph it establishes that the structure is symmetric and raises otherwise (``decider.inputProperty.require_symmetric``): once per column_index, on the host -- a
     copy of the CSR to the host and a pass of gnna_reverse_edges_i32 over it, about a second at 1e8 edges; only the answer is
     kept, nothing of the size of the edge list stays on the device."""
 
@@ -498,10 +535,15 @@ class GATAttention(Function):
         info = ctx.info
         if not any(ctx.needs_input_grad[:3]):
             return None, None, None, None, None
-        from .decider import inputProperty
-        inputProperty.require_symmetric(info)    # raises on a structure that is not symmetric (answer cached per column_index)
+        transposed = None
+        if _is_directed(info):
+            t = info.transposed()
+            transposed = [t.row_pointers, t.column_index, t.partPtr, t.part2Node]
+        else:
+            from .decider import inputProperty
+            inputProperty.require_symmetric(info)    # raises on a structure that is not symmetric (answer cached per column_index)
         dH, d_el, d_er = GNNA.gat_backward(H, el, er, lse, Y, dY, info.row_pointers, info.column_index, info.partPtr,
-                                           info.part2Node, info.partSize, ctx.negative_slope)
+                                           info.part2Node, info.partSize, ctx.negative_slope, transposed)
         need = ctx.needs_input_grad
         return (dH if need[0] else None, d_el if need[1] else None, d_er if need[2] else None, None, None)
 
@@ -510,7 +552,8 @@ class GATConv(Module):
     """Additive graph attention (GAT): H = X W; per head h, s[e] = leaky_relu(<H_h[row(e)], a_l[h]> + <H_h[col(e)], a_r[h]>),
     alpha = edge softmax of s over every row, Y_h = A_alpha H_h.  Heads are concatenated (concat=True, [N, heads * out]) or
     averaged ([N, out]).  The scores are nnz-sized elementwise torch work; softmax and aggregation are libgnna kernels.
-    Needs the graph's structure to be symmetric (the backward gathers through the reverse-edge map).
+    Needs the graph's structure to be symmetric (the backward gathers through the reverse-edge map) unless the graph is
+    ``directed`` (then it gathers over the transposed structure).
     fused=True: the attention runs on GATAttention instead -- the same function, with alpha made from node-sized values inside
     the gathers: no per-edge tensor, one call for all heads."""
 

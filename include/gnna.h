@@ -100,6 +100,33 @@ GNNA_API int gnna_build_part_i32(int partSize, const int32_t *indptr, int64_t nu
                         int32_t *partPtr /* [num_parts + 1] */,
                         int32_t *part2Node /* [num_parts] */, int64_t num_parts);
 
+/* ---- structure builders (device; gnna_transpose.hip) -----------------------------------
+ * What a backward pass on a DIRECTED graph needs -- the transposed CSR, its partition and the edge permutation -- built on the
+ * device from device arrays; nothing is copied to the host but one count per call.  All pointers are DEVICE pointers.  They are
+ * prepare-time calls: each reads a count back and so SYNCHRONISES `stream`, and inside a stream capture each returns
+ * GNNA_ERR_UNSUPPORTED.  Scratch is library scratch in a slot of their own (grow-only, per stream, like every other).
+ *
+ * gnna_transpose_csr_i32: the CSR of A^T for the CSR of a rectangular A [num_out_rows x num_in_rows] (the two may differ).
+ *   Row j of the result lists the destination rows i of the edges i <- j, in increasing position e of the edge in column_index
+ *   (a STABLE order), and t_perm[p] is that position: t_perm = numpy.argsort(column_index, kind="stable") and
+ *   t_column_index = the row of every edge, in that order.  The same bits on every run and for every launch shape (a stable
+ *   radix sort over the ids: integer counts, no position is handed out by an atomic).  Rows need not be sorted; duplicates and
+ *   self loops are kept as they are.  Column ids outside [0, num_in_rows) are DROPPED, as every gather skips them:
+ *   t_row_pointers[num_in_rows] is the number of edges kept, and t_column_index / t_perm are -1 from there to nnz =
+ *   row_pointers[num_out_rows] (the count that is read back).  t_perm may be NULL.  nnz = 0 and num_out_rows = 0 are fine
+ *   (t_row_pointers is all zeros).  row_pointers must start at 0 and not decrease (not checked).  Fewer than 2^31 - 1 rows on
+ *   either side.  Scratch: 8 bytes per edge (12 without t_perm) + 1 KiB per 4,096 edges.
+ * gnna_count_parts_device_i32 / gnna_build_part_device_i32: gnna_count_parts / gnna_build_part_i32 for DEVICE row pointers and
+ *   device outputs -- the same part_pointers and part2Node, element for element, closing sentinel included.  The count call
+ *   reads its result back (it synchronises); the build call counts again to check num_parts (it synchronises too) and writes
+ *   nothing when num_parts is not the count.  A row whose pointers decrease counts as empty (the host call refuses it). */
+GNNA_API int gnna_transpose_csr_i32(const int32_t *row_pointers, const int32_t *column_index, int64_t num_out_rows,
+        int64_t num_in_rows, int32_t *t_row_pointers /* [num_in_rows + 1] */, int32_t *t_column_index /* [nnz] */,
+        int32_t *t_perm /* [nnz], may be NULL */, void *stream);
+GNNA_API int64_t gnna_count_parts_device_i32(int partSize, const int32_t *indptr, int64_t num_nodes, void *stream);
+GNNA_API int gnna_build_part_device_i32(int partSize, const int32_t *indptr, int64_t num_nodes,
+        int32_t *partPtr /* [num_parts + 1] */, int32_t *part2Node /* [num_parts] */, int64_t num_parts, void *stream);
+
 /* ---- graph inputs (host) --------------------------------------------------------------
  * Native counterparts of the reference loader's CSR construction
  * (GNNAdvisor/dataset.py:99-122) and of the renumbering hook (rabbit.reorder,
@@ -353,6 +380,19 @@ GNNA_API int gnna_gat_backward_f32(const float *H, int64_t ld_h, const float *el
         const int32_t *row_pointers, const int32_t *column_index, const int32_t *part_pointers, const int32_t *part2Node,
         float negative_slope, float *dH, int64_t ld_dh, float *d_el, float *d_er, int64_t num_nodes, int heads, int dim,
         int64_t num_parts, int partSize, unsigned flags, void *stream);
+/* gnna_gat_backward_f32 for a DIRECTED graph: the source-side pass (row j gathers dY[i] over the edges j -> i: d_er, dH) walks a
+ * second structure, the transposed CSR of the first with its own partition (gnna_transpose_csr_i32 +
+ * gnna_build_part_device_i32 at the same partSize; t_row_pointers is not read, like row_pointers); the destination-side pass
+ * (d_el) walks the graph itself.  No symmetry is assumed.  gnna_gat_backward_f32 is this call with the same structure given
+ * twice.  Everything else as above. */
+GNNA_API int gnna_gat_backward_dir_f32(const float *H, int64_t ld_h, const float *el, const float *er, const float *lse,
+        const float *Y, int64_t ld_y, const float *dY, int64_t ld_dy,
+        const int32_t *row_pointers, const int32_t *column_index, const int32_t *part_pointers, const int32_t *part2Node,
+        int64_t num_parts,
+        const int32_t *t_row_pointers, const int32_t *t_column_index, const int32_t *t_part_pointers, const int32_t *t_part2Node,
+        int64_t t_num_parts,
+        float negative_slope, float *dH, int64_t ld_dh, float *d_el, float *d_er, int64_t num_nodes, int heads, int dim,
+        int partSize, unsigned flags, void *stream);
 
 /* Reverse-edge map of a CSR whose structure is symmetric (host pointers): rev[e] is the position of the edge col(e) -> row(e)
  * that matches e; the k-th (i, j) of row i pairs with the k-th (j, i) of row j (positions in increasing order), a self loop
