@@ -9,6 +9,7 @@ not a port of its CUDA code.  Layout:
 * ``_lib``           ctypes binding of the C ABI.
 * ``decider``        ``inputProperty`` / Decider   (reference: GNNAdvisor/param.py)
 * ``ops``            autograd ops + GCNConv/GINConv (reference: GNNAdvisor/gnn_conv.py)
+* ``sampling``      ``NeighborSampler`` / ``SampledBlock``: device-side neighbor sampling, mini-batch blocks (new)
 * ``verify``         ``Verification`` harness       (reference: GNNAdvisor/unitest.py)
 * ``graph``          synthetic graphs, CSR + degree builder (reference: GNNAdvisor/dataset.py:99-122)
 * ``dist``           dst-range sharding + RCCL all-gather halo exchange (new)

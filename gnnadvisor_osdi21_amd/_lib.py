@@ -51,7 +51,7 @@ EXPORTS = ("gnna_version", "gnna_build_id", "gnna_last_error", "gnna_count_parts
            "gnna_debug_untrusted_copies", "gnna_agg_edge_ld_f32", "gnna_edge_softmax_f32", "gnna_edge_softmax_backward_f32",
            "gnna_reverse_edges_i32", "gnna_agg_ld_x16", "gnna_prepare_x16", "gnna_agg_reduce_ld_f32", "gnna_scatter_arg_ld_f32",
            "gnna_gat_forward_f32", "gnna_gat_backward_f32", "gnna_gat_backward_dir_f32", "gnna_transpose_csr_i32",
-           "gnna_count_parts_device_i32", "gnna_build_part_device_i32")
+           "gnna_count_parts_device_i32", "gnna_build_part_device_i32", "gnna_sample_neighbors_i32")
 
 
 def load() -> ctypes.CDLL:
@@ -210,6 +210,10 @@ def load() -> ctypes.CDLL:
     L.gnna_build_part_device_i32.restype = ctypes.c_int
     L.gnna_build_part_device_i32.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_int64, ctypes.c_void_p]
+    L.gnna_sample_neighbors_i32.restype = ctypes.c_int
+    L.gnna_sample_neighbors_i32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                            ctypes.c_int, ctypes.c_uint64, ctypes.c_int] + [ctypes.c_void_p] * 6 + [
+        ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]
     _lib = L
     return L
 
@@ -974,3 +978,62 @@ def build_part_device(partSize: int, indptr):
         _check(load().gnna_build_part_device_i32(int(partSize), ip.data_ptr(), ip.numel() - 1, pp.data_ptr(), _ptr(p2n), P,
                                                  _stream(ip.device)))
     return pp, p2n
+
+
+def sample_neighbors(row_pointers, column_index, seeds, fanout, rng_seed, partSize=None, want_edge_ids=True, *,
+                     edge_capacity=None, src_capacity=None):
+    """gnna_sample_neighbors_i32 (device): one mini-batch block for the destination rows `seeds` (distinct int32 ids) of the
+    device CSR row_pointers [N + 1] / column_index [nnz].  Every row keeps all its edges when fanout <= 0 or it has at most
+    `fanout`, else the `fanout` positions with the smallest splitmix64(rng_seed, position) key, in increasing position (the
+    rule is spelled out in include/gnna.h).  -> dict: row_pointers [S + 1], column_index [nnz_b] (LOCAL source ids: 0 .. S-1
+    are the seeds in the order given, the other sources follow in increasing global id), edge_ids [nnz_b] (positions in
+    column_index; None with want_edge_ids=False), src_nodes [num_src] (global ids), partPtr [P + 1] / part2Node [P] (what
+    build_part gives for the block's row pointers; None without partSize), num_dst, num_src.  The arrays are trimmed views of
+    buffers sized here (S * fanout edges, or the sum of the seeds' degrees).  One stream synchronisation; refuses to run inside
+    a stream capture.  O(N) device work per call.  edge_capacity / src_capacity override the sizes chosen here; a GnnaError
+    raised for a capacity that is too small carries the needed (nnz, num_src, num_parts) as ``.counts``."""
+    rp, ci = _device_i32(row_pointers, "row_pointers"), _device_i32(column_index, "column_index")
+    sd = _device_i32(seeds, "seeds")
+    assert rp.numel() >= 1 and ci.device == rp.device and sd.device == rp.device, \
+        "row_pointers must be [num_nodes + 1]; column_index and seeds live on its device"
+    n, S, fanout = rp.numel() - 1, sd.numel(), int(fanout)
+    rng_seed = int(rng_seed) & 0xFFFFFFFFFFFFFFFF
+    want_part = partSize is not None
+    if want_part and int(partSize) <= 0:
+        raise GnnaError(f"partSize must be positive (got {partSize})")
+    dev = rp.device
+    with torch.cuda.device(dev):
+        if fanout >= 1:
+            edge_cap = S * fanout
+        elif S > 0:
+            # every neighbour: the seeds' degrees (ids outside the graph are the library's to report)
+            rows = sd.long().clamp(0, max(n - 1, 0))
+            edge_cap = int((rp[rows + 1] - rp[rows]).clamp(min=0).sum()) if n > 0 else 0
+        else:
+            edge_cap = 0
+        edge_cap = min(edge_cap, ci.numel())
+        src_cap = min(S + edge_cap, max(n, S))
+        if edge_capacity is not None:
+            edge_cap = int(edge_capacity)
+        if src_capacity is not None:
+            src_cap = int(src_capacity)
+        if edge_cap < 0 or src_cap < 0:
+            raise GnnaError("capacities must not be negative")
+        blk_rp = torch.empty(S + 1, dtype=torch.int32, device=dev)
+        blk_ci = torch.empty(edge_cap, dtype=torch.int32, device=dev)
+        eid = torch.empty(edge_cap, dtype=torch.int32, device=dev) if want_edge_ids else None
+        src = torch.empty(src_cap, dtype=torch.int32, device=dev)
+        pp = torch.empty(edge_cap + 1, dtype=torch.int32, device=dev) if want_part else None
+        p2n = torch.empty(edge_cap, dtype=torch.int32, device=dev) if want_part else None
+        counts = (ctypes.c_int64 * 3)()
+        rc = load().gnna_sample_neighbors_i32(rp.data_ptr(), _ptr(ci), n, _ptr(sd), S, fanout, rng_seed,
+                                              int(partSize) if want_part else 0, blk_rp.data_ptr(), _ptr(blk_ci), _ptr(eid),
+                                              _ptr(src), _ptr(pp), _ptr(p2n), edge_cap, src_cap, counts, _stream(dev))
+    if rc != GNNA_OK:
+        err = GnnaError(f"libgnna error {rc}: {load().gnna_last_error().decode()}")
+        err.counts = tuple(int(c) for c in counts)
+        raise err
+    nnz, num_src, P = int(counts[0]), int(counts[1]), int(counts[2])
+    return {"row_pointers": blk_rp, "column_index": blk_ci[:nnz], "edge_ids": eid[:nnz] if want_edge_ids else None,
+            "src_nodes": src[:num_src], "partPtr": pp[:P + 1] if want_part else None,
+            "part2Node": p2n[:P] if want_part else None, "num_dst": S, "num_src": num_src}

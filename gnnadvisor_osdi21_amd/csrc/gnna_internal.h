@@ -235,6 +235,14 @@ int reserve_x16(DeviceState *ds, hipStream_t stream, int64_t num_in_rows, int64_
 // out[r, 0:dim] = 0 for every row (rows `ld` floats apart): the dense prologue without its validation (gnna_agg.hip).
 int launch_zero_fill(DeviceState *ds, hipStream_t stream, float *out, int64_t rows, int dim, int64_t ld);
 
+// ---- device structure builders (gnna_transpose.hip; also used by gnna_sample.hip) ------------------------------------
+// Tiles of the exclusive scan over n ints: the ints of `partial` that launch_exclusive_scan needs.
+int64_t scan_tiles(int64_t n);
+// data[i] <- sum of data[0 .. i) for i < n, in place (int32 counts whose total fits int32); three launches, no read-back.
+int launch_exclusive_scan(hipStream_t stream, int32_t *data, int64_t n, int32_t *partial);
+// GNNA_ERR_UNSUPPORTED when `stream` is being captured (the prepare-time calls read a count back).
+int refuse_capture(const char *what, hipStream_t stream);
+
 // ---- optional per-call kernel timing (gnna_profile_begin/end) ---------------------------------------
 // Returns the index of this call in the active profile (-1 when not profiling).
 int profile_acquire_call(bool has_work);

@@ -95,6 +95,9 @@ scan_apply_kernel(int32_t *__restrict__ data, int64_t n, const int32_t *__restri
     }
 }
 
+}  // namespace
+
+// (shared with gnna_sample.hip through gnna_internal.h)
 int64_t scan_tiles(int64_t n) { return (n + kScanTile - 1) / kScanTile; }
 
 // data[i] <- sum of data[0 .. i) for i < n; `partial` holds scan_tiles(n) ints.
@@ -109,6 +112,8 @@ int launch_exclusive_scan(hipStream_t stream, int32_t *data, int64_t n, int32_t 
     if (e != hipSuccess) return fail(GNNA_ERR_HIP, "scan launch: %s", hipGetErrorString(e));
     return GNNA_OK;
 }
+
+namespace {
 
 // ---- the radix passes -------------------------------------------------------------------------------------------------
 
@@ -276,6 +281,8 @@ unsigned grid_for(int64_t items, int num_cus)
 
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
+}  // namespace
+
 int refuse_capture(const char *what, hipStream_t stream)
 {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -284,6 +291,8 @@ int refuse_capture(const char *what, hipStream_t stream)
         return fail(GNNA_ERR_UNSUPPORTED, "%s reads a count back and cannot run inside a stream capture: call it before capturing", what);
     return GNNA_OK;
 }
+
+namespace {
 
 int read_back_i32(const char *what, hipStream_t stream, const int32_t *src, int32_t *value)
 {

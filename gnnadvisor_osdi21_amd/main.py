@@ -19,8 +19,19 @@ import torch
 import torch.nn.functional as F
 
 
+class _Parser(argparse.ArgumentParser):
+    """argparse takes `--fanout -1,-1` for two options: the value is joined to its flag before parsing."""
+
+    def parse_known_args(self, args=None, namespace=None):
+        args = list(sys.argv[1:] if args is None else args)
+        for i in range(len(args) - 2, -1, -1):
+            if args[i] == "--fanout":
+                args[i: i + 2] = ["--fanout=" + args[i + 1]]
+        return super().parse_known_args(args, namespace)
+
+
 def build_parser():
-    p = argparse.ArgumentParser()
+    p = _Parser()
     p.add_argument("--dataDir", type=str, default="../osdi-ae-graphs", help="the path to graphs")
     p.add_argument("--dataset", type=str, default='amazon0601', help="dataset")
     p.add_argument("--dim", type=int, default=96, help="input embedding dimension size")
@@ -62,6 +73,11 @@ def build_parser():
                    help="True: the graph is directed -- every backward pass aggregates over the transposed structure, built on "
                         "the device right after the partition (False: the structure is taken to be symmetric, as the "
                         "reference does, and the backward passes reuse the forward graph)")
+    p.add_argument('--fanout', type=str, default=None,
+                   help="--model sage: train on sampled mini-batches -- a comma list with one entry per layer, the neighbours "
+                        "sampled per node at that layer (-1: all of them), e.g. 25,10; the blocks are drawn on the device "
+                        "(sampling.NeighborSampler, MI355X addition)")
+    p.add_argument('--batch_size', type=int, default=1024, help="--fanout: seed nodes per mini-batch")
     p.add_argument('--policy', type=str, default='mi355x', choices=['mi355x', 'compat'], help="Decider policy")
     p.add_argument('--force_rabbit', default='False', **tf,
                    help="True: with --enable_rabbit True in auto mode, renumber even when the mi355x cost gate says the run is "
@@ -96,6 +112,25 @@ def main(argv=None, capture=None):
         raise SystemExit("--heads must be >= 1")
     if flag(args.fused_attention) and args.model != 'gat':
         raise SystemExit("--fused_attention True selects the fused GAT attention: run it with --model gat (got --model %s)" % args.model)
+    fanouts = None
+    if args.fanout is not None:
+        if args.model != 'sage':
+            raise SystemExit("--fanout trains GraphSAGE on sampled blocks: run it with --model sage (got --model %s)" % args.model)
+        if flag(args.hip_graph):
+            raise SystemExit("--fanout does not support --hip_graph True: every batch samples new blocks and reads their sizes "
+                             "back; run it with --hip_graph False")
+        if args.dtype != 'float32':
+            raise SystemExit("--fanout: the GraphSAGE layers on a block are float32 only; use --dtype float32")
+        if single_spmm or verify_spmm:
+            raise SystemExit("--fanout does not go with --single_spmm / --verify_spmm: they run one full-graph aggregation")
+        try:
+            fanouts = [int(f) for f in args.fanout.split(",")]
+        except ValueError:
+            raise SystemExit("--fanout takes a comma list of integers, e.g. 25,10 (got %r)" % args.fanout)
+        if len(fanouts) != 2:
+            raise SystemExit("--fanout needs one entry per layer: --model sage has 2 layers (got %d)" % len(fanouts))
+        if args.batch_size < 1:
+            raise SystemExit("--batch_size must be >= 1")
     assert torch.cuda.is_available(), "requires an MI355X GPU: there is no CPU path"
     device = torch.device('cuda')
     if flag(args.tune_gemm):
@@ -246,7 +281,11 @@ def main(argv=None, capture=None):
                 self.conv1 = SAGEConv(dataset.num_features, args.hidden, aggregator=args.aggregator)
                 self.conv2 = SAGEConv(args.hidden, dataset.num_classes, aggregator=args.aggregator)
 
-            def forward(self):
+            def forward(self, x=None, blocks=None):
+                if blocks is not None:      # a sampled mini-batch: x holds the rows of blocks[0]'s source nodes
+                    x = self.conv1(x, blocks[0], relu=True)
+                    x = self.conv2(x, blocks[1])
+                    return F.log_softmax(x, dim=1)
                 x = self.conv1(dataset.x, inputInfo.set_input(), relu=True)
                 x = self.conv2(x, inputInfo.set_hidden())
                 return F.log_softmax(x, dim=1)
@@ -291,9 +330,49 @@ def main(argv=None, capture=None):
         optimizer.step()
         return loss
 
-    if not use_graph:
+    if fanouts is not None:
+        # one epoch = the seeds 0 .. num_nodes-1 in batches; every batch samples its blocks with a fresh rng_seed, gathers
+        # the features of the first block's source nodes and makes one step on the batch's labels
+        from .sampling import NeighborSampler
+        sampler = NeighborSampler(inputInfo, fanouts)
+        all_nodes = torch.arange(dataset.num_nodes, dtype=torch.int32, device=device)
+        batches = [all_nodes[lo: lo + args.batch_size] for lo in range(0, dataset.num_nodes, args.batch_size)]
+        drawn = [0]
+        first_loss = [None]
+        if capture is not None:
+            capture.update(sampler=sampler)
+
+        def train():                                   # noqa: F811  (the mini-batch epoch replaces the full-graph step)
+            model.train()
+            loss = None
+            for seeds in batches:
+                blocks, input_nodes = sampler.sample(seeds, 0x5A17 + drawn[0] * len(fanouts))
+                drawn[0] += 1
+                optimizer.zero_grad()
+                loss = nll_loss(model(dataset.x.index_select(0, input_nodes), blocks), dataset.y.index_select(0, seeds))
+                loss.backward()
+                optimizer.step()
+                if first_loss[0] is None:
+                    first_loss[0] = float(loss.detach())
+                    if verbose_mode:
+                        print("# first loss: {:.6f}".format(first_loss[0]))
+            return loss
+
+        for _ in range(max(1, -(-10 // len(batches)))):   # dry run: at least 10 steps
+            loss = train()
+        torch.cuda.synchronize()
+        start_train = time.perf_counter()
+        for _ in range(1, args.num_epoches + 1):
+            loss = train()
+        torch.cuda.synchronize()
+        train_time = time.perf_counter() - start_train
+        if capture is not None:
+            capture.update(first_loss=first_loss[0], final_loss=float(loss.detach()))
+    elif not use_graph:
         for i in range(10):   # dry run
             loss = train()
+            if i == 0 and capture is not None:
+                capture.update(first_loss=float(loss.detach()))
             if i == 0 and verbose_mode:
                 print("# first loss: {:.6f}".format(float(loss)))
         torch.cuda.synchronize()

@@ -14,7 +14,8 @@ import torch
 from torch.autograd import Function
 from torch.nn import Module, Parameter
 
-from . import load_extension
+from . import _lib, load_extension
+from .sampling import SampledBlock
 
 GNNA = load_extension()
 
@@ -43,6 +44,42 @@ def _backward_graph(ctx):
     (decider.inputProperty.transposed, built on the device and cached), the forward graph itself when the structure is
     symmetric (``directed`` false: the reference's assumption and this package's default)."""
     return _graph_args(ctx.info.transposed()) if ctx.directed else ctx.graph
+
+
+# ---- sampled blocks (sampling.SampledBlock): rectangular, [num_src, F] -> [num_dst, F] ------------------------------------
+# The GraphSAGE operators take a block where they take an inputProperty.  Forward and backward go through the rectangular
+# entries of libgnna (gnna_agg_ld_f32, gnna_agg_reduce_ld_f32, gnna_scatter_arg_ld_f32); the backward of a sum aggregates dY over
+# block.transposed(), which is only built when the layer's input needs a gradient (the first layer's does not).
+
+def _is_block(info):
+    return isinstance(info, SampledBlock)
+
+
+def _refuse_block(info, layer):
+    if _is_block(info):
+        raise TypeError(f"{layer} does not take a SampledBlock: blocks are supported by the GraphSAGE operators "
+                        "(ScatterAndGather, NeighborMean, NeighborMax, NeighborMin, SAGEConv)")
+
+
+def _block_features(X, block, what):
+    if X.dtype != torch.float32:
+        raise TypeError(f"{what} on a SampledBlock: float32 features only (got {X.dtype})")
+    if X.dim() != 2 or X.shape[0] != block.num_src:
+        raise ValueError(f"{what} on a SampledBlock: X must be [num_src = {block.num_src}, F] (got {tuple(X.shape)})")
+    return X if X.shape[1] <= 1 or X.stride(1) == 1 else X.contiguous()
+
+
+def _block_sum(X, graph, num_out_rows):
+    """Neighbor sum over a block or its transpose: X [rows gathered from, F] -> [num_out_rows, F]."""
+    return _lib.agg_ld(_lib.MODE_SAG, X, graph.column_index, graph.partPtr, graph.part2Node, num_out_rows, graph.partSize)
+
+
+def _block_sum_backward(ctx, dY):
+    """A^T dY over the transposed block, or nothing when the layer's input needs no gradient."""
+    if not ctx.needs_input_grad[0]:
+        return None
+    block = ctx.block
+    return _block_sum(dY.contiguous(), block.transposed(), block.num_src)
 
 
 # ---- features stored in bfloat16 / float16 (libgnna gnna_agg_ld_x16: fp32 accumulation, one rounding of the result) ------
@@ -123,6 +160,9 @@ class ScatterAndGather(Function):
 
     @staticmethod
     def forward(ctx, X, inputInfo):
+        ctx.block = inputInfo if _is_block(inputInfo) else None
+        if ctx.block is not None:
+            return _block_sum(_block_features(X, inputInfo, "ScatterAndGather"), inputInfo, inputInfo.num_dst)
         _remember_graph(ctx, inputInfo)
         ctx.knobs = _knobs(inputInfo)
         if X.dtype in _X16:
@@ -131,6 +171,8 @@ class ScatterAndGather(Function):
 
     @staticmethod
     def backward(ctx, d_output):
+        if ctx.block is not None:
+            return _block_sum_backward(ctx, d_output), None
         bgraph = _backward_graph(ctx)
         if d_output.dtype in _X16:
             return _aggregate_x16(0, d_output, bgraph, ctx.knobs[0]), None
@@ -280,6 +322,7 @@ class GCNConv(_NeighborConv):
         """X: [num_nodes, input_dim]; inputInfo: decider.inputProperty holding the CSR, the
         sqrt-degree vector and the neighbor-group partition on X's device.  relu=True returns relu(layer) with the
         clamp fused into the aggregation (same values as F.relu(conv(X, inputInfo)))."""
+        _refuse_block(inputInfo, "GCNConv")
         dt = _x16_dtype(X)
         if dt is not None:      # bfloat16 / float16 features (a cast model, or torch.autocast): fp32 accumulation, 16-bit result
             return GNNAFunction_X16.apply(X, self.weights, inputInfo, 1, 1.0, True, relu, dt)
@@ -306,6 +349,7 @@ class GINConv(_NeighborConv):
     def forward(self, X, inputInfo, relu=False):
         """relu=True returns relu(layer): fused into the aggregation when the layer runs update-first (the aggregation is
         its last step), an ordinary F.relu behind the dense update otherwise."""
+        _refuse_block(inputInfo, "GINConv")
         dt = _x16_dtype(X)
         if dt is not None:
             return GNNAFunction_X16.apply(X, self.weights, inputInfo, 2, self.eplison, self._use_update_first(X), relu, dt)
@@ -318,6 +362,15 @@ class GINConv(_NeighborConv):
 # ---- max / min / mean over the neighbours, GraphSAGE ------------------------------------------------------------------
 
 def _extreme_forward(op, ctx, X, inputInfo):
+    ctx.block = inputInfo if _is_block(inputInfo) else None
+    if ctx.block is not None:
+        X = _block_features(X, inputInfo, "neighbor max / min")
+        ci = inputInfo.column_index
+        ctx.num_in_rows = X.shape[0]
+        Y, arg = _lib.agg_reduce_ld(op, X, ci, inputInfo.partPtr, inputInfo.part2Node, inputInfo.partSize,
+                                    num_out_rows=inputInfo.num_dst)
+        ctx.save_for_backward(arg, ci)
+        return Y
     if X.dtype != torch.float32:
         raise TypeError(f"neighbor max / min: float32 features only (got {X.dtype})")
     ci = inputInfo.column_index
@@ -329,6 +382,10 @@ def _extreme_forward(op, ctx, X, inputInfo):
 
 def _extreme_backward(ctx, dY):
     arg, ci = ctx.saved_tensors
+    if ctx.block is not None:
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        return _lib.scatter_arg_ld(dY.contiguous(), arg, ci, ctx.num_in_rows), None
     return GNNA.scatter_arg(dY.contiguous(), arg, ci, ctx.num_in_rows), None
 
 
@@ -362,6 +419,11 @@ class NeighborMean(Function):
 
     @staticmethod
     def forward(ctx, X, inputInfo):
+        ctx.block = inputInfo if _is_block(inputInfo) else None
+        if ctx.block is not None:
+            inv = inputInfo.inv_row_counts()
+            ctx.save_for_backward(inv)
+            return _block_sum(_block_features(X, inputInfo, "NeighborMean"), inputInfo, inputInfo.num_dst).mul_(inv.unsqueeze(1))
         if X.dtype != torch.float32:
             raise TypeError(f"NeighborMean: float32 features only (got {X.dtype})")
         _remember_graph(ctx, inputInfo)
@@ -373,6 +435,8 @@ class NeighborMean(Function):
     @staticmethod
     def backward(ctx, dY):
         inv, = ctx.saved_tensors
+        if ctx.block is not None:
+            return _block_sum_backward(ctx, dY * inv.unsqueeze(1)), None
         return GNNA.SAG(dY * inv.unsqueeze(1), *_backward_graph(ctx), *ctx.knobs), None
 
 
@@ -380,7 +444,9 @@ class SAGEConv(Module):
     """GraphSAGE layer: Y = X W_self + agg(X) W_neigh (+ b), agg the mean, the element-wise max or the element-wise min over
     every node's neighbours.  Both weights are drawn like the other layers' (U(-1/sqrt(out), 1/sqrt(out))).
     mean: when the layer narrows, X W_neigh is aggregated instead of X (the linear map commutes with the mean; the rule is
-    GINConv's).  max / min: the order is fixed -- aggregate, then multiply.  float32 only."""
+    GINConv's).  max / min: the order is fixed -- aggregate, then multiply.  float32 only.
+    `inputInfo` may be a sampling.SampledBlock: X is then [num_src, F], the result [num_dst, F], and the self term reads the
+    block's destination rows X[:num_dst]."""
 
     _AGG = {"mean": NeighborMean, "max": NeighborMax, "min": NeighborMin}
 
@@ -418,7 +484,7 @@ class SAGEConv(Module):
             N = agg.apply(torch.mm(X, self.weights_neigh), inputInfo)
         else:
             N = torch.mm(agg.apply(X, inputInfo), self.weights_neigh)
-        Y = torch.addmm(N, X, self.weights_self)
+        Y = torch.addmm(N, X[:inputInfo.num_dst] if _is_block(inputInfo) else X, self.weights_self)
         if self.bias is not None:
             Y = Y + self.bias
         return torch.relu(Y) if relu else Y
@@ -574,6 +640,7 @@ class GATConv(Module):
             self.att_r.uniform_(-bound, bound)
 
     def forward(self, X, inputInfo):
+        _refuse_block(inputInfo, "GATConv")
         n = X.shape[0]
         H = torch.mm(X, self.weights)
         Hh = H.view(n, self.heads, self.out_dim)

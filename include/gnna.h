@@ -127,6 +127,57 @@ GNNA_API int64_t gnna_count_parts_device_i32(int partSize, const int32_t *indptr
 GNNA_API int gnna_build_part_device_i32(int partSize, const int32_t *indptr, int64_t num_nodes,
         int32_t *partPtr /* [num_parts + 1] */, int32_t *part2Node /* [num_parts] */, int64_t num_parts, void *stream);
 
+/* ---- neighbor sampling (device; gnna_sample.hip) -----------------------------------------
+ * gnna_sample_neighbors_i32 builds one mini-batch BLOCK: the sampled edges of `num_seeds` destination rows as a rectangular
+ * CSR [num_seeds x num_src] over LOCAL source ids, the global id of every local source, and (optionally) the neighbor-group
+ * partition of the block -- what gnna_agg_ld_f32 / gnna_agg_reduce_ld_f32 / gnna_scatter_arg_ld_f32 take with
+ * num_out_rows = num_seeds and num_in_rows = num_src.  All pointers are DEVICE pointers except `counts`.  A prepare-time call
+ * like the structure builders above: ONE record (counts and an error word) is read back per call, which SYNCHRONISES `stream`
+ * once, and inside a stream capture the call returns GNNA_ERR_UNSUPPORTED.
+ *
+ * The sampling rule.
+ *   Destination row i of the block is node r = seeds[i].
+ *   Its candidate edges are the positions e in [row_pointers[r], row_pointers[r+1]).  Let d be their number.
+ *   If fanout <= 0 or d <= fanout, all of them are taken.
+ *   Otherwise the `fanout` positions with the smallest 64-bit key are taken, and a tie goes to the smaller e.
+ *   The key of position e is the splitmix64 finaliser, with all arithmetic mod 2^64:
+ *     z = rng_seed + 0x9E3779B97F4A7C15 * (e + 1)
+ *     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *     z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *     key = z ^ (z >> 31)
+ *   The taken positions are written in increasing e.
+ *   Random priorities give a uniform sample without replacement.
+ *   The result depends on nothing but (rng_seed, e).  It is the same bits for every launch shape and run.  No atomic ever
+ *   hands out a position.
+ *
+ * Local ids.
+ *   Local ids 0 .. num_seeds-1 are the seeds, in the order given: src_nodes[i] = seeds[i].  The destination features of a block
+ *   are therefore the first num_seeds rows of its source features.
+ *   Every other sampled source id gets a local id from num_seeds upwards, in increasing global id.
+ *   blk_column_index[p] is the local id of column_index[blk_edge_ids[p]].
+ *   Duplicate edges and self loops are kept as they are.
+ *
+ * Partition.  When partPtr and part2Node are given, they hold exactly what gnna_build_part_i32(partSize, blk_row_pointers,
+ *   num_seeds) writes, closing sentinel included (num_parts <= nnz of the block, so edge_capacity bounds both).
+ *
+ * counts (HOST, always written once the record is back): nnz of the block, num_src, num_parts (0 without a partition).
+ * Errors found on the device, returned as GNNA_ERR_INVALID_ARGUMENT with gnna_last_error() naming the cause: a seed outside
+ *   [0, num_nodes); a duplicate seed; a selected column id outside [0, num_nodes); a capacity that is too small -- then `counts`
+ *   still holds the needed sizes and the outputs are unspecified (nothing is written beyond a capacity).
+ * partSize <= 0 together with partition outputs, and negative sizes: GNNA_ERR_INVALID_ARGUMENT.  num_seeds = 0 is fine.
+ *   row_pointers must not decrease along the seeds' rows (a row whose pointers decrease counts as empty).
+ * Cost: the relabelling marks and scans one flag per node of the graph, so a call is O(num_nodes) work on top of the seeds'
+ *   rows; scratch (library scratch in a slot of its own, grow-only per stream) is 8 bytes per node + 4 per seed. */
+GNNA_API int gnna_sample_neighbors_i32(const int32_t *row_pointers, const int32_t *column_index, int64_t num_nodes,
+        const int32_t *seeds, int64_t num_seeds /* distinct ids in [0, num_nodes) */, int fanout /* >= 1; <= 0: every neighbour */,
+        uint64_t rng_seed, int partSize, int32_t *blk_row_pointers /* [num_seeds + 1] */,
+        int32_t *blk_column_index /* [edge_capacity], LOCAL source ids */,
+        int32_t *blk_edge_ids /* [edge_capacity], positions in column_index; may be NULL */,
+        int32_t *src_nodes /* [src_capacity], global id of every local source */,
+        int32_t *partPtr /* [edge_capacity + 1] */, int32_t *part2Node /* [edge_capacity] */ /* both may be NULL */,
+        int64_t edge_capacity, int64_t src_capacity, int64_t counts[3] /* HOST: nnz of the block, num_src, num_parts */,
+        void *stream);
+
 /* ---- graph inputs (host) --------------------------------------------------------------
  * Native counterparts of the reference loader's CSR construction
  * (GNNAdvisor/dataset.py:99-122) and of the renumbering hook (rabbit.reorder,
