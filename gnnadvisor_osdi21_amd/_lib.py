@@ -51,7 +51,8 @@ EXPORTS = ("gnna_version", "gnna_build_id", "gnna_last_error", "gnna_count_parts
            "gnna_debug_untrusted_copies", "gnna_agg_edge_ld_f32", "gnna_edge_softmax_f32", "gnna_edge_softmax_backward_f32",
            "gnna_reverse_edges_i32", "gnna_agg_ld_x16", "gnna_prepare_x16", "gnna_agg_reduce_ld_f32", "gnna_scatter_arg_ld_f32",
            "gnna_gat_forward_f32", "gnna_gat_backward_f32", "gnna_gat_backward_dir_f32", "gnna_transpose_csr_i32",
-           "gnna_count_parts_device_i32", "gnna_build_part_device_i32", "gnna_sample_neighbors_i32")
+           "gnna_count_parts_device_i32", "gnna_build_part_device_i32", "gnna_sample_neighbors_i32",
+           "gnna_agg_typed_expand_ld_f32", "gnna_agg_typed_contract_ld_f32", "gnna_typed_coef_grad_ld_f32")
 
 
 def load() -> ctypes.CDLL:
@@ -214,6 +215,15 @@ def load() -> ctypes.CDLL:
     L.gnna_sample_neighbors_i32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                                             ctypes.c_int, ctypes.c_uint64, ctypes.c_int] + [ctypes.c_void_p] * 6 + [
         ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]
+    for fn in (L.gnna_agg_typed_expand_ld_f32, L.gnna_agg_typed_contract_ld_f32):
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int] + [
+            ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_uint,
+                                    ctypes.c_void_p]
+    L.gnna_typed_coef_grad_ld_f32.restype = ctypes.c_int
+    L.gnna_typed_coef_grad_ld_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                              ctypes.c_int64] + [ctypes.c_void_p] * 6 + [
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p]
     _lib = L
     return L
 
@@ -1037,3 +1047,90 @@ def sample_neighbors(row_pointers, column_index, seeds, fanout, rng_seed, partSi
     return {"row_pointers": blk_rp, "column_index": blk_ci[:nnz], "edge_ids": eid[:nnz] if want_edge_ids else None,
             "src_nodes": src[:num_src], "partPtr": pp[:P + 1] if want_part else None,
             "part2Node": p2n[:P] if want_part else None, "num_dst": S, "num_src": num_src}
+
+
+# ---- relation-typed aggregation (gnna_typed.hip) ---------------------------------------------------------------------------
+TYPED_LDS_CELLS = 4096      # kTypedLdsCells: the coefficient table (rows padded to the kernel's stride) lives in LDS up to here
+TYPED_MAX_BASES = 16
+
+
+def _typed_edges(column_index, edge_type, edge_norm, device):
+    assert edge_type.dtype == torch.int32 and edge_type.is_contiguous() and edge_type.numel() == column_index.numel() \
+        and edge_type.device == device, "edge_type must be a contiguous int32 tensor indexed like column_index"
+    assert edge_norm is None or (edge_norm.dtype == torch.float32 and edge_norm.is_contiguous()
+                                 and edge_norm.numel() == column_index.numel() and edge_norm.device == device), \
+        "edge_norm must be a contiguous float32 tensor indexed like column_index"
+
+
+def _coef_table(coef, device):
+    assert coef.dtype == torch.float32 and coef.dim() == 2 and coef.is_contiguous() and coef.device == device, \
+        "coef must be a contiguous float32 [num_types, num_bases] tensor on the features' device"
+    return coef.shape[0], coef.shape[1]
+
+
+def agg_typed_expand(X, coef, column_index, edge_type, edge_norm, part_pointers, part2Node, num_out_rows, partSize=32, out=None):
+    """gnna_agg_typed_expand_ld_f32: out[i, b * dim + f] = sum_e n[e] * coef[t[e], b] * X[column_index[e], f] -> [num_out_rows,
+    num_bases * dim].  edge_type int32 / edge_norm float32 (or None: 1) are indexed like column_index.  Strided X / out as in
+    agg_ld."""
+    if not X.is_cuda:
+        raise GnnaError("aggregation needs device tensors: there is no CPU path in libgnna")
+    xp, n_in, dim, ld_x = _rows_view(X, "X")
+    R, B = _coef_table(coef, X.device)
+    _typed_edges(column_index, edge_type, edge_norm, X.device)
+    if out is None:
+        out = _fresh_output((num_out_rows, B * dim), X.device)
+    yp, n_out, width, ld_out = _rows_view(out, "out")
+    assert n_out == int(num_out_rows) and width == B * dim and out.device == X.device
+    with torch.cuda.device(X.device):
+        _check(load().gnna_agg_typed_expand_ld_f32(xp, ld_x, n_in, column_index.data_ptr(), edge_type.data_ptr(), _ptr(edge_norm),
+                                                   coef.data_ptr(), R, B, part_pointers.data_ptr(), part2Node.data_ptr(), yp,
+                                                   ld_out, int(num_out_rows), dim, part2Node.numel(), int(partSize), 0,
+                                                   _stream(X.device)))
+    return out
+
+
+def agg_typed_contract(G, coef, column_index, edge_type, edge_norm, part_pointers, part2Node, num_out_rows, partSize=32, out=None):
+    """gnna_agg_typed_contract_ld_f32: out[i, f] = sum_e n[e] * sum_b coef[t[e], b] * G[column_index[e], b * dim + f] for G
+    [num_in_rows, num_bases * dim] -> [num_out_rows, dim], over the structure given (the backward of agg_typed_expand: the
+    transposed structure, with edge_type / edge_norm permuted by its perm)."""
+    if not G.is_cuda:
+        raise GnnaError("aggregation needs device tensors: there is no CPU path in libgnna")
+    gp, n_in, width, ld_g = _rows_view(G, "G")
+    R, B = _coef_table(coef, G.device)
+    assert width % B == 0, "G must be [num_in_rows, num_bases * dim]"
+    dim = width // B
+    _typed_edges(column_index, edge_type, edge_norm, G.device)
+    if out is None:
+        out = _fresh_output((num_out_rows, dim), G.device)
+    yp, n_out, dim_o, ld_out = _rows_view(out, "out")
+    assert n_out == int(num_out_rows) and dim_o == dim and out.device == G.device
+    with torch.cuda.device(G.device):
+        _check(load().gnna_agg_typed_contract_ld_f32(gp, ld_g, n_in, column_index.data_ptr(), edge_type.data_ptr(), _ptr(edge_norm),
+                                                     coef.data_ptr(), R, B, part_pointers.data_ptr(), part2Node.data_ptr(), yp,
+                                                     ld_out, int(num_out_rows), dim, part2Node.numel(), int(partSize), 0,
+                                                     _stream(G.device)))
+    return out
+
+
+def typed_coef_grad(X, G, column_index, edge_type, edge_norm, part_pointers, part2Node, num_types, partSize=32, out=None,
+                    accumulate=False):
+    """gnna_typed_coef_grad_ld_f32: out[r, b] (+)= sum_{e: t[e] = r} n[e] * <X[column_index[e]], G[row(e), b * dim : (b + 1) * dim]>
+    for X [num_in_rows, dim] and G [num_out_rows, num_bases * dim] over the forward structure -> [num_types, num_bases]."""
+    if not X.is_cuda:
+        raise GnnaError("aggregation needs device tensors: there is no CPU path in libgnna")
+    xp, n_in, dim, ld_x = _rows_view(X, "X")
+    gp, n_out, width, ld_g = _rows_view(G, "G")
+    assert width % dim == 0 and G.device == X.device, "G must be [num_out_rows, num_bases * dim] on X's device"
+    B = width // dim
+    _typed_edges(column_index, edge_type, edge_norm, X.device)
+    if out is None:
+        assert not accumulate, "accumulate needs an existing `out`"
+        out = _fresh_output((int(num_types), B), X.device)
+    assert tuple(out.shape) == (int(num_types), B)
+    _coef_table(out, X.device)
+    with torch.cuda.device(X.device):
+        _check(load().gnna_typed_coef_grad_ld_f32(xp, ld_x, n_in, gp, ld_g, n_out, column_index.data_ptr(), edge_type.data_ptr(),
+                                                  _ptr(edge_norm), part_pointers.data_ptr(), part2Node.data_ptr(), out.data_ptr(),
+                                                  int(num_types), B, dim, part2Node.numel(), int(partSize),
+                                                  ACCUMULATE if accumulate else 0, _stream(X.device)))
+    return out

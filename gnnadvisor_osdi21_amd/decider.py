@@ -171,7 +171,8 @@ REORDER_S_PER_NODE = 3.9e-7
 REFERENCE_EPOCHS = 200 + 10          # GNNA_main.py:25 (--num_epoches) + the 10 dry runs (:188-189)
 
 
-def expected_aggregations(model, in_dim, hidden, classes, epochs=REFERENCE_EPOCHS, heads=1, aggregator="mean"):
+def expected_aggregations(model, in_dim, hidden, classes, epochs=REFERENCE_EPOCHS, heads=1, aggregator="mean",
+                          num_relations=1, num_bases=0):
     """[(feature width, aggregations at that width)] of a whole training run of the reference's models (GNNA_main.py:143-171):
     GCN aggregates X W, i.e. at each layer's OUTPUT width, forward and backward; GIN aggregates at each layer's input width
     (forward; backward too unless it is the first layer) or, evaluated update-first (ops.GINConv), at the output width.
@@ -179,9 +180,16 @@ def expected_aggregations(model, in_dim, hidden, classes, epochs=REFERENCE_EPOCH
     gather of dY): `heads` per step on the hidden layer, one on the output layer.
     GraphSAGE (main.py --model sage, two ops.SAGEConv layers): the mean aggregator follows GIN's rule per layer (the neighbor
     weights commute with the mean); max / min gather once per layer and step at the layer's INPUT width -- their backward
-    (scatter_arg) is num_nodes x width work, not a gather, and the first layer's features need no gradient."""
+    (scatter_arg) is num_nodes x width work, not a gather, and the first layer's features need no gradient.
+    R-GCN (main.py --model rgcn, two ops.RGCNConv layers, aggregate-first): an aggregation into B x D columns gathers D-wide rows,
+    so every layer gathers at its INPUT width -- forward, and once more for the coefficient gradient when the layer has bases;
+    the second layer's feature gradient gathers rows of B x hidden floats (B = num_bases, or num_relations without bases)."""
     units = lambda w: (int(w) + 63) // 64
     out = []
+    if model == "rgcn":
+        B = int(num_bases) if num_bases else int(num_relations)
+        per_layer = 2 if num_bases else 1
+        return [(in_dim, per_layer * epochs), (hidden, per_layer * epochs), (B * hidden, epochs)]
     if model == "sage":
         dims = [in_dim, hidden, classes]
         for i, (a, b) in enumerate(zip(dims[:-1], dims[1:])):

@@ -37,7 +37,12 @@ def build_parser():
     p.add_argument("--dim", type=int, default=96, help="input embedding dimension size")
     p.add_argument("--hidden", type=int, default=16, help="hidden dimension size")
     p.add_argument("--classes", type=int, default=22, help="output classes size")
-    p.add_argument('--model', type=str, default='gcn', choices=['gcn', 'gin', 'gat', 'sage'], help="GCN, GIN, GAT or GraphSAGE")
+    p.add_argument('--model', type=str, default='gcn', choices=['gcn', 'gin', 'gat', 'sage', 'rgcn'],
+                   help="GCN, GIN, GAT, GraphSAGE or R-GCN")
+    p.add_argument('--num_relations', type=int, default=4,
+                   help="--model rgcn: relation types of the edges (synthetic: a seeded hash of every edge's end points)")
+    p.add_argument('--num_bases', type=int, default=0,
+                   help="--model rgcn: bases of the weight decomposition W_r = sum_b c[r, b] V_b (0: none, one weight per relation)")
     p.add_argument('--aggregator', type=str, default='mean', choices=['mean', 'max', 'min'],
                    help="GraphSAGE: how a node's neighbours are reduced (mean, element-wise max or element-wise min)")
     p.add_argument('--heads', type=int, default=1, help="GAT: attention heads of the hidden layer (the output layer has one)")
@@ -104,6 +109,19 @@ def main(argv=None, capture=None):
     if args.dtype != 'float32' and args.model == 'sage':
         raise SystemExit("--dtype %s: the GraphSAGE layers (max / min / mean over the neighbours) are float32 only; "
                          "run --model sage with --dtype float32" % args.dtype)
+    if args.model == 'rgcn':
+        if flag(args.hip_graph):
+            # (the relational graph builds its transposed structure and permuted edge arrays at the first backward: not captured)
+            raise SystemExit("--model rgcn does not support --hip_graph True: run it with --hip_graph False")
+        if args.dtype != 'float32':
+            raise SystemExit("--dtype %s: the R-GCN layers (relation-typed aggregation) are float32 only; "
+                             "run --model rgcn with --dtype float32" % args.dtype)
+        if args.num_relations < 1:
+            raise SystemExit("--num_relations must be >= 1")
+        if not 0 <= args.num_bases <= 16:
+            raise SystemExit("--num_bases must be in 0 .. 16 (0: no decomposition)")
+        if args.num_bases == 0 and args.num_relations > 16:
+            raise SystemExit("--model rgcn without bases supports at most 16 relations: pass --num_bases")
     if args.dtype != 'float32' and flag(args.hip_graph):
         raise SystemExit("--dtype %s does not support --hip_graph True yet: run it with --hip_graph False" % args.dtype)
     if args.dtype != 'float32' and (flag(args.single_spmm) or flag(args.verify_spmm)):
@@ -145,7 +163,7 @@ def main(argv=None, capture=None):
     from . import load_extension
     from .decider import inputProperty
     from .loader import custom_dataset
-    from .ops import GATConv, GCNConv, GINConv, SAGEConv
+    from .ops import GATConv, GCNConv, GINConv, RGCNConv, SAGEConv
     GNNA = load_extension()
 
     # ---- loading data --------------------------------------------------------------------
@@ -169,7 +187,8 @@ def main(argv=None, capture=None):
     from .decider import expected_aggregations
     inputInfo.expected_aggregations = [(args.hidden, args.num_epoches)] if (single_spmm or verify_spmm) else \
         expected_aggregations(args.model, dataset.num_features, args.hidden, dataset.num_classes, args.num_epoches + 10,
-                              heads=args.heads, aggregator=args.aggregator)
+                              heads=args.heads, aggregator=args.aggregator, num_relations=args.num_relations,
+                              num_bases=args.num_bases)
     inputInfo.force_renumbering = flag(args.force_rabbit)
     inputInfo.decider()
     inputInfo = inputInfo.set_input()
@@ -288,6 +307,26 @@ def main(argv=None, capture=None):
                     return F.log_softmax(x, dim=1)
                 x = self.conv1(dataset.x, inputInfo.set_input(), relu=True)
                 x = self.conv2(x, inputInfo.set_hidden())
+                return F.log_softmax(x, dim=1)
+    elif args.model == 'rgcn':
+        # the types are made here, from the CSR the kernels run on: a renumbering (decider) cannot misalign them
+        from .relational import RelationalGraph, synthetic_edge_types
+        rel = RelationalGraph(inputInfo, synthetic_edge_types(inputInfo.row_pointers, inputInfo.column_index,
+                                                              args.num_relations, seed=0x52474E), args.num_relations)
+        rel.transposed()                # (the second layer's feature gradient runs on it: built here, not inside an epoch)
+        bases = args.num_bases or None
+        if capture is not None:
+            capture.update(rel=rel)
+
+        class Net(torch.nn.Module):
+            def __init__(self):
+                super().__init__()
+                self.conv1 = RGCNConv(dataset.num_features, args.hidden, args.num_relations, num_bases=bases)
+                self.conv2 = RGCNConv(args.hidden, dataset.num_classes, args.num_relations, num_bases=bases)
+
+            def forward(self):
+                x = self.conv1(dataset.x, rel, relu=True)
+                x = self.conv2(x, rel)
                 return F.log_softmax(x, dim=1)
     else:
         class Net(torch.nn.Module):

@@ -490,6 +490,100 @@ class SAGEConv(Module):
         return torch.relu(Y) if relu else Y
 
 
+# ---- relation-typed aggregation, R-GCN -------------------------------------------------------------------------------
+
+def _typed_features(X, rel, what):
+    from .relational import RelationalGraph
+    if not isinstance(rel, RelationalGraph):
+        raise TypeError(f"{what} takes a relational.RelationalGraph (got {type(rel).__name__})")
+    if X.dtype != torch.float32 or _x16_dtype(X) is not None:
+        raise TypeError(f"{what} computes in float32 only: 16-bit features and torch.autocast are not supported "
+                        f"(got {X.dtype}{', inside torch.autocast' if X.dtype == torch.float32 else ''})")
+    if X.dim() != 2 or X.shape[0] != rel.num_src:
+        raise ValueError(f"{what}: X must be [{rel.num_src}, F] (got {tuple(X.shape)})")
+    return X if X.shape[1] <= 1 or X.stride(1) == 1 else X.contiguous()
+
+
+class TypedAggregate(Function):
+    """``TypedAggregate.apply(X, coef, rel) -> T`` with T[i, b F + f] = sum_e n[e] coef[t[e], b] X[col(e), f] over the edges of
+    row i (libgnna gnna_agg_typed_expand_ld_f32): X [num_src, F], coef [num_relations, B], T [num_dst, B F]; t and n are
+    ``rel``'s edge types and factors.  One pass over the ids gathers every source row once for all B bases; no per-edge tensor is
+    made in forward or backward.  dX runs over ``rel.transposed()`` (gnna_agg_typed_contract_ld_f32), built at the first backward
+    that needs it and skipped when X needs no gradient; dcoef (gnna_typed_coef_grad_ld_f32) is skipped when coef needs none."""
+
+    @staticmethod
+    def forward(ctx, X, coef, rel):
+        X = _typed_features(X, rel, "TypedAggregate")
+        coef = coef.detach().float().contiguous()
+        ctx.rel = rel
+        ctx.save_for_backward(X, coef)
+        return rel.expand(X, coef)
+
+    @staticmethod
+    def backward(ctx, dT):
+        X, coef = ctx.saved_tensors
+        if dT.dim() == 2 and dT.shape[1] > 1 and dT.stride(1) != 1:
+            dT = dT.contiguous()
+        dX = ctx.rel.contract(dT, coef) if ctx.needs_input_grad[0] else None
+        dcoef = ctx.rel.coef_grad(X, dT) if ctx.needs_input_grad[1] else None
+        return dX, dcoef, None
+
+
+class RGCNConv(Module):
+    """Relational GCN layer in basis form: W_r = sum_b coef[r, b] V_b and
+        Y[i] = sum_r sum_{j in N_r(i)} n W_r^T X[j] + W_self^T X[i] + bias,
+    evaluated aggregate-first as ONE typed aggregation into a B-times wider matrix and ONE product:
+        T = TypedAggregate(X, coef, rel)  [num_dst, B in_dim],   Y = T V.view(B in_dim, out_dim) + X_dst W_self + bias.
+    num_bases=None is R-GCN without decomposition: B = num_relations (<= 16) and coef is the fixed identity.  ``rel`` is a
+    relational.RelationalGraph; over a SampledBlock the self term reads the block's destination rows X[:num_dst].  float32 only.
+    (The update-first order -- X V_b first, then a contraction -- is not implemented.)"""
+
+    def __init__(self, in_dim, out_dim, num_relations, num_bases=None, bias=True, self_loop=True):
+        super().__init__()
+        R = int(num_relations)
+        if R < 1:
+            raise ValueError("num_relations must be >= 1")
+        if num_bases is None:
+            if R > _lib.TYPED_MAX_BASES:
+                raise ValueError(f"RGCNConv without bases keeps one weight per relation and supports at most "
+                                 f"{_lib.TYPED_MAX_BASES} of them (got num_relations = {R}): pass num_bases")
+            B = R
+            self.register_buffer("coef", torch.eye(R))
+        else:
+            B = int(num_bases)
+            if not 1 <= B <= _lib.TYPED_MAX_BASES:
+                raise ValueError(f"num_bases must be in 1 .. {_lib.TYPED_MAX_BASES} (got {num_bases})")
+            self.coef = Parameter(torch.empty(R, B))
+        self.in_dim, self.out_dim, self.num_relations, self.num_bases = int(in_dim), int(out_dim), R, B
+        self.V = Parameter(torch.empty(B, self.in_dim, self.out_dim))
+        self.W_self = Parameter(torch.empty(self.in_dim, self.out_dim)) if self_loop else None
+        self.bias = Parameter(torch.empty(self.out_dim)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        bound = 1.0 / math.sqrt(self.out_dim)
+        with torch.no_grad():
+            self.V.uniform_(-bound, bound)
+            if isinstance(self.coef, Parameter):
+                self.coef.uniform_(-1.0 / math.sqrt(self.num_bases), 1.0 / math.sqrt(self.num_bases))
+            if self.W_self is not None:
+                self.W_self.uniform_(-bound, bound)
+            if self.bias is not None:
+                self.bias.zero_()
+
+    def forward(self, X, rel, relu=False):
+        X = _typed_features(X, rel, "RGCNConv")
+        if rel.num_relations != self.num_relations:
+            raise ValueError(f"the graph has {rel.num_relations} relations, the layer {self.num_relations}")
+        T = TypedAggregate.apply(X, self.coef, rel)
+        Y = torch.mm(T, self.V.view(self.num_bases * self.in_dim, self.out_dim))
+        if self.W_self is not None:
+            Y = torch.addmm(Y, X[:rel.num_dst] if rel.is_block else X, self.W_self)
+        if self.bias is not None:
+            Y = Y + self.bias
+        return torch.relu(Y) if relu else Y
+
+
 # ---- edge-valued aggregation, edge softmax, GAT ----------------------------------------------------------------------
 
 def _heads_of(w):

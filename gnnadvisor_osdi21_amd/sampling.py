@@ -74,9 +74,10 @@ class SampledBlock(object):
 class NeighborSampler(object):
     """``NeighborSampler(inputInfo, fanouts)``: `inputInfo` holds the full graph's device ``row_pointers`` / ``column_index``
     (a ``decider.inputProperty``, or any bundle with them); ``fanouts[l]`` is the number of neighbours layer `l` samples per
-    destination (<= 0: all of them).  partSize defaults to the bundle's."""
+    destination (<= 0: all of them).  partSize defaults to the bundle's.  want_edge_ids: the blocks keep ``edge_ids`` (what
+    per-edge data of the full graph -- relation types -- is read through)."""
 
-    def __init__(self, inputInfo, fanouts, partSize=None):
+    def __init__(self, inputInfo, fanouts, partSize=None, want_edge_ids=False):
         self.fanouts = [int(f) for f in fanouts]
         if not self.fanouts:
             raise ValueError("fanouts must name at least one layer")
@@ -86,6 +87,7 @@ class NeighborSampler(object):
         self.column_index = ci
         self.row_pointers = inputInfo.row_pointers.to(ci.device)
         self.partSize = int(partSize if partSize is not None else (getattr(inputInfo, "partSize", None) or 32))
+        self.want_edge_ids = bool(want_edge_ids)
 
     def sample(self, seeds, rng_seed):
         """-> (blocks, input_nodes).  Sampled from the batch outwards: the last layer's block has `seeds` as destinations, the
@@ -95,7 +97,7 @@ class NeighborSampler(object):
         blocks = []
         for layer in reversed(range(len(self.fanouts))):
             blk = SampledBlock.sample(self.row_pointers, self.column_index, dst, self.fanouts[layer], int(rng_seed) + layer,
-                                      self.partSize, want_edge_ids=False)
+                                      self.partSize, want_edge_ids=self.want_edge_ids)
             blocks.append(blk)
             dst = blk.src_nodes
         blocks.reverse()

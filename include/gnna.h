@@ -445,6 +445,51 @@ GNNA_API int gnna_gat_backward_dir_f32(const float *H, int64_t ld_h, const float
         float negative_slope, float *dH, int64_t ld_dh, float *d_el, float *d_er, int64_t num_nodes, int heads, int dim,
         int partSize, unsigned flags, void *stream);
 
+/* Relation-typed aggregation (gnna_typed.hip): what an R-GCN layer in basis form, W_r = sum_b C[r, b] V_b, needs around its one
+ * GEMM.  Every edge position e (indexed like column_index) has a type edge_type[e] in [0, num_types) and a factor edge_norm[e]
+ * (fp32; NULL: 1); coef is the table C [num_types, num_bases], contiguous fp32.  The weight of an edge for basis b,
+ * edge_norm[e] * C[edge_type[e], b], is made where the edge's row is gathered: no buffer of the size of the edge list is
+ * allocated, read or written by the library, and edge_type is read once per pass (once per column block of 256 floats when
+ * dim > 256).  All matrices are fp32 device pointers with leading dimensions in floats; the calls are rectangular
+ * (num_in_rows: rows gathered from; num_out_rows: rows of the structure, i.e. the values of part2Node) and take every partition
+ * gnna_agg_ld_f32 accepts (rows split over many groups, groups in any order, groups with decreasing pointers taken as empty).
+ *   expand:    out[i, b dim + f] = sum_{e in row i} edge_norm[e] C[edge_type[e], b] X[column_index[e], f]
+ *              X [num_in_rows, dim] (ld_x >= dim), out [num_out_rows, num_bases * dim] (ld_out >= num_bases * dim).  A source row is
+ *              gathered once per edge and feeds the num_bases accumulators of a lane.
+ *   contract:  out[i, f] = sum_{e in row i} edge_norm[e] sum_b C[edge_type[e], b] G[column_index[e], b dim + f]
+ *              G [num_in_rows, num_bases * dim] (ld_g >= num_bases * dim), out [num_out_rows, dim] (ld_out >= dim).  Runs over whatever
+ *              structure it is given: for the backward of expand the caller passes the transposed structure
+ *              (gnna_transpose_csr_i32 + gnna_build_part_device_i32) with edge_type / edge_norm permuted by t_perm.
+ *   coef grad: dcoef[r, b] = sum_{e: edge_type[e] = r} edge_norm[e] <X[column_index[e], :], G[row(e), b dim : (b + 1) dim]>
+ *              over the forward structure; X [num_in_rows, dim], G [num_out_rows, num_bases * dim], dcoef [num_types, num_bases]
+ *              contiguous.  Partial sums are kept per workgroup in an LDS table while num_types * (num_bases rounded up to a power
+ *              of two) <= 4096 cells, with one float atomic per non-zero cell and workgroup to dcoef; a larger table is added to
+ *              dcoef edge by edge.  dcoef is cleared first unless flags has GNNA_ACCUMULATE.
+ * An edge whose column id is outside [0, num_in_rows) or whose type is outside [0, num_types) counts for nothing, in all three
+ * alike: its row is not read and no entry of coef enters a sum on its behalf (a non-finite row of coef reaches only the edges of
+ * that type).  Outputs are zero-filled and rows meet through float atomics: no plan,
+ * no validation pass, no synchronisation, no library scratch (the calls work inside a stream capture as they stand) -- and no
+ * deterministic schedule: with gnna_tuning.deterministic = 1 the calls return GNNA_ERR_UNSUPPORTED, as gnna_agg_ld_x16 does.
+ * Limits (GNNA_ERR_UNSUPPORTED beyond): 1 <= num_bases <= 16, num_types >= 1, any dim >= 1 (dim % 4 != 0 and rows wider than one
+ * wave-wide load are handled inside the call), otherwise those of gnna_agg_ld_f32.  flags: GNNA_ACCUMULATE on the coef grad only
+ * (expand / contract: GNNA_ERR_UNSUPPORTED, as the GAT entries); GNNA_EPILOGUE_RELU is not accepted.  Sizes < 1 (num_types,
+ * num_bases, dim, partSize) or negative, null pointers, a leading dimension below the row width, an output that aliases an input:
+ * GNNA_ERR_INVALID_ARGUMENT, before any device work.  The aliasing check compares the output's address with those of the feature
+ * matrices, coef and edge_norm, as the neighbouring entries do: ranges that overlap at other addresses, or an output placed over
+ * one of the int32 arrays, are the caller's to avoid. */
+GNNA_API int gnna_agg_typed_expand_ld_f32(const float *X, int64_t ld_x, int64_t num_in_rows, const int32_t *column_index,
+        const int32_t *edge_type, const float *edge_norm, const float *coef, int num_types, int num_bases,
+        const int32_t *part_pointers, const int32_t *part2Node, float *out, int64_t ld_out, int64_t num_out_rows, int dim,
+        int64_t num_parts, int partSize, unsigned flags, void *stream);
+GNNA_API int gnna_agg_typed_contract_ld_f32(const float *G, int64_t ld_g, int64_t num_in_rows, const int32_t *column_index,
+        const int32_t *edge_type, const float *edge_norm, const float *coef, int num_types, int num_bases,
+        const int32_t *part_pointers, const int32_t *part2Node, float *out, int64_t ld_out, int64_t num_out_rows, int dim,
+        int64_t num_parts, int partSize, unsigned flags, void *stream);
+GNNA_API int gnna_typed_coef_grad_ld_f32(const float *X, int64_t ld_x, int64_t num_in_rows, const float *G, int64_t ld_g,
+        int64_t num_out_rows, const int32_t *column_index, const int32_t *edge_type, const float *edge_norm,
+        const int32_t *part_pointers, const int32_t *part2Node, float *dcoef, int num_types, int num_bases, int dim,
+        int64_t num_parts, int partSize, unsigned flags, void *stream);
+
 /* Reverse-edge map of a CSR whose structure is symmetric (host pointers): rev[e] is the position of the edge col(e) -> row(e)
  * that matches e; the k-th (i, j) of row i pairs with the k-th (j, i) of row j (positions in increasing order), a self loop
  * may pair with itself, rows need not be sorted.  gnna_host_threads() threads; the result does not depend on their number.
