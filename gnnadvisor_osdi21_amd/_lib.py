@@ -52,7 +52,8 @@ EXPORTS = ("gnna_version", "gnna_build_id", "gnna_last_error", "gnna_count_parts
            "gnna_reverse_edges_i32", "gnna_agg_ld_x16", "gnna_prepare_x16", "gnna_agg_reduce_ld_f32", "gnna_scatter_arg_ld_f32",
            "gnna_gat_forward_f32", "gnna_gat_backward_f32", "gnna_gat_backward_dir_f32", "gnna_transpose_csr_i32",
            "gnna_count_parts_device_i32", "gnna_build_part_device_i32", "gnna_sample_neighbors_i32",
-           "gnna_agg_typed_expand_ld_f32", "gnna_agg_typed_contract_ld_f32", "gnna_typed_coef_grad_ld_f32")
+           "gnna_agg_typed_expand_ld_f32", "gnna_agg_typed_contract_ld_f32", "gnna_typed_coef_grad_ld_f32",
+           "gnna_gat_forward_rect_f32", "gnna_gat_backward_rect_f32")
 
 
 def load() -> ctypes.CDLL:
@@ -204,6 +205,17 @@ def load() -> ctypes.CDLL:
         [ctypes.c_void_p] * 4 + [ctypes.c_int64]) * 2 + [
         ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
         ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p]
+    # the rectangular forms: (num_out_rows, num_in_rows) where the square ones take num_nodes
+    L.gnna_gat_forward_rect_f32.restype = ctypes.c_int
+    L.gnna_gat_forward_rect_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 6 + [
+        ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p]
+    L.gnna_gat_backward_rect_f32.restype = ctypes.c_int
+    L.gnna_gat_backward_rect_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64] + (
+        [ctypes.c_void_p] * 4 + [ctypes.c_int64]) * 2 + [
+        ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p]
     L.gnna_transpose_csr_i32.restype = ctypes.c_int
     L.gnna_transpose_csr_i32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 4
     L.gnna_count_parts_device_i32.restype = ctypes.c_int64
@@ -866,31 +878,54 @@ def scatter_arg_ld(grad_out, arg, column_index, num_in_rows, out=None, accumulat
 def _node_heads(t, n, what):
     """[n, heads] contiguous float32 device tensor -> heads."""
     assert t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == n and t.is_contiguous(), \
-        f"{what} must be a contiguous float32 [num_nodes, heads] tensor"
+        f"{what} must be a contiguous float32 [{n}, heads] tensor (num_nodes rows; on a rectangular structure el / lse / d_el " \
+        f"have num_out_rows rows, er / d_er num_in_rows)"
     return t.shape[1]
+
+
+def _gat_sizes(H, el, er, row_pointers):
+    """(H's pointer, num_out_rows, num_in_rows, width, heads, ld_h) of a GAT attention call, taken from the tensors:
+    num_in_rows = H.shape[0] = er.shape[0], num_out_rows = el.shape[0] = row_pointers.numel() - 1."""
+    hp, n_in, width, ld_h = _rows_view(H, "H")
+    assert el.dim() == 2 and row_pointers.dim() == 1, "el must be [num_out_rows, heads], row_pointers [num_out_rows + 1]"
+    n_out = el.shape[0]
+    assert row_pointers.numel() == n_out + 1, \
+        f"row_pointers must be [num_out_rows + 1] with num_out_rows = el.shape[0] = {n_out} (got {row_pointers.numel()} entries)"
+    heads = _node_heads(el, n_out, "el")
+    assert _node_heads(er, n_in, "er") == heads and heads >= 1 and width % heads == 0, \
+        "H must be [num_in_rows, heads * dim], er [num_in_rows, heads] and el [num_out_rows, heads]"
+    return hp, n_out, n_in, width, heads, ld_h
 
 
 def gat_forward(H, el, er, row_pointers, column_index, part_pointers, part2Node, partSize=32, negative_slope=0.2, out=None,
                 lse=None, relu=False):
     """gnna_gat_forward_f32: fused multi-head GAT attention.  H [N, heads * dim], el / er [N, heads] -> (out, lse) with
     out[i, h] = sum_e alpha(e, h) H[col(e), h], alpha = exp(leaky_relu(el[i, h] + er[j, h]) - lse[i, h]); no per-edge tensor.
-    `H` and `out` may be row-strided views (stride(1) == 1): they are passed with their leading dimension."""
+    `H` and `out` may be row-strided views (stride(1) == 1): they are passed with their leading dimension.
+    Rectangular structures (a sampled block): H [num_in_rows, heads * dim], er [num_in_rows, heads], el [num_out_rows, heads]
+    with num_out_rows = row_pointers.numel() - 1 -> out [num_out_rows, heads * dim], lse [num_out_rows, heads]; when the two
+    counts differ the call is gnna_gat_forward_rect_f32."""
     if not H.is_cuda:
         raise GnnaError("GAT attention needs device tensors: there is no CPU path in libgnna")
-    hp, n, width, ld_h = _rows_view(H, "H")
-    heads = _node_heads(el, n, "el")
-    assert _node_heads(er, n, "er") == heads and heads >= 1 and width % heads == 0, "H must be [num_nodes, heads * dim]"
+    hp, n_out, n_in, width, heads, ld_h = _gat_sizes(H, el, er, row_pointers)
     if out is None:
-        out = _fresh_output((n, width), H.device)
+        out = _fresh_output((n_out, width), H.device)
     if lse is None:
-        lse = _fresh_output((n, heads), H.device)
+        lse = _fresh_output((n_out, heads), H.device)
     op_, n_o, width_o, ld_out = _rows_view(out, "out")
-    assert n_o == n and width_o == width and _node_heads(lse, n, "lse") == heads
+    assert n_o == n_out and width_o == width and _node_heads(lse, n_out, "lse") == heads
+    flags = EPILOGUE_RELU if relu else 0
     with torch.cuda.device(H.device):
-        _check(load().gnna_gat_forward_f32(hp, ld_h, el.data_ptr(), er.data_ptr(), row_pointers.data_ptr(), column_index.data_ptr(),
-                                           part_pointers.data_ptr(), part2Node.data_ptr(), float(negative_slope), op_, ld_out,
-                                           lse.data_ptr(), n, heads, width // heads, part2Node.numel(), int(partSize),
-                                           EPILOGUE_RELU if relu else 0, _stream(H.device)))
+        if n_out == n_in:
+            _check(load().gnna_gat_forward_f32(hp, ld_h, el.data_ptr(), er.data_ptr(), row_pointers.data_ptr(),
+                                               column_index.data_ptr(), part_pointers.data_ptr(), part2Node.data_ptr(),
+                                               float(negative_slope), op_, ld_out, lse.data_ptr(), n_out, heads, width // heads,
+                                               part2Node.numel(), int(partSize), flags, _stream(H.device)))
+        else:
+            _check(load().gnna_gat_forward_rect_f32(hp, ld_h, el.data_ptr(), er.data_ptr(), row_pointers.data_ptr(),
+                                                    column_index.data_ptr(), part_pointers.data_ptr(), part2Node.data_ptr(),
+                                                    float(negative_slope), op_, ld_out, lse.data_ptr(), n_out, n_in, heads,
+                                                    width // heads, part2Node.numel(), int(partSize), flags, _stream(H.device)))
     return out, lse
 
 
@@ -899,39 +934,49 @@ def gat_backward(H, el, er, lse, Y, dY, row_pointers, column_index, part_pointer
     """gnna_gat_backward_f32: (dH, d_el, d_er) of gat_forward for the gradient dY of its output Y, on a graph whose structure
     is symmetric (not checked here).  dH is the attention part only (sum alpha dY); strided H / Y / dY / dH as in gat_forward.
     transposed = (t_row_pointers, t_column_index, t_part_pointers, t_part2Node) of `transpose_csr` / `build_part_device` at the
-    same partSize: gnna_gat_backward_dir_f32, exact on a directed graph."""
+    same partSize: gnna_gat_backward_dir_f32, exact on a directed graph.
+    Rectangular structures (sizes as in gat_forward; Y, dY, lse have num_out_rows rows): gnna_gat_backward_rect_f32, which needs
+    `transposed` (num_in_rows rows) -> dH [num_in_rows, heads * dim], d_el [num_out_rows, heads], d_er [num_in_rows, heads]."""
     if not H.is_cuda:
         raise GnnaError("GAT attention needs device tensors: there is no CPU path in libgnna")
-    hp, n, width, ld_h = _rows_view(H, "H")
+    hp, n_out, n_in, width, heads, ld_h = _gat_sizes(H, el, er, row_pointers)
     yp, n_y, width_y, ld_y = _rows_view(Y, "Y")
     gp, n_g, width_g, ld_g = _rows_view(dY, "dY")
-    heads = _node_heads(el, n, "el")
-    assert _node_heads(er, n, "er") == heads and _node_heads(lse, n, "lse") == heads and width % heads == 0
-    assert (n_y, width_y) == (n, width) and (n_g, width_g) == (n, width), "Y and dY must have the shape of H"
+    assert _node_heads(lse, n_out, "lse") == heads
+    assert (n_y, width_y) == (n_out, width) and (n_g, width_g) == (n_out, width), \
+        "Y and dY must be [num_out_rows, heads * dim] (the shape of H on a square graph)"
+    rect = n_out != n_in
+    if rect and transposed is None:
+        raise GnnaError(f"GAT attention backward on a rectangular structure ({n_out} destination rows, {n_in} source rows) needs "
+                        "`transposed`: a rectangular structure is never its own transpose")
     if dH is None:
-        dH = _fresh_output((n, width), H.device)
+        dH = _fresh_output((n_in, width), H.device)
     dp, n_d, width_d, ld_d = _rows_view(dH, "dH")
-    assert (n_d, width_d) == (n, width)
-    d_el, d_er = _fresh_output((n, heads), H.device), _fresh_output((n, heads), H.device)
+    assert (n_d, width_d) == (n_in, width), "dH must have the shape of H"
     if transposed is not None:
         t_rp, t_ci, t_pp, t_p2n = transposed
         for t in (column_index, part_pointers, part2Node, t_rp, t_ci, t_pp, t_p2n):
             assert t.dtype == torch.int32 and t.is_contiguous() and t.device == H.device, \
                 "the graph and its transpose must be contiguous int32 tensors on H's device"
-        assert t_rp.numel() == n + 1 and t_pp.numel() == t_p2n.numel() + 1, "transposed: [N + 1] row pointers, [P + 1] / [P] partition"
+        assert t_rp.numel() == n_in + 1 and t_pp.numel() == t_p2n.numel() + 1, \
+            "transposed: [num_in_rows + 1] row pointers, [P + 1] / [P] partition"
+    d_el, d_er = _fresh_output((n_out, heads), H.device), _fresh_output((n_in, heads), H.device)
+    if transposed is not None:
+        entry = load().gnna_gat_backward_rect_f32 if rect else load().gnna_gat_backward_dir_f32
+        sizes = (n_out, n_in) if rect else (n_out,)
         with torch.cuda.device(H.device):
-            _check(load().gnna_gat_backward_dir_f32(hp, ld_h, el.data_ptr(), er.data_ptr(), lse.data_ptr(), yp, ld_y, gp, ld_g,
-                                                    row_pointers.data_ptr(), column_index.data_ptr(), part_pointers.data_ptr(),
-                                                    part2Node.data_ptr(), part2Node.numel(), t_rp.data_ptr(), t_ci.data_ptr(),
-                                                    t_pp.data_ptr(), t_p2n.data_ptr(), t_p2n.numel(), float(negative_slope), dp, ld_d,
-                                                    d_el.data_ptr(), d_er.data_ptr(), n, heads, width // heads, int(partSize), 0,
-                                                    _stream(H.device)))
+            _check(entry(hp, ld_h, el.data_ptr(), er.data_ptr(), lse.data_ptr(), yp, ld_y, gp, ld_g,
+                         row_pointers.data_ptr(), column_index.data_ptr(), part_pointers.data_ptr(),
+                         part2Node.data_ptr(), part2Node.numel(), t_rp.data_ptr(), t_ci.data_ptr(),
+                         t_pp.data_ptr(), t_p2n.data_ptr(), t_p2n.numel(), float(negative_slope), dp, ld_d,
+                         d_el.data_ptr(), d_er.data_ptr(), *sizes, heads, width // heads, int(partSize), 0,
+                         _stream(H.device)))
         return dH, d_el, d_er
     with torch.cuda.device(H.device):
         _check(load().gnna_gat_backward_f32(hp, ld_h, el.data_ptr(), er.data_ptr(), lse.data_ptr(), yp, ld_y, gp, ld_g,
                                             row_pointers.data_ptr(), column_index.data_ptr(), part_pointers.data_ptr(),
                                             part2Node.data_ptr(), float(negative_slope), dp, ld_d, d_el.data_ptr(), d_er.data_ptr(),
-                                            n, heads, width // heads, part2Node.numel(), int(partSize), 0, _stream(H.device)))
+                                            n_out, heads, width // heads, part2Node.numel(), int(partSize), 0, _stream(H.device)))
     return dH, d_el, d_er
 
 

@@ -1,4 +1,5 @@
-// gnna_gat.hip -- fused multi-head GAT attention, forward and backward (gnna_gat_forward_f32 / gnna_gat_backward_f32).
+// gnna_gat.hip -- fused multi-head GAT attention, forward and backward (gnna_gat_forward_f32 / gnna_gat_backward_f32 and their
+// rectangular forms gnna_gat_forward_rect_f32 / gnna_gat_backward_rect_f32, which the square entries call).
 // CDNA4 / gfx950 only.  No counterpart in the reference (it has no attention layer).
 //
 // With lse[i, h] = logsumexp over the edges of row i of s = leaky_relu(el[i, h] + er[j, h]) known, the attention coefficient of
@@ -26,6 +27,14 @@
 // the call.  dim % 4 != 0: the last lane of a head loads its 1..3 floats one by one; nothing is staged.  At the end of a run the
 // 64 / LPR partial rows meet by a butterfly and are ADDED with float atomics (correct for every partition gnna_agg_ld_f32
 // accepts, no validation pass), so the outputs are zero-filled first and there is no deterministic schedule for these passes.
+//
+// Rectangular structures (sampled blocks): num_out_rows destination rows gather from num_in_rows source rows, so every pass has
+// two bounds -- one for the rows it walks (what part2Node names), one for the ids it gathers:
+//     pass                         rows < (indexed by row)                      ids < (indexed by id)
+//     gat_lse_kernel               num_out_rows (el, lse)                       num_in_rows (er)
+//     gat_pull_kernel<FWD>         num_out_rows (el, lse, out)                  num_in_rows (H, er)
+//     gat_pull_kernel<BWD_DST>     num_out_rows (pack, dY, d_el)                num_in_rows (H, er)
+//     gat_pull_kernel<BWD_SRC>     num_in_rows  (er, H, dH, d_er)               num_out_rows (dY, pack)     [transposed structure]
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -115,7 +124,7 @@ __device__ __forceinline__ MaxSum seg_reduce(MaxSum v, int w)
 // One row [beg, end) swept by `nl` lanes (this one: index t), four edges per lane and step, HB heads from hb0 on.
 template <int HB>
 __device__ __forceinline__ void lse_row(const float *__restrict__ el_row, const float *__restrict__ er,
-                                        const int32_t *__restrict__ col, int64_t beg, int64_t end, int t, int nl, uint32_t N,
+                                        const int32_t *__restrict__ col, int64_t beg, int64_t end, int t, int nl, uint32_t M,
                                         int heads, int hb0, float slope, MaxSum acc[HB])
 {
     float eli[HB];
@@ -130,7 +139,7 @@ __device__ __forceinline__ void lse_row(const float *__restrict__ el_row, const 
         for (int k = 0; k < 4; k++) {
             const int64_t ee = e + (int64_t)k * nl;
             id[k] = ee < end ? col[ee] : -1;
-            if ((uint32_t)id[k] >= N) id[k] = -1;                  // an id outside the graph is skipped, in every pass alike
+            if ((uint32_t)id[k] >= M) id[k] = -1;                  // an id outside the source rows is skipped, in every pass alike
         }
 #pragma unroll
         for (int hh = 0; hh < HB; hh++) {
@@ -147,11 +156,11 @@ __device__ __forceinline__ void lse_row(const float *__restrict__ el_row, const 
 
 __device__ __forceinline__ float lse_of(MaxSum v) { return v.m == -INFINITY ? 0.f : v.m + logf(v.l); }
 
-// blockIdx.y: block of HB heads.  seg: lanes per row (4 .. 64, a power of two).
+// blockIdx.y: block of HB heads.  seg: lanes per row (4 .. 64, a power of two).  N rows (el, lse), ids < M (er).
 template <int HB>
 __global__ void __launch_bounds__(kBlock)
 gat_lse_kernel(const float *__restrict__ el, const float *__restrict__ er, const int32_t *__restrict__ rp,
-               const int32_t *__restrict__ col, int64_t N, int heads, float slope, float *__restrict__ lse, int seg)
+               const int32_t *__restrict__ col, int64_t N, int64_t M, int heads, float slope, float *__restrict__ lse, int seg)
 {
     constexpr int kMaxTile = kWavesPerBlock * (kWave / 4);
     __shared__ int s_long[kMaxTile];
@@ -178,7 +187,7 @@ gat_lse_kernel(const float *__restrict__ el, const float *__restrict__ er, const
     // short rows (and rows without edges: lse = 0): the segment -- every lane of a segment takes the same branch
     if (row < N && !is_long) {
         MaxSum acc[HB];
-        lse_row<HB>(el + (size_t)row * heads, er, col, beg, end, t, seg, (uint32_t)N, heads, hb0, slope, acc);
+        lse_row<HB>(el + (size_t)row * heads, er, col, beg, end, t, seg, (uint32_t)M, heads, hb0, slope, acc);
 #pragma unroll
         for (int hh = 0; hh < HB; hh++) {
             const MaxSum v = seg_reduce(acc[hh], seg);
@@ -191,7 +200,7 @@ gat_lse_kernel(const float *__restrict__ el, const float *__restrict__ er, const
     for (int q = 0; q < nlong; q++) {
         const int64_t rr = r0 + s_long[q];
         MaxSum acc[HB];
-        lse_row<HB>(el + (size_t)rr * heads, er, col, rp[rr], rp[rr + 1], tid, kBlock, (uint32_t)N, heads, hb0, slope, acc);
+        lse_row<HB>(el + (size_t)rr * heads, er, col, rp[rr], rp[rr + 1], tid, kBlock, (uint32_t)M, heads, hb0, slope, acc);
 #pragma unroll
         for (int hh = 0; hh < HB; hh++) {
             const MaxSum v = seg_reduce(acc[hh], kWave);
@@ -229,14 +238,14 @@ gat_pack_kernel(const float *__restrict__ G, size_t ldg, const float *__restrict
 struct GatArgs {
     const float *own; size_t ld_own;      // the row's own features: dY (SIDE_BWD_DST), H (SIDE_BWD_SRC); unused forward
     const float *gat; size_t ld_gat;      // the gathered rows: H (SIDE_FWD, SIDE_BWD_DST), dY (SIDE_BWD_SRC)
-    const float *el, *er, *lse;           // [N, heads]; el and lse: forward only
-    const VT *pack;                       // backward: (el, lse, c, 0) per (node, head)
+    const float *el, *er, *lse;           // [rows, heads]; el and lse: forward only.  er: by id (SIDE_BWD_SRC: by row)
+    const VT *pack;                       // backward: (el, lse, c, 0) per (destination row, head)
     const int32_t *col, *pp, *p2n;
     float *out; size_t ld_out;            // out (SIDE_FWD), dH (SIDE_BWD_SRC): zero-filled, added to
-    float *dsc;                           // d_el (SIDE_BWD_DST), d_er (SIDE_BWD_SRC): [N, heads], zero-filled, added to
+    float *dsc;                           // d_el (SIDE_BWD_DST), d_er (SIDE_BWD_SRC): [rows, heads], zero-filled, added to
     float slope;
     int64_t P;
-    uint32_t N;
+    uint32_t N, M;                        // rows of the structure walked (part2Node < N), rows gathered from (ids < M)
     int heads, dim, G, xcd_remap;
 };
 
@@ -268,7 +277,7 @@ gat_pull_kernel(const GatArgs p)
         e = p.pp[g0 + lane + 1];
         r = p.p2n[g0 + lane];
     }
-    // a group without edges, with a negative range or with a row outside the graph contributes nothing and ends the run
+    // a group without edges, with a negative range or with a row outside its side's rows contributes nothing and ends the run
     const bool bad = lane >= cnt || e <= s || s < 0 || (uint32_t)r >= p.N;
     const int prev_r = __shfl_up(r, 1);
     const int prev_bad = __shfl_up((int)bad, 1);
@@ -309,7 +318,7 @@ gat_pull_kernel(const GatArgs p)
                 int id = -1;
                 if (lane < nb) {
                     id = p.col[(int64_t)e0 + lane];
-                    if ((uint32_t)id >= p.N) id = -1;           // (an id outside the graph is skipped, never read)
+                    if ((uint32_t)id >= p.M) id = -1;           // (an id outside the gathered side is skipped, never read)
                 }
 #pragma unroll
                 for (int u0 = 0; u0 < LPR; u0 += U) {
@@ -429,7 +438,7 @@ unsigned grid_for(size_t work_items, int num_cus)
     return (unsigned)std::max<size_t>(1, std::min<size_t>(blocks, (size_t)num_cus * 8));
 }
 
-int launch_lse(hipStream_t stream, const float *el, const float *er, const int32_t *rp, const int32_t *col, int64_t N,
+int launch_lse(hipStream_t stream, const float *el, const float *er, const int32_t *rp, const int32_t *col, int64_t N, int64_t M,
                int64_t avg, int heads, float slope, float *lse)
 {
     // lanes per row: about a quarter of the average degree (every lane reads 4 edges per step), 4 .. 64
@@ -441,28 +450,33 @@ int launch_lse(hipStream_t stream, const float *el, const float *er, const int32
     while (hb < 8 && hb < heads) hb <<= 1;
     const dim3 grid((unsigned)blocks, (unsigned)((heads + hb - 1) / hb));
     switch (hb) {
-    case 1: hipLaunchKernelGGL(gat_lse_kernel<1>, grid, dim3(kBlock), 0, stream, el, er, rp, col, N, heads, slope, lse, seg); break;
-    case 2: hipLaunchKernelGGL(gat_lse_kernel<2>, grid, dim3(kBlock), 0, stream, el, er, rp, col, N, heads, slope, lse, seg); break;
-    case 4: hipLaunchKernelGGL(gat_lse_kernel<4>, grid, dim3(kBlock), 0, stream, el, er, rp, col, N, heads, slope, lse, seg); break;
-    default: hipLaunchKernelGGL(gat_lse_kernel<8>, grid, dim3(kBlock), 0, stream, el, er, rp, col, N, heads, slope, lse, seg); break;
+    case 1: hipLaunchKernelGGL(gat_lse_kernel<1>, grid, dim3(kBlock), 0, stream, el, er, rp, col, N, M, heads, slope, lse, seg); break;
+    case 2: hipLaunchKernelGGL(gat_lse_kernel<2>, grid, dim3(kBlock), 0, stream, el, er, rp, col, N, M, heads, slope, lse, seg); break;
+    case 4: hipLaunchKernelGGL(gat_lse_kernel<4>, grid, dim3(kBlock), 0, stream, el, er, rp, col, N, M, heads, slope, lse, seg); break;
+    default: hipLaunchKernelGGL(gat_lse_kernel<8>, grid, dim3(kBlock), 0, stream, el, er, rp, col, N, M, heads, slope, lse, seg); break;
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(GNNA_ERR_HIP, "GAT lse launch: %s", hipGetErrorString(e));
     return GNNA_OK;
 }
 
-// what both entry points check alike
-int check_common(const char *what, int64_t num_nodes, int heads, int dim, int64_t num_parts, int partSize, unsigned flags,
-                 unsigned allowed_flags)
+// what both entry points check alike.  rect: the rectangular entries name both row counts in their messages.
+int check_common(const char *what, bool rect, int64_t num_out_rows, int64_t num_in_rows, int heads, int dim, int64_t num_parts,
+                 int partSize, unsigned flags, unsigned allowed_flags)
 {
     if (flags & GNNA_ACCUMULATE) return fail(GNNA_ERR_UNSUPPORTED, "%s: GNNA_ACCUMULATE is not supported", what);
     if (flags & ~allowed_flags) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", what, flags);
-    if (num_nodes < 0 || num_parts < 0 || heads < 1 || dim < 1)
+    if (num_out_rows < 0 || num_in_rows < 0 || num_parts < 0 || heads < 1 || dim < 1) {
+        if (rect)
+            return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: bad size (num_out_rows=%lld num_in_rows=%lld heads=%d dim=%d num_parts=%lld)",
+                        what, (long long)num_out_rows, (long long)num_in_rows, heads, dim, (long long)num_parts);
         return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: bad size (num_nodes=%lld heads=%d dim=%d num_parts=%lld)", what,
-                    (long long)num_nodes, heads, dim, (long long)num_parts);
+                    (long long)num_out_rows, heads, dim, (long long)num_parts);
+    }
     if (partSize <= 0) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: partSize must be positive (got %d)", what, partSize);
-    if (num_nodes >= ((int64_t)1 << 29))
-        return fail(GNNA_ERR_UNSUPPORTED, "%s: %lld rows in one call (at most 536870911): shard the rows", what, (long long)num_nodes);
+    const int64_t most = std::max(num_out_rows, num_in_rows);
+    if (most >= ((int64_t)1 << 29))
+        return fail(GNNA_ERR_UNSUPPORTED, "%s: %lld rows in one call (at most 536870911): shard the rows", what, (long long)most);
     if (dim > kMaxDim) return fail(GNNA_ERR_UNSUPPORTED, "%s: at most %d floats per head (got %d)", what, kMaxDim, dim);
     if (heads > 64) return fail(GNNA_ERR_UNSUPPORTED, "%s: at most 64 heads (got %d)", what, heads);
     gnna_tuning tune;
@@ -475,6 +489,124 @@ int check_common(const char *what, int64_t num_nodes, int heads, int dim, int64_
 }
 
 bool bad_ld(int64_t ld, int64_t width) { return ld < width || ld >= ((int64_t)1 << 29); }
+
+// The forward of both entries: num_out_rows rows (el, lse, out) gather from num_in_rows rows (H, er).
+int gat_forward_impl(const char *what, bool rect, const float *H, int64_t ld_h, const float *el, const float *er,
+                     const int32_t *row_pointers, const int32_t *column_index, const int32_t *part_pointers,
+                     const int32_t *part2Node, float negative_slope, float *out, int64_t ld_out, float *lse, int64_t num_out_rows,
+                     int64_t num_in_rows, int heads, int dim, int64_t num_parts, int partSize, unsigned flags, void *stream_v)
+{
+    int rc = check_common(what, rect, num_out_rows, num_in_rows, heads, dim, num_parts, partSize, flags,
+                          GNNA_ACCUMULATE | GNNA_EPILOGUE_RELU);
+    if (rc != GNNA_OK) return rc;
+    if (num_out_rows == 0) return GNNA_OK;                    // nothing to write
+    const int64_t W = (int64_t)heads * dim;
+    const bool no_in = num_in_rows == 0;                      // every id is out of range: out = 0, lse = 0, H / el / er not read
+    if ((!no_in && bad_ld(ld_h, W)) || bad_ld(ld_out, W))
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: row strides must be >= heads * dim and < 2^29 floats (ld_h=%lld ld_out=%lld)",
+                    what, (long long)ld_h, (long long)ld_out);
+    if ((!no_in && (!H || !el || !er || !row_pointers)) || !out || !lse) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
+    if (!no_in && num_parts > 0 && (!column_index || !part_pointers || !part2Node))
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null index pointer", what);
+    if (out == H || out == el || out == er || out == lse || lse == el || lse == er || lse == H)
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: an output must not alias an input or the other output", what);
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    DeviceState *ds = nullptr;
+    rc = get_device_state(&ds);
+    if (rc != GNNA_OK) return rc;
+    rc = launch_zero_fill(ds, stream, out, num_out_rows, (int)W, ld_out);
+    if (rc != GNNA_OK) return rc;
+    if (num_parts == 0 || no_in) return launch_zero_fill(ds, stream, lse, num_out_rows, heads, heads);
+    gnna_tuning tune;
+    gnna_get_tuning(&tune);
+    apply_graph_hints(column_index, (int)W, &tune);
+    // edges per row, for the segment width of the lse pass only: the graph's hint, else what the groups can hold at most
+    const int64_t avg = tune.avg_degree > 0 ? tune.avg_degree : (num_parts * (int64_t)partSize + num_out_rows - 1) / num_out_rows;
+    rc = launch_lse(stream, el, er, row_pointers, column_index, num_out_rows, num_in_rows, avg, heads, negative_slope, lse);
+    if (rc != GNNA_OK) return rc;
+    GatArgs a{};
+    a.gat = H; a.ld_gat = (size_t)ld_h; a.el = el; a.er = er; a.lse = lse;
+    a.col = column_index; a.pp = part_pointers; a.p2n = part2Node; a.out = out; a.ld_out = (size_t)ld_out;
+    a.slope = negative_slope; a.P = num_parts; a.N = (uint32_t)num_out_rows; a.M = (uint32_t)num_in_rows; a.heads = heads; a.dim = dim;
+    a.xcd_remap = tune.xcd_remap != 0 ? 1 : 0;
+    rc = launch_pull<SIDE_FWD>(ds, stream, a, partSize);
+    if (rc != GNNA_OK) return rc;
+    if (flags & GNNA_EPILOGUE_RELU) {
+        hipLaunchKernelGGL(gat_relu_kernel, dim3(grid_for((size_t)num_out_rows * (size_t)W, ds->num_cus)), dim3(kBlock), 0, stream,
+                           out, (size_t)ld_out, (size_t)num_out_rows, (int)W);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(GNNA_ERR_HIP, "%s: epilogue launch: %s", what, hipGetErrorString(e));
+    }
+    return GNNA_OK;
+}
+
+// The backward of all entries: the destination-side pass walks the structure (num_out_rows rows, ids < num_in_rows), the
+// source-side pass the transposed one (num_in_rows rows, ids < num_out_rows).
+int gat_backward_impl(const char *what, bool rect, const float *H, int64_t ld_h, const float *el, const float *er, const float *lse,
+                      const float *Y, int64_t ld_y, const float *dY, int64_t ld_dy, const int32_t *column_index,
+                      const int32_t *part_pointers, const int32_t *part2Node, int64_t num_parts, const int32_t *t_column_index,
+                      const int32_t *t_part_pointers, const int32_t *t_part2Node, int64_t t_num_parts, float negative_slope,
+                      float *dH, int64_t ld_dh, float *d_el, float *d_er, int64_t num_out_rows, int64_t num_in_rows, int heads,
+                      int dim, int partSize, unsigned flags, void *stream_v)
+{
+    int rc = check_common(what, rect, num_out_rows, num_in_rows, heads, dim, num_parts, partSize, flags, GNNA_ACCUMULATE);
+    if (rc != GNNA_OK) return rc;
+    if (t_num_parts < 0) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: bad size (t_num_parts=%lld)", what, (long long)t_num_parts);
+    if (num_out_rows == 0 && num_in_rows == 0) return GNNA_OK;
+    const int64_t W = (int64_t)heads * dim;
+    const bool one_side = num_out_rows == 0 || num_in_rows == 0;      // no edge can exist: the outputs that have rows are 0
+    if (one_side) {
+        if (num_in_rows > 0 && (bad_ld(ld_dh, W) || !dH || !d_er))
+            return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: dH / d_er: null pointer or a row stride outside [heads * dim, 2^29)", what);
+        if (num_out_rows > 0 && !d_el) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
+    } else {
+        if (bad_ld(ld_h, W) || bad_ld(ld_y, W) || bad_ld(ld_dy, W) || bad_ld(ld_dh, W))
+            return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: row strides must be >= heads * dim and < 2^29 floats (ld_h=%lld ld_y=%lld "
+                        "ld_dy=%lld ld_dh=%lld)", what, (long long)ld_h, (long long)ld_y, (long long)ld_dy, (long long)ld_dh);
+        if (!H || !el || !er || !lse || !Y || !dY || !dH || !d_el || !d_er) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
+        if ((num_parts > 0 && (!column_index || !part_pointers || !part2Node)) ||
+            (t_num_parts > 0 && (!t_column_index || !t_part_pointers || !t_part2Node)))
+            return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null index pointer", what);
+        const void *ins[] = {H, el, er, lse, Y, dY};
+        const void *outs[] = {dH, d_el, d_er};
+        for (const void *o : outs)
+            for (const void *i : ins)
+                if (o == i) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: an output must not alias an input", what);
+        if (dH == d_el || dH == d_er || d_el == d_er) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: the outputs must not alias each other", what);
+    }
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    DeviceState *ds = nullptr;
+    rc = get_device_state(&ds);
+    if (rc != GNNA_OK) return rc;
+    rc = launch_zero_fill(ds, stream, dH, num_in_rows, (int)W, ld_dh);
+    if (rc == GNNA_OK) rc = launch_zero_fill(ds, stream, d_el, num_out_rows, heads, heads);
+    if (rc == GNNA_OK) rc = launch_zero_fill(ds, stream, d_er, num_in_rows, heads, heads);
+    if (rc != GNNA_OK || one_side || (num_parts == 0 && t_num_parts == 0)) return rc;
+    void *ws = nullptr;
+    rc = get_workspace(ds, stream, kSlotGatPack, ((size_t)num_out_rows * heads * sizeof(VT) + 255) & ~(size_t)255, &ws);
+    if (rc != GNNA_OK) return rc;
+    VT *pack = static_cast<VT *>(ws);
+    hipLaunchKernelGGL(gat_pack_kernel, dim3(grid_for((size_t)num_out_rows * heads, ds->num_cus)), dim3(kBlock), 0, stream, dY,
+                       (size_t)ld_dy, Y, (size_t)ld_y, el, lse, pack, (size_t)num_out_rows, heads, dim);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "%s: pack launch: %s", what, hipGetErrorString(e));
+    gnna_tuning tune;
+    gnna_get_tuning(&tune);
+    GatArgs a{};
+    a.er = er; a.pack = pack; a.col = column_index; a.pp = part_pointers; a.p2n = part2Node;
+    a.slope = negative_slope; a.P = num_parts; a.heads = heads; a.dim = dim;
+    a.xcd_remap = tune.xcd_remap != 0 ? 1 : 0;
+    // destination side: row i pulls H[j], er[j] -> d_el
+    a.N = (uint32_t)num_out_rows; a.M = (uint32_t)num_in_rows;
+    a.own = dY; a.ld_own = (size_t)ld_dy; a.gat = H; a.ld_gat = (size_t)ld_h; a.dsc = d_el;
+    rc = launch_pull<SIDE_BWD_DST>(ds, stream, a, partSize);
+    if (rc != GNNA_OK) return rc;
+    // source side: row j pulls dY[i], (el, lse, c)[i] -> d_er, dH -- over the edges j -> i, the rows of the transposed structure
+    a.N = (uint32_t)num_in_rows; a.M = (uint32_t)num_out_rows;
+    a.col = t_column_index; a.pp = t_part_pointers; a.p2n = t_part2Node; a.P = t_num_parts;
+    a.own = H; a.ld_own = (size_t)ld_h; a.gat = dY; a.ld_gat = (size_t)ld_dy; a.dsc = d_er; a.out = dH; a.ld_out = (size_t)ld_dh;
+    return launch_pull<SIDE_BWD_SRC>(ds, stream, a, partSize);
+}
 
 }  // namespace
 }  // namespace gnna
@@ -489,47 +621,19 @@ int gnna_gat_forward_f32(const float *H, int64_t ld_h, const float *el, const fl
                          float negative_slope, float *out, int64_t ld_out, float *lse, int64_t num_nodes, int heads, int dim,
                          int64_t num_parts, int partSize, unsigned flags, void *stream_v)
 {
-    const char *what = "gnna_gat_forward_f32";
-    int rc = check_common(what, num_nodes, heads, dim, num_parts, partSize, flags, GNNA_ACCUMULATE | GNNA_EPILOGUE_RELU);
-    if (rc != GNNA_OK) return rc;
-    if (num_nodes == 0) return GNNA_OK;
-    const int64_t W = (int64_t)heads * dim;
-    if (bad_ld(ld_h, W) || bad_ld(ld_out, W))
-        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: row strides must be >= heads * dim and < 2^29 floats (ld_h=%lld ld_out=%lld)",
-                    what, (long long)ld_h, (long long)ld_out);
-    if (!H || !el || !er || !out || !lse || !row_pointers) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
-    if (num_parts > 0 && (!column_index || !part_pointers || !part2Node))
-        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null index pointer", what);
-    if (out == H || out == el || out == er || out == lse || lse == el || lse == er || lse == H)
-        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: an output must not alias an input or the other output", what);
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    DeviceState *ds = nullptr;
-    rc = get_device_state(&ds);
-    if (rc != GNNA_OK) return rc;
-    rc = launch_zero_fill(ds, stream, out, num_nodes, (int)W, ld_out);
-    if (rc != GNNA_OK) return rc;
-    if (num_parts == 0) return launch_zero_fill(ds, stream, lse, num_nodes, heads, heads);
-    gnna_tuning tune;
-    gnna_get_tuning(&tune);
-    apply_graph_hints(column_index, (int)W, &tune);
-    // edges per row, for the segment width of the lse pass only: the graph's hint, else what the groups can hold at most
-    const int64_t avg = tune.avg_degree > 0 ? tune.avg_degree : (num_parts * (int64_t)partSize + num_nodes - 1) / num_nodes;
-    rc = launch_lse(stream, el, er, row_pointers, column_index, num_nodes, avg, heads, negative_slope, lse);
-    if (rc != GNNA_OK) return rc;
-    GatArgs a{};
-    a.gat = H; a.ld_gat = (size_t)ld_h; a.el = el; a.er = er; a.lse = lse;
-    a.col = column_index; a.pp = part_pointers; a.p2n = part2Node; a.out = out; a.ld_out = (size_t)ld_out;
-    a.slope = negative_slope; a.P = num_parts; a.N = (uint32_t)num_nodes; a.heads = heads; a.dim = dim;
-    a.xcd_remap = tune.xcd_remap != 0 ? 1 : 0;
-    rc = launch_pull<SIDE_FWD>(ds, stream, a, partSize);
-    if (rc != GNNA_OK) return rc;
-    if (flags & GNNA_EPILOGUE_RELU) {
-        hipLaunchKernelGGL(gat_relu_kernel, dim3(grid_for((size_t)num_nodes * (size_t)W, ds->num_cus)), dim3(kBlock), 0, stream,
-                           out, (size_t)ld_out, (size_t)num_nodes, (int)W);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(GNNA_ERR_HIP, "%s: epilogue launch: %s", what, hipGetErrorString(e));
-    }
-    return GNNA_OK;
+    return gat_forward_impl("gnna_gat_forward_f32", false, H, ld_h, el, er, row_pointers, column_index, part_pointers, part2Node,
+                            negative_slope, out, ld_out, lse, num_nodes, num_nodes, heads, dim, num_parts, partSize, flags, stream_v);
+}
+
+int gnna_gat_forward_rect_f32(const float *H, int64_t ld_h, const float *el, const float *er, const int32_t *row_pointers,
+                              const int32_t *column_index, const int32_t *part_pointers, const int32_t *part2Node,
+                              float negative_slope, float *out, int64_t ld_out, float *lse, int64_t num_out_rows,
+                              int64_t num_in_rows, int heads, int dim, int64_t num_parts, int partSize, unsigned flags,
+                              void *stream_v)
+{
+    return gat_forward_impl("gnna_gat_forward_rect_f32", true, H, ld_h, el, er, row_pointers, column_index, part_pointers, part2Node,
+                            negative_slope, out, ld_out, lse, num_out_rows, num_in_rows, heads, dim, num_parts, partSize, flags,
+                            stream_v);
 }
 
 int gnna_gat_backward_f32(const float *H, int64_t ld_h, const float *el, const float *er, const float *lse, const float *Y,
@@ -538,10 +642,11 @@ int gnna_gat_backward_f32(const float *H, int64_t ld_h, const float *el, const f
                           float negative_slope, float *dH, int64_t ld_dh, float *d_el, float *d_er, int64_t num_nodes,
                           int heads, int dim, int64_t num_parts, int partSize, unsigned flags, void *stream_v)
 {
+    (void)row_pointers;     // both passes walk the neighbor-groups
     // a symmetric structure is its own transpose
-    return gnna_gat_backward_dir_f32(H, ld_h, el, er, lse, Y, ld_y, dY, ld_dy, row_pointers, column_index, part_pointers, part2Node,
-                                     num_parts, row_pointers, column_index, part_pointers, part2Node, num_parts, negative_slope,
-                                     dH, ld_dh, d_el, d_er, num_nodes, heads, dim, partSize, flags, stream_v);
+    return gat_backward_impl("gnna_gat_backward_f32", false, H, ld_h, el, er, lse, Y, ld_y, dY, ld_dy, column_index, part_pointers,
+                             part2Node, num_parts, column_index, part_pointers, part2Node, num_parts, negative_slope, dH, ld_dh,
+                             d_el, d_er, num_nodes, num_nodes, heads, dim, partSize, flags, stream_v);
 }
 
 int gnna_gat_backward_dir_f32(const float *H, int64_t ld_h, const float *el, const float *er, const float *lse, const float *Y,
@@ -552,57 +657,26 @@ int gnna_gat_backward_dir_f32(const float *H, int64_t ld_h, const float *el, con
                               float negative_slope, float *dH, int64_t ld_dh, float *d_el, float *d_er, int64_t num_nodes,
                               int heads, int dim, int partSize, unsigned flags, void *stream_v)
 {
-    const char *what = "gnna_gat_backward_f32";
-    (void)row_pointers;     // both passes walk the neighbor-groups
+    (void)row_pointers;
     (void)t_row_pointers;
-    int rc = check_common(what, num_nodes, heads, dim, num_parts, partSize, flags, GNNA_ACCUMULATE);
-    if (rc != GNNA_OK) return rc;
-    if (t_num_parts < 0) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: bad size (t_num_parts=%lld)", what, (long long)t_num_parts);
-    if (num_nodes == 0) return GNNA_OK;
-    const int64_t W = (int64_t)heads * dim;
-    if (bad_ld(ld_h, W) || bad_ld(ld_y, W) || bad_ld(ld_dy, W) || bad_ld(ld_dh, W))
-        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: row strides must be >= heads * dim and < 2^29 floats (ld_h=%lld ld_y=%lld "
-                    "ld_dy=%lld ld_dh=%lld)", what, (long long)ld_h, (long long)ld_y, (long long)ld_dy, (long long)ld_dh);
-    if (!H || !el || !er || !lse || !Y || !dY || !dH || !d_el || !d_er) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
-    if ((num_parts > 0 && (!column_index || !part_pointers || !part2Node)) ||
-        (t_num_parts > 0 && (!t_column_index || !t_part_pointers || !t_part2Node)))
-        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null index pointer", what);
-    const void *ins[] = {H, el, er, lse, Y, dY};
-    const void *outs[] = {dH, d_el, d_er};
-    for (const void *o : outs)
-        for (const void *i : ins)
-            if (o == i) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: an output must not alias an input", what);
-    if (dH == d_el || dH == d_er || d_el == d_er) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: the outputs must not alias each other", what);
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    DeviceState *ds = nullptr;
-    rc = get_device_state(&ds);
-    if (rc != GNNA_OK) return rc;
-    rc = launch_zero_fill(ds, stream, dH, num_nodes, (int)W, ld_dh);
-    if (rc == GNNA_OK) rc = launch_zero_fill(ds, stream, d_el, num_nodes, heads, heads);
-    if (rc == GNNA_OK) rc = launch_zero_fill(ds, stream, d_er, num_nodes, heads, heads);
-    if (rc != GNNA_OK || (num_parts == 0 && t_num_parts == 0)) return rc;
-    void *ws = nullptr;
-    rc = get_workspace(ds, stream, kSlotGatPack, ((size_t)num_nodes * heads * sizeof(VT) + 255) & ~(size_t)255, &ws);
-    if (rc != GNNA_OK) return rc;
-    VT *pack = static_cast<VT *>(ws);
-    hipLaunchKernelGGL(gat_pack_kernel, dim3(grid_for((size_t)num_nodes * heads, ds->num_cus)), dim3(kBlock), 0, stream, dY,
-                       (size_t)ld_dy, Y, (size_t)ld_y, el, lse, pack, (size_t)num_nodes, heads, dim);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "%s: pack launch: %s", what, hipGetErrorString(e));
-    gnna_tuning tune;
-    gnna_get_tuning(&tune);
-    GatArgs a{};
-    a.er = er; a.pack = pack; a.col = column_index; a.pp = part_pointers; a.p2n = part2Node;
-    a.slope = negative_slope; a.P = num_parts; a.N = (uint32_t)num_nodes; a.heads = heads; a.dim = dim;
-    a.xcd_remap = tune.xcd_remap != 0 ? 1 : 0;
-    // destination side: row i pulls H[j], er[j] -> d_el
-    a.own = dY; a.ld_own = (size_t)ld_dy; a.gat = H; a.ld_gat = (size_t)ld_h; a.dsc = d_el;
-    rc = launch_pull<SIDE_BWD_DST>(ds, stream, a, partSize);
-    if (rc != GNNA_OK) return rc;
-    // source side: row j pulls dY[i], (el, lse, c)[i] -> d_er, dH -- over the edges j -> i, the rows of the transposed structure
-    a.col = t_column_index; a.pp = t_part_pointers; a.p2n = t_part2Node; a.P = t_num_parts;
-    a.own = H; a.ld_own = (size_t)ld_h; a.gat = dY; a.ld_gat = (size_t)ld_dy; a.dsc = d_er; a.out = dH; a.ld_out = (size_t)ld_dh;
-    return launch_pull<SIDE_BWD_SRC>(ds, stream, a, partSize);
+    return gat_backward_impl("gnna_gat_backward_f32", false, H, ld_h, el, er, lse, Y, ld_y, dY, ld_dy, column_index, part_pointers,
+                             part2Node, num_parts, t_column_index, t_part_pointers, t_part2Node, t_num_parts, negative_slope, dH,
+                             ld_dh, d_el, d_er, num_nodes, num_nodes, heads, dim, partSize, flags, stream_v);
+}
+
+int gnna_gat_backward_rect_f32(const float *H, int64_t ld_h, const float *el, const float *er, const float *lse, const float *Y,
+                               int64_t ld_y, const float *dY, int64_t ld_dy, const int32_t *row_pointers,
+                               const int32_t *column_index, const int32_t *part_pointers, const int32_t *part2Node,
+                               int64_t num_parts, const int32_t *t_row_pointers, const int32_t *t_column_index,
+                               const int32_t *t_part_pointers, const int32_t *t_part2Node, int64_t t_num_parts,
+                               float negative_slope, float *dH, int64_t ld_dh, float *d_el, float *d_er, int64_t num_out_rows,
+                               int64_t num_in_rows, int heads, int dim, int partSize, unsigned flags, void *stream_v)
+{
+    (void)row_pointers;
+    (void)t_row_pointers;
+    return gat_backward_impl("gnna_gat_backward_rect_f32", true, H, ld_h, el, er, lse, Y, ld_y, dY, ld_dy, column_index,
+                             part_pointers, part2Node, num_parts, t_column_index, t_part_pointers, t_part2Node, t_num_parts,
+                             negative_slope, dH, ld_dh, d_el, d_er, num_out_rows, num_in_rows, heads, dim, partSize, flags, stream_v);
 }
 
 #pragma GCC visibility pop

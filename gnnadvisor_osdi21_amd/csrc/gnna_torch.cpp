@@ -467,24 +467,29 @@ torch::Tensor edge_softmax_backward(const torch::Tensor &probs, const torch::Ten
     return gs;
 }
 
-// Fused multi-head GAT attention (gnna_gat_forward_f32 / gnna_gat_backward_f32): H [N, heads * dim], el / er [N, heads].  No
-// per-edge tensor is made.  H, Y and dY go through their leading dimension (copied only when the inner stride is not 1).
+// Fused multi-head GAT attention (gnna_gat_forward_f32 / gnna_gat_backward_f32 and their rectangular forms): H [num_in_rows,
+// heads * dim], er [num_in_rows, heads], el [num_out_rows, heads] with num_out_rows = row_pointers.numel() - 1 (a square graph:
+// both are num_nodes; a sampled block: num_dst and num_src).  No per-edge tensor is made.  H, Y and dY go through their leading
+// dimension (copied only when the inner stride is not 1).  Every shape is checked before any device work.
 static torch::Tensor gat_rows(const torch::Tensor &t, const char *what, int64_t n, int64_t width)
 {
     CHECK_CUDA(t); CHECK_F32(t);
-    TORCH_CHECK(t.dim() == 2 && t.size(0) == n && t.size(1) == width, what, " must be [num_nodes, heads * dim]");
+    TORCH_CHECK(t.dim() == 2 && t.size(0) == n && t.size(1) == width, what, " must be [", n, ", heads * dim = ", width,
+                "] (num_nodes rows; on a rectangular structure H has num_in_rows rows, Y and dY num_out_rows)");
     const bool rows_ok = (width <= 1 || t.stride(1) == 1) && (n <= 1 || t.stride(0) >= width);
     return rows_ok ? t : t.contiguous();
 }
 
-static void gat_check_graph(const torch::Tensor &H, const torch::Tensor &row_pointers, const torch::Tensor &column_index,
-                            const torch::Tensor &part_pointers, const torch::Tensor &part2Node)
+// the structure walked by rows of `rows` rows (the graph: num_out_rows; its transpose: num_in_rows)
+static void gat_check_graph(const torch::Tensor &H, int64_t rows, const torch::Tensor &row_pointers,
+                            const torch::Tensor &column_index, const torch::Tensor &part_pointers, const torch::Tensor &part2Node)
 {
     CHECK_INPUT(row_pointers); CHECK_I32(row_pointers);
     CHECK_INPUT(column_index); CHECK_I32(column_index);
     CHECK_INPUT(part_pointers); CHECK_I32(part_pointers);
     CHECK_INPUT(part2Node); CHECK_I32(part2Node);
-    TORCH_CHECK(row_pointers.dim() == 1 && row_pointers.size(0) == H.size(0) + 1, "row_pointers must be [num_nodes + 1]");
+    TORCH_CHECK(row_pointers.dim() == 1 && row_pointers.size(0) == rows + 1, "row_pointers must be [num_nodes + 1] (", rows + 1,
+                " entries: one more than the rows of the side it walks)");
     TORCH_CHECK(part_pointers.numel() == part2Node.numel() + 1, "part_pointers must be [num_parts + 1]");
     TORCH_CHECK(row_pointers.device() == H.device() && column_index.device() == H.device() &&
                 part_pointers.device() == H.device() && part2Node.device() == H.device(), "H and the graph must be on one device");
@@ -494,8 +499,8 @@ static int gat_heads(const torch::Tensor &H, const torch::Tensor &el, const torc
 {
     CHECK_INPUT(el); CHECK_F32(el); CHECK_INPUT(er); CHECK_F32(er);
     TORCH_CHECK(H.dim() == 2, "H must be 2-D [num_nodes, heads * dim]");
-    TORCH_CHECK(el.dim() == 2 && el.size(0) == H.size(0) && el.size(1) >= 1 && er.sizes() == el.sizes(),
-                "el and er must be [num_nodes, heads]");
+    TORCH_CHECK(el.dim() == 2 && el.size(1) >= 1 && er.dim() == 2 && er.size(0) == H.size(0) && er.size(1) == el.size(1),
+                "el and er must be [num_nodes, heads] (rectangular: el [num_out_rows, heads], er [num_in_rows = H.size(0), heads])");
     TORCH_CHECK(H.size(1) >= el.size(1) && H.size(1) % el.size(1) == 0, "H must be [num_nodes, heads * dim]");
     TORCH_CHECK(el.device() == H.device() && er.device() == H.device(), "H, el and er must be on one device");
     return (int)el.size(1);
@@ -507,21 +512,29 @@ gat_forward(const torch::Tensor &H_in, const torch::Tensor &el, const torch::Ten
             double negative_slope)
 {
     const int heads = gat_heads(H_in, el, er);
-    const int64_t n = H_in.size(0), width = H_in.size(1);
-    const torch::Tensor H = gat_rows(H_in, "H", n, width);
-    gat_check_graph(H, row_pointers, column_index, part_pointers, part2Node);
+    const int64_t n_in = H_in.size(0), n_out = el.size(0), width = H_in.size(1);
+    const torch::Tensor H = gat_rows(H_in, "H", n_in, width);
+    gat_check_graph(H, n_out, row_pointers, column_index, part_pointers, part2Node);
     auto ld_of = [&](const torch::Tensor &t) { return t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(t.size(1), t.stride(0)); };
     at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(H.device());
     static const bool poison = std::getenv("GNNA_DEBUG_POISON") && std::atoi(std::getenv("GNNA_DEBUG_POISON")) != 0;
     const float nan = std::numeric_limits<float>::quiet_NaN();
-    auto Y = poison ? torch::full({n, width}, nan, el.options()) : torch::empty({n, width}, el.options());
-    auto lse = poison ? torch::full({n, (int64_t)heads}, nan, el.options()) : torch::empty({n, (int64_t)heads}, el.options());
+    auto Y = poison ? torch::full({n_out, width}, nan, el.options()) : torch::empty({n_out, width}, el.options());
+    auto lse = poison ? torch::full({n_out, (int64_t)heads}, nan, el.options()) : torch::empty({n_out, (int64_t)heads}, el.options());
     void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-    int rc = gnna_gat_forward_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(),
+    int rc;
+    if (n_out == n_in)
+        rc = gnna_gat_forward_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(),
                                   row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
                                   part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), (float)negative_slope,
-                                  Y.data_ptr<float>(), width, lse.data_ptr<float>(), n, heads, (int)(width / heads),
+                                  Y.data_ptr<float>(), width, lse.data_ptr<float>(), n_out, heads, (int)(width / heads),
                                   part2Node.size(0), partSize, 0u, stream);
+    else
+        rc = gnna_gat_forward_rect_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(),
+                                       row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
+                                       part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), (float)negative_slope,
+                                       Y.data_ptr<float>(), width, lse.data_ptr<float>(), n_out, n_in, heads,
+                                       (int)(width / heads), part2Node.size(0), partSize, 0u, stream);
     TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
     return std::make_tuple(Y, lse);
 }
@@ -533,34 +546,52 @@ gat_backward(const torch::Tensor &H_in, const torch::Tensor &el, const torch::Te
              double negative_slope, const c10::optional<std::vector<torch::Tensor>> &transposed)
 {
     const int heads = gat_heads(H_in, el, er);
-    const int64_t n = H_in.size(0), width = H_in.size(1);
-    const torch::Tensor H = gat_rows(H_in, "H", n, width), Y = gat_rows(Y_in, "Y", n, width), dY = gat_rows(dY_in, "dY", n, width);
-    // transposed = (t_row_pointers, t_column_index, t_part_pointers, t_part2Node): the source-side pass walks it (directed graphs)
+    const int64_t n_in = H_in.size(0), n_out = el.size(0), width = H_in.size(1);
+    const bool rect = n_out != n_in;
+    TORCH_CHECK(!rect || transposed.has_value(), "gat_backward on a rectangular structure (", n_out, " destination rows, ", n_in,
+                " source rows) needs `transposed`: a rectangular structure is never its own transpose");
+    const torch::Tensor H = gat_rows(H_in, "H", n_in, width), Y = gat_rows(Y_in, "Y", n_out, width),
+                        dY = gat_rows(dY_in, "dY", n_out, width);
+    // transposed = (t_row_pointers, t_column_index, t_part_pointers, t_part2Node): the source-side pass walks it (directed graphs,
+    // blocks): num_in_rows rows
     const torch::Tensor *t_rp = &row_pointers, *t_ci = &column_index, *t_pp = &part_pointers, *t_p2n = &part2Node;
     if (transposed.has_value()) {
         TORCH_CHECK(transposed->size() == 4, "transposed must be (t_row_pointers, t_column_index, t_part_pointers, t_part2Node)");
         t_rp = &(*transposed)[0]; t_ci = &(*transposed)[1]; t_pp = &(*transposed)[2]; t_p2n = &(*transposed)[3];
-        gat_check_graph(H, *t_rp, *t_ci, *t_pp, *t_p2n);
+        gat_check_graph(H, n_in, *t_rp, *t_ci, *t_pp, *t_p2n);
     }
     CHECK_INPUT(lse); CHECK_F32(lse);
-    TORCH_CHECK(lse.sizes() == el.sizes() && lse.device() == H.device(), "lse must be [num_nodes, heads] on H's device");
+    TORCH_CHECK(lse.sizes() == el.sizes() && lse.device() == H.device(), "lse must be [num_nodes, heads] (the shape of el) on H's device");
     TORCH_CHECK(Y.device() == H.device() && dY.device() == H.device(), "H, Y and dY must be on one device");
-    gat_check_graph(H, row_pointers, column_index, part_pointers, part2Node);
+    gat_check_graph(H, n_out, row_pointers, column_index, part_pointers, part2Node);
     auto ld_of = [&](const torch::Tensor &t) { return t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(t.size(1), t.stride(0)); };
     at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(H.device());
     static const bool poison = std::getenv("GNNA_DEBUG_POISON") && std::atoi(std::getenv("GNNA_DEBUG_POISON")) != 0;
     const float nan = std::numeric_limits<float>::quiet_NaN();
-    auto fresh = [&](int64_t cols) { return poison ? torch::full({n, cols}, nan, el.options()) : torch::empty({n, cols}, el.options()); };
-    auto dH = fresh(width), d_el = fresh(heads), d_er = fresh(heads);
+    auto fresh = [&](int64_t rows, int64_t cols) {
+        return poison ? torch::full({rows, cols}, nan, el.options()) : torch::empty({rows, cols}, el.options());
+    };
+    auto dH = fresh(n_in, width), d_el = fresh(n_out, heads), d_er = fresh(n_in, heads);
     void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-    int rc = gnna_gat_backward_dir_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(), lse.data_ptr<float>(),
+    int rc;
+    if (!rect)
+        rc = gnna_gat_backward_dir_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(), lse.data_ptr<float>(),
                                        Y.data_ptr<float>(), ld_of(Y), dY.data_ptr<float>(), ld_of(dY),
                                        row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
                                        part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), part2Node.size(0),
                                        t_rp->data_ptr<int32_t>(), t_ci->data_ptr<int32_t>(), t_pp->data_ptr<int32_t>(),
                                        t_p2n->data_ptr<int32_t>(), t_p2n->size(0), (float)negative_slope,
-                                       dH.data_ptr<float>(), width, d_el.data_ptr<float>(), d_er.data_ptr<float>(), n, heads,
+                                       dH.data_ptr<float>(), width, d_el.data_ptr<float>(), d_er.data_ptr<float>(), n_out, heads,
                                        (int)(width / heads), partSize, 0u, stream);
+    else
+        rc = gnna_gat_backward_rect_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(), lse.data_ptr<float>(),
+                                        Y.data_ptr<float>(), ld_of(Y), dY.data_ptr<float>(), ld_of(dY),
+                                        row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
+                                        part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), part2Node.size(0),
+                                        t_rp->data_ptr<int32_t>(), t_ci->data_ptr<int32_t>(), t_pp->data_ptr<int32_t>(),
+                                        t_p2n->data_ptr<int32_t>(), t_p2n->size(0), (float)negative_slope,
+                                        dH.data_ptr<float>(), width, d_el.data_ptr<float>(), d_er.data_ptr<float>(), n_out, n_in,
+                                        heads, (int)(width / heads), partSize, 0u, stream);
     TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
     return std::make_tuple(dH, d_el, d_er);
 }
@@ -913,12 +944,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("edge_softmax_backward", &edge_softmax_backward, "gradient of edge_softmax: probs * (grad - sum_row probs * grad) (extension)",
           pybind11::arg("probs"), pybind11::arg("grad"), pybind11::arg("row_pointers"));
     m.def("gat_forward", &gat_forward,
-          "fused multi-head GAT attention -> (Y, lse): Y[i, h] = sum_e exp(leaky_relu(el[i, h] + er[col(e), h]) - lse[i, h]) H[col(e), h] (extension)",
+          "fused multi-head GAT attention -> (Y, lse): Y[i, h] = sum_e exp(leaky_relu(el[i, h] + er[col(e), h]) - lse[i, h]) H[col(e), h] (extension).  "
+          "Rectangular structures: H [num_in_rows, heads * dim], er [num_in_rows, heads], el [num_out_rows, heads], row_pointers [num_out_rows + 1]",
           pybind11::arg("H"), pybind11::arg("el"), pybind11::arg("er"), pybind11::arg("row_pointers"), pybind11::arg("column_index"),
           pybind11::arg("part_pointers"), pybind11::arg("part2Node"), pybind11::arg("partSize"), pybind11::arg("negative_slope") = 0.2);
     m.def("gat_backward", &gat_backward,
           "gradient of gat_forward -> (dH, d_el, d_er); dH is the attention part only (extension).  The structure must be symmetric "
-          "unless transposed = [t_row_pointers, t_column_index, t_part_pointers, t_part2Node] (transpose_csr, build_part_device) is given",
+          "unless transposed = [t_row_pointers, t_column_index, t_part_pointers, t_part2Node] (transpose_csr, build_part_device) is given; "
+          "a rectangular structure (el.size(0) != H.size(0)) always needs it: dH / d_er get num_in_rows rows, d_el num_out_rows",
           pybind11::arg("H"), pybind11::arg("el"), pybind11::arg("er"), pybind11::arg("lse"), pybind11::arg("Y"), pybind11::arg("dY"),
           pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("part_pointers"), pybind11::arg("part2Node"),
           pybind11::arg("partSize"), pybind11::arg("negative_slope") = 0.2, pybind11::arg("transposed") = pybind11::none());

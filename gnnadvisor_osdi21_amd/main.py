@@ -79,9 +79,9 @@ def build_parser():
                         "the device right after the partition (False: the structure is taken to be symmetric, as the "
                         "reference does, and the backward passes reuse the forward graph)")
     p.add_argument('--fanout', type=str, default=None,
-                   help="--model sage: train on sampled mini-batches -- a comma list with one entry per layer, the neighbours "
-                        "sampled per node at that layer (-1: all of them), e.g. 25,10; the blocks are drawn on the device "
-                        "(sampling.NeighborSampler, MI355X addition)")
+                   help="--model sage, or --model gat with --fused_attention True: train on sampled mini-batches -- a comma list "
+                        "with one entry per layer, the neighbours sampled per node at that layer (-1: all of them), e.g. 25,10; "
+                        "the blocks are drawn on the device (sampling.NeighborSampler, MI355X addition)")
     p.add_argument('--batch_size', type=int, default=1024, help="--fanout: seed nodes per mini-batch")
     p.add_argument('--policy', type=str, default='mi355x', choices=['mi355x', 'compat'], help="Decider policy")
     p.add_argument('--force_rabbit', default='False', **tf,
@@ -132,13 +132,17 @@ def main(argv=None, capture=None):
         raise SystemExit("--fused_attention True selects the fused GAT attention: run it with --model gat (got --model %s)" % args.model)
     fanouts = None
     if args.fanout is not None:
-        if args.model != 'sage':
-            raise SystemExit("--fanout trains GraphSAGE on sampled blocks: run it with --model sage (got --model %s)" % args.model)
+        if args.model == 'gat' and not flag(args.fused_attention):
+            raise SystemExit("--model gat --fanout runs on the fused attention kernels only (the composed path would build "
+                             "per-edge tensors for every batch): add --fused_attention True")
+        if args.model not in ('sage', 'gat'):
+            raise SystemExit("--fanout trains GraphSAGE on sampled blocks: run it with --model sage, or with --model gat "
+                             "--fused_attention True (got --model %s)" % args.model)
         if flag(args.hip_graph):
             raise SystemExit("--fanout does not support --hip_graph True: every batch samples new blocks and reads their sizes "
                              "back; run it with --hip_graph False")
         if args.dtype != 'float32':
-            raise SystemExit("--fanout: the GraphSAGE layers on a block are float32 only; use --dtype float32")
+            raise SystemExit("--fanout: the layers that take a block are float32 only; use --dtype float32")
         if single_spmm or verify_spmm:
             raise SystemExit("--fanout does not go with --single_spmm / --verify_spmm: they run one full-graph aggregation")
         try:
@@ -146,7 +150,7 @@ def main(argv=None, capture=None):
         except ValueError:
             raise SystemExit("--fanout takes a comma list of integers, e.g. 25,10 (got %r)" % args.fanout)
         if len(fanouts) != 2:
-            raise SystemExit("--fanout needs one entry per layer: --model sage has 2 layers (got %d)" % len(fanouts))
+            raise SystemExit("--fanout needs one entry per layer: --model %s has 2 layers (got %d)" % (args.model, len(fanouts)))
         if args.batch_size < 1:
             raise SystemExit("--batch_size must be >= 1")
     assert torch.cuda.is_available(), "requires an MI355X GPU: there is no CPU path"
@@ -287,7 +291,11 @@ def main(argv=None, capture=None):
                 self.conv1 = GATConv(dataset.num_features, args.hidden, heads=args.heads, concat=True, fused=fused)
                 self.conv2 = GATConv(args.hidden * args.heads, dataset.num_classes, heads=1, fused=fused)
 
-            def forward(self):
+            def forward(self, x=None, blocks=None):
+                if blocks is not None:      # a sampled mini-batch (--fused_attention True): x holds blocks[0]'s source rows
+                    x = F.elu(self.conv1(x, blocks[0]))
+                    x = self.conv2(x, blocks[1])
+                    return F.log_softmax(x, dim=1)
                 x = F.elu(self.conv1(dataset.x, inputInfo.set_input()))
                 x = self.conv2(x, inputInfo.set_hidden())
                 return F.log_softmax(x, dim=1)

@@ -50,6 +50,8 @@ def _backward_graph(ctx):
 # The GraphSAGE operators take a block where they take an inputProperty.  Forward and backward go through the rectangular
 # entries of libgnna (gnna_agg_ld_f32, gnna_agg_reduce_ld_f32, gnna_scatter_arg_ld_f32); the backward of a sum aggregates dY over
 # block.transposed(), which is only built when the layer's input needs a gradient (the first layer's does not).
+# The fused attention (GATAttention, GATConv(fused=True)) takes a block too, through gnna_gat_forward_rect_f32 /
+# gnna_gat_backward_rect_f32; its backward always runs on block.transposed() (the gradient of the layer's own weight needs dH).
 
 def _is_block(info):
     return isinstance(info, SampledBlock)
@@ -58,7 +60,8 @@ def _is_block(info):
 def _refuse_block(info, layer):
     if _is_block(info):
         raise TypeError(f"{layer} does not take a SampledBlock: blocks are supported by the GraphSAGE operators "
-                        "(ScatterAndGather, NeighborMean, NeighborMax, NeighborMin, SAGEConv)")
+                        "(ScatterAndGather, NeighborMean, NeighborMax, NeighborMin, SAGEConv) and by the fused attention "
+                        "(GATAttention, GATConv(fused=True))")
 
 
 def _block_features(X, block, what):
@@ -677,11 +680,24 @@ class GATAttention(Function):
     nnz x 4 bytes of ids and a partition stay on the device) and nothing is assumed.  Otherwise the backward reads row j's edges
     as the edges j -> i, so before its first backward on a graph it establishes that the structure is symmetric and raises otherwise (``decider.inputProperty.require_symmetric``): once per column_index, on the host -- a
     copy of the CSR to the host and a pass of gnna_reverse_edges_i32 over it, about a second at 1e8 edges; only the answer is
-    kept, nothing of the size of the edge list stays on the device."""
+    kept, nothing of the size of the edge list stays on the device.
+
+    `inputInfo` may be a sampling.SampledBlock (gnna_gat_forward_rect_f32 / gnna_gat_backward_rect_f32): H is
+    [num_src, heads * F], er [num_src, heads], el [num_dst, heads] and Y [num_dst, heads * F].  The backward runs on
+    ``block.transposed()``, built at the first backward in which H, el or er needs a gradient (the forward alone builds
+    nothing); no symmetry check is made for a block."""
 
     @staticmethod
     def forward(ctx, H, el, er, inputInfo, negative_slope):
         info = inputInfo
+        if _is_block(info):
+            H = _block_features(H, info, "GATAttention")
+            if er.dim() != 2 or er.shape[0] != info.num_src or el.dim() != 2 or el.shape[0] != info.num_dst or \
+                    el.shape[1] != er.shape[1]:
+                raise ValueError(f"GATAttention on a SampledBlock: el must be [num_dst = {info.num_dst}, heads] and er "
+                                 f"[num_src = {info.num_src}, heads] (got {tuple(el.shape)} and {tuple(er.shape)})")
+            if el.dtype != torch.float32 or er.dtype != torch.float32:
+                raise TypeError(f"GATAttention on a SampledBlock: float32 scores only (got {el.dtype}, {er.dtype})")
         el, er = el.contiguous(), er.contiguous()
         Y, lse = GNNA.gat_forward(H, el, er, info.row_pointers, info.column_index, info.partPtr, info.part2Node, info.partSize,
                                   float(negative_slope))
@@ -696,7 +712,7 @@ class GATAttention(Function):
         if not any(ctx.needs_input_grad[:3]):
             return None, None, None, None, None
         transposed = None
-        if _is_directed(info):
+        if _is_block(info) or _is_directed(info):      # (a block is never symmetric: require_symmetric is not for it)
             t = info.transposed()
             transposed = [t.row_pointers, t.column_index, t.partPtr, t.part2Node]
         else:
@@ -715,7 +731,11 @@ class GATConv(Module):
     Needs the graph's structure to be symmetric (the backward gathers through the reverse-edge map) unless the graph is
     ``directed`` (then it gathers over the transposed structure).
     fused=True: the attention runs on GATAttention instead -- the same function, with alpha made from node-sized values inside
-    the gathers: no per-edge tensor, one call for all heads."""
+    the gathers: no per-edge tensor, one call for all heads.
+    With fused=True `inputInfo` may be a sampling.SampledBlock: X is [num_src, in], H = X W covers all num_src rows, er comes
+    from all of H and el from H[:num_dst] (a block's destination rows are its first source rows); the result is
+    [num_dst, heads * out] ([num_dst, out] with concat=False).  float32 only.  fused=False refuses a block: the composed path
+    would build per-edge tensors for every batch."""
 
     def __init__(self, input_dim, output_dim, heads=1, concat=True, negative_slope=0.2, fused=False):
         super().__init__()
@@ -734,12 +754,19 @@ class GATConv(Module):
             self.att_r.uniform_(-bound, bound)
 
     def forward(self, X, inputInfo):
-        _refuse_block(inputInfo, "GATConv")
-        n = X.shape[0]
+        block = _is_block(inputInfo)
+        if block:
+            if not self.fused:
+                _refuse_block(inputInfo, "GATConv(fused=False)")
+            if X.dtype != torch.float32 or _x16_dtype(X) is not None:
+                raise TypeError("GATConv on a SampledBlock computes in float32 only: 16-bit features and torch.autocast are not "
+                                f"supported (got {X.dtype}{', inside torch.autocast' if X.dtype == torch.float32 else ''})")
+            X = _block_features(X, inputInfo, "GATConv")
         H = torch.mm(X, self.weights)
-        Hh = H.view(n, self.heads, self.out_dim)
-        el = (Hh * self.att_l).sum(-1)          # [N, heads]: destination side
-        er = (Hh * self.att_r).sum(-1)          # source side
+        Hh = H.view(X.shape[0], self.heads, self.out_dim)
+        n = inputInfo.num_dst if block else X.shape[0]      # rows of the result
+        el = ((Hh[:n] if block else Hh) * self.att_l).sum(-1)      # [N, heads] ([num_dst, heads]): destination side
+        er = (Hh * self.att_r).sum(-1)          # [N, heads] ([num_src, heads]): source side
         if self.fused:
             Y = GATAttention.apply(H, el, er, inputInfo, self.negative_slope)
         else:

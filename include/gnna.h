@@ -444,6 +444,34 @@ GNNA_API int gnna_gat_backward_dir_f32(const float *H, int64_t ld_h, const float
         int64_t t_num_parts,
         float negative_slope, float *dH, int64_t ld_dh, float *d_el, float *d_er, int64_t num_nodes, int heads, int dim,
         int partSize, unsigned flags, void *stream);
+/* The fused GAT attention on a RECTANGULAR structure (a sampled block): num_out_rows destination rows gather from num_in_rows
+ * source rows.  Formulas, skipping rules, flags, limits (each row count < 2^29), scratch and error rules are those of
+ * gnna_gat_forward_f32 / gnna_gat_backward_dir_f32 above; the square entries are these calls with both counts = num_nodes.
+ * The differences:
+ *   H, dH: [num_in_rows, heads * dim];  er, d_er: [num_in_rows, heads];  out, Y, dY: [num_out_rows, heads * dim];
+ *   el, lse, d_el: [num_out_rows, heads] (scratch of the backward: num_out_rows x heads x 16 bytes).
+ *   The forward structure (row_pointers, column_index and its partition) has num_out_rows rows and ids in [0, num_in_rows); the
+ *   transposed structure has num_in_rows rows and ids in [0, num_out_rows): what gnna_transpose_csr_i32(row_pointers,
+ *   column_index, num_out_rows, num_in_rows, ...) and gnna_build_part_device_i32 at the same partSize produce.  The backward
+ *   always takes it: a rectangular structure is never its own transpose (null t_ pointers with t_num_parts > 0:
+ *   GNNA_ERR_INVALID_ARGUMENT).
+ *   An id >= num_in_rows is skipped in the lse pass, the forward pass and the d_el pass; an id >= num_out_rows is skipped in the
+ *   source-side pass (d_er, dH); a neighbor-group whose row is outside its side's row count contributes nothing.
+ *   Every element of every output is written: rows of dH / d_er that no edge reaches are 0, rows of out / lse / d_el without
+ *   edges are 0.  num_out_rows = 0 or num_in_rows = 0: GNNA_OK after zero-filling whatever output has rows (no input is read). */
+GNNA_API int gnna_gat_forward_rect_f32(const float *H, int64_t ld_h, const float *el, const float *er,
+        const int32_t *row_pointers, const int32_t *column_index, const int32_t *part_pointers, const int32_t *part2Node,
+        float negative_slope, float *out, int64_t ld_out, float *lse,
+        int64_t num_out_rows, int64_t num_in_rows, int heads, int dim, int64_t num_parts, int partSize,
+        unsigned flags, void *stream);
+GNNA_API int gnna_gat_backward_rect_f32(const float *H, int64_t ld_h, const float *el, const float *er, const float *lse,
+        const float *Y, int64_t ld_y, const float *dY, int64_t ld_dy,
+        const int32_t *row_pointers, const int32_t *column_index, const int32_t *part_pointers, const int32_t *part2Node,
+        int64_t num_parts,
+        const int32_t *t_row_pointers, const int32_t *t_column_index, const int32_t *t_part_pointers, const int32_t *t_part2Node,
+        int64_t t_num_parts,
+        float negative_slope, float *dH, int64_t ld_dh, float *d_el, float *d_er,
+        int64_t num_out_rows, int64_t num_in_rows, int heads, int dim, int partSize, unsigned flags, void *stream);
 
 /* Relation-typed aggregation (gnna_typed.hip): what an R-GCN layer in basis form, W_r = sum_b C[r, b] V_b, needs around its one
  * GEMM.  Every edge position e (indexed like column_index) has a type edge_type[e] in [0, num_types) and a factor edge_norm[e]
