@@ -495,9 +495,25 @@ int launch_zero_fill(DeviceState *ds, hipStream_t stream, float *out, int64_t ro
     blocks = std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)ds->num_cus * 8));
     hipLaunchKernelGGL(prologue_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, out, n_floats, dim, (int)ld, nullptr, nullptr,
                        (int64_t)0, nullptr, 0, /*validate=*/0, /*zero_fill=*/1, nullptr, (int64_t)0, nullptr, nullptr, nullptr, 0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "zero-fill launch: %s", hipGetErrorString(e));
-    return GNNA_OK;
+    return launch_ok("zero-fill launch");
+}
+
+namespace {
+__global__ void __launch_bounds__(kBlock)
+relu_rows_kernel(float *__restrict__ Y, size_t ld, size_t rows, int D)
+{
+    const size_t n = rows * (size_t)D;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / (unsigned)D, c = i - r * (unsigned)D;
+        if (Y[r * ld + c] < 0.f) Y[r * ld + c] = 0.f;          // (a NaN is not below 0: it stays)
+    }
+}
+}  // namespace
+
+void launch_relu_rows(DeviceState *ds, hipStream_t stream, float *out, int64_t rows, int dim, int64_t ld)
+{
+    hipLaunchKernelGGL(relu_rows_kernel, dim3(elementwise_grid(rows * dim, ds->num_cus, 8)), dim3(kBlock), 0, stream, out,
+                       (size_t)ld, (size_t)rows, dim);
 }
 
 namespace {
@@ -582,7 +598,7 @@ int launch_agg(int mode, const float *input, int64_t ld_in, int64_t num_in_rows,
         return fail(GNNA_ERR_UNSUPPORTED, "%lld destination rows in one call (at most 536870911): shard the rows",
                     (long long)num_nodes);
     if (num_nodes == 0 || dim == 0) return GNNA_OK;
-    if (ld_in < dim || ld_out < dim || ld_in >= ((int64_t)1 << 29) || ld_out >= ((int64_t)1 << 29))
+    if (bad_ld(ld_in, dim) || bad_ld(ld_out, dim))
         return fail(GNNA_ERR_INVALID_ARGUMENT, "row strides must be >= dim and < 2^29 floats (ld_in=%lld ld_out=%lld dim=%d)",
                     (long long)ld_in, (long long)ld_out, dim);
     if (!out || !input) return fail(GNNA_ERR_INVALID_ARGUMENT, "null feature pointer");
@@ -970,7 +986,7 @@ int gnna_agg_ld_x16(int mode, int in_type, const void *input, int64_t ld_in, int
     if (num_out_rows >= ((int64_t)1 << 29))
         return fail(GNNA_ERR_UNSUPPORTED, "%lld destination rows in one call (at most 536870911): shard the rows", (long long)num_out_rows);
     if (num_out_rows == 0 || dim == 0) return GNNA_OK;
-    if (ld_in < dim || ld_out < dim || ld_in >= ((int64_t)1 << 29) || ld_out >= ((int64_t)1 << 29))
+    if (bad_ld(ld_in, dim) || bad_ld(ld_out, dim))
         return fail(GNNA_ERR_INVALID_ARGUMENT, "row strides must be >= dim and < 2^29 elements (ld_in=%lld ld_out=%lld dim=%d)",
                     (long long)ld_in, (long long)ld_out, dim);
     if (!out || !input) return fail(GNNA_ERR_INVALID_ARGUMENT, "null feature pointer");
@@ -980,22 +996,20 @@ int gnna_agg_ld_x16(int mode, int in_type, const void *input, int64_t ld_in, int
         return fail(GNNA_ERR_INVALID_ARGUMENT, "null index pointer");
     if (mode == MODE_GCN && (!degrees_out || !degrees_in)) return fail(GNNA_ERR_INVALID_ARGUMENT, "null degrees pointer");
     if (out == input) return fail(GNNA_ERR_INVALID_ARGUMENT, "out must not alias input");
-    gnna_tuning tune;
-    gnna_get_tuning(&tune);
     // every row is added with float atomics (gnna_x16.hip): the order of the additions is not fixed
-    if (tune.deterministic == 1)
-        return fail(GNNA_ERR_UNSUPPORTED, "gnna_agg_ld_x16 has no deterministic schedule (gnna_tuning.deterministic = 1): its rows meet "
-                                          "in fp32 through float atomics; use gnna_agg_ld_f32 on fp32 features");
+    int rc = deterministic_refused("gnna_agg_ld_x16",
+                                   "its rows meet in fp32 through float atomics; use gnna_agg_ld_f32 on fp32 features");
+    if (rc != GNNA_OK) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     DeviceState *ds = nullptr;
-    int rc = get_device_state(&ds);
+    rc = get_device_state(&ds);
     if (rc != GNNA_OK) return rc;
     X16Launch c;
     c.mode = mode; c.in_type = in_type; c.out_type = out_type; c.input = input; c.ld_in = ld_in; c.num_in_rows = num_in_rows;
     c.column_index = column_index; c.degrees_out = degrees_out; c.degrees_in = degrees_in; c.epsilon = epsilon;
     c.part_pointers = part_pointers; c.part2Node = part2Node; c.out = out; c.ld_out = ld_out; c.num_out_rows = num_out_rows;
     c.dim = dim; c.num_parts = num_parts; c.partSize = partSize;
-    c.accumulate = (flags & GNNA_ACCUMULATE) != 0; c.relu = (flags & GNNA_EPILOGUE_RELU) != 0; c.xcd_remap = tune.xcd_remap != 0;
+    c.accumulate = (flags & GNNA_ACCUMULATE) != 0; c.relu = (flags & GNNA_EPILOGUE_RELU) != 0; c.xcd_remap = xcd_remap_on() != 0;
     c.prof_call = profile_acquire_call(num_parts > 0);
     profile_record(c.prof_call, 0, stream);
     t_last_phases = 1;

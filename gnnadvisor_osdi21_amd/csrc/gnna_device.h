@@ -8,13 +8,9 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "gnna_launch.h"   // kWave, kBlock, kWavesPerBlock, kXcds
+
 namespace gnna {
-
-
-constexpr int kWave = 64;
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / kWave;
-constexpr int kXcds = 8;
 
 // MODE_EDGE: per-edge weights supplied by the caller (w[e], indexed like column_index)
 enum { MODE_SAG = 0, MODE_GCN = 1, MODE_GIN = 2, MODE_SDDMM = 3, MODE_EDGE = 4 };

@@ -379,63 +379,26 @@ gat_pull_kernel(const GatArgs p)
     }
 }
 
-__global__ void __launch_bounds__(kBlock)
-gat_relu_kernel(float *__restrict__ Y, size_t ld, size_t rows, int D)
-{
-    const size_t n = rows * (size_t)D;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t r = i / (unsigned)D, c = i - r * (unsigned)D;
-        if (Y[r * ld + c] < 0.f) Y[r * ld + c] = 0.f;
-    }
-}
-
-template <int SIDE, int LOG_LPH>
-void launch_pull_lpr(int log_lpr, dim3 grid, hipStream_t stream, const GatArgs &a)
-{
-#define GNNA_GAT_CASE(L)                                                                                                  \
-    case L:                                                                                                               \
-        if constexpr (L >= LOG_LPH) hipLaunchKernelGGL((gat_pull_kernel<SIDE, LOG_LPH, L>), grid, dim3(kBlock), 0, stream, a); \
-        break;
-    switch (log_lpr) {
-        GNNA_GAT_CASE(0) GNNA_GAT_CASE(1) GNNA_GAT_CASE(2) GNNA_GAT_CASE(3) GNNA_GAT_CASE(4) GNNA_GAT_CASE(5) GNNA_GAT_CASE(6)
-    }
-#undef GNNA_GAT_CASE
-}
-
 template <int SIDE>
 int launch_pull(DeviceState *ds, hipStream_t stream, GatArgs a, int partSize)
 {
     if (a.P <= 0) return GNNA_OK;
-    int log_lph = 0;
-    while ((4 << log_lph) < a.dim) log_lph++;
+    const int log_lph = log2_lanes(a.dim, 4);                  // (dim <= kMaxDim: never capped)
     int log_lpr = log_lph;
     while (log_lpr < 6 && (1 << (log_lpr - log_lph)) < a.heads) log_lpr++;
-    // groups per wavefront: 64, fewer while that leaves compute units without a chunk
-    int G = std::max(1, std::min(kWave, 2048 / std::max(1, partSize)));     // about 2048 edges per wavefront at most
-    while (G > 1 && (a.P + G - 1) / G < (int64_t)ds->num_cus * 16) G >>= 1;
-    a.G = G;
-    const int64_t chunks = (a.P + G - 1) / G;
-    const int64_t blocks = (chunks + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (blocks > 0x7fffffffll) return fail(GNNA_ERR_UNSUPPORTED, "GAT attention: %lld neighbor-groups in one call", (long long)a.P);
-    const dim3 grid((unsigned)blocks);
-    switch (log_lph) {
-    case 0: launch_pull_lpr<SIDE, 0>(log_lpr, grid, stream, a); break;
-    case 1: launch_pull_lpr<SIDE, 1>(log_lpr, grid, stream, a); break;
-    case 2: launch_pull_lpr<SIDE, 2>(log_lpr, grid, stream, a); break;
-    case 3: launch_pull_lpr<SIDE, 3>(log_lpr, grid, stream, a); break;
-    case 4: launch_pull_lpr<SIDE, 4>(log_lpr, grid, stream, a); break;
-    case 5: launch_pull_lpr<SIDE, 5>(log_lpr, grid, stream, a); break;
-    default: launch_pull_lpr<SIDE, 6>(log_lpr, grid, stream, a); break;
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "GAT attention launch: %s", hipGetErrorString(e));
-    return GNNA_OK;
-}
-
-unsigned grid_for(size_t work_items, int num_cus)
-{
-    const size_t blocks = (work_items + kBlock - 1) / kBlock;
-    return (unsigned)std::max<size_t>(1, std::min<size_t>(blocks, (size_t)num_cus * 8));
+    const ChunkGrid cg = chunk_grid(a.P, partSize, ds->num_cus);
+    a.G = cg.G;
+    if (cg.blocks > 0x7fffffffll)
+        return fail(GNNA_ERR_UNSUPPORTED, "GAT attention: %lld neighbor-groups in one call", (long long)a.P);
+    const dim3 grid((unsigned)cg.blocks);
+    dispatch_lpr(log_lph, [&](auto H) {
+        dispatch_lpr(log_lpr, [&](auto L) {
+            constexpr int LOG_LPH = decltype(H)::value, LOG_LPR = decltype(L)::value;
+            if constexpr (LOG_LPR >= LOG_LPH)      // (a row has at least the lanes of one head)
+                hipLaunchKernelGGL((gat_pull_kernel<SIDE, LOG_LPH, LOG_LPR>), grid, dim3(kBlock), 0, stream, a);
+        });
+    });
+    return launch_ok("GAT attention launch");
 }
 
 int launch_lse(hipStream_t stream, const float *el, const float *er, const int32_t *rp, const int32_t *col, int64_t N, int64_t M,
@@ -455,9 +418,7 @@ int launch_lse(hipStream_t stream, const float *el, const float *er, const int32
     case 4: hipLaunchKernelGGL(gat_lse_kernel<4>, grid, dim3(kBlock), 0, stream, el, er, rp, col, N, M, heads, slope, lse, seg); break;
     default: hipLaunchKernelGGL(gat_lse_kernel<8>, grid, dim3(kBlock), 0, stream, el, er, rp, col, N, M, heads, slope, lse, seg); break;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "GAT lse launch: %s", hipGetErrorString(e));
-    return GNNA_OK;
+    return launch_ok("GAT lse launch");
 }
 
 // what both entry points check alike.  rect: the rectangular entries name both row counts in their messages.
@@ -479,16 +440,9 @@ int check_common(const char *what, bool rect, int64_t num_out_rows, int64_t num_
         return fail(GNNA_ERR_UNSUPPORTED, "%s: %lld rows in one call (at most 536870911): shard the rows", what, (long long)most);
     if (dim > kMaxDim) return fail(GNNA_ERR_UNSUPPORTED, "%s: at most %d floats per head (got %d)", what, kMaxDim, dim);
     if (heads > 64) return fail(GNNA_ERR_UNSUPPORTED, "%s: at most 64 heads (got %d)", what, heads);
-    gnna_tuning tune;
-    gnna_get_tuning(&tune);
     // the gathered rows are added with float atomics: the order of the additions is not fixed
-    if (tune.deterministic == 1)
-        return fail(GNNA_ERR_UNSUPPORTED, "%s has no deterministic schedule (gnna_tuning.deterministic = 1): its rows are added "
-                                          "with float atomics", what);
-    return GNNA_OK;
+    return deterministic_refused(what, "its rows are added with float atomics");
 }
-
-bool bad_ld(int64_t ld, int64_t width) { return ld < width || ld >= ((int64_t)1 << 29); }
 
 // The forward of both entries: num_out_rows rows (el, lse, out) gather from num_in_rows rows (H, er).
 int gat_forward_impl(const char *what, bool rect, const float *H, int64_t ld_h, const float *el, const float *er,
@@ -528,14 +482,12 @@ int gat_forward_impl(const char *what, bool rect, const float *H, int64_t ld_h, 
     a.gat = H; a.ld_gat = (size_t)ld_h; a.el = el; a.er = er; a.lse = lse;
     a.col = column_index; a.pp = part_pointers; a.p2n = part2Node; a.out = out; a.ld_out = (size_t)ld_out;
     a.slope = negative_slope; a.P = num_parts; a.N = (uint32_t)num_out_rows; a.M = (uint32_t)num_in_rows; a.heads = heads; a.dim = dim;
-    a.xcd_remap = tune.xcd_remap != 0 ? 1 : 0;
+    a.xcd_remap = tune.xcd_remap != 0 ? 1 : 0;                // (this tune went through apply_graph_hints: not xcd_remap_on())
     rc = launch_pull<SIDE_FWD>(ds, stream, a, partSize);
     if (rc != GNNA_OK) return rc;
     if (flags & GNNA_EPILOGUE_RELU) {
-        hipLaunchKernelGGL(gat_relu_kernel, dim3(grid_for((size_t)num_out_rows * (size_t)W, ds->num_cus)), dim3(kBlock), 0, stream,
-                           out, (size_t)ld_out, (size_t)num_out_rows, (int)W);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(GNNA_ERR_HIP, "%s: epilogue launch: %s", what, hipGetErrorString(e));
+        launch_relu_rows(ds, stream, out, num_out_rows, (int)W, ld_out);
+        return launch_ok("%s: epilogue launch", what);
     }
     return GNNA_OK;
 }
@@ -586,16 +538,14 @@ int gat_backward_impl(const char *what, bool rect, const float *H, int64_t ld_h,
     rc = get_workspace(ds, stream, kSlotGatPack, ((size_t)num_out_rows * heads * sizeof(VT) + 255) & ~(size_t)255, &ws);
     if (rc != GNNA_OK) return rc;
     VT *pack = static_cast<VT *>(ws);
-    hipLaunchKernelGGL(gat_pack_kernel, dim3(grid_for((size_t)num_out_rows * heads, ds->num_cus)), dim3(kBlock), 0, stream, dY,
+    hipLaunchKernelGGL(gat_pack_kernel, dim3(elementwise_grid(num_out_rows * heads, ds->num_cus, 8)), dim3(kBlock), 0, stream, dY,
                        (size_t)ld_dy, Y, (size_t)ld_y, el, lse, pack, (size_t)num_out_rows, heads, dim);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "%s: pack launch: %s", what, hipGetErrorString(e));
-    gnna_tuning tune;
-    gnna_get_tuning(&tune);
+    rc = launch_ok("%s: pack launch", what);
+    if (rc != GNNA_OK) return rc;
     GatArgs a{};
     a.er = er; a.pack = pack; a.col = column_index; a.pp = part_pointers; a.p2n = part2Node;
     a.slope = negative_slope; a.P = num_parts; a.heads = heads; a.dim = dim;
-    a.xcd_remap = tune.xcd_remap != 0 ? 1 : 0;
+    a.xcd_remap = xcd_remap_on();
     // destination side: row i pulls H[j], er[j] -> d_el
     a.N = (uint32_t)num_out_rows; a.M = (uint32_t)num_in_rows;
     a.own = dY; a.ld_own = (size_t)ld_dy; a.gat = H; a.ld_gat = (size_t)ld_h; a.dsc = d_el;

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "gnna.h"
+#include "gnna_launch.h"
 
 namespace gnna {
 
@@ -28,6 +29,27 @@ int host_thread_budget(int cap);
 // call; overrides tune->avg_degree / nonlocal_ids when there is an entry, and tune->column_phases when a
 // measured schedule for this feature width was registered with gnna_set_graph_phases().  (gnna_host.cpp)
 void apply_graph_hints(const void *column_index, int dim, gnna_tuning *tune);
+
+// ---- what the launchers of the kernel families share (grids and lane layouts: gnna_launch.h) ------
+// After a launch: GNNA_OK, or GNNA_ERR_HIP with the message "<prefix>: <HIP's error string>"; the prefix is printf-style.
+// (gnna_runtime.hip)
+int launch_ok(const char *prefix_fmt, ...) __attribute__((format(printf, 1, 2)));
+// gnna_tuning.xcd_remap as the kernels take it
+inline int xcd_remap_on()
+{
+    gnna_tuning tune;
+    gnna_get_tuning(&tune);
+    return tune.xcd_remap != 0 ? 1 : 0;
+}
+// An entry whose sums meet through float atomics, under gnna_tuning.deterministic = 1: GNNA_ERR_UNSUPPORTED and
+// "<what> has no deterministic schedule (gnna_tuning.deterministic = 1): <reason>".
+inline int deterministic_refused(const char *what, const char *reason)
+{
+    gnna_tuning tune;
+    gnna_get_tuning(&tune);
+    if (tune.deterministic != 1) return GNNA_OK;
+    return fail(GNNA_ERR_UNSUPPORTED, "%s has no deterministic schedule (gnna_tuning.deterministic = 1): %s", what, reason);
+}
 
 // ---- per-device runtime state (gnna_runtime.hip) -------------------------------------------------
 struct Workspace {
@@ -234,6 +256,9 @@ int launch_x16(DeviceState *ds, hipStream_t stream, const X16Launch &c);
 int reserve_x16(DeviceState *ds, hipStream_t stream, int64_t num_in_rows, int64_t num_out_rows, int dim);
 // out[r, 0:dim] = 0 for every row (rows `ld` floats apart): the dense prologue without its validation (gnna_agg.hip).
 int launch_zero_fill(DeviceState *ds, hipStream_t stream, float *out, int64_t rows, int dim, int64_t ld);
+// out[r, 0:dim] = max(out[r, 0:dim], 0) for every row (NaN stays NaN, as torch.relu): the ReLU epilogue of the entries that do
+// not fuse it.  Enqueues only: the caller's launch_ok reports a failed launch in the entry's own words (gnna_agg.hip).
+void launch_relu_rows(DeviceState *ds, hipStream_t stream, float *out, int64_t rows, int dim, int64_t ld);
 
 // ---- device structure builders (gnna_transpose.hip; also used by gnna_sample.hip) ------------------------------------
 // Tiles of the exclusive scan over n ints: the ints of `partial` that launch_exclusive_scan needs.

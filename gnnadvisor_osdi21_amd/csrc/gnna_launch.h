@@ -1,0 +1,69 @@
+// gnna_launch.h -- launch geometry of the kernels of libgnna.so: the block shape and the host arithmetic that turns a call's
+// sizes into a grid and a lane layout.  Every kernel family calls these and does not copy them.  Plain host functions without
+// a HIP type, so a test compiles this header with the host compiler alone (tests/test_launch_geometry.py).
+#ifndef GNNA_LAUNCH_H_
+#define GNNA_LAUNCH_H_
+
+#include <algorithm>
+#include <cstdint>
+#include <type_traits>
+
+namespace gnna {
+
+constexpr int kWave = 64;
+constexpr int kBlock = 256;
+constexpr int kWavesPerBlock = kBlock / kWave;
+constexpr int kXcds = 8;
+
+// Grid of a gather whose wavefronts take chunks of G consecutive neighbor-groups: G = 64 (about 2048 edges per wavefront at
+// most), fewer while that leaves compute units without a chunk; kWavesPerBlock chunks per block.  The caller refuses
+// blocks > 0x7fffffff in its own words.
+struct ChunkGrid {
+    int G;
+    int64_t blocks;
+};
+inline ChunkGrid chunk_grid(int64_t num_parts, int partSize, int num_cus)
+{
+    int G = std::max(1, std::min(kWave, 2048 / std::max(1, partSize)));
+    while (G > 1 && (num_parts + G - 1) / G < (int64_t)num_cus * 16) G >>= 1;
+    const int64_t chunks = (num_parts + G - 1) / G;
+    return {G, (chunks + kWavesPerBlock - 1) / kWavesPerBlock};
+}
+
+// log2 of the lanes that cover `dim` elements at elems_per_lane each: the smallest power of two that does, 2^cap at most
+// (wider rows are taken in column blocks).
+inline int log2_lanes(int dim, int elems_per_lane, int cap = 6)
+{
+    int l = 0;
+    while (l < cap && (elems_per_lane << l) < dim) l++;
+    return l;
+}
+
+// f(std::integral_constant<int, L>) for L = log_lpr in 0 .. 6 (above: 6): a run-time lane count becomes a template argument.
+template <class F>
+void dispatch_lpr(int log_lpr, F &&f)
+{
+    switch (log_lpr) {
+    case 0: f(std::integral_constant<int, 0>()); break;
+    case 1: f(std::integral_constant<int, 1>()); break;
+    case 2: f(std::integral_constant<int, 2>()); break;
+    case 3: f(std::integral_constant<int, 3>()); break;
+    case 4: f(std::integral_constant<int, 4>()); break;
+    case 5: f(std::integral_constant<int, 5>()); break;
+    default: f(std::integral_constant<int, 6>()); break;
+    }
+}
+
+// Blocks of a grid-stride kernel over `items` work items: one thread each, blocks_per_cu blocks per compute unit at most.
+inline unsigned elementwise_grid(int64_t items, int num_cus, int blocks_per_cu)
+{
+    const int64_t blocks = (items + kBlock - 1) / kBlock;
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)num_cus * blocks_per_cu));
+}
+
+// a row stride that is narrower than the row or does not fit the kernels' 32-bit element offsets
+inline bool bad_ld(int64_t ld, int64_t width) { return ld < width || ld >= ((int64_t)1 << 29); }
+
+}  // namespace gnna
+
+#endif

@@ -263,21 +263,9 @@ scatter_arg_kernel(const float *__restrict__ go, size_t ld_go, const int32_t *__
 template <int OP>
 void launch_main(int log_lpr, dim3 grid, hipStream_t stream, const ReduceArgs &a)
 {
-    switch (log_lpr) {
-    case 0: hipLaunchKernelGGL((reduce_kernel<OP, 0>), grid, dim3(kBlock), 0, stream, a); break;
-    case 1: hipLaunchKernelGGL((reduce_kernel<OP, 1>), grid, dim3(kBlock), 0, stream, a); break;
-    case 2: hipLaunchKernelGGL((reduce_kernel<OP, 2>), grid, dim3(kBlock), 0, stream, a); break;
-    case 3: hipLaunchKernelGGL((reduce_kernel<OP, 3>), grid, dim3(kBlock), 0, stream, a); break;
-    case 4: hipLaunchKernelGGL((reduce_kernel<OP, 4>), grid, dim3(kBlock), 0, stream, a); break;
-    case 5: hipLaunchKernelGGL((reduce_kernel<OP, 5>), grid, dim3(kBlock), 0, stream, a); break;
-    default: hipLaunchKernelGGL((reduce_kernel<OP, 6>), grid, dim3(kBlock), 0, stream, a); break;
-    }
-}
-
-unsigned grid_for(size_t work_items, int num_cus)
-{
-    const size_t blocks = (work_items + kBlock - 1) / kBlock;
-    return (unsigned)std::max<size_t>(1, std::min<size_t>(blocks, (size_t)num_cus * 8));
+    dispatch_lpr(log_lpr, [&](auto L) {
+        hipLaunchKernelGGL((reduce_kernel<OP, decltype(L)::value>), grid, dim3(kBlock), 0, stream, a);
+    });
 }
 
 // Scratch of the reduce entry: slot 5 = the keys.  Eager calls of a stream share it (grow-only), a captured call gets its
@@ -309,8 +297,8 @@ int gnna_agg_reduce_ld_f32(int op, const float *input, int64_t ld_in, int64_t nu
     if (partSize <= 0) return fail(GNNA_ERR_INVALID_ARGUMENT, "partSize must be positive (got %d)", partSize);
     if (num_out_rows >= ((int64_t)1 << 29))
         return fail(GNNA_ERR_UNSUPPORTED, "%lld destination rows in one call (at most 536870911): shard the rows", (long long)num_out_rows);
-    if (ld_in < dim || ld_out < dim || (arg && ld_arg < dim) || ld_in >= ((int64_t)1 << 29) || ld_out >= ((int64_t)1 << 29) ||
-        ld_arg >= ((int64_t)1 << 29))
+    // (a null arg leaves ld_arg with its upper bound only: nothing is strided by it)
+    if (bad_ld(ld_in, dim) || bad_ld(ld_out, dim) || (arg ? bad_ld(ld_arg, dim) : ld_arg >= ((int64_t)1 << 29)))
         return fail(GNNA_ERR_INVALID_ARGUMENT, "row strides must be >= dim and < 2^29 elements (ld_in=%lld ld_out=%lld ld_arg=%lld dim=%d)",
                     (long long)ld_in, (long long)ld_out, (long long)ld_arg, dim);
     if (num_out_rows == 0) return GNNA_OK;
@@ -326,17 +314,13 @@ int gnna_agg_reduce_ld_f32(int op, const float *input, int64_t ld_in, int64_t nu
     int rc = get_device_state(&ds);
     if (rc != GNNA_OK) return rc;
     const size_t n = (size_t)num_out_rows * (size_t)dim;
-    const unsigned eblocks = grid_for(n, ds->num_cus);
+    const unsigned eblocks = elementwise_grid((int64_t)n, ds->num_cus, 8);
     const int relu = (flags & GNNA_EPILOGUE_RELU) ? 1 : 0;
     if (!work) {
         hipLaunchKernelGGL(reduce_empty_kernel, dim3(eblocks), dim3(kBlock), 0, stream, out, (size_t)ld_out, arg, (size_t)ld_arg,
                            (size_t)num_out_rows, dim);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(GNNA_ERR_HIP, "neighbor reduce launch: %s", hipGetErrorString(e));
-        return GNNA_OK;
+        return launch_ok("neighbor reduce launch");
     }
-    gnna_tuning tune;
-    gnna_get_tuning(&tune);
     void *ws = nullptr;
     rc = get_workspace(ds, stream, kSlotReduceKeys, (n * sizeof(u64) + 255) & ~(size_t)255, &ws);
     if (rc != GNNA_OK) return rc;
@@ -348,25 +332,18 @@ int gnna_agg_reduce_ld_f32(int op, const float *input, int64_t ld_in, int64_t nu
     a.X = input; a.ldx = (size_t)ld_in; a.col = column_index; a.pp = part_pointers; a.p2n = part2Node; a.K = K;
     a.P = num_parts; a.num_in_rows = (uint32_t)std::min<int64_t>(num_in_rows, (int64_t)1 << 31);   // (ids are int32)
     a.num_out_rows = (uint32_t)num_out_rows;
-    a.D = dim; a.xcd_remap = tune.xcd_remap != 0 ? 1 : 0;
-    // groups per wavefront: 64, fewer while that leaves compute units without a chunk
-    int G = std::max(1, std::min(kWave, 2048 / std::max(1, partSize)));     // about 2048 edges per wavefront at most
-    while (G > 1 && (num_parts + G - 1) / G < (int64_t)ds->num_cus * 16) G >>= 1;
-    a.G = G;
-    const int64_t chunks = (num_parts + G - 1) / G;
-    const int64_t blocks = (chunks + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (blocks > 0x7fffffffll)
+    a.D = dim; a.xcd_remap = xcd_remap_on();
+    const ChunkGrid cg = chunk_grid(num_parts, partSize, ds->num_cus);
+    a.G = cg.G;
+    if (cg.blocks > 0x7fffffffll)
         return fail(GNNA_ERR_UNSUPPORTED, "neighbor reduce: %lld neighbor-groups in one call", (long long)num_parts);
-    int log_lpr = 0;
-    while (log_lpr < 6 && (4 << log_lpr) < dim) log_lpr++;
-    const dim3 grid((unsigned)blocks);
+    const int log_lpr = log2_lanes(dim, 4);
+    const dim3 grid((unsigned)cg.blocks);
     if (op == GNNA_REDUCE_MAX) launch_main<GNNA_REDUCE_MAX>(log_lpr, grid, stream, a);
     else launch_main<GNNA_REDUCE_MIN>(log_lpr, grid, stream, a);
     hipLaunchKernelGGL(reduce_finish_kernel, dim3(eblocks), dim3(kBlock), 0, stream, K, out, (size_t)ld_out, arg, (size_t)ld_arg,
                        (size_t)num_out_rows, dim, op, relu);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "neighbor reduce launch: %s", hipGetErrorString(e));
-    return GNNA_OK;
+    return launch_ok("neighbor reduce launch");
 }
 
 int gnna_scatter_arg_ld_f32(const float *grad_out, int64_t ld_go, const int32_t *arg, int64_t ld_arg, const int32_t *column_index,
@@ -378,26 +355,22 @@ int gnna_scatter_arg_ld_f32(const float *grad_out, int64_t ld_go, const int32_t 
     if (num_out_rows < 0 || num_in_rows < 0)
         return fail(GNNA_ERR_INVALID_ARGUMENT, "negative size (num_out_rows=%lld num_in_rows=%lld)", (long long)num_out_rows,
                     (long long)num_in_rows);
-    if (ld_go < dim || ld_arg < dim || ld_gi < dim || ld_go >= ((int64_t)1 << 29) || ld_arg >= ((int64_t)1 << 29) ||
-        ld_gi >= ((int64_t)1 << 29))
+    if (bad_ld(ld_go, dim) || bad_ld(ld_arg, dim) || bad_ld(ld_gi, dim))
         return fail(GNNA_ERR_INVALID_ARGUMENT, "row strides must be >= dim and < 2^29 elements (ld_go=%lld ld_arg=%lld ld_gi=%lld dim=%d)",
                     (long long)ld_go, (long long)ld_arg, (long long)ld_gi, dim);
     if (num_out_rows >= ((int64_t)1 << 29) || num_in_rows >= ((int64_t)1 << 31))
         return fail(GNNA_ERR_UNSUPPORTED, "too many rows in one call (num_out_rows=%lld num_in_rows=%lld)", (long long)num_out_rows,
                     (long long)num_in_rows);
-    gnna_tuning tune;
-    gnna_get_tuning(&tune);
     // one float atomic per element: the order of the additions into a source row is not fixed
-    if (tune.deterministic == 1)
-        return fail(GNNA_ERR_UNSUPPORTED, "gnna_scatter_arg_ld_f32 has no deterministic schedule (gnna_tuning.deterministic = 1): "
-                                          "its sums meet through float atomics");
+    int rc = deterministic_refused("gnna_scatter_arg_ld_f32", "its sums meet through float atomics");
+    if (rc != GNNA_OK) return rc;
     if (num_in_rows == 0) return GNNA_OK;
     if (!grad_in) return fail(GNNA_ERR_INVALID_ARGUMENT, "null grad_in pointer");
     if (num_out_rows > 0 && (!grad_out || !arg || !column_index)) return fail(GNNA_ERR_INVALID_ARGUMENT, "null pointer argument");
     if (grad_in == grad_out) return fail(GNNA_ERR_INVALID_ARGUMENT, "grad_in must not alias grad_out");
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     DeviceState *ds = nullptr;
-    int rc = get_device_state(&ds);
+    rc = get_device_state(&ds);
     if (rc != GNNA_OK) return rc;
     if (!(flags & GNNA_ACCUMULATE)) {
         rc = launch_zero_fill(ds, stream, grad_in, num_in_rows, dim, ld_gi);
@@ -405,11 +378,10 @@ int gnna_scatter_arg_ld_f32(const float *grad_out, int64_t ld_go, const int32_t 
     }
     if (num_out_rows == 0) return GNNA_OK;
     const size_t n = (size_t)num_out_rows * (size_t)dim;
-    hipLaunchKernelGGL(scatter_arg_kernel, dim3(grid_for(n, ds->num_cus)), dim3(kBlock), 0, stream, grad_out, (size_t)ld_go, arg,
-                       (size_t)ld_arg, column_index, grad_in, (size_t)ld_gi, (uint32_t)num_in_rows, (size_t)num_out_rows, dim);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "scatter_arg launch: %s", hipGetErrorString(e));
-    return GNNA_OK;
+    hipLaunchKernelGGL(scatter_arg_kernel, dim3(elementwise_grid((int64_t)n, ds->num_cus, 8)), dim3(kBlock), 0, stream, grad_out,
+                       (size_t)ld_go, arg, (size_t)ld_arg, column_index, grad_in, (size_t)ld_gi, (uint32_t)num_in_rows,
+                       (size_t)num_out_rows, dim);
+    return launch_ok("scatter_arg launch");
 }
 
 }  // extern "C"

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cstdarg>
+#include <cstdio>
 #include <mutex>
 #include <vector>
 
@@ -19,6 +21,18 @@ std::mutex g_dev_mutex;
 std::atomic<uint32_t> g_seq{0};
 
 }  // namespace
+
+int launch_ok(const char *prefix_fmt, ...)
+{
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return GNNA_OK;
+    char prefix[256];
+    va_list ap;
+    va_start(ap, prefix_fmt);
+    std::vsnprintf(prefix, sizeof(prefix), prefix_fmt, ap);
+    va_end(ap);
+    return fail(GNNA_ERR_HIP, "%s: %s", prefix, hipGetErrorString(e));
+}
 
 int get_device_state(DeviceState **out)
 {

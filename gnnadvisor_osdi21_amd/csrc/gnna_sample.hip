@@ -322,12 +322,6 @@ part_fill_kernel(const int32_t *__restrict__ blk_rp, const int32_t *__restrict__
     }
 }
 
-unsigned grid_for(int64_t items, int num_cus)
-{
-    const int64_t blocks = (items + kBlock - 1) / kBlock;
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)num_cus * 16));
-}
-
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 int pow2_at_least(int64_t x)
@@ -388,10 +382,10 @@ int gnna_sample_neighbors_i32(const int32_t *row_pointers, const int32_t *column
 
     const dim3 block(kBlock);
     const int64_t clear_words = (int64_t)((rec_bytes + pos_bytes + mark_bytes) / 4);
-    hipLaunchKernelGGL(clear_kernel, dim3(grid_for(clear_words, ds->num_cus)), block, 0, stream, reinterpret_cast<int32_t *>(ws),
-                       clear_words);
-    hipLaunchKernelGGL(seed_kernel, dim3(grid_for(num_seeds + 1, ds->num_cus)), block, 0, stream, row_pointers, (uint32_t)num_nodes,
-                       seeds, num_seeds, fanout, seedpos, blk_row_pointers, rec);
+    hipLaunchKernelGGL(clear_kernel, dim3(elementwise_grid(clear_words, ds->num_cus, 16)), block, 0, stream,
+                       reinterpret_cast<int32_t *>(ws), clear_words);
+    hipLaunchKernelGGL(seed_kernel, dim3(elementwise_grid(num_seeds + 1, ds->num_cus, 16)), block, 0, stream, row_pointers,
+                       (uint32_t)num_nodes, seeds, num_seeds, fanout, seedpos, blk_row_pointers, rec);
     rc = launch_exclusive_scan(stream, blk_row_pointers, num_seeds + 1, partial);
     if (rc != GNNA_OK) return rc;
     if (num_seeds > 0) {
@@ -411,15 +405,15 @@ int gnna_sample_neighbors_i32(const int32_t *row_pointers, const int32_t *column
     rc = launch_exclusive_scan(stream, mark, num_nodes + 1, partial);
     if (rc != GNNA_OK) return rc;
     const int64_t relabel_items = std::max(std::max(num_nodes, num_seeds), edge_capacity);
-    hipLaunchKernelGGL(relabel_kernel, dim3(grid_for(relabel_items, ds->num_cus)), block, 0, stream, seeds, num_seeds, num_nodes,
-                       seedpos, mark, blk_row_pointers, blk_column_index, src_nodes, edge_capacity, src_capacity, rec);
+    hipLaunchKernelGGL(relabel_kernel, dim3(elementwise_grid(relabel_items, ds->num_cus, 16)), block, 0, stream, seeds, num_seeds,
+                       num_nodes, seedpos, mark, blk_row_pointers, blk_column_index, src_nodes, edge_capacity, src_capacity, rec);
     if (partPtr) {
-        hipLaunchKernelGGL(part_count_kernel, dim3(grid_for(num_seeds + 1, ds->num_cus)), block, 0, stream, blk_row_pointers, num_seeds,
-                           partSize, first_part);
+        hipLaunchKernelGGL(part_count_kernel, dim3(elementwise_grid(num_seeds + 1, ds->num_cus, 16)), block, 0, stream,
+                           blk_row_pointers, num_seeds, partSize, first_part);
         rc = launch_exclusive_scan(stream, first_part, num_seeds + 1, partial);
         if (rc != GNNA_OK) return rc;
-        hipLaunchKernelGGL(part_fill_kernel, dim3(grid_for(edge_capacity + 1, ds->num_cus)), block, 0, stream, blk_row_pointers,
-                           first_part, num_seeds, partSize, edge_capacity, partPtr, part2Node, rec);
+        hipLaunchKernelGGL(part_fill_kernel, dim3(elementwise_grid(edge_capacity + 1, ds->num_cus, 16)), block, 0, stream,
+                           blk_row_pointers, first_part, num_seeds, partSize, edge_capacity, partPtr, part2Node, rec);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(GNNA_ERR_HIP, "%s: launch: %s", what, hipGetErrorString(e));

@@ -108,9 +108,7 @@ int launch_exclusive_scan(hipStream_t stream, int32_t *data, int64_t n, int32_t 
     hipLaunchKernelGGL(scan_reduce_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, stream, data, n, partial);
     hipLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(kBlock), 0, stream, partial, tiles);
     hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, stream, data, n, partial);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "scan launch: %s", hipGetErrorString(e));
-    return GNNA_OK;
+    return launch_ok("scan launch");
 }
 
 namespace {
@@ -273,12 +271,6 @@ part_fill_kernel(const int32_t *__restrict__ rp, const int32_t *__restrict__ fir
     }
 }
 
-unsigned grid_for(int64_t items, int num_cus)
-{
-    const int64_t blocks = (items + kBlock - 1) / kBlock;
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)num_cus * 16));
-}
-
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -312,7 +304,8 @@ int scan_parts(const char *what, DeviceState *ds, hipStream_t stream, int partSi
     if (rc != GNNA_OK) return rc;
     int32_t *count = static_cast<int32_t *>(ws);
     int32_t *partial = reinterpret_cast<int32_t *>(static_cast<char *>(ws) + align256((size_t)n * 4));
-    hipLaunchKernelGGL(part_count_kernel, dim3(grid_for(n, ds->num_cus)), dim3(kBlock), 0, stream, rp, num_nodes, partSize, count);
+    hipLaunchKernelGGL(part_count_kernel, dim3(elementwise_grid(n, ds->num_cus, 16)), dim3(kBlock), 0, stream, rp, num_nodes,
+                       partSize, count);
     rc = launch_exclusive_scan(stream, count, n, partial);
     if (rc != GNNA_OK) return rc;
     int32_t total = 0;
@@ -363,11 +356,9 @@ int gnna_transpose_csr_i32(const int32_t *row_pointers, const int32_t *column_in
     const int64_t nnz = nnz32;
     if (nnz < 0) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: row_pointers[num_out_rows] = %d", what, nnz32);
     if (nnz == 0) {
-        hipLaunchKernelGGL(fill_i32_kernel, dim3(grid_for(num_in_rows + 1, ds->num_cus)), dim3(kBlock), 0, stream, t_row_pointers,
-                           num_in_rows + 1, 0);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(GNNA_ERR_HIP, "%s: launch: %s", what, hipGetErrorString(e));
-        return GNNA_OK;
+        hipLaunchKernelGGL(fill_i32_kernel, dim3(elementwise_grid(num_in_rows + 1, ds->num_cus, 16)), dim3(kBlock), 0, stream,
+                           t_row_pointers, num_in_rows + 1, 0);
+        return launch_ok("%s: launch", what);
     }
     if (!column_index || !t_column_index) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null index pointer", what);
     if (t_column_index == column_index || t_perm == column_index || t_perm == t_column_index ||
@@ -413,13 +404,11 @@ int gnna_transpose_csr_i32(const int32_t *row_pointers, const int32_t *column_in
         keys_in = keys_out;
         vals_in = vals_out;
     }
-    hipLaunchKernelGGL(transpose_rows_kernel, dim3(grid_for(num_in_rows + 1, ds->num_cus)), block, 0, stream, keys_b, nnz, num_in_rows,
-                       t_row_pointers);
-    hipLaunchKernelGGL(transpose_finish_kernel, dim3(grid_for(nnz, ds->num_cus)), block, 0, stream, row_pointers, num_out_rows, n_in,
-                       nnz, keys_b, vals_b, t_perm != nullptr);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "%s: launch: %s", what, hipGetErrorString(e));
-    return GNNA_OK;
+    hipLaunchKernelGGL(transpose_rows_kernel, dim3(elementwise_grid(num_in_rows + 1, ds->num_cus, 16)), block, 0, stream, keys_b,
+                       nnz, num_in_rows, t_row_pointers);
+    hipLaunchKernelGGL(transpose_finish_kernel, dim3(elementwise_grid(nnz, ds->num_cus, 16)), block, 0, stream, row_pointers,
+                       num_out_rows, n_in, nnz, keys_b, vals_b, t_perm != nullptr);
+    return launch_ok("%s: launch", what);
 }
 
 int64_t gnna_count_parts_device_i32(int partSize, const int32_t *indptr, int64_t num_nodes, void *stream_v)
@@ -462,11 +451,9 @@ int gnna_build_part_device_i32(int partSize, const int32_t *indptr, int64_t num_
     if (expect != num_parts)
         return fail(GNNA_ERR_INVALID_ARGUMENT, "num_parts=%lld but the CSR has %lld groups at partSize=%d", (long long)num_parts,
                     (long long)expect, partSize);
-    hipLaunchKernelGGL(part_fill_kernel, dim3(grid_for(num_parts + 1, ds->num_cus)), dim3(kBlock), 0, stream, indptr, first_part,
-                       num_nodes, partSize, num_parts, partPtr, part2Node);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "%s: launch: %s", what, hipGetErrorString(e));
-    return GNNA_OK;
+    hipLaunchKernelGGL(part_fill_kernel, dim3(elementwise_grid(num_parts + 1, ds->num_cus, 16)), dim3(kBlock), 0, stream, indptr,
+                       first_part, num_nodes, partSize, num_parts, partPtr, part2Node);
+    return launch_ok("%s: launch", what);
 }
 
 #pragma GCC visibility pop

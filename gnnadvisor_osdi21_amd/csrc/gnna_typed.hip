@@ -414,38 +414,29 @@ enum { KIND_EXPAND = 0, KIND_CONTRACT = 1, KIND_COEF_GRAD = 2 };
 template <int KIND, int BT>
 void launch_lpr(int log_lpr, dim3 grid, size_t lds_bytes, hipStream_t stream, const TypedArgs &a)
 {
-#define GNNA_TYPED_CASE(L)                                                                                                         \
-    case L:                                                                                                                        \
-        if constexpr (KIND == KIND_EXPAND) hipLaunchKernelGGL((typed_expand_kernel<BT, L>), grid, dim3(kBlock), lds_bytes, stream, a); \
-        else if constexpr (KIND == KIND_CONTRACT) hipLaunchKernelGGL((typed_contract_kernel<L>), grid, dim3(kBlock), lds_bytes, stream, a); \
-        else hipLaunchKernelGGL((typed_coef_grad_kernel<BT, L>), grid, dim3(kBlock), lds_bytes, stream, a);                        \
-        break;
-    switch (log_lpr) {
-        GNNA_TYPED_CASE(0) GNNA_TYPED_CASE(1) GNNA_TYPED_CASE(2) GNNA_TYPED_CASE(3) GNNA_TYPED_CASE(4) GNNA_TYPED_CASE(5)
-        default: GNNA_TYPED_CASE(6)
-    }
-#undef GNNA_TYPED_CASE
+    dispatch_lpr(log_lpr, [&](auto LL) {
+        constexpr int L = decltype(LL)::value;
+        const dim3 block(kBlock);
+        if constexpr (KIND == KIND_EXPAND) hipLaunchKernelGGL((typed_expand_kernel<BT, L>), grid, block, lds_bytes, stream, a);
+        else if constexpr (KIND == KIND_CONTRACT) hipLaunchKernelGGL((typed_contract_kernel<L>), grid, block, lds_bytes, stream, a);
+        else hipLaunchKernelGGL((typed_coef_grad_kernel<BT, L>), grid, block, lds_bytes, stream, a);
+    });
 }
 
 template <int KIND>
 int launch_typed(DeviceState *ds, hipStream_t stream, TypedArgs a, int partSize, const char *what)
 {
     if (a.P <= 0) return GNNA_OK;
-    int log_lpr = 0;
-    while (log_lpr < 6 && (4 << log_lpr) < a.dim) log_lpr++;
+    const int log_lpr = log2_lanes(a.dim, 4);
     int bt = 1;
     while (bt < a.B) bt <<= 1;
     a.BS = KIND == KIND_CONTRACT ? (a.B + 3) & ~3 : bt;
     a.lds = (int64_t)a.R * a.BS <= kTypedLdsCells ? 1 : 0;
     const size_t lds_bytes = a.lds ? (size_t)a.R * a.BS * sizeof(float) : 0;
-    // groups per wavefront: 64, fewer while that leaves compute units without a chunk
-    int G = std::max(1, std::min(kWave, 2048 / std::max(1, partSize)));     // about 2048 edges per wavefront at most
-    while (G > 1 && (a.P + G - 1) / G < (int64_t)ds->num_cus * 16) G >>= 1;
-    a.G = G;
-    const int64_t chunks = (a.P + G - 1) / G;
-    const int64_t blocks = (chunks + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (blocks > 0x7fffffffll) return fail(GNNA_ERR_UNSUPPORTED, "%s: %lld neighbor-groups in one call", what, (long long)a.P);
-    const dim3 grid((unsigned)blocks);
+    const ChunkGrid cg = chunk_grid(a.P, partSize, ds->num_cus);
+    a.G = cg.G;
+    if (cg.blocks > 0x7fffffffll) return fail(GNNA_ERR_UNSUPPORTED, "%s: %lld neighbor-groups in one call", what, (long long)a.P);
+    const dim3 grid((unsigned)cg.blocks);
     if constexpr (KIND == KIND_CONTRACT) {
         launch_lpr<KIND, 1>(log_lpr, grid, lds_bytes, stream, a);
     } else {
@@ -457,9 +448,7 @@ int launch_typed(DeviceState *ds, hipStream_t stream, TypedArgs a, int partSize,
         default: launch_lpr<KIND, 16>(log_lpr, grid, lds_bytes, stream, a); break;
         }
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "%s launch: %s", what, hipGetErrorString(e));
-    return GNNA_OK;
+    return launch_ok("%s launch", what);
 }
 
 // what the three entry points check alike, before any device work
@@ -481,22 +470,8 @@ int check_typed(const char *what, int64_t num_in_rows, int64_t num_out_rows, int
     if ((int64_t)num_bases * dim >= ((int64_t)1 << 29) || (int64_t)num_types * kMaxBases >= ((int64_t)1 << 29))
         return fail(GNNA_ERR_UNSUPPORTED, "%s: num_bases * dim and num_types * 16 must stay below 2^29 (num_types=%d num_bases=%d "
                     "dim=%d)", what, num_types, num_bases, dim);
-    gnna_tuning tune;
-    gnna_get_tuning(&tune);
     // the gathered rows are added with float atomics: the order of the additions is not fixed
-    if (tune.deterministic == 1)
-        return fail(GNNA_ERR_UNSUPPORTED, "%s has no deterministic schedule (gnna_tuning.deterministic = 1): its sums are added "
-                                          "with float atomics", what);
-    return GNNA_OK;
-}
-
-bool bad_ld(int64_t ld, int64_t width) { return ld < width || ld >= ((int64_t)1 << 29); }
-
-int xcd_remap_on()
-{
-    gnna_tuning tune;
-    gnna_get_tuning(&tune);
-    return tune.xcd_remap != 0 ? 1 : 0;
+    return deterministic_refused(what, "its sums are added with float atomics");
 }
 
 }  // namespace

@@ -284,20 +284,6 @@ x16_finish_kernel(const float *__restrict__ F, size_t ldf, uint16_t *__restrict_
     }
 }
 
-// fp32 output: out = max(out, 0) over the D columns of every row (NaN stays NaN, as torch.relu)
-__global__ void __launch_bounds__(kBlock)
-x16_relu_kernel(float *__restrict__ Y, size_t ld, size_t rows, int D)
-{
-    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t nthreads = (size_t)gridDim.x * blockDim.x;
-    const size_t n = rows * (size_t)D;
-    for (size_t i = tid; i < n; i += nthreads) {
-        const size_t r = i / (unsigned)D, c = i - r * (unsigned)D;
-        const float v = Y[r * ld + c];
-        if (v < 0.f) Y[r * ld + c] = 0.f;
-    }
-}
-
 // staged copy of source rows that cannot be read 16 bytes at a time: Xs[r, 0:Dp] = X[r, 0:D] | zeros, Dp a multiple of 8
 __global__ void __launch_bounds__(kBlock)
 x16_stage_kernel(const uint16_t *__restrict__ X, size_t ld_in, uint16_t *__restrict__ Xs, size_t rows, int D, int Dp)
@@ -314,21 +300,9 @@ x16_stage_kernel(const uint16_t *__restrict__ X, size_t ld_in, uint16_t *__restr
 template <int TYPE, bool WEIGHTED>
 void launch_main(int log_lpr, dim3 grid, hipStream_t stream, const X16Args &a)
 {
-    switch (log_lpr) {
-    case 0: hipLaunchKernelGGL((x16_kernel<TYPE, 0, WEIGHTED>), grid, dim3(kBlock), 0, stream, a); break;
-    case 1: hipLaunchKernelGGL((x16_kernel<TYPE, 1, WEIGHTED>), grid, dim3(kBlock), 0, stream, a); break;
-    case 2: hipLaunchKernelGGL((x16_kernel<TYPE, 2, WEIGHTED>), grid, dim3(kBlock), 0, stream, a); break;
-    case 3: hipLaunchKernelGGL((x16_kernel<TYPE, 3, WEIGHTED>), grid, dim3(kBlock), 0, stream, a); break;
-    case 4: hipLaunchKernelGGL((x16_kernel<TYPE, 4, WEIGHTED>), grid, dim3(kBlock), 0, stream, a); break;
-    case 5: hipLaunchKernelGGL((x16_kernel<TYPE, 5, WEIGHTED>), grid, dim3(kBlock), 0, stream, a); break;
-    default: hipLaunchKernelGGL((x16_kernel<TYPE, 6, WEIGHTED>), grid, dim3(kBlock), 0, stream, a); break;
-    }
-}
-
-unsigned grid_for(size_t work_items, int num_cus)
-{
-    const size_t blocks = (work_items + kBlock - 1) / kBlock;
-    return (unsigned)std::max<size_t>(1, std::min<size_t>(blocks, (size_t)num_cus * 8));
+    dispatch_lpr(log_lpr, [&](auto L) {
+        hipLaunchKernelGGL((x16_kernel<TYPE, decltype(L)::value, WEIGHTED>), grid, dim3(kBlock), 0, stream, a);
+    });
 }
 
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -365,7 +339,7 @@ int launch_x16(DeviceState *ds, hipStream_t stream, const X16Launch &c)
         void *xs = nullptr;
         rc = get_workspace(ds, stream, kSlotX16Stage, align256((size_t)c.num_in_rows * (size_t)dp * elem), &xs);
         if (rc != GNNA_OK) return rc;
-        hipLaunchKernelGGL(x16_stage_kernel, dim3(grid_for((size_t)c.num_in_rows * dp, ds->num_cus)), dim3(kBlock), 0, stream,
+        hipLaunchKernelGGL(x16_stage_kernel, dim3(elementwise_grid(c.num_in_rows * dp, ds->num_cus, 8)), dim3(kBlock), 0, stream,
                            static_cast<const uint16_t *>(c.input), (size_t)c.ld_in, static_cast<uint16_t *>(xs),
                            (size_t)c.num_in_rows, c.dim, dp);
         X = static_cast<const char *>(xs);
@@ -399,30 +373,26 @@ int launch_x16(DeviceState *ds, hipStream_t stream, const X16Launch &c)
         a.P = c.num_parts; a.num_in_rows = (uint32_t)std::min<int64_t>(c.num_in_rows, (int64_t)1 << 31);   // (ids are int32)
          a.num_out_rows = (uint32_t)c.num_out_rows;
         a.D = c.dim; a.xcd_remap = c.xcd_remap ? 1 : 0;
-        // groups per wavefront: 64, fewer while that leaves compute units without a chunk
-        int G = std::max(1, std::min(kWave, 2048 / std::max(1, c.partSize)));     // about 2048 edges per wavefront at most
-        while (G > 1 && (c.num_parts + G - 1) / G < (int64_t)ds->num_cus * 16) G >>= 1;
-        a.G = G;
-        const int64_t chunks = (c.num_parts + G - 1) / G;
-        const int64_t blocks = (chunks + kWavesPerBlock - 1) / kWavesPerBlock;
-        if (blocks > 0x7fffffffll) return fail(GNNA_ERR_UNSUPPORTED, "16-bit aggregation: %lld neighbor-groups in one call", (long long)c.num_parts);
-        int log_lpr = 0;
-        while (log_lpr < 6 && (8 << log_lpr) < c.dim) log_lpr++;
-        const dim3 grid((unsigned)blocks);
+        const ChunkGrid cg = chunk_grid(c.num_parts, c.partSize, ds->num_cus);
+        a.G = cg.G;
+        if (cg.blocks > 0x7fffffffll)
+            return fail(GNNA_ERR_UNSUPPORTED, "16-bit aggregation: %lld neighbor-groups in one call", (long long)c.num_parts);
+        const int log_lpr = log2_lanes(c.dim, 8);
+        const dim3 grid((unsigned)cg.blocks);
         const bool weighted = c.mode == MODE_GCN;
         if (c.in_type == GNNA_BF16) {
             if (weighted) launch_main<GNNA_BF16, true>(log_lpr, grid, stream, a); else launch_main<GNNA_BF16, false>(log_lpr, grid, stream, a);
         } else {
             if (weighted) launch_main<GNNA_F16, true>(log_lpr, grid, stream, a); else launch_main<GNNA_F16, false>(log_lpr, grid, stream, a);
         }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(GNNA_ERR_HIP, "16-bit aggregation launch: %s", hipGetErrorString(e));
+        rc = launch_ok("16-bit aggregation launch");
+        if (rc != GNNA_OK) return rc;
     }
     // ---- epilogue: ReLU, and the one rounding of a 16-bit output ------------------------------------------------------------
     if (out16) {
         const int vec = (c.dim & 7) == 0 && (c.ld_out & 7) == 0 && (reinterpret_cast<uintptr_t>(c.out) & 15) == 0 &&
                         (reinterpret_cast<uintptr_t>(F) & 15) == 0;
-        const unsigned blocks = grid_for((size_t)c.num_out_rows * (size_t)c.dim / (vec ? 8 : 1), ds->num_cus);
+        const unsigned blocks = elementwise_grid(c.num_out_rows * c.dim / (vec ? 8 : 1), ds->num_cus, 8);
         uint16_t *o = static_cast<uint16_t *>(c.out);
         if (c.in_type == GNNA_BF16)
             hipLaunchKernelGGL(x16_finish_kernel<GNNA_BF16>, dim3(blocks), dim3(kBlock), 0, stream, F, ldf, o, (size_t)c.ld_out,
@@ -431,12 +401,9 @@ int launch_x16(DeviceState *ds, hipStream_t stream, const X16Launch &c)
             hipLaunchKernelGGL(x16_finish_kernel<GNNA_F16>, dim3(blocks), dim3(kBlock), 0, stream, F, ldf, o, (size_t)c.ld_out,
                                (size_t)c.num_out_rows, c.dim, c.relu ? 1 : 0, vec);
     } else if (c.relu) {
-        hipLaunchKernelGGL(x16_relu_kernel, dim3(grid_for((size_t)c.num_out_rows * (size_t)c.dim, ds->num_cus)), dim3(kBlock), 0, stream,
-                           F, ldf, (size_t)c.num_out_rows, c.dim);
+        launch_relu_rows(ds, stream, F, c.num_out_rows, c.dim, c.ld_out);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "16-bit aggregation epilogue: %s", hipGetErrorString(e));
-    return GNNA_OK;
+    return launch_ok("16-bit aggregation epilogue");
 }
 
 }  // namespace gnna

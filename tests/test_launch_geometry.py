@@ -1,0 +1,74 @@
+"""Launch geometry of the gather kernels, pinned (no GPU): a small program with its own main includes csrc/gnna_launch.h alone,
+is compiled with the host C++ compiler (g++, as oracle/ compiles its sources) and prints what chunk_grid and log2_lanes answer.
+The expected values were worked out by hand from the formula every launcher carried before it was shared: G = max(1, min(64,
+2048 / partSize)), halved while ceil(P / G) < 16 * num_cus; blocks = ceil(ceil(P / G) / 4).  A slip here costs speed, not
+correctness, so no parity test would see it."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "gnnadvisor_osdi21_amd", "csrc")
+
+# (num_parts, partSize, num_cus) -> (G, blocks)
+CHUNK_GRID = [
+    ((1, 32, 256), (1, 1)),
+    ((5000, 32, 256), (1, 1250)),
+    ((10000, 32, 256), (2, 1250)),
+    ((262145, 32, 256), (64, 1025)),
+    ((262080, 32, 256), (32, 2048)),
+    ((81923, 100, 256), (20, 1025)),
+    ((81900, 100, 256), (10, 2048)),
+    ((257, 4096, 256), (1, 65)),
+    ((1000, 32, 1), (64, 4)),
+]
+LANES_4 = dict(zip((1, 4, 5, 8, 9, 64, 65, 128, 129, 256, 257, 1000), (0, 0, 1, 1, 2, 4, 5, 5, 6, 6, 6, 6)))
+LANES_8 = dict(zip((8, 9, 512, 513), (0, 1, 6, 6)))
+
+PROGRAM = r"""
+#include "gnna_launch.h"
+
+#include <cstdio>
+#include <cstdlib>
+
+int main(int argc, char **argv)
+{
+    for (int i = 1; i + 3 < argc; i += 4) {
+        const long long a = std::atoll(argv[i + 1]);
+        const int b = std::atoi(argv[i + 2]), c = std::atoi(argv[i + 3]);
+        if (argv[i][0] == 'g') {
+            const gnna::ChunkGrid g = gnna::chunk_grid(a, b, c);
+            std::printf("%d %lld\n", g.G, (long long)g.blocks);
+        } else {
+            std::printf("%d\n", gnna::log2_lanes((int)a, b));
+        }
+    }
+    return 0;
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def answers(tmp_path_factory):
+    """One compile, one run: every question on the command line, one answer per line."""
+    d = tmp_path_factory.mktemp("launch_geometry")
+    src, exe = str(d / "geometry.cpp"), str(d / "geometry")
+    with open(src, "w") as f:
+        f.write(PROGRAM)
+    subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-std=c++17", "-Wall", "-Wextra", "-I" + CSRC, src,
+                           "-o", exe])
+    asked = [("g",) + k for k, _ in CHUNK_GRID] + [("l", d_, 4, 0) for d_ in LANES_4] + [("l", d_, 8, 0) for d_ in LANES_8]
+    out = subprocess.check_output([exe] + [str(x) for q in asked for x in q], text=True).splitlines()
+    assert len(out) == len(asked)
+    return {q: tuple(int(x) for x in line.split()) for q, line in zip(asked, out)}
+
+
+@pytest.mark.parametrize("args, want", CHUNK_GRID, ids=["P%d_ps%d_cus%d" % k for k, _ in CHUNK_GRID])
+def test_chunk_grid(answers, args, want):
+    assert answers[("g",) + args] == want
+
+
+def test_log2_lanes(answers):
+    assert {d: answers[("l", d, 4, 0)][0] for d in LANES_4} == LANES_4
+    assert {d: answers[("l", d, 8, 0)][0] for d in LANES_8} == LANES_8
