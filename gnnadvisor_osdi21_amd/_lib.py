@@ -34,26 +34,76 @@ class Tuning(ctypes.Structure):
 
 _lib = None
 
-_AGG_COMMON = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]  # input, row_pointers, column_index
-_TAIL = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,        # part_pointers, part2Node, out
-         ctypes.c_int64, ctypes.c_int, ctypes.c_int64,             # num_nodes, dim, num_parts
-         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]  # partSize, dimWorker, warpPerBlock, stream
-
-EXPORTS = ("gnna_version", "gnna_build_id", "gnna_last_error", "gnna_count_parts", "gnna_build_part_i32",
-           "gnna_sag_f32", "gnna_agg_gcn_f32", "gnna_agg_gin_f32", "gnna_set_tuning", "gnna_get_tuning",
-           "gnna_profile_begin", "gnna_profile_end", "gnna_agg_rect_f32",
-           "gnna_csr_from_edges_i32", "gnna_degrees_f32", "gnna_edge_span", "gnna_reorder_rcm_i32",
-           "gnna_last_num_phases", "gnna_sddmm_f32", "gnna_sddmm_ld_f32", "gnna_agg_rect_windows_f32", "gnna_set_graph_hints", "gnna_xtg_f32", "gnna_set_graph_phases",
-           "gnna_last_num_launches", "gnna_reorder_community_i32", "gnna_prepare_graph", "gnna_release_graph",
-           "gnna_runtime_counters", "gnna_row_counts_i64", "gnna_row_splits_i64", "gnna_csr_from_edges_range_i32",
-           "gnna_forget_graph", "gnna_agg_ld_f32", "gnna_preferred_ld", "gnna_device_cus", "gnna_host_threads",
-           "gnna_reorder_community_csr_i32", "gnna_relabel_edges_i32", "gnna_relabel_csr_i32", "gnna_runtime_counters_ex", "gnna_forget_plans",
-           "gnna_debug_untrusted_copies", "gnna_agg_edge_ld_f32", "gnna_edge_softmax_f32", "gnna_edge_softmax_backward_f32",
-           "gnna_reverse_edges_i32", "gnna_agg_ld_x16", "gnna_prepare_x16", "gnna_agg_reduce_ld_f32", "gnna_scatter_arg_ld_f32",
-           "gnna_gat_forward_f32", "gnna_gat_backward_f32", "gnna_gat_backward_dir_f32", "gnna_transpose_csr_i32",
-           "gnna_count_parts_device_i32", "gnna_build_part_device_i32", "gnna_sample_neighbors_i32",
-           "gnna_agg_typed_expand_ld_f32", "gnna_agg_typed_contract_ld_f32", "gnna_typed_coef_grad_ld_f32",
-           "gnna_gat_forward_rect_f32", "gnna_gat_backward_rect_f32")
+# ---- the C ABI as ctypes sees it: entry -> (restype, argtypes; None: never assigned).  load() applies it, EXPORTS is its keys ----
+p, i, i64, u, u64, f, s = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint, ctypes.c_uint64, ctypes.c_float, ctypes.c_char_p
+pd, pi, pi64 = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64)
+_REF_TAIL = [p, p, p, i64, i, i64, i, i, i, p]       # part_pointers, part2Node, out, num_nodes, dim, num_parts, partSize, dimWorker, warpPerBlock, stream
+_RECT = [i, p, i64, p, p, p, f, p, p, p, i64, i, i64, i, i]    # gnna_agg_rect_f32 up to `accumulate`
+_SIZES = [i64, i64, i, i64, i, u, p]                 # the tail of the *_ld entries: ld of the last output, num_out_rows, dim, num_parts, partSize, flags, stream
+_GAT_FWD = [p, i64, p, p, p, p, p, p, f, p, i64, p]  # H, ld_h, el, er, the graph, slope, out, ld_out, lse
+_GAT_BWD = [p, i64, p, p, p, p, i64, p, i64]         # H, ld_h, el, er, lse, Y, ld_y, dY, ld_dy
+_GAT_BOTH = ([p] * 4 + [i64]) * 2 + [f, p, i64, p, p]   # the graph and its transpose with their num_parts, slope, dH, ld_dh, d_el, d_er
+_TYPED = [p, i64, i64, p, p, p, p, i, i, p, p, p] + _SIZES
+SIGNATURES = {
+    "gnna_version": (i, None), "gnna_build_id": (s, None), "gnna_last_error": (s, None), "gnna_device_cus": (i, None),
+    "gnna_host_threads": (i, None), "gnna_last_num_phases": (i, None), "gnna_last_num_launches": (i, None),
+    "gnna_count_parts": (i64, [i, p, i64]),
+    "gnna_build_part_i32": (i, [i, p, i64, p, p, i64]),
+    "gnna_sag_f32": (i, [p, p, p, p] + _REF_TAIL),
+    "gnna_agg_gcn_f32": (i, [p, p, p, p] + _REF_TAIL),
+    "gnna_agg_gin_f32": (i, [p, p, p, f] + _REF_TAIL),
+    "gnna_set_tuning": (i, [ctypes.POINTER(Tuning)]),
+    "gnna_get_tuning": (None, [ctypes.POINTER(Tuning)]),
+    "gnna_agg_rect_f32": (i, _RECT + [p]),
+    "gnna_agg_rect_windows_f32": (i, _RECT + [i, i, i, p]),
+    "gnna_agg_ld_f32": (i, [i, p, i64, i64, p, p, p, f, p, p, p] + _SIZES),
+    "gnna_agg_ld_x16": (i, [i, i, p, i64, i64, p, p, p, f, p, p, p, i] + _SIZES),
+    "gnna_prepare_x16": (i, [i64, i64, p, i, p]),
+    "gnna_preferred_ld": (i64, [i, i64, i64]),
+    "gnna_set_graph_hints": (i, [p, i, i]),
+    "gnna_set_graph_phases": (i, [p, i, i]),
+    "gnna_xtg_f32": (i, [p, p, p, i64, i, i, p]),
+    "gnna_csr_from_edges_i32": (i64, [p, p, i64, i64, p, p]),
+    "gnna_row_counts_i64": (i, [p, i64, i64, p]),
+    "gnna_row_splits_i64": (i, [p, i64, i, p, p]),
+    "gnna_csr_from_edges_range_i32": (i64, [p, p, i64, i64, i64, i64, p, p, i64]),
+    "gnna_degrees_f32": (i, [p, i64, p]),
+    "gnna_edge_span": (i, [p, p, i64, pd]),
+    "gnna_reorder_rcm_i32": (i, [p, p, i64, i64, p]),
+    "gnna_reorder_community_i32": (i, [p, p, i64, i64, p]),
+    "gnna_reorder_community_csr_i32": (i, [p, p, i64, p]),
+    "gnna_relabel_edges_i32": (i, [p, p, i64, p, i64, pd]),
+    "gnna_relabel_csr_i32": (i, [p, p, i64, p, p, p]),
+    "gnna_sddmm_ld_f32": (i, [p, i64, p, i64, p, p, p, p, i64, i64, i, i64, i, p]),
+    "gnna_sddmm_f32": (i, [p, p, p, p, p, p, i64, i64, i, i64, i, p]),
+    "gnna_prepare_graph": (i, [p, p, p, i64, i64, i64, i, pi, i, pi, p]),
+    "gnna_release_graph": (i, [p]), "gnna_forget_graph": (i, [p]), "gnna_forget_plans": (i, [p]),
+    "gnna_runtime_counters": (None, [pi64]),
+    "gnna_runtime_counters_ex": (i, [pi64, i]),
+    "gnna_debug_untrusted_copies": (i, [p]),
+    "gnna_profile_begin": (i, [i]),
+    "gnna_profile_end": (i, [pd, pd, pi]),
+    "gnna_agg_edge_ld_f32": (i, [p, i64, i64, p, p, p, p, p] + _SIZES),
+    "gnna_edge_softmax_f32": (i, [p, p, i64, i64, i, p, p]),
+    "gnna_edge_softmax_backward_f32": (i, [p, p, p, i64, i64, i, p, p]),
+    "gnna_reverse_edges_i32": (i, [p, p, i64, p]),
+    "gnna_agg_reduce_ld_f32": (i, [i, p, i64, i64, p, p, p, p, i64, p] + _SIZES),
+    "gnna_scatter_arg_ld_f32": (i, [p, i64, p, i64, p, i64, p, i64, i64, i, u, p]),
+    "gnna_gat_forward_f32": (i, _GAT_FWD + [i64, i, i, i64, i, u, p]),
+    "gnna_gat_forward_rect_f32": (i, _GAT_FWD + [i64, i64, i, i, i64, i, u, p]),       # (num_out_rows, num_in_rows) for num_nodes
+    "gnna_gat_backward_f32": (i, _GAT_BWD + [p, p, p, p, f, p, i64, p, p, i64, i, i, i64, i, u, p]),
+    "gnna_gat_backward_dir_f32": (i, _GAT_BWD + _GAT_BOTH + [i64, i, i, i, u, p]),
+    "gnna_gat_backward_rect_f32": (i, _GAT_BWD + _GAT_BOTH + [i64, i64, i, i, i, u, p]),
+    "gnna_transpose_csr_i32": (i, [p, p, i64, i64, p, p, p, p]),
+    "gnna_count_parts_device_i32": (i64, [i, p, i64, p]),
+    "gnna_build_part_device_i32": (i, [i, p, i64, p, p, i64, p]),
+    "gnna_sample_neighbors_i32": (i, [p, p, i64, p, i64, i, u64, i, p, p, p, p, p, p, i64, i64, pi64, p]),
+    "gnna_agg_typed_expand_ld_f32": (i, _TYPED),
+    "gnna_agg_typed_contract_ld_f32": (i, _TYPED),
+    "gnna_typed_coef_grad_ld_f32": (i, [p, i64, i64, p, i64, i64, p, p, p, p, p, p, i, i, i, i64, i, u, p]),
+}
+del p, i, i64, u, u64, f, s, pd, pi, pi64
+EXPORTS = tuple(SIGNATURES)
 
 
 def load() -> ctypes.CDLL:
@@ -66,176 +116,11 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -m gnnadvisor_osdi21_amd.build`). There is no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    L.gnna_version.restype = ctypes.c_int
-    L.gnna_build_id.restype = ctypes.c_char_p
-    L.gnna_last_error.restype = ctypes.c_char_p
-    L.gnna_device_cus.restype = ctypes.c_int
-    L.gnna_host_threads.restype = ctypes.c_int
-    L.gnna_count_parts.restype = ctypes.c_int64
-    L.gnna_count_parts.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64]
-    L.gnna_build_part_i32.restype = ctypes.c_int
-    L.gnna_build_part_i32.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
-                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
-    L.gnna_sag_f32.restype = ctypes.c_int
-    L.gnna_sag_f32.argtypes = _AGG_COMMON + [ctypes.c_void_p] + _TAIL
-    L.gnna_agg_gcn_f32.restype = ctypes.c_int
-    L.gnna_agg_gcn_f32.argtypes = _AGG_COMMON + [ctypes.c_void_p] + _TAIL
-    L.gnna_agg_gin_f32.restype = ctypes.c_int
-    L.gnna_agg_gin_f32.argtypes = _AGG_COMMON + [ctypes.c_float] + _TAIL
-    L.gnna_set_tuning.restype = ctypes.c_int
-    L.gnna_set_tuning.argtypes = [ctypes.POINTER(Tuning)]
-    L.gnna_get_tuning.restype = None
-    L.gnna_get_tuning.argtypes = [ctypes.POINTER(Tuning)]
-    L.gnna_agg_rect_f32.restype = ctypes.c_int
-    L.gnna_agg_rect_f32.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
-                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
-                                    ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-    L.gnna_agg_ld_x16.restype = ctypes.c_int
-    L.gnna_agg_ld_x16.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
-                                  ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
-                                  ctypes.c_int, ctypes.c_uint, ctypes.c_void_p]
-    L.gnna_prepare_x16.restype = ctypes.c_int
-    L.gnna_prepare_x16.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-    L.gnna_agg_ld_f32.restype = ctypes.c_int
-    L.gnna_agg_ld_f32.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
-                                  ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
-                                  ctypes.c_int, ctypes.c_uint, ctypes.c_void_p]
-    L.gnna_preferred_ld.restype = ctypes.c_int64
-    L.gnna_preferred_ld.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_int64]
-    L.gnna_agg_rect_windows_f32.restype = ctypes.c_int
-    L.gnna_agg_rect_windows_f32.argtypes = (L.gnna_agg_rect_f32.argtypes[:-1]
-                                            + [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p])
-    L.gnna_set_graph_hints.restype = ctypes.c_int
-    L.gnna_set_graph_hints.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
-    L.gnna_set_graph_phases.restype = ctypes.c_int
-    L.gnna_set_graph_phases.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
-    L.gnna_xtg_f32.restype = ctypes.c_int
-    L.gnna_xtg_f32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
-                               ctypes.c_int, ctypes.c_void_p]
-    L.gnna_csr_from_edges_i32.restype = ctypes.c_int64
-    L.gnna_csr_from_edges_i32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                          ctypes.c_void_p, ctypes.c_void_p]
-    L.gnna_row_counts_i64.restype = ctypes.c_int
-    L.gnna_row_counts_i64.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
-    L.gnna_row_splits_i64.restype = ctypes.c_int
-    L.gnna_row_splits_i64.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-    L.gnna_csr_from_edges_range_i32.restype = ctypes.c_int64
-    L.gnna_csr_from_edges_range_i32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                                ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_int64]
-    L.gnna_degrees_f32.restype = ctypes.c_int
-    L.gnna_degrees_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
-    L.gnna_edge_span.restype = ctypes.c_int
-    L.gnna_edge_span.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_double)]
-    L.gnna_reorder_rcm_i32.restype = ctypes.c_int
-    L.gnna_reorder_rcm_i32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                       ctypes.c_void_p]
-    L.gnna_reorder_community_i32.restype = ctypes.c_int
-    L.gnna_reorder_community_i32.argtypes = L.gnna_reorder_rcm_i32.argtypes
-    L.gnna_reorder_community_csr_i32.restype = ctypes.c_int
-    L.gnna_reorder_community_csr_i32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
-    L.gnna_relabel_edges_i32.restype = ctypes.c_int
-    L.gnna_relabel_edges_i32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
-                                         ctypes.POINTER(ctypes.c_double)]
-    L.gnna_relabel_csr_i32.restype = ctypes.c_int
-    L.gnna_relabel_csr_i32.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int64] + [ctypes.c_void_p] * 3
-    L.gnna_last_num_phases.restype = ctypes.c_int
-    L.gnna_last_num_launches.restype = ctypes.c_int
-    L.gnna_sddmm_ld_f32.restype = ctypes.c_int
-    L.gnna_sddmm_ld_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4 + [
-        ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]
-    L.gnna_sddmm_f32.restype = ctypes.c_int
-    L.gnna_sddmm_f32.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
-                                                        ctypes.c_int, ctypes.c_void_p]
-    L.gnna_prepare_graph.restype = ctypes.c_int
-    L.gnna_prepare_graph.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                     ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
-                                     ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]
-    L.gnna_release_graph.restype = ctypes.c_int
-    L.gnna_release_graph.argtypes = [ctypes.c_void_p]
-    L.gnna_forget_graph.restype = ctypes.c_int
-    L.gnna_forget_graph.argtypes = [ctypes.c_void_p]
-    L.gnna_forget_plans.restype = ctypes.c_int
-    L.gnna_forget_plans.argtypes = [ctypes.c_void_p]
-    L.gnna_runtime_counters.restype = None
-    L.gnna_runtime_counters.argtypes = [ctypes.POINTER(ctypes.c_int64)]
-    L.gnna_runtime_counters_ex.restype = ctypes.c_int
-    L.gnna_runtime_counters_ex.argtypes = [ctypes.POINTER(ctypes.c_int64), ctypes.c_int]
-    L.gnna_debug_untrusted_copies.restype = ctypes.c_int
-    L.gnna_debug_untrusted_copies.argtypes = [ctypes.c_void_p]
-    L.gnna_profile_begin.restype = ctypes.c_int
-    L.gnna_profile_begin.argtypes = [ctypes.c_int]
-    L.gnna_profile_end.restype = ctypes.c_int
-    L.gnna_profile_end.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
-                                   ctypes.POINTER(ctypes.c_int)]
-    L.gnna_agg_edge_ld_f32.restype = ctypes.c_int
-    L.gnna_agg_edge_ld_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 5 + [
-        ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p]
-    L.gnna_edge_softmax_f32.restype = ctypes.c_int
-    L.gnna_edge_softmax_f32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
-                                        ctypes.c_void_p, ctypes.c_void_p]
-    L.gnna_edge_softmax_backward_f32.restype = ctypes.c_int
-    L.gnna_edge_softmax_backward_f32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                                 ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-    L.gnna_reverse_edges_i32.restype = ctypes.c_int
-    L.gnna_reverse_edges_i32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
-    L.gnna_agg_reduce_ld_f32.restype = ctypes.c_int
-    L.gnna_agg_reduce_ld_f32.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 4 + [
-        ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_uint,
-        ctypes.c_void_p]
-    L.gnna_scatter_arg_ld_f32.restype = ctypes.c_int
-    L.gnna_scatter_arg_ld_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                          ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
-                                          ctypes.c_uint, ctypes.c_void_p]
-    L.gnna_gat_forward_f32.restype = ctypes.c_int
-    L.gnna_gat_forward_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 6 + [
-        ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p]
-    L.gnna_gat_backward_f32.restype = ctypes.c_int
-    L.gnna_gat_backward_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 4 + [
-        ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
-        ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p]
-    L.gnna_gat_backward_dir_f32.restype = ctypes.c_int
-    L.gnna_gat_backward_dir_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64] + (
-        [ctypes.c_void_p] * 4 + [ctypes.c_int64]) * 2 + [
-        ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
-        ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p]
-    # the rectangular forms: (num_out_rows, num_in_rows) where the square ones take num_nodes
-    L.gnna_gat_forward_rect_f32.restype = ctypes.c_int
-    L.gnna_gat_forward_rect_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 6 + [
-        ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p]
-    L.gnna_gat_backward_rect_f32.restype = ctypes.c_int
-    L.gnna_gat_backward_rect_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                             ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64] + (
-        [ctypes.c_void_p] * 4 + [ctypes.c_int64]) * 2 + [
-        ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p]
-    L.gnna_transpose_csr_i32.restype = ctypes.c_int
-    L.gnna_transpose_csr_i32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 4
-    L.gnna_count_parts_device_i32.restype = ctypes.c_int64
-    L.gnna_count_parts_device_i32.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
-    L.gnna_build_part_device_i32.restype = ctypes.c_int
-    L.gnna_build_part_device_i32.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                             ctypes.c_int64, ctypes.c_void_p]
-    L.gnna_sample_neighbors_i32.restype = ctypes.c_int
-    L.gnna_sample_neighbors_i32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
-                                            ctypes.c_int, ctypes.c_uint64, ctypes.c_int] + [ctypes.c_void_p] * 6 + [
-        ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]
-    for fn in (L.gnna_agg_typed_expand_ld_f32, L.gnna_agg_typed_contract_ld_f32):
-        fn.restype = ctypes.c_int
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int] + [
-            ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_uint,
-                                    ctypes.c_void_p]
-    L.gnna_typed_coef_grad_ld_f32.restype = ctypes.c_int
-    L.gnna_typed_coef_grad_ld_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
-                                              ctypes.c_int64] + [ctypes.c_void_p] * 6 + [
-        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype = restype
+        if argtypes is not None:
+            fn.argtypes = argtypes
     _lib = L
     return L
 
@@ -251,6 +136,18 @@ def _ptr(t: torch.Tensor | None) -> int | None:
 
 def _stream(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def _call(device, fn_name: str, *args) -> None:
+    """One call of a stream-taking entry: on `device`, with that device's current stream appended to `args`; raises GnnaError
+    on an error code."""
+    with torch.cuda.device(device):
+        _check(getattr(load(), fn_name)(*args, _stream(device)))
+
+
+def _need_device(t: torch.Tensor, what: str) -> None:
+    if not t.is_cuda:
+        raise GnnaError(f"{what} needs device tensors: there is no CPU path in libgnna")
 
 
 def set_tuning(groups_per_chunk=-1, loads_in_flight=-1, blocks_per_cu=-1, xcd_remap=-1,
@@ -397,20 +294,21 @@ def edge_span(src, dst) -> float:
     return v.value
 
 
-def reorder_rcm(src, dst, num_nodes: int) -> torch.Tensor:
-    """new_id[old_id] from the native reverse Cuthill-McKee renumbering."""
+def _reorder(entry: str, src, dst, num_nodes: int) -> torch.Tensor:
     s, d = _host_i32(src), _host_i32(dst)
     out = torch.empty(int(num_nodes), dtype=torch.int32)
-    _check(load().gnna_reorder_rcm_i32(s.data_ptr(), d.data_ptr(), s.numel(), int(num_nodes), out.data_ptr()))
+    _check(getattr(load(), entry)(s.data_ptr(), d.data_ptr(), s.numel(), int(num_nodes), out.data_ptr()))
     return out
+
+
+def reorder_rcm(src, dst, num_nodes: int) -> torch.Tensor:
+    """new_id[old_id] from the native reverse Cuthill-McKee renumbering."""
+    return _reorder("gnna_reorder_rcm_i32", src, dst, num_nodes)
 
 
 def reorder_community(src, dst, num_nodes: int) -> torch.Tensor:
     """new_id[old_id] from the native community renumbering (label propagation + chain + barycentre sweeps)."""
-    s, d = _host_i32(src), _host_i32(dst)
-    out = torch.empty(int(num_nodes), dtype=torch.int32)
-    _check(load().gnna_reorder_community_i32(s.data_ptr(), d.data_ptr(), s.numel(), int(num_nodes), out.data_ptr()))
-    return out
+    return _reorder("gnna_reorder_community_i32", src, dst, num_nodes)
 
 
 def reorder_community_csr(row_pointers, column_index, num_nodes: int) -> torch.Tensor:
@@ -479,47 +377,45 @@ def build_part(partSize: int, indptr: torch.Tensor):
     return pp, p2n
 
 
-def _fresh_output(shape, device) -> torch.Tensor:
+def _fresh_output(shape, device, dtype=torch.float32) -> torch.Tensor:
     """A new output tensor: the library writes every element.  GNNA_DEBUG_POISON=1 (the test suite sets it) starts it
-    as NaN, so that an element the library fails to write cannot hide behind whatever the allocator hands back."""
+    as NaN (an int32 `arg` as INT_MIN), so that an element the library fails to write cannot hide behind whatever the
+    allocator hands back or pass for one it wrote."""
     if os.environ.get("GNNA_DEBUG_POISON", "0") not in ("", "0"):
-        return torch.full(tuple(shape), float("nan"), dtype=torch.float32, device=device)
-    return torch.empty(tuple(shape), dtype=torch.float32, device=device)
+        return torch.full(tuple(shape), float("nan") if dtype.is_floating_point else -(2 ** 31), dtype=dtype, device=device)
+    return torch.empty(tuple(shape), dtype=dtype, device=device)
 
 
-def _agg(fn, X, row_pointers, column_index, extra, part_pointers, part2Node, partSize, dimWorker,
+def _agg(fn_name, X, row_pointers, column_index, extra, part_pointers, part2Node, partSize, dimWorker,
          warpPerBlock, out):
-    if not X.is_cuda:
-        raise GnnaError("aggregation needs device tensors: there is no CPU path in libgnna")
+    _need_device(X, "aggregation")
     assert X.dtype == torch.float32 and X.is_contiguous() and X.dim() == 2
     for t in (column_index, part_pointers, part2Node):
         assert t.dtype == torch.int32 and t.is_contiguous() and t.device == X.device
     if out is None:
         out = _fresh_output(X.shape, X.device)
-    with torch.cuda.device(X.device):
-        _check(fn(X.data_ptr(), _ptr(row_pointers), column_index.data_ptr(), extra,
-                  part_pointers.data_ptr(), part2Node.data_ptr(), out.data_ptr(),
-                  X.shape[0], X.shape[1], part2Node.numel(),
-                  int(partSize), int(dimWorker), int(warpPerBlock), _stream(X.device)))
+    _call(X.device, fn_name, X.data_ptr(), _ptr(row_pointers), column_index.data_ptr(), extra,
+          part_pointers.data_ptr(), part2Node.data_ptr(), out.data_ptr(), X.shape[0], X.shape[1], part2Node.numel(),
+          int(partSize), int(dimWorker), int(warpPerBlock))
     return out
 
 
 def sag(X, row_pointers, column_index, degrees, part_pointers, part2Node, partSize=32, dimWorker=32,
         warpPerBlock=4, out=None):
-    return _agg(load().gnna_sag_f32, X, row_pointers, column_index, _ptr(degrees), part_pointers,
+    return _agg("gnna_sag_f32", X, row_pointers, column_index, _ptr(degrees), part_pointers,
                 part2Node, partSize, dimWorker, warpPerBlock, out)
 
 
 def agg_gcn(X, row_pointers, column_index, degrees, part_pointers, part2Node, partSize=32,
             dimWorker=32, warpPerBlock=4, out=None):
     assert degrees.dtype == torch.float32 and degrees.device == X.device
-    return _agg(load().gnna_agg_gcn_f32, X, row_pointers, column_index, degrees.data_ptr(),
+    return _agg("gnna_agg_gcn_f32", X, row_pointers, column_index, degrees.data_ptr(),
                 part_pointers, part2Node, partSize, dimWorker, warpPerBlock, out)
 
 
 def agg_gin(X, row_pointers, column_index, epsilon, part_pointers, part2Node, partSize=32,
             dimWorker=32, warpPerBlock=4, out=None):
-    return _agg(load().gnna_agg_gin_f32, X, row_pointers, column_index, ctypes.c_float(epsilon),
+    return _agg("gnna_agg_gin_f32", X, row_pointers, column_index, ctypes.c_float(epsilon),
                 part_pointers, part2Node, partSize, dimWorker, warpPerBlock, out)
 
 
@@ -534,42 +430,56 @@ def agg_rect(mode, X, column_index, part_pointers, part2Node, num_out_rows, part
     (gnna_agg_rect_windows_f32: stateless; the column ids of every neighbor-group must be in increasing order -- the
     loader's CSR has them sorted -- else the call returns GNNA_ERR_UNSUPPORTED; the first call on a partition counts
     the ids per window and synchronises the stream once)."""
-    if not X.is_cuda:
-        raise GnnaError("aggregation needs device tensors: there is no CPU path in libgnna")
+    _need_device(X, "aggregation")
     assert X.dtype == torch.float32 and X.is_contiguous() and X.dim() == 2
     if out is None:
         assert not accumulate, "accumulate needs an existing `out`"
         out = _fresh_output((num_out_rows, X.shape[1]), X.device)
+    args = (int(mode), X.data_ptr(), X.shape[0], column_index.data_ptr(), _ptr(degrees_out), _ptr(degrees_in), float(epsilon),
+            part_pointers.data_ptr(), part2Node.data_ptr(), out.data_ptr(), int(num_out_rows), X.shape[1], part2Node.numel(),
+            int(partSize), 1 if accumulate else 0)
     if windows is not None:
         K, wb, we = (int(v) for v in windows)
         assert wb == 0 or out is not None
-        with torch.cuda.device(X.device):
-            _check(load().gnna_agg_rect_windows_f32(
-                int(mode), X.data_ptr(), X.shape[0], column_index.data_ptr(), _ptr(degrees_out), _ptr(degrees_in),
-                float(epsilon), part_pointers.data_ptr(), part2Node.data_ptr(), out.data_ptr(), int(num_out_rows),
-                X.shape[1], part2Node.numel(), int(partSize), 1 if accumulate else 0, K, wb, we, _stream(X.device)))
-        return out
-    with torch.cuda.device(X.device):
-        _check(load().gnna_agg_rect_f32(int(mode), X.data_ptr(), X.shape[0], column_index.data_ptr(),
-                                        _ptr(degrees_out), _ptr(degrees_in), float(epsilon),
-                                        part_pointers.data_ptr(), part2Node.data_ptr(), out.data_ptr(),
-                                        int(num_out_rows), X.shape[1], part2Node.numel(), int(partSize),
-                                        1 if accumulate else 0, _stream(X.device)))
+        _call(X.device, "gnna_agg_rect_windows_f32", *args, K, wb, we)
+    else:
+        _call(X.device, "gnna_agg_rect_f32", *args)
     return out
 
 
 ACCUMULATE, EPILOGUE_RELU = 1, 2
 
 
-def _rows_view(t: torch.Tensor, what: str):
-    """(data pointer, rows, dim, leading dimension) of a 2-D float32 device tensor whose rows are contiguous."""
-    assert t.dtype == torch.float32 and t.dim() == 2, f"{what} must be a 2-D float32 tensor"
+def _flags(accumulate=False, relu=False) -> int:
+    return (ACCUMULATE if accumulate else 0) | (EPILOGUE_RELU if relu else 0)
+
+
+def _rows_view(t: torch.Tensor, what: str, dtype=torch.float32, unit="floats"):
+    """(data pointer, rows, dim, leading dimension) of a 2-D device tensor whose rows are contiguous: float32, or of any
+    element type with dtype=None (the leading dimension is counted in elements)."""
+    assert (dtype is None or t.dtype == dtype) and t.dim() == 2, \
+        f"{what} must be a 2-D {'' if dtype is None else str(dtype).replace('torch.', '') + ' '}tensor"
     if t.shape[1] > 1 and t.stride(1) != 1:
-        raise GnnaError(f"{what}: the floats of a row must be contiguous (stride(1) == 1)")
+        raise GnnaError(f"{what}: the {unit} of a row must be contiguous (stride(1) == 1)")
     ld = t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0))
     if ld < t.shape[1]:
         raise GnnaError(f"{what}: rows overlap (stride(0) = {t.stride(0)} < {t.shape[1]})")
     return t.data_ptr(), t.shape[0], t.shape[1], ld
+
+
+def _rows_view_any(t: torch.Tensor, what: str):
+    return _rows_view(t, what, dtype=None, unit="elements")
+
+
+def _out_rows(out, rows, width, device, accumulate=False):
+    """(out, its data pointer, its leading dimension) of a float32 result [rows, width] on `device`: the caller's `out`, which
+    may be a row-strided view, or a fresh tensor -- which there is nothing to accumulate into."""
+    if out is None:
+        assert not accumulate, "accumulate needs an existing `out`"
+        out = _fresh_output((rows, width), device)
+    ptr, n, w, ld = _rows_view(out, "out")
+    assert n == int(rows) and w == width and out.device == device
+    return out, ptr, ld
 
 
 def agg_ld(mode, X, column_index, part_pointers, part2Node, num_out_rows, partSize=32, degrees_out=None,
@@ -577,20 +487,12 @@ def agg_ld(mode, X, column_index, part_pointers, part2Node, num_out_rows, partSi
     """gnna_agg_ld_f32: the rectangular aggregation with leading dimensions and the ReLU epilogue.  `X` and `out` may be
     row-strided views (a column block ``M[:, a:b]``, a padded buffer ``P[:, :dim]``): stride(1) must be 1, stride(0) is
     handed over as the leading dimension.  relu: out = max(out, 0) after the aggregation."""
-    if not X.is_cuda:
-        raise GnnaError("aggregation needs device tensors: there is no CPU path in libgnna")
+    _need_device(X, "aggregation")
     xp, n_in, dim, ld_in = _rows_view(X, "X")
-    if out is None:
-        assert not accumulate, "accumulate needs an existing `out`"
-        out = _fresh_output((num_out_rows, dim), X.device)
-    yp, n_out, dim_o, ld_out = _rows_view(out, "out")
-    assert n_out == int(num_out_rows) and dim_o == dim and out.device == X.device
-    flags = (ACCUMULATE if accumulate else 0) | (EPILOGUE_RELU if relu else 0)
-    with torch.cuda.device(X.device):
-        _check(load().gnna_agg_ld_f32(int(mode), xp, ld_in, n_in, column_index.data_ptr(), _ptr(degrees_out),
-                                      _ptr(degrees_in), float(epsilon), part_pointers.data_ptr(), part2Node.data_ptr(),
-                                      yp, ld_out, int(num_out_rows), dim, part2Node.numel(), int(partSize), flags,
-                                      _stream(X.device)))
+    out, yp, ld_out = _out_rows(out, num_out_rows, dim, X.device, accumulate)
+    _call(X.device, "gnna_agg_ld_f32", int(mode), xp, ld_in, n_in, column_index.data_ptr(), _ptr(degrees_out), _ptr(degrees_in),
+          float(epsilon), part_pointers.data_ptr(), part2Node.data_ptr(), yp, ld_out, int(num_out_rows), dim, part2Node.numel(),
+          int(partSize), _flags(accumulate, relu))
     return out
 
 
@@ -598,34 +500,18 @@ F32, BF16, F16 = 0, 1, 2        # GNNA_F32 / GNNA_BF16 / GNNA_F16
 _X16_TYPES = {torch.bfloat16: BF16, torch.float16: F16}
 
 
-def _rows_view_any(t: torch.Tensor, what: str):
-    """_rows_view for any element type: the leading dimension is counted in elements."""
-    assert t.dim() == 2, f"{what} must be a 2-D tensor"
-    if t.shape[1] > 1 and t.stride(1) != 1:
-        raise GnnaError(f"{what}: the elements of a row must be contiguous (stride(1) == 1)")
-    ld = t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0))
-    if ld < t.shape[1]:
-        raise GnnaError(f"{what}: rows overlap (stride(0) = {t.stride(0)} < {t.shape[1]})")
-    return t.data_ptr(), t.shape[0], t.shape[1], ld
-
-
 def agg_ld_x16(mode, X, column_index, part_pointers, part2Node, num_out_rows, partSize=32, degrees_out=None,
                degrees_in=None, epsilon=1.0, out=None, out_dtype=None, accumulate=False, relu=False):
     """gnna_agg_ld_x16: agg_ld over bfloat16 / float16 `X`, accumulated in fp32.  The result is float32 or has X's dtype
     (`out_dtype`, default X's; or the dtype of a given `out`), rounded once.  Degrees stay float32.  accumulate needs a
     float32 `out`.  float16 results beyond +-65504 are +-inf (GCN coefficients get large: prefer bfloat16 / float32)."""
-    if not X.is_cuda:
-        raise GnnaError("aggregation needs device tensors: there is no CPU path in libgnna")
+    _need_device(X, "aggregation")
     if X.dtype not in _X16_TYPES:
         raise GnnaError(f"agg_ld_x16 takes bfloat16 or float16 features (got {X.dtype}); float32 goes through agg_ld")
     xp, n_in, dim, ld_in = _rows_view_any(X, "X")
     if out is None:
         assert not accumulate, "accumulate needs an existing `out`"
-        out_dtype = X.dtype if out_dtype is None else out_dtype
-        if os.environ.get("GNNA_DEBUG_POISON", "0") not in ("", "0"):
-            out = torch.full((int(num_out_rows), dim), float("nan"), dtype=out_dtype, device=X.device)
-        else:
-            out = torch.empty((int(num_out_rows), dim), dtype=out_dtype, device=X.device)
+        out = _fresh_output((int(num_out_rows), dim), X.device, X.dtype if out_dtype is None else out_dtype)
     elif out_dtype is not None and out.dtype != out_dtype:
         raise GnnaError(f"out is {out.dtype}, out_dtype says {out_dtype}")
     if out.dtype != torch.float32 and out.dtype != X.dtype:
@@ -635,12 +521,9 @@ def agg_ld_x16(mode, X, column_index, part_pointers, part2Node, num_out_rows, pa
     assert n_out == int(num_out_rows) and dim_o == dim and out.device == X.device
     for t in (degrees_out, degrees_in):
         assert t is None or t.dtype == torch.float32, "degrees stay float32"
-    flags = (ACCUMULATE if accumulate else 0) | (EPILOGUE_RELU if relu else 0)
-    with torch.cuda.device(X.device):
-        _check(load().gnna_agg_ld_x16(int(mode), _X16_TYPES[X.dtype], xp, ld_in, n_in, column_index.data_ptr(),
-                                      _ptr(degrees_out), _ptr(degrees_in), float(epsilon), part_pointers.data_ptr(),
-                                      part2Node.data_ptr(), yp, out_type, ld_out, int(num_out_rows), dim,
-                                      part2Node.numel(), int(partSize), flags, _stream(X.device)))
+    _call(X.device, "gnna_agg_ld_x16", int(mode), _X16_TYPES[X.dtype], xp, ld_in, n_in, column_index.data_ptr(), _ptr(degrees_out),
+          _ptr(degrees_in), float(epsilon), part_pointers.data_ptr(), part2Node.data_ptr(), yp, out_type, ld_out, int(num_out_rows),
+          dim, part2Node.numel(), int(partSize), _flags(accumulate, relu))
     return out
 
 
@@ -650,8 +533,7 @@ def prepare_x16(num_in_rows: int, num_out_rows: int, dims, device=None) -> None:
     dims = [int(d) for d in dims]
     arr = (ctypes.c_int * max(1, len(dims)))(*dims)
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    with torch.cuda.device(device):
-        _check(load().gnna_prepare_x16(int(num_in_rows), int(num_out_rows), arr, len(dims), _stream(device)))
+    _call(device, "gnna_prepare_x16", int(num_in_rows), int(num_out_rows), arr, len(dims))
 
 
 def preferred_ld(dim: int, num_in_rows: int, num_edges: int) -> int:
@@ -680,10 +562,8 @@ def prepare_graph(column_index, part_pointers, part2Node, num_in_rows: int, num_
     dims = [int(d) for d in dims]
     arr = (ctypes.c_int * max(1, len(dims)))(*dims)
     out = (ctypes.c_int * max(1, len(dims)))()
-    with torch.cuda.device(column_index.device):
-        _check(load().gnna_prepare_graph(column_index.data_ptr(), part_pointers.data_ptr(), part2Node.data_ptr(),
-                                         part2Node.numel(), int(num_in_rows), int(num_out_rows), int(partSize),
-                                         arr, len(dims), out, _stream(column_index.device)))
+    _call(column_index.device, "gnna_prepare_graph", column_index.data_ptr(), part_pointers.data_ptr(), part2Node.data_ptr(),
+          part2Node.numel(), int(num_in_rows), int(num_out_rows), int(partSize), arr, len(dims), out)
     _forget_when_freed(column_index)
     return {d: int(out[i]) for i, d in enumerate(dims)}
 
@@ -722,16 +602,13 @@ def set_graph_phases(column_index, dim: int, column_phases: int) -> None:
 
 def xtg(X, G, out=None):
     """dW[K, N] = X^T G for X [M, K], G [M, N] (fp32, MFMA): the weight gradient of the dense update."""
-    if not X.is_cuda:
-        raise GnnaError("xtg needs device tensors: there is no CPU path in libgnna")
+    _need_device(X, "xtg")
     assert X.dtype == torch.float32 and G.dtype == torch.float32 and X.dim() == 2 and G.dim() == 2
     assert X.shape[0] == G.shape[0]
     X, G = X.contiguous(), G.contiguous()
     if out is None:
         out = torch.empty(X.shape[1], G.shape[1], dtype=torch.float32, device=X.device)
-    with torch.cuda.device(X.device):
-        _check(load().gnna_xtg_f32(X.data_ptr(), G.data_ptr(), out.data_ptr(), X.shape[0], X.shape[1], G.shape[1],
-                              _stream(X.device)))
+    _call(X.device, "gnna_xtg_f32", X.data_ptr(), G.data_ptr(), out.data_ptr(), X.shape[0], X.shape[1], G.shape[1])
     return out
 
 
@@ -739,22 +616,18 @@ def sddmm(dst_feat, src_feat, column_index, part_pointers, part2Node, partSize=3
     """edge_out[e] = <dst_feat[row(e)], src_feat[column_index[e]]> over the neighbor-group partition
     (build-defined extension, see include/gnna.h).  Both feature matrices may be row-strided views (stride(1) == 1):
     their stride(0) is handed over as the leading dimension (gnna_sddmm_ld_f32)."""
-    if not dst_feat.is_cuda:
-        raise GnnaError("sddmm needs device tensors: there is no CPU path in libgnna")
+    _need_device(dst_feat, "sddmm")
     ap, n_out, dim, ld_dst = _rows_view(dst_feat, "dst_feat")
     bp, n_in, dim_b, ld_src = _rows_view(src_feat, "src_feat")
     assert dim == dim_b and dst_feat.device == src_feat.device
     if out is None:
         out = torch.zeros(column_index.numel(), dtype=torch.float32, device=dst_feat.device)
-    with torch.cuda.device(dst_feat.device):
-        if ld_dst == dim and ld_src == dim:
-            _check(load().gnna_sddmm_f32(ap, bp, column_index.data_ptr(), part_pointers.data_ptr(), part2Node.data_ptr(),
-                                         out.data_ptr(), n_out, n_in, dim, part2Node.numel(), int(partSize),
-                                         _stream(dst_feat.device)))
-        else:
-            _check(load().gnna_sddmm_ld_f32(ap, ld_dst, bp, ld_src, column_index.data_ptr(), part_pointers.data_ptr(),
-                                            part2Node.data_ptr(), out.data_ptr(), n_out, n_in, dim, part2Node.numel(),
-                                            int(partSize), _stream(dst_feat.device)))
+    tail = (column_index.data_ptr(), part_pointers.data_ptr(), part2Node.data_ptr(), out.data_ptr(), n_out, n_in, dim,
+            part2Node.numel(), int(partSize))
+    if ld_dst == dim and ld_src == dim:
+        _call(dst_feat.device, "gnna_sddmm_f32", ap, bp, *tail)
+    else:
+        _call(dst_feat.device, "gnna_sddmm_ld_f32", ap, ld_dst, bp, ld_src, *tail)
     return out
 
 
@@ -762,21 +635,13 @@ def agg_edge(X, column_index, edge_weight, part_pointers, part2Node, num_out_row
              accumulate=False, relu=False):
     """gnna_agg_edge_ld_f32: out[i] (+)= sum_e w[e] * X[column_index[e]] with caller-supplied edge weights `edge_weight`
     ([nnz] float32, indexed like column_index).  Strided X / out as in agg_ld."""
-    if not X.is_cuda:
-        raise GnnaError("aggregation needs device tensors: there is no CPU path in libgnna")
+    _need_device(X, "aggregation")
     assert edge_weight.dtype == torch.float32 and edge_weight.is_contiguous() and edge_weight.numel() == column_index.numel(), \
         "edge_weight must be a contiguous float32 tensor indexed like column_index"
     xp, n_in, dim, ld_in = _rows_view(X, "X")
-    if out is None:
-        assert not accumulate, "accumulate needs an existing `out`"
-        out = _fresh_output((num_out_rows, dim), X.device)
-    yp, n_out, dim_o, ld_out = _rows_view(out, "out")
-    assert n_out == int(num_out_rows) and dim_o == dim and out.device == X.device
-    flags = (ACCUMULATE if accumulate else 0) | (EPILOGUE_RELU if relu else 0)
-    with torch.cuda.device(X.device):
-        _check(load().gnna_agg_edge_ld_f32(xp, ld_in, n_in, column_index.data_ptr(), edge_weight.data_ptr(),
-                                           part_pointers.data_ptr(), part2Node.data_ptr(), yp, ld_out, int(num_out_rows), dim,
-                                           part2Node.numel(), int(partSize), flags, _stream(X.device)))
+    out, yp, ld_out = _out_rows(out, num_out_rows, dim, X.device, accumulate)
+    _call(X.device, "gnna_agg_edge_ld_f32", xp, ld_in, n_in, column_index.data_ptr(), edge_weight.data_ptr(), part_pointers.data_ptr(),
+          part2Node.data_ptr(), yp, ld_out, int(num_out_rows), dim, part2Node.numel(), int(partSize), _flags(accumulate, relu))
     return out
 
 
@@ -785,9 +650,8 @@ def edge_softmax(scores, row_pointers, out=None):
     assert scores.is_cuda and scores.dtype == torch.float32 and scores.is_contiguous() and scores.dim() in (1, 2)
     heads, nnz = (1, scores.numel()) if scores.dim() == 1 else scores.shape
     out = torch.empty_like(scores) if out is None else out
-    with torch.cuda.device(scores.device):
-        _check(load().gnna_edge_softmax_f32(scores.data_ptr(), row_pointers.data_ptr(), row_pointers.numel() - 1, nnz, heads,
-                                            out.data_ptr(), _stream(scores.device)))
+    _call(scores.device, "gnna_edge_softmax_f32", scores.data_ptr(), row_pointers.data_ptr(), row_pointers.numel() - 1, nnz, heads,
+          out.data_ptr())
     return out
 
 
@@ -797,10 +661,8 @@ def edge_softmax_backward(probs, grad_probs, row_pointers, out=None):
     assert grad_probs.shape == probs.shape and grad_probs.dtype == torch.float32 and grad_probs.is_contiguous()
     heads, nnz = (1, probs.numel()) if probs.dim() == 1 else probs.shape
     out = torch.empty_like(probs) if out is None else out
-    with torch.cuda.device(probs.device):
-        _check(load().gnna_edge_softmax_backward_f32(probs.data_ptr(), grad_probs.data_ptr(), row_pointers.data_ptr(),
-                                                     row_pointers.numel() - 1, nnz, heads, out.data_ptr(),
-                                                     _stream(probs.device)))
+    _call(probs.device, "gnna_edge_softmax_backward_f32", probs.data_ptr(), grad_probs.data_ptr(), row_pointers.data_ptr(),
+          row_pointers.numel() - 1, nnz, heads, out.data_ptr())
     return out
 
 
@@ -819,12 +681,8 @@ REDUCE_MAX, REDUCE_MIN = 0, 1   # GNNA_REDUCE_MAX / GNNA_REDUCE_MIN
 def _arg_view(t: torch.Tensor, rows: int, dim: int, what: str):
     """(data pointer, leading dimension) of a 2-D int32 device tensor [rows, dim] whose rows are contiguous."""
     assert t.dtype == torch.int32 and t.dim() == 2 and tuple(t.shape) == (rows, dim), f"{what} must be int32 [{rows}, {dim}]"
-    if dim > 1 and t.stride(1) != 1:
-        raise GnnaError(f"{what}: the elements of a row must be contiguous (stride(1) == 1)")
-    ld = t.stride(0) if rows > 1 else max(dim, t.stride(0))
-    if ld < dim:
-        raise GnnaError(f"{what}: rows overlap (stride(0) = {t.stride(0)} < {dim})")
-    return t.data_ptr(), ld
+    ptr, _, _, ld = _rows_view(t, what, dtype=torch.int32, unit="elements")
+    return ptr, ld
 
 
 def agg_reduce_ld(op, X, column_index, part_pointers, part2Node, partSize=32, *, num_out_rows=None, out=None, want_arg=True,
@@ -833,45 +691,31 @@ def agg_reduce_ld(op, X, column_index, part_pointers, part2Node, partSize=32, *,
     X[column_index[e], f] and arg[i, f] = the smallest such position e (int32; -1 and out = 0 for rows without edges).
     -> (out, arg); arg is None with want_arg=False.  `X`, `out` and a caller's `arg` may be row-strided views (stride(1) == 1):
     they are passed with their leading dimension, no copy.  relu: out = max(out, 0), arg unchanged."""
-    if not X.is_cuda:
-        raise GnnaError("aggregation needs device tensors: there is no CPU path in libgnna")
+    _need_device(X, "aggregation")
     xp, n_in, dim, ld_in = _rows_view(X, "X")
     n_out = n_in if num_out_rows is None else int(num_out_rows)
-    if out is None:
-        out = _fresh_output((n_out, dim), X.device)
-    yp, rows_o, dim_o, ld_out = _rows_view(out, "out")
-    assert rows_o == n_out and dim_o == dim and out.device == X.device
+    out, yp, ld_out = _out_rows(out, n_out, dim, X.device)
     ap, ld_arg = None, dim
     if arg is not None or want_arg:
         if arg is None:
-            # (poisoned like a fresh `out`: a position the library fails to write cannot pass for one it wrote)
-            poison = os.environ.get("GNNA_DEBUG_POISON", "0") not in ("", "0")
-            arg = (torch.full((n_out, dim), -(2 ** 31), dtype=torch.int32, device=X.device) if poison
-                   else torch.empty((n_out, dim), dtype=torch.int32, device=X.device))
+            arg = _fresh_output((n_out, dim), X.device, torch.int32)
         assert arg.device == X.device
         ap, ld_arg = _arg_view(arg, n_out, dim, "arg")
-    with torch.cuda.device(X.device):
-        _check(load().gnna_agg_reduce_ld_f32(int(op), xp, ld_in, n_in, column_index.data_ptr(), part_pointers.data_ptr(),
-                                             part2Node.data_ptr(), yp, ld_out, ap, ld_arg, n_out, dim, part2Node.numel(),
-                                             int(partSize), EPILOGUE_RELU if relu else 0, _stream(X.device)))
+    _call(X.device, "gnna_agg_reduce_ld_f32", int(op), xp, ld_in, n_in, column_index.data_ptr(), part_pointers.data_ptr(),
+          part2Node.data_ptr(), yp, ld_out, ap, ld_arg, n_out, dim, part2Node.numel(), int(partSize), _flags(relu=relu))
     return out, arg
 
 
 def scatter_arg_ld(grad_out, arg, column_index, num_in_rows, out=None, accumulate=False):
     """gnna_scatter_arg_ld_f32, the backward of agg_reduce_ld: out[column_index[arg[i, f]], f] += grad_out[i, f] for every
     arg[i, f] >= 0; `out` [num_in_rows, dim] is cleared first unless accumulate.  Strided views as in agg_reduce_ld."""
-    if not grad_out.is_cuda:
-        raise GnnaError("scatter_arg needs device tensors: there is no CPU path in libgnna")
+    _need_device(grad_out, "scatter_arg")
     gp, n_out, dim, ld_go = _rows_view(grad_out, "grad_out")
     ap, ld_arg = _arg_view(arg, n_out, dim, "arg")
-    if out is None:
-        assert not accumulate, "accumulate needs an existing `out`"
-        out = _fresh_output((int(num_in_rows), dim), grad_out.device)
-    op_, rows_i, dim_i, ld_gi = _rows_view(out, "out")
-    assert rows_i == int(num_in_rows) and dim_i == dim and out.device == grad_out.device and arg.device == grad_out.device
-    with torch.cuda.device(grad_out.device):
-        _check(load().gnna_scatter_arg_ld_f32(gp, ld_go, ap, ld_arg, column_index.data_ptr(), n_out, op_, ld_gi, int(num_in_rows),
-                                              dim, ACCUMULATE if accumulate else 0, _stream(grad_out.device)))
+    out, op_, ld_gi = _out_rows(out, int(num_in_rows), dim, grad_out.device, accumulate)
+    assert arg.device == grad_out.device
+    _call(grad_out.device, "gnna_scatter_arg_ld_f32", gp, ld_go, ap, ld_arg, column_index.data_ptr(), n_out, op_, ld_gi,
+          int(num_in_rows), dim, _flags(accumulate))
     return out
 
 
@@ -905,8 +749,7 @@ def gat_forward(H, el, er, row_pointers, column_index, part_pointers, part2Node,
     Rectangular structures (a sampled block): H [num_in_rows, heads * dim], er [num_in_rows, heads], el [num_out_rows, heads]
     with num_out_rows = row_pointers.numel() - 1 -> out [num_out_rows, heads * dim], lse [num_out_rows, heads]; when the two
     counts differ the call is gnna_gat_forward_rect_f32."""
-    if not H.is_cuda:
-        raise GnnaError("GAT attention needs device tensors: there is no CPU path in libgnna")
+    _need_device(H, "GAT attention")
     hp, n_out, n_in, width, heads, ld_h = _gat_sizes(H, el, er, row_pointers)
     if out is None:
         out = _fresh_output((n_out, width), H.device)
@@ -914,18 +757,10 @@ def gat_forward(H, el, er, row_pointers, column_index, part_pointers, part2Node,
         lse = _fresh_output((n_out, heads), H.device)
     op_, n_o, width_o, ld_out = _rows_view(out, "out")
     assert n_o == n_out and width_o == width and _node_heads(lse, n_out, "lse") == heads
-    flags = EPILOGUE_RELU if relu else 0
-    with torch.cuda.device(H.device):
-        if n_out == n_in:
-            _check(load().gnna_gat_forward_f32(hp, ld_h, el.data_ptr(), er.data_ptr(), row_pointers.data_ptr(),
-                                               column_index.data_ptr(), part_pointers.data_ptr(), part2Node.data_ptr(),
-                                               float(negative_slope), op_, ld_out, lse.data_ptr(), n_out, heads, width // heads,
-                                               part2Node.numel(), int(partSize), flags, _stream(H.device)))
-        else:
-            _check(load().gnna_gat_forward_rect_f32(hp, ld_h, el.data_ptr(), er.data_ptr(), row_pointers.data_ptr(),
-                                                    column_index.data_ptr(), part_pointers.data_ptr(), part2Node.data_ptr(),
-                                                    float(negative_slope), op_, ld_out, lse.data_ptr(), n_out, n_in, heads,
-                                                    width // heads, part2Node.numel(), int(partSize), flags, _stream(H.device)))
+    entry, sizes = ("gnna_gat_forward_f32", (n_out,)) if n_out == n_in else ("gnna_gat_forward_rect_f32", (n_out, n_in))
+    _call(H.device, entry, hp, ld_h, el.data_ptr(), er.data_ptr(), row_pointers.data_ptr(), column_index.data_ptr(),
+          part_pointers.data_ptr(), part2Node.data_ptr(), float(negative_slope), op_, ld_out, lse.data_ptr(), *sizes, heads,
+          width // heads, part2Node.numel(), int(partSize), _flags(relu=relu))
     return out, lse
 
 
@@ -937,8 +772,7 @@ def gat_backward(H, el, er, lse, Y, dY, row_pointers, column_index, part_pointer
     same partSize: gnna_gat_backward_dir_f32, exact on a directed graph.
     Rectangular structures (sizes as in gat_forward; Y, dY, lse have num_out_rows rows): gnna_gat_backward_rect_f32, which needs
     `transposed` (num_in_rows rows) -> dH [num_in_rows, heads * dim], d_el [num_out_rows, heads], d_er [num_in_rows, heads]."""
-    if not H.is_cuda:
-        raise GnnaError("GAT attention needs device tensors: there is no CPU path in libgnna")
+    _need_device(H, "GAT attention")
     hp, n_out, n_in, width, heads, ld_h = _gat_sizes(H, el, er, row_pointers)
     yp, n_y, width_y, ld_y = _rows_view(Y, "Y")
     gp, n_g, width_g, ld_g = _rows_view(dY, "dY")
@@ -961,22 +795,15 @@ def gat_backward(H, el, er, lse, Y, dY, row_pointers, column_index, part_pointer
         assert t_rp.numel() == n_in + 1 and t_pp.numel() == t_p2n.numel() + 1, \
             "transposed: [num_in_rows + 1] row pointers, [P + 1] / [P] partition"
     d_el, d_er = _fresh_output((n_out, heads), H.device), _fresh_output((n_in, heads), H.device)
+    head = (hp, ld_h, el.data_ptr(), er.data_ptr(), lse.data_ptr(), yp, ld_y, gp, ld_g, row_pointers.data_ptr(),
+            column_index.data_ptr(), part_pointers.data_ptr(), part2Node.data_ptr())
+    outs = (float(negative_slope), dp, ld_d, d_el.data_ptr(), d_er.data_ptr())
     if transposed is not None:
-        entry = load().gnna_gat_backward_rect_f32 if rect else load().gnna_gat_backward_dir_f32
-        sizes = (n_out, n_in) if rect else (n_out,)
-        with torch.cuda.device(H.device):
-            _check(entry(hp, ld_h, el.data_ptr(), er.data_ptr(), lse.data_ptr(), yp, ld_y, gp, ld_g,
-                         row_pointers.data_ptr(), column_index.data_ptr(), part_pointers.data_ptr(),
-                         part2Node.data_ptr(), part2Node.numel(), t_rp.data_ptr(), t_ci.data_ptr(),
-                         t_pp.data_ptr(), t_p2n.data_ptr(), t_p2n.numel(), float(negative_slope), dp, ld_d,
-                         d_el.data_ptr(), d_er.data_ptr(), *sizes, heads, width // heads, int(partSize), 0,
-                         _stream(H.device)))
-        return dH, d_el, d_er
-    with torch.cuda.device(H.device):
-        _check(load().gnna_gat_backward_f32(hp, ld_h, el.data_ptr(), er.data_ptr(), lse.data_ptr(), yp, ld_y, gp, ld_g,
-                                            row_pointers.data_ptr(), column_index.data_ptr(), part_pointers.data_ptr(),
-                                            part2Node.data_ptr(), float(negative_slope), dp, ld_d, d_el.data_ptr(), d_er.data_ptr(),
-                                            n_out, heads, width // heads, part2Node.numel(), int(partSize), 0, _stream(H.device)))
+        _call(H.device, "gnna_gat_backward_rect_f32" if rect else "gnna_gat_backward_dir_f32", *head, part2Node.numel(),
+              t_rp.data_ptr(), t_ci.data_ptr(), t_pp.data_ptr(), t_p2n.data_ptr(), t_p2n.numel(), *outs,
+              *((n_out, n_in) if rect else (n_out,)), heads, width // heads, int(partSize), 0)
+    else:
+        _call(H.device, "gnna_gat_backward_f32", *head, *outs, n_out, heads, width // heads, part2Node.numel(), int(partSize), 0)
     return dH, d_el, d_er
 
 
@@ -1006,8 +833,7 @@ def transpose_csr(row_pointers, column_index, num_in_rows=None, want_perm=True):
         # (the library trusts row_pointers[num_out_rows] for the edge count: it must not exceed what column_index holds)
         if n_out > 0 and int(rp[-1]) != nnz:
             raise GnnaError(f"row_pointers[-1] = {int(rp[-1])} but column_index holds {nnz} ids")
-        _check(load().gnna_transpose_csr_i32(rp.data_ptr(), _ptr(ci), n_out, n_in, t_rp.data_ptr(), _ptr(t_ci), _ptr(t_perm),
-                                             _stream(rp.device)))
+        _call(rp.device, "gnna_transpose_csr_i32", rp.data_ptr(), _ptr(ci), n_out, n_in, t_rp.data_ptr(), _ptr(t_ci), _ptr(t_perm))
     return t_rp, t_ci, t_perm
 
 
@@ -1029,9 +855,7 @@ def build_part_device(partSize: int, indptr):
     P = count_parts_device(partSize, ip)
     pp = torch.empty(P + 1, dtype=torch.int32, device=ip.device)
     p2n = torch.empty(P, dtype=torch.int32, device=ip.device)
-    with torch.cuda.device(ip.device):
-        _check(load().gnna_build_part_device_i32(int(partSize), ip.data_ptr(), ip.numel() - 1, pp.data_ptr(), _ptr(p2n), P,
-                                                 _stream(ip.device)))
+    _call(ip.device, "gnna_build_part_device_i32", int(partSize), ip.data_ptr(), ip.numel() - 1, pp.data_ptr(), _ptr(p2n), P)
     return pp, p2n
 
 
@@ -1117,20 +941,14 @@ def agg_typed_expand(X, coef, column_index, edge_type, edge_norm, part_pointers,
     """gnna_agg_typed_expand_ld_f32: out[i, b * dim + f] = sum_e n[e] * coef[t[e], b] * X[column_index[e], f] -> [num_out_rows,
     num_bases * dim].  edge_type int32 / edge_norm float32 (or None: 1) are indexed like column_index.  Strided X / out as in
     agg_ld."""
-    if not X.is_cuda:
-        raise GnnaError("aggregation needs device tensors: there is no CPU path in libgnna")
+    _need_device(X, "aggregation")
     xp, n_in, dim, ld_x = _rows_view(X, "X")
     R, B = _coef_table(coef, X.device)
     _typed_edges(column_index, edge_type, edge_norm, X.device)
-    if out is None:
-        out = _fresh_output((num_out_rows, B * dim), X.device)
-    yp, n_out, width, ld_out = _rows_view(out, "out")
-    assert n_out == int(num_out_rows) and width == B * dim and out.device == X.device
-    with torch.cuda.device(X.device):
-        _check(load().gnna_agg_typed_expand_ld_f32(xp, ld_x, n_in, column_index.data_ptr(), edge_type.data_ptr(), _ptr(edge_norm),
-                                                   coef.data_ptr(), R, B, part_pointers.data_ptr(), part2Node.data_ptr(), yp,
-                                                   ld_out, int(num_out_rows), dim, part2Node.numel(), int(partSize), 0,
-                                                   _stream(X.device)))
+    out, yp, ld_out = _out_rows(out, num_out_rows, B * dim, X.device)
+    _call(X.device, "gnna_agg_typed_expand_ld_f32", xp, ld_x, n_in, column_index.data_ptr(), edge_type.data_ptr(), _ptr(edge_norm),
+          coef.data_ptr(), R, B, part_pointers.data_ptr(), part2Node.data_ptr(), yp, ld_out, int(num_out_rows), dim,
+          part2Node.numel(), int(partSize), 0)
     return out
 
 
@@ -1138,22 +956,16 @@ def agg_typed_contract(G, coef, column_index, edge_type, edge_norm, part_pointer
     """gnna_agg_typed_contract_ld_f32: out[i, f] = sum_e n[e] * sum_b coef[t[e], b] * G[column_index[e], b * dim + f] for G
     [num_in_rows, num_bases * dim] -> [num_out_rows, dim], over the structure given (the backward of agg_typed_expand: the
     transposed structure, with edge_type / edge_norm permuted by its perm)."""
-    if not G.is_cuda:
-        raise GnnaError("aggregation needs device tensors: there is no CPU path in libgnna")
+    _need_device(G, "aggregation")
     gp, n_in, width, ld_g = _rows_view(G, "G")
     R, B = _coef_table(coef, G.device)
     assert width % B == 0, "G must be [num_in_rows, num_bases * dim]"
     dim = width // B
     _typed_edges(column_index, edge_type, edge_norm, G.device)
-    if out is None:
-        out = _fresh_output((num_out_rows, dim), G.device)
-    yp, n_out, dim_o, ld_out = _rows_view(out, "out")
-    assert n_out == int(num_out_rows) and dim_o == dim and out.device == G.device
-    with torch.cuda.device(G.device):
-        _check(load().gnna_agg_typed_contract_ld_f32(gp, ld_g, n_in, column_index.data_ptr(), edge_type.data_ptr(), _ptr(edge_norm),
-                                                     coef.data_ptr(), R, B, part_pointers.data_ptr(), part2Node.data_ptr(), yp,
-                                                     ld_out, int(num_out_rows), dim, part2Node.numel(), int(partSize), 0,
-                                                     _stream(G.device)))
+    out, yp, ld_out = _out_rows(out, num_out_rows, dim, G.device)
+    _call(G.device, "gnna_agg_typed_contract_ld_f32", gp, ld_g, n_in, column_index.data_ptr(), edge_type.data_ptr(), _ptr(edge_norm),
+          coef.data_ptr(), R, B, part_pointers.data_ptr(), part2Node.data_ptr(), yp, ld_out, int(num_out_rows), dim,
+          part2Node.numel(), int(partSize), 0)
     return out
 
 
@@ -1161,8 +973,7 @@ def typed_coef_grad(X, G, column_index, edge_type, edge_norm, part_pointers, par
                     accumulate=False):
     """gnna_typed_coef_grad_ld_f32: out[r, b] (+)= sum_{e: t[e] = r} n[e] * <X[column_index[e]], G[row(e), b * dim : (b + 1) * dim]>
     for X [num_in_rows, dim] and G [num_out_rows, num_bases * dim] over the forward structure -> [num_types, num_bases]."""
-    if not X.is_cuda:
-        raise GnnaError("aggregation needs device tensors: there is no CPU path in libgnna")
+    _need_device(X, "aggregation")
     xp, n_in, dim, ld_x = _rows_view(X, "X")
     gp, n_out, width, ld_g = _rows_view(G, "G")
     assert width % dim == 0 and G.device == X.device, "G must be [num_out_rows, num_bases * dim] on X's device"
@@ -1173,9 +984,7 @@ def typed_coef_grad(X, G, column_index, edge_type, edge_norm, part_pointers, par
         out = _fresh_output((int(num_types), B), X.device)
     assert tuple(out.shape) == (int(num_types), B)
     _coef_table(out, X.device)
-    with torch.cuda.device(X.device):
-        _check(load().gnna_typed_coef_grad_ld_f32(xp, ld_x, n_in, gp, ld_g, n_out, column_index.data_ptr(), edge_type.data_ptr(),
-                                                  _ptr(edge_norm), part_pointers.data_ptr(), part2Node.data_ptr(), out.data_ptr(),
-                                                  int(num_types), B, dim, part2Node.numel(), int(partSize),
-                                                  ACCUMULATE if accumulate else 0, _stream(X.device)))
+    _call(X.device, "gnna_typed_coef_grad_ld_f32", xp, ld_x, n_in, gp, ld_g, n_out, column_index.data_ptr(), edge_type.data_ptr(),
+          _ptr(edge_norm), part_pointers.data_ptr(), part2Node.data_ptr(), out.data_ptr(), int(num_types), B, dim,
+          part2Node.numel(), int(partSize), _flags(accumulate))
     return out

@@ -27,6 +27,7 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
 #include <atomic>
+#include <functional>
 #include <mutex>
 #include <vector>
 
@@ -186,6 +187,68 @@ void forget_graph(const torch::Tensor &column_index)
     (void)gnna_forget_graph(static_cast<const int32_t *>(ci));
 }
 
+// ---- shared by the wrappers below: one copy of the tensor checks, the output allocation and the call tail -------------
+// A wrapper for a new operator goes next to the one it resembles and is made of these.  Where the CHECK_* macros would have
+// stringified their argument, a helper is handed the name: the text is the same ("column_index must be a CUDA tensor").
+
+// leading dimension of a [rows, dim] view with contiguous rows (a single row may carry any stride(0))
+int64_t ld_of(const torch::Tensor &t) { return t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(t.size(1), t.stride(0)); }
+
+// GNNA_DEBUG_POISON=1 (the test suite sets it): every fresh output starts as NaN, an int32 one as `int_fill`, so that an
+// element the library fails to write cannot go unnoticed (NaN in every float type: the 16-bit outputs are covered as well)
+bool poisoned()
+{
+    static const bool poison = std::getenv("GNNA_DEBUG_POISON") && std::atoi(std::getenv("GNNA_DEBUG_POISON")) != 0;
+    return poison;
+}
+torch::Tensor fresh(at::IntArrayRef sizes, const at::TensorOptions &options, int32_t int_fill = std::numeric_limits<int32_t>::min())
+{
+    if (!poisoned()) return torch::empty(sizes, options);
+    if (c10::typeMetaToScalarType(options.dtype()) == at::kInt) return torch::full(sizes, int_fill, options);
+    return torch::full(sizes, std::numeric_limits<float>::quiet_NaN(), options);
+}
+
+void check_input(const torch::Tensor &t, const char *name)
+{
+    TORCH_CHECK(t.is_cuda(), name, " must be a CUDA tensor");
+    TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+}
+void check_i32(const torch::Tensor &t, const char *name) { TORCH_CHECK(t.scalar_type() == at::kInt, name, " must be int32 (got ", t.scalar_type(), ")"); }
+void check_f32(const torch::Tensor &t, const char *name) { TORCH_CHECK(t.scalar_type() == at::kFloat, name, " must be float32 (got ", t.scalar_type(), ")"); }
+void check_ids(const torch::Tensor &t, const char *name) { check_input(t, name); check_i32(t, name); }
+void check_floats(const torch::Tensor &t, const char *name) { check_input(t, name); check_f32(t, name); }
+void check_partition(const torch::Tensor &column_index, const torch::Tensor &part_pointers, const torch::Tensor &part2Node)
+{
+    check_ids(column_index, "column_index");
+    check_ids(part_pointers, "part_pointers");
+    check_ids(part2Node, "part2Node");
+}
+void check_rows(const torch::Tensor &t, const char *name)
+{
+    TORCH_CHECK(t.size(1) <= 1 || t.stride(1) == 1, name, ": the floats of a row must be contiguous (stride(1) == 1)");
+}
+
+// The caller's `out` ([n, dim], rows contiguous; float32, or whatever `check_dtype` accepts where one is given) or, without one, a
+// fresh tensor -- which there is nothing to accumulate into.
+torch::Tensor out_or_fresh(const c10::optional<torch::Tensor> &out_opt, int64_t n, int64_t dim, const at::TensorOptions &options,
+                           bool accumulate, const std::function<void(const torch::Tensor &)> &check_dtype = nullptr)
+{
+    if (!out_opt.has_value()) {
+        TORCH_CHECK(!accumulate, "accumulate needs an existing `out`");
+        return fresh({n, dim}, options);
+    }
+    const torch::Tensor &out = *out_opt;
+    CHECK_CUDA(out);
+    if (check_dtype) check_dtype(out); else CHECK_F32(out);
+    TORCH_CHECK(out.dim() == 2 && out.size(0) == n && out.size(1) == dim, "out must be [num_nodes, dim] like input");
+    check_rows(out, "out");
+    return out;
+}
+
+// PyTorch's current stream of the current device: call it under the device guard of the tensors
+void *current_stream() { return at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream(); }
+void check_rc(int64_t rc) { TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error()); }
+
 // Runs one aggregation of `input` ([N, dim]) into a fresh tensor on input's device/stream.
 torch::Tensor aggregate(AggKind kind, const torch::Tensor &input, const torch::Tensor &row_pointers,
                         const torch::Tensor &column_index, const torch::Tensor *degrees, float epsilon,
@@ -205,11 +268,9 @@ torch::Tensor aggregate(AggKind kind, const torch::Tensor &input, const torch::T
     if (kind == AGG_GCN) TORCH_CHECK(degrees->size(0) >= input.size(0), "degrees shorter than num_nodes");
 
     at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(input.device());
-    // fully overwritten by the library (prologue + stores / atomics).  GNNA_DEBUG_POISON=1 (the test suite sets it)
-    // starts every output as NaN so that an element the library fails to write cannot go unnoticed
-    static const bool poison = std::getenv("GNNA_DEBUG_POISON") && std::atoi(std::getenv("GNNA_DEBUG_POISON")) != 0;
-    auto out = poison ? torch::full_like(input, std::numeric_limits<float>::quiet_NaN()) : torch::empty_like(input);
-    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+    // fully overwritten by the library (prologue + stores / atomics)
+    auto out = poisoned() ? torch::full_like(input, std::numeric_limits<float>::quiet_NaN()) : torch::empty_like(input);
+    void *stream = current_stream();
 
     const float *x = input.data_ptr<float>();
     const int32_t *rp = row_pointers.data_ptr<int32_t>();
@@ -236,7 +297,7 @@ torch::Tensor aggregate(AggKind kind, const torch::Tensor &input, const torch::T
                               warpPerBlock, stream);
         break;
     }
-    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+    check_rc(rc);
     return out;
 }
 
@@ -259,57 +320,40 @@ torch::Tensor aggregate_general(int mode, const torch::Tensor &input, const torc
         TORCH_CHECK(out_dtype == input.scalar_type() || (x16 && out_dtype == at::kFloat),
                     "out_dtype must be float32 or the input's dtype ", input.scalar_type(), " (got ", out_dtype, ")");
     }
-    CHECK_INPUT(column_index); CHECK_I32(column_index);
-    CHECK_INPUT(part_pointers); CHECK_I32(part_pointers);
-    CHECK_INPUT(part2Node); CHECK_I32(part2Node);
+    check_partition(column_index, part_pointers, part2Node);
     TORCH_CHECK(mode >= 0 && mode <= 2, "mode must be 0 (sag), 1 (gcn) or 2 (gin)");
-    TORCH_CHECK(input.size(1) <= 1 || input.stride(1) == 1, "input: the floats of a row must be contiguous (stride(1) == 1)");
-    const int64_t n = input.size(0);
-    const int64_t dim = input.size(1);
-    auto ld_of = [&](const torch::Tensor &t) { return t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(t.size(1), t.stride(0)); };
+    check_rows(input, "input");
+    const int64_t n = input.size(0), dim = input.size(1);
     if (mode == 1) {
         TORCH_CHECK(degrees.has_value(), "mode 1 (gcn) needs the degree norms");
-        CHECK_INPUT((*degrees)); CHECK_F32((*degrees));
+        check_floats(*degrees, "(*degrees)");
         TORCH_CHECK(degrees->size(0) >= n, "degrees shorter than num_nodes");
     }
     at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(input.device());
-    static const bool poison = std::getenv("GNNA_DEBUG_POISON") && std::atoi(std::getenv("GNNA_DEBUG_POISON")) != 0;
-    torch::Tensor out;
-    if (out_opt.has_value()) {
-        out = *out_opt;
-        CHECK_CUDA(out);
-        if (x16) {
-            TORCH_CHECK(out.scalar_type() == at::kFloat || out.scalar_type() == input.scalar_type(),
-                        "out must be float32 or have the input's dtype ", input.scalar_type(), " (got ", out.scalar_type(), ")");
-            TORCH_CHECK(out_dtype_obj.is_none() || out.scalar_type() == out_dtype, "out is ", out.scalar_type(), ", out_dtype says ", out_dtype);
-        } else {
+    const torch::Tensor out = out_or_fresh(out_opt, n, dim, input.options().dtype(out_dtype), accumulate, [&](const torch::Tensor &out) {
+        if (!x16) {
             CHECK_F32(out);
+            return;
         }
-        TORCH_CHECK(out.dim() == 2 && out.size(0) == n && out.size(1) == dim, "out must be [num_nodes, dim] like input");
-        TORCH_CHECK(dim <= 1 || out.stride(1) == 1, "out: the floats of a row must be contiguous (stride(1) == 1)");
-    } else {
-        TORCH_CHECK(!accumulate, "accumulate needs an existing `out`");
-        // (the poison covers the 16-bit outputs as well: an element the library leaves unwritten is NaN in every float type)
-        const auto opts = input.options().dtype(out_dtype);
-        out = poison ? torch::full({n, dim}, std::numeric_limits<float>::quiet_NaN(), opts) : torch::empty({n, dim}, opts);
-    }
-    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+        TORCH_CHECK(out.scalar_type() == at::kFloat || out.scalar_type() == input.scalar_type(),
+                    "out must be float32 or have the input's dtype ", input.scalar_type(), " (got ", out.scalar_type(), ")");
+        TORCH_CHECK(out_dtype_obj.is_none() || out.scalar_type() == out_dtype, "out is ", out.scalar_type(), ", out_dtype says ", out_dtype);
+    });
+    void *stream = current_stream();
     const float *deg = degrees.has_value() ? degrees->data_ptr<float>() : nullptr;
     const unsigned flags = (accumulate ? GNNA_ACCUMULATE : 0u) | (relu ? GNNA_EPILOGUE_RELU : 0u);
     if (x16) {
         // features stored in 16 bits, accumulated in fp32 (gnna_agg_ld_x16); the degrees stay fp32
         const int in_type = input.scalar_type() == at::kBFloat16 ? GNNA_BF16 : GNNA_F16;
         const int out_type = out.scalar_type() == at::kFloat ? GNNA_F32 : in_type;
-        int rc = gnna_agg_ld_x16(mode, in_type, input.data_ptr(), ld_of(input), n, column_index.data_ptr<int32_t>(), deg, deg,
+        check_rc(gnna_agg_ld_x16(mode, in_type, input.data_ptr(), ld_of(input), n, column_index.data_ptr<int32_t>(), deg, deg,
                                  (float)epsilon, part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(),
-                                 out.data_ptr(), out_type, ld_of(out), n, (int)dim, part2Node.size(0), partSize, flags, stream);
-        TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+                                 out.data_ptr(), out_type, ld_of(out), n, (int)dim, part2Node.size(0), partSize, flags, stream));
         return out;
     }
-    int rc = gnna_agg_ld_f32(mode, input.data_ptr<float>(), ld_of(input), n, column_index.data_ptr<int32_t>(), deg, deg,
+    check_rc(gnna_agg_ld_f32(mode, input.data_ptr<float>(), ld_of(input), n, column_index.data_ptr<int32_t>(), deg, deg,
                              (float)epsilon, part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(),
-                             out.data_ptr<float>(), ld_of(out), n, (int)dim, part2Node.size(0), partSize, flags, stream);
-    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+                             out.data_ptr<float>(), ld_of(out), n, (int)dim, part2Node.size(0), partSize, flags, stream));
     return out;
 }
 
@@ -321,36 +365,22 @@ torch::Tensor aggregate_edge(const torch::Tensor &input, const torch::Tensor &co
     CHECK_CUDA(input);
     TORCH_CHECK(input.dim() == 2, "input must be 2-D [num_nodes, dim]");
     CHECK_F32(input);
-    CHECK_INPUT(column_index); CHECK_I32(column_index);
-    CHECK_INPUT(edge_weight); CHECK_F32(edge_weight);
-    CHECK_INPUT(part_pointers); CHECK_I32(part_pointers);
-    CHECK_INPUT(part2Node); CHECK_I32(part2Node);
+    check_ids(column_index, "column_index");
+    check_floats(edge_weight, "edge_weight");
+    check_ids(part_pointers, "part_pointers");
+    check_ids(part2Node, "part2Node");
     TORCH_CHECK(edge_weight.dim() == 1 && edge_weight.size(0) == column_index.numel(),
                 "edge_weight must be [nnz], indexed like column_index");
     TORCH_CHECK(edge_weight.device() == input.device() && column_index.device() == input.device(),
                 "input, column_index and edge_weight must be on one device");
-    TORCH_CHECK(input.size(1) <= 1 || input.stride(1) == 1, "input: the floats of a row must be contiguous (stride(1) == 1)");
-    const int64_t n = input.size(0);
-    const int64_t dim = input.size(1);
-    auto ld_of = [&](const torch::Tensor &t) { return t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(t.size(1), t.stride(0)); };
+    check_rows(input, "input");
+    const int64_t n = input.size(0), dim = input.size(1);
     at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(input.device());
-    static const bool poison = std::getenv("GNNA_DEBUG_POISON") && std::atoi(std::getenv("GNNA_DEBUG_POISON")) != 0;
-    torch::Tensor out;
-    if (out_opt.has_value()) {
-        out = *out_opt;
-        CHECK_CUDA(out); CHECK_F32(out);
-        TORCH_CHECK(out.dim() == 2 && out.size(0) == n && out.size(1) == dim, "out must be [num_nodes, dim] like input");
-        TORCH_CHECK(dim <= 1 || out.stride(1) == 1, "out: the floats of a row must be contiguous (stride(1) == 1)");
-    } else {
-        TORCH_CHECK(!accumulate, "accumulate needs an existing `out`");
-        out = poison ? torch::full({n, dim}, std::numeric_limits<float>::quiet_NaN(), input.options()) : torch::empty({n, dim}, input.options());
-    }
-    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+    const torch::Tensor out = out_or_fresh(out_opt, n, dim, input.options(), accumulate);
     const unsigned flags = (accumulate ? GNNA_ACCUMULATE : 0u) | (relu ? GNNA_EPILOGUE_RELU : 0u);
-    int rc = gnna_agg_edge_ld_f32(input.data_ptr<float>(), ld_of(input), n, column_index.data_ptr<int32_t>(),
+    check_rc(gnna_agg_edge_ld_f32(input.data_ptr<float>(), ld_of(input), n, column_index.data_ptr<int32_t>(),
                                   edge_weight.data_ptr<float>(), part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(),
-                                  out.data_ptr<float>(), ld_of(out), n, (int)dim, part2Node.size(0), partSize, flags, stream);
-    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+                                  out.data_ptr<float>(), ld_of(out), n, (int)dim, part2Node.size(0), partSize, flags, current_stream()));
     return out;
 }
 
@@ -364,38 +394,20 @@ aggregate_reduce(int op, const torch::Tensor &input, const torch::Tensor &column
     CHECK_CUDA(input);
     TORCH_CHECK(input.dim() == 2, "input must be 2-D [num_nodes, dim]");
     CHECK_F32(input);
-    CHECK_INPUT(column_index); CHECK_I32(column_index);
-    CHECK_INPUT(part_pointers); CHECK_I32(part_pointers);
-    CHECK_INPUT(part2Node); CHECK_I32(part2Node);
+    check_partition(column_index, part_pointers, part2Node);
     TORCH_CHECK(op == GNNA_REDUCE_MAX || op == GNNA_REDUCE_MIN, "op must be 0 (max) or 1 (min)");
     TORCH_CHECK(column_index.device() == input.device(), "input and column_index must be on one device");
     TORCH_CHECK(input.size(1) >= 1, "input must have at least one column");
-    TORCH_CHECK(input.size(1) <= 1 || input.stride(1) == 1, "input: the floats of a row must be contiguous (stride(1) == 1)");
-    const int64_t n = input.size(0);
-    const int64_t dim = input.size(1);
-    auto ld_of = [&](const torch::Tensor &t) { return t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(t.size(1), t.stride(0)); };
+    check_rows(input, "input");
+    const int64_t n = input.size(0), dim = input.size(1);
     at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(input.device());
-    static const bool poison = std::getenv("GNNA_DEBUG_POISON") && std::atoi(std::getenv("GNNA_DEBUG_POISON")) != 0;
-    torch::Tensor out;
-    if (out_opt.has_value()) {
-        out = *out_opt;
-        CHECK_CUDA(out); CHECK_F32(out);
-        TORCH_CHECK(out.dim() == 2 && out.size(0) == n && out.size(1) == dim, "out must be [num_nodes, dim] like input");
-        TORCH_CHECK(dim <= 1 || out.stride(1) == 1, "out: the floats of a row must be contiguous (stride(1) == 1)");
-    } else {
-        out = poison ? torch::full({n, dim}, std::numeric_limits<float>::quiet_NaN(), input.options()) : torch::empty({n, dim}, input.options());
-    }
+    const torch::Tensor out = out_or_fresh(out_opt, n, dim, input.options(), /*accumulate=*/false);
     c10::optional<torch::Tensor> arg;
-    if (want_arg) {
-        const auto opts = input.options().dtype(at::kInt);
-        arg = poison ? torch::full({n, dim}, std::numeric_limits<int32_t>::min(), opts) : torch::empty({n, dim}, opts);
-    }
-    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-    int rc = gnna_agg_reduce_ld_f32(op, input.data_ptr<float>(), ld_of(input), n, column_index.data_ptr<int32_t>(),
+    if (want_arg) arg = fresh({n, dim}, input.options().dtype(at::kInt));
+    check_rc(gnna_agg_reduce_ld_f32(op, input.data_ptr<float>(), ld_of(input), n, column_index.data_ptr<int32_t>(),
                                     part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), out.data_ptr<float>(),
                                     ld_of(out), arg.has_value() ? arg->data_ptr<int32_t>() : nullptr, dim, n, (int)dim,
-                                    part2Node.size(0), partSize, relu ? GNNA_EPILOGUE_RELU : 0u, stream);
-    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+                                    part2Node.size(0), partSize, relu ? GNNA_EPILOGUE_RELU : 0u, current_stream()));
     return std::make_tuple(out, arg);
 }
 
@@ -406,33 +418,27 @@ torch::Tensor scatter_arg(const torch::Tensor &grad_out, const torch::Tensor &ar
     CHECK_CUDA(grad_out);
     TORCH_CHECK(grad_out.dim() == 2, "grad_out must be 2-D [num_nodes, dim]");
     CHECK_F32(grad_out);
-    CHECK_INPUT(arg); CHECK_I32(arg);
-    CHECK_INPUT(column_index); CHECK_I32(column_index);
+    check_ids(arg, "arg");
+    check_ids(column_index, "column_index");
     TORCH_CHECK(arg.dim() == 2 && arg.size(0) == grad_out.size(0) && arg.size(1) == grad_out.size(1), "arg must be [num_nodes, dim] like grad_out");
     TORCH_CHECK(arg.device() == grad_out.device() && column_index.device() == grad_out.device(),
                 "grad_out, arg and column_index must be on one device");
     TORCH_CHECK(grad_out.size(1) >= 1, "grad_out must have at least one column");
-    TORCH_CHECK(grad_out.size(1) <= 1 || grad_out.stride(1) == 1, "grad_out: the floats of a row must be contiguous (stride(1) == 1)");
+    check_rows(grad_out, "grad_out");
     TORCH_CHECK(num_in_rows >= 0, "num_in_rows must not be negative");
-    const int64_t n = grad_out.size(0);
-    const int64_t dim = grad_out.size(1);
-    auto ld_of = [&](const torch::Tensor &t) { return t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(t.size(1), t.stride(0)); };
+    const int64_t n = grad_out.size(0), dim = grad_out.size(1);
     at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(grad_out.device());
-    static const bool poison = std::getenv("GNNA_DEBUG_POISON") && std::atoi(std::getenv("GNNA_DEBUG_POISON")) != 0;
-    auto out = poison ? torch::full({num_in_rows, dim}, std::numeric_limits<float>::quiet_NaN(), grad_out.options())
-                      : torch::empty({num_in_rows, dim}, grad_out.options());
-    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-    int rc = gnna_scatter_arg_ld_f32(grad_out.data_ptr<float>(), ld_of(grad_out), arg.data_ptr<int32_t>(), dim,
-                                     column_index.data_ptr<int32_t>(), n, out.data_ptr<float>(), dim, num_in_rows, (int)dim, 0u, stream);
-    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+    auto out = fresh({num_in_rows, dim}, grad_out.options());
+    check_rc(gnna_scatter_arg_ld_f32(grad_out.data_ptr<float>(), ld_of(grad_out), arg.data_ptr<int32_t>(), dim,
+                                     column_index.data_ptr<int32_t>(), n, out.data_ptr<float>(), dim, num_in_rows, (int)dim, 0u, current_stream()));
     return out;
 }
 
 // Edge softmax and its backward: scores [nnz] or head-major [heads, nnz] over the rows of row_pointers.
 torch::Tensor edge_softmax(const torch::Tensor &scores, const torch::Tensor &row_pointers)
 {
-    CHECK_INPUT(scores); CHECK_F32(scores);
-    CHECK_INPUT(row_pointers); CHECK_I32(row_pointers);
+    check_floats(scores, "scores");
+    check_ids(row_pointers, "row_pointers");
     TORCH_CHECK(scores.dim() == 1 || scores.dim() == 2, "scores must be [nnz] or [heads, nnz]");
     TORCH_CHECK(row_pointers.dim() == 1 && row_pointers.size(0) >= 1, "row_pointers must be [num_rows + 1]");
     TORCH_CHECK(row_pointers.device() == scores.device(), "scores and row_pointers must be on one device");
@@ -440,18 +446,16 @@ torch::Tensor edge_softmax(const torch::Tensor &scores, const torch::Tensor &row
     auto probs = torch::empty_like(scores);
     const int heads = scores.dim() == 2 ? (int)scores.size(0) : 1;
     const int64_t nnz = scores.size(scores.dim() - 1);
-    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-    int rc = gnna_edge_softmax_f32(scores.data_ptr<float>(), row_pointers.data_ptr<int32_t>(), row_pointers.size(0) - 1, nnz, heads,
-                                   probs.data_ptr<float>(), stream);
-    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+    check_rc(gnna_edge_softmax_f32(scores.data_ptr<float>(), row_pointers.data_ptr<int32_t>(), row_pointers.size(0) - 1, nnz, heads,
+                                   probs.data_ptr<float>(), current_stream()));
     return probs;
 }
 
 torch::Tensor edge_softmax_backward(const torch::Tensor &probs, const torch::Tensor &grad, const torch::Tensor &row_pointers)
 {
-    CHECK_INPUT(probs); CHECK_F32(probs);
-    CHECK_INPUT(grad); CHECK_F32(grad);
-    CHECK_INPUT(row_pointers); CHECK_I32(row_pointers);
+    check_floats(probs, "probs");
+    check_floats(grad, "grad");
+    check_ids(row_pointers, "row_pointers");
     TORCH_CHECK(probs.dim() == 1 || probs.dim() == 2, "probs must be [nnz] or [heads, nnz]");
     TORCH_CHECK(grad.sizes() == probs.sizes(), "grad must have the shape of probs");
     TORCH_CHECK(row_pointers.dim() == 1 && row_pointers.size(0) >= 1, "row_pointers must be [num_rows + 1]");
@@ -460,10 +464,8 @@ torch::Tensor edge_softmax_backward(const torch::Tensor &probs, const torch::Ten
     auto gs = torch::empty_like(probs);
     const int heads = probs.dim() == 2 ? (int)probs.size(0) : 1;
     const int64_t nnz = probs.size(probs.dim() - 1);
-    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-    int rc = gnna_edge_softmax_backward_f32(probs.data_ptr<float>(), grad.data_ptr<float>(), row_pointers.data_ptr<int32_t>(),
-                                            row_pointers.size(0) - 1, nnz, heads, gs.data_ptr<float>(), stream);
-    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+    check_rc(gnna_edge_softmax_backward_f32(probs.data_ptr<float>(), grad.data_ptr<float>(), row_pointers.data_ptr<int32_t>(),
+                                            row_pointers.size(0) - 1, nnz, heads, gs.data_ptr<float>(), current_stream()));
     return gs;
 }
 
@@ -484,10 +486,8 @@ static torch::Tensor gat_rows(const torch::Tensor &t, const char *what, int64_t 
 static void gat_check_graph(const torch::Tensor &H, int64_t rows, const torch::Tensor &row_pointers,
                             const torch::Tensor &column_index, const torch::Tensor &part_pointers, const torch::Tensor &part2Node)
 {
-    CHECK_INPUT(row_pointers); CHECK_I32(row_pointers);
-    CHECK_INPUT(column_index); CHECK_I32(column_index);
-    CHECK_INPUT(part_pointers); CHECK_I32(part_pointers);
-    CHECK_INPUT(part2Node); CHECK_I32(part2Node);
+    check_ids(row_pointers, "row_pointers");
+    check_partition(column_index, part_pointers, part2Node);
     TORCH_CHECK(row_pointers.dim() == 1 && row_pointers.size(0) == rows + 1, "row_pointers must be [num_nodes + 1] (", rows + 1,
                 " entries: one more than the rows of the side it walks)");
     TORCH_CHECK(part_pointers.numel() == part2Node.numel() + 1, "part_pointers must be [num_parts + 1]");
@@ -497,7 +497,8 @@ static void gat_check_graph(const torch::Tensor &H, int64_t rows, const torch::T
 
 static int gat_heads(const torch::Tensor &H, const torch::Tensor &el, const torch::Tensor &er)
 {
-    CHECK_INPUT(el); CHECK_F32(el); CHECK_INPUT(er); CHECK_F32(er);
+    check_floats(el, "el");
+    check_floats(er, "er");
     TORCH_CHECK(H.dim() == 2, "H must be 2-D [num_nodes, heads * dim]");
     TORCH_CHECK(el.dim() == 2 && el.size(1) >= 1 && er.dim() == 2 && er.size(0) == H.size(0) && er.size(1) == el.size(1),
                 "el and er must be [num_nodes, heads] (rectangular: el [num_out_rows, heads], er [num_in_rows = H.size(0), heads])");
@@ -515,27 +516,21 @@ gat_forward(const torch::Tensor &H_in, const torch::Tensor &el, const torch::Ten
     const int64_t n_in = H_in.size(0), n_out = el.size(0), width = H_in.size(1);
     const torch::Tensor H = gat_rows(H_in, "H", n_in, width);
     gat_check_graph(H, n_out, row_pointers, column_index, part_pointers, part2Node);
-    auto ld_of = [&](const torch::Tensor &t) { return t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(t.size(1), t.stride(0)); };
     at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(H.device());
-    static const bool poison = std::getenv("GNNA_DEBUG_POISON") && std::atoi(std::getenv("GNNA_DEBUG_POISON")) != 0;
-    const float nan = std::numeric_limits<float>::quiet_NaN();
-    auto Y = poison ? torch::full({n_out, width}, nan, el.options()) : torch::empty({n_out, width}, el.options());
-    auto lse = poison ? torch::full({n_out, (int64_t)heads}, nan, el.options()) : torch::empty({n_out, (int64_t)heads}, el.options());
-    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-    int rc;
+    auto Y = fresh({n_out, width}, el.options()), lse = fresh({n_out, (int64_t)heads}, el.options());
+    void *stream = current_stream();
     if (n_out == n_in)
-        rc = gnna_gat_forward_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(),
-                                  row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
-                                  part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), (float)negative_slope,
-                                  Y.data_ptr<float>(), width, lse.data_ptr<float>(), n_out, heads, (int)(width / heads),
-                                  part2Node.size(0), partSize, 0u, stream);
+        check_rc(gnna_gat_forward_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(),
+                                      row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
+                                      part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), (float)negative_slope,
+                                      Y.data_ptr<float>(), width, lse.data_ptr<float>(), n_out, heads, (int)(width / heads),
+                                      part2Node.size(0), partSize, 0u, stream));
     else
-        rc = gnna_gat_forward_rect_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(),
-                                       row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
-                                       part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), (float)negative_slope,
-                                       Y.data_ptr<float>(), width, lse.data_ptr<float>(), n_out, n_in, heads,
-                                       (int)(width / heads), part2Node.size(0), partSize, 0u, stream);
-    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+        check_rc(gnna_gat_forward_rect_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(),
+                                           row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
+                                           part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), (float)negative_slope,
+                                           Y.data_ptr<float>(), width, lse.data_ptr<float>(), n_out, n_in, heads,
+                                           (int)(width / heads), part2Node.size(0), partSize, 0u, stream));
     return std::make_tuple(Y, lse);
 }
 
@@ -560,39 +555,32 @@ gat_backward(const torch::Tensor &H_in, const torch::Tensor &el, const torch::Te
         t_rp = &(*transposed)[0]; t_ci = &(*transposed)[1]; t_pp = &(*transposed)[2]; t_p2n = &(*transposed)[3];
         gat_check_graph(H, n_in, *t_rp, *t_ci, *t_pp, *t_p2n);
     }
-    CHECK_INPUT(lse); CHECK_F32(lse);
+    check_floats(lse, "lse");
     TORCH_CHECK(lse.sizes() == el.sizes() && lse.device() == H.device(), "lse must be [num_nodes, heads] (the shape of el) on H's device");
     TORCH_CHECK(Y.device() == H.device() && dY.device() == H.device(), "H, Y and dY must be on one device");
     gat_check_graph(H, n_out, row_pointers, column_index, part_pointers, part2Node);
-    auto ld_of = [&](const torch::Tensor &t) { return t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(t.size(1), t.stride(0)); };
     at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(H.device());
-    static const bool poison = std::getenv("GNNA_DEBUG_POISON") && std::atoi(std::getenv("GNNA_DEBUG_POISON")) != 0;
-    const float nan = std::numeric_limits<float>::quiet_NaN();
-    auto fresh = [&](int64_t rows, int64_t cols) {
-        return poison ? torch::full({rows, cols}, nan, el.options()) : torch::empty({rows, cols}, el.options());
-    };
-    auto dH = fresh(n_in, width), d_el = fresh(n_out, heads), d_er = fresh(n_in, heads);
-    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-    int rc;
+    auto dH = fresh({n_in, width}, el.options()), d_el = fresh({n_out, (int64_t)heads}, el.options()),
+         d_er = fresh({n_in, (int64_t)heads}, el.options());
+    void *stream = current_stream();
     if (!rect)
-        rc = gnna_gat_backward_dir_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(), lse.data_ptr<float>(),
-                                       Y.data_ptr<float>(), ld_of(Y), dY.data_ptr<float>(), ld_of(dY),
-                                       row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
-                                       part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), part2Node.size(0),
-                                       t_rp->data_ptr<int32_t>(), t_ci->data_ptr<int32_t>(), t_pp->data_ptr<int32_t>(),
-                                       t_p2n->data_ptr<int32_t>(), t_p2n->size(0), (float)negative_slope,
-                                       dH.data_ptr<float>(), width, d_el.data_ptr<float>(), d_er.data_ptr<float>(), n_out, heads,
-                                       (int)(width / heads), partSize, 0u, stream);
+        check_rc(gnna_gat_backward_dir_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(), lse.data_ptr<float>(),
+                                           Y.data_ptr<float>(), ld_of(Y), dY.data_ptr<float>(), ld_of(dY),
+                                           row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
+                                           part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), part2Node.size(0),
+                                           t_rp->data_ptr<int32_t>(), t_ci->data_ptr<int32_t>(), t_pp->data_ptr<int32_t>(),
+                                           t_p2n->data_ptr<int32_t>(), t_p2n->size(0), (float)negative_slope,
+                                           dH.data_ptr<float>(), width, d_el.data_ptr<float>(), d_er.data_ptr<float>(), n_out, heads,
+                                           (int)(width / heads), partSize, 0u, stream));
     else
-        rc = gnna_gat_backward_rect_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(), lse.data_ptr<float>(),
-                                        Y.data_ptr<float>(), ld_of(Y), dY.data_ptr<float>(), ld_of(dY),
-                                        row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
-                                        part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), part2Node.size(0),
-                                        t_rp->data_ptr<int32_t>(), t_ci->data_ptr<int32_t>(), t_pp->data_ptr<int32_t>(),
-                                        t_p2n->data_ptr<int32_t>(), t_p2n->size(0), (float)negative_slope,
-                                        dH.data_ptr<float>(), width, d_el.data_ptr<float>(), d_er.data_ptr<float>(), n_out, n_in,
-                                        heads, (int)(width / heads), partSize, 0u, stream);
-    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+        check_rc(gnna_gat_backward_rect_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(), lse.data_ptr<float>(),
+                                            Y.data_ptr<float>(), ld_of(Y), dY.data_ptr<float>(), ld_of(dY),
+                                            row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
+                                            part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), part2Node.size(0),
+                                            t_rp->data_ptr<int32_t>(), t_ci->data_ptr<int32_t>(), t_pp->data_ptr<int32_t>(),
+                                            t_p2n->data_ptr<int32_t>(), t_p2n->size(0), (float)negative_slope,
+                                            dH.data_ptr<float>(), width, d_el.data_ptr<float>(), d_er.data_ptr<float>(), n_out, n_in,
+                                            heads, (int)(width / heads), partSize, 0u, stream));
     return std::make_tuple(dH, d_el, d_er);
 }
 
@@ -601,21 +589,16 @@ torch::Tensor sddmm(const torch::Tensor &A, const torch::Tensor &B, const torch:
                     const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize)
 {
     CHECK_CUDA(A); CHECK_CUDA(B); CHECK_F32(A); CHECK_F32(B);
-    CHECK_INPUT(column_index); CHECK_I32(column_index);
-    CHECK_INPUT(part_pointers); CHECK_I32(part_pointers);
-    CHECK_INPUT(part2Node); CHECK_I32(part2Node);
+    check_partition(column_index, part_pointers, part2Node);
     TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.size(1) == B.size(1), "A [rows, dim] and B [num_nodes, dim] expected");
     TORCH_CHECK(A.device() == B.device() && column_index.device() == A.device(), "A, B and column_index must be on one device");
     TORCH_CHECK(A.size(1) <= 1 || (A.stride(1) == 1 && B.stride(1) == 1), "the floats of a row must be contiguous (stride(1) == 1)");
-    auto ld_of = [&](const torch::Tensor &t) { return t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(t.size(1), t.stride(0)); };
     at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(A.device());
     // (edges of rows without a neighbor-group -- none in a partition of the full CSR -- stay zero)
     auto out = torch::zeros({column_index.numel()}, A.options());
-    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-    int rc = gnna_sddmm_ld_f32(A.data_ptr<float>(), ld_of(A), B.data_ptr<float>(), ld_of(B), column_index.data_ptr<int32_t>(),
+    check_rc(gnna_sddmm_ld_f32(A.data_ptr<float>(), ld_of(A), B.data_ptr<float>(), ld_of(B), column_index.data_ptr<int32_t>(),
                                part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), out.data_ptr<float>(),
-                               A.size(0), B.size(0), (int)A.size(1), part2Node.size(0), partSize, stream);
-    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+                               A.size(0), B.size(0), (int)A.size(1), part2Node.size(0), partSize, current_stream()));
     return out;
 }
 
@@ -858,7 +841,7 @@ static void check_device_ids(const torch::Tensor &t, const char *what)
 {
     TORCH_CHECK(t.is_cuda(), what, " must be a CUDA tensor (the builder runs on the device)");
     TORCH_CHECK(t.is_contiguous() && t.dim() == 1, what, " must be a contiguous 1-D tensor");
-    TORCH_CHECK(t.scalar_type() == at::kInt, what, " must be int32 (got ", t.scalar_type(), ")");
+    check_i32(t, what);
 }
 
 // (t_row_pointers [num_in_rows + 1], t_column_index [nnz], t_perm [nnz]) of A^T; t_perm is omitted with want_perm = false.
@@ -878,11 +861,9 @@ std::vector<torch::Tensor> transpose_csr(const torch::Tensor &row_pointers, cons
     auto t_ci = torch::empty({nnz}, row_pointers.options());
     torch::Tensor t_perm;
     if (want_perm) t_perm = torch::empty({nnz}, row_pointers.options());
-    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-    int rc = gnna_transpose_csr_i32(row_pointers.data_ptr<int32_t>(), nnz ? column_index.data_ptr<int32_t>() : nullptr, n_out, n_in,
+    check_rc(gnna_transpose_csr_i32(row_pointers.data_ptr<int32_t>(), nnz ? column_index.data_ptr<int32_t>() : nullptr, n_out, n_in,
                                     t_rp.data_ptr<int32_t>(), nnz ? t_ci.data_ptr<int32_t>() : nullptr,
-                                    want_perm && nnz ? t_perm.data_ptr<int32_t>() : nullptr, stream);
-    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+                                    want_perm && nnz ? t_perm.data_ptr<int32_t>() : nullptr, current_stream()));
     if (want_perm) return {t_rp, t_ci, t_perm};
     return {t_rp, t_ci};
 }
@@ -894,14 +875,13 @@ std::vector<torch::Tensor> build_part_device(int partSize, const torch::Tensor &
     TORCH_CHECK(indptr.numel() >= 1, "indptr must have num_nodes + 1 entries");
     const int64_t num_nodes = indptr.numel() - 1;
     at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(indptr.device());
-    void *stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+    void *stream = current_stream();
     const int64_t num_parts = gnna_count_parts_device_i32(partSize, indptr.data_ptr<int32_t>(), num_nodes, stream);
     TORCH_CHECK(num_parts >= 0, "GNNAdvisor (libgnna) error ", num_parts, ": ", gnna_last_error());
     auto partPtr = torch::empty({num_parts + 1}, indptr.options());
     auto part2Node = torch::empty({num_parts}, indptr.options());
-    int rc = gnna_build_part_device_i32(partSize, indptr.data_ptr<int32_t>(), num_nodes, partPtr.data_ptr<int32_t>(),
-                                        num_parts ? part2Node.data_ptr<int32_t>() : nullptr, num_parts, stream);
-    TORCH_CHECK(rc == GNNA_OK, "GNNAdvisor (libgnna) error ", rc, ": ", gnna_last_error());
+    check_rc(gnna_build_part_device_i32(partSize, indptr.data_ptr<int32_t>(), num_nodes, partPtr.data_ptr<int32_t>(),
+                                        num_parts ? part2Node.data_ptr<int32_t>() : nullptr, num_parts, stream));
     return {partPtr, part2Node};
 }
 

@@ -13,13 +13,14 @@ import torch
 
 import oracle
 from gnnadvisor_osdi21_amd import _lib, decider, graph, load_extension
+from util import declared_entries
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_library_exports_every_declared_symbol_of_version_601():
     header = open(os.path.join(ROOT, "include", "gnna.h")).read()
-    declared = set(re.findall(r"GNNA_API\s+[\w\s\*]+?\b(gnna_\w+)\s*\(", header))
+    declared = declared_entries(header)
     assert declared, "no GNNA_API declarations found"
     lib = _lib.load()
     for name in declared:

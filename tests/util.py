@@ -6,6 +6,12 @@ import oracle
 from gnnadvisor_osdi21_amd import _lib, graph
 
 
+def declared_entries(header_text):
+    """Names of the functions a header declares with GNNA_API (include/gnna.h)."""
+    import re
+    return set(re.findall(r"GNNA_API\s+[\w\s\*]+?\b(gnna_\w+)\s*\(", header_text))
+
+
 def make_case(num_nodes, num_edges, dim, partSize, seed, kind="uniform", x="randn"):
     """Seeded CPU graph + features + the product's partition (all numpy/torch CPU)."""
     if kind == "uniform":
