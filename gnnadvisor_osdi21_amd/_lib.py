@@ -102,8 +102,14 @@ SIGNATURES = {
     "gnna_agg_typed_contract_ld_f32": (i, _TYPED),
     "gnna_typed_coef_grad_ld_f32": (i, [p, i64, i64, p, i64, i64, p, p, p, p, p, p, i, i, i, i64, i, u, p]),
 }
+# entries added after the pinned 601 surface (include/gnna_ext.h): a second table, applied by load() the same way
+EXT_SIGNATURES = {
+    "gnna_gat_forward_drop_f32": (i, _GAT_FWD[:9] + [f, u64] + _GAT_FWD[9:] + [i64, i64, i, i, i64, i, u, p]),     # attn_drop, rng_seed after the slope
+    "gnna_gat_backward_drop_f32": (i, _GAT_BWD + _GAT_BOTH[:11] + [f, u64] + _GAT_BOTH[11:] + [i64, i64, i, i, i, u, p]),
+}
 del p, i, i64, u, u64, f, s, pd, pi, pi64
 EXPORTS = tuple(SIGNATURES)
+EXT_EXPORTS = tuple(EXT_SIGNATURES)
 
 
 def load() -> ctypes.CDLL:
@@ -116,7 +122,7 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -m gnnadvisor_osdi21_amd.build`). There is no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in (*SIGNATURES.items(), *EXT_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype = restype
         if argtypes is not None:
@@ -749,6 +755,21 @@ def gat_forward(H, el, er, row_pointers, column_index, part_pointers, part2Node,
     Rectangular structures (a sampled block): H [num_in_rows, heads * dim], er [num_in_rows, heads], el [num_out_rows, heads]
     with num_out_rows = row_pointers.numel() - 1 -> out [num_out_rows, heads * dim], lse [num_out_rows, heads]; when the two
     counts differ the call is gnna_gat_forward_rect_f32."""
+    return _gat_forward(None, H, el, er, row_pointers, column_index, part_pointers, part2Node, partSize, negative_slope, out, lse, relu)
+
+
+def gat_forward_drop(H, el, er, row_pointers, column_index, part_pointers, part2Node, partSize, negative_slope, attn_drop, rng_seed,
+                     out=None, lse=None, relu=False):
+    """gnna_gat_forward_drop_f32 (include/gnna_ext.h): gat_forward with attention dropout -- every alpha is scaled by
+    k(rng_seed, i, j, h) = 0 or 1 / (1 - attn_drop), a function of the seed, the two row numbers and the head that every pass
+    recomputes (no mask tensor).  lse is that of the undropped scores.  attn_drop in [0, 1), rng_seed in [0, 2^64).  -> (out, lse).
+    Every structure goes through the one (rectangular) entry."""
+    return _gat_forward((float(attn_drop), int(rng_seed)), H, el, er, row_pointers, column_index, part_pointers, part2Node, partSize,
+                        negative_slope, out, lse, relu)
+
+
+def _gat_forward(drop, H, el, er, row_pointers, column_index, part_pointers, part2Node, partSize, negative_slope, out, lse, relu):
+    """What gat_forward and gat_forward_drop (drop = (attn_drop, rng_seed)) share."""
     _need_device(H, "GAT attention")
     hp, n_out, n_in, width, heads, ld_h = _gat_sizes(H, el, er, row_pointers)
     if out is None:
@@ -758,9 +779,11 @@ def gat_forward(H, el, er, row_pointers, column_index, part_pointers, part2Node,
     op_, n_o, width_o, ld_out = _rows_view(out, "out")
     assert n_o == n_out and width_o == width and _node_heads(lse, n_out, "lse") == heads
     entry, sizes = ("gnna_gat_forward_f32", (n_out,)) if n_out == n_in else ("gnna_gat_forward_rect_f32", (n_out, n_in))
+    if drop is not None:
+        entry, sizes = "gnna_gat_forward_drop_f32", (n_out, n_in)
     _call(H.device, entry, hp, ld_h, el.data_ptr(), er.data_ptr(), row_pointers.data_ptr(), column_index.data_ptr(),
-          part_pointers.data_ptr(), part2Node.data_ptr(), float(negative_slope), op_, ld_out, lse.data_ptr(), *sizes, heads,
-          width // heads, part2Node.numel(), int(partSize), _flags(relu=relu))
+          part_pointers.data_ptr(), part2Node.data_ptr(), float(negative_slope), *(drop or ()), op_, ld_out, lse.data_ptr(), *sizes,
+          heads, width // heads, part2Node.numel(), int(partSize), _flags(relu=relu))
     return out, lse
 
 
@@ -772,6 +795,22 @@ def gat_backward(H, el, er, lse, Y, dY, row_pointers, column_index, part_pointer
     same partSize: gnna_gat_backward_dir_f32, exact on a directed graph.
     Rectangular structures (sizes as in gat_forward; Y, dY, lse have num_out_rows rows): gnna_gat_backward_rect_f32, which needs
     `transposed` (num_in_rows rows) -> dH [num_in_rows, heads * dim], d_el [num_out_rows, heads], d_er [num_in_rows, heads]."""
+    return _gat_backward(None, H, el, er, lse, Y, dY, row_pointers, column_index, part_pointers, part2Node, partSize, negative_slope,
+                         dH, transposed)
+
+
+def gat_backward_drop(H, el, er, lse, Y, dY, row_pointers, column_index, part_pointers, part2Node, partSize, negative_slope,
+                      attn_drop, rng_seed, dH=None, transposed=None):
+    """gnna_gat_backward_drop_f32 (include/gnna_ext.h): (dH, d_el, d_er) of gat_forward_drop for the same attn_drop and rng_seed;
+    Y is that call's output.  `transposed` as for gat_backward; without it (a square graph whose structure is symmetric, not
+    checked here) the graph's own structure is passed as the transposed one."""
+    return _gat_backward((float(attn_drop), int(rng_seed)), H, el, er, lse, Y, dY, row_pointers, column_index, part_pointers,
+                         part2Node, partSize, negative_slope, dH, transposed)
+
+
+def _gat_backward(drop, H, el, er, lse, Y, dY, row_pointers, column_index, part_pointers, part2Node, partSize, negative_slope, dH,
+                  transposed):
+    """What gat_backward and gat_backward_drop (drop = (attn_drop, rng_seed)) share."""
     _need_device(H, "GAT attention")
     hp, n_out, n_in, width, heads, ld_h = _gat_sizes(H, el, er, row_pointers)
     yp, n_y, width_y, ld_y = _rows_view(Y, "Y")
@@ -797,8 +836,13 @@ def gat_backward(H, el, er, lse, Y, dY, row_pointers, column_index, part_pointer
     d_el, d_er = _fresh_output((n_out, heads), H.device), _fresh_output((n_in, heads), H.device)
     head = (hp, ld_h, el.data_ptr(), er.data_ptr(), lse.data_ptr(), yp, ld_y, gp, ld_g, row_pointers.data_ptr(),
             column_index.data_ptr(), part_pointers.data_ptr(), part2Node.data_ptr())
-    outs = (float(negative_slope), dp, ld_d, d_el.data_ptr(), d_er.data_ptr())
-    if transposed is not None:
+    outs = (float(negative_slope), *(drop or ()), dp, ld_d, d_el.data_ptr(), d_er.data_ptr())
+    if drop is not None:
+        if transposed is None:
+            t_rp, t_ci, t_pp, t_p2n = row_pointers, column_index, part_pointers, part2Node
+        _call(H.device, "gnna_gat_backward_drop_f32", *head, part2Node.numel(), t_rp.data_ptr(), t_ci.data_ptr(), t_pp.data_ptr(),
+              t_p2n.data_ptr(), t_p2n.numel(), *outs, n_out, n_in, heads, width // heads, int(partSize), 0)
+    elif transposed is not None:
         _call(H.device, "gnna_gat_backward_rect_f32" if rect else "gnna_gat_backward_dir_f32", *head, part2Node.numel(),
               t_rp.data_ptr(), t_ci.data_ptr(), t_pp.data_ptr(), t_p2n.data_ptr(), t_p2n.numel(), *outs,
               *((n_out, n_in) if rect else (n_out,)), heads, width // heads, int(partSize), 0)

@@ -29,9 +29,9 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 LIB_SOURCES = [os.path.join(CSRC, f) for f in ("gnna_agg.hip", "gnna_stream.hip", "gnna_sweep.hip", "gnna_x16.hip", "gnna_reduce.hip", "gnna_sddmm.hip", "gnna_edge.hip", "gnna_gat.hip", "gnna_typed.hip", "gnna_transpose.hip", "gnna_sample.hip",
                                                 "gnna_gemm.hip", "gnna_runtime.hip", "gnna_host.cpp", "gnna_reorder.cpp")]
 LIB_DEPS = LIB_SOURCES + [os.path.join(CSRC, "gnna_internal.h"), os.path.join(CSRC, "gnna_device.h"), os.path.join(CSRC, "gnna_launch.h"),
-                           os.path.join(INCLUDE, "gnna.h")]
+                           os.path.join(INCLUDE, "gnna.h"), os.path.join(INCLUDE, "gnna_ext.h")]
 EXT_SOURCES = [os.path.join(CSRC, "gnna_torch.cpp")]
-EXT_DEPS = EXT_SOURCES + [os.path.join(INCLUDE, "gnna.h")]
+EXT_DEPS = EXT_SOURCES + [os.path.join(INCLUDE, "gnna.h"), os.path.join(INCLUDE, "gnna_ext.h")]
 
 
 def source_hash() -> str:

@@ -99,6 +99,16 @@ __device__ __forceinline__ void vset(typename VecOf<VEC>::T &v, int k, float x)
     if constexpr (VEC == 1) v = x; else v[k] = x;
 }
 
+// The key of a position e under rng_seed: the splitmix64 finaliser of z = rng_seed + 0x9E3779B97F4A7C15 * (e + 1), all arithmetic
+// mod 2^64 (include/gnna.h: the sampling rule; include/gnna_ext.h: the attention-dropout mask).  A bijection of e for a fixed seed.
+__device__ __forceinline__ uint64_t key_of_position(uint64_t rng_seed, uint64_t e)
+{
+    uint64_t z = rng_seed + 0x9E3779B97F4A7C15ull * (e + 1ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
 // Inclusive prefix sum over the 64 lanes with DPP row shifts and row broadcasts (no LDS round trips).
 __device__ __forceinline__ int wave_inclusive_scan(int v)
 {

@@ -1,5 +1,6 @@
 // gnna_gat.hip -- fused multi-head GAT attention, forward and backward (gnna_gat_forward_f32 / gnna_gat_backward_f32 and their
-// rectangular forms gnna_gat_forward_rect_f32 / gnna_gat_backward_rect_f32, which the square entries call).
+// rectangular forms gnna_gat_forward_rect_f32 / gnna_gat_backward_rect_f32, which the square entries call; with attention dropout
+// gnna_gat_forward_drop_f32 / gnna_gat_backward_drop_f32 of gnna_ext.h, the rectangular entries with a mask).
 // CDNA4 / gfx950 only.  No counterpart in the reference (it has no attention layer).
 //
 // With lse[i, h] = logsumexp over the edges of row i of s = leaky_relu(el[i, h] + er[j, h]) known, the attention coefficient of
@@ -28,6 +29,11 @@
 // 64 / LPR partial rows meet by a butterfly and are ADDED with float atomics (correct for every partition gnna_agg_ld_f32
 // accepts, no validation pass), so the outputs are zero-filled first and there is no deterministic schedule for these passes.
 //
+// Attention dropout (the DROP instances of gat_pull_kernel): alpha' = alpha * k after the softmax, k = 0 or 1 / (1 - attn_drop)
+// decided by a splitmix64 key of (rng_seed, i, j, h) that every pass computes beside alpha (gnna_ext.h has the rule).  lse and
+// the pack pass do not change: Y = sum alpha' H, so c = <dY, Y> = sum_e alpha' dalpha is still the row's constant, and
+// dz = alpha * (k * dalpha - c) * (z > 0 ? 1 : negative_slope), dH[j] = sum alpha * k * dY[i].
+//
 // Rectangular structures (sampled blocks): num_out_rows destination rows gather from num_in_rows source rows, so every pass has
 // two bounds -- one for the rows it walks (what part2Node names), one for the ids it gathers:
 //     pass                         rows < (indexed by row)                      ids < (indexed by id)
@@ -41,7 +47,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "gnna.h"
+#include "gnna_ext.h"
 #include "gnna_device.h"
 #include "gnna_internal.h"
 
@@ -247,9 +253,24 @@ struct GatArgs {
     int64_t P;
     uint32_t N, M;                        // rows of the structure walked (part2Node < N), rows gathered from (ids < M)
     int heads, dim, G, xcd_remap;
+    // attention dropout (gnna_ext.h: the mask rule), read by the DROP instances only
+    uint64_t rng_seed;
+    uint32_t drop_thr;                    // an edge is kept when the upper 32 bits of its key are >= drop_thr
+    float keep_scale;                     // 1 / (1 - attn_drop)
 };
 
-template <int SIDE, int LOG_LPH, int LOG_LPR>
+// k(i, j, h) of the mask rule: keep_scale for a kept edge i <- j of head h, 0 for a dropped one.  A function of the two row
+// numbers and the head alone, so the three passes agree without an edge position, a perm array or a reverse-edge map.
+__device__ __forceinline__ float drop_factor(const GatArgs &p, uint32_t i, uint32_t j, int h)
+{
+    const uint64_t u = ((uint64_t)i << 35) | ((uint64_t)j << 6) | (uint64_t)(uint32_t)h;
+    return (uint32_t)(key_of_position(p.rng_seed, u) >> 32) >= p.drop_thr ? p.keep_scale : 0.f;
+}
+
+// DROP: attention dropout after the softmax -- every edge's alpha is scaled by k = drop_factor where it is accumulated, and
+// dalpha where it meets c (a dropped edge still contributes -alpha * c to dz).  The DROP = false instances are the code they
+// were before the mask existed.
+template <int SIDE, int LOG_LPH, int LOG_LPR, bool DROP>
 __global__ void __launch_bounds__(kBlock)
 gat_pull_kernel(const GatArgs p)
 {
@@ -326,6 +347,7 @@ gat_pull_kernel(const GatArgs p)
                     VT v[U];
                     VT rec[SIDE == SIDE_BWD_SRC ? U : 1];
                     float sc[U];
+                    float kf[DROP ? U : 1];
                     bool live[U];
 #pragma unroll
                     for (int k = 0; k < U; k++) {
@@ -339,6 +361,9 @@ gat_pull_kernel(const GatArgs p)
                             if constexpr (SIDE == SIDE_BWD_SRC) rec[k] = p.pack[(size_t)(uint32_t)idj * heads + h];
                             else sc[k] = p.er[(size_t)(uint32_t)idj * heads + h];
                         }
+                        // (the LPH lanes of a head compute the same key, as they compute the same alpha; an idle lane's is unused)
+                        if constexpr (DROP)
+                            kf[k] = SIDE == SIDE_BWD_SRC ? drop_factor(p, (uint32_t)idj, row, h) : drop_factor(p, row, (uint32_t)idj, h);
                     }
 #pragma unroll
                     for (int k = 0; k < U; k++) {
@@ -350,9 +375,11 @@ gat_pull_kernel(const GatArgs p)
                         if constexpr (SIDE != SIDE_FWD) {
                             const float part = (ownv[0] * v[k][0] + ownv[1] * v[k][1]) + (ownv[2] * v[k][2] + ownv[3] * v[k][3]);
                             const float dalpha = head_sum<LPH>(part);
-                            dzs += alpha * (dalpha - c_e) * (z > 0.f ? 1.f : p.slope);
+                            if constexpr (DROP) dzs += alpha * (kf[k] * dalpha - c_e) * (z > 0.f ? 1.f : p.slope);
+                            else dzs += alpha * (dalpha - c_e) * (z > 0.f ? 1.f : p.slope);
                         }
                         if constexpr (SIDE != SIDE_BWD_DST) {
+                            if constexpr (DROP) alpha *= kf[k];
 #pragma unroll
                             for (int q = 0; q < 4; q++) acc[q] = __builtin_fmaf(alpha, v[k][q], acc[q]);
                         }
@@ -379,8 +406,8 @@ gat_pull_kernel(const GatArgs p)
     }
 }
 
-template <int SIDE>
-int launch_pull(DeviceState *ds, hipStream_t stream, GatArgs a, int partSize)
+template <int SIDE, bool DROP>
+int launch_pull_drop(DeviceState *ds, hipStream_t stream, GatArgs a, int partSize)
 {
     if (a.P <= 0) return GNNA_OK;
     const int log_lph = log2_lanes(a.dim, 4);                  // (dim <= kMaxDim: never capped)
@@ -395,10 +422,17 @@ int launch_pull(DeviceState *ds, hipStream_t stream, GatArgs a, int partSize)
         dispatch_lpr(log_lpr, [&](auto L) {
             constexpr int LOG_LPH = decltype(H)::value, LOG_LPR = decltype(L)::value;
             if constexpr (LOG_LPR >= LOG_LPH)      // (a row has at least the lanes of one head)
-                hipLaunchKernelGGL((gat_pull_kernel<SIDE, LOG_LPH, LOG_LPR>), grid, dim3(kBlock), 0, stream, a);
+                hipLaunchKernelGGL((gat_pull_kernel<SIDE, LOG_LPH, LOG_LPR, DROP>), grid, dim3(kBlock), 0, stream, a);
         });
     });
     return launch_ok("GAT attention launch");
+}
+
+// attn_drop = 0 keeps every edge with k = 1: the call runs the instances without the mask
+template <int SIDE>
+int launch_pull(DeviceState *ds, hipStream_t stream, const GatArgs &a, int partSize)
+{
+    return a.drop_thr ? launch_pull_drop<SIDE, true>(ds, stream, a, partSize) : launch_pull_drop<SIDE, false>(ds, stream, a, partSize);
 }
 
 int launch_lse(hipStream_t stream, const float *el, const float *er, const int32_t *rp, const int32_t *col, int64_t N, int64_t M,
@@ -444,14 +478,32 @@ int check_common(const char *what, bool rect, int64_t num_out_rows, int64_t num_
     return deterministic_refused(what, "its rows are added with float atomics");
 }
 
-// The forward of both entries: num_out_rows rows (el, lse, out) gather from num_in_rows rows (H, er).
+// attn_drop of the drop entries: [0, 1), refused before any device work (a NaN fails the first comparison)
+int check_drop(const char *what, float attn_drop)
+{
+    if (!(attn_drop >= 0.f) || attn_drop >= 1.f)
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: attn_drop must be in [0, 1) (got %g)", what, (double)attn_drop);
+    return GNNA_OK;
+}
+
+// thr = (uint32) floor((double)attn_drop * 2^32) and k = 1 / (1 - attn_drop) in fp32, as gnna_ext.h states them
+void set_drop(GatArgs *a, float attn_drop, uint64_t rng_seed)
+{
+    a->rng_seed = rng_seed;
+    a->drop_thr = (uint32_t)std::floor((double)attn_drop * 4294967296.0);
+    a->keep_scale = 1.0f / (1.0f - attn_drop);
+}
+
+// The forward of all entries: num_out_rows rows (el, lse, out) gather from num_in_rows rows (H, er).
 int gat_forward_impl(const char *what, bool rect, const float *H, int64_t ld_h, const float *el, const float *er,
                      const int32_t *row_pointers, const int32_t *column_index, const int32_t *part_pointers,
-                     const int32_t *part2Node, float negative_slope, float *out, int64_t ld_out, float *lse, int64_t num_out_rows,
-                     int64_t num_in_rows, int heads, int dim, int64_t num_parts, int partSize, unsigned flags, void *stream_v)
+                     const int32_t *part2Node, float negative_slope, float attn_drop, uint64_t rng_seed, float *out, int64_t ld_out,
+                     float *lse, int64_t num_out_rows, int64_t num_in_rows, int heads, int dim, int64_t num_parts, int partSize,
+                     unsigned flags, void *stream_v)
 {
     int rc = check_common(what, rect, num_out_rows, num_in_rows, heads, dim, num_parts, partSize, flags,
                           GNNA_ACCUMULATE | GNNA_EPILOGUE_RELU);
+    if (rc == GNNA_OK) rc = check_drop(what, attn_drop);
     if (rc != GNNA_OK) return rc;
     if (num_out_rows == 0) return GNNA_OK;                    // nothing to write
     const int64_t W = (int64_t)heads * dim;
@@ -483,6 +535,7 @@ int gat_forward_impl(const char *what, bool rect, const float *H, int64_t ld_h, 
     a.col = column_index; a.pp = part_pointers; a.p2n = part2Node; a.out = out; a.ld_out = (size_t)ld_out;
     a.slope = negative_slope; a.P = num_parts; a.N = (uint32_t)num_out_rows; a.M = (uint32_t)num_in_rows; a.heads = heads; a.dim = dim;
     a.xcd_remap = tune.xcd_remap != 0 ? 1 : 0;                // (this tune went through apply_graph_hints: not xcd_remap_on())
+    set_drop(&a, attn_drop, rng_seed);
     rc = launch_pull<SIDE_FWD>(ds, stream, a, partSize);
     if (rc != GNNA_OK) return rc;
     if (flags & GNNA_EPILOGUE_RELU) {
@@ -498,10 +551,11 @@ int gat_backward_impl(const char *what, bool rect, const float *H, int64_t ld_h,
                       const float *Y, int64_t ld_y, const float *dY, int64_t ld_dy, const int32_t *column_index,
                       const int32_t *part_pointers, const int32_t *part2Node, int64_t num_parts, const int32_t *t_column_index,
                       const int32_t *t_part_pointers, const int32_t *t_part2Node, int64_t t_num_parts, float negative_slope,
-                      float *dH, int64_t ld_dh, float *d_el, float *d_er, int64_t num_out_rows, int64_t num_in_rows, int heads,
+                      float attn_drop, uint64_t rng_seed, float *dH, int64_t ld_dh, float *d_el, float *d_er, int64_t num_out_rows, int64_t num_in_rows, int heads,
                       int dim, int partSize, unsigned flags, void *stream_v)
 {
     int rc = check_common(what, rect, num_out_rows, num_in_rows, heads, dim, num_parts, partSize, flags, GNNA_ACCUMULATE);
+    if (rc == GNNA_OK) rc = check_drop(what, attn_drop);
     if (rc != GNNA_OK) return rc;
     if (t_num_parts < 0) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: bad size (t_num_parts=%lld)", what, (long long)t_num_parts);
     if (num_out_rows == 0 && num_in_rows == 0) return GNNA_OK;
@@ -546,6 +600,7 @@ int gat_backward_impl(const char *what, bool rect, const float *H, int64_t ld_h,
     a.er = er; a.pack = pack; a.col = column_index; a.pp = part_pointers; a.p2n = part2Node;
     a.slope = negative_slope; a.P = num_parts; a.heads = heads; a.dim = dim;
     a.xcd_remap = xcd_remap_on();
+    set_drop(&a, attn_drop, rng_seed);
     // destination side: row i pulls H[j], er[j] -> d_el
     a.N = (uint32_t)num_out_rows; a.M = (uint32_t)num_in_rows;
     a.own = dY; a.ld_own = (size_t)ld_dy; a.gat = H; a.ld_gat = (size_t)ld_h; a.dsc = d_el;
@@ -572,7 +627,7 @@ int gnna_gat_forward_f32(const float *H, int64_t ld_h, const float *el, const fl
                          int64_t num_parts, int partSize, unsigned flags, void *stream_v)
 {
     return gat_forward_impl("gnna_gat_forward_f32", false, H, ld_h, el, er, row_pointers, column_index, part_pointers, part2Node,
-                            negative_slope, out, ld_out, lse, num_nodes, num_nodes, heads, dim, num_parts, partSize, flags, stream_v);
+                            negative_slope, 0.f, 0, out, ld_out, lse, num_nodes, num_nodes, heads, dim, num_parts, partSize, flags, stream_v);
 }
 
 int gnna_gat_forward_rect_f32(const float *H, int64_t ld_h, const float *el, const float *er, const int32_t *row_pointers,
@@ -582,7 +637,7 @@ int gnna_gat_forward_rect_f32(const float *H, int64_t ld_h, const float *el, con
                               void *stream_v)
 {
     return gat_forward_impl("gnna_gat_forward_rect_f32", true, H, ld_h, el, er, row_pointers, column_index, part_pointers, part2Node,
-                            negative_slope, out, ld_out, lse, num_out_rows, num_in_rows, heads, dim, num_parts, partSize, flags,
+                            negative_slope, 0.f, 0, out, ld_out, lse, num_out_rows, num_in_rows, heads, dim, num_parts, partSize, flags,
                             stream_v);
 }
 
@@ -595,7 +650,7 @@ int gnna_gat_backward_f32(const float *H, int64_t ld_h, const float *el, const f
     (void)row_pointers;     // both passes walk the neighbor-groups
     // a symmetric structure is its own transpose
     return gat_backward_impl("gnna_gat_backward_f32", false, H, ld_h, el, er, lse, Y, ld_y, dY, ld_dy, column_index, part_pointers,
-                             part2Node, num_parts, column_index, part_pointers, part2Node, num_parts, negative_slope, dH, ld_dh,
+                             part2Node, num_parts, column_index, part_pointers, part2Node, num_parts, negative_slope, 0.f, 0, dH, ld_dh,
                              d_el, d_er, num_nodes, num_nodes, heads, dim, partSize, flags, stream_v);
 }
 
@@ -610,8 +665,8 @@ int gnna_gat_backward_dir_f32(const float *H, int64_t ld_h, const float *el, con
     (void)row_pointers;
     (void)t_row_pointers;
     return gat_backward_impl("gnna_gat_backward_f32", false, H, ld_h, el, er, lse, Y, ld_y, dY, ld_dy, column_index, part_pointers,
-                             part2Node, num_parts, t_column_index, t_part_pointers, t_part2Node, t_num_parts, negative_slope, dH,
-                             ld_dh, d_el, d_er, num_nodes, num_nodes, heads, dim, partSize, flags, stream_v);
+                             part2Node, num_parts, t_column_index, t_part_pointers, t_part2Node, t_num_parts, negative_slope, 0.f, 0,
+                             dH, ld_dh, d_el, d_er, num_nodes, num_nodes, heads, dim, partSize, flags, stream_v);
 }
 
 int gnna_gat_backward_rect_f32(const float *H, int64_t ld_h, const float *el, const float *er, const float *lse, const float *Y,
@@ -626,7 +681,36 @@ int gnna_gat_backward_rect_f32(const float *H, int64_t ld_h, const float *el, co
     (void)t_row_pointers;
     return gat_backward_impl("gnna_gat_backward_rect_f32", true, H, ld_h, el, er, lse, Y, ld_y, dY, ld_dy, column_index,
                              part_pointers, part2Node, num_parts, t_column_index, t_part_pointers, t_part2Node, t_num_parts,
-                             negative_slope, dH, ld_dh, d_el, d_er, num_out_rows, num_in_rows, heads, dim, partSize, flags, stream_v);
+                             negative_slope, 0.f, 0, dH, ld_dh, d_el, d_er, num_out_rows, num_in_rows, heads, dim, partSize, flags,
+                             stream_v);
+}
+
+int gnna_gat_forward_drop_f32(const float *H, int64_t ld_h, const float *el, const float *er, const int32_t *row_pointers,
+                              const int32_t *column_index, const int32_t *part_pointers, const int32_t *part2Node,
+                              float negative_slope, float attn_drop, uint64_t rng_seed, float *out, int64_t ld_out, float *lse,
+                              int64_t num_out_rows, int64_t num_in_rows, int heads, int dim, int64_t num_parts, int partSize,
+                              unsigned flags, void *stream_v)
+{
+    return gat_forward_impl("gnna_gat_forward_drop_f32", true, H, ld_h, el, er, row_pointers, column_index, part_pointers, part2Node,
+                            negative_slope, attn_drop, rng_seed, out, ld_out, lse, num_out_rows, num_in_rows, heads, dim, num_parts,
+                            partSize, flags, stream_v);
+}
+
+int gnna_gat_backward_drop_f32(const float *H, int64_t ld_h, const float *el, const float *er, const float *lse, const float *Y,
+                               int64_t ld_y, const float *dY, int64_t ld_dy, const int32_t *row_pointers,
+                               const int32_t *column_index, const int32_t *part_pointers, const int32_t *part2Node,
+                               int64_t num_parts, const int32_t *t_row_pointers, const int32_t *t_column_index,
+                               const int32_t *t_part_pointers, const int32_t *t_part2Node, int64_t t_num_parts,
+                               float negative_slope, float attn_drop, uint64_t rng_seed, float *dH, int64_t ld_dh, float *d_el,
+                               float *d_er, int64_t num_out_rows, int64_t num_in_rows, int heads, int dim, int partSize,
+                               unsigned flags, void *stream_v)
+{
+    (void)row_pointers;
+    (void)t_row_pointers;
+    return gat_backward_impl("gnna_gat_backward_drop_f32", true, H, ld_h, el, er, lse, Y, ld_y, dY, ld_dy, column_index,
+                             part_pointers, part2Node, num_parts, t_column_index, t_part_pointers, t_part2Node, t_num_parts,
+                             negative_slope, attn_drop, rng_seed, dH, ld_dh, d_el, d_er, num_out_rows, num_in_rows, heads, dim,
+                             partSize, flags, stream_v);
 }
 
 #pragma GCC visibility pop

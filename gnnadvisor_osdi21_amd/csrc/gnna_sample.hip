@@ -32,14 +32,6 @@ constexpr int kLongRow = 2048;        // rows with more candidate positions get 
 // the record that is read back: 8 x int64
 enum { REC_NNZ = 0, REC_SRC = 1, REC_PARTS = 2, REC_BAD_SEED = 3, REC_DUP_SEED = 4, REC_BAD_COLUMN = 5, REC_WORDS = 8 };
 
-__device__ __forceinline__ uint64_t key_of_position(uint64_t rng_seed, int64_t e)
-{
-    uint64_t z = rng_seed + 0x9E3779B97F4A7C15ull * (uint64_t)(e + 1);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 __global__ void __launch_bounds__(kBlock)
 clear_kernel(int32_t *__restrict__ words, int64_t n)
 {

@@ -31,7 +31,7 @@
 #include <mutex>
 #include <vector>
 
-#include "gnna.h"
+#include "gnna_ext.h"
 
 #define CHECK_CUDA(x) TORCH_CHECK(x.is_cuda(), #x " must be a CUDA tensor")
 #define CHECK_CONTIGUOUS(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -507,10 +507,14 @@ static int gat_heads(const torch::Tensor &H, const torch::Tensor &el, const torc
     return (int)el.size(1);
 }
 
-std::tuple<torch::Tensor, torch::Tensor>
-gat_forward(const torch::Tensor &H_in, const torch::Tensor &el, const torch::Tensor &er, const torch::Tensor &row_pointers,
-            const torch::Tensor &column_index, const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize,
-            double negative_slope)
+// (attn_drop, rng_seed) of gat_forward_drop / gat_backward_drop: the mask rule of gnna_ext.h, whose entries take every structure
+// in the rectangular form
+struct GatDrop { float attn_drop; uint64_t rng_seed; };
+
+static std::tuple<torch::Tensor, torch::Tensor>
+gat_forward_any(const torch::Tensor &H_in, const torch::Tensor &el, const torch::Tensor &er, const torch::Tensor &row_pointers,
+                const torch::Tensor &column_index, const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize,
+                double negative_slope, const GatDrop *drop)
 {
     const int heads = gat_heads(H_in, el, er);
     const int64_t n_in = H_in.size(0), n_out = el.size(0), width = H_in.size(1);
@@ -519,7 +523,13 @@ gat_forward(const torch::Tensor &H_in, const torch::Tensor &el, const torch::Ten
     at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(H.device());
     auto Y = fresh({n_out, width}, el.options()), lse = fresh({n_out, (int64_t)heads}, el.options());
     void *stream = current_stream();
-    if (n_out == n_in)
+    if (drop)
+        check_rc(gnna_gat_forward_drop_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(),
+                                           row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
+                                           part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), (float)negative_slope,
+                                           drop->attn_drop, drop->rng_seed, Y.data_ptr<float>(), width, lse.data_ptr<float>(), n_out,
+                                           n_in, heads, (int)(width / heads), part2Node.size(0), partSize, 0u, stream));
+    else if (n_out == n_in)
         check_rc(gnna_gat_forward_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(),
                                       row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
                                       part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), (float)negative_slope,
@@ -534,11 +544,28 @@ gat_forward(const torch::Tensor &H_in, const torch::Tensor &el, const torch::Ten
     return std::make_tuple(Y, lse);
 }
 
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
-gat_backward(const torch::Tensor &H_in, const torch::Tensor &el, const torch::Tensor &er, const torch::Tensor &lse,
-             const torch::Tensor &Y_in, const torch::Tensor &dY_in, const torch::Tensor &row_pointers,
-             const torch::Tensor &column_index, const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize,
-             double negative_slope, const c10::optional<std::vector<torch::Tensor>> &transposed)
+std::tuple<torch::Tensor, torch::Tensor>
+gat_forward(const torch::Tensor &H, const torch::Tensor &el, const torch::Tensor &er, const torch::Tensor &row_pointers,
+            const torch::Tensor &column_index, const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize,
+            double negative_slope)
+{
+    return gat_forward_any(H, el, er, row_pointers, column_index, part_pointers, part2Node, partSize, negative_slope, nullptr);
+}
+
+std::tuple<torch::Tensor, torch::Tensor>
+gat_forward_drop(const torch::Tensor &H, const torch::Tensor &el, const torch::Tensor &er, const torch::Tensor &row_pointers,
+                 const torch::Tensor &column_index, const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize,
+                 double negative_slope, double attn_drop, uint64_t rng_seed)
+{
+    const GatDrop drop{(float)attn_drop, rng_seed};
+    return gat_forward_any(H, el, er, row_pointers, column_index, part_pointers, part2Node, partSize, negative_slope, &drop);
+}
+
+static std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
+gat_backward_any(const torch::Tensor &H_in, const torch::Tensor &el, const torch::Tensor &er, const torch::Tensor &lse,
+                 const torch::Tensor &Y_in, const torch::Tensor &dY_in, const torch::Tensor &row_pointers,
+                 const torch::Tensor &column_index, const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize,
+                 double negative_slope, const c10::optional<std::vector<torch::Tensor>> &transposed, const GatDrop *drop)
 {
     const int heads = gat_heads(H_in, el, er);
     const int64_t n_in = H_in.size(0), n_out = el.size(0), width = H_in.size(1);
@@ -563,7 +590,16 @@ gat_backward(const torch::Tensor &H_in, const torch::Tensor &el, const torch::Te
     auto dH = fresh({n_in, width}, el.options()), d_el = fresh({n_out, (int64_t)heads}, el.options()),
          d_er = fresh({n_in, (int64_t)heads}, el.options());
     void *stream = current_stream();
-    if (!rect)
+    if (drop)       // (a symmetric graph without `transposed`: its own structure, given twice)
+        check_rc(gnna_gat_backward_drop_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(), lse.data_ptr<float>(),
+                                            Y.data_ptr<float>(), ld_of(Y), dY.data_ptr<float>(), ld_of(dY),
+                                            row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
+                                            part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), part2Node.size(0),
+                                            t_rp->data_ptr<int32_t>(), t_ci->data_ptr<int32_t>(), t_pp->data_ptr<int32_t>(),
+                                            t_p2n->data_ptr<int32_t>(), t_p2n->size(0), (float)negative_slope, drop->attn_drop,
+                                            drop->rng_seed, dH.data_ptr<float>(), width, d_el.data_ptr<float>(),
+                                            d_er.data_ptr<float>(), n_out, n_in, heads, (int)(width / heads), partSize, 0u, stream));
+    else if (!rect)
         check_rc(gnna_gat_backward_dir_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(), lse.data_ptr<float>(),
                                            Y.data_ptr<float>(), ld_of(Y), dY.data_ptr<float>(), ld_of(dY),
                                            row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
@@ -582,6 +618,27 @@ gat_backward(const torch::Tensor &H_in, const torch::Tensor &el, const torch::Te
                                             dH.data_ptr<float>(), width, d_el.data_ptr<float>(), d_er.data_ptr<float>(), n_out, n_in,
                                             heads, (int)(width / heads), partSize, 0u, stream));
     return std::make_tuple(dH, d_el, d_er);
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
+gat_backward(const torch::Tensor &H, const torch::Tensor &el, const torch::Tensor &er, const torch::Tensor &lse,
+             const torch::Tensor &Y, const torch::Tensor &dY, const torch::Tensor &row_pointers, const torch::Tensor &column_index,
+             const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize, double negative_slope,
+             const c10::optional<std::vector<torch::Tensor>> &transposed)
+{
+    return gat_backward_any(H, el, er, lse, Y, dY, row_pointers, column_index, part_pointers, part2Node, partSize, negative_slope,
+                            transposed, nullptr);
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
+gat_backward_drop(const torch::Tensor &H, const torch::Tensor &el, const torch::Tensor &er, const torch::Tensor &lse,
+                  const torch::Tensor &Y, const torch::Tensor &dY, const torch::Tensor &row_pointers, const torch::Tensor &column_index,
+                  const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize, double negative_slope,
+                  double attn_drop, uint64_t rng_seed, const c10::optional<std::vector<torch::Tensor>> &transposed)
+{
+    const GatDrop drop{(float)attn_drop, rng_seed};
+    return gat_backward_any(H, el, er, lse, Y, dY, row_pointers, column_index, part_pointers, part2Node, partSize, negative_slope,
+                            transposed, &drop);
 }
 
 // SDDMM (gnna_sddmm_ld_f32): edge_out[e] = <A[row(e)], B[column_index[e]]>; A and B may be row-strided views.
@@ -935,6 +992,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           pybind11::arg("H"), pybind11::arg("el"), pybind11::arg("er"), pybind11::arg("lse"), pybind11::arg("Y"), pybind11::arg("dY"),
           pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("part_pointers"), pybind11::arg("part2Node"),
           pybind11::arg("partSize"), pybind11::arg("negative_slope") = 0.2, pybind11::arg("transposed") = pybind11::none());
+    m.def("gat_forward_drop", &gat_forward_drop,
+          "gat_forward with attention dropout (extension; gnna_ext.h): every alpha is scaled by k(rng_seed, i, j, h) = 0 or "
+          "1 / (1 - attn_drop), a function of the seed, the two row numbers and the head that every pass recomputes; lse is that of "
+          "the undropped scores.  attn_drop in [0, 1)",
+          pybind11::arg("H"), pybind11::arg("el"), pybind11::arg("er"), pybind11::arg("row_pointers"), pybind11::arg("column_index"),
+          pybind11::arg("part_pointers"), pybind11::arg("part2Node"), pybind11::arg("partSize"), pybind11::arg("negative_slope"),
+          pybind11::arg("attn_drop"), pybind11::arg("rng_seed"));
+    m.def("gat_backward_drop", &gat_backward_drop,
+          "gradient of gat_forward_drop for the same attn_drop and rng_seed -> (dH, d_el, d_er) (extension; gnna_ext.h); `transposed` "
+          "as for gat_backward",
+          pybind11::arg("H"), pybind11::arg("el"), pybind11::arg("er"), pybind11::arg("lse"), pybind11::arg("Y"), pybind11::arg("dY"),
+          pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("part_pointers"), pybind11::arg("part2Node"),
+          pybind11::arg("partSize"), pybind11::arg("negative_slope"), pybind11::arg("attn_drop"), pybind11::arg("rng_seed"),
+          pybind11::arg("transposed") = pybind11::none());
     m.def("transpose_csr", &transpose_csr,
           "device-built CSR of A^T (extension) -> [t_row_pointers, t_column_index, t_perm]: row j lists the rows i of the edges i <- j in "
           "increasing position e, t_perm[p] = e (a stable argsort of column_index); ids outside [0, num_in_rows) are dropped",

@@ -74,6 +74,11 @@ def build_parser():
     p.add_argument('--fused_attention', default='False', **tf,
                    help="True: --model gat runs both layers on the fused attention kernels (GATConv(fused=True): alpha is made "
                         "from node-sized values where the rows are gathered, no per-edge tensor; MI355X addition)")
+    p.add_argument('--attn_drop', type=float, default=0.0,
+                   help="--model gat: dropout on the attention coefficients of both layers while training (GATConv(attn_drop=P), "
+                        "P in [0, 1); 0.6 in the GAT paper).  With --fused_attention True the mask is made inside the kernels from "
+                        "one host-drawn seed per layer and step, with --fanout too; a captured HIP graph would replay one seed and "
+                        "so one mask, one more reason --hip_graph stays refused for --model gat (MI355X addition)")
     p.add_argument('--directed', default='False', **tf,
                    help="True: the graph is directed -- every backward pass aggregates over the transposed structure, built on "
                         "the device right after the partition (False: the structure is taken to be symmetric, as the "
@@ -130,6 +135,10 @@ def main(argv=None, capture=None):
         raise SystemExit("--heads must be >= 1")
     if flag(args.fused_attention) and args.model != 'gat':
         raise SystemExit("--fused_attention True selects the fused GAT attention: run it with --model gat (got --model %s)" % args.model)
+    if args.attn_drop != 0.0 and args.model != 'gat':
+        raise SystemExit("--attn_drop drops attention coefficients: run it with --model gat (got --model %s)" % args.model)
+    if not 0.0 <= args.attn_drop < 1.0:
+        raise SystemExit("--attn_drop must be in [0, 1) (got %r)" % args.attn_drop)
     fanouts = None
     if args.fanout is not None:
         if args.model == 'gat' and not flag(args.fused_attention):
@@ -288,8 +297,9 @@ def main(argv=None, capture=None):
         class Net(torch.nn.Module):
             def __init__(self):
                 super().__init__()
-                self.conv1 = GATConv(dataset.num_features, args.hidden, heads=args.heads, concat=True, fused=fused)
-                self.conv2 = GATConv(args.hidden * args.heads, dataset.num_classes, heads=1, fused=fused)
+                self.conv1 = GATConv(dataset.num_features, args.hidden, heads=args.heads, concat=True, fused=fused,
+                                     attn_drop=args.attn_drop)
+                self.conv2 = GATConv(args.hidden * args.heads, dataset.num_classes, heads=1, fused=fused, attn_drop=args.attn_drop)
 
             def forward(self, x=None, blocks=None):
                 if blocks is not None:      # a sampled mini-batch (--fused_attention True): x holds blocks[0]'s source rows
@@ -428,6 +438,8 @@ def main(argv=None, capture=None):
             loss = train()
         torch.cuda.synchronize()
         train_time = time.perf_counter() - start_train
+        if capture is not None:
+            capture.update(final_loss=float(loss.detach()))
     else:
         # libgnna never synchronises and allocates its per-stream scratch on first use, so the dry runs
         # are made on the capture stream; after them one epoch is recorded and replayed per epoch

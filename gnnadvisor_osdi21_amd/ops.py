@@ -685,11 +685,21 @@ class GATAttention(Function):
     `inputInfo` may be a sampling.SampledBlock (gnna_gat_forward_rect_f32 / gnna_gat_backward_rect_f32): H is
     [num_src, heads * F], er [num_src, heads], el [num_dst, heads] and Y [num_dst, heads * F].  The backward runs on
     ``block.transposed()``, built at the first backward in which H, el or er needs a gradient (the forward alone builds
-    nothing); no symmetry check is made for a block."""
+    nothing); no symmetry check is made for a block.
+
+    Attention dropout: ``GATAttention.apply(H, el, er, inputInfo, negative_slope, attn_drop, rng_seed)`` scales every alpha by
+    k = 0 (with probability attn_drop) or 1 / (1 - attn_drop) after the softmax (libgnna gnna_gat_forward_drop_f32 /
+    gnna_gat_backward_drop_f32, include/gnna_ext.h).  Whether an edge i <- j of head h is kept is a function of (rng_seed, i, j, h)
+    that the forward and both backward passes recompute: there is no mask tensor, the saved tensors stay node-sized and the seed
+    is a Python int on ctx.  Duplicate edges (i, j) are kept or dropped together.  attn_drop = 0 (or the five-argument call) runs
+    the plain entries."""
 
     @staticmethod
-    def forward(ctx, H, el, er, inputInfo, negative_slope):
+    def forward(ctx, H, el, er, inputInfo, negative_slope, attn_drop=0.0, rng_seed=0):
         info = inputInfo
+        attn_drop, rng_seed = float(attn_drop), int(rng_seed) & (2 ** 64 - 1)      # (the key arithmetic is mod 2^64)
+        if not 0.0 <= attn_drop < 1.0:
+            raise ValueError(f"GATAttention: attn_drop must be in [0, 1) (got {attn_drop})")
         if _is_block(info):
             H = _block_features(H, info, "GATAttention")
             if er.dim() != 2 or er.shape[0] != info.num_src or el.dim() != 2 or el.shape[0] != info.num_dst or \
@@ -699,9 +709,12 @@ class GATAttention(Function):
             if el.dtype != torch.float32 or er.dtype != torch.float32:
                 raise TypeError(f"GATAttention on a SampledBlock: float32 scores only (got {el.dtype}, {er.dtype})")
         el, er = el.contiguous(), er.contiguous()
-        Y, lse = GNNA.gat_forward(H, el, er, info.row_pointers, info.column_index, info.partPtr, info.part2Node, info.partSize,
-                                  float(negative_slope))
-        ctx.info, ctx.negative_slope = info, float(negative_slope)
+        graph = (info.row_pointers, info.column_index, info.partPtr, info.part2Node, info.partSize, float(negative_slope))
+        if attn_drop > 0.0:
+            Y, lse = GNNA.gat_forward_drop(H, el, er, *graph, attn_drop, rng_seed)
+        else:
+            Y, lse = GNNA.gat_forward(H, el, er, *graph)
+        ctx.info, ctx.negative_slope, ctx.attn_drop, ctx.rng_seed = info, float(negative_slope), attn_drop, rng_seed
         ctx.save_for_backward(H, el, er, lse, Y)
         return Y
 
@@ -709,8 +722,9 @@ class GATAttention(Function):
     def backward(ctx, dY):
         H, el, er, lse, Y = ctx.saved_tensors
         info = ctx.info
+        rest = (None,) * (len(ctx.needs_input_grad) - 3)       # inputInfo, negative_slope (, attn_drop (, rng_seed))
         if not any(ctx.needs_input_grad[:3]):
-            return None, None, None, None, None
+            return (None, None, None) + rest
         transposed = None
         if _is_block(info) or _is_directed(info):      # (a block is never symmetric: require_symmetric is not for it)
             t = info.transposed()
@@ -718,10 +732,13 @@ class GATAttention(Function):
         else:
             from .decider import inputProperty
             inputProperty.require_symmetric(info)    # raises on a structure that is not symmetric (answer cached per column_index)
-        dH, d_el, d_er = GNNA.gat_backward(H, el, er, lse, Y, dY, info.row_pointers, info.column_index, info.partPtr,
-                                           info.part2Node, info.partSize, ctx.negative_slope, transposed)
+        graph = (info.row_pointers, info.column_index, info.partPtr, info.part2Node, info.partSize, ctx.negative_slope)
+        if ctx.attn_drop > 0.0:     # (a symmetric graph: the binding passes its structure as the transposed one)
+            dH, d_el, d_er = GNNA.gat_backward_drop(H, el, er, lse, Y, dY, *graph, ctx.attn_drop, ctx.rng_seed, transposed)
+        else:
+            dH, d_el, d_er = GNNA.gat_backward(H, el, er, lse, Y, dY, *graph, transposed)
         need = ctx.needs_input_grad
-        return (dH if need[0] else None, d_el if need[1] else None, d_er if need[2] else None, None, None)
+        return (dH if need[0] else None, d_el if need[1] else None, d_er if need[2] else None) + rest
 
 
 class GATConv(Module):
@@ -735,10 +752,22 @@ class GATConv(Module):
     With fused=True `inputInfo` may be a sampling.SampledBlock: X is [num_src, in], H = X W covers all num_src rows, er comes
     from all of H and el from H[:num_dst] (a block's destination rows are its first source rows); the result is
     [num_dst, heads * out] ([num_dst, out] with concat=False).  float32 only.  fused=False refuses a block: the composed path
-    would build per-edge tensors for every batch."""
+    would build per-edge tensors for every batch.
+    attn_drop: dropout on the attention coefficients after the softmax (the `attn_drop` of DGL's GATConv, the `dropout` of PyG's),
+    active only in training mode; ``model.eval()`` or attn_drop = 0 takes exactly the path without it.  fused=True: the mask is a
+    function of (seed, destination row, source row, head) made inside the kernels (GATAttention); one 63-bit seed per forward,
+    drawn on the host from torch's CPU default generator (no device synchronisation; ``torch.manual_seed`` reproduces a run)
+    unless ``forward(..., rng_seed=...)`` gives it, and kept as ``self.last_rng_seed``.  fused=False:
+    ``torch.nn.functional.dropout`` on alpha -- the same distribution from another generator (torch's device generator, one draw
+    per edge position), so the two paths drop different edges for the same seed, and only the fused one drops duplicate edges
+    together."""
 
-    def __init__(self, input_dim, output_dim, heads=1, concat=True, negative_slope=0.2, fused=False):
+    def __init__(self, input_dim, output_dim, heads=1, concat=True, negative_slope=0.2, fused=False, attn_drop=0.0):
         super().__init__()
+        self.attn_drop = float(attn_drop)
+        if not 0.0 <= self.attn_drop < 1.0:
+            raise ValueError(f"GATConv: attn_drop must be in [0, 1) (got {attn_drop})")
+        self.last_rng_seed = None
         self.heads, self.out_dim, self.concat, self.negative_slope = int(heads), int(output_dim), bool(concat), float(negative_slope)
         self.fused = bool(fused)
         self.weights = Parameter(torch.empty(input_dim, self.heads * self.out_dim))
@@ -753,8 +782,9 @@ class GATConv(Module):
             self.att_l.uniform_(-bound, bound)
             self.att_r.uniform_(-bound, bound)
 
-    def forward(self, X, inputInfo):
+    def forward(self, X, inputInfo, rng_seed=None):
         block = _is_block(inputInfo)
+        drop = self.training and self.attn_drop > 0.0
         if block:
             if not self.fused:
                 _refuse_block(inputInfo, "GATConv(fused=False)")
@@ -767,12 +797,19 @@ class GATConv(Module):
         n = inputInfo.num_dst if block else X.shape[0]      # rows of the result
         el = ((Hh[:n] if block else Hh) * self.att_l).sum(-1)      # [N, heads] ([num_dst, heads]): destination side
         er = (Hh * self.att_r).sum(-1)          # [N, heads] ([num_src, heads]): source side
-        if self.fused:
+        if self.fused and drop:
+            if rng_seed is None:
+                rng_seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())       # (a CPU tensor: no device synchronisation)
+            self.last_rng_seed = int(rng_seed)
+            Y = GATAttention.apply(H, el, er, inputInfo, self.negative_slope, self.attn_drop, self.last_rng_seed)
+        elif self.fused:
             Y = GATAttention.apply(H, el, er, inputInfo, self.negative_slope)
         else:
             rows, ci = inputInfo.edge_rows(), inputInfo.column_index
             s = torch.nn.functional.leaky_relu(el.index_select(0, rows) + er.index_select(0, ci), self.negative_slope)
             alpha = EdgeSoftmax.apply(s.t().contiguous(), inputInfo.row_pointers)      # [heads, nnz]
+            if drop:
+                alpha = torch.nn.functional.dropout(alpha, self.attn_drop, training=True)
             Y = EdgeWeightedAggregate.apply(H, alpha, inputInfo)
         if self.concat or self.heads == 1:
             return Y
