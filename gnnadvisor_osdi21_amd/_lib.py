@@ -107,9 +107,21 @@ EXT_SIGNATURES = {
     "gnna_gat_forward_drop_f32": (i, _GAT_FWD[:9] + [f, u64] + _GAT_FWD[9:] + [i64, i64, i, i, i64, i, u, p]),     # attn_drop, rng_seed after the slope
     "gnna_gat_backward_drop_f32": (i, _GAT_BWD + _GAT_BOTH[:11] + [f, u64] + _GAT_BOTH[11:] + [i64, i64, i, i, i, u, p]),
 }
+# fused GATv2 attention (include/gnna_gatv2.h): a third table
+_GRAPH_T = ([p] * 4 + [i64]) * 2                         # the graph and its transpose, each with its num_parts
+GATV2_SIGNATURES = {
+    # Hs, ld_hs, Hd, ld_hd, att, the graph, slope, attn_drop, rng_seed, out, ld_out, lse, sizes
+    "gnna_gatv2_forward_f32": (i, [p, i64, p, i64, p] + [p] * 4 + [f, f, u64, p, i64, p, i64, i64, i, i, i64, i, u, p]),
+    # Hs, ld_hs, Hd, ld_hd, att, lse, Y, ld_y, dY, ld_dy, both structures, slope, attn_drop, rng_seed, dHs, ld_dhs, dHd, ld_dhd, d_att, sizes
+    "gnna_gatv2_backward_f32": (i, [p, i64, p, i64, p, p, p, i64, p, i64] + _GRAPH_T + [f, f, u64, p, i64, p, i64, p,
+                                                                                       i64, i64, i, i, i, u, p]),
+}
 del p, i, i64, u, u64, f, s, pd, pi, pi64
 EXPORTS = tuple(SIGNATURES)
 EXT_EXPORTS = tuple(EXT_SIGNATURES)
+GATV2_EXPORTS = tuple(GATV2_SIGNATURES)
+# every table load() applies (an extension of the surface adds its table here)
+SIGNATURE_TABLES = (SIGNATURES, EXT_SIGNATURES, GATV2_SIGNATURES)
 
 
 def load() -> ctypes.CDLL:
@@ -122,11 +134,12 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -m gnnadvisor_osdi21_amd.build`). There is no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in (*SIGNATURES.items(), *EXT_SIGNATURES.items()):
-        fn = getattr(L, name)
-        fn.restype = restype
-        if argtypes is not None:
-            fn.argtypes = argtypes
+    for table in SIGNATURE_TABLES:
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(L, name)
+            fn.restype = restype
+            if argtypes is not None:
+                fn.argtypes = argtypes
     _lib = L
     return L
 
@@ -849,6 +862,80 @@ def _gat_backward(drop, H, el, er, lse, Y, dY, row_pointers, column_index, part_
     else:
         _call(H.device, "gnna_gat_backward_f32", *head, *outs, n_out, heads, width // heads, part2Node.numel(), int(partSize), 0)
     return dH, d_el, d_er
+
+
+def _gatv2_sizes(Hs, Hd, att, row_pointers):
+    """(Hs's pointer, ld_hs, Hd's pointer, ld_hd, num_out_rows, num_in_rows, width, heads) of a GATv2 attention call, taken from
+    the tensors: num_in_rows = Hs.shape[0], num_out_rows = Hd.shape[0] = row_pointers.numel() - 1, heads = att.shape[0]."""
+    sp, n_in, width, ld_hs = _rows_view(Hs, "Hs")
+    dp, n_out, width_d, ld_hd = _rows_view(Hd, "Hd")
+    assert width_d == width and Hd.device == Hs.device, "Hs must be [num_in_rows, heads * dim] and Hd [num_out_rows, heads * dim]"
+    assert row_pointers.dim() == 1 and row_pointers.numel() == n_out + 1, \
+        f"row_pointers must be [num_out_rows + 1] with num_out_rows = Hd.shape[0] = {n_out} (got {row_pointers.numel()} entries)"
+    assert att.dtype == torch.float32 and att.dim() == 2 and att.is_contiguous() and att.device == Hs.device \
+        and att.shape[0] >= 1 and att.numel() == width, "att must be a contiguous float32 [heads, dim] tensor with heads * dim = Hs.shape[1]"
+    return sp, ld_hs, dp, ld_hd, n_out, n_in, width, att.shape[0]
+
+
+def gatv2_forward(Hs, Hd, att, row_pointers, column_index, part_pointers, part2Node, partSize=32, negative_slope=0.2, attn_drop=0.0,
+                  rng_seed=0, out=None, lse=None, relu=False):
+    """gnna_gatv2_forward_f32 (include/gnna_gatv2.h): fused multi-head GATv2 attention.  Hs [num_in_rows, heads * dim] (source
+    side and message), Hd [num_out_rows, heads * dim] (destination side), att [heads, dim] -> (out, lse) with
+    z = sum_d att[h, d] * leaky_relu(Hs[j, h, d] + Hd[i, h, d]), out[i, h] = sum_e exp(z - lse[i, h]) * k * Hs[col(e), h]; k is the
+    dropout factor of gat_forward_drop (1 at attn_drop = 0).  No per-edge tensor.  `Hs`, `Hd` and `out` may be row-strided views
+    (stride(1) == 1); Hs and Hd may be the same tensor."""
+    _need_device(Hs, "GATv2 attention")
+    sp, ld_hs, dp, ld_hd, n_out, n_in, width, heads = _gatv2_sizes(Hs, Hd, att, row_pointers)
+    if out is None:
+        out = _fresh_output((n_out, width), Hs.device)
+    if lse is None:
+        lse = _fresh_output((n_out, heads), Hs.device)
+    op_, n_o, width_o, ld_out = _rows_view(out, "out")
+    assert n_o == n_out and width_o == width and _node_heads(lse, n_out, "lse") == heads
+    _call(Hs.device, "gnna_gatv2_forward_f32", sp, ld_hs, dp, ld_hd, att.data_ptr(), row_pointers.data_ptr(), column_index.data_ptr(),
+          part_pointers.data_ptr(), part2Node.data_ptr(), float(negative_slope), float(attn_drop), int(rng_seed), op_, ld_out,
+          lse.data_ptr(), n_out, n_in, heads, width // heads, part2Node.numel(), int(partSize), _flags(relu=relu))
+    return out, lse
+
+
+def gatv2_backward(Hs, Hd, att, lse, Y, dY, row_pointers, column_index, part_pointers, part2Node, partSize=32, negative_slope=0.2,
+                   attn_drop=0.0, rng_seed=0, transposed=None, dHs=None, dHd=None, d_att=None):
+    """gnna_gatv2_backward_f32: (dHs, dHd, d_att) of gatv2_forward for the gradient dY of its output Y (same attn_drop and
+    rng_seed).  transposed = (t_row_pointers, t_column_index, t_part_pointers, t_part2Node) at the same partSize; without it (a
+    square graph whose structure is symmetric, not checked here) the graph's own structure is passed as the transposed one."""
+    _need_device(Hs, "GATv2 attention")
+    sp, ld_hs, dp, ld_hd, n_out, n_in, width, heads = _gatv2_sizes(Hs, Hd, att, row_pointers)
+    yp, n_y, width_y, ld_y = _rows_view(Y, "Y")
+    gp, n_g, width_g, ld_g = _rows_view(dY, "dY")
+    assert _node_heads(lse, n_out, "lse") == heads
+    assert (n_y, width_y) == (n_out, width) and (n_g, width_g) == (n_out, width), "Y and dY must be [num_out_rows, heads * dim]"
+    if n_out != n_in and transposed is None:
+        raise GnnaError(f"GATv2 attention backward on a rectangular structure ({n_out} destination rows, {n_in} source rows) needs "
+                        "`transposed`: a rectangular structure is never its own transpose")
+    if transposed is None:
+        transposed = (row_pointers, column_index, part_pointers, part2Node)
+    t_rp, t_ci, t_pp, t_p2n = transposed
+    for t in (column_index, part_pointers, part2Node, t_rp, t_ci, t_pp, t_p2n):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.device == Hs.device, \
+            "the graph and its transpose must be contiguous int32 tensors on Hs's device"
+    assert t_rp.numel() == n_in + 1 and t_pp.numel() == t_p2n.numel() + 1, \
+        "transposed: [num_in_rows + 1] row pointers, [P + 1] / [P] partition"
+    if dHs is None:
+        dHs = _fresh_output((n_in, width), Hs.device)
+    if dHd is None:
+        dHd = _fresh_output((n_out, width), Hs.device)
+    if d_att is None:
+        d_att = _fresh_output(tuple(att.shape), Hs.device)
+    sgp, n_s, width_s, ld_dhs = _rows_view(dHs, "dHs")
+    dgp, n_d, width_dd, ld_dhd = _rows_view(dHd, "dHd")
+    assert (n_s, width_s) == (n_in, width) and (n_d, width_dd) == (n_out, width), "dHs / dHd must have the shapes of Hs / Hd"
+    assert d_att.dtype == torch.float32 and d_att.is_contiguous() and d_att.numel() == width and d_att.device == Hs.device
+    _call(Hs.device, "gnna_gatv2_backward_f32", sp, ld_hs, dp, ld_hd, att.data_ptr(), lse.data_ptr(), yp, ld_y, gp, ld_g,
+          row_pointers.data_ptr(), column_index.data_ptr(), part_pointers.data_ptr(), part2Node.data_ptr(), part2Node.numel(),
+          t_rp.data_ptr(), t_ci.data_ptr(), t_pp.data_ptr(), t_p2n.data_ptr(), t_p2n.numel(), float(negative_slope),
+          float(attn_drop), int(rng_seed), sgp, ld_dhs, dgp, ld_dhd, d_att.data_ptr(), n_out, n_in, heads, width // heads,
+          int(partSize), 0)
+    return dHs, dHd, d_att
 
 
 def _device_i32(t, what):

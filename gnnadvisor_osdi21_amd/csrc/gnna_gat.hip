@@ -30,7 +30,8 @@
 // accepts, no validation pass), so the outputs are zero-filled first and there is no deterministic schedule for these passes.
 //
 // Attention dropout (the DROP instances of gat_pull_kernel): alpha' = alpha * k after the softmax, k = 0 or 1 / (1 - attn_drop)
-// decided by a splitmix64 key of (rng_seed, i, j, h) that every pass computes beside alpha (gnna_ext.h has the rule).  lse and
+// decided by a splitmix64 key of (rng_seed, i, j, h) that every pass computes beside alpha (gnna_ext.h has the rule; the key is
+// key_of_position(rng_seed, u) of gnna_device.h, packed and compared by drop_factor of gnna_gat_common.h).  lse and
 // the pack pass do not change: Y = sum alpha' H, so c = <dY, Y> = sum_e alpha' dalpha is still the row's constant, and
 // dz = alpha * (k * dalpha - c) * (z > 0 ? 1 : negative_slope), dH[j] = sum alpha * k * dY[i].
 //
@@ -43,90 +44,18 @@
 //     gat_pull_kernel<BWD_SRC>     num_in_rows  (er, H, dH, d_er)               num_out_rows (dY, pack)     [transposed structure]
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cmath>
-#include <cstdint>
-
 #include "gnna_ext.h"
-#include "gnna_device.h"
-#include "gnna_internal.h"
+#include "gnna_gat_common.h"
 
 namespace gnna {
 namespace {
 
-typedef VecOf<4>::T VT;
-typedef VecOf<4>::M MT;
+using namespace gat;      // the folds, the online (max, sum), the dropout factor and the checks: gnna_gat_common.h
 
 constexpr int kSlotGatPack = 6;   // library scratch: (el, lse, c, 0) per (node, head) of a backward call
-constexpr int kLongIters = 8;     // lse pass: a row of more than SEG * 4 * kLongIters edges goes to the whole block
-constexpr int kMaxDim = 256;      // floats per head (LPH <= 64)
 
 enum { SIDE_FWD = 0, SIDE_BWD_DST = 1, SIDE_BWD_SRC = 2 };
-
-__device__ __forceinline__ float leaky(float z, float slope) { return z > 0.f ? z : z * slope; }
-
-// the first n4 (<= 4) floats at p, the others 0
-__device__ __forceinline__ VT load_piece(const float *__restrict__ p, int n4)
-{
-    if (n4 >= 4) return *reinterpret_cast<const MT *>(p);
-    VT v = (VT)(0.f);
-    if (n4 > 0) v[0] = p[0];
-    if (n4 > 1) v[1] = p[1];
-    if (n4 > 2) v[2] = p[2];
-    return v;
-}
-
-// sum over the LPH consecutive lanes of a head; result in every lane of the head
-template <int LPH>
-__device__ __forceinline__ float head_sum(float v)
-{
-    if constexpr (LPH == 1) return v;
-    else if constexpr (LPH == 2) return v + dpp_move<0xB1>(v);      // quad_perm [1,0,3,2]
-    else return lane_group_sum<LPH>(v);
-}
-
-// sum over the 64 / LPR lanes that share lane % LPR (the partial rows of a wavefront); result in every lane
-template <int LPR>
-__device__ __forceinline__ float slots_sum(float v)
-{
-    v = slot_reduce<LPR>(v);                                        // strides 32 .. 4
-    if constexpr (LPR <= 2) v += dpp_move<0x4E>(v);                 // quad_perm [2,3,0,1]: stride 2
-    if constexpr (LPR <= 1) v += dpp_move<0xB1>(v);                 // quad_perm [1,0,3,2]: stride 1
-    return v;
-}
-
 // ---- (a) lse[i, h] ------------------------------------------------------------------------------------------------------
-
-struct MaxSum { float m, l; };
-
-__device__ __forceinline__ MaxSum ms_merge(MaxSum a, MaxSum b)
-{
-    const float m = fmaxf(a.m, b.m);
-    if (m == -INFINITY) return a;
-    const float fa = a.m == -INFINITY ? 0.f : expf(a.m - m);
-    const float fb = b.m == -INFINITY ? 0.f : expf(b.m - m);
-    return MaxSum{m, a.l * fa + b.l * fb};
-}
-
-// four scores enter together (-inf: no edge): one rescale of the running sum per step
-__device__ __forceinline__ MaxSum ms_add4(MaxSum a, const float x[4])
-{
-    const float mx = fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3]));
-    const float m = fmaxf(a.m, mx);
-    if (m == -INFINITY) return a;
-    float l = a.m == -INFINITY ? 0.f : a.l * expf(a.m - m);
-#pragma unroll
-    for (int k = 0; k < 4; k++) l += x[k] == -INFINITY ? 0.f : expf(x[k] - m);
-    return MaxSum{m, l};
-}
-
-// butterfly over the `w` lanes of a segment (a power of two <= 64)
-__device__ __forceinline__ MaxSum seg_reduce(MaxSum v, int w)
-{
-    for (int d = w >> 1; d > 0; d >>= 1) v = ms_merge(v, MaxSum{__shfl_xor(v.m, d), __shfl_xor(v.l, d)});
-    return v;
-}
-
 // One row [beg, end) swept by `nl` lanes (this one: index t), four edges per lane and step, HB heads from hb0 on.
 template <int HB>
 __device__ __forceinline__ void lse_row(const float *__restrict__ el_row, const float *__restrict__ er,
@@ -159,8 +88,6 @@ __device__ __forceinline__ void lse_row(const float *__restrict__ el_row, const 
         }
     }
 }
-
-__device__ __forceinline__ float lse_of(MaxSum v) { return v.m == -INFINITY ? 0.f : v.m + logf(v.l); }
 
 // blockIdx.y: block of HB heads.  seg: lanes per row (4 .. 64, a power of two).  N rows (el, lse), ids < M (er).
 template <int HB>
@@ -263,8 +190,7 @@ struct GatArgs {
 // numbers and the head alone, so the three passes agree without an edge position, a perm array or a reverse-edge map.
 __device__ __forceinline__ float drop_factor(const GatArgs &p, uint32_t i, uint32_t j, int h)
 {
-    const uint64_t u = ((uint64_t)i << 35) | ((uint64_t)j << 6) | (uint64_t)(uint32_t)h;
-    return (uint32_t)(key_of_position(p.rng_seed, u) >> 32) >= p.drop_thr ? p.keep_scale : 0.f;
+    return gat::drop_factor(p.rng_seed, p.drop_thr, p.keep_scale, i, j, h);
 }
 
 // DROP: attention dropout after the softmax -- every edge's alpha is scaled by k = drop_factor where it is accumulated, and
@@ -455,43 +381,12 @@ int launch_lse(hipStream_t stream, const float *el, const float *er, const int32
     return launch_ok("GAT lse launch");
 }
 
-// what both entry points check alike.  rect: the rectangular entries name both row counts in their messages.
-int check_common(const char *what, bool rect, int64_t num_out_rows, int64_t num_in_rows, int heads, int dim, int64_t num_parts,
-                 int partSize, unsigned flags, unsigned allowed_flags)
-{
-    if (flags & GNNA_ACCUMULATE) return fail(GNNA_ERR_UNSUPPORTED, "%s: GNNA_ACCUMULATE is not supported", what);
-    if (flags & ~allowed_flags) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", what, flags);
-    if (num_out_rows < 0 || num_in_rows < 0 || num_parts < 0 || heads < 1 || dim < 1) {
-        if (rect)
-            return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: bad size (num_out_rows=%lld num_in_rows=%lld heads=%d dim=%d num_parts=%lld)",
-                        what, (long long)num_out_rows, (long long)num_in_rows, heads, dim, (long long)num_parts);
-        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: bad size (num_nodes=%lld heads=%d dim=%d num_parts=%lld)", what,
-                    (long long)num_out_rows, heads, dim, (long long)num_parts);
-    }
-    if (partSize <= 0) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: partSize must be positive (got %d)", what, partSize);
-    const int64_t most = std::max(num_out_rows, num_in_rows);
-    if (most >= ((int64_t)1 << 29))
-        return fail(GNNA_ERR_UNSUPPORTED, "%s: %lld rows in one call (at most 536870911): shard the rows", what, (long long)most);
-    if (dim > kMaxDim) return fail(GNNA_ERR_UNSUPPORTED, "%s: at most %d floats per head (got %d)", what, kMaxDim, dim);
-    if (heads > 64) return fail(GNNA_ERR_UNSUPPORTED, "%s: at most 64 heads (got %d)", what, heads);
-    // the gathered rows are added with float atomics: the order of the additions is not fixed
-    return deterministic_refused(what, "its rows are added with float atomics");
-}
-
-// attn_drop of the drop entries: [0, 1), refused before any device work (a NaN fails the first comparison)
-int check_drop(const char *what, float attn_drop)
-{
-    if (!(attn_drop >= 0.f) || attn_drop >= 1.f)
-        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: attn_drop must be in [0, 1) (got %g)", what, (double)attn_drop);
-    return GNNA_OK;
-}
-
 // thr = (uint32) floor((double)attn_drop * 2^32) and k = 1 / (1 - attn_drop) in fp32, as gnna_ext.h states them
 void set_drop(GatArgs *a, float attn_drop, uint64_t rng_seed)
 {
     a->rng_seed = rng_seed;
-    a->drop_thr = (uint32_t)std::floor((double)attn_drop * 4294967296.0);
-    a->keep_scale = 1.0f / (1.0f - attn_drop);
+    a->drop_thr = drop_threshold(attn_drop);
+    a->keep_scale = drop_keep_scale(attn_drop);
 }
 
 // The forward of all entries: num_out_rows rows (el, lse, out) gather from num_in_rows rows (H, er).

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "gnna_ext.h"
+#include "gnna_gatv2.h"
 
 #define CHECK_CUDA(x) TORCH_CHECK(x.is_cuda(), #x " must be a CUDA tensor")
 #define CHECK_CONTIGUOUS(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -641,6 +642,76 @@ gat_backward_drop(const torch::Tensor &H, const torch::Tensor &el, const torch::
                             transposed, &drop);
 }
 
+// Fused GATv2 attention (gnna_gatv2_forward_f32 / gnna_gatv2_backward_f32, gnna_gatv2.h): Hs [num_in_rows, heads * dim] (the source
+// side and the message), Hd [num_out_rows, heads * dim] with num_out_rows = row_pointers.numel() - 1, att [heads, dim].  One
+// (rectangular) entry for every structure; attn_drop = 0 is the plain function.  Hs and Hd may be the same tensor.
+static int gatv2_heads(const torch::Tensor &Hs, const torch::Tensor &Hd, const torch::Tensor &att)
+{
+    check_floats(att, "att");
+    TORCH_CHECK(Hs.dim() == 2 && Hd.dim() == 2 && Hs.size(1) == Hd.size(1), "Hs must be [num_in_rows, heads * dim] and Hd [num_out_rows, heads * dim]");
+    TORCH_CHECK(att.dim() == 2 && att.size(0) >= 1 && att.size(1) >= 1 && att.size(0) * att.size(1) == Hs.size(1),
+                "att must be [heads, dim] with heads * dim = Hs.size(1)");
+    TORCH_CHECK(Hd.device() == Hs.device() && att.device() == Hs.device(), "Hs, Hd and att must be on one device");
+    return (int)att.size(0);
+}
+
+std::tuple<torch::Tensor, torch::Tensor>
+gatv2_forward(const torch::Tensor &Hs_in, const torch::Tensor &Hd_in, const torch::Tensor &att, const torch::Tensor &row_pointers,
+              const torch::Tensor &column_index, const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize,
+              double negative_slope, double attn_drop, uint64_t rng_seed)
+{
+    const int heads = gatv2_heads(Hs_in, Hd_in, att);
+    const int64_t n_in = Hs_in.size(0), n_out = Hd_in.size(0), width = Hs_in.size(1);
+    const torch::Tensor Hs = gat_rows(Hs_in, "Hs", n_in, width), Hd = gat_rows(Hd_in, "Hd", n_out, width);
+    gat_check_graph(Hs, n_out, row_pointers, column_index, part_pointers, part2Node);
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(Hs.device());
+    auto Y = fresh({n_out, width}, att.options()), lse = fresh({n_out, (int64_t)heads}, att.options());
+    check_rc(gnna_gatv2_forward_f32(Hs.data_ptr<float>(), ld_of(Hs), Hd.data_ptr<float>(), ld_of(Hd), att.data_ptr<float>(),
+                                    row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
+                                    part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), (float)negative_slope,
+                                    (float)attn_drop, rng_seed, Y.data_ptr<float>(), width, lse.data_ptr<float>(), n_out, n_in, heads,
+                                    (int)(width / heads), part2Node.size(0), partSize, 0u, current_stream()));
+    return std::make_tuple(Y, lse);
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
+gatv2_backward(const torch::Tensor &Hs_in, const torch::Tensor &Hd_in, const torch::Tensor &att, const torch::Tensor &lse,
+               const torch::Tensor &Y_in, const torch::Tensor &dY_in, const torch::Tensor &row_pointers,
+               const torch::Tensor &column_index, const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize,
+               double negative_slope, double attn_drop, uint64_t rng_seed,
+               const c10::optional<std::vector<torch::Tensor>> &transposed)
+{
+    const int heads = gatv2_heads(Hs_in, Hd_in, att);
+    const int64_t n_in = Hs_in.size(0), n_out = Hd_in.size(0), width = Hs_in.size(1);
+    TORCH_CHECK(n_out == n_in || transposed.has_value(), "gatv2_backward on a rectangular structure (", n_out, " destination rows, ",
+                n_in, " source rows) needs `transposed`: a rectangular structure is never its own transpose");
+    const torch::Tensor Hs = gat_rows(Hs_in, "Hs", n_in, width), Hd = gat_rows(Hd_in, "Hd", n_out, width),
+                        Y = gat_rows(Y_in, "Y", n_out, width), dY = gat_rows(dY_in, "dY", n_out, width);
+    // (a symmetric graph without `transposed`: its own structure, given twice)
+    const torch::Tensor *t_rp = &row_pointers, *t_ci = &column_index, *t_pp = &part_pointers, *t_p2n = &part2Node;
+    if (transposed.has_value()) {
+        TORCH_CHECK(transposed->size() == 4, "transposed must be (t_row_pointers, t_column_index, t_part_pointers, t_part2Node)");
+        t_rp = &(*transposed)[0]; t_ci = &(*transposed)[1]; t_pp = &(*transposed)[2]; t_p2n = &(*transposed)[3];
+        gat_check_graph(Hs, n_in, *t_rp, *t_ci, *t_pp, *t_p2n);
+    }
+    check_floats(lse, "lse");
+    TORCH_CHECK(lse.dim() == 2 && lse.size(0) == n_out && lse.size(1) == heads && lse.device() == Hs.device(),
+                "lse must be [num_out_rows, heads] on Hs's device");
+    TORCH_CHECK(Y.device() == Hs.device() && dY.device() == Hs.device(), "Hs, Y and dY must be on one device");
+    gat_check_graph(Hs, n_out, row_pointers, column_index, part_pointers, part2Node);
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(Hs.device());
+    auto dHs = fresh({n_in, width}, att.options()), dHd = fresh({n_out, width}, att.options()), d_att = fresh(att.sizes(), att.options());
+    check_rc(gnna_gatv2_backward_f32(Hs.data_ptr<float>(), ld_of(Hs), Hd.data_ptr<float>(), ld_of(Hd), att.data_ptr<float>(),
+                                     lse.data_ptr<float>(), Y.data_ptr<float>(), ld_of(Y), dY.data_ptr<float>(), ld_of(dY),
+                                     row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
+                                     part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), part2Node.size(0),
+                                     t_rp->data_ptr<int32_t>(), t_ci->data_ptr<int32_t>(), t_pp->data_ptr<int32_t>(),
+                                     t_p2n->data_ptr<int32_t>(), t_p2n->size(0), (float)negative_slope, (float)attn_drop, rng_seed,
+                                     dHs.data_ptr<float>(), width, dHd.data_ptr<float>(), width, d_att.data_ptr<float>(), n_out, n_in,
+                                     heads, (int)(width / heads), partSize, 0u, current_stream()));
+    return std::make_tuple(dHs, dHd, d_att);
+}
+
 // SDDMM (gnna_sddmm_ld_f32): edge_out[e] = <A[row(e)], B[column_index[e]]>; A and B may be row-strided views.
 torch::Tensor sddmm(const torch::Tensor &A, const torch::Tensor &B, const torch::Tensor &column_index,
                     const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize)
@@ -1005,6 +1076,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           pybind11::arg("H"), pybind11::arg("el"), pybind11::arg("er"), pybind11::arg("lse"), pybind11::arg("Y"), pybind11::arg("dY"),
           pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("part_pointers"), pybind11::arg("part2Node"),
           pybind11::arg("partSize"), pybind11::arg("negative_slope"), pybind11::arg("attn_drop"), pybind11::arg("rng_seed"),
+          pybind11::arg("transposed") = pybind11::none());
+    m.def("gatv2_forward", &gatv2_forward,
+          "fused multi-head GATv2 attention -> (Y, lse) (extension; gnna_gatv2.h): z = sum_d att[h, d] * leaky_relu(Hs[col(e), h, d] + "
+          "Hd[i, h, d]), Y[i, h] = sum_e exp(z - lse[i, h]) * k * Hs[col(e), h] with the dropout factor k of gat_forward_drop (1 at "
+          "attn_drop = 0).  Hs [num_in_rows, heads * dim], Hd [num_out_rows, heads * dim], att [heads, dim], row_pointers [num_out_rows + 1]",
+          pybind11::arg("Hs"), pybind11::arg("Hd"), pybind11::arg("att"), pybind11::arg("row_pointers"), pybind11::arg("column_index"),
+          pybind11::arg("part_pointers"), pybind11::arg("part2Node"), pybind11::arg("partSize"), pybind11::arg("negative_slope") = 0.2,
+          pybind11::arg("attn_drop") = 0.0, pybind11::arg("rng_seed") = 0);
+    m.def("gatv2_backward", &gatv2_backward,
+          "gradient of gatv2_forward for the same attn_drop and rng_seed -> (dHs, dHd, d_att) (extension; gnna_gatv2.h); `transposed` "
+          "as for gat_backward",
+          pybind11::arg("Hs"), pybind11::arg("Hd"), pybind11::arg("att"), pybind11::arg("lse"), pybind11::arg("Y"), pybind11::arg("dY"),
+          pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("part_pointers"), pybind11::arg("part2Node"),
+          pybind11::arg("partSize"), pybind11::arg("negative_slope") = 0.2, pybind11::arg("attn_drop") = 0.0, pybind11::arg("rng_seed") = 0,
           pybind11::arg("transposed") = pybind11::none());
     m.def("transpose_csr", &transpose_csr,
           "device-built CSR of A^T (extension) -> [t_row_pointers, t_column_index, t_perm]: row j lists the rows i of the edges i <- j in "

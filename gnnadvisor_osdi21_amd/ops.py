@@ -814,3 +814,138 @@ class GATConv(Module):
         if self.concat or self.heads == 1:
             return Y
         return Y.view(n, self.heads, self.out_dim).mean(1)
+
+
+class GATv2Attention(Function):
+    """The attention of a GATv2 layer ("dynamic" attention, Brody et al.) in one fused call per direction (libgnna
+    gnna_gatv2_forward_f32 / gnna_gatv2_backward_f32, include/gnna_gatv2.h):
+    ``GATv2Attention.apply(Hs, Hd, att, inputInfo, negative_slope, attn_drop=0.0, rng_seed=0) -> Y`` with Hs [N, heads * F] (the
+    source side and the message), Hd [N, heads * F] (the destination side), att [heads, F] and
+    Y[i, h] = sum_e alpha(e, h) k Hs[col(e), h], alpha = softmax over row i of z = sum_d att[h, d] leaky_relu(Hs[col(e), h, d] +
+    Hd[i, h, d]).  The non-linearity sits inside the dot product, so the score cannot be made from two node-sized scalars as in
+    GATAttention: every kernel recomputes z from the row it gathers and the row's own Hd piece.  No [nnz] tensor is made, saved or
+    cached (saved: Hs, Hd, att, lse, Y -- all node-sized).  Returns (dHs, dHd, d_att).  Hs and Hd may be the same tensor (shared
+    weights): autograd adds the two gradients.
+
+    `inputInfo` is a graph, a ``directed`` graph or a sampling.SampledBlock (Hs [num_src, heads * F], Hd [num_dst, heads * F],
+    Y [num_dst, heads * F]); ``transposed()`` / ``require_symmetric`` are handled exactly as in GATAttention.  attn_drop / rng_seed:
+    the mask rule of GATAttention (include/gnna_ext.h), recomputed in every pass; attn_drop = 0 is the plain function."""
+
+    @staticmethod
+    def forward(ctx, Hs, Hd, att, inputInfo, negative_slope, attn_drop=0.0, rng_seed=0):
+        info = inputInfo
+        attn_drop, rng_seed = float(attn_drop), int(rng_seed) & (2 ** 64 - 1)      # (the key arithmetic is mod 2^64)
+        if not 0.0 <= attn_drop < 1.0:
+            raise ValueError(f"GATv2Attention: attn_drop must be in [0, 1) (got {attn_drop})")
+        for t, name in ((Hs, "Hs"), (Hd, "Hd"), (att, "att")):
+            if t.dtype != torch.float32:
+                raise TypeError(f"GATv2Attention: float32 only (got {name}: {t.dtype})")
+        if att.dim() != 2 or Hs.dim() != 2 or Hd.dim() != 2 or Hs.shape[1] != Hd.shape[1] or att.numel() != Hs.shape[1]:
+            raise ValueError(f"GATv2Attention: Hs [num_src, heads * F], Hd [num_dst, heads * F] and att [heads, F] expected (got "
+                             f"{tuple(Hs.shape)}, {tuple(Hd.shape)} and {tuple(att.shape)})")
+        if _is_block(info):
+            Hs = _block_features(Hs, info, "GATv2Attention")
+            if Hd.shape[0] != info.num_dst:
+                raise ValueError(f"GATv2Attention on a SampledBlock: Hd must be [num_dst = {info.num_dst}, heads * F] "
+                                 f"(got {tuple(Hd.shape)})")
+        att = att.contiguous()
+        Y, lse = GNNA.gatv2_forward(Hs, Hd, att, info.row_pointers, info.column_index, info.partPtr, info.part2Node, info.partSize,
+                                    float(negative_slope), attn_drop, rng_seed)
+        ctx.info, ctx.negative_slope, ctx.attn_drop, ctx.rng_seed = info, float(negative_slope), attn_drop, rng_seed
+        ctx.save_for_backward(Hs, Hd, att, lse, Y)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        Hs, Hd, att, lse, Y = ctx.saved_tensors
+        info = ctx.info
+        rest = (None,) * (len(ctx.needs_input_grad) - 3)       # inputInfo, negative_slope (, attn_drop (, rng_seed))
+        if not any(ctx.needs_input_grad[:3]):
+            return (None, None, None) + rest
+        transposed = None
+        if _is_block(info) or _is_directed(info):      # (a block is never symmetric: require_symmetric is not for it)
+            t = info.transposed()
+            transposed = [t.row_pointers, t.column_index, t.partPtr, t.part2Node]
+        else:
+            from .decider import inputProperty
+            inputProperty.require_symmetric(info)    # raises on a structure that is not symmetric (answer cached per column_index)
+        dHs, dHd, d_att = GNNA.gatv2_backward(Hs, Hd, att, lse, Y, dY, info.row_pointers, info.column_index, info.partPtr,
+                                              info.part2Node, info.partSize, ctx.negative_slope, ctx.attn_drop, ctx.rng_seed,
+                                              transposed)
+        need = ctx.needs_input_grad
+        return (dHs if need[0] else None, dHd if need[1] else None, d_att if need[2] else None) + rest
+
+
+class GATv2Conv(Module):
+    """GATv2 ("How Attentive are Graph Attention Networks?"): Hs = X W_l, Hd = X W_r; per head h,
+    z[e] = <att[h], leaky_relu(Hs_h[col(e)] + Hd_h[row(e)])>, alpha = edge softmax of z over every row, Y_h = A_alpha Hs_h.  Heads
+    are concatenated (concat=True, [N, heads * out]) or averaged ([N, out]).  share_weights: W_r is W_l (no second parameter), so
+    Hd = Hs.  fused=True (the default): the attention runs on GATv2Attention -- no per-edge tensor, one call for all heads.
+    fused=False is the composed path: t and z are [nnz, heads * out]-sized torch work (index_select, add, leaky_relu, dot), then
+    EdgeSoftmax, torch dropout and EdgeWeightedAggregate; it exists to be compared with, and its memory is why it is not the default.
+    With fused=True `inputInfo` may be a sampling.SampledBlock: X is [num_src, in], Hs covers all num_src rows and Hd is
+    X[:num_dst] W_r (with share_weights: the first num_dst rows of Hs); fused=False refuses a block.  float32 only.
+    attn_drop, ``forward(..., rng_seed=...)`` and ``last_rng_seed`` are GATConv's."""
+
+    def __init__(self, input_dim, output_dim, heads=1, concat=True, negative_slope=0.2, share_weights=False, attn_drop=0.0,
+                 fused=True):
+        super().__init__()
+        self.attn_drop = float(attn_drop)
+        if not 0.0 <= self.attn_drop < 1.0:
+            raise ValueError(f"GATv2Conv: attn_drop must be in [0, 1) (got {attn_drop})")
+        if int(heads) < 1 or int(output_dim) < 1:
+            raise ValueError(f"GATv2Conv: heads and output_dim must be >= 1 (got {heads}, {output_dim})")
+        self.last_rng_seed = None
+        self.heads, self.out_dim, self.concat, self.negative_slope = int(heads), int(output_dim), bool(concat), float(negative_slope)
+        self.share_weights, self.fused = bool(share_weights), bool(fused)
+        self.W_l = Parameter(torch.empty(input_dim, self.heads * self.out_dim))
+        if self.share_weights:
+            self.register_parameter("W_r", None)
+        else:
+            self.W_r = Parameter(torch.empty(input_dim, self.heads * self.out_dim))
+        self.att = Parameter(torch.empty(self.heads, self.out_dim))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        bound = 1.0 / math.sqrt(self.out_dim)
+        with torch.no_grad():
+            self.W_l.uniform_(-bound, bound)
+            if self.W_r is not None:
+                self.W_r.uniform_(-bound, bound)
+            self.att.uniform_(-bound, bound)
+
+    def forward(self, X, inputInfo, rng_seed=None):
+        block = _is_block(inputInfo)
+        drop = self.training and self.attn_drop > 0.0
+        if block and not self.fused:
+            _refuse_block(inputInfo, "GATv2Conv(fused=False)")
+        if X.dtype != torch.float32 or _x16_dtype(X) is not None:
+            raise TypeError("GATv2Conv computes in float32 only: 16-bit features and torch.autocast are not "
+                            f"supported (got {X.dtype}{', inside torch.autocast' if X.dtype == torch.float32 else ''})")
+        if block:
+            X = _block_features(X, inputInfo, "GATv2Conv")
+        n = inputInfo.num_dst if block else X.shape[0]      # rows of the result
+        Hs = torch.mm(X, self.W_l)
+        if self.share_weights:
+            Hd = Hs[:n] if block else Hs
+        else:
+            Hd = torch.mm(X[:n] if block else X, self.W_r)
+        if self.fused:
+            if drop:
+                if rng_seed is None:
+                    rng_seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())       # (a CPU tensor: no device synchronisation)
+                self.last_rng_seed = int(rng_seed)
+                Y = GATv2Attention.apply(Hs, Hd, self.att, inputInfo, self.negative_slope, self.attn_drop, self.last_rng_seed)
+            else:
+                Y = GATv2Attention.apply(Hs, Hd, self.att, inputInfo, self.negative_slope)
+        else:
+            rows, ci = inputInfo.edge_rows(), inputInfo.column_index
+            t = torch.nn.functional.leaky_relu(Hs.index_select(0, ci) + Hd.index_select(0, rows), self.negative_slope)
+            z = (t.view(-1, self.heads, self.out_dim) * self.att).sum(-1)              # [nnz, heads]
+            alpha = EdgeSoftmax.apply(z.t().contiguous(), inputInfo.row_pointers)      # [heads, nnz]
+            if drop:
+                alpha = torch.nn.functional.dropout(alpha, self.attn_drop, training=True)
+            Y = EdgeWeightedAggregate.apply(Hs, alpha, inputInfo)
+        if self.concat or self.heads == 1:
+            return Y
+        return Y.view(n, self.heads, self.out_dim).mean(1)
