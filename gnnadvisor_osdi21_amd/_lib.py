@@ -8,6 +8,7 @@ fails loudly.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 
 import torch
@@ -116,12 +117,21 @@ GATV2_SIGNATURES = {
     "gnna_gatv2_backward_f32": (i, [p, i64, p, i64, p, p, p, i64, p, i64] + _GRAPH_T + [f, f, u64, p, i64, p, i64, p,
                                                                                        i64, i64, i, i, i, u, p]),
 }
+# fused dot-product attention (include/gnna_dotattn.h): a fourth table
+DOTATTN_SIGNATURES = {
+    # Q, ld_q, K, ld_k, V, ld_v, the graph, scale, attn_drop, rng_seed, out, ld_out, lse, sizes
+    "gnna_dot_attn_forward_f32": (i, [p, i64] * 3 + [p] * 4 + [f, f, u64, p, i64, p, i64, i64, i, i, i64, i, u, p]),
+    # Q, ld_q, K, ld_k, V, ld_v, lse, Y, ld_y, dY, ld_dy, both structures, scale, attn_drop, rng_seed, dQ, ld_dq, dK, ld_dk, dV, ld_dv, sizes
+    "gnna_dot_attn_backward_f32": (i, [p, i64] * 3 + [p, p, i64, p, i64] + _GRAPH_T + [f, f, u64] + [p, i64] * 3 +
+                                   [i64, i64, i, i, i, u, p]),
+}
 del p, i, i64, u, u64, f, s, pd, pi, pi64
 EXPORTS = tuple(SIGNATURES)
 EXT_EXPORTS = tuple(EXT_SIGNATURES)
 GATV2_EXPORTS = tuple(GATV2_SIGNATURES)
+DOTATTN_EXPORTS = tuple(DOTATTN_SIGNATURES)
 # every table load() applies (an extension of the surface adds its table here)
-SIGNATURE_TABLES = (SIGNATURES, EXT_SIGNATURES, GATV2_SIGNATURES)
+SIGNATURE_TABLES = (SIGNATURES, EXT_SIGNATURES, GATV2_SIGNATURES, DOTATTN_SIGNATURES)
 
 
 def load() -> ctypes.CDLL:
@@ -936,6 +946,88 @@ def gatv2_backward(Hs, Hd, att, lse, Y, dY, row_pointers, column_index, part_poi
           float(attn_drop), int(rng_seed), sgp, ld_dhs, dgp, ld_dhd, d_att.data_ptr(), n_out, n_in, heads, width // heads,
           int(partSize), 0)
     return dHs, dHd, d_att
+
+
+def _dot_attn_sizes(Q, K, V, heads, row_pointers):
+    """(Q's pointer, ld_q, K's pointer, ld_k, V's pointer, ld_v, num_out_rows, num_in_rows, width) of a dot-product attention call,
+    taken from the tensors: num_out_rows = Q.shape[0] = row_pointers.numel() - 1, num_in_rows = K.shape[0] = V.shape[0]."""
+    qp, n_out, width, ld_q = _rows_view(Q, "Q")
+    kp, n_in, width_k, ld_k = _rows_view(K, "K")
+    vp, n_v, width_v, ld_v = _rows_view(V, "V")
+    assert width_k == width and width_v == width and n_v == n_in and K.device == Q.device and V.device == Q.device, \
+        "Q must be [num_out_rows, heads * dim], K and V [num_in_rows, heads * dim]"
+    assert int(heads) >= 1 and width % int(heads) == 0, f"heads = {heads} must divide the row width {width}"
+    assert row_pointers.dim() == 1 and row_pointers.numel() == n_out + 1, \
+        f"row_pointers must be [num_out_rows + 1] with num_out_rows = Q.shape[0] = {n_out} (got {row_pointers.numel()} entries)"
+    return qp, ld_q, kp, ld_k, vp, ld_v, n_out, n_in, width
+
+
+def dot_attn_forward(Q, K, V, heads, row_pointers, column_index, part_pointers, part2Node, partSize=32, scale=None, attn_drop=0.0,
+                     rng_seed=0, out=None, lse=None, relu=False):
+    """gnna_dot_attn_forward_f32 (include/gnna_dotattn.h): fused multi-head scaled dot-product graph attention.  Q [num_out_rows,
+    heads * dim], K and V [num_in_rows, heads * dim] -> (out, lse) with z = scale * <Q[i, h], K[j, h]>,
+    out[i, h] = sum_e exp(z - lse[i, h]) * k * V[col(e), h]; k is the dropout factor of gat_forward_drop (1 at attn_drop = 0);
+    scale defaults to 1 / sqrt(dim).  No per-edge tensor.  `Q`, `K`, `V` and `out` may be row-strided views (stride(1) == 1), for
+    instance column slices of one projection matrix."""
+    _need_device(Q, "dot-product attention")
+    qp, ld_q, kp, ld_k, vp, ld_v, n_out, n_in, width = _dot_attn_sizes(Q, K, V, heads, row_pointers)
+    heads = int(heads)
+    if scale is None:
+        scale = 1.0 / math.sqrt(width // heads)
+    if out is None:
+        out = _fresh_output((n_out, width), Q.device)
+    if lse is None:
+        lse = _fresh_output((n_out, heads), Q.device)
+    op_, n_o, width_o, ld_out = _rows_view(out, "out")
+    assert n_o == n_out and width_o == width and _node_heads(lse, n_out, "lse") == heads
+    _call(Q.device, "gnna_dot_attn_forward_f32", qp, ld_q, kp, ld_k, vp, ld_v, row_pointers.data_ptr(), column_index.data_ptr(),
+          part_pointers.data_ptr(), part2Node.data_ptr(), float(scale), float(attn_drop), int(rng_seed), op_, ld_out,
+          lse.data_ptr(), n_out, n_in, heads, width // heads, part2Node.numel(), int(partSize), _flags(relu=relu))
+    return out, lse
+
+
+def dot_attn_backward(Q, K, V, heads, lse, Y, dY, row_pointers, column_index, part_pointers, part2Node, partSize=32, scale=None,
+                      attn_drop=0.0, rng_seed=0, transposed=None, dQ=None, dK=None, dV=None):
+    """gnna_dot_attn_backward_f32: (dQ, dK, dV) of dot_attn_forward for the gradient dY of its output Y (same scale, attn_drop and
+    rng_seed).  transposed = (t_row_pointers, t_column_index, t_part_pointers, t_part2Node) at the same partSize; without it (a
+    square graph whose structure is symmetric, not checked here) the graph's own structure is passed as the transposed one."""
+    _need_device(Q, "dot-product attention")
+    qp, ld_q, kp, ld_k, vp, ld_v, n_out, n_in, width = _dot_attn_sizes(Q, K, V, heads, row_pointers)
+    heads = int(heads)
+    if scale is None:
+        scale = 1.0 / math.sqrt(width // heads)
+    yp, n_y, width_y, ld_y = _rows_view(Y, "Y")
+    gp, n_g, width_g, ld_g = _rows_view(dY, "dY")
+    assert _node_heads(lse, n_out, "lse") == heads
+    assert (n_y, width_y) == (n_out, width) and (n_g, width_g) == (n_out, width), "Y and dY must be [num_out_rows, heads * dim]"
+    if n_out != n_in and transposed is None:
+        raise GnnaError(f"dot-product attention backward on a rectangular structure ({n_out} destination rows, {n_in} source rows) "
+                        "needs `transposed`: a rectangular structure is never its own transpose")
+    if transposed is None:
+        transposed = (row_pointers, column_index, part_pointers, part2Node)
+    t_rp, t_ci, t_pp, t_p2n = transposed
+    for t in (column_index, part_pointers, part2Node, t_rp, t_ci, t_pp, t_p2n):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.device == Q.device, \
+            "the graph and its transpose must be contiguous int32 tensors on Q's device"
+    assert t_rp.numel() == n_in + 1 and t_pp.numel() == t_p2n.numel() + 1, \
+        "transposed: [num_in_rows + 1] row pointers, [P + 1] / [P] partition"
+    if dQ is None:
+        dQ = _fresh_output((n_out, width), Q.device)
+    if dK is None:
+        dK = _fresh_output((n_in, width), Q.device)
+    if dV is None:
+        dV = _fresh_output((n_in, width), Q.device)
+    dqp, n_q, width_q, ld_dq = _rows_view(dQ, "dQ")
+    dkp, n_k, width_k, ld_dk = _rows_view(dK, "dK")
+    dvp, n_v, width_v, ld_dv = _rows_view(dV, "dV")
+    assert (n_q, width_q) == (n_out, width) and (n_k, width_k) == (n_in, width) and (n_v, width_v) == (n_in, width), \
+        "dQ / dK / dV must have the shapes of Q / K / V"
+    _call(Q.device, "gnna_dot_attn_backward_f32", qp, ld_q, kp, ld_k, vp, ld_v, lse.data_ptr(), yp, ld_y, gp, ld_g,
+          row_pointers.data_ptr(), column_index.data_ptr(), part_pointers.data_ptr(), part2Node.data_ptr(), part2Node.numel(),
+          t_rp.data_ptr(), t_ci.data_ptr(), t_pp.data_ptr(), t_p2n.data_ptr(), t_p2n.numel(), float(scale),
+          float(attn_drop), int(rng_seed), dqp, ld_dq, dkp, ld_dk, dvp, ld_dv, n_out, n_in, heads, width // heads,
+          int(partSize), 0)
+    return dQ, dK, dV
 
 
 def _device_i32(t, what):

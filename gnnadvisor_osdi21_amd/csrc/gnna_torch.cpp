@@ -29,10 +29,12 @@
 #include <atomic>
 #include <functional>
 #include <mutex>
+#include <cmath>
 #include <vector>
 
 #include "gnna_ext.h"
 #include "gnna_gatv2.h"
+#include "gnna_dotattn.h"
 
 #define CHECK_CUDA(x) TORCH_CHECK(x.is_cuda(), #x " must be a CUDA tensor")
 #define CHECK_CONTIGUOUS(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -712,6 +714,75 @@ gatv2_backward(const torch::Tensor &Hs_in, const torch::Tensor &Hd_in, const tor
     return std::make_tuple(dHs, dHd, d_att);
 }
 
+// Fused scaled dot-product graph attention (gnna_dot_attn_forward_f32 / gnna_dot_attn_backward_f32, gnna_dotattn.h): Q [num_out_rows,
+// heads * dim] with num_out_rows = row_pointers.numel() - 1, K and V [num_in_rows, heads * dim].  One (rectangular) entry for every
+// structure; attn_drop = 0 is the plain function.  Q, K and V go through their leading dimensions: column slices of one projection
+// matrix are passed as they are.
+static void dot_attn_shapes(const torch::Tensor &Q, const torch::Tensor &K, const torch::Tensor &V, int64_t heads, double scale)
+{
+    TORCH_CHECK(Q.dim() == 2 && K.dim() == 2 && V.dim() == 2 && K.size(1) == Q.size(1) && V.size(1) == Q.size(1) && V.size(0) == K.size(0),
+                "Q must be [num_out_rows, heads * dim], K and V [num_in_rows, heads * dim]");
+    TORCH_CHECK(heads >= 1 && Q.size(1) >= 1 && Q.size(1) % heads == 0, "heads (", heads, ") must divide heads * dim = ", Q.size(1));
+    TORCH_CHECK(std::isfinite(scale), "scale must be finite (got ", scale, ")");
+    TORCH_CHECK(K.device() == Q.device() && V.device() == Q.device(), "Q, K and V must be on one device");
+}
+
+std::tuple<torch::Tensor, torch::Tensor>
+dot_attn_forward(const torch::Tensor &Q_in, const torch::Tensor &K_in, const torch::Tensor &V_in, int64_t heads,
+                 const torch::Tensor &row_pointers, const torch::Tensor &column_index, const torch::Tensor &part_pointers,
+                 const torch::Tensor &part2Node, int partSize, double scale, double attn_drop, uint64_t rng_seed)
+{
+    dot_attn_shapes(Q_in, K_in, V_in, heads, scale);
+    const int64_t n_in = K_in.size(0), n_out = Q_in.size(0), width = Q_in.size(1);
+    const torch::Tensor Q = gat_rows(Q_in, "Q", n_out, width), K = gat_rows(K_in, "K", n_in, width), V = gat_rows(V_in, "V", n_in, width);
+    gat_check_graph(Q, n_out, row_pointers, column_index, part_pointers, part2Node);
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(Q.device());
+    auto Y = fresh({n_out, width}, Q.options()), lse = fresh({n_out, heads}, Q.options());
+    check_rc(gnna_dot_attn_forward_f32(Q.data_ptr<float>(), ld_of(Q), K.data_ptr<float>(), ld_of(K), V.data_ptr<float>(), ld_of(V),
+                                       row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
+                                       part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), (float)scale,
+                                       (float)attn_drop, rng_seed, Y.data_ptr<float>(), width, lse.data_ptr<float>(), n_out, n_in,
+                                       (int)heads, (int)(width / heads), part2Node.size(0), partSize, 0u, current_stream()));
+    return std::make_tuple(Y, lse);
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
+dot_attn_backward(const torch::Tensor &Q_in, const torch::Tensor &K_in, const torch::Tensor &V_in, int64_t heads,
+                  const torch::Tensor &lse, const torch::Tensor &Y_in, const torch::Tensor &dY_in, const torch::Tensor &row_pointers,
+                  const torch::Tensor &column_index, const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize,
+                  double scale, double attn_drop, uint64_t rng_seed, const c10::optional<std::vector<torch::Tensor>> &transposed)
+{
+    dot_attn_shapes(Q_in, K_in, V_in, heads, scale);
+    const int64_t n_in = K_in.size(0), n_out = Q_in.size(0), width = Q_in.size(1);
+    TORCH_CHECK(n_out == n_in || transposed.has_value(), "dot_attn_backward on a rectangular structure (", n_out, " destination rows, ",
+                n_in, " source rows) needs `transposed`: a rectangular structure is never its own transpose");
+    const torch::Tensor Q = gat_rows(Q_in, "Q", n_out, width), K = gat_rows(K_in, "K", n_in, width), V = gat_rows(V_in, "V", n_in, width),
+                        Y = gat_rows(Y_in, "Y", n_out, width), dY = gat_rows(dY_in, "dY", n_out, width);
+    // (a symmetric graph without `transposed`: its own structure, given twice)
+    const torch::Tensor *t_rp = &row_pointers, *t_ci = &column_index, *t_pp = &part_pointers, *t_p2n = &part2Node;
+    if (transposed.has_value()) {
+        TORCH_CHECK(transposed->size() == 4, "transposed must be (t_row_pointers, t_column_index, t_part_pointers, t_part2Node)");
+        t_rp = &(*transposed)[0]; t_ci = &(*transposed)[1]; t_pp = &(*transposed)[2]; t_p2n = &(*transposed)[3];
+        gat_check_graph(Q, n_in, *t_rp, *t_ci, *t_pp, *t_p2n);
+    }
+    check_floats(lse, "lse");
+    TORCH_CHECK(lse.dim() == 2 && lse.size(0) == n_out && lse.size(1) == heads && lse.device() == Q.device(),
+                "lse must be [num_out_rows, heads] on Q's device");
+    TORCH_CHECK(Y.device() == Q.device() && dY.device() == Q.device(), "Q, Y and dY must be on one device");
+    gat_check_graph(Q, n_out, row_pointers, column_index, part_pointers, part2Node);
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(Q.device());
+    auto dQ = fresh({n_out, width}, Q.options()), dK = fresh({n_in, width}, Q.options()), dV = fresh({n_in, width}, Q.options());
+    check_rc(gnna_dot_attn_backward_f32(Q.data_ptr<float>(), ld_of(Q), K.data_ptr<float>(), ld_of(K), V.data_ptr<float>(), ld_of(V),
+                                        lse.data_ptr<float>(), Y.data_ptr<float>(), ld_of(Y), dY.data_ptr<float>(), ld_of(dY),
+                                        row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
+                                        part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), part2Node.size(0),
+                                        t_rp->data_ptr<int32_t>(), t_ci->data_ptr<int32_t>(), t_pp->data_ptr<int32_t>(),
+                                        t_p2n->data_ptr<int32_t>(), t_p2n->size(0), (float)scale, (float)attn_drop, rng_seed,
+                                        dQ.data_ptr<float>(), width, dK.data_ptr<float>(), width, dV.data_ptr<float>(), width, n_out,
+                                        n_in, (int)heads, (int)(width / heads), partSize, 0u, current_stream()));
+    return std::make_tuple(dQ, dK, dV);
+}
+
 // SDDMM (gnna_sddmm_ld_f32): edge_out[e] = <A[row(e)], B[column_index[e]]>; A and B may be row-strided views.
 torch::Tensor sddmm(const torch::Tensor &A, const torch::Tensor &B, const torch::Tensor &column_index,
                     const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize)
@@ -1091,6 +1162,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("part_pointers"), pybind11::arg("part2Node"),
           pybind11::arg("partSize"), pybind11::arg("negative_slope") = 0.2, pybind11::arg("attn_drop") = 0.0, pybind11::arg("rng_seed") = 0,
           pybind11::arg("transposed") = pybind11::none());
+    m.def("dot_attn_forward", &dot_attn_forward,
+          "fused multi-head scaled dot-product graph attention -> (Y, lse) (extension; gnna_dotattn.h): z = scale * <Q[i, h], K[col(e), h]>, "
+          "Y[i, h] = sum_e exp(z - lse[i, h]) * k * V[col(e), h] with the dropout factor k of gat_forward_drop (1 at attn_drop = 0).  "
+          "Q [num_out_rows, heads * dim], K and V [num_in_rows, heads * dim] (row-strided views are passed as they are), "
+          "row_pointers [num_out_rows + 1]",
+          pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("heads"), pybind11::arg("row_pointers"),
+          pybind11::arg("column_index"), pybind11::arg("part_pointers"), pybind11::arg("part2Node"), pybind11::arg("partSize"),
+          pybind11::arg("scale"), pybind11::arg("attn_drop") = 0.0, pybind11::arg("rng_seed") = 0);
+    m.def("dot_attn_backward", &dot_attn_backward,
+          "gradient of dot_attn_forward for the same scale, attn_drop and rng_seed -> (dQ, dK, dV) (extension; gnna_dotattn.h); "
+          "`transposed` as for gat_backward",
+          pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("heads"), pybind11::arg("lse"), pybind11::arg("Y"),
+          pybind11::arg("dY"), pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("part_pointers"),
+          pybind11::arg("part2Node"), pybind11::arg("partSize"), pybind11::arg("scale"), pybind11::arg("attn_drop") = 0.0,
+          pybind11::arg("rng_seed") = 0, pybind11::arg("transposed") = pybind11::none());
     m.def("transpose_csr", &transpose_csr,
           "device-built CSR of A^T (extension) -> [t_row_pointers, t_column_index, t_perm]: row j lists the rows i of the edges i <- j in "
           "increasing position e, t_perm[p] = e (a stable argsort of column_index); ids outside [0, num_in_rows) are dropped",

@@ -37,15 +37,16 @@ def build_parser():
     p.add_argument("--dim", type=int, default=96, help="input embedding dimension size")
     p.add_argument("--hidden", type=int, default=16, help="hidden dimension size")
     p.add_argument("--classes", type=int, default=22, help="output classes size")
-    p.add_argument('--model', type=str, default='gcn', choices=['gcn', 'gin', 'gat', 'gatv2', 'sage', 'rgcn'],
-                   help="GCN, GIN, GAT, GATv2 (dynamic attention, two layers as gat), GraphSAGE or R-GCN")
+    p.add_argument('--model', type=str, default='gcn', choices=['gcn', 'gin', 'gat', 'gatv2', 'transformer', 'sage', 'rgcn'],
+                   help="GCN, GIN, GAT, GATv2 (dynamic attention, two layers as gat), graph transformer (dot-product attention, two "
+                        "TransformerConv layers as gat), GraphSAGE or R-GCN")
     p.add_argument('--num_relations', type=int, default=4,
                    help="--model rgcn: relation types of the edges (synthetic: a seeded hash of every edge's end points)")
     p.add_argument('--num_bases', type=int, default=0,
                    help="--model rgcn: bases of the weight decomposition W_r = sum_b c[r, b] V_b (0: none, one weight per relation)")
     p.add_argument('--aggregator', type=str, default='mean', choices=['mean', 'max', 'min'],
                    help="GraphSAGE: how a node's neighbours are reduced (mean, element-wise max or element-wise min)")
-    p.add_argument('--heads', type=int, default=1, help="GAT, GATv2: attention heads of the hidden layer (the output layer has one)")
+    p.add_argument('--heads', type=int, default=1, help="GAT, GATv2, transformer: attention heads of the hidden layer (the output layer has one)")
     p.add_argument("--num_epoches", type=int, default=200, help="number of epoches for training, default=200")
     p.add_argument("--partSize", type=int, default=32, help="neighbor-group size")
     p.add_argument("--dimWorker", type=int, default=32, help="number of worker threads (hint on MI355X)")
@@ -74,18 +75,19 @@ def build_parser():
     p.add_argument('--fused_attention', default='False', **tf,
                    help="True: --model gat runs both layers on the fused attention kernels (GATConv(fused=True): alpha is made "
                         "from node-sized values where the rows are gathered, no per-edge tensor; MI355X addition); --model gatv2 likewise "
-                        "(GATv2Conv(fused=...): False is the composed path with [nnz, heads * hidden] tensors)")
+                        "(GATv2Conv(fused=...): False is the composed path with [nnz, heads * hidden] tensors) and --model transformer "
+                        "(TransformerConv(fused=...))")
     p.add_argument('--attn_drop', type=float, default=0.0,
                    help="--model gat: dropout on the attention coefficients of both layers while training (GATConv(attn_drop=P), "
                         "P in [0, 1); 0.6 in the GAT paper).  With --fused_attention True the mask is made inside the kernels from "
                         "one host-drawn seed per layer and step, with --fanout too; a captured HIP graph would replay one seed and "
-                        "so one mask, one more reason --hip_graph stays refused for --model gat (MI355X addition); --model gatv2 likewise")
+                        "so one mask, one more reason --hip_graph stays refused for --model gat (MI355X addition); --model gatv2 and --model transformer likewise")
     p.add_argument('--directed', default='False', **tf,
                    help="True: the graph is directed -- every backward pass aggregates over the transposed structure, built on "
                         "the device right after the partition (False: the structure is taken to be symmetric, as the "
                         "reference does, and the backward passes reuse the forward graph)")
     p.add_argument('--fanout', type=str, default=None,
-                   help="--model sage, or --model gat / gatv2 with --fused_attention True: train on sampled mini-batches -- a comma list "
+                   help="--model sage, or --model gat / gatv2 / transformer with --fused_attention True: train on sampled mini-batches -- a comma list "
                         "with one entry per layer, the neighbours sampled per node at that layer (-1: all of them), e.g. 25,10; "
                         "the blocks are drawn on the device (sampling.NeighborSampler, MI355X addition)")
     p.add_argument('--batch_size', type=int, default=1024, help="--fanout: seed nodes per mini-batch")
@@ -106,7 +108,7 @@ def main(argv=None, capture=None):
     enable_rabbit, loadFromTxt = flag(args.enable_rabbit), flag(args.loadFromTxt)
     single_spmm, verify_spmm = flag(args.single_spmm), flag(args.verify_spmm)
 
-    attention = args.model in ('gat', 'gatv2')      # the two attention models share their flags and refusals
+    attention = args.model in ('gat', 'gatv2', 'transformer')      # the attention models share their flags and refusals
     if attention and flag(args.hip_graph):
         # (the attention layers build their per-edge arrays and the SDDMM's id copies at first use: not captured yet)
         raise SystemExit("--model %s does not support --hip_graph True: run it with --hip_graph False" % args.model)
@@ -146,7 +148,7 @@ def main(argv=None, capture=None):
         if attention and not flag(args.fused_attention):
             raise SystemExit("--model %s --fanout runs on the fused attention kernels only (the composed path would build "
                              "per-edge tensors for every batch): add --fused_attention True" % args.model)
-        if args.model not in ('sage', 'gat', 'gatv2'):
+        if args.model not in ('sage', 'gat', 'gatv2', 'transformer'):
             raise SystemExit("--fanout trains GraphSAGE on sampled blocks: run it with --model sage, or with --model gat "
                              "--fused_attention True (got --model %s)" % args.model)
         if flag(args.hip_graph):
@@ -178,7 +180,7 @@ def main(argv=None, capture=None):
     from . import load_extension
     from .decider import inputProperty
     from .loader import custom_dataset
-    from .ops import GATConv, GATv2Conv, GCNConv, GINConv, RGCNConv, SAGEConv
+    from .ops import GATConv, GATv2Conv, GCNConv, GINConv, RGCNConv, SAGEConv, TransformerConv
     GNNA = load_extension()
 
     # ---- loading data --------------------------------------------------------------------
@@ -201,7 +203,7 @@ def main(argv=None, capture=None):
     # what the run ahead will aggregate (the mi355x renumbering gate weighs the host seconds of a renumbering against it)
     from .decider import expected_aggregations
     inputInfo.expected_aggregations = [(args.hidden, args.num_epoches)] if (single_spmm or verify_spmm) else \
-        expected_aggregations('gat' if args.model == 'gatv2' else args.model, dataset.num_features, args.hidden, dataset.num_classes, args.num_epoches + 10,
+        expected_aggregations('gat' if args.model in ('gatv2', 'transformer') else args.model, dataset.num_features, args.hidden, dataset.num_classes, args.num_epoches + 10,
                               heads=args.heads, aggregator=args.aggregator, num_relations=args.num_relations,
                               num_bases=args.num_bases)
     inputInfo.force_renumbering = flag(args.force_rabbit)
@@ -320,6 +322,25 @@ def main(argv=None, capture=None):
                 self.conv1 = GATv2Conv(dataset.num_features, args.hidden, heads=args.heads, concat=True, fused=fused,
                                        attn_drop=args.attn_drop)
                 self.conv2 = GATv2Conv(args.hidden * args.heads, dataset.num_classes, heads=1, fused=fused, attn_drop=args.attn_drop)
+
+            def forward(self, x=None, blocks=None):
+                if blocks is not None:      # a sampled mini-batch (--fused_attention True): x holds blocks[0]'s source rows
+                    x = F.elu(self.conv1(x, blocks[0]))
+                    x = self.conv2(x, blocks[1])
+                    return F.log_softmax(x, dim=1)
+                x = F.elu(self.conv1(dataset.x, inputInfo.set_input()))
+                x = self.conv2(x, inputInfo.set_hidden())
+                return F.log_softmax(x, dim=1)
+    elif args.model == 'transformer':
+        fused = flag(args.fused_attention)
+
+        class Net(torch.nn.Module):
+            def __init__(self):
+                super().__init__()
+                self.conv1 = TransformerConv(dataset.num_features, args.hidden, heads=args.heads, concat=True, fused=fused,
+                                             attn_drop=args.attn_drop)
+                self.conv2 = TransformerConv(args.hidden * args.heads, dataset.num_classes, heads=1, fused=fused,
+                                             attn_drop=args.attn_drop)
 
             def forward(self, x=None, blocks=None):
                 if blocks is not None:      # a sampled mini-batch (--fused_attention True): x holds blocks[0]'s source rows

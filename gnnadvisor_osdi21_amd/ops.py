@@ -949,3 +949,139 @@ class GATv2Conv(Module):
         if self.concat or self.heads == 1:
             return Y
         return Y.view(n, self.heads, self.out_dim).mean(1)
+
+
+class DotAttention(Function):
+    """Scaled dot-product attention over the edges of a graph -- the attention of graph transformers (TransformerConv / UniMP,
+    DotGatConv, the inner step of HGT and GPS layers) -- in one fused call per direction (libgnna gnna_dot_attn_forward_f32 /
+    gnna_dot_attn_backward_f32, include/gnna_dotattn.h):
+    ``DotAttention.apply(Q, K, V, inputInfo, heads, scale=None, attn_drop=0.0, rng_seed=0) -> Y`` with Q [N, heads * F] (the
+    queries of the destination rows), K and V [N, heads * F] (the keys and the messages of the source rows) and
+    Y[i, h] = sum_e alpha(e, h) k V[col(e), h], alpha = softmax over row i of z = scale * <Q[i, h], K[col(e), h]>; scale defaults to
+    1 / sqrt(F), which is why the op is told `heads`.  Every kernel recomputes z from the rows it gathers; no [nnz] tensor is made,
+    saved or cached (saved: Q, K, V, lse, Y -- all node-sized).  Returns (dQ, dK, dV).  Q, K and V may be row-strided views
+    (column slices of one projection matrix): they are passed with their strides, not copied.
+
+    `inputInfo` is a graph, a ``directed`` graph or a sampling.SampledBlock (Q [num_dst, heads * F], K and V [num_src, heads * F],
+    Y [num_dst, heads * F]); ``transposed()`` / ``require_symmetric`` are handled exactly as in GATv2Attention.  attn_drop /
+    rng_seed: the mask rule of GATAttention (include/gnna_ext.h), recomputed in every pass; attn_drop = 0 is the plain function."""
+
+    @staticmethod
+    def forward(ctx, Q, K, V, inputInfo, heads, scale=None, attn_drop=0.0, rng_seed=0):
+        info = inputInfo
+        heads = int(heads)
+        attn_drop, rng_seed = float(attn_drop), int(rng_seed) & (2 ** 64 - 1)      # (the key arithmetic is mod 2^64)
+        if not 0.0 <= attn_drop < 1.0:
+            raise ValueError(f"DotAttention: attn_drop must be in [0, 1) (got {attn_drop})")
+        for t, name in ((Q, "Q"), (K, "K"), (V, "V")):
+            if t.dtype != torch.float32:
+                raise TypeError(f"DotAttention: float32 only (got {name}: {t.dtype})")
+        if Q.dim() != 2 or K.dim() != 2 or V.dim() != 2 or K.shape[1] != Q.shape[1] or V.shape != K.shape or heads < 1 or \
+                Q.shape[1] % heads != 0:
+            raise ValueError(f"DotAttention: Q [num_dst, heads * F], K and V [num_src, heads * F] with heads = {heads} expected (got "
+                             f"{tuple(Q.shape)}, {tuple(K.shape)} and {tuple(V.shape)})")
+        scale = 1.0 / math.sqrt(Q.shape[1] // heads) if scale is None else float(scale)
+        if not math.isfinite(scale):
+            raise ValueError(f"DotAttention: scale must be finite (got {scale})")
+        if _is_block(info):
+            K = _block_features(K, info, "DotAttention")
+            if V.shape[0] != info.num_src or Q.shape[0] != info.num_dst:
+                raise ValueError(f"DotAttention on a SampledBlock: Q must be [num_dst = {info.num_dst}, heads * F] and V "
+                                 f"[num_src = {info.num_src}, heads * F] (got {tuple(Q.shape)} and {tuple(V.shape)})")
+        Y, lse = GNNA.dot_attn_forward(Q, K, V, heads, info.row_pointers, info.column_index, info.partPtr, info.part2Node,
+                                       info.partSize, scale, attn_drop, rng_seed)
+        ctx.info, ctx.heads, ctx.scale, ctx.attn_drop, ctx.rng_seed = info, heads, scale, attn_drop, rng_seed
+        ctx.save_for_backward(Q, K, V, lse, Y)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        Q, K, V, lse, Y = ctx.saved_tensors
+        info = ctx.info
+        rest = (None,) * (len(ctx.needs_input_grad) - 3)       # inputInfo, heads (, scale (, attn_drop (, rng_seed)))
+        if not any(ctx.needs_input_grad[:3]):
+            return (None, None, None) + rest
+        transposed = None
+        if _is_block(info) or _is_directed(info):      # (a block is never symmetric: require_symmetric is not for it)
+            t = info.transposed()
+            transposed = [t.row_pointers, t.column_index, t.partPtr, t.part2Node]
+        else:
+            from .decider import inputProperty
+            inputProperty.require_symmetric(info)    # raises on a structure that is not symmetric (answer cached per column_index)
+        dQ, dK, dV = GNNA.dot_attn_backward(Q, K, V, ctx.heads, lse, Y, dY, info.row_pointers, info.column_index, info.partPtr,
+                                            info.part2Node, info.partSize, ctx.scale, ctx.attn_drop, ctx.rng_seed, transposed)
+        need = ctx.needs_input_grad
+        return (dQ if need[0] else None, dK if need[1] else None, dV if need[2] else None) + rest
+
+
+class TransformerConv(Module):
+    """The graph transformer layer ("Masked Label Prediction: Unified Message Passing Model", PyG's TransformerConv without edge
+    features, biases or the beta gate): [Q | K | V] = X W with one weight [in, 3 * heads * out] and one torch.mm; per head h,
+    z[e] = <Q_h[row(e)], K_h[col(e)]> / sqrt(out), alpha = edge softmax of z over every row, Y_h = A_alpha V_h.  Heads are
+    concatenated (concat=True, [N, heads * out]) or averaged ([N, out]); root_weight adds the skip connection X W_skip.  Q, K and V
+    are handed on as column slices of the product, never copied.  fused=True (the default, for memory, not as a speed claim): the
+    attention runs on DotAttention -- no per-edge tensor, one call for all heads.  fused=False is the composed path: Q[rows] and
+    K[cols] are [nnz, heads * out]-sized torch work (index_select, product, sum), then EdgeSoftmax, torch dropout and
+    EdgeWeightedAggregate; it exists to be compared with.  With fused=True `inputInfo` may be a sampling.SampledBlock: X is
+    [num_src, in], K and V cover all num_src rows, Q is the first num_dst rows and the skip connection reads X[:num_dst];
+    fused=False refuses a block.  float32 only.  attn_drop, ``forward(..., rng_seed=...)`` and ``last_rng_seed`` are GATConv's."""
+
+    def __init__(self, input_dim, output_dim, heads=1, concat=True, root_weight=True, attn_drop=0.0, fused=True):
+        super().__init__()
+        self.attn_drop = float(attn_drop)
+        if not 0.0 <= self.attn_drop < 1.0:
+            raise ValueError(f"TransformerConv: attn_drop must be in [0, 1) (got {attn_drop})")
+        if int(heads) < 1 or int(output_dim) < 1:
+            raise ValueError(f"TransformerConv: heads and output_dim must be >= 1 (got {heads}, {output_dim})")
+        self.last_rng_seed = None
+        self.heads, self.out_dim, self.concat = int(heads), int(output_dim), bool(concat)
+        self.root_weight, self.fused = bool(root_weight), bool(fused)
+        self.weights = Parameter(torch.empty(input_dim, 3 * self.heads * self.out_dim))
+        if self.root_weight:
+            self.W_skip = Parameter(torch.empty(input_dim, self.heads * self.out_dim if self.concat else self.out_dim))
+        else:
+            self.register_parameter("W_skip", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        bound = 1.0 / math.sqrt(self.out_dim)
+        with torch.no_grad():
+            self.weights.uniform_(-bound, bound)
+            if self.W_skip is not None:
+                self.W_skip.uniform_(-bound, bound)
+
+    def forward(self, X, inputInfo, rng_seed=None):
+        block = _is_block(inputInfo)
+        drop = self.training and self.attn_drop > 0.0
+        if block and not self.fused:
+            _refuse_block(inputInfo, "TransformerConv(fused=False)")
+        if X.dtype != torch.float32 or _x16_dtype(X) is not None:
+            raise TypeError("TransformerConv computes in float32 only: 16-bit features and torch.autocast are not "
+                            f"supported (got {X.dtype}{', inside torch.autocast' if X.dtype == torch.float32 else ''})")
+        if block:
+            X = _block_features(X, inputInfo, "TransformerConv")
+        n = inputInfo.num_dst if block else X.shape[0]      # rows of the result
+        W = self.heads * self.out_dim
+        P = torch.mm(X, self.weights)                       # [num_src, 3 * heads * out]: Q | K | V
+        Q, K, V = P[:n, :W], P[:, W:2 * W], P[:, 2 * W:]
+        if self.fused:
+            if drop:
+                if rng_seed is None:
+                    rng_seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())       # (a CPU tensor: no device synchronisation)
+                self.last_rng_seed = int(rng_seed)
+                Y = DotAttention.apply(Q, K, V, inputInfo, self.heads, None, self.attn_drop, self.last_rng_seed)
+            else:
+                Y = DotAttention.apply(Q, K, V, inputInfo, self.heads)
+        else:
+            rows, ci = inputInfo.edge_rows(), inputInfo.column_index
+            qk = Q.index_select(0, rows) * K.index_select(0, ci)                       # [nnz, heads * out]
+            z = qk.view(-1, self.heads, self.out_dim).sum(-1) / math.sqrt(self.out_dim)
+            alpha = EdgeSoftmax.apply(z.t().contiguous(), inputInfo.row_pointers)      # [heads, nnz]
+            if drop:
+                alpha = torch.nn.functional.dropout(alpha, self.attn_drop, training=True)
+            Y = EdgeWeightedAggregate.apply(V.contiguous(), alpha, inputInfo)
+        if not (self.concat or self.heads == 1):
+            Y = Y.view(n, self.heads, self.out_dim).mean(1)
+        if self.W_skip is not None:
+            Y = Y + torch.mm(X[:n] if block else X, self.W_skip)
+        return Y
