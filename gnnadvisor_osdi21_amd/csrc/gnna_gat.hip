@@ -50,7 +50,7 @@
 namespace gnna {
 namespace {
 
-using namespace gat;      // the folds, the online (max, sum), the dropout factor and the checks: gnna_gat_common.h
+using namespace gat;      // the folds, the online (max, sum), the dropout factor, the pull launcher, the checks: gnna_gat_common.h
 
 constexpr int kSlotGatPack = 6;   // library scratch: (el, lse, c, 0) per (node, head) of a backward call
 
@@ -208,40 +208,21 @@ gat_pull_kernel(const GatArgs p)
     const int lane = threadIdx.x & (kWave - 1);
     const int sub = lane >> LOG_LPR, cl = lane & (LPR - 1);
     const int hl = cl >> LOG_LPH, fl = (cl & (LPH - 1)) * 4;
-    // consecutive chunks on one XCD (workgroups go round the 8 XCDs): neighbouring rows share source rows in that L2
-    uint32_t vb = blockIdx.x;
-    if (p.xcd_remap) {
-        const uint32_t nb = gridDim.x, q = nb / kXcds, rem = nb % kXcds, x = vb % kXcds, i = vb / kXcds;
-        vb = x < rem ? x * (q + 1) + i : rem * (q + 1) + (x - rem) * q + i;
-    }
-    const int64_t chunk = (int64_t)vb * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t g0 = chunk * p.G;
+    const int64_t g0 = pull_chunk(p.xcd_remap) * p.G;
     if (g0 >= p.P) return;
     const int cnt = (int)(p.P - g0 < (int64_t)p.G ? p.P - g0 : (int64_t)p.G);
-    int s = 0, e = 0, r = -1;
-    if (lane < cnt) {
-        s = p.pp[g0 + lane];
-        e = p.pp[g0 + lane + 1];
-        r = p.p2n[g0 + lane];
-    }
-    // a group without edges, with a negative range or with a row outside its side's rows contributes nothing and ends the run
-    const bool bad = lane >= cnt || e <= s || s < 0 || (uint32_t)r >= p.N;
-    const int prev_r = __shfl_up(r, 1);
-    const int prev_bad = __shfl_up((int)bad, 1);
-    const bool first = lane == 0 || bad || prev_bad != 0 || r != prev_r;
-    unsigned long long starts = __ballot(first);
-    if (cnt < kWave) starts &= (1ull << cnt) - 1ull;
-    const int bad_i = bad ? 1 : 0;
+    const PullGroups g = pull_groups(p, g0, cnt, lane);
+    unsigned long long starts = g.starts;
     const int heads = p.heads;
 
     while (starts) {
         const int a = __builtin_ctzll(starts);
         starts &= starts - 1ull;
         const int b = starts ? __builtin_ctzll(starts) : cnt;
-        if (__builtin_amdgcn_readlane(bad_i, a)) continue;
-        const int rs = __builtin_amdgcn_readlane(s, a);
-        const int re = __builtin_amdgcn_readlane(e, b - 1);
-        const uint32_t row = (uint32_t)__builtin_amdgcn_readlane(r, a);
+        if (__builtin_amdgcn_readlane(g.bad, a)) continue;
+        const int rs = __builtin_amdgcn_readlane(g.s, a);
+        const int re = __builtin_amdgcn_readlane(g.e, b - 1);
+        const uint32_t row = (uint32_t)__builtin_amdgcn_readlane(g.r, a);
         if (re <= rs) continue;
         for (int hb0 = 0; hb0 < heads; hb0 += HB) {
             const int h = hb0 + hl;
@@ -332,33 +313,12 @@ gat_pull_kernel(const GatArgs p)
     }
 }
 
-template <int SIDE, bool DROP>
-int launch_pull_drop(DeviceState *ds, hipStream_t stream, GatArgs a, int partSize)
-{
-    if (a.P <= 0) return GNNA_OK;
-    const int log_lph = log2_lanes(a.dim, 4);                  // (dim <= kMaxDim: never capped)
-    int log_lpr = log_lph;
-    while (log_lpr < 6 && (1 << (log_lpr - log_lph)) < a.heads) log_lpr++;
-    const ChunkGrid cg = chunk_grid(a.P, partSize, ds->num_cus);
-    a.G = cg.G;
-    if (cg.blocks > 0x7fffffffll)
-        return fail(GNNA_ERR_UNSUPPORTED, "GAT attention: %lld neighbor-groups in one call", (long long)a.P);
-    const dim3 grid((unsigned)cg.blocks);
-    dispatch_lpr(log_lph, [&](auto H) {
-        dispatch_lpr(log_lpr, [&](auto L) {
-            constexpr int LOG_LPH = decltype(H)::value, LOG_LPR = decltype(L)::value;
-            if constexpr (LOG_LPR >= LOG_LPH)      // (a row has at least the lanes of one head)
-                hipLaunchKernelGGL((gat_pull_kernel<SIDE, LOG_LPH, LOG_LPR, DROP>), grid, dim3(kBlock), 0, stream, a);
-        });
-    });
-    return launch_ok("GAT attention launch");
-}
-
-// attn_drop = 0 keeps every edge with k = 1: the call runs the instances without the mask
 template <int SIDE>
 int launch_pull(DeviceState *ds, hipStream_t stream, const GatArgs &a, int partSize)
 {
-    return a.drop_thr ? launch_pull_drop<SIDE, true>(ds, stream, a, partSize) : launch_pull_drop<SIDE, false>(ds, stream, a, partSize);
+    return gat::launch_pull("GAT attention", ds, stream, a, partSize, [](auto H, auto L, auto D) {
+        return gat_pull_kernel<SIDE, decltype(H)::value, decltype(L)::value, decltype(D)::value>;
+    });
 }
 
 int launch_lse(hipStream_t stream, const float *el, const float *er, const int32_t *rp, const int32_t *col, int64_t N, int64_t M,
@@ -379,14 +339,6 @@ int launch_lse(hipStream_t stream, const float *el, const float *er, const int32
     default: hipLaunchKernelGGL(gat_lse_kernel<8>, grid, dim3(kBlock), 0, stream, el, er, rp, col, N, M, heads, slope, lse, seg); break;
     }
     return launch_ok("GAT lse launch");
-}
-
-// thr = (uint32) floor((double)attn_drop * 2^32) and k = 1 / (1 - attn_drop) in fp32, as gnna_ext.h states them
-void set_drop(GatArgs *a, float attn_drop, uint64_t rng_seed)
-{
-    a->rng_seed = rng_seed;
-    a->drop_thr = drop_threshold(attn_drop);
-    a->keep_scale = drop_keep_scale(attn_drop);
 }
 
 // The forward of all entries: num_out_rows rows (el, lse, out) gather from num_in_rows rows (H, er).
@@ -418,9 +370,7 @@ int gat_forward_impl(const char *what, bool rect, const float *H, int64_t ld_h, 
     rc = launch_zero_fill(ds, stream, out, num_out_rows, (int)W, ld_out);
     if (rc != GNNA_OK) return rc;
     if (num_parts == 0 || no_in) return launch_zero_fill(ds, stream, lse, num_out_rows, heads, heads);
-    gnna_tuning tune;
-    gnna_get_tuning(&tune);
-    apply_graph_hints(column_index, (int)W, &tune);
+    const gnna_tuning tune = hinted_tuning(column_index, (int)W);
     // edges per row, for the segment width of the lse pass only: the graph's hint, else what the groups can hold at most
     const int64_t avg = tune.avg_degree > 0 ? tune.avg_degree : (num_parts * (int64_t)partSize + num_out_rows - 1) / num_out_rows;
     rc = launch_lse(stream, el, er, row_pointers, column_index, num_out_rows, num_in_rows, avg, heads, negative_slope, lse);
@@ -429,15 +379,11 @@ int gat_forward_impl(const char *what, bool rect, const float *H, int64_t ld_h, 
     a.gat = H; a.ld_gat = (size_t)ld_h; a.el = el; a.er = er; a.lse = lse;
     a.col = column_index; a.pp = part_pointers; a.p2n = part2Node; a.out = out; a.ld_out = (size_t)ld_out;
     a.slope = negative_slope; a.P = num_parts; a.N = (uint32_t)num_out_rows; a.M = (uint32_t)num_in_rows; a.heads = heads; a.dim = dim;
-    a.xcd_remap = tune.xcd_remap != 0 ? 1 : 0;                // (this tune went through apply_graph_hints: not xcd_remap_on())
+    a.xcd_remap = tune.xcd_remap != 0 ? 1 : 0;
     set_drop(&a, attn_drop, rng_seed);
     rc = launch_pull<SIDE_FWD>(ds, stream, a, partSize);
     if (rc != GNNA_OK) return rc;
-    if (flags & GNNA_EPILOGUE_RELU) {
-        launch_relu_rows(ds, stream, out, num_out_rows, (int)W, ld_out);
-        return launch_ok("%s: epilogue launch", what);
-    }
-    return GNNA_OK;
+    return relu_epilogue(what, ds, stream, flags, out, num_out_rows, (int)W, ld_out);
 }
 
 // The backward of all entries: the destination-side pass walks the structure (num_out_rows rows, ids < num_in_rows), the
@@ -468,12 +414,9 @@ int gat_backward_impl(const char *what, bool rect, const float *H, int64_t ld_h,
         if ((num_parts > 0 && (!column_index || !part_pointers || !part2Node)) ||
             (t_num_parts > 0 && (!t_column_index || !t_part_pointers || !t_part2Node)))
             return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null index pointer", what);
-        const void *ins[] = {H, el, er, lse, Y, dY};
-        const void *outs[] = {dH, d_el, d_er};
-        for (const void *o : outs)
-            for (const void *i : ins)
-                if (o == i) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: an output must not alias an input", what);
-        if (dH == d_el || dH == d_er || d_el == d_er) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: the outputs must not alias each other", what);
+        const void *const ins[] = {H, el, er, lse, Y, dY}, *const outs[] = {dH, d_el, d_er};
+        rc = check_alias(what, ins, outs);
+        if (rc != GNNA_OK) return rc;
     }
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     DeviceState *ds = nullptr;

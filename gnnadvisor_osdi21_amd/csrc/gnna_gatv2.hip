@@ -9,13 +9,14 @@
 // run and column block).  With lse[i, h] known, alpha = exp(z - lse[i, h]) is recomputed wherever a row is gathered and no buffer
 // of the size of the edge list exists anywhere.
 //
-//   forward   (a) gatv2_lse_kernel: rows of the CSR, one wavefront per row (the whole block for long rows, after the short
+//   forward   (a) gat::lse_kernel<LseArgs> (gnna_gat_common.h: the lse pass shared with gnna_dotattn.hip; LseArgs below says what
+//                 the score is): rows of the CSR, one wavefront per row (the whole block for long rows, after the short
 //                 ones); 64 / LPR edges per wave-wide load, four loads per step, online (max, sum) per head and slot.  The slots,
 //                 then the waves, meet in a fixed order; one writer per (row, head), plain stores: the same bits on every run.
 //             (b) gatv2_pull_kernel<SIDE_FWD>: out[i] = sum_e alpha * k * Hs[col(e)] over the neighbor-groups.
 //             Two full gathers of Hs.  A one-pass online softmax would keep (max, sum, row accumulator) per run and need a merge
 //             across the waves (and workgroups) that share a destination row: out of scope here, see DESIGN 7k.
-//   backward  gatv2_pack_kernel: (lse, c = <dY[i, h, :], Y[i, h, :]>) per (row, head), 8 bytes, in library scratch;
+//   backward  gat::lse_c_pack_kernel (gnna_gat_common.h, shared with gnna_dotattn.hip): (lse, c = <dY[i, h, :], Y[i, h, :]>) per (row, head), 8 bytes, in library scratch;
 //             gatv2_pull_kernel<SIDE_BWD_DST>: row i pulls Hs[j]:                     dHd[i] = sum_e g, d_att += sum_e dz * lrelu(t)
 //             gatv2_pull_kernel<SIDE_BWD_SRC>: row j pulls dY[i], Hd[i], pack[i]:      dHs[j] = sum_e (alpha * k * dY[i] + g)
 //                 (over the transposed structure; a symmetric graph passes its own)
@@ -55,6 +56,7 @@ __device__ __forceinline__ float score_part(const VT hs, const VT hd, const VT a
 
 // ---- (a) lse[i, h] ------------------------------------------------------------------------------------------------------
 
+// (the score of gat::lse_kernel, gnna_gat_common.h)
 struct LseArgs {
     const float *hs; size_t ld_hs;        // by id (< M)
     const float *hd; size_t ld_hd;        // by row (< N)
@@ -65,114 +67,16 @@ struct LseArgs {
     uint32_t M;
     int heads, dim;
     float slope;
+
+    struct Own { VT hd, at; };
+    __device__ __forceinline__ Own own(int64_t row, size_t colf, int n4) const
+    {
+        return Own{load_piece(hd + (size_t)row * ld_hd + colf, n4), load_piece(att + colf, n4)};
+    }
+    __device__ __forceinline__ const float *gathered(uint32_t id) const { return hs + (size_t)id * ld_hs; }
+    __device__ __forceinline__ float part(const Own &o, const VT v) const { return score_part(v, o.hd, o.at, slope); }
+    __device__ __forceinline__ float scaled(float s) const { return s; }
 };
-
-// The edges [beg, end) of `row` swept by `nl` slots of LPR lanes (this one: slot t), four edges per slot and step, for the heads
-// of the column block at hb0.  Every lane of a wavefront makes the same number of steps (the folds are wave-wide).
-template <int LOG_LPH, int LOG_LPR>
-__device__ __forceinline__ MaxSum lse_sweep(const LseArgs &p, int64_t row, int64_t beg, int64_t end, int t, int nl, int hb0, int cl)
-{
-    constexpr int LPH = 1 << LOG_LPH;
-    const int h = hb0 + (cl >> LOG_LPH), fl = (cl & (LPH - 1)) * 4;
-    const int n4 = h < p.heads ? p.dim - fl : 0;
-    const bool ok = n4 > 0;
-    const size_t colf = (size_t)(ok ? h : 0) * p.dim + (ok ? fl : 0);
-    VT hd = (VT)(0.f), at = (VT)(0.f);
-    if (ok) {
-        hd = load_piece(p.hd + (size_t)row * p.ld_hd + colf, n4);
-        at = load_piece(p.att + colf, n4);
-    }
-    MaxSum acc{-INFINITY, 0.f};
-    for (int64_t base = beg; base < end; base += (int64_t)nl * 4) {
-        int id[4];
-        VT v[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int64_t ee = base + t + (int64_t)k * nl;
-            id[k] = ee < end ? p.col[ee] : -1;
-            if ((uint32_t)id[k] >= p.M) id[k] = -1;                // an id outside the source rows is skipped, in every pass alike
-            v[k] = (VT)(0.f);
-            if (id[k] >= 0 && ok) v[k] = load_piece(p.hs + (size_t)(uint32_t)id[k] * p.ld_hs + colf, n4);
-        }
-        float x[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const float z = head_sum<LPH>(score_part(v[k], hd, at, p.slope));
-            x[k] = id[k] >= 0 ? z : -INFINITY;
-        }
-        acc = ms_add4(acc, x);
-    }
-    // the 64 / LPR slots of the wavefront meet (lanes that share lane % LPR), in a fixed order
-#pragma unroll
-    for (int d = kWave >> 1; d >= (1 << LOG_LPR); d >>= 1) acc = ms_merge(acc, MaxSum{__shfl_xor(acc.m, d), __shfl_xor(acc.l, d)});
-    return acc;
-}
-
-// One wavefront per row; N rows (Hd, lse), ids < M (Hs).
-template <int LOG_LPH, int LOG_LPR>
-__global__ void __launch_bounds__(kBlock)
-gatv2_lse_kernel(const LseArgs p)
-{
-    constexpr int LPH = 1 << LOG_LPH, LPR = 1 << LOG_LPR, HB = LPR / LPH, R = kWave / LPR;
-    __shared__ int s_long[kWavesPerBlock];
-    __shared__ int s_nlong;
-    __shared__ float s_red[2][kWavesPerBlock][LPR];
-    const int tid = threadIdx.x;
-    const int lane = tid & (kWave - 1);
-    const int wib = tid >> 6;
-    const int sub = lane >> LOG_LPR, cl = lane & (LPR - 1);
-    const int hl = cl >> LOG_LPH;
-    const bool writer = sub == 0 && (cl & (LPH - 1)) == 0;          // the first lane of a head in the first slot
-    if (tid == 0) s_nlong = 0;
-    __syncthreads();
-
-    const int64_t r0 = (int64_t)blockIdx.x * kWavesPerBlock;
-    const int64_t row = r0 + wib;
-    int64_t beg = 0, end = 0;
-    if (row < p.N) { beg = p.rp[row]; end = p.rp[row + 1]; }
-    const bool is_long = end - beg > R * 4 * kLongIters;
-    if (is_long && lane == 0) s_long[atomicAdd(&s_nlong, 1)] = wib;
-    // short rows (and rows without edges: lse = 0): the wavefront
-    if (row < p.N && !is_long) {
-        for (int hb0 = 0; hb0 < p.heads; hb0 += HB) {
-            const MaxSum v = lse_sweep<LOG_LPH, LOG_LPR>(p, row, beg, end, sub, R, hb0, cl);
-            if (writer && hb0 + hl < p.heads) p.lse[(size_t)row * p.heads + hb0 + hl] = lse_of(v);
-        }
-    }
-    __syncthreads();
-    // long rows: the whole block, one after the other (the list's order may vary; a row's result does not depend on it)
-    const int nlong = s_nlong;
-    for (int q = 0; q < nlong; q++) {
-        const int64_t rr = r0 + s_long[q];
-        const int64_t lb = p.rp[rr], le = p.rp[rr + 1];
-        for (int hb0 = 0; hb0 < p.heads; hb0 += HB) {
-            const MaxSum v = lse_sweep<LOG_LPH, LOG_LPR>(p, rr, lb, le, wib * R + sub, kWavesPerBlock * R, hb0, cl);
-            __syncthreads();
-            if (sub == 0) { s_red[0][wib][cl] = v.m; s_red[1][wib][cl] = v.l; }
-            __syncthreads();
-            MaxSum r{s_red[0][0][cl], s_red[1][0][cl]};
-#pragma unroll
-            for (int w = 1; w < kWavesPerBlock; w++) r = ms_merge(r, MaxSum{s_red[0][w][cl], s_red[1][w][cl]});
-            if (wib == 0 && writer && hb0 + hl < p.heads) p.lse[(size_t)rr * p.heads + hb0 + hl] = lse_of(r);
-        }
-    }
-}
-
-// ---- c[i, h] = <dY[i, h, :], Y[i, h, :]>, packed with lse -----------------------------------------------------------------
-
-__global__ void __launch_bounds__(kBlock)
-gatv2_pack_kernel(const float *__restrict__ G, size_t ldg, const float *__restrict__ Y, size_t ldy, const float *__restrict__ lse,
-                  float2 *__restrict__ pack, size_t N, int heads, int dim)
-{
-    const size_t n = N * (size_t)heads;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t r = i / (unsigned)heads, h = i - r * (unsigned)heads;
-        const float *g = G + r * ldg + h * (size_t)dim, *y = Y + r * ldy + h * (size_t)dim;
-        float c = 0.f;
-        for (int f = 0; f < dim; f++) c = __builtin_fmaf(g[f], y[f], c);
-        pack[i] = make_float2(lse[i], c);
-    }
-}
 
 // ---- the gather ----------------------------------------------------------------------------------------------------------
 
@@ -211,32 +115,12 @@ gatv2_pull_kernel(const PullArgs p)
     const int wib = threadIdx.x >> 6;
     const int sub = lane >> LOG_LPR, cl = lane & (LPR - 1);
     const int hl = cl >> LOG_LPH, fl = (cl & (LPH - 1)) * 4;
-    // consecutive chunks on one XCD (workgroups go round the 8 XCDs): neighbouring rows share source rows in that L2
-    uint32_t vb = blockIdx.x;
-    if (p.xcd_remap) {
-        const uint32_t nb = gridDim.x, q = nb / kXcds, rem = nb % kXcds, x = vb % kXcds, i = vb / kXcds;
-        vb = x < rem ? x * (q + 1) + i : rem * (q + 1) + (x - rem) * q + i;
-    }
-    const int64_t chunk = (int64_t)vb * kWavesPerBlock + wib;
-    const int64_t g0 = chunk * p.G;
+    const int64_t g0 = pull_chunk(p.xcd_remap) * p.G;
     // (a wavefront without groups walks nothing but stays for the workgroup's barriers of SIDE_BWD_DST)
     const int cnt = g0 >= p.P ? 0 : (int)(p.P - g0 < (int64_t)p.G ? p.P - g0 : (int64_t)p.G);
     if constexpr (SIDE != SIDE_BWD_DST)
         if (cnt == 0) return;
-    int s = 0, e = 0, r = -1;
-    if (lane < cnt) {
-        s = p.pp[g0 + lane];
-        e = p.pp[g0 + lane + 1];
-        r = p.p2n[g0 + lane];
-    }
-    // a group without edges, with a negative range or with a row outside its side's rows contributes nothing and ends the run
-    const bool bad = lane >= cnt || e <= s || s < 0 || (uint32_t)r >= p.N;
-    const int prev_r = __shfl_up(r, 1);
-    const int prev_bad = __shfl_up((int)bad, 1);
-    const bool first = lane == 0 || bad || prev_bad != 0 || r != prev_r;
-    unsigned long long starts0 = __ballot(first);
-    if (cnt < kWave) starts0 &= (1ull << cnt) - 1ull;
-    const int bad_i = bad ? 1 : 0;
+    const PullGroups g = pull_groups(p, g0, cnt, lane);
     const int heads = p.heads;
 
     // One run -- the edges [rs, re) of `row` -- for the column block at hb0: the row's own pieces, the gather, the butterfly, the
@@ -344,10 +228,10 @@ gatv2_pull_kernel(const PullArgs p)
         const int a = __builtin_ctzll(starts);
         starts &= starts - 1ull;
         const int b = starts ? __builtin_ctzll(starts) : cnt;
-        if (__builtin_amdgcn_readlane(bad_i, a)) return false;
-        rs = __builtin_amdgcn_readlane(s, a);
-        re = __builtin_amdgcn_readlane(e, b - 1);
-        row = (uint32_t)__builtin_amdgcn_readlane(r, a);
+        if (__builtin_amdgcn_readlane(g.bad, a)) return false;
+        rs = __builtin_amdgcn_readlane(g.s, a);
+        re = __builtin_amdgcn_readlane(g.e, b - 1);
+        row = (uint32_t)__builtin_amdgcn_readlane(g.r, a);
         return re > rs;
     };
     int rs = 0, re = 0;
@@ -355,7 +239,7 @@ gatv2_pull_kernel(const PullArgs p)
     if constexpr (SIDE != SIDE_BWD_DST) {
         // runs outside, column blocks inside, as gat_pull_kernel: a run is decoded once
         VT unused = (VT)(0.f);
-        unsigned long long starts = starts0;
+        unsigned long long starts = g.starts;
         while (starts) {
             if (!next_run(starts, rs, re, row)) continue;
             for (int hb0 = 0; hb0 < heads; hb0 += HB) run_block(hb0, rs, re, row, unused);
@@ -365,7 +249,7 @@ gatv2_pull_kernel(const PullArgs p)
         // the slots of the wavefront and the waves of the workgroup and goes out with one atomic per element
         for (int hb0 = 0; hb0 < heads; hb0 += HB) {
             VT da = (VT)(0.f);
-            unsigned long long starts = starts0;
+            unsigned long long starts = g.starts;
             while (starts)
                 if (next_run(starts, rs, re, row)) run_block(hb0, rs, re, row, da);
 #pragma unroll
@@ -390,56 +274,12 @@ gatv2_pull_kernel(const PullArgs p)
     }
 }
 
-template <int SIDE, bool DROP>
-int launch_pull_drop(DeviceState *ds, hipStream_t stream, PullArgs a, int partSize)
-{
-    if (a.P <= 0) return GNNA_OK;
-    const int log_lph = log2_lanes(a.dim, 4);                  // (dim <= kMaxDim: never capped)
-    int log_lpr = log_lph;
-    while (log_lpr < 6 && (1 << (log_lpr - log_lph)) < a.heads) log_lpr++;
-    const ChunkGrid cg = chunk_grid(a.P, partSize, ds->num_cus);
-    a.G = cg.G;
-    if (cg.blocks > 0x7fffffffll)
-        return fail(GNNA_ERR_UNSUPPORTED, "GATv2 attention: %lld neighbor-groups in one call", (long long)a.P);
-    const dim3 grid((unsigned)cg.blocks);
-    dispatch_lpr(log_lph, [&](auto H) {
-        dispatch_lpr(log_lpr, [&](auto L) {
-            constexpr int LOG_LPH = decltype(H)::value, LOG_LPR = decltype(L)::value;
-            if constexpr (LOG_LPR >= LOG_LPH)      // (a row has at least the lanes of one head)
-                hipLaunchKernelGGL((gatv2_pull_kernel<SIDE, LOG_LPH, LOG_LPR, DROP>), grid, dim3(kBlock), 0, stream, a);
-        });
-    });
-    return launch_ok("GATv2 attention launch");
-}
-
-// attn_drop = 0 keeps every edge with k = 1: the call runs the instances without the mask
 template <int SIDE>
 int launch_pull(DeviceState *ds, hipStream_t stream, const PullArgs &a, int partSize)
 {
-    return a.drop_thr ? launch_pull_drop<SIDE, true>(ds, stream, a, partSize) : launch_pull_drop<SIDE, false>(ds, stream, a, partSize);
-}
-
-int launch_lse(hipStream_t stream, const LseArgs &a)
-{
-    const int log_lph = log2_lanes(a.dim, 4);
-    int log_lpr = log_lph;
-    while (log_lpr < 6 && (1 << (log_lpr - log_lph)) < a.heads) log_lpr++;
-    const dim3 grid((unsigned)((a.N + kWavesPerBlock - 1) / kWavesPerBlock));      // (N < 2^29)
-    dispatch_lpr(log_lph, [&](auto H) {
-        dispatch_lpr(log_lpr, [&](auto L) {
-            constexpr int LOG_LPH = decltype(H)::value, LOG_LPR = decltype(L)::value;
-            if constexpr (LOG_LPR >= LOG_LPH)
-                hipLaunchKernelGGL((gatv2_lse_kernel<LOG_LPH, LOG_LPR>), grid, dim3(kBlock), 0, stream, a);
-        });
+    return gat::launch_pull("GATv2 attention", ds, stream, a, partSize, [](auto H, auto L, auto D) {
+        return gatv2_pull_kernel<SIDE, decltype(H)::value, decltype(L)::value, decltype(D)::value>;
     });
-    return launch_ok("GATv2 lse launch");
-}
-
-void set_drop(PullArgs *a, float attn_drop, uint64_t rng_seed)
-{
-    a->rng_seed = rng_seed;
-    a->drop_thr = drop_threshold(attn_drop);
-    a->keep_scale = drop_keep_scale(attn_drop);
 }
 
 }  // namespace
@@ -480,27 +320,21 @@ int gnna_gatv2_forward_f32(const float *Hs, int64_t ld_hs, const float *Hd, int6
     rc = launch_zero_fill(ds, stream, out, num_out_rows, (int)W, ld_out);
     if (rc != GNNA_OK) return rc;
     if (num_parts == 0 || no_in) return launch_zero_fill(ds, stream, lse, num_out_rows, heads, heads);
-    gnna_tuning tune;
-    gnna_get_tuning(&tune);
-    apply_graph_hints(column_index, (int)W, &tune);
+    const gnna_tuning tune = hinted_tuning(column_index, (int)W);
     LseArgs l{};
     l.hs = Hs; l.ld_hs = (size_t)ld_hs; l.hd = Hd; l.ld_hd = (size_t)ld_hd; l.att = att; l.rp = row_pointers; l.col = column_index;
     l.lse = lse; l.N = num_out_rows; l.M = (uint32_t)num_in_rows; l.heads = heads; l.dim = dim; l.slope = negative_slope;
-    rc = launch_lse(stream, l);
+    rc = launch_lse("GATv2 lse", stream, l);
     if (rc != GNNA_OK) return rc;
     PullArgs a{};
     a.own = Hd; a.ld_own = (size_t)ld_hd; a.gat = Hs; a.ld_gat = (size_t)ld_hs; a.att = att; a.lse = lse;
     a.col = column_index; a.pp = part_pointers; a.p2n = part2Node; a.out = out; a.ld_out = (size_t)ld_out;
     a.slope = negative_slope; a.P = num_parts; a.N = (uint32_t)num_out_rows; a.M = (uint32_t)num_in_rows; a.heads = heads; a.dim = dim;
-    a.xcd_remap = tune.xcd_remap != 0 ? 1 : 0;                // (this tune went through apply_graph_hints: not xcd_remap_on())
+    a.xcd_remap = tune.xcd_remap != 0 ? 1 : 0;
     set_drop(&a, attn_drop, rng_seed);
     rc = launch_pull<SIDE_FWD>(ds, stream, a, partSize);
     if (rc != GNNA_OK) return rc;
-    if (flags & GNNA_EPILOGUE_RELU) {
-        launch_relu_rows(ds, stream, out, num_out_rows, (int)W, ld_out);
-        return launch_ok("%s: epilogue launch", what);
-    }
-    return GNNA_OK;
+    return relu_epilogue(what, ds, stream, flags, out, num_out_rows, (int)W, ld_out);
 }
 
 // The destination-side pass walks the structure (num_out_rows rows, ids < num_in_rows), the source-side pass the transposed one
@@ -538,13 +372,9 @@ int gnna_gatv2_backward_f32(const float *Hs, int64_t ld_hs, const float *Hd, int
         if ((num_parts > 0 && (!column_index || !part_pointers || !part2Node)) ||
             (t_num_parts > 0 && (!t_column_index || !t_part_pointers || !t_part2Node)))
             return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null index pointer", what);
-        const void *ins[] = {Hs, Hd, att, lse, Y, dY};
-        const void *outs[] = {dHs, dHd, d_att};
-        for (const void *o : outs)
-            for (const void *i : ins)
-                if (o == i) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: an output must not alias an input", what);
-        if (dHs == dHd || dHs == d_att || dHd == d_att)
-            return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: the outputs must not alias each other", what);
+        const void *const ins[] = {Hs, Hd, att, lse, Y, dY}, *const outs[] = {dHs, dHd, d_att};
+        rc = check_alias(what, ins, outs);
+        if (rc != GNNA_OK) return rc;
     }
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     DeviceState *ds = nullptr;
@@ -554,16 +384,10 @@ int gnna_gatv2_backward_f32(const float *Hs, int64_t ld_hs, const float *Hd, int
     if (rc == GNNA_OK) rc = launch_zero_fill(ds, stream, dHs, num_in_rows, (int)W, ld_dhs);
     if (rc == GNNA_OK) rc = launch_zero_fill(ds, stream, dHd, num_out_rows, (int)W, ld_dhd);
     if (rc != GNNA_OK || one_side || (num_parts == 0 && t_num_parts == 0)) return rc;
-    void *ws = nullptr;
-    rc = get_workspace(ds, stream, kSlotGatv2Pack, ((size_t)num_out_rows * heads * sizeof(float2) + 255) & ~(size_t)255, &ws);
-    if (rc != GNNA_OK) return rc;
-    float2 *pack = static_cast<float2 *>(ws);
-    hipLaunchKernelGGL(gatv2_pack_kernel, dim3(elementwise_grid(num_out_rows * heads, ds->num_cus, 8)), dim3(kBlock), 0, stream, dY,
-                       (size_t)ld_dy, Y, (size_t)ld_y, lse, pack, (size_t)num_out_rows, heads, dim);
-    rc = launch_ok("%s: pack launch", what);
-    if (rc != GNNA_OK) return rc;
     PullArgs a{};
-    a.att = att; a.pack = pack; a.slope = negative_slope; a.heads = heads; a.dim = dim;
+    rc = launch_lse_c_pack<kSlotGatv2Pack>(what, ds, stream, dY, ld_dy, Y, ld_y, lse, num_out_rows, heads, dim, &a.pack);
+    if (rc != GNNA_OK) return rc;
+    a.att = att; a.slope = negative_slope; a.heads = heads; a.dim = dim;
     a.xcd_remap = xcd_remap_on();
     set_drop(&a, attn_drop, rng_seed);
     // destination side: row i pulls Hs[j] -> dHd, d_att

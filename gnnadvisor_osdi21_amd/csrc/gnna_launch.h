@@ -54,6 +54,31 @@ void dispatch_lpr(int log_lpr, F &&f)
     }
 }
 
+// Lane layout of the fused attention kernels (gnna_gat.hip, gnna_gatv2.hip, gnna_dotattn.hip): 2^log_lph lanes of 4 floats cover
+// a head of `dim` floats, 2^log_lpr lanes a row of a column block -- as many whole heads as fit in a wavefront, `heads` at most.
+struct AttnLayout {
+    int log_lph, log_lpr;
+};
+inline AttnLayout attn_layout(int heads, int dim)
+{
+    const int log_lph = log2_lanes(dim, 4);
+    int log_lpr = log_lph;
+    while (log_lpr < 6 && (1 << (log_lpr - log_lph)) < heads) log_lpr++;
+    return {log_lph, log_lpr};
+}
+
+// f(std::integral_constant<int, log_lph>, std::integral_constant<int, log_lpr>) for the layouts that exist (a row has at least
+// the lanes of one head).
+template <class F>
+void dispatch_layout(AttnLayout layout, F &&f)
+{
+    dispatch_lpr(layout.log_lph, [&](auto H) {
+        dispatch_lpr(layout.log_lpr, [&](auto L) {
+            if constexpr (decltype(L)::value >= decltype(H)::value) f(H, L);
+        });
+    });
+}
+
 // Blocks of a grid-stride kernel over `items` work items: one thread each, blocks_per_cu blocks per compute unit at most.
 inline unsigned elementwise_grid(int64_t items, int num_cus, int blocks_per_cu)
 {

@@ -1,8 +1,11 @@
 """Launch geometry of the gather kernels, pinned (no GPU): a small program with its own main includes csrc/gnna_launch.h alone,
-is compiled with the host C++ compiler (g++, as oracle/ compiles its sources) and prints what chunk_grid and log2_lanes answer.
+is compiled with the host C++ compiler (g++, as oracle/ compiles its sources) and prints what chunk_grid, log2_lanes and
+attn_layout answer.
 The expected values were worked out by hand from the formula every launcher carried before it was shared: G = max(1, min(64,
 2048 / partSize)), halved while ceil(P / G) < 16 * num_cus; blocks = ceil(ceil(P / G) / 4).  A slip here costs speed, not
-correctness, so no parity test would see it."""
+correctness, so no parity test would see it.  attn_layout is the lane layout of the fused attention kernels: log_lph =
+log2_lanes(dim, 4), then log_lpr raised from log_lph while log_lpr < 6 and 2^(log_lpr - log_lph) < heads; the values were worked
+out by hand from that rule."""
 import os
 import subprocess
 
@@ -25,6 +28,22 @@ CHUNK_GRID = [
 ]
 LANES_4 = dict(zip((1, 4, 5, 8, 9, 64, 65, 128, 129, 256, 257, 1000), (0, 0, 1, 1, 2, 4, 5, 5, 6, 6, 6, 6)))
 LANES_8 = dict(zip((8, 9, 512, 513), (0, 1, 6, 6)))
+# (heads, dim) -> (log_lph, log_lpr); the first eight are the shapes the GPU tests of the three attention families run (8 x 40:
+# capped, 4 heads per column block, so two blocks)
+ATTN_LAYOUT = [
+    ((1, 64), (4, 4)),
+    ((4, 16), (2, 4)),
+    ((3, 5), (1, 3)),
+    ((8, 8), (1, 4)),
+    ((1, 256), (6, 6)),
+    ((64, 1), (0, 6)),
+    ((2, 33), (4, 5)),
+    ((8, 40), (4, 6)),
+    ((1, 1), (0, 0)),
+    ((1, 4), (0, 0)),
+    ((1, 5), (1, 1)),
+    ((2, 4), (0, 1)),
+]
 
 PROGRAM = r"""
 #include "gnna_launch.h"
@@ -40,6 +59,9 @@ int main(int argc, char **argv)
         if (argv[i][0] == 'g') {
             const gnna::ChunkGrid g = gnna::chunk_grid(a, b, c);
             std::printf("%d %lld\n", g.G, (long long)g.blocks);
+        } else if (argv[i][0] == 'a') {
+            const gnna::AttnLayout y = gnna::attn_layout((int)a, b);
+            std::printf("%d %d\n", y.log_lph, y.log_lpr);
         } else {
             std::printf("%d\n", gnna::log2_lanes((int)a, b));
         }
@@ -59,6 +81,7 @@ def answers(tmp_path_factory):
     subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-std=c++17", "-Wall", "-Wextra", "-I" + CSRC, src,
                            "-o", exe])
     asked = [("g",) + k for k, _ in CHUNK_GRID] + [("l", d_, 4, 0) for d_ in LANES_4] + [("l", d_, 8, 0) for d_ in LANES_8]
+    asked += [("a",) + k + (0,) for k, _ in ATTN_LAYOUT]
     out = subprocess.check_output([exe] + [str(x) for q in asked for x in q], text=True).splitlines()
     assert len(out) == len(asked)
     return {q: tuple(int(x) for x in line.split()) for q, line in zip(asked, out)}
@@ -72,3 +95,8 @@ def test_chunk_grid(answers, args, want):
 def test_log2_lanes(answers):
     assert {d: answers[("l", d, 4, 0)][0] for d in LANES_4} == LANES_4
     assert {d: answers[("l", d, 8, 0)][0] for d in LANES_8} == LANES_8
+
+
+@pytest.mark.parametrize("args, want", ATTN_LAYOUT, ids=["%dx%d" % k for k, _ in ATTN_LAYOUT])
+def test_attn_layout(answers, args, want):
+    assert answers[("a",) + args + (0,)] == want
