@@ -125,6 +125,16 @@ DOTATTN_SIGNATURES = {
     "gnna_dot_attn_backward_f32": (i, [p, i64] * 3 + [p, p, i64, p, i64] + _GRAPH_T + [f, f, u64] + [p, i64] * 3 +
                                    [i64, i64, i, i, i, u, p]),
 }
+# fused GAT attention with a per-edge score term (include/gnna_gat_edge.h): a fifth table
+GATEDGE_SIGNATURES = {
+    # gnna_gat_forward_drop_f32 with ee after er and num_edges after the row counts
+    "gnna_gat_edge_forward_f32": (i, _GAT_FWD[:4] + [p] + _GAT_FWD[4:9] + [f, u64] + _GAT_FWD[9:] + [i64, i64, i64, i, i, i64, i, u, p]),
+    # gnna_gat_backward_drop_f32 with ee after er, t_edge_pos after the transposed structure, d_ee after d_er, num_edges after the row counts
+    "gnna_gat_edge_backward_f32": (i, _GAT_BWD[:4] + [p] + _GAT_BWD[4:] + _GAT_BOTH[:10] + [p, f, f, u64] + _GAT_BOTH[11:] +
+                                   [p, i64, i64, i64, i, i, i, u, p]),
+    # el, er, ee, lse, row_pointers, column_index, slope, alpha, num_out_rows, num_in_rows, num_edges, heads, stream
+    "gnna_gat_alpha_f32": (i, [p] * 6 + [f, p, i64, i64, i64, i, p]),
+}
 del p, i, i64, u, u64, f, s, pd, pi, pi64
 EXPORTS = tuple(SIGNATURES)
 EXT_EXPORTS = tuple(EXT_SIGNATURES)
@@ -132,6 +142,9 @@ GATV2_EXPORTS = tuple(GATV2_SIGNATURES)
 DOTATTN_EXPORTS = tuple(DOTATTN_SIGNATURES)
 # every table load() applies (an extension of the surface adds its table here)
 SIGNATURE_TABLES = (SIGNATURES, EXT_SIGNATURES, GATV2_SIGNATURES, DOTATTN_SIGNATURES)
+# the tables of later headers, which load() applies after those (SIGNATURE_TABLES restates the four headers before them and stays)
+GATEDGE_EXPORTS = tuple(GATEDGE_SIGNATURES)
+LATER_SIGNATURE_TABLES = (GATEDGE_SIGNATURES,)
 
 
 def load() -> ctypes.CDLL:
@@ -144,7 +157,7 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -m gnnadvisor_osdi21_amd.build`). There is no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    for table in SIGNATURE_TABLES:
+    for table in SIGNATURE_TABLES + LATER_SIGNATURE_TABLES:
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype = restype
@@ -872,6 +885,92 @@ def _gat_backward(drop, H, el, er, lse, Y, dY, row_pointers, column_index, part_
     else:
         _call(H.device, "gnna_gat_backward_f32", *head, *outs, n_out, heads, width // heads, part2Node.numel(), int(partSize), 0)
     return dH, d_el, d_er
+
+
+def _edge_heads(t, nnz, heads, what):
+    assert t.dtype == torch.float32 and t.dim() == 2 and tuple(t.shape) == (nnz, heads) and t.is_contiguous(), \
+        f"{what} must be a contiguous float32 [num_edges = {nnz}, heads = {heads}] tensor (edge-major, indexed like column_index)"
+
+
+def gat_edge_forward(H, el, er, ee, row_pointers, column_index, part_pointers, part2Node, partSize=32, negative_slope=0.2,
+                     attn_drop=0.0, rng_seed=0, out=None, lse=None, relu=False):
+    """gnna_gat_edge_forward_f32 (include/gnna_gat_edge.h): gat_forward_drop with a per-edge score term, z = el[i, h] + er[j, h] +
+    ee[e, h] for the edge at position e of column_index.  ee is [num_edges, heads] float32, contiguous.  -> (out, lse)."""
+    _need_device(H, "GAT attention")
+    hp, n_out, n_in, width, heads, ld_h = _gat_sizes(H, el, er, row_pointers)
+    nnz = column_index.numel()
+    _edge_heads(ee, nnz, heads, "ee")
+    if out is None:
+        out = _fresh_output((n_out, width), H.device)
+    if lse is None:
+        lse = _fresh_output((n_out, heads), H.device)
+    op_, n_o, width_o, ld_out = _rows_view(out, "out")
+    assert n_o == n_out and width_o == width and _node_heads(lse, n_out, "lse") == heads
+    _call(H.device, "gnna_gat_edge_forward_f32", hp, ld_h, el.data_ptr(), er.data_ptr(), ee.data_ptr(), row_pointers.data_ptr(),
+          column_index.data_ptr(), part_pointers.data_ptr(), part2Node.data_ptr(), float(negative_slope), float(attn_drop),
+          int(rng_seed), op_, ld_out, lse.data_ptr(), n_out, n_in, nnz, heads, width // heads, part2Node.numel(), int(partSize),
+          _flags(relu=relu))
+    return out, lse
+
+
+def gat_edge_backward(H, el, er, ee, lse, Y, dY, row_pointers, column_index, part_pointers, part2Node, t_edge_pos, partSize=32,
+                      negative_slope=0.2, attn_drop=0.0, rng_seed=0, transposed=None, dH=None, d_ee=None, accumulate=False):
+    """gnna_gat_edge_backward_f32: (dH, d_el, d_er, d_ee) of gat_edge_forward for the gradient dY of its output Y (same ee,
+    attn_drop and rng_seed).  t_edge_pos int32 [num_edges]: the forward position of every position of the transposed structure --
+    the `perm` of transpose_csr with `transposed` = (t_row_pointers, t_column_index, t_part_pointers, t_part2Node), or the
+    reverse-edge map of a symmetric graph without `transposed` (its own structure is passed as the transposed one).  d_ee
+    [num_edges, heads] has one writer per element: the same bits on every run."""
+    _need_device(H, "GAT attention")
+    hp, n_out, n_in, width, heads, ld_h = _gat_sizes(H, el, er, row_pointers)
+    nnz = column_index.numel()
+    _edge_heads(ee, nnz, heads, "ee")
+    yp, n_y, width_y, ld_y = _rows_view(Y, "Y")
+    gp, n_g, width_g, ld_g = _rows_view(dY, "dY")
+    assert _node_heads(lse, n_out, "lse") == heads
+    assert (n_y, width_y) == (n_out, width) and (n_g, width_g) == (n_out, width), "Y and dY must be [num_out_rows, heads * dim]"
+    if n_out != n_in and transposed is None:
+        raise GnnaError(f"GAT attention backward on a rectangular structure ({n_out} destination rows, {n_in} source rows) needs "
+                        "`transposed`: a rectangular structure is never its own transpose")
+    if transposed is None:
+        transposed = (row_pointers, column_index, part_pointers, part2Node)
+    t_rp, t_ci, t_pp, t_p2n = transposed
+    for t in (column_index, part_pointers, part2Node, t_rp, t_ci, t_pp, t_p2n, t_edge_pos):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.device == H.device, \
+            "the graph, its transpose and t_edge_pos must be contiguous int32 tensors on H's device"
+    assert t_rp.numel() == n_in + 1 and t_pp.numel() == t_p2n.numel() + 1, \
+        "transposed: [num_in_rows + 1] row pointers, [P + 1] / [P] partition"
+    assert t_edge_pos.numel() == nnz and t_ci.numel() == nnz, "t_edge_pos and the transposed column_index must be [num_edges]"
+    if dH is None:
+        dH = _fresh_output((n_in, width), H.device)
+    dp, n_d, width_d, ld_d = _rows_view(dH, "dH")
+    assert (n_d, width_d) == (n_in, width), "dH must have the shape of H"
+    if d_ee is None:
+        d_ee = _fresh_output((nnz, heads), H.device)
+    _edge_heads(d_ee, nnz, heads, "d_ee")
+    d_el, d_er = _fresh_output((n_out, heads), H.device), _fresh_output((n_in, heads), H.device)
+    _call(H.device, "gnna_gat_edge_backward_f32", hp, ld_h, el.data_ptr(), er.data_ptr(), ee.data_ptr(), lse.data_ptr(), yp, ld_y, gp,
+          ld_g, row_pointers.data_ptr(), column_index.data_ptr(), part_pointers.data_ptr(), part2Node.data_ptr(), part2Node.numel(),
+          t_rp.data_ptr(), t_ci.data_ptr(), t_pp.data_ptr(), t_p2n.data_ptr(), t_p2n.numel(), t_edge_pos.data_ptr(),
+          float(negative_slope), float(attn_drop), int(rng_seed), dp, ld_d, d_el.data_ptr(), d_er.data_ptr(), d_ee.data_ptr(), n_out,
+          n_in, nnz, heads, width // heads, int(partSize), _flags(accumulate))
+    return dH, d_el, d_er, d_ee
+
+
+def gat_alpha(el, er, ee, lse, row_pointers, column_index, negative_slope=0.2, alpha=None):
+    """gnna_gat_alpha_f32: the attention coefficients edge for edge, alpha [num_edges, heads] = exp(leaky_relu(el[i, h] + er[j, h]
+    + ee[e, h]) - lse[i, h]) (undropped; 0 for a skipped edge), from the lse of a forward call.  ee None: those of gat_forward."""
+    _need_device(el, "GAT attention")
+    n_out, n_in, nnz = el.shape[0], er.shape[0], column_index.numel()
+    heads = _node_heads(el, n_out, "el")
+    assert _node_heads(er, n_in, "er") == heads and _node_heads(lse, n_out, "lse") == heads and row_pointers.numel() == n_out + 1
+    if ee is not None:
+        _edge_heads(ee, nnz, heads, "ee")
+    if alpha is None:
+        alpha = _fresh_output((nnz, heads), el.device)
+    _edge_heads(alpha, nnz, heads, "alpha")
+    _call(el.device, "gnna_gat_alpha_f32", el.data_ptr(), er.data_ptr(), _ptr(ee), lse.data_ptr(), row_pointers.data_ptr(),
+          column_index.data_ptr(), float(negative_slope), alpha.data_ptr(), n_out, n_in, nnz, heads)
+    return alpha
 
 
 def _gatv2_sizes(Hs, Hd, att, row_pointers):

@@ -30,10 +30,11 @@ LIB_SOURCES = [os.path.join(CSRC, f) for f in ("gnna_agg.hip", "gnna_stream.hip"
                                                 "gnna_gemm.hip", "gnna_runtime.hip", "gnna_host.cpp", "gnna_reorder.cpp")]
 LIB_DEPS = LIB_SOURCES + [os.path.join(CSRC, "gnna_internal.h"), os.path.join(CSRC, "gnna_device.h"), os.path.join(CSRC, "gnna_launch.h"),
                            os.path.join(CSRC, "gnna_gat_common.h"), os.path.join(INCLUDE, "gnna.h"), os.path.join(INCLUDE, "gnna_ext.h"),
-                           os.path.join(INCLUDE, "gnna_gatv2.h"), os.path.join(INCLUDE, "gnna_dotattn.h")]
+                           os.path.join(INCLUDE, "gnna_gatv2.h"), os.path.join(INCLUDE, "gnna_dotattn.h"),
+                           os.path.join(INCLUDE, "gnna_gat_edge.h")]
 EXT_SOURCES = [os.path.join(CSRC, "gnna_torch.cpp")]
 EXT_DEPS = EXT_SOURCES + [os.path.join(INCLUDE, "gnna.h"), os.path.join(INCLUDE, "gnna_ext.h"), os.path.join(INCLUDE, "gnna_gatv2.h"),
-                          os.path.join(INCLUDE, "gnna_dotattn.h")]
+                          os.path.join(INCLUDE, "gnna_dotattn.h"), os.path.join(INCLUDE, "gnna_gat_edge.h")]
 
 
 def source_hash() -> str:

@@ -35,6 +35,7 @@
 #include "gnna_ext.h"
 #include "gnna_gatv2.h"
 #include "gnna_dotattn.h"
+#include "gnna_gat_edge.h"
 
 #define CHECK_CUDA(x) TORCH_CHECK(x.is_cuda(), #x " must be a CUDA tensor")
 #define CHECK_CONTIGUOUS(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -644,6 +645,105 @@ gat_backward_drop(const torch::Tensor &H, const torch::Tensor &el, const torch::
                             transposed, &drop);
 }
 
+// Fused GAT attention with a per-edge score term (gnna_gat_edge.h): gat_forward_drop / gat_backward_drop with ee [num_edges,
+// heads] (edge-major, indexed like column_index) in the score, its gradient d_ee, and the coefficients edge for edge.
+static void gat_check_edge_term(const torch::Tensor &t, const char *name, const torch::Tensor &column_index, int heads)
+{
+    check_floats(t, name);
+    TORCH_CHECK(t.dim() == 2 && t.size(0) == column_index.numel() && t.size(1) == heads, name, " must be [num_edges = ",
+                column_index.numel(), ", heads = ", heads, "] (edge-major, indexed like column_index)");
+    TORCH_CHECK(t.device() == column_index.device(), name, " and the graph must be on one device");
+}
+
+std::tuple<torch::Tensor, torch::Tensor>
+gat_edge_forward(const torch::Tensor &H_in, const torch::Tensor &el, const torch::Tensor &er, const torch::Tensor &ee,
+                 const torch::Tensor &row_pointers, const torch::Tensor &column_index, const torch::Tensor &part_pointers,
+                 const torch::Tensor &part2Node, int partSize, double negative_slope, double attn_drop, uint64_t rng_seed)
+{
+    const int heads = gat_heads(H_in, el, er);
+    const int64_t n_in = H_in.size(0), n_out = el.size(0), width = H_in.size(1);
+    const torch::Tensor H = gat_rows(H_in, "H", n_in, width);
+    gat_check_graph(H, n_out, row_pointers, column_index, part_pointers, part2Node);
+    gat_check_edge_term(ee, "ee", column_index, heads);
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(H.device());
+    auto Y = fresh({n_out, width}, el.options()), lse = fresh({n_out, (int64_t)heads}, el.options());
+    check_rc(gnna_gat_edge_forward_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(), ee.data_ptr<float>(),
+                                       row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
+                                       part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), (float)negative_slope,
+                                       (float)attn_drop, rng_seed, Y.data_ptr<float>(), width, lse.data_ptr<float>(), n_out, n_in,
+                                       column_index.numel(), heads, (int)(width / heads), part2Node.size(0), partSize, 0u,
+                                       current_stream()));
+    return std::make_tuple(Y, lse);
+}
+
+// t_edge_pos [num_edges]: the forward position of every position of the transposed structure -- transpose_csr's t_perm with
+// `transposed`, the reverse-edge map of a symmetric graph without (its own structure is then given twice)
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+gat_edge_backward(const torch::Tensor &H_in, const torch::Tensor &el, const torch::Tensor &er, const torch::Tensor &ee,
+                  const torch::Tensor &lse, const torch::Tensor &Y_in, const torch::Tensor &dY_in, const torch::Tensor &row_pointers,
+                  const torch::Tensor &column_index, const torch::Tensor &part_pointers, const torch::Tensor &part2Node,
+                  const torch::Tensor &t_edge_pos, int partSize, double negative_slope, double attn_drop, uint64_t rng_seed,
+                  const c10::optional<std::vector<torch::Tensor>> &transposed)
+{
+    const int heads = gat_heads(H_in, el, er);
+    const int64_t n_in = H_in.size(0), n_out = el.size(0), width = H_in.size(1), nnz = column_index.numel();
+    TORCH_CHECK(n_out == n_in || transposed.has_value(), "gat_edge_backward on a rectangular structure (", n_out, " destination rows, ",
+                n_in, " source rows) needs `transposed`: a rectangular structure is never its own transpose");
+    const torch::Tensor H = gat_rows(H_in, "H", n_in, width), Y = gat_rows(Y_in, "Y", n_out, width),
+                        dY = gat_rows(dY_in, "dY", n_out, width);
+    const torch::Tensor *t_rp = &row_pointers, *t_ci = &column_index, *t_pp = &part_pointers, *t_p2n = &part2Node;
+    if (transposed.has_value()) {
+        TORCH_CHECK(transposed->size() == 4, "transposed must be (t_row_pointers, t_column_index, t_part_pointers, t_part2Node)");
+        t_rp = &(*transposed)[0]; t_ci = &(*transposed)[1]; t_pp = &(*transposed)[2]; t_p2n = &(*transposed)[3];
+        gat_check_graph(H, n_in, *t_rp, *t_ci, *t_pp, *t_p2n);
+    }
+    check_floats(lse, "lse");
+    TORCH_CHECK(lse.sizes() == el.sizes() && lse.device() == H.device(), "lse must be [num_nodes, heads] (the shape of el) on H's device");
+    TORCH_CHECK(Y.device() == H.device() && dY.device() == H.device(), "H, Y and dY must be on one device");
+    gat_check_graph(H, n_out, row_pointers, column_index, part_pointers, part2Node);
+    gat_check_edge_term(ee, "ee", column_index, heads);
+    check_ids(t_edge_pos, "t_edge_pos");
+    TORCH_CHECK(t_edge_pos.dim() == 1 && t_edge_pos.numel() == nnz && t_ci->numel() == nnz && t_edge_pos.device() == H.device(),
+                "t_edge_pos and the transposed column_index must be [num_edges = ", nnz, "] on H's device");
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(H.device());
+    auto dH = fresh({n_in, width}, el.options()), d_el = fresh({n_out, (int64_t)heads}, el.options()),
+         d_er = fresh({n_in, (int64_t)heads}, el.options()), d_ee = fresh({nnz, (int64_t)heads}, el.options());
+    check_rc(gnna_gat_edge_backward_f32(H.data_ptr<float>(), ld_of(H), el.data_ptr<float>(), er.data_ptr<float>(), ee.data_ptr<float>(),
+                                        lse.data_ptr<float>(), Y.data_ptr<float>(), ld_of(Y), dY.data_ptr<float>(), ld_of(dY),
+                                        row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
+                                        part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), part2Node.size(0),
+                                        t_rp->data_ptr<int32_t>(), t_ci->data_ptr<int32_t>(), t_pp->data_ptr<int32_t>(),
+                                        t_p2n->data_ptr<int32_t>(), t_p2n->size(0), t_edge_pos.data_ptr<int32_t>(),
+                                        (float)negative_slope, (float)attn_drop, rng_seed, dH.data_ptr<float>(), width,
+                                        d_el.data_ptr<float>(), d_er.data_ptr<float>(), d_ee.data_ptr<float>(), n_out, n_in, nnz, heads,
+                                        (int)(width / heads), partSize, 0u, current_stream()));
+    return std::make_tuple(dH, d_el, d_er, d_ee);
+}
+
+torch::Tensor gat_alpha(const torch::Tensor &el, const torch::Tensor &er, const c10::optional<torch::Tensor> &ee, const torch::Tensor &lse,
+                        const torch::Tensor &row_pointers, const torch::Tensor &column_index, double negative_slope)
+{
+    check_floats(el, "el");
+    check_floats(er, "er");
+    check_floats(lse, "lse");
+    check_ids(row_pointers, "row_pointers");
+    check_ids(column_index, "column_index");
+    TORCH_CHECK(el.dim() == 2 && el.size(1) >= 1 && er.dim() == 2 && er.size(1) == el.size(1) && lse.sizes() == el.sizes(),
+                "el and lse must be [num_out_rows, heads], er [num_in_rows, heads]");
+    TORCH_CHECK(row_pointers.dim() == 1 && row_pointers.size(0) == el.size(0) + 1, "row_pointers must be [num_out_rows + 1]");
+    TORCH_CHECK(er.device() == el.device() && lse.device() == el.device() && row_pointers.device() == el.device() &&
+                column_index.device() == el.device(), "el, er, lse and the graph must be on one device");
+    const int heads = (int)el.size(1);
+    if (ee.has_value()) gat_check_edge_term(*ee, "ee", column_index, heads);
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(el.device());
+    auto alpha = fresh({column_index.numel(), (int64_t)heads}, el.options());
+    check_rc(gnna_gat_alpha_f32(el.data_ptr<float>(), er.data_ptr<float>(), ee.has_value() ? ee->data_ptr<float>() : nullptr,
+                                lse.data_ptr<float>(), row_pointers.data_ptr<int32_t>(), column_index.data_ptr<int32_t>(),
+                                (float)negative_slope, alpha.data_ptr<float>(), el.size(0), er.size(0), column_index.numel(), heads,
+                                current_stream()));
+    return alpha;
+}
+
 // Fused GATv2 attention (gnna_gatv2_forward_f32 / gnna_gatv2_backward_f32, gnna_gatv2.h): Hs [num_in_rows, heads * dim] (the source
 // side and the message), Hd [num_out_rows, heads * dim] with num_out_rows = row_pointers.numel() - 1, att [heads, dim].  One
 // (rectangular) entry for every structure; attn_drop = 0 is the plain function.  Hs and Hd may be the same tensor.
@@ -1148,6 +1248,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("part_pointers"), pybind11::arg("part2Node"),
           pybind11::arg("partSize"), pybind11::arg("negative_slope"), pybind11::arg("attn_drop"), pybind11::arg("rng_seed"),
           pybind11::arg("transposed") = pybind11::none());
+    m.def("gat_edge_forward", &gat_edge_forward,
+          "gat_forward_drop with a per-edge score term (extension; gnna_gat_edge.h): z = el[i, h] + er[col(e), h] + ee[e, h]; "
+          "ee [num_edges, heads], edge-major, indexed like column_index -> (Y, lse)",
+          pybind11::arg("H"), pybind11::arg("el"), pybind11::arg("er"), pybind11::arg("ee"), pybind11::arg("row_pointers"),
+          pybind11::arg("column_index"), pybind11::arg("part_pointers"), pybind11::arg("part2Node"), pybind11::arg("partSize"),
+          pybind11::arg("negative_slope") = 0.2, pybind11::arg("attn_drop") = 0.0, pybind11::arg("rng_seed") = 0);
+    m.def("gat_edge_backward", &gat_edge_backward,
+          "gradient of gat_edge_forward for the same ee, attn_drop and rng_seed -> (dH, d_el, d_er, d_ee) (extension; gnna_gat_edge.h).  "
+          "t_edge_pos [num_edges]: the forward position of every position of the transposed structure (transpose_csr's t_perm with "
+          "`transposed`, the reverse-edge map of a symmetric graph without)",
+          pybind11::arg("H"), pybind11::arg("el"), pybind11::arg("er"), pybind11::arg("ee"), pybind11::arg("lse"), pybind11::arg("Y"),
+          pybind11::arg("dY"), pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("part_pointers"),
+          pybind11::arg("part2Node"), pybind11::arg("t_edge_pos"), pybind11::arg("partSize"), pybind11::arg("negative_slope") = 0.2,
+          pybind11::arg("attn_drop") = 0.0, pybind11::arg("rng_seed") = 0, pybind11::arg("transposed") = pybind11::none());
+    m.def("gat_alpha", &gat_alpha,
+          "attention coefficients edge for edge (extension; gnna_gat_edge.h) -> alpha [num_edges, heads] = exp(leaky_relu(el[i, h] + "
+          "er[col(e), h] + ee[e, h]) - lse[i, h]), undropped, 0 for a skipped edge; ee None: those of gat_forward",
+          pybind11::arg("el"), pybind11::arg("er"), pybind11::arg("ee"), pybind11::arg("lse"), pybind11::arg("row_pointers"),
+          pybind11::arg("column_index"), pybind11::arg("negative_slope") = 0.2);
     m.def("gatv2_forward", &gatv2_forward,
           "fused multi-head GATv2 attention -> (Y, lse) (extension; gnna_gatv2.h): z = sum_d att[h, d] * leaky_relu(Hs[col(e), h, d] + "
           "Hd[i, h, d]), Y[i, h] = sum_e exp(z - lse[i, h]) * k * Hs[col(e), h] with the dropout factor k of gat_forward_drop (1 at "

@@ -82,6 +82,11 @@ def build_parser():
                         "P in [0, 1); 0.6 in the GAT paper).  With --fused_attention True the mask is made inside the kernels from "
                         "one host-drawn seed per layer and step, with --fanout too; a captured HIP graph would replay one seed and "
                         "so one mask, one more reason --hip_graph stays refused for --model gat (MI355X addition); --model gatv2 and --model transformer likewise")
+    p.add_argument('--edge_dim', type=int, default=0,
+                   help="--model gat: D > 0 gives both layers edge features in the score (GATConv(edge_dim=D): one scalar per edge "
+                        "and head before the leaky ReLU, as PyG's GATConv(edge_dim=...)).  The driver draws synthetic features "
+                        "[nnz, D] from a seeded generator once the graph's CSR is fixed; with --fanout every block takes the rows of "
+                        "its own edges (SampledBlock.edge_ids).  0: none (MI355X addition)")
     p.add_argument('--directed', default='False', **tf,
                    help="True: the graph is directed -- every backward pass aggregates over the transposed structure, built on "
                         "the device right after the partition (False: the structure is taken to be symmetric, as the "
@@ -143,6 +148,10 @@ def main(argv=None, capture=None):
         raise SystemExit("--attn_drop drops attention coefficients: run it with --model gat (got --model %s)" % args.model)
     if not 0.0 <= args.attn_drop < 1.0:
         raise SystemExit("--attn_drop must be in [0, 1) (got %r)" % args.attn_drop)
+    if args.edge_dim < 0:
+        raise SystemExit("--edge_dim must be >= 0 (got %d)" % args.edge_dim)
+    if args.edge_dim > 0 and args.model != 'gat':
+        raise SystemExit("--edge_dim puts edge features into the GAT score: run it with --model gat (got --model %s)" % args.model)
     fanouts = None
     if args.fanout is not None:
         if attention and not flag(args.fused_attention):
@@ -265,8 +274,17 @@ def main(argv=None, capture=None):
             _gnna_lib.prepare_graph(t_graph.column_index, t_graph.partPtr, t_graph.part2Node, dataset.num_nodes,
                                     dataset.num_nodes, inputInfo.partSize, _prep_widths)
     degrees = inputInfo.degrees
+    edge_attr = None
+    if args.edge_dim > 0:
+        # synthetic edge features in the order of the column_index the Decider has settled on (a renumbering is behind us)
+        gen = torch.Generator(device='cpu').manual_seed(0xED6E)
+        edge_attr = torch.randn(inputInfo.column_index.numel(), args.edge_dim, generator=gen).to(device)
+        if inputInfo.directed:
+            inputInfo.transposed().perm           # (the source-side pass reads the edge term through the permutation)
+        elif flag(args.fused_attention) and args.fanout is None:
+            inputInfo.reverse_edges()             # (... through the reverse-edge map: built here, not inside the first step)
     if capture is not None:
-        capture.update(dataset=dataset, inputInfo=inputInfo, args=args)
+        capture.update(dataset=dataset, inputInfo=inputInfo, args=args, edge_attr=edge_attr)
 
     # ---- single-SpMM verification / profiling (GNNA_main.py:116-137) -------------------------------
     if verify_spmm or single_spmm:
@@ -298,20 +316,28 @@ def main(argv=None, capture=None):
     elif args.model == 'gat':
         fused = flag(args.fused_attention)
 
+        edge_dim = args.edge_dim if args.edge_dim > 0 else None
+
+        def edges_of(block):         # the edge features of a block's own edges, or of the whole graph
+            if edge_attr is None:
+                return None
+            return edge_attr if block is None else edge_attr.index_select(0, block.edge_ids.long())
+
         class Net(torch.nn.Module):
             def __init__(self):
                 super().__init__()
                 self.conv1 = GATConv(dataset.num_features, args.hidden, heads=args.heads, concat=True, fused=fused,
-                                     attn_drop=args.attn_drop)
-                self.conv2 = GATConv(args.hidden * args.heads, dataset.num_classes, heads=1, fused=fused, attn_drop=args.attn_drop)
+                                     attn_drop=args.attn_drop, edge_dim=edge_dim)
+                self.conv2 = GATConv(args.hidden * args.heads, dataset.num_classes, heads=1, fused=fused, attn_drop=args.attn_drop,
+                                     edge_dim=edge_dim)
 
             def forward(self, x=None, blocks=None):
                 if blocks is not None:      # a sampled mini-batch (--fused_attention True): x holds blocks[0]'s source rows
-                    x = F.elu(self.conv1(x, blocks[0]))
-                    x = self.conv2(x, blocks[1])
+                    x = F.elu(self.conv1(x, blocks[0], edge_attr=edges_of(blocks[0])))
+                    x = self.conv2(x, blocks[1], edge_attr=edges_of(blocks[1]))
                     return F.log_softmax(x, dim=1)
-                x = F.elu(self.conv1(dataset.x, inputInfo.set_input()))
-                x = self.conv2(x, inputInfo.set_hidden())
+                x = F.elu(self.conv1(dataset.x, inputInfo.set_input(), edge_attr=edges_of(None)))
+                x = self.conv2(x, inputInfo.set_hidden(), edge_attr=edges_of(None))
                 return F.log_softmax(x, dim=1)
     elif args.model == 'gatv2':
         fused = flag(args.fused_attention)
@@ -432,7 +458,7 @@ def main(argv=None, capture=None):
         # one epoch = the seeds 0 .. num_nodes-1 in batches; every batch samples its blocks with a fresh rng_seed, gathers
         # the features of the first block's source nodes and makes one step on the batch's labels
         from .sampling import NeighborSampler
-        sampler = NeighborSampler(inputInfo, fanouts)
+        sampler = NeighborSampler(inputInfo, fanouts, want_edge_ids=args.edge_dim > 0)      # (the blocks' edge features)
         all_nodes = torch.arange(dataset.num_nodes, dtype=torch.int32, device=device)
         batches = [all_nodes[lo: lo + args.batch_size] for lo in range(0, dataset.num_nodes, args.batch_size)]
         drawn = [0]

@@ -741,6 +741,65 @@ class GATAttention(Function):
         return (dH if need[0] else None, d_el if need[1] else None, d_er if need[2] else None) + rest
 
 
+class GATEdgeAttention(Function):
+    """GATAttention with a per-edge score term (libgnna gnna_gat_edge_forward_f32 / gnna_gat_edge_backward_f32,
+    include/gnna_gat_edge.h): ``GATEdgeAttention.apply(H, el, er, ee, inputInfo, negative_slope, attn_drop=0.0, rng_seed=0) -> Y``
+    with ee [nnz, heads] float32, edge-major in the order of ``inputInfo.column_index``, and
+    alpha = softmax over row i of leaky_relu(el[i, h] + er[col(e), h] + ee[e, h]).  ee is one scalar per (edge, head) -- what
+    PyG's GATConv(edge_dim=...) adds to the score -- and a gradient-carrying input: the backward returns d_ee [nnz, heads] beside
+    the gradients of H, el and er.  Saved: the node-sized tensors of GATAttention and ee; alpha is still made inside the gathers.
+
+    The source-side pass of the backward finds an edge's ee through a position map of nnz x 4 bytes: ``info.reverse_edges()`` on
+    a graph whose structure is symmetric (``require_symmetric`` first, as GATAttention), the ``perm`` of ``info.transposed()`` on
+    a ``directed`` graph or a sampling.SampledBlock (whose ee rows are those of the block's own edges)."""
+
+    @staticmethod
+    def forward(ctx, H, el, er, ee, inputInfo, negative_slope, attn_drop=0.0, rng_seed=0):
+        info = inputInfo
+        attn_drop, rng_seed = float(attn_drop), int(rng_seed) & (2 ** 64 - 1)
+        if not 0.0 <= attn_drop < 1.0:
+            raise ValueError(f"GATEdgeAttention: attn_drop must be in [0, 1) (got {attn_drop})")
+        if _is_block(info):
+            H = _block_features(H, info, "GATEdgeAttention")
+            if er.dim() != 2 or er.shape[0] != info.num_src or el.dim() != 2 or el.shape[0] != info.num_dst or \
+                    el.shape[1] != er.shape[1]:
+                raise ValueError(f"GATEdgeAttention on a SampledBlock: el must be [num_dst = {info.num_dst}, heads] and er "
+                                 f"[num_src = {info.num_src}, heads] (got {tuple(el.shape)} and {tuple(er.shape)})")
+        nnz = info.column_index.numel()
+        if ee.dim() != 2 or el.dim() != 2 or tuple(ee.shape) != (nnz, el.shape[1]):
+            raise ValueError(f"GATEdgeAttention: ee must be [nnz = {nnz}, heads = {el.shape[-1]}] in the order of column_index "
+                             f"(got {tuple(ee.shape)})")
+        if any(t.dtype != torch.float32 for t in (H, el, er, ee)):
+            raise TypeError(f"GATEdgeAttention: float32 only (got {H.dtype}, {el.dtype}, {er.dtype}, {ee.dtype})")
+        el, er, ee = el.contiguous(), er.contiguous(), ee.contiguous()
+        graph = (info.row_pointers, info.column_index, info.partPtr, info.part2Node, info.partSize, float(negative_slope))
+        Y, lse = GNNA.gat_edge_forward(H, el, er, ee, *graph, attn_drop, rng_seed)
+        ctx.info, ctx.negative_slope, ctx.attn_drop, ctx.rng_seed = info, float(negative_slope), attn_drop, rng_seed
+        ctx.save_for_backward(H, el, er, ee, lse, Y)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        H, el, er, ee, lse, Y = ctx.saved_tensors
+        info = ctx.info
+        rest = (None,) * (len(ctx.needs_input_grad) - 4)
+        if not any(ctx.needs_input_grad[:4]):
+            return (None, None, None, None) + rest
+        transposed = None
+        if _is_block(info) or _is_directed(info):
+            t = info.transposed()
+            transposed, t_edge_pos = [t.row_pointers, t.column_index, t.partPtr, t.part2Node], t.perm
+        else:
+            from .decider import inputProperty
+            inputProperty.require_symmetric(info)
+            t_edge_pos = info.reverse_edges()
+        dH, d_el, d_er, d_ee = GNNA.gat_edge_backward(H, el, er, ee, lse, Y, dY, info.row_pointers, info.column_index, info.partPtr,
+                                                      info.part2Node, t_edge_pos, info.partSize, ctx.negative_slope, ctx.attn_drop,
+                                                      ctx.rng_seed, transposed)
+        need = ctx.needs_input_grad
+        return (dH if need[0] else None, d_el if need[1] else None, d_er if need[2] else None, d_ee if need[3] else None) + rest
+
+
 class GATConv(Module):
     """Additive graph attention (GAT): H = X W; per head h, s[e] = leaky_relu(<H_h[row(e)], a_l[h]> + <H_h[col(e)], a_r[h]>),
     alpha = edge softmax of s over every row, Y_h = A_alpha H_h.  Heads are concatenated (concat=True, [N, heads * out]) or
@@ -760,9 +819,18 @@ class GATConv(Module):
     unless ``forward(..., rng_seed=...)`` gives it, and kept as ``self.last_rng_seed``.  fused=False:
     ``torch.nn.functional.dropout`` on alpha -- the same distribution from another generator (torch's device generator, one draw
     per edge position), so the two paths drop different edges for the same seed, and only the fused one drops duplicate edges
-    together."""
+    together.
+    edge_dim: edge features in the score, as PyG's GATConv(edge_dim=...): ``forward(..., edge_attr=...)`` takes edge_attr
+    [nnz, edge_dim] float32 in the order of ``inputInfo.column_index`` (for a block: the rows of the block's own edges, which the
+    caller selects with ``block.edge_ids``), and every edge adds ee[e, h] = <(edge_attr[e] weights_edge)_h, att_e[h]> to the
+    score before the leaky ReLU.  The layer forms M[d, h] = sum_c weights_edge[d, h out + c] att_e[h, c] and ee = edge_attr @ M
+    -- the same function without the [nnz, heads * out] intermediate; autograd carries d_ee to weights_edge, att_e and
+    edge_attr.  fused=True runs GATEdgeAttention (ee and d_ee, [nnz, heads], are the only per-edge tensors); fused=False adds ee
+    to the composed score.
+    ``forward(..., return_attention_weights=True)`` returns (Y, alpha) with alpha [nnz, heads], the undropped coefficients
+    edge for edge, detached (fused: libgnna gnna_gat_alpha_f32 after a second forward pass for the log-sum-exp; composed: its softmax)."""
 
-    def __init__(self, input_dim, output_dim, heads=1, concat=True, negative_slope=0.2, fused=False, attn_drop=0.0):
+    def __init__(self, input_dim, output_dim, heads=1, concat=True, negative_slope=0.2, fused=False, attn_drop=0.0, edge_dim=None):
         super().__init__()
         self.attn_drop = float(attn_drop)
         if not 0.0 <= self.attn_drop < 1.0:
@@ -773,6 +841,12 @@ class GATConv(Module):
         self.weights = Parameter(torch.empty(input_dim, self.heads * self.out_dim))
         self.att_l = Parameter(torch.empty(self.heads, self.out_dim))
         self.att_r = Parameter(torch.empty(self.heads, self.out_dim))
+        self.edge_dim = None if edge_dim is None else int(edge_dim)
+        if self.edge_dim is not None:
+            if self.edge_dim < 1:
+                raise ValueError(f"GATConv: edge_dim must be positive (got {edge_dim})")
+            self.weights_edge = Parameter(torch.empty(self.edge_dim, self.heads * self.out_dim))
+            self.att_e = Parameter(torch.empty(self.heads, self.out_dim))
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -781,8 +855,29 @@ class GATConv(Module):
             self.weights.uniform_(-bound, bound)
             self.att_l.uniform_(-bound, bound)
             self.att_r.uniform_(-bound, bound)
+            if self.edge_dim is not None:
+                self.weights_edge.uniform_(-bound, bound)
+                self.att_e.uniform_(-bound, bound)
 
-    def forward(self, X, inputInfo, rng_seed=None):
+    def _edge_scores(self, edge_attr, inputInfo):
+        """ee [nnz, heads] of the layer's edge features, or None for a layer without them."""
+        if self.edge_dim is None:
+            if edge_attr is not None:
+                raise ValueError("GATConv: edge_attr given to a layer built without edge_dim")
+            return None
+        if edge_attr is None:
+            raise ValueError(f"GATConv(edge_dim={self.edge_dim}): forward needs edge_attr [nnz, {self.edge_dim}]")
+        nnz = inputInfo.column_index.numel()
+        if edge_attr.dim() != 2 or tuple(edge_attr.shape) != (nnz, self.edge_dim):
+            raise ValueError(f"GATConv: edge_attr must be [nnz = {nnz}, edge_dim = {self.edge_dim}] in the order of column_index "
+                             f"(got {tuple(edge_attr.shape)})")
+        if edge_attr.dtype != torch.float32 or _x16_dtype(edge_attr) is not None:
+            raise TypeError("GATConv with edge features computes in float32 only: 16-bit features and torch.autocast are not "
+                            f"supported (got {edge_attr.dtype}{', inside torch.autocast' if edge_attr.dtype == torch.float32 else ''})")
+        M = (self.weights_edge.view(self.edge_dim, self.heads, self.out_dim) * self.att_e).sum(-1)      # [edge_dim, heads]
+        return torch.mm(edge_attr, M)
+
+    def forward(self, X, inputInfo, rng_seed=None, edge_attr=None, return_attention_weights=False):
         block = _is_block(inputInfo)
         drop = self.training and self.attn_drop > 0.0
         if block:
@@ -792,28 +887,61 @@ class GATConv(Module):
                 raise TypeError("GATConv on a SampledBlock computes in float32 only: 16-bit features and torch.autocast are not "
                                 f"supported (got {X.dtype}{', inside torch.autocast' if X.dtype == torch.float32 else ''})")
             X = _block_features(X, inputInfo, "GATConv")
+        ee = self._edge_scores(edge_attr, inputInfo)
+        if ee is not None and (X.dtype != torch.float32 or _x16_dtype(X) is not None):
+            raise TypeError("GATConv with edge features computes in float32 only: 16-bit features and torch.autocast are not "
+                            f"supported (got {X.dtype}{', inside torch.autocast' if X.dtype == torch.float32 else ''})")
         H = torch.mm(X, self.weights)
         Hh = H.view(X.shape[0], self.heads, self.out_dim)
         n = inputInfo.num_dst if block else X.shape[0]      # rows of the result
         el = ((Hh[:n] if block else Hh) * self.att_l).sum(-1)      # [N, heads] ([num_dst, heads]): destination side
         er = (Hh * self.att_r).sum(-1)          # [N, heads] ([num_src, heads]): source side
+        weights = None
         if self.fused and drop:
             if rng_seed is None:
                 rng_seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())       # (a CPU tensor: no device synchronisation)
             self.last_rng_seed = int(rng_seed)
-            Y = GATAttention.apply(H, el, er, inputInfo, self.negative_slope, self.attn_drop, self.last_rng_seed)
+            if ee is not None:
+                Y = GATEdgeAttention.apply(H, el, er, ee, inputInfo, self.negative_slope, self.attn_drop, self.last_rng_seed)
+            else:
+                Y = GATAttention.apply(H, el, er, inputInfo, self.negative_slope, self.attn_drop, self.last_rng_seed)
         elif self.fused:
-            Y = GATAttention.apply(H, el, er, inputInfo, self.negative_slope)
+            if ee is not None:
+                Y = GATEdgeAttention.apply(H, el, er, ee, inputInfo, self.negative_slope)
+            else:
+                Y = GATAttention.apply(H, el, er, inputInfo, self.negative_slope)
         else:
             rows, ci = inputInfo.edge_rows(), inputInfo.column_index
-            s = torch.nn.functional.leaky_relu(el.index_select(0, rows) + er.index_select(0, ci), self.negative_slope)
+            z = el.index_select(0, rows) + er.index_select(0, ci)
+            if ee is not None:
+                z = z + ee
+            s = torch.nn.functional.leaky_relu(z, self.negative_slope)
             alpha = EdgeSoftmax.apply(s.t().contiguous(), inputInfo.row_pointers)      # [heads, nnz]
+            if return_attention_weights:
+                weights = alpha.detach().t().contiguous()
             if drop:
                 alpha = torch.nn.functional.dropout(alpha, self.attn_drop, training=True)
             Y = EdgeWeightedAggregate.apply(H, alpha, inputInfo)
-        if self.concat or self.heads == 1:
-            return Y
-        return Y.view(n, self.heads, self.out_dim).mean(1)
+        if self.fused and return_attention_weights:
+            weights = _fused_attention_weights(H, el, er, ee, inputInfo, self.negative_slope)
+        if not (self.concat or self.heads == 1):
+            Y = Y.view(n, self.heads, self.out_dim).mean(1)
+        return (Y, weights) if return_attention_weights else Y
+
+
+def _fused_attention_weights(H, el, er, ee, info, negative_slope):
+    """alpha [nnz, heads] of the fused attention (libgnna gnna_gat_alpha_f32), edge for edge from el, er, ee and the log-sum-exp
+    of the rows.  The autograd Functions keep their lse to themselves, so this asks the forward entry for it once more (without
+    dropout: lse is that of the undropped scores) -- the price of the option, a second forward pass."""
+    with torch.no_grad():
+        H, el, er = H.detach(), el.detach().contiguous(), er.detach().contiguous()
+        graph = (info.row_pointers, info.column_index, info.partPtr, info.part2Node, info.partSize, float(negative_slope))
+        if ee is None:
+            lse = GNNA.gat_forward(H, el, er, *graph)[1]
+        else:
+            ee = ee.detach().contiguous()
+            lse = GNNA.gat_edge_forward(H, el, er, ee, *graph)[1]
+        return GNNA.gat_alpha(el, er, ee, lse, info.row_pointers, info.column_index, float(negative_slope))
 
 
 class GATv2Attention(Function):
