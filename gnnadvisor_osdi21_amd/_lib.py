@@ -135,6 +135,11 @@ GATEDGE_SIGNATURES = {
     # el, er, ee, lse, row_pointers, column_index, slope, alpha, num_out_rows, num_in_rows, num_edges, heads, stream
     "gnna_gat_alpha_f32": (i, [p] * 6 + [f, p, i64, i64, i64, i, p]),
 }
+# neighbor statistics from one gather (include/gnna_stats.h): a sixth table
+STATS_SIGNATURES = {
+    # input, ld_in, num_in_rows, the partition, (sum, ld) (sumsq, ld), (max, ld, argmax, ld) (min, ld, argmin, ld), num_out_rows, dim, num_parts, partSize, flags, stream
+    "gnna_agg_stats_ld_f32": (i, [p, i64, i64, p, p, p] + [p, i64] * 6 + [i64, i, i64, i, u, p]),
+}
 del p, i, i64, u, u64, f, s, pd, pi, pi64
 EXPORTS = tuple(SIGNATURES)
 EXT_EXPORTS = tuple(EXT_SIGNATURES)
@@ -144,7 +149,8 @@ DOTATTN_EXPORTS = tuple(DOTATTN_SIGNATURES)
 SIGNATURE_TABLES = (SIGNATURES, EXT_SIGNATURES, GATV2_SIGNATURES, DOTATTN_SIGNATURES)
 # the tables of later headers, which load() applies after those (SIGNATURE_TABLES restates the four headers before them and stays)
 GATEDGE_EXPORTS = tuple(GATEDGE_SIGNATURES)
-LATER_SIGNATURE_TABLES = (GATEDGE_SIGNATURES,)
+STATS_EXPORTS = tuple(STATS_SIGNATURES)
+LATER_SIGNATURE_TABLES = (GATEDGE_SIGNATURES, STATS_SIGNATURES)
 
 
 def load() -> ctypes.CDLL:
@@ -759,6 +765,47 @@ def scatter_arg_ld(grad_out, arg, column_index, num_in_rows, out=None, accumulat
     _call(grad_out.device, "gnna_scatter_arg_ld_f32", gp, ld_go, ap, ld_arg, column_index.data_ptr(), n_out, op_, ld_gi,
           int(num_in_rows), dim, _flags(accumulate))
     return out
+
+
+STATS = ("sum", "sumsq", "max", "min")
+
+
+def agg_stats_ld(X, column_index, part_pointers, part2Node, num_out_rows=None, partSize=32, want=STATS, out=None):
+    """gnna_agg_stats_ld_f32 (include/gnna_stats.h): the statistics named in `want` over the edges e of every row i of
+    x = X[column_index[e], f], from one walk over the ids and one load of every source row -- "sum", "sumsq" (sum of x * x), "max"
+    and "min", the last two with the smallest winning position e ("argmax" / "argmin", int32; -1 and 0 for rows without edges) and
+    the bits agg_reduce_ld gives.  -> a dict with a tensor [num_out_rows, dim] for every name wanted, "argmax" / "argmin" next to
+    "max" / "min".  `X` may be a row-strided view (stride(1) == 1), and so may the tensors of `out`, a dict that supplies some of
+    the results (float32; int32 for the positions, which are not computed when `out` holds the value but not them)."""
+    _need_device(X, "aggregation")
+    want = tuple(want)
+    unknown = [w for w in want if w not in STATS]
+    if unknown or not want:
+        raise ValueError(f"want must name some of {STATS} (got {want!r})")
+    xp, n_in, dim, ld_in = _rows_view(X, "X")
+    n_out = n_in if num_out_rows is None else int(num_out_rows)
+    out = dict(out or {})
+    res, args = {}, []
+    for name in STATS:
+        wanted = name in want
+        val = None
+        if wanted:
+            val, vp, ld = _out_rows(out.get(name), n_out, dim, X.device)
+            res[name] = val
+        args += [vp if wanted else None, ld if wanted else dim]
+        if name in ("max", "min"):
+            arg = None
+            if wanted and ("arg" + name in out or name not in out):
+                arg = out.get("arg" + name)
+                if arg is None:
+                    arg = _fresh_output((n_out, dim), X.device, torch.int32)
+                assert arg.device == X.device
+                ap, ld_arg = _arg_view(arg, n_out, dim, "arg" + name)
+                res["arg" + name] = arg
+            args += [ap if arg is not None else None, ld_arg if arg is not None else dim]
+    _call(X.device, "gnna_agg_stats_ld_f32", xp, ld_in, n_in, column_index.data_ptr(), part_pointers.data_ptr(), part2Node.data_ptr(),
+          *args, n_out, dim, part2Node.numel(), int(partSize), 0)
+    return res
 
 
 def _node_heads(t, n, what):

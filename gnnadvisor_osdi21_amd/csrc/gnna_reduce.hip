@@ -5,7 +5,7 @@
 // No counterpart in the reference (its kernels only sum, GNNAdvisor_kernel.cu:186-259); the partition arguments are those of
 // gnna_agg_ld_f32.
 //
-// Everything here is ONE operation: the unsigned 64-bit maximum over the edges of a row of the key
+// Everything here is ONE operation: the unsigned 64-bit maximum over the edges of a row of the key (gnna_keys.h)
 //       (order(x) << 32) | (0xFFFFFFFF - edge position)
 // where order() maps the 32 bits of a float to an unsigned that orders like the float (inverted for min).  The largest key
 // holds the extreme value and, among equal values, the smallest edge position.  An unsigned maximum is associative and
@@ -35,48 +35,10 @@
 #include "gnna.h"
 #include "gnna_device.h"
 #include "gnna_internal.h"
+#include "gnna_keys.h"
 
 namespace gnna {
 namespace {
-
-typedef unsigned long long u64;
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));    // global_load_dwordx4 needs dword alignment only
-
-// the bits of a float -> an unsigned that orders like the float (OP = GNNA_REDUCE_MIN: in the opposite order)
-template <int OP>
-__device__ __forceinline__ uint32_t order_of(float v)
-{
-    const uint32_t b = __float_as_uint(v);
-    const uint32_t m = (uint32_t)((int32_t)b >> 31);
-    if constexpr (OP == GNNA_REDUCE_MAX) return b ^ (m | 0x80000000u);
-    else return b ^ (~m & 0x7fffffffu);
-}
-__device__ __forceinline__ float value_of(uint32_t k, int op)
-{
-    if (op != GNNA_REDUCE_MAX) k = ~k;
-    return __uint_as_float((k & 0x80000000u) ? k ^ 0x80000000u : ~k);
-}
-
-__device__ __forceinline__ u64 pack(uint32_t hi, uint32_t lo) { return ((u64)hi << 32) | lo; }
-__device__ __forceinline__ u64 umax64(u64 a, u64 b) { return a > b ? a : b; }
-
-// max of the key over the lane pair (l, l ^ STRIDE), in both lanes
-template <int STRIDE>
-__device__ __forceinline__ u64 pair_max(u64 k)
-{
-    const uint32_t hi = (uint32_t)(k >> 32), lo = (uint32_t)k;
-    if constexpr (STRIDE == 32) {
-        auto h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-        auto l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-        return umax64(pack(h[0], l[0]), pack(h[1], l[1]));      // (own, partner) or (partner, own): the same order in both words
-    } else if constexpr (STRIDE == 16) {
-        auto h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-        auto l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-        return umax64(pack(h[0], l[0]), pack(h[1], l[1]));
-    } else {
-        return umax64(k, pack((uint32_t)__shfl_xor((int)hi, STRIDE), (uint32_t)__shfl_xor((int)lo, STRIDE)));
-    }
-}
 
 struct ReduceArgs {
     const float *X;             // source rows
@@ -186,14 +148,7 @@ reduce_kernel(const ReduceArgs p)
             }
             // ---- the R partial rows of the wavefront -> one row, in every lane ---------------------------------------------
 #pragma unroll
-            for (int q = 0; q < 4; q++) {
-                if constexpr (R >= 2) best[q] = pair_max<32>(best[q]);
-                if constexpr (R >= 4) best[q] = pair_max<16>(best[q]);
-                if constexpr (R >= 8) best[q] = pair_max<8>(best[q]);
-                if constexpr (R >= 16) best[q] = pair_max<4>(best[q]);
-                if constexpr (R >= 32) best[q] = pair_max<2>(best[q]);
-                if constexpr (R >= 64) best[q] = pair_max<1>(best[q]);
-            }
+            for (int q = 0; q < 4; q++) best[q] = partial_rows_max<R>(best[q]);
             if (sub == 0 && col_ok) {
                 u64 *dst = p.K + (size_t)row * (size_t)p.D + (size_t)mycol;
 #pragma unroll
@@ -215,13 +170,9 @@ reduce_finish_kernel(const u64 *__restrict__ K, float *__restrict__ out, size_t 
     const size_t n = rows * (size_t)D;
     for (size_t i = tid; i < n; i += nthreads) {
         const size_t r = i / (unsigned)D, c = i - r * (unsigned)D;
-        const u64 k = K[i];
-        float v = 0.f;
-        int32_t pos = -1;
-        if (k != 0ull) {
-            v = value_of((uint32_t)(k >> 32), op);
-            pos = (int32_t)(0xFFFFFFFFu - (uint32_t)k);
-        }
+        float v;
+        int32_t pos;
+        key_result(K[i], op, &v, &pos);
         if (relu) v = v > 0.f ? v : (v != v ? v : 0.f);         // NaN stays NaN, as torch.relu
         out[r * ld_out + c] = v;
         if (arg) arg[r * ld_arg + c] = pos;

@@ -36,6 +36,7 @@
 #include "gnna_gatv2.h"
 #include "gnna_dotattn.h"
 #include "gnna_gat_edge.h"
+#include "gnna_stats.h"
 
 #define CHECK_CUDA(x) TORCH_CHECK(x.is_cuda(), #x " must be a CUDA tensor")
 #define CHECK_CONTIGUOUS(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -413,6 +414,39 @@ aggregate_reduce(int op, const torch::Tensor &input, const torch::Tensor &column
                                     ld_of(out), arg.has_value() ? arg->data_ptr<int32_t>() : nullptr, dim, n, (int)dim,
                                     part2Node.size(0), partSize, relu ? GNNA_EPILOGUE_RELU : 0u, current_stream()));
     return std::make_tuple(out, arg);
+}
+
+// Sum, sum of squares, max and min over every row's neighbours from one gather (gnna_agg_stats_ld_f32) -> (sum, sumsq, max, argmax,
+// min, argmin), each [num_out_rows, dim]; None for a statistic that was not asked for (argmax / argmin come with max / min).
+// Strided X as aggregate_ld; num_out_rows < 0: as many rows as X has.
+std::tuple<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>,
+           c10::optional<torch::Tensor>, c10::optional<torch::Tensor>>
+aggregate_stats(const torch::Tensor &input, const torch::Tensor &column_index, const torch::Tensor &part_pointers,
+                const torch::Tensor &part2Node, int partSize, int64_t num_out_rows, bool want_sum, bool want_sumsq, bool want_max,
+                bool want_min)
+{
+    CHECK_CUDA(input);
+    TORCH_CHECK(input.dim() == 2, "input must be 2-D [num_nodes, dim]");
+    CHECK_F32(input);
+    check_partition(column_index, part_pointers, part2Node);
+    TORCH_CHECK(want_sum || want_sumsq || want_max || want_min, "no statistic asked for");
+    TORCH_CHECK(column_index.device() == input.device(), "input and column_index must be on one device");
+    TORCH_CHECK(input.size(1) >= 1, "input must have at least one column");
+    check_rows(input, "input");
+    const int64_t n_in = input.size(0), dim = input.size(1), n = num_out_rows < 0 ? n_in : num_out_rows;
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(input.device());
+    c10::optional<torch::Tensor> sum, sumsq, mx, amx, mn, amn;
+    if (want_sum) sum = fresh({n, dim}, input.options());
+    if (want_sumsq) sumsq = fresh({n, dim}, input.options());
+    if (want_max) { mx = fresh({n, dim}, input.options()); amx = fresh({n, dim}, input.options().dtype(at::kInt)); }
+    if (want_min) { mn = fresh({n, dim}, input.options()); amn = fresh({n, dim}, input.options().dtype(at::kInt)); }
+    auto fp = [](const c10::optional<torch::Tensor> &t) { return t.has_value() ? t->data_ptr<float>() : nullptr; };
+    auto ip = [](const c10::optional<torch::Tensor> &t) { return t.has_value() ? t->data_ptr<int32_t>() : nullptr; };
+    check_rc(gnna_agg_stats_ld_f32(input.data_ptr<float>(), ld_of(input), n_in, column_index.data_ptr<int32_t>(),
+                                   part_pointers.data_ptr<int32_t>(), part2Node.data_ptr<int32_t>(), fp(sum), dim, fp(sumsq), dim,
+                                   fp(mx), dim, ip(amx), dim, fp(mn), dim, ip(amn), dim, n, (int)dim, part2Node.size(0), partSize, 0u,
+                                   current_stream()));
+    return std::make_tuple(sum, sumsq, mx, amx, mn, amn);
 }
 
 // Backward of aggregate_reduce (gnna_scatter_arg_ld_f32): grad_in[column_index[arg[i, f]], f] += grad_out[i, f], arg >= 0.
@@ -1215,6 +1249,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           pybind11::arg("op"), pybind11::arg("X"), pybind11::arg("column_index"), pybind11::arg("partPtr"),
           pybind11::arg("part2Node"), pybind11::arg("partSize"), pybind11::arg("out") = pybind11::none(),
           pybind11::arg("want_arg") = true, pybind11::arg("relu") = false);
+    m.def("aggregate_stats", &aggregate_stats,
+          "sum, sum of squares, max and min over every row's neighbours from one gather (extension) -> (sum, sumsq, max, argmax, min, "
+          "argmin); None for what was not asked for; the extrema are aggregate_reduce's bits",
+          pybind11::arg("X"), pybind11::arg("column_index"), pybind11::arg("partPtr"), pybind11::arg("part2Node"),
+          pybind11::arg("partSize"), pybind11::arg("num_out_rows") = -1, pybind11::arg("want_sum") = true,
+          pybind11::arg("want_sumsq") = true, pybind11::arg("want_max") = true, pybind11::arg("want_min") = true);
     m.def("scatter_arg", &scatter_arg,
           "backward of aggregate_reduce (extension): grad_in[column_index[arg[i, f]], f] += grad_out[i, f] for arg >= 0",
           pybind11::arg("grad_out"), pybind11::arg("arg"), pybind11::arg("column_index"), pybind11::arg("num_in_rows"));

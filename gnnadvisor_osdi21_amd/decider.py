@@ -183,7 +183,9 @@ def expected_aggregations(model, in_dim, hidden, classes, epochs=REFERENCE_EPOCH
     (scatter_arg) is num_nodes x width work, not a gather, and the first layer's features need no gradient.
     R-GCN (main.py --model rgcn, two ops.RGCNConv layers, aggregate-first): an aggregation into B x D columns gathers D-wide rows,
     so every layer gathers at its INPUT width -- forward, and once more for the coefficient gradient when the layer has bases;
-    the second layer's feature gradient gathers rows of B x hidden floats (B = num_bases, or num_relations without bases)."""
+    the second layer's feature gradient gathers rows of B x hidden floats (B = num_bases, or num_relations without bases).
+    PNA (main.py --model pna, two ops.PNAConv layers): every layer gathers once per step at its INPUT width (all its statistics
+    come from that one gather), and the backward of every layer but the first sums [a | b] at twice that width."""
     units = lambda w: (int(w) + 63) // 64
     out = []
     if model == "rgcn":
@@ -201,6 +203,9 @@ def expected_aggregations(model, in_dim, hidden, classes, epochs=REFERENCE_EPOCH
             else:
                 out.append((a, (2 if needs_dx else 1) * epochs))
         return out
+    if model == "pna":
+        # one gather per layer and step at the layer's input width; the backward of every layer but the first sums [a | b]
+        return [(in_dim, epochs), (hidden, epochs), (2 * hidden, epochs)]
     if model == "gat":
         return [(hidden, 2 * heads * epochs), (classes, 2 * epochs)]
     if model == "gin":

@@ -493,6 +493,162 @@ class SAGEConv(Module):
         return torch.relu(Y) if relu else Y
 
 
+# ---- several statistics of the neighbours from one gather, PNA --------------------------------------------------------
+
+_STAT_NEEDS = {"mean": ("sum",), "std": ("sum", "sumsq"), "max": ("max",), "min": ("min",)}
+
+
+class NeighborStats(Function):
+    """``NeighborStats.apply(X, inputInfo, eps=1e-5) -> (mean, std, max, min)`` of every node's neighbours, from ONE gather
+    (libgnna gnna_agg_stats_ld_f32: sum, sum of squares, max and min while a source row is in registers).  With c = max(count, 1):
+    mean = sum / c, var = relu(sumsq / c - mean^2), std = sqrt(var + eps) (PyG's StdAggregation); max / min are NeighborMax's /
+    NeighborMin's bits, a row without edges gives 0 (std: sqrt(eps)).  A fourth argument names the results wanted
+    (``want=("mean", "std")``): the others come back as None and only the statistics they need are computed.
+
+    Backward: dX[j] = (A^T a)[j] + X[j] * (A^T b)[j] + the gradients of max and min routed to their winning sources, with
+    a = (g_mean - g_std * mean / std) / c and b = g_std / (c * std); A^T a and A^T b are ONE neighbor sum of [a | b] at width 2F
+    over the backward graph (the graph itself, ``transposed()`` when ``directed``, the transposed block).  The derivative of the
+    relu on var is left out on purpose: where var is that close to 0 its sign is rounding noise, and a gate would switch a whole
+    row's gradient on or off by it.  Outputs that receive no gradient cost nothing; an X that needs none, nothing at all.
+
+    The variance is the uncentred form in fp32: keep the features at unit scale.  With a large common offset (10 * randn + 3)
+    rows whose std sits at the sqrt(eps) floor (degree 1, duplicate edges) amplify the rounding of sumsq / c - mean^2 in dX.
+    float32 only.  `inputInfo`: a decider.inputProperty (symmetric or ``directed``) or a sampling.SampledBlock (X [num_src, F]
+    -> results [num_dst, F])."""
+
+    @staticmethod
+    def forward(ctx, X, inputInfo, eps=1e-5, want=("mean", "std", "max", "min")):
+        unknown = [w for w in want if w not in _STAT_NEEDS]
+        if unknown or not want:
+            raise ValueError(f"want must name some of {sorted(_STAT_NEEDS)} (got {tuple(want)!r})")
+        if X.dtype != torch.float32 or _x16_dtype(X) is not None:
+            raise TypeError("NeighborStats computes in float32 only: 16-bit features and torch.autocast are not supported "
+                            f"(got {X.dtype}{', inside torch.autocast' if X.dtype == torch.float32 else ''})")
+        ctx.set_materialize_grads(False)
+        ctx.block = inputInfo if _is_block(inputInfo) else None
+        if ctx.block is not None:
+            X = _block_features(X, inputInfo, "NeighborStats")
+            n_out = inputInfo.num_dst
+        else:
+            _remember_graph(ctx, inputInfo)
+            ctx.knobs = _knobs(inputInfo)
+            X = X if X.dim() == 2 and (X.shape[1] <= 1 or X.stride(1) == 1) else X.contiguous()
+            n_out = X.shape[0]
+        need = {k for w in want for k in _STAT_NEEDS[w]}
+        ci = inputInfo.column_index
+        s, q, mx, amx, mn, amn = GNNA.aggregate_stats(X, ci, inputInfo.partPtr, inputInfo.part2Node, inputInfo.partSize, n_out,
+                                                      "sum" in need, "sumsq" in need, "max" in need, "min" in need)
+        inv = inputInfo.inv_row_counts().unsqueeze(1)
+        mean = std = None
+        if s is not None:
+            mean = s.mul_(inv)
+        if q is not None:
+            std = torch.relu_(q.mul_(inv).addcmul_(mean, mean, value=-1.0)).add_(eps).sqrt_()
+        ctx.save_for_backward(X, inv, mean, std, amx, amn, ci)
+        out = {"mean": mean, "std": std, "max": mx, "min": mn}
+        return tuple(out[k] if k in want else None for k in ("mean", "std", "max", "min"))
+
+    @staticmethod
+    def backward(ctx, g_mean, g_std, g_max, g_min):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        X, inv, mean, std, amx, amn, ci = ctx.saved_tensors
+        F = X.shape[1]
+        dX = None
+        if g_mean is not None or g_std is not None:
+            # one neighbor sum over the backward graph: of [a | b] when the std has a gradient, of a alone otherwise
+            if g_std is None:
+                ab = g_mean * inv
+            else:
+                ab = torch.empty(mean.shape[0], 2 * F, device=X.device, dtype=X.dtype)
+                b = torch.div(g_std * inv, std, out=ab[:, F:])
+                torch.mul(b, mean, out=ab[:, :F]).neg_()
+                if g_mean is not None:
+                    ab[:, :F].addcmul_(g_mean, inv)
+            if ctx.block is not None:
+                T = _block_sum(ab, ctx.block.transposed(), ctx.block.num_src)
+            else:
+                T = GNNA.SAG(ab, *_backward_graph(ctx), *ctx.knobs)
+            dX = T if g_std is None else torch.addcmul(T[:, :F], X, T[:, F:])
+        for g, arg in ((g_max, amx), (g_min, amn)):
+            if g is not None:
+                dX = _lib.scatter_arg_ld(g.contiguous(), arg, ci, X.shape[0], out=dX, accumulate=dX is not None)
+        return dX, None, None, None
+
+
+class PNAConv(Module):
+    """Principal Neighbourhood Aggregation layer (Corso et al., 2020) on the one-gather statistics of NeighborStats:
+
+        Y = X[:num_dst] W_self + sum over the scalers s of  s(d) * ([a_1(X) | ... | a_k(X)] W_s)  (+ b)
+
+    with the aggregators a_i among mean, max, min and std of a node's neighbours, d = max(count, 1), and the scalers
+    identity (1), amplification (log(d + 1) / delta) and attenuation (delta / log(d + 1)).  The messages are the source
+    features themselves: this is the form without PyG's pre-MLP on (x_i, x_j), towers and edge features, which would need
+    [nnz, F] tensors.  Whatever subset of aggregators is asked for, only the statistics it needs are computed.
+
+    delta: the value given, else the mean of log(d + 1) over the rows of the graph of the first forward, kept in the buffer
+    ``delta``; ``PNAConv.delta_of(inputInfo)`` computes it, so that mini-batch training can pass the full graph's value.
+    The weights are drawn like the other layers' (U(-1/sqrt(out), 1/sqrt(out))).  float32 only.  `inputInfo` may be a
+    sampling.SampledBlock: X is then [num_src, F], the result [num_dst, F]."""
+
+    AGGREGATORS = ("mean", "max", "min", "std")
+    SCALERS = ("identity", "amplification", "attenuation")
+
+    def __init__(self, input_dim, output_dim, aggregators=AGGREGATORS, scalers=SCALERS, delta=None, bias=False, eps=1e-5):
+        super().__init__()
+        aggregators, scalers = tuple(aggregators), tuple(scalers)
+        for what, got, known in (("aggregator", aggregators, self.AGGREGATORS), ("scaler", scalers, self.SCALERS)):
+            unknown = [a for a in got if a not in known]
+            if unknown or not got or len(set(got)) != len(got):
+                raise ValueError(f"{what}s must be distinct names among {known} (got {got!r})")
+        if delta is not None and not float(delta) > 0.0:
+            raise ValueError(f"delta must be positive (got {delta!r})")
+        self.aggregators, self.scalers, self.eps = aggregators, scalers, float(eps)
+        self.weights_self = Parameter(torch.empty(input_dim, output_dim))
+        self.weights_scaler = torch.nn.ParameterList(Parameter(torch.empty(len(aggregators) * input_dim, output_dim)) for _ in scalers)
+        self.bias = Parameter(torch.empty(output_dim)) if bias else None
+        self.register_buffer("delta", torch.tensor(float("nan") if delta is None else float(delta)))
+        self._delta_checked = delta is not None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        bound = 1.0 / math.sqrt(self.weights_self.size(1))
+        with torch.no_grad():
+            for w in (self.weights_self, *self.weights_scaler):
+                w.uniform_(-bound, bound)
+            if self.bias is not None:
+                self.bias.zero_()
+
+    @staticmethod
+    def delta_of(inputInfo):
+        """mean over the rows of log(max(count, 1) + 1): the delta of the graph (or block) `inputInfo`."""
+        return float(torch.log(1.0 / inputInfo.inv_row_counts() + 1.0).mean())
+
+    def forward(self, X, inputInfo, relu=False):
+        if X.dtype != torch.float32 or _x16_dtype(X) is not None:
+            raise TypeError("PNAConv computes in float32 only: 16-bit features and torch.autocast are not supported "
+                            f"(got {X.dtype}{', inside torch.autocast' if X.dtype == torch.float32 else ''})")
+        if not self._delta_checked:           # (a loaded state may have brought a value: NaN means "not set yet")
+            if bool(torch.isnan(self.delta)):
+                self.delta.fill_(self.delta_of(inputInfo))
+            self._delta_checked = True
+        stats = dict(zip(("mean", "std", "max", "min"), NeighborStats.apply(X, inputInfo, self.eps, self.aggregators)))
+        A = torch.cat([stats[a] for a in self.aggregators], dim=1)
+        Y = torch.mm(X[:inputInfo.num_dst] if _is_block(inputInfo) else X, self.weights_self)
+        logd = torch.log(1.0 / inputInfo.inv_row_counts() + 1.0).unsqueeze(1)
+        for name, W in zip(self.scalers, self.weights_scaler):
+            M = torch.mm(A, W)
+            if name == "identity":
+                Y = Y + M
+            elif name == "amplification":
+                Y = Y + M * (logd / self.delta)
+            else:
+                Y = Y + M * (self.delta / logd)
+        if self.bias is not None:
+            Y = Y + self.bias
+        return torch.relu(Y) if relu else Y
+
+
 # ---- relation-typed aggregation, R-GCN -------------------------------------------------------------------------------
 
 def _typed_features(X, rel, what):
