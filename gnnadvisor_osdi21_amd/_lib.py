@@ -140,6 +140,13 @@ STATS_SIGNATURES = {
     # input, ld_in, num_in_rows, the partition, (sum, ld) (sumsq, ld), (max, ld, argmax, ld) (min, ld, argmin, ld), num_out_rows, dim, num_parts, partSize, flags, stream
     "gnna_agg_stats_ld_f32": (i, [p, i64, i64, p, p, p] + [p, i64] * 6 + [i64, i, i64, i, u, p]),
 }
+# softmax neighbor aggregation (include/gnna_softagg.h): a seventh table
+SOFTAGG_SIGNATURES = {
+    # input, ld_in, num_in_rows, temp, temp_len, row_pointers, column_index, (out, ld) (lse, ld) (sq, ld), num_out_rows, dim, flags, stream
+    "gnna_agg_softmax_ld_f32": (i, [p, i64, i64, p, i, p, p] + [p, i64] * 3 + [i64, i, u, p]),
+    # input, ld_in, num_in_rows, temp, temp_len, (lse, ld) (Y, ld) (dY, ld), the transposed structure, d_input, ld_din, num_out_rows, dim, flags, stream
+    "gnna_agg_softmax_backward_ld_f32": (i, [p, i64, i64, p, i] + [p, i64] * 3 + [p, p, p, i64, i64, i, u, p]),
+}
 del p, i, i64, u, u64, f, s, pd, pi, pi64
 EXPORTS = tuple(SIGNATURES)
 EXT_EXPORTS = tuple(EXT_SIGNATURES)
@@ -151,6 +158,9 @@ SIGNATURE_TABLES = (SIGNATURES, EXT_SIGNATURES, GATV2_SIGNATURES, DOTATTN_SIGNAT
 GATEDGE_EXPORTS = tuple(GATEDGE_SIGNATURES)
 STATS_EXPORTS = tuple(STATS_SIGNATURES)
 LATER_SIGNATURE_TABLES = (GATEDGE_SIGNATURES, STATS_SIGNATURES)
+# the tables of the headers after gnna_stats.h, which load() applies last (the two tuples above stay as their tests pin them)
+SOFTAGG_EXPORTS = tuple(SOFTAGG_SIGNATURES)
+NEWER_SIGNATURE_TABLES = (SOFTAGG_SIGNATURES,)
 
 
 def load() -> ctypes.CDLL:
@@ -163,7 +173,7 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -m gnnadvisor_osdi21_amd.build`). There is no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    for table in SIGNATURE_TABLES + LATER_SIGNATURE_TABLES:
+    for table in SIGNATURE_TABLES + LATER_SIGNATURE_TABLES + NEWER_SIGNATURE_TABLES:
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype = restype
@@ -806,6 +816,60 @@ def agg_stats_ld(X, column_index, part_pointers, part2Node, num_out_rows=None, p
     _call(X.device, "gnna_agg_stats_ld_f32", xp, ld_in, n_in, column_index.data_ptr(), part_pointers.data_ptr(), part2Node.data_ptr(),
           *args, n_out, dim, part2Node.numel(), int(partSize), 0)
     return res
+
+
+def _temp_arg(temp, dim, device):
+    """(pointer, length) of a temperature: a float32 device tensor of 1 or `dim` elements, contiguous."""
+    assert temp.dtype == torch.float32 and temp.device == device and temp.is_contiguous() and temp.numel() in (1, dim), \
+        f"temp must be a contiguous float32 tensor of 1 or {dim} elements on {device}"
+    return temp.data_ptr(), temp.numel()
+
+
+def _ids_ptr(column_index, row_pointers):
+    """column_index's address; a graph without edges has none, and row_pointers' stands for it (no id is ever read)."""
+    return column_index.data_ptr() or row_pointers.data_ptr()
+
+
+def agg_softmax(X, temp, row_pointers, column_index, num_out_rows=None, want_sq=False, out=None, lse=None, sq=None):
+    """gnna_agg_softmax_ld_f32 (include/gnna_softagg.h): softmax aggregation with a temperature, per channel, in one gather.  Over the
+    edges i <- j of row i of the CSR (row_pointers, column_index), with s = temp[f] * X[j, f]: lse[i, f] = logsumexp_j s,
+    out[i, f] = sum_j exp(s - lse) X[j, f] and, with want_sq (or a given `sq`), sq[i, f] = sum_j exp(s - lse) X[j, f]^2; rows
+    without edges get 0.  `temp`: a float32 device tensor of 1 or dim elements.  -> (out, lse, sq | None), each
+    [num_out_rows, dim] (num_out_rows: row_pointers.numel() - 1 when not given).  `X` and a caller's `out` / `lse` / `sq` may be
+    row-strided views (stride(1) == 1).  The same bits on every run; accepted under set_tuning(deterministic=1)."""
+    _need_device(X, "aggregation")
+    xp, n_in, dim, ld_in = _rows_view(X, "X")
+    n_out = row_pointers.numel() - 1 if num_out_rows is None else int(num_out_rows)
+    assert row_pointers.numel() == n_out + 1, f"row_pointers must be [num_out_rows + 1 = {n_out + 1}] (got {row_pointers.numel()} entries)"
+    tp, tl = _temp_arg(temp, dim, X.device)
+    out, op_, ld_out = _out_rows(out, n_out, dim, X.device)
+    lse, lp, ld_lse = _out_rows(lse, n_out, dim, X.device)
+    qp, ld_sq = None, dim
+    if want_sq or sq is not None:
+        sq, qp, ld_sq = _out_rows(sq, n_out, dim, X.device)
+    _call(X.device, "gnna_agg_softmax_ld_f32", xp, ld_in, n_in, tp, tl, row_pointers.data_ptr(), _ids_ptr(column_index, row_pointers),
+          op_, ld_out, lp, ld_lse, qp, ld_sq, n_out, dim, 0)
+    return out, lse, sq
+
+
+def agg_softmax_backward(X, temp, lse, Y, dY, t_row_pointers, t_column_index, out=None):
+    """gnna_agg_softmax_backward_ld_f32: dX[j, f] = sum over the transposed edges j <- i of alpha * dY[i, f] *
+    (1 + temp[f] * (X[j, f] - Y[i, f])) with alpha = exp(temp[f] * X[j, f] - lse[i, f]), from agg_softmax's `lse` and `out` (Y).
+    (t_row_pointers, t_column_index): A^T as a CSR of X.shape[0] rows whose ids are destination rows.  -> dX like X; source rows
+    without transposed edges get 0.  Strided views as in agg_softmax.  The gradient of `temp` needs no call:
+    dt[f] = sum_i dY[i, f] * (sq[i, f] - Y[i, f]^2)."""
+    _need_device(X, "aggregation")
+    xp, n_in, dim, ld_in = _rows_view(X, "X")
+    assert t_row_pointers.numel() == n_in + 1, f"t_row_pointers must be [num_in_rows + 1 = {n_in + 1}] (got {t_row_pointers.numel()} entries)"
+    tp, tl = _temp_arg(temp, dim, X.device)
+    lp, n_out, w, ld_lse = _rows_view(lse, "lse")
+    yp, ny, wy, ld_y = _rows_view(Y, "Y")
+    gp, ng, wg, ld_dy = _rows_view(dY, "dY")
+    assert (ny, ng) == (n_out, n_out) and (w, wy, wg) == (dim, dim, dim), "lse, Y and dY must be [num_out_rows, dim]"
+    out, op_, ld_din = _out_rows(out, n_in, dim, X.device)
+    _call(X.device, "gnna_agg_softmax_backward_ld_f32", xp, ld_in, n_in, tp, tl, lp, ld_lse, yp, ld_y, gp, ld_dy,
+          t_row_pointers.data_ptr(), _ids_ptr(t_column_index, t_row_pointers), op_, ld_din, n_out, dim, 0)
+    return out
 
 
 def _node_heads(t, n, what):

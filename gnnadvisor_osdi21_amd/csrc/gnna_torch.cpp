@@ -37,6 +37,7 @@
 #include "gnna_dotattn.h"
 #include "gnna_gat_edge.h"
 #include "gnna_stats.h"
+#include "gnna_softagg.h"
 
 #define CHECK_CUDA(x) TORCH_CHECK(x.is_cuda(), #x " must be a CUDA tensor")
 #define CHECK_CONTIGUOUS(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -447,6 +448,74 @@ aggregate_stats(const torch::Tensor &input, const torch::Tensor &column_index, c
                                    fp(mx), dim, ip(amx), dim, fp(mn), dim, ip(amn), dim, n, (int)dim, part2Node.size(0), partSize, 0u,
                                    current_stream()));
     return std::make_tuple(sum, sumsq, mx, amx, mn, amn);
+}
+
+// Softmax aggregation with a temperature, per channel, in one gather (gnna_agg_softmax_ld_f32) -> (out, lse, sq), each
+// [num_out_rows, dim] with num_out_rows = row_pointers.size(0) - 1; sq is None unless want_sq.  temp: 1 or dim floats on the
+// device.  Strided X as aggregate_ld.
+static const int32_t *softagg_ids(const torch::Tensor &column_index, const torch::Tensor &row_pointers)
+{
+    // (a graph without edges has no column_index address: row_pointers' stands for it, no id is ever read)
+    return column_index.numel() > 0 ? column_index.data_ptr<int32_t>() : row_pointers.data_ptr<int32_t>();
+}
+static void softagg_check(const torch::Tensor &input, const torch::Tensor &temp, const torch::Tensor &row_pointers,
+                          const torch::Tensor &column_index)
+{
+    CHECK_CUDA(input);
+    TORCH_CHECK(input.dim() == 2, "input must be 2-D [num_nodes, dim]");
+    CHECK_F32(input);
+    check_floats(temp, "temp");
+    check_ids(row_pointers, "row_pointers");
+    check_ids(column_index, "column_index");
+    TORCH_CHECK(input.size(1) >= 1, "input must have at least one column");
+    TORCH_CHECK(temp.numel() == 1 || temp.numel() == input.size(1), "temp must have 1 or dim = ", input.size(1), " elements (got ",
+                temp.numel(), ")");
+    TORCH_CHECK(row_pointers.dim() == 1 && row_pointers.size(0) >= 1, "row_pointers must be [rows + 1]");
+    TORCH_CHECK(temp.device() == input.device() && row_pointers.device() == input.device() && column_index.device() == input.device(),
+                "input, temp, row_pointers and column_index must be on one device");
+    check_rows(input, "input");
+}
+std::tuple<torch::Tensor, torch::Tensor, c10::optional<torch::Tensor>>
+aggregate_softmax(const torch::Tensor &input, const torch::Tensor &temp, const torch::Tensor &row_pointers,
+                  const torch::Tensor &column_index, bool want_sq)
+{
+    softagg_check(input, temp, row_pointers, column_index);
+    const int64_t n_in = input.size(0), dim = input.size(1), n = row_pointers.size(0) - 1;
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(input.device());
+    const torch::Tensor out = fresh({n, dim}, input.options()), lse = fresh({n, dim}, input.options());
+    c10::optional<torch::Tensor> sq;
+    if (want_sq) sq = fresh({n, dim}, input.options());
+    check_rc(gnna_agg_softmax_ld_f32(input.data_ptr<float>(), ld_of(input), n_in, temp.data_ptr<float>(), (int)temp.numel(),
+                                     row_pointers.data_ptr<int32_t>(), softagg_ids(column_index, row_pointers), out.data_ptr<float>(), dim,
+                                     lse.data_ptr<float>(), dim, sq.has_value() ? sq->data_ptr<float>() : nullptr, dim, n, (int)dim, 0u,
+                                     current_stream()));
+    return std::make_tuple(out, lse, sq);
+}
+
+// Backward of aggregate_softmax (gnna_agg_softmax_backward_ld_f32) -> d_input like input.  (t_row_pointers, t_column_index): A^T,
+// input.size(0) rows whose ids are destination rows.  Strided input, lse, Y and dY as aggregate_ld.
+torch::Tensor aggregate_softmax_backward(const torch::Tensor &input, const torch::Tensor &temp, const torch::Tensor &lse,
+                                         const torch::Tensor &Y, const torch::Tensor &dY, const torch::Tensor &t_row_pointers,
+                                         const torch::Tensor &t_column_index)
+{
+    softagg_check(input, temp, t_row_pointers, t_column_index);
+    const int64_t n_in = input.size(0), dim = input.size(1);
+    TORCH_CHECK(t_row_pointers.size(0) == n_in + 1, "t_row_pointers must be [num_in_rows + 1] (the transposed structure has input's rows)");
+    const int64_t n = lse.dim() == 2 ? lse.size(0) : -1;
+    for (const torch::Tensor *t : {&lse, &Y, &dY}) {
+        CHECK_CUDA((*t));
+        CHECK_F32((*t));
+        TORCH_CHECK(t->dim() == 2 && t->size(0) == n && t->size(1) == dim && t->device() == input.device(),
+                    "lse, Y and dY must be [num_out_rows, dim] on input's device");
+        check_rows(*t, "lse / Y / dY");
+    }
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(input.device());
+    const torch::Tensor out = fresh({n_in, dim}, input.options());
+    check_rc(gnna_agg_softmax_backward_ld_f32(input.data_ptr<float>(), ld_of(input), n_in, temp.data_ptr<float>(), (int)temp.numel(),
+                                              lse.data_ptr<float>(), ld_of(lse), Y.data_ptr<float>(), ld_of(Y), dY.data_ptr<float>(),
+                                              ld_of(dY), t_row_pointers.data_ptr<int32_t>(), softagg_ids(t_column_index, t_row_pointers),
+                                              out.data_ptr<float>(), dim, n, (int)dim, 0u, current_stream()));
+    return out;
 }
 
 // Backward of aggregate_reduce (gnna_scatter_arg_ld_f32): grad_in[column_index[arg[i, f]], f] += grad_out[i, f], arg >= 0.
@@ -1255,6 +1324,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           pybind11::arg("X"), pybind11::arg("column_index"), pybind11::arg("partPtr"), pybind11::arg("part2Node"),
           pybind11::arg("partSize"), pybind11::arg("num_out_rows") = -1, pybind11::arg("want_sum") = true,
           pybind11::arg("want_sumsq") = true, pybind11::arg("want_max") = true, pybind11::arg("want_min") = true);
+    m.def("aggregate_softmax", &aggregate_softmax,
+          "softmax aggregation with a temperature, per channel, in one gather (extension) -> (out, lse, sq): over the edges i <- j of "
+          "row i, lse[i, f] = logsumexp_j temp[f] * X[j, f], out = sum_j alpha X[j], sq = sum_j alpha X[j]^2 (None unless want_sq); "
+          "temp has 1 or dim elements; rows without edges give 0",
+          pybind11::arg("X"), pybind11::arg("temp"), pybind11::arg("row_pointers"), pybind11::arg("column_index"),
+          pybind11::arg("want_sq") = false);
+    m.def("aggregate_softmax_backward", &aggregate_softmax_backward,
+          "backward of aggregate_softmax (extension): dX[j, f] = sum over the transposed edges j <- i of exp(temp[f] X[j, f] - lse[i, f]) "
+          "dY[i, f] (1 + temp[f] (X[j, f] - Y[i, f]))",
+          pybind11::arg("X"), pybind11::arg("temp"), pybind11::arg("lse"), pybind11::arg("Y"), pybind11::arg("dY"),
+          pybind11::arg("t_row_pointers"), pybind11::arg("t_column_index"));
     m.def("scatter_arg", &scatter_arg,
           "backward of aggregate_reduce (extension): grad_in[column_index[arg[i, f]], f] += grad_out[i, f] for arg >= 0",
           pybind11::arg("grad_out"), pybind11::arg("arg"), pybind11::arg("column_index"), pybind11::arg("num_in_rows"));

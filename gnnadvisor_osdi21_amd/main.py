@@ -37,9 +37,13 @@ def build_parser():
     p.add_argument("--dim", type=int, default=96, help="input embedding dimension size")
     p.add_argument("--hidden", type=int, default=16, help="hidden dimension size")
     p.add_argument("--classes", type=int, default=22, help="output classes size")
-    p.add_argument('--model', type=str, default='gcn', choices=['gcn', 'gin', 'gat', 'gatv2', 'transformer', 'sage', 'rgcn', 'pna'],
+    p.add_argument('--model', type=str, default='gcn', choices=['gcn', 'gin', 'gat', 'gatv2', 'transformer', 'sage', 'rgcn', 'pna', 'gen'],
                    help="GCN, GIN, GAT, GATv2 (dynamic attention, two layers as gat), graph transformer (dot-product attention, two "
-                        "TransformerConv layers as gat), GraphSAGE, R-GCN or PNA (two PNAConv layers: mean, max, min and std from one gather)")
+                        "TransformerConv layers as gat), GraphSAGE, R-GCN, PNA (two PNAConv layers: mean, max, min and std from one gather) "
+                        "or GEN (two GENConv layers: softmax aggregation with a temperature from one gather)")
+    p.add_argument('--softmax_t', type=float, default=1.0, help="--model gen: the (initial) temperature of the softmax aggregation")
+    p.add_argument('--learn_t', default='False', choices=['True', 'False'],
+                   help="--model gen: True learns the temperature of each layer (one value per layer)")
     p.add_argument('--num_relations', type=int, default=4,
                    help="--model rgcn: relation types of the edges (synthetic: a seeded hash of every edge's end points)")
     p.add_argument('--num_bases', type=int, default=0,
@@ -92,7 +96,7 @@ def build_parser():
                         "the device right after the partition (False: the structure is taken to be symmetric, as the "
                         "reference does, and the backward passes reuse the forward graph)")
     p.add_argument('--fanout', type=str, default=None,
-                   help="--model sage / pna, or --model gat / gatv2 / transformer with --fused_attention True: train on sampled mini-batches -- a comma list "
+                   help="--model sage / pna / gen, or --model gat / gatv2 / transformer with --fused_attention True: train on sampled mini-batches -- a comma list "
                         "with one entry per layer, the neighbours sampled per node at that layer (-1: all of them), e.g. 25,10; "
                         "the blocks are drawn on the device (sampling.NeighborSampler, MI355X addition)")
     p.add_argument('--batch_size', type=int, default=1024, help="--fanout: seed nodes per mini-batch")
@@ -126,6 +130,9 @@ def main(argv=None, capture=None):
     if args.dtype != 'float32' and args.model == 'pna':
         raise SystemExit("--dtype %s: the PNA layers (mean / std / max / min over the neighbours from one gather) are float32 only; "
                          "run --model pna with --dtype float32" % args.dtype)
+    if args.dtype != 'float32' and args.model == 'gen':
+        raise SystemExit("--dtype %s: the GEN layers (softmax aggregation over the neighbours from one gather) are float32 only; "
+                         "run --model gen with --dtype float32" % args.dtype)
     if args.model == 'rgcn':
         if flag(args.hip_graph):
             # (the relational graph builds its transposed structure and permuted edge arrays at the first backward: not captured)
@@ -160,7 +167,7 @@ def main(argv=None, capture=None):
         if attention and not flag(args.fused_attention):
             raise SystemExit("--model %s --fanout runs on the fused attention kernels only (the composed path would build "
                              "per-edge tensors for every batch): add --fused_attention True" % args.model)
-        if args.model not in ('sage', 'pna', 'gat', 'gatv2', 'transformer'):
+        if args.model not in ('sage', 'pna', 'gen', 'gat', 'gatv2', 'transformer'):
             raise SystemExit("--fanout trains GraphSAGE on sampled blocks: run it with --model sage, or with --model gat "
                              "--fused_attention True (got --model %s)" % args.model)
         if flag(args.hip_graph):
@@ -192,7 +199,7 @@ def main(argv=None, capture=None):
     from . import load_extension
     from .decider import inputProperty
     from .loader import custom_dataset
-    from .ops import GATConv, GATv2Conv, GCNConv, GINConv, PNAConv, RGCNConv, SAGEConv, TransformerConv
+    from .ops import GATConv, GATv2Conv, GCNConv, GENConv, GINConv, PNAConv, RGCNConv, SAGEConv, TransformerConv
     GNNA = load_extension()
 
     # ---- loading data --------------------------------------------------------------------
@@ -406,6 +413,21 @@ def main(argv=None, capture=None):
                 super().__init__()
                 self.conv1 = PNAConv(dataset.num_features, args.hidden, delta=delta)
                 self.conv2 = PNAConv(args.hidden, dataset.num_classes, delta=delta)
+
+            def forward(self, x=None, blocks=None):
+                if blocks is not None:      # a sampled mini-batch: x holds the rows of blocks[0]'s source nodes
+                    x = self.conv1(x, blocks[0], relu=True)
+                    x = self.conv2(x, blocks[1])
+                    return F.log_softmax(x, dim=1)
+                x = self.conv1(dataset.x, inputInfo.set_input(), relu=True)
+                x = self.conv2(x, inputInfo.set_hidden())
+                return F.log_softmax(x, dim=1)
+    elif args.model == 'gen':
+        class Net(torch.nn.Module):
+            def __init__(self):
+                super().__init__()
+                self.conv1 = GENConv(dataset.num_features, args.hidden, t=args.softmax_t, learn_t=flag(args.learn_t))
+                self.conv2 = GENConv(args.hidden, dataset.num_classes, t=args.softmax_t, learn_t=flag(args.learn_t))
 
             def forward(self, x=None, blocks=None):
                 if blocks is not None:      # a sampled mini-batch: x holds the rows of blocks[0]'s source nodes

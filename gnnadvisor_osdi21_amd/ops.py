@@ -649,6 +649,173 @@ class PNAConv(Module):
         return torch.relu(Y) if relu else Y
 
 
+# ---- softmax aggregation with a temperature (the learnable aggregator), GENConv -------------------------------------------
+
+def _temp_vector(temp, F, device, what):
+    """`temp` as the contiguous float32 vector of 1 or F elements the library takes."""
+    if not isinstance(temp, torch.Tensor) or temp.dtype != torch.float32 or temp.numel() not in (1, F):
+        raise ValueError(f"{what}: temp must be a float32 tensor of 1 or F = {F} elements "
+                         f"(got {tuple(temp.shape) if isinstance(temp, torch.Tensor) else temp!r})")
+    return temp.detach().reshape(-1).to(device).contiguous()
+
+
+class NeighborSoftmax(Function):
+    """``NeighborSoftmax.apply(X, temp, inputInfo) -> Y``: softmax aggregation with a temperature, per channel (PyG's
+    aggr.SoftmaxAggregation, the aggregator of DeeperGCN's GENConv), from ONE gather (libgnna gnna_agg_softmax_ld_f32):
+
+        Y[i, f] = sum over the edges i <- j of alpha * X[j, f],   alpha = softmax_j(temp[f] * X[j, f])
+
+    `temp`: a float32 tensor of 1 or F elements; 0 gives the mean, a large value approaches the max, a negative one is a soft min.
+    A row without edges gives 0.  Nothing of edge-list size is made: the op saves X, temp, Y and lse [rows, F], and
+    sq = sum_j alpha X[j]^2 only when `temp` needs a gradient.
+
+    Backward: dX from one gather over the backward graph (the graph itself, ``transposed()`` when ``directed``, the transposed
+    block; libgnna gnna_agg_softmax_backward_ld_f32, alpha = exp(temp * x - lse) per edge, never exp(-lse)), and
+    dtemp[f] = sum_i dY[i, f] * (sq[i, f] - Y[i, f]^2) in node-sized torch arithmetic.  What needs no gradient is not computed.
+    The same bits on every run.  float32 only.  `inputInfo`: a decider.inputProperty (symmetric or ``directed``) or a
+    sampling.SampledBlock (X [num_src, F] -> Y [num_dst, F])."""
+
+    @staticmethod
+    def forward(ctx, X, temp, inputInfo):
+        if X.dtype != torch.float32 or _x16_dtype(X) is not None:
+            raise TypeError("NeighborSoftmax computes in float32 only: 16-bit features and torch.autocast are not supported "
+                            f"(got {X.dtype}{', inside torch.autocast' if X.dtype == torch.float32 else ''})")
+        ctx.set_materialize_grads(False)
+        ctx.block = inputInfo if _is_block(inputInfo) else None
+        if ctx.block is not None:
+            X = _block_features(X, inputInfo, "NeighborSoftmax")
+        else:
+            _remember_graph(ctx, inputInfo)
+            X = X if X.dim() == 2 and (X.shape[1] <= 1 or X.stride(1) == 1) else X.contiguous()
+        t = _temp_vector(temp, X.shape[1], X.device, "NeighborSoftmax")
+        ctx.temp_shape = temp.shape
+        Y, lse, sq = GNNA.aggregate_softmax(X, t, inputInfo.row_pointers, inputInfo.column_index, bool(ctx.needs_input_grad[1]))
+        ctx.save_for_backward(X, t, Y, lse, sq)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        if dY is None:
+            return None, None, None
+        X, t, Y, lse, sq = ctx.saved_tensors
+        dX = dt = None
+        if ctx.needs_input_grad[0]:
+            # (the gradient of a sum() arrives as an expanded scalar: the library takes rows that are laid out)
+            if (dY.shape[1] > 1 and dY.stride(1) != 1) or (dY.shape[0] > 1 and dY.stride(0) < dY.shape[1]):
+                dY = dY.contiguous()
+            if ctx.block is not None:
+                bgraph = ctx.block.transposed()
+                rp, ci = bgraph.row_pointers, bgraph.column_index
+            else:
+                rp, ci = _backward_graph(ctx)[:2]
+            dX = GNNA.aggregate_softmax_backward(X, t, lse, Y, dY, rp, ci)
+        if ctx.needs_input_grad[1]:
+            per_channel = torch.addcmul(sq, Y, Y, value=-1.0).mul_(dY).sum(0)
+            dt = (per_channel if t.numel() > 1 else per_channel.sum()).reshape(ctx.temp_shape)
+        return dX, dt, None
+
+
+def _composed_softmax_aggregation(X, temp, info):
+    """The same function from torch ops, with [nnz, F] tensors: the timing baseline and a second opinion."""
+    rp, ci = info.row_pointers.long(), info.column_index.long()
+    n = rp.numel() - 1
+    dst = torch.repeat_interleave(torch.arange(n, device=X.device), rp[1:] - rp[:-1])
+    xj = X.index_select(0, ci)
+    s = xj * temp.reshape(1, -1)
+    idx = dst.unsqueeze(1).expand_as(s)
+    m = torch.full((n, X.shape[1]), float("-inf"), device=X.device, dtype=X.dtype).scatter_reduce(0, idx, s.detach(), "amax")
+    m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
+    e = torch.exp(s - m.index_select(0, dst))
+    l = torch.zeros_like(m).index_add_(0, dst, e)
+    a = torch.zeros_like(m).index_add_(0, dst, e * xj)
+    return torch.where(l > 0, a / torch.where(l > 0, l, torch.ones_like(l)), torch.zeros_like(a))
+
+
+class SoftmaxAggregation(Module):
+    """``SoftmaxAggregation(t=1.0, learn=False, channels=1, fused=True)(X, inputInfo) -> [rows, F]``: NeighborSoftmax with its
+    temperature kept in the module -- `channels` values (1, or the feature width F for one temperature per channel) that start at
+    `t`; a Parameter ``t`` when `learn`, a buffer otherwise.  fused=False is the composition from torch ops (index_select,
+    scatter_reduce("amax"), index_add_), which makes several [nnz, F] tensors: it exists as the timing baseline and as a second
+    opinion, and does not take a SampledBlock."""
+
+    def __init__(self, t=1.0, learn=False, channels=1, fused=True):
+        super().__init__()
+        if not isinstance(channels, int) or channels < 1:
+            raise ValueError(f"channels must be a positive integer (got {channels!r})")
+        if not math.isfinite(float(t)):
+            raise ValueError(f"t must be finite (got {t!r})")
+        self.learn, self.fused = bool(learn), bool(fused)
+        init = torch.full((channels,), float(t))
+        if self.learn:
+            self.t = Parameter(init)
+        else:
+            self.register_buffer("t", init)
+
+    def forward(self, X, inputInfo):
+        if self.t.numel() not in (1, X.shape[1]):
+            raise ValueError(f"SoftmaxAggregation has {self.t.numel()} temperatures, the features {X.shape[1]} channels")
+        if self.fused:
+            return NeighborSoftmax.apply(X, self.t, inputInfo)
+        _refuse_block(inputInfo, "SoftmaxAggregation(fused=False)")
+        if X.dtype != torch.float32 or _x16_dtype(X) is not None:
+            raise TypeError("SoftmaxAggregation computes in float32 only: 16-bit features and torch.autocast are not supported "
+                            f"(got {X.dtype}{', inside torch.autocast' if X.dtype == torch.float32 else ''})")
+        return _composed_softmax_aggregation(X, self.t, inputInfo)
+
+
+class GENConv(Module):
+    """GENeralized graph convolution (DeeperGCN; Li et al., 2020) on the one-gather softmax aggregation:
+
+        h = X W_in  (X itself when input_dim == output_dim),   m = relu(h) + eps,   a = SoftmaxAggregation(m)
+        Y = MLP(h[:num_dst] + a),   MLP = Linear(out, 2 * out) -> ReLU -> Linear(2 * out, out)
+
+    The messages are node-sized: this is the form without edge features.  Left out against PyG's GENConv: the normalisation
+    inside the MLP, the ``powermean`` aggregator and edge attributes (which would need an [nnz, F] input).  `t`, `learn_t` and
+    `channels` are SoftmaxAggregation's (channels: 1 or output_dim).  The weights are drawn like the other layers'
+    (U(-1/sqrt(columns), 1/sqrt(columns))); `bias` adds one to each Linear of the MLP.  float32 only.  `inputInfo` may be a
+    sampling.SampledBlock (fused=True): X is then [num_src, F], the result [num_dst, F]."""
+
+    def __init__(self, input_dim, output_dim, t=1.0, learn_t=False, channels=1, eps=1e-7, bias=False, fused=True):
+        super().__init__()
+        if channels not in (1, output_dim):
+            raise ValueError(f"channels must be 1 or output_dim = {output_dim} (got {channels!r})")
+        if not float(eps) >= 0.0:
+            raise ValueError(f"eps must be >= 0 (got {eps!r})")
+        self.eps = float(eps)
+        self.weights_in = Parameter(torch.empty(input_dim, output_dim)) if input_dim != output_dim else None
+        self.aggr = SoftmaxAggregation(t, learn_t, channels, fused)
+        self.weights_mlp1 = Parameter(torch.empty(output_dim, 2 * output_dim))
+        self.weights_mlp2 = Parameter(torch.empty(2 * output_dim, output_dim))
+        self.bias_mlp1 = Parameter(torch.empty(2 * output_dim)) if bias else None
+        self.bias_mlp2 = Parameter(torch.empty(output_dim)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        with torch.no_grad():
+            for w in (self.weights_in, self.weights_mlp1, self.weights_mlp2):
+                if w is not None:
+                    bound = 1.0 / math.sqrt(w.size(1))
+                    w.uniform_(-bound, bound)
+            for b in (self.bias_mlp1, self.bias_mlp2):
+                if b is not None:
+                    b.zero_()
+
+    def forward(self, X, inputInfo, relu=False):
+        if X.dtype != torch.float32 or _x16_dtype(X) is not None:
+            raise TypeError("GENConv computes in float32 only: 16-bit features and torch.autocast are not supported "
+                            f"(got {X.dtype}{', inside torch.autocast' if X.dtype == torch.float32 else ''})")
+        h = X if self.weights_in is None else torch.mm(X, self.weights_in)
+        a = self.aggr(torch.relu(h) + self.eps, inputInfo)
+        z = (h[:inputInfo.num_dst] if _is_block(inputInfo) else h) + a
+        z = torch.mm(z, self.weights_mlp1)
+        if self.bias_mlp1 is not None:
+            z = z + self.bias_mlp1
+        Y = torch.mm(torch.relu(z), self.weights_mlp2)
+        if self.bias_mlp2 is not None:
+            Y = Y + self.bias_mlp2
+        return torch.relu(Y) if relu else Y
+
+
 # ---- relation-typed aggregation, R-GCN -------------------------------------------------------------------------------
 
 def _typed_features(X, rel, what):
