@@ -147,6 +147,13 @@ SOFTAGG_SIGNATURES = {
     # input, ld_in, num_in_rows, temp, temp_len, (lse, ld) (Y, ld) (dY, ld), the transposed structure, d_input, ld_din, num_out_rows, dim, flags, stream
     "gnna_agg_softmax_backward_ld_f32": (i, [p, i64, i64, p, i] + [p, i64] * 3 + [p, p, p, i64, i64, i, u, p]),
 }
+# graph-level readout over the rows of every graph of a batch (include/gnna_pool.h): an eighth table
+POOL_SIGNATURES = {
+    # input, ld_in, num_rows, graph_pointers, num_segments, (sum, ld), (max, ld, argmax, ld) (min, ld, argmin, ld), dim, flags, stream
+    "gnna_segment_pool_ld_f32": (i, [p, i64, i64, p, i64] + [p, i64] * 5 + [i, u, p]),
+    # (d_sum, ld), (d_max, ld, argmax, ld) (d_min, ld, argmin, ld), graph_pointers, num_segments, d_input, ld_din, num_rows, dim, flags, stream
+    "gnna_segment_pool_backward_ld_f32": (i, [p, i64] * 5 + [p, i64, p, i64, i64, i, u, p]),
+}
 del p, i, i64, u, u64, f, s, pd, pi, pi64
 EXPORTS = tuple(SIGNATURES)
 EXT_EXPORTS = tuple(EXT_SIGNATURES)
@@ -161,6 +168,9 @@ LATER_SIGNATURE_TABLES = (GATEDGE_SIGNATURES, STATS_SIGNATURES)
 # the tables of the headers after gnna_stats.h, which load() applies last (the two tuples above stay as their tests pin them)
 SOFTAGG_EXPORTS = tuple(SOFTAGG_SIGNATURES)
 NEWER_SIGNATURE_TABLES = (SOFTAGG_SIGNATURES,)
+# the tables of the headers after gnna_softagg.h, which load() applies last of all (the three tuples above stay as their tests pin them)
+POOL_EXPORTS = tuple(POOL_SIGNATURES)
+POOL_SIGNATURE_TABLES = (POOL_SIGNATURES,)
 
 
 def load() -> ctypes.CDLL:
@@ -173,7 +183,7 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -m gnnadvisor_osdi21_amd.build`). There is no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    for table in SIGNATURE_TABLES + LATER_SIGNATURE_TABLES + NEWER_SIGNATURE_TABLES:
+    for table in SIGNATURE_TABLES + LATER_SIGNATURE_TABLES + NEWER_SIGNATURE_TABLES + POOL_SIGNATURE_TABLES:
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype = restype
@@ -869,6 +879,91 @@ def agg_softmax_backward(X, temp, lse, Y, dY, t_row_pointers, t_column_index, ou
     out, op_, ld_din = _out_rows(out, n_in, dim, X.device)
     _call(X.device, "gnna_agg_softmax_backward_ld_f32", xp, ld_in, n_in, tp, tl, lp, ld_lse, yp, ld_y, gp, ld_dy,
           t_row_pointers.data_ptr(), _ids_ptr(t_column_index, t_row_pointers), op_, ld_din, n_out, dim, 0)
+    return out
+
+
+POOL_TILE_ROWS = 256            # GNNA_POOL_TILE_ROWS: the rows a wavefront walks; segments that cross a multiple of it are joined from pieces
+POOL_LONG_STEPS = 16            # GNNA_POOL_LONG_STEPS: a segment of more than this many tiles per slot of a wavefront is joined by a workgroup
+POOL_MEAN = 1                   # GNNA_POOL_MEAN
+POOL_STATS = ("sum", "max", "min")
+
+
+def _graph_pointers_arg(graph_pointers, device):
+    assert graph_pointers.dtype == torch.int32 and graph_pointers.dim() == 1 and graph_pointers.numel() >= 1 and \
+        graph_pointers.is_contiguous() and graph_pointers.device == device, \
+        f"graph_pointers must be a contiguous int32 tensor [num_graphs + 1] on {device}"
+    return graph_pointers.data_ptr(), graph_pointers.numel() - 1
+
+
+def segment_pool(X, graph_pointers, want=("sum",), mean=False, out=None):
+    """gnna_segment_pool_ld_f32 (include/gnna_pool.h): the statistics named in `want` -- "sum", "max", "min" -- over the rows
+    [graph_pointers[g], graph_pointers[g + 1]) of X for every graph g of a batch, from one read of X.  "max" / "min" come with
+    "argmax" / "argmin", the smallest winning row (int32; -1 and the value 0 for a graph without rows), in the order of
+    agg_reduce_ld; mean=True divides the sum by the rows of the graph (0 for none).  -> a dict with a tensor [num_graphs, dim] for
+    every name wanted.  `X` may be a row-strided view (stride(1) == 1), and so may the tensors of `out`, a dict that supplies some
+    of the results (the rows are not computed when `out` holds the value but not them).  graph_pointers: int32 [num_graphs + 1] on
+    X's device, not descending; rows outside [graph_pointers[0], graph_pointers[-1]) belong to no graph.  The same bits on every
+    run; accepted under set_tuning(deterministic=1)."""
+    want = tuple(want)
+    if not want or [w for w in want if w not in POOL_STATS]:
+        raise ValueError(f"want must name some of {POOL_STATS} (got {want!r})")
+    _need_device(X, "segment_pool")
+    xp, n, dim, ld_in = _rows_view(X, "X")
+    gp, G = _graph_pointers_arg(graph_pointers, X.device)
+    out = dict(out or {})
+    res, args = {}, []
+    for name in POOL_STATS:
+        wanted = name in want
+        if wanted:
+            val, vp, ld = _out_rows(out.get(name), G, dim, X.device)
+            res[name] = val
+        args += [vp if wanted else None, ld if wanted else dim]
+        if name != "sum":
+            arg = None
+            if wanted and ("arg" + name in out or name not in out):
+                arg = out.get("arg" + name)
+                if arg is None:
+                    arg = _fresh_output((G, dim), X.device, torch.int32)
+                assert arg.device == X.device
+                ap, ld_arg = _arg_view(arg, G, dim, "arg" + name)
+                res["arg" + name] = arg
+            args += [ap if arg is not None else None, ld_arg if arg is not None else dim]
+    if G > 0:           # (the outputs of a batch without graphs are empty and have no address)
+        _call(X.device, "gnna_segment_pool_ld_f32", xp if n > 0 else None, ld_in, n, gp, G, *args, dim, POOL_MEAN if mean else 0)
+    return res
+
+
+def segment_pool_backward(graph_pointers, num_rows, d_sum=None, d_max=None, argmax=None, d_min=None, argmin=None, mean=False, out=None):
+    """gnna_segment_pool_backward_ld_f32: dX[r, f] = s * d_sum[g, f] + (argmax[g, f] == r) * d_max[g, f] + (argmin[g, f] == r) *
+    d_min[g, f] for the rows r of graph g, s = 1 or, with mean, 1 / the rows of the graph; a row of no graph gets 0.  One pass that
+    writes every element of dX [num_rows, dim] once, nothing is cleared first.  Any of d_sum, (d_max, argmax), (d_min, argmin) may be
+    None, not all.  Strided views as in segment_pool."""
+    given = [t for t in (d_sum, d_max, d_min) if t is not None]
+    if not given:
+        raise ValueError("segment_pool_backward needs d_sum, d_max or d_min")
+    if (d_max is None) != (argmax is None) or (d_min is None) != (argmin is None):
+        raise ValueError("d_max comes with argmax, d_min with argmin")
+    _need_device(given[0], "segment_pool_backward")
+    device = given[0].device
+    gp, G = _graph_pointers_arg(graph_pointers, device)
+    dim = given[0].shape[1]
+    args = []
+    for grad, arg, name in ((d_sum, None, "d_sum"), (d_max, argmax, "d_max"), (d_min, argmin, "d_min")):
+        if grad is None:
+            args += [None, dim] * (1 if name == "d_sum" else 2)
+            continue
+        vp, rows, w, ld = _rows_view(grad, name)
+        assert (rows, w) == (G, dim) and grad.device == device, f"{name} must be [num_graphs = {G}, dim = {dim}] on {device}"
+        args += [vp, ld]
+        if name != "d_sum":
+            assert arg.device == device
+            args += list(_arg_view(arg, G, dim, "arg" + name[2:]))
+    out, op_, ld_din = _out_rows(out, int(num_rows), dim, device)
+    if G == 0:          # (the gradients of a batch without graphs are empty and have no address: one row stands for them, unread)
+        stand_in = torch.zeros(1, dim, dtype=torch.float32, device=device)
+        args = [stand_in.data_ptr(), dim] + [None, dim] * 4
+    _call(device, "gnna_segment_pool_backward_ld_f32", *args, gp, G, op_ if int(num_rows) > 0 else None, ld_din, int(num_rows), dim,
+          POOL_MEAN if mean else 0)
     return out
 
 

@@ -38,6 +38,7 @@
 #include "gnna_gat_edge.h"
 #include "gnna_stats.h"
 #include "gnna_softagg.h"
+#include "gnna_pool.h"
 
 #define CHECK_CUDA(x) TORCH_CHECK(x.is_cuda(), #x " must be a CUDA tensor")
 #define CHECK_CONTIGUOUS(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -515,6 +516,82 @@ torch::Tensor aggregate_softmax_backward(const torch::Tensor &input, const torch
                                               lse.data_ptr<float>(), ld_of(lse), Y.data_ptr<float>(), ld_of(Y), dY.data_ptr<float>(),
                                               ld_of(dY), t_row_pointers.data_ptr<int32_t>(), softagg_ids(t_column_index, t_row_pointers),
                                               out.data_ptr<float>(), dim, n, (int)dim, 0u, current_stream()));
+    return out;
+}
+
+// Graph-level readout (gnna_segment_pool_ld_f32) -> (sum, max, argmax, min, argmin), each [num_graphs, dim] with num_graphs =
+// graph_pointers.size(0) - 1; None for a statistic that was not asked for (argmax / argmin, the winning rows, come with max / min).
+// mean: the sum divided by the rows of the graph.  Strided input as aggregate_ld.
+std::tuple<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>,
+           c10::optional<torch::Tensor>>
+segment_pool(const torch::Tensor &input, const torch::Tensor &graph_pointers, bool want_sum, bool want_max, bool want_min, bool mean)
+{
+    CHECK_CUDA(input);
+    TORCH_CHECK(input.dim() == 2, "input must be 2-D [num_nodes, dim]");
+    CHECK_F32(input);
+    check_ids(graph_pointers, "graph_pointers");
+    TORCH_CHECK(want_sum || want_max || want_min, "no statistic asked for");
+    TORCH_CHECK(graph_pointers.dim() == 1 && graph_pointers.size(0) >= 1, "graph_pointers must be [num_graphs + 1]");
+    TORCH_CHECK(graph_pointers.device() == input.device(), "input and graph_pointers must be on one device");
+    TORCH_CHECK(input.size(1) >= 1, "input must have at least one column");
+    check_rows(input, "input");
+    const int64_t n = input.size(0), dim = input.size(1), g = graph_pointers.size(0) - 1;
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(input.device());
+    c10::optional<torch::Tensor> sum, mx, amx, mn, amn;
+    if (want_sum) sum = fresh({g, dim}, input.options());
+    if (want_max) { mx = fresh({g, dim}, input.options()); amx = fresh({g, dim}, input.options().dtype(at::kInt)); }
+    if (want_min) { mn = fresh({g, dim}, input.options()); amn = fresh({g, dim}, input.options().dtype(at::kInt)); }
+    auto fp = [](const c10::optional<torch::Tensor> &t) { return t.has_value() ? t->data_ptr<float>() : nullptr; };
+    auto ip = [](const c10::optional<torch::Tensor> &t) { return t.has_value() ? t->data_ptr<int32_t>() : nullptr; };
+    if (g == 0) return std::make_tuple(sum, mx, amx, mn, amn);     // (empty outputs have no address)
+    check_rc(gnna_segment_pool_ld_f32(n > 0 ? input.data_ptr<float>() : nullptr, ld_of(input), n, graph_pointers.data_ptr<int32_t>(), g,
+                                      fp(sum), dim, fp(mx), dim, ip(amx), dim, fp(mn), dim, ip(amn), dim, (int)dim,
+                                      mean ? GNNA_POOL_MEAN : 0u, current_stream()));
+    return std::make_tuple(sum, mx, amx, mn, amn);
+}
+
+// Backward of segment_pool (gnna_segment_pool_backward_ld_f32) -> d_input [num_rows, dim]: every row gets the gradient of its
+// graph's sum (divided by the graph's rows with mean) plus those of the max / min it won; a row of no graph gets 0.  Any of d_sum,
+// (d_max, argmax), (d_min, argmin) may be None, not all.
+torch::Tensor segment_pool_backward(const c10::optional<torch::Tensor> &d_sum, const c10::optional<torch::Tensor> &d_max,
+                                    const c10::optional<torch::Tensor> &argmax, const c10::optional<torch::Tensor> &d_min,
+                                    const c10::optional<torch::Tensor> &argmin, const torch::Tensor &graph_pointers, int64_t num_rows,
+                                    bool mean)
+{
+    check_ids(graph_pointers, "graph_pointers");
+    TORCH_CHECK(graph_pointers.dim() == 1 && graph_pointers.size(0) >= 1, "graph_pointers must be [num_graphs + 1]");
+    TORCH_CHECK(d_sum.has_value() || d_max.has_value() || d_min.has_value(), "no gradient given");
+    TORCH_CHECK(d_max.has_value() == argmax.has_value() && d_min.has_value() == argmin.has_value(), "d_max comes with argmax, d_min with argmin");
+    TORCH_CHECK(num_rows >= 0, "num_rows must not be negative");
+    const int64_t g = graph_pointers.size(0) - 1;
+    const torch::Tensor &first = d_sum.has_value() ? *d_sum : d_max.has_value() ? *d_max : *d_min;
+    TORCH_CHECK(first.dim() == 2 && first.size(1) >= 1, "the gradients must be 2-D [num_graphs, dim]");
+    const int64_t dim = first.size(1);
+    for (const c10::optional<torch::Tensor> *t : {&d_sum, &d_max, &d_min}) {
+        if (!t->has_value()) continue;
+        CHECK_CUDA((**t));
+        CHECK_F32((**t));
+        TORCH_CHECK((*t)->dim() == 2 && (*t)->size(0) == g && (*t)->size(1) == dim && (*t)->device() == graph_pointers.device(),
+                    "d_sum, d_max and d_min must be [num_graphs, dim] on graph_pointers' device");
+        check_rows(**t, "d_sum / d_max / d_min");
+    }
+    for (const c10::optional<torch::Tensor> *t : {&argmax, &argmin}) {
+        if (!t->has_value()) continue;
+        CHECK_CUDA((**t));
+        CHECK_I32((**t));
+        TORCH_CHECK((*t)->dim() == 2 && (*t)->size(0) == g && (*t)->size(1) == dim && (*t)->device() == graph_pointers.device(),
+                    "argmax and argmin must be int32 [num_graphs, dim] on graph_pointers' device");
+        check_rows(**t, "argmax / argmin");
+    }
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(first.device());
+    const torch::Tensor out = fresh({num_rows, dim}, first.options());
+    auto fp = [](const c10::optional<torch::Tensor> &t) { return t.has_value() ? t->data_ptr<float>() : nullptr; };
+    auto ip = [](const c10::optional<torch::Tensor> &t) { return t.has_value() ? t->data_ptr<int32_t>() : nullptr; };
+    auto ld = [&](const c10::optional<torch::Tensor> &t) { return t.has_value() ? ld_of(*t) : dim; };
+    check_rc(gnna_segment_pool_backward_ld_f32(fp(d_sum), ld(d_sum), fp(d_max), ld(d_max), ip(argmax), ld(argmax), fp(d_min), ld(d_min),
+                                               ip(argmin), ld(argmin), graph_pointers.data_ptr<int32_t>(), g,
+                                               num_rows > 0 ? out.data_ptr<float>() : nullptr, dim, num_rows, (int)dim,
+                                               mean ? GNNA_POOL_MEAN : 0u, current_stream()));
     return out;
 }
 
@@ -1335,6 +1412,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           "dY[i, f] (1 + temp[f] (X[j, f] - Y[i, f]))",
           pybind11::arg("X"), pybind11::arg("temp"), pybind11::arg("lse"), pybind11::arg("Y"), pybind11::arg("dY"),
           pybind11::arg("t_row_pointers"), pybind11::arg("t_column_index"));
+    m.def("segment_pool", &segment_pool,
+          "graph-level readout (extension) -> (sum, max, argmax, min, argmin), each [num_graphs, dim]: over the rows "
+          "[graph_pointers[g], graph_pointers[g + 1]) of X, from one read of X; argmax / argmin are the winning rows (-1 and the value 0 "
+          "for a graph without rows); mean divides the sum by the rows of the graph; None for what was not asked for",
+          pybind11::arg("X"), pybind11::arg("graph_pointers"), pybind11::arg("want_sum") = true, pybind11::arg("want_max") = false,
+          pybind11::arg("want_min") = false, pybind11::arg("mean") = false);
+    m.def("segment_pool_backward", &segment_pool_backward,
+          "backward of segment_pool (extension): dX[r, f] = s d_sum[g, f] + (argmax[g, f] == r) d_max[g, f] + (argmin[g, f] == r) "
+          "d_min[g, f] for the rows r of graph g, s = 1 or 1 / rows with mean; one pass that writes every row, 0 for a row of no graph",
+          pybind11::arg("d_sum"), pybind11::arg("d_max"), pybind11::arg("argmax"), pybind11::arg("d_min"), pybind11::arg("argmin"),
+          pybind11::arg("graph_pointers"), pybind11::arg("num_rows"), pybind11::arg("mean") = false);
     m.def("scatter_arg", &scatter_arg,
           "backward of aggregate_reduce (extension): grad_in[column_index[arg[i, f]], f] += grad_out[i, f] for arg >= 0",
           pybind11::arg("grad_out"), pybind11::arg("arg"), pybind11::arg("column_index"), pybind11::arg("num_in_rows"));

@@ -252,6 +252,38 @@ def uniform_graph(num_nodes: int, num_edges: int, *, seed: int = 0, symmetric: b
     return graph_from_edges(u, v, num_nodes)
 
 
+def small_graphs(num_graphs: int, min_nodes: int, max_nodes: int, avg_degree: float = 4.0, seed: int = 0, device="cpu"):
+    """Seeded batches shaped like the reference's "Type II" inputs (collections of small graphs from the graph-kernel
+    benchmarks): `num_graphs` graphs whose sizes are drawn uniformly from [min_nodes, max_nodes], each with about
+    avg_degree * nodes / 2 undirected edges drawn inside the graph and stored in both directions (duplicates merged, self loops
+    allowed).  -> (row_pointers int32 [N + 1], column_index int32 [nnz] with ids LOCAL to their graph, graph_pointers int32
+    [G + 1]) on `device`: the arrays of a batching.GraphDataset.  The same arguments give the same arrays."""
+    if num_graphs < 0 or min_nodes < 0 or max_nodes < min_nodes:
+        raise ValueError(f"small_graphs: need num_graphs >= 0 and 0 <= min_nodes <= max_nodes (got {num_graphs}, {min_nodes}, {max_nodes})")
+    g = torch.Generator()
+    g.manual_seed(int(seed))
+    sizes = torch.randint(min_nodes, max_nodes + 1, (num_graphs,), generator=g, dtype=torch.int64)
+    gp = torch.zeros(num_graphs + 1, dtype=torch.int64)
+    gp[1:] = torch.cumsum(sizes, 0)
+    n = int(gp[-1])
+    if n >= 2 ** 31:
+        raise ValueError("small_graphs: fewer than 2^31 nodes in all (int32 CSR)")
+    pairs = torch.floor(sizes.double() * float(avg_degree) / 2).long()            # undirected edges per graph
+    which = torch.repeat_interleave(torch.arange(num_graphs), pairs)
+    m = int(which.numel())
+    u = (torch.rand(m, generator=g, dtype=torch.float64) * sizes[which].double()).long()
+    v = (torch.rand(m, generator=g, dtype=torch.float64) * sizes[which].double()).long()
+    src, dst = torch.cat([u, v]) + gp[torch.cat([which, which])], torch.cat([v, u])
+    # (rows are global so that the builder sorts them into their graphs; the columns stay local: key = row * max_nodes + column)
+    width = max(int(max_nodes), 1)
+    key = torch.unique(src * width + dst, sorted=True)
+    rows, cols = torch.div(key, width, rounding_mode="floor"), key % width
+    rp = torch.zeros(n + 1, dtype=torch.int64)
+    if n:
+        rp[1:] = torch.cumsum(torch.bincount(rows, minlength=n), 0)
+    return rp.to(torch.int32).to(device), cols.to(torch.int32).to(device), gp.to(torch.int32).to(device)
+
+
 # Named synthetic stand-ins for BASELINE.json's configs (SURVEY.md 8d).  Shapes follow the
 # public dataset cards; the graphs themselves are seeded power-law graphs.
 CONFIGS = {

@@ -1,0 +1,167 @@
+"""Graph classification on batches of small graphs: conv layers, a readout, a linear layer.
+
+    python -m gnnadvisor_osdi21_amd.graph_main --model gin --num_graphs 4096 --graph_nodes 8,72 --batch_graphs 256 --readout sum
+
+The reference evaluates half of its inputs ("Type II": collections of small graphs) with node-level drivers only; this driver
+finishes such a model inside the library.  A seeded synthetic collection (graph.small_graphs) is kept on the device as a
+batching.GraphDataset; every step cuts a mini-batch of ``--batch_graphs`` graphs out of it (GraphDataset.batch), runs two or more
+GCN / GIN layers on the block-diagonal CSR, reduces the node rows of every graph to one row (ops.Readout, one fused call for all
+the statistics of ``--readout``), and trains a per-graph classifier.  Prints ``Time (ms): %.3f`` per epoch as main.py does.
+The label of a graph is a function of its size and its features' mean, so that the loss has something to learn.
+"""
+import argparse
+import sys
+import time
+
+import torch
+
+
+def _bool(text):
+    if text not in ("True", "False"):
+        raise argparse.ArgumentTypeError("expected True or False (got %r)" % text)
+    return text == "True"
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="graph classification on batches of small graphs")
+    p.add_argument("--model", type=str, default="gin", help="gcn or gin")
+    p.add_argument("--num_graphs", type=int, default=4096, help="graphs in the synthetic collection")
+    p.add_argument("--graph_nodes", type=str, default="8,72", help="MIN,MAX nodes per graph")
+    p.add_argument("--avg_degree", type=float, default=4.0, help="average degree inside a graph")
+    p.add_argument("--batch_graphs", type=int, default=256, help="graphs per mini-batch")
+    p.add_argument("--readout", type=str, default="sum", help="comma list of sum, mean, max, min")
+    p.add_argument("--fused_readout", type=_bool, default=True, help="False: the readout composed from torch ops")
+    p.add_argument("--dim", type=int, default=32, help="input feature width")
+    p.add_argument("--hidden", type=int, default=64, help="hidden width")
+    p.add_argument("--classes", type=int, default=4, help="graph classes")
+    p.add_argument("--num_layers", type=int, default=2, help="conv layers (>= 2)")
+    p.add_argument("--num_epoches", type=int, default=20, help="epochs (passes over the collection)")
+    p.add_argument("--partSize", type=int, default=32, help="neighbor-group size")
+    p.add_argument("--lr", type=float, default=0.01)
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--dtype", type=str, default="float32")
+    p.add_argument("--verbose_mode", type=_bool, default=False)
+    return p
+
+
+def _parse(args):
+    if args.model not in ("gcn", "gin"):
+        raise SystemExit("--model %s: graph_main trains gcn or gin (the other layers take a GraphBatch too: build the model with ops)"
+                         % args.model)
+    if args.dtype != "float32":
+        raise SystemExit("--dtype %s: the readout (sum / mean / max / min over the rows of a graph) is float32 only; "
+                         "run graph_main with --dtype float32" % args.dtype)
+    try:
+        lo, hi = (int(v) for v in args.graph_nodes.split(","))
+    except ValueError:
+        raise SystemExit("--graph_nodes takes MIN,MAX, e.g. 8,72 (got %r)" % args.graph_nodes)
+    if lo < 1 or hi < lo:
+        raise SystemExit("--graph_nodes needs 1 <= MIN <= MAX (got %r)" % args.graph_nodes)
+    modes = tuple(m for m in args.readout.split(",") if m)
+    from .ops import POOL_MODES
+    if not modes or [m for m in modes if m not in POOL_MODES] or len(set(modes)) != len(modes):
+        raise SystemExit("--readout takes a comma list of sum, mean, max, min, each once (got %r)" % args.readout)
+    if args.num_graphs < 1:
+        raise SystemExit("--num_graphs must be >= 1")
+    if args.batch_graphs < 1:
+        raise SystemExit("--batch_graphs must be >= 1")
+    if args.num_layers < 2:
+        raise SystemExit("--num_layers must be >= 2 (got %d)" % args.num_layers)
+    if args.num_epoches < 1:
+        raise SystemExit("--num_epoches must be >= 1")
+    return lo, hi, modes
+
+
+def build_model(args, modes):
+    from torch.nn import Linear, Module, ModuleList
+
+    from .ops import GCNConv, GINConv, Readout
+    conv = GCNConv if args.model == "gcn" else GINConv
+
+    class Net(Module):
+        def __init__(self):
+            super().__init__()
+            dims = [args.dim] + [args.hidden] * args.num_layers
+            self.convs = ModuleList(conv(a, b) for a, b in zip(dims[:-1], dims[1:]))
+            self.readout = Readout(modes, fused=args.fused_readout)
+            self.lin = Linear(args.hidden * len(modes), args.classes)
+
+        def forward(self, x, batch):
+            for layer in self.convs:
+                x = torch.relu(layer(x, batch))
+            return torch.log_softmax(self.lin(self.readout(x, batch)), dim=1)
+
+    return Net()
+
+
+def make_dataset(args, lo, hi, device):
+    from .batching import GraphDataset
+    from .graph import small_graphs
+    rp, ci, gp = small_graphs(args.num_graphs, lo, hi, args.avg_degree, seed=args.seed, device=device)
+    g = torch.Generator()
+    g.manual_seed(args.seed + 1)
+    n = int(rp.numel()) - 1
+    x = torch.randn(n, args.dim, generator=g)
+    sizes = (gp[1:] - gp[:-1]).cpu().long()
+    which = torch.repeat_interleave(torch.arange(args.num_graphs), sizes)
+    mean0 = torch.zeros(args.num_graphs).index_add_(0, which, x[:, 0]) / sizes.clamp(min=1).float()
+    # classes by the quantiles of (size, mean of feature 0): something a sum or mean readout can learn
+    score = (sizes.float() - sizes.float().mean()) / (sizes.float().std() + 1e-6) + 4.0 * mean0
+    order = score.argsort()
+    y = torch.empty(args.num_graphs, dtype=torch.int64)
+    y[order] = torch.arange(args.num_graphs) * args.classes // args.num_graphs
+    return GraphDataset(rp, ci, gp, x.to(device), y.to(device))
+
+
+def main(argv=None, capture=None):
+    args = build_parser().parse_args(argv)
+    lo, hi, modes = _parse(args)
+    if not torch.cuda.is_available():
+        raise SystemExit("graph_main needs a GPU: there is no CPU path in libgnna")
+    device = torch.device("cuda")
+    torch.manual_seed(args.seed)
+    dataset = make_dataset(args, lo, hi, device)
+    model = build_model(args, modes).to(device)
+    optimizer = torch.optim.Adam(model.parameters(), lr=args.lr)
+    B = min(args.batch_graphs, args.num_graphs)
+    # the mini-batches are the same every epoch: cut them out once (each is a few arrays on the device)
+    ids = torch.arange(args.num_graphs, device=device)
+    batches = [dataset.batch(ids[k: k + B], partSize=args.partSize, hiddenDim=args.hidden) for k in range(0, args.num_graphs, B)]
+    if args.verbose_mode:
+        print("# %d graphs, %d nodes, %d edges, %d batches of up to %d graphs, readout %s (%s)" % (
+            args.num_graphs, dataset.num_nodes, int(dataset.column_index.numel()), len(batches), B, ",".join(modes),
+            "fused" if args.fused_readout else "composed"))
+
+    def epoch():
+        total = torch.zeros((), device=device)
+        for b in batches:
+            optimizer.zero_grad(set_to_none=True)
+            loss = torch.nn.functional.nll_loss(model(b.x, b), b.y)
+            loss.backward()
+            optimizer.step()
+            total += loss.detach() * b.num_graphs
+        return total / args.num_graphs
+
+    model.train()
+    first = epoch()                                   # dry run; also the loss after one epoch
+    if capture is not None:
+        capture.update(first_loss=float(first))
+    if args.verbose_mode:
+        print("# loss after 1 epoch: {:.6f}".format(float(first)))
+    torch.cuda.synchronize()
+    start = time.perf_counter()
+    for _ in range(args.num_epoches):
+        loss = epoch()
+    torch.cuda.synchronize()
+    train_time = time.perf_counter() - start
+    if capture is not None:
+        capture.update(final_loss=float(loss), epoch_ms=train_time * 1e3 / args.num_epoches)
+    if args.verbose_mode:
+        print("# final loss: {:.6f}".format(float(loss)))
+    print('Time (ms): {:.3f}'.format(train_time * 1e3 / args.num_epoches))
+    print()
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

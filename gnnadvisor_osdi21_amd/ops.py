@@ -1536,3 +1536,139 @@ class TransformerConv(Module):
         if self.W_skip is not None:
             Y = Y + torch.mm(X[:n] if block else X, self.W_skip)
         return Y
+
+
+# ---- graph-level readout: one row per graph of a batch (batching.GraphBatch) ------------------------------------------------
+POOL_MODES = ("sum", "mean", "max", "min")
+
+
+def _graph_pointers_of(batch, device):
+    """graph_pointers (int32 [G + 1] on `device`) of a batching.GraphBatch, or the tensor itself."""
+    gp = getattr(batch, "graph_pointers", batch)
+    if not isinstance(gp, torch.Tensor) or gp.dtype != torch.int32 or gp.dim() != 1 or gp.numel() < 1:
+        raise TypeError("a readout takes a GraphBatch or its graph_pointers, an int32 tensor [num_graphs + 1] (an unsorted "
+                        "`batch` vector is not supported: the rows of a graph must be contiguous)")
+    return gp.to(device).contiguous()
+
+
+def _laid_out(t):
+    """`t` with rows the library can stride over (the gradient of a sum() arrives as an expanded scalar)."""
+    if t is None or ((t.shape[1] <= 1 or t.stride(1) == 1) and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])):
+        return t
+    return t.contiguous()
+
+
+class SegmentPool(Function):
+    """``SegmentPool.apply(X, graph_pointers, want_sum, want_max, want_min, mean) -> (sum, max, min)``: the statistics over the rows
+    [graph_pointers[g], graph_pointers[g + 1]) of X for every graph g, each [G, F], from ONE read of X (libgnna
+    gnna_segment_pool_ld_f32); None for a statistic that was not asked for.  `mean` turns the sum into the mean.  A graph without
+    rows gives 0.  The op saves the winning rows argmax / argmin [G, F] and graph_pointers -- nothing of the size of X.
+
+    Backward: one pass that writes every row of dX once (libgnna gnna_segment_pool_backward_ld_f32): a row gets the gradient of its
+    graph's sum (over the rows of the graph with `mean`) plus those of the max / min elements it won; ties go to the smallest row.
+    The gradient of an output that was not used is not read, and nothing runs when X needs no gradient.  The same bits on every
+    run.  float32 only."""
+
+    @staticmethod
+    def forward(ctx, X, graph_pointers, want_sum=True, want_max=False, want_min=False, mean=False):
+        if X.dtype != torch.float32 or _x16_dtype(X) is not None:
+            raise TypeError("SegmentPool computes in float32 only: 16-bit features and torch.autocast are not supported "
+                            f"(got {X.dtype}{', inside torch.autocast' if X.dtype == torch.float32 else ''})")
+        if X.dim() != 2:
+            raise ValueError(f"SegmentPool: X must be [rows, F] (got {tuple(X.shape)})")
+        ctx.set_materialize_grads(False)
+        gp = _graph_pointers_of(graph_pointers, X.device)
+        s, mx, amx, mn, amn = GNNA.segment_pool(_laid_out(X), gp, bool(want_sum), bool(want_max), bool(want_min), bool(mean))
+        ctx.save_for_backward(gp, amx, amn)
+        ctx.num_rows, ctx.mean, ctx.width = X.shape[0], bool(mean), X.shape[1]
+        return s, mx, mn
+
+    @staticmethod
+    def backward(ctx, d_sum, d_max, d_min):
+        nothing = (None,) * 6
+        if not ctx.needs_input_grad[0] or (d_sum is None and d_max is None and d_min is None):
+            return nothing
+        gp, amx, amn = ctx.saved_tensors
+        if gp.numel() == 1:                                  # a batch without graphs: every row is a row of no graph
+            return (torch.zeros(ctx.num_rows, ctx.width, dtype=torch.float32, device=gp.device),) + nothing[1:]
+        dX = GNNA.segment_pool_backward(_laid_out(d_sum), _laid_out(d_max), amx if d_max is not None else None, _laid_out(d_min),
+                                        amn if d_min is not None else None, gp, ctx.num_rows, ctx.mean)
+        return (dX,) + nothing[1:]
+
+
+def global_add_pool(X, batch):
+    """[G, F]: the sum of the rows of every graph of `batch` (a batching.GraphBatch or its graph_pointers)."""
+    return SegmentPool.apply(X, batch, True, False, False, False)[0]
+
+
+def global_mean_pool(X, batch):
+    """[G, F]: the mean of the rows of every graph; 0 for a graph without rows."""
+    return SegmentPool.apply(X, batch, True, False, False, True)[0]
+
+
+def global_max_pool(X, batch):
+    """[G, F]: the element-wise maximum over the rows of every graph; 0 for a graph without rows."""
+    return SegmentPool.apply(X, batch, False, True, False, False)[1]
+
+
+def global_min_pool(X, batch):
+    """[G, F]: the element-wise minimum over the rows of every graph; 0 for a graph without rows."""
+    return SegmentPool.apply(X, batch, False, False, True, False)[2]
+
+
+def _composed_readout(X, batch, modes):
+    """The same statistics from torch ops on the `batch` vector (index_add_, scatter_reduce): the timing baseline and a second
+    opinion.  It makes an [N] index tensor (an [N, F] one for the extrema) and fills before it adds."""
+    gp = _graph_pointers_of(batch, X.device).long()
+    G = gp.numel() - 1
+    rows = getattr(batch, "batch", None)
+    if rows is None or rows.device != X.device:
+        rows = torch.repeat_interleave(torch.arange(G, device=X.device), gp[1:] - gp[:-1])
+    counts = (gp[1:] - gp[:-1]).clamp(min=0)
+    lo = int(gp[0]) if G else 0
+    Xg = X[lo: lo + rows.numel()]                          # rows of no graph lie before the first and after the last graph
+    out = []
+    for mode in modes:
+        if mode in ("sum", "mean"):
+            s = torch.zeros(G, X.shape[1], dtype=X.dtype, device=X.device).index_add_(0, rows, Xg)
+            out.append(s if mode == "sum" else s / counts.clamp(min=1).to(X.dtype).unsqueeze(1))
+        else:
+            idx = rows.unsqueeze(1).expand_as(Xg)
+            r = torch.zeros(G, X.shape[1], dtype=X.dtype, device=X.device).scatter_reduce(0, idx, Xg, "amax" if mode == "max" else "amin",
+                                                                                           include_self=False)
+            out.append(r)
+    return out
+
+
+class Readout(Module):
+    """``Readout(modes=("sum",), fused=True)(X, batch) -> [G, F * len(modes)]``: the chosen statistics -- some of "sum", "mean",
+    "max", "min" -- of the rows of every graph of `batch` (a batching.GraphBatch or its graph_pointers), side by side in the order of
+    `modes`.  fused=True takes all of them from ONE call of SegmentPool, one read of X ("mean" next to "sum" is the sum times
+    1 / rows, [G, F] arithmetic).  fused=False is the composition from torch ops (index_add_, scatter_reduce), kept as the timing
+    baseline and as a second opinion.  float32 only."""
+
+    def __init__(self, modes=("sum",), fused=True):
+        super().__init__()
+        modes = (modes,) if isinstance(modes, str) else tuple(modes)
+        if not modes or [m for m in modes if m not in POOL_MODES] or len(set(modes)) != len(modes):
+            raise ValueError(f"modes must name some of {POOL_MODES}, each once (got {modes!r})")
+        self.modes, self.fused = modes, bool(fused)
+
+    def forward(self, X, batch):
+        if X.dtype != torch.float32 or _x16_dtype(X) is not None:
+            raise TypeError("Readout computes in float32 only: 16-bit features and torch.autocast are not supported "
+                            f"(got {X.dtype}{', inside torch.autocast' if X.dtype == torch.float32 else ''})")
+        if not self.fused:
+            parts = _composed_readout(X, batch, self.modes)
+            return parts[0] if len(parts) == 1 else torch.cat(parts, 1)
+        both = "sum" in self.modes and "mean" in self.modes
+        s, mx, mn = SegmentPool.apply(X, batch, "sum" in self.modes or "mean" in self.modes, "max" in self.modes, "min" in self.modes,
+                                      "mean" in self.modes and not both)
+        parts = []
+        for mode in self.modes:
+            if mode == "mean" and both:
+                gp = _graph_pointers_of(batch, X.device)
+                parts.append(s * (1.0 / (gp[1:] - gp[:-1]).clamp(min=1).float()).unsqueeze(1))
+            else:
+                parts.append({"sum": s, "mean": s, "max": mx, "min": mn}[mode])
+        return parts[0] if len(parts) == 1 else torch.cat(parts, 1)
