@@ -154,6 +154,13 @@ POOL_SIGNATURES = {
     # (d_sum, ld), (d_max, ld, argmax, ld) (d_min, ld, argmin, ld), graph_pointers, num_segments, d_input, ld_din, num_rows, dim, flags, stream
     "gnna_segment_pool_backward_ld_f32": (i, [p, i64] * 5 + [p, i64, p, i64, i64, i, u, p]),
 }
+# attention readout over the rows of every graph of a batch (include/gnna_attnpool.h): a ninth table
+ATTNPOOL_SIGNATURES = {
+    # input, ld_in, num_rows, gate, ld_gate, gate_dim, graph_pointers, num_segments, (out, ld) (lse, ld), dim, flags, stream
+    "gnna_segment_attn_pool_ld_f32": (i, [p, i64, i64, p, i64, i, p, i64] + [p, i64] * 2 + [i, u, p]),
+    # input, ld_in, gate, ld_gate, gate_dim, (lse, ld) (Y, ld) (dY, ld), graph_pointers, num_segments, (d_input, ld) (d_gate, ld), num_rows, dim, flags, stream
+    "gnna_segment_attn_pool_backward_ld_f32": (i, [p, i64, p, i64, i] + [p, i64] * 3 + [p, i64] + [p, i64] * 2 + [i64, i, u, p]),
+}
 del p, i, i64, u, u64, f, s, pd, pi, pi64
 EXPORTS = tuple(SIGNATURES)
 EXT_EXPORTS = tuple(EXT_SIGNATURES)
@@ -171,6 +178,9 @@ NEWER_SIGNATURE_TABLES = (SOFTAGG_SIGNATURES,)
 # the tables of the headers after gnna_softagg.h, which load() applies last of all (the three tuples above stay as their tests pin them)
 POOL_EXPORTS = tuple(POOL_SIGNATURES)
 POOL_SIGNATURE_TABLES = (POOL_SIGNATURES,)
+# the table of the header after gnna_pool.h, which load() applies after all of those (the four tuples above stay as their tests pin them)
+ATTNPOOL_EXPORTS = tuple(ATTNPOOL_SIGNATURES)
+ATTNPOOL_SIGNATURE_TABLES = (ATTNPOOL_SIGNATURES,)
 
 
 def load() -> ctypes.CDLL:
@@ -183,7 +193,7 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -m gnnadvisor_osdi21_amd.build`). There is no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    for table in SIGNATURE_TABLES + LATER_SIGNATURE_TABLES + NEWER_SIGNATURE_TABLES + POOL_SIGNATURE_TABLES:
+    for table in SIGNATURE_TABLES + LATER_SIGNATURE_TABLES + NEWER_SIGNATURE_TABLES + POOL_SIGNATURE_TABLES + ATTNPOOL_SIGNATURE_TABLES:
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype = restype
@@ -965,6 +975,72 @@ def segment_pool_backward(graph_pointers, num_rows, d_sum=None, d_max=None, argm
     _call(device, "gnna_segment_pool_backward_ld_f32", *args, gp, G, op_ if int(num_rows) > 0 else None, ld_din, int(num_rows), dim,
           POOL_MEAN if mean else 0)
     return out
+
+
+def _gate_view(gate, n, dim, device):
+    """(pointer, gate_dim, leading dimension) of a gate [n], [n, 1] or [n, dim] on `device`: a score per row or per element."""
+    g2 = gate.unsqueeze(1) if gate.dim() == 1 else gate
+    gp_, rows, gate_dim, ld_gate = _rows_view(g2, "gate")
+    assert rows == n and gate_dim in (1, dim) and gate.device == device, \
+        f"gate must be [{n}], [{n}, 1] or [{n}, {dim}] on {device} (got {tuple(gate.shape)})"
+    return gp_, gate_dim, ld_gate
+
+
+def segment_attn_pool(X, gate, graph_pointers, out=None):
+    """gnna_segment_attn_pool_ld_f32 (include/gnna_attnpool.h): attention pooling over the rows [graph_pointers[g],
+    graph_pointers[g + 1]) of X for every graph g of a batch, from one read of X and of the gate.  `gate` is [N] or [N, 1] (a score
+    per row) or [N, dim] (a score per element); with s = gate[r, c]: lse[g, c] = log sum_r exp(s) and out[g, f] =
+    sum_r exp(s - lse[g, c]) * X[r, f]; a graph without rows gets 0 in both.  -> dict(out= [num_graphs, dim], lse= [num_graphs,
+    gate_dim]).  `X`, `gate` (which may be `X` itself) and the tensors of `out`, a dict that supplies some of the results, may be
+    row-strided views (stride(1) == 1); lse is not computed when `out` holds "out" but not "lse".  graph_pointers as in
+    segment_pool.  Finite gates of any size neither overflow nor underflow to 0 / 0.  The same bits on every run; accepted under
+    set_tuning(deterministic=1)."""
+    _need_device(X, "segment_attn_pool")
+    xp, n, dim, ld_in = _rows_view(X, "X")
+    gtp, gate_dim, ld_gate = _gate_view(gate, n, dim, X.device)
+    gp, G = _graph_pointers_arg(graph_pointers, X.device)
+    given = dict(out or {})
+    res = {}
+    res["out"], op_, ld_out = _out_rows(given.get("out"), G, dim, X.device)
+    lp, ld_lse = None, gate_dim
+    if "lse" in given or "out" not in given:
+        res["lse"], lp, ld_lse = _out_rows(given.get("lse"), G, gate_dim, X.device)
+    if G > 0:           # (the outputs of a batch without graphs are empty and have no address)
+        _call(X.device, "gnna_segment_attn_pool_ld_f32", xp if n > 0 else None, ld_in, n, gtp if n > 0 else None, ld_gate, gate_dim,
+              gp, G, op_, ld_out, lp, ld_lse, dim, 0)
+    return res
+
+
+def segment_attn_pool_backward(X, gate, lse, Y, dY, graph_pointers, need_input=True, need_gate=True, out=None):
+    """gnna_segment_attn_pool_backward_ld_f32: from segment_attn_pool's `lse` and `out` (Y) and the gradient dY of `out`, with
+    alpha = exp(gate[r, c] - lse[g, c]) for the rows r of graph g: d_input[r, f] = alpha * dY[g, f] and d_gate[r, c] = alpha *
+    dY[g, f] * (X[r, f] - Y[g, f]), summed over f for a gate per row; a row of no graph gets 0.  One pass that writes every element
+    once, nothing is cleared first.  -> (d_input like X | None, d_gate [N, gate_dim] | None): need_input / need_gate (not both
+    False) choose what is computed; `out` may supply "d_input" / "d_gate".  Strided views as in segment_attn_pool."""
+    if not need_input and not need_gate:
+        raise ValueError("segment_attn_pool_backward needs need_input or need_gate")
+    _need_device(X, "segment_attn_pool_backward")
+    xp, n, dim, ld_in = _rows_view(X, "X")
+    gtp, gate_dim, ld_gate = _gate_view(gate, n, dim, X.device)
+    gp, G = _graph_pointers_arg(graph_pointers, X.device)
+    lp, gl, wl, ld_lse = _rows_view(lse, "lse")
+    yp, gy, wy, ld_y = _rows_view(Y, "Y")
+    dp, gd, wd, ld_dy = _rows_view(dY, "dY")
+    assert (gl, gy, gd) == (G, G, G) and (wl, wy, wd) == (gate_dim, dim, dim) and lse.device == Y.device == dY.device == X.device, \
+        f"lse must be [{G}, {gate_dim}], Y and dY [{G}, {dim}] on {X.device}"
+    given = dict(out or {})
+    d_input = d_gate = dip = dgp = None
+    ld_din, ld_dgate = dim, gate_dim
+    if need_input:
+        d_input, dip, ld_din = _out_rows(given.get("d_input"), n, dim, X.device)
+    if need_gate:
+        d_gate, dgp, ld_dgate = _out_rows(given.get("d_gate"), n, gate_dim, X.device)
+    if n > 0:
+        if G == 0:      # (the tensors of a batch without graphs are empty and have no address; none is read)
+            lp = yp = dp = None
+        _call(X.device, "gnna_segment_attn_pool_backward_ld_f32", xp, ld_in, gtp, ld_gate, gate_dim, lp, ld_lse, yp, ld_y, dp, ld_dy,
+              gp, G, dip, ld_din, dgp, ld_dgate, n, dim, 0)
+    return d_input, d_gate
 
 
 def _node_heads(t, n, what):

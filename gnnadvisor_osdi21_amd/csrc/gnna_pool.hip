@@ -28,6 +28,7 @@
 #include "gnna_gat_common.h"     // gat::load_piece, gat::slots_sum, gat::check_alias
 #include "gnna_internal.h"
 #include "gnna_keys.h"
+#include "gnna_segments.h"
 
 namespace gnna {
 namespace {
@@ -54,31 +55,11 @@ struct PoolArgs {
     int D, mean;
 };
 
-// graph_pointers[g] clamped to [0, N]; the same value in every lane of a wavefront whose lanes ask for the same g
-__device__ __forceinline__ int64_t seg_ptr(const int32_t *__restrict__ gp, int64_t N, int64_t g)
-{
-    const int64_t v = gp[g];
-    return v < 0 ? 0 : (v > N ? N : v);
-}
-
-// the first segment whose end lies beyond row r (G: none): where the walk of a tile that begins at r starts
-__device__ __forceinline__ int64_t first_segment(const int32_t *__restrict__ gp, int64_t G, int64_t N, int64_t r)
-{
-    int64_t lo = 0, hi = G;
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (seg_ptr(gp, N, mid + 1) > r) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ int64_t uniform64(int64_t v)
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
+// (the clamped pointers, the search for a tile's first segment and the partial store: gnna_segments.h)
+using seg::seg_ptr;
+using seg::first_segment;
+using seg::uniform64;
+using seg::store_piece;
 
 // what a lane holds of a piece or a segment: four columns
 struct Acc {
@@ -330,18 +311,6 @@ __device__ __forceinline__ i32x4 load_ipiece(const int32_t *__restrict__ q, int 
     if (n4 > 1) v[1] = q[1];
     if (n4 > 2) v[2] = q[2];
     return v;
-}
-
-// the first n4 (<= 4) floats of v to q
-__device__ __forceinline__ void store_piece(float *__restrict__ q, const VT v, int n4)
-{
-    if (n4 >= 4) {
-        *reinterpret_cast<gat::MT *>(q) = v;
-        return;
-    }
-    if (n4 > 0) q[0] = v[0];
-    if (n4 > 1) q[1] = v[1];
-    if (n4 > 2) q[2] = v[2];
 }
 
 template <int LOG_LPR>

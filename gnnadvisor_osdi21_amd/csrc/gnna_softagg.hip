@@ -26,6 +26,7 @@
 #include "gnna_device.h"
 #include "gnna_gat_common.h"     // gat::load_piece, gat::slots_sum, gat::check_alias
 #include "gnna_internal.h"
+#include "gnna_segments.h"
 
 namespace gnna {
 namespace {
@@ -41,28 +42,15 @@ constexpr int kBwdEdges = 2;     // records (three 16-byte loads each) per slot 
 // (slots of a wavefront) * (edges per slot and step) * kLongSteps edges.
 constexpr int kLongSteps = 32;
 
-// exp(d) for d <= 0 (and -inf -> 0): one v_exp_f32.  The product d * log2(e) is rounded once, an error of at most |d| * 2^-24 in
-// the exponent, i.e. |d| * e^d * 2^-24 <= 2^-24 / e in the value: every use below is a weight relative to a maximum of 1, where
-// that is below half an ulp of the largest weight.
-__device__ __forceinline__ float exp_nonpos(float d) { return __builtin_amdgcn_exp2f(d * 1.44269504088896340736f); }
+// (exp of a non-positive number, one v_exp_f32, and the partial store of a lane's four columns: gnna_segments.h)
+using seg::exp_nonpos;
+using seg::store_piece;
 
 // this lane's four temperatures: the one value of a scalar temperature, or the piece of the per-channel vector
 __device__ __forceinline__ VT temp_piece(const float *__restrict__ temp, int temp_len, int mycol, int n4)
 {
     if (temp_len == 1) return (VT)(temp[0]);
     return load_piece(temp + mycol, n4);
-}
-
-// the first n4 (<= 4) floats of v to p
-__device__ __forceinline__ void store_piece(float *__restrict__ p, const VT v, int n4)
-{
-    if (n4 >= 4) {
-        *reinterpret_cast<gat::MT *>(p) = v;
-        return;
-    }
-    if (n4 > 0) p[0] = v[0];
-    if (n4 > 1) p[1] = v[1];
-    if (n4 > 2) p[2] = v[2];
 }
 
 // The ids of the E edges of slot t in the step at `base` (edges base + t + k * nl, k < E); -1 past the end of the row and for an id

@@ -39,6 +39,7 @@
 #include "gnna_stats.h"
 #include "gnna_softagg.h"
 #include "gnna_pool.h"
+#include "gnna_attnpool.h"
 
 #define CHECK_CUDA(x) TORCH_CHECK(x.is_cuda(), #x " must be a CUDA tensor")
 #define CHECK_CONTIGUOUS(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -593,6 +594,73 @@ torch::Tensor segment_pool_backward(const c10::optional<torch::Tensor> &d_sum, c
                                                num_rows > 0 ? out.data_ptr<float>() : nullptr, dim, num_rows, (int)dim,
                                                mean ? GNNA_POOL_MEAN : 0u, current_stream()));
     return out;
+}
+
+// Attention readout (gnna_segment_attn_pool_ld_f32) -> (out [num_graphs, dim], lse [num_graphs, gate_dim]) with num_graphs =
+// graph_pointers.size(0) - 1: the softmax-weighted sum of the rows of every graph.  gate: [num_rows, 1] (a score per row) or
+// [num_rows, dim] (a score per element); it may be input itself.  Strided input and gate as aggregate_ld.
+static void attn_pool_check(const torch::Tensor &input, const torch::Tensor &gate, const torch::Tensor &graph_pointers)
+{
+    CHECK_CUDA(input);
+    TORCH_CHECK(input.dim() == 2, "input must be 2-D [num_nodes, dim]");
+    CHECK_F32(input);
+    CHECK_CUDA(gate);
+    CHECK_F32(gate);
+    check_ids(graph_pointers, "graph_pointers");
+    TORCH_CHECK(graph_pointers.dim() == 1 && graph_pointers.size(0) >= 1, "graph_pointers must be [num_graphs + 1]");
+    TORCH_CHECK(input.size(1) >= 1, "input must have at least one column");
+    TORCH_CHECK(gate.dim() == 2 && gate.size(0) == input.size(0) && (gate.size(1) == 1 || gate.size(1) == input.size(1)),
+                "gate must be [num_nodes, 1] or [num_nodes, dim = ", input.size(1), "]");
+    TORCH_CHECK(graph_pointers.device() == input.device() && gate.device() == input.device(),
+                "input, gate and graph_pointers must be on one device");
+    check_rows(input, "input");
+    check_rows(gate, "gate");
+}
+std::tuple<torch::Tensor, torch::Tensor> segment_attn_pool(const torch::Tensor &input, const torch::Tensor &gate,
+                                                           const torch::Tensor &graph_pointers)
+{
+    attn_pool_check(input, gate, graph_pointers);
+    const int64_t n = input.size(0), dim = input.size(1), gd = gate.size(1), g = graph_pointers.size(0) - 1;
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(input.device());
+    const torch::Tensor out = fresh({g, dim}, input.options()), lse = fresh({g, gd}, input.options());
+    if (g == 0) return std::make_tuple(out, lse);                  // (empty outputs have no address)
+    check_rc(gnna_segment_attn_pool_ld_f32(n > 0 ? input.data_ptr<float>() : nullptr, ld_of(input), n,
+                                           n > 0 ? gate.data_ptr<float>() : nullptr, ld_of(gate), (int)gd,
+                                           graph_pointers.data_ptr<int32_t>(), g, out.data_ptr<float>(), dim, lse.data_ptr<float>(), gd,
+                                           (int)dim, 0u, current_stream()));
+    return std::make_tuple(out, lse);
+}
+
+// Backward of segment_attn_pool (gnna_segment_attn_pool_backward_ld_f32) -> (d_input like input, d_gate like gate), None for the
+// one that is not needed: with alpha = exp(gate - lse), d_input = alpha dY and d_gate = alpha dY (input - Y), summed over the
+// columns for a score per row; a row of no graph gets 0.
+std::tuple<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>>
+segment_attn_pool_backward(const torch::Tensor &input, const torch::Tensor &gate, const torch::Tensor &lse, const torch::Tensor &Y,
+                           const torch::Tensor &dY, const torch::Tensor &graph_pointers, bool need_input, bool need_gate)
+{
+    attn_pool_check(input, gate, graph_pointers);
+    TORCH_CHECK(need_input || need_gate, "neither d_input nor d_gate asked for");
+    const int64_t n = input.size(0), dim = input.size(1), gd = gate.size(1), g = graph_pointers.size(0) - 1;
+    for (const torch::Tensor *t : {&lse, &Y, &dY}) {
+        CHECK_CUDA((*t));
+        CHECK_F32((*t));
+        TORCH_CHECK(t->dim() == 2 && t->size(0) == g && t->size(1) == (t == &lse ? gd : dim) && t->device() == input.device(),
+                    "lse must be [num_graphs, gate_dim], Y and dY [num_graphs, dim], on input's device");
+        check_rows(*t, "lse / Y / dY");
+    }
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(input.device());
+    c10::optional<torch::Tensor> d_input, d_gate;
+    if (need_input) d_input = fresh({n, dim}, input.options());
+    if (need_gate) d_gate = fresh({n, gd}, input.options());
+    if (n == 0) return std::make_tuple(d_input, d_gate);
+    auto fp = [&](const torch::Tensor &t) { return g > 0 ? t.data_ptr<float>() : nullptr; };     // (empty tensors have no address)
+    check_rc(gnna_segment_attn_pool_backward_ld_f32(input.data_ptr<float>(), ld_of(input), gate.data_ptr<float>(), ld_of(gate), (int)gd,
+                                                    fp(lse), ld_of(lse), fp(Y), ld_of(Y), fp(dY), ld_of(dY),
+                                                    graph_pointers.data_ptr<int32_t>(), g,
+                                                    d_input.has_value() ? d_input->data_ptr<float>() : nullptr, dim,
+                                                    d_gate.has_value() ? d_gate->data_ptr<float>() : nullptr, gd, n, (int)dim, 0u,
+                                                    current_stream()));
+    return std::make_tuple(d_input, d_gate);
 }
 
 // Backward of aggregate_reduce (gnna_scatter_arg_ld_f32): grad_in[column_index[arg[i, f]], f] += grad_out[i, f], arg >= 0.
@@ -1423,6 +1491,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           "d_min[g, f] for the rows r of graph g, s = 1 or 1 / rows with mean; one pass that writes every row, 0 for a row of no graph",
           pybind11::arg("d_sum"), pybind11::arg("d_max"), pybind11::arg("argmax"), pybind11::arg("d_min"), pybind11::arg("argmin"),
           pybind11::arg("graph_pointers"), pybind11::arg("num_rows"), pybind11::arg("mean") = false);
+    m.def("segment_attn_pool", &segment_attn_pool,
+          "attention readout (extension) -> (out [num_graphs, dim], lse [num_graphs, gate_dim]): over the rows r in "
+          "[graph_pointers[g], graph_pointers[g + 1]) of X, lse[g, c] = logsumexp_r gate[r, c] and out[g, f] = sum_r exp(gate[r, c] - "
+          "lse[g, c]) X[r, f], from one read of X and gate; gate is [num_nodes, 1] (a score per row) or [num_nodes, dim] (a score per "
+          "element) and may be X itself; a graph without rows gives 0",
+          pybind11::arg("X"), pybind11::arg("gate"), pybind11::arg("graph_pointers"));
+    m.def("segment_attn_pool_backward", &segment_attn_pool_backward,
+          "backward of segment_attn_pool (extension) -> (d_input, d_gate), None for the one not needed: with alpha = exp(gate[r, c] - "
+          "lse[g, c]), d_input[r, f] = alpha dY[g, f] and d_gate[r, c] = alpha dY[g, f] (X[r, f] - Y[g, f]), summed over f for a score "
+          "per row; one pass that writes every row, 0 for a row of no graph",
+          pybind11::arg("X"), pybind11::arg("gate"), pybind11::arg("lse"), pybind11::arg("Y"), pybind11::arg("dY"),
+          pybind11::arg("graph_pointers"), pybind11::arg("need_input") = true, pybind11::arg("need_gate") = true);
     m.def("scatter_arg", &scatter_arg,
           "backward of aggregate_reduce (extension): grad_in[column_index[arg[i, f]], f] += grad_out[i, f] for arg >= 0",
           pybind11::arg("grad_out"), pybind11::arg("arg"), pybind11::arg("column_index"), pybind11::arg("num_in_rows"));

@@ -6,7 +6,8 @@ The reference evaluates half of its inputs ("Type II": collections of small grap
 finishes such a model inside the library.  A seeded synthetic collection (graph.small_graphs) is kept on the device as a
 batching.GraphDataset; every step cuts a mini-batch of ``--batch_graphs`` graphs out of it (GraphDataset.batch), runs two or more
 GCN / GIN layers on the block-diagonal CSR, reduces the node rows of every graph to one row (ops.Readout, one fused call for all
-the statistics of ``--readout``), and trains a per-graph classifier.  Prints ``Time (ms): %.3f`` per epoch as main.py does.
+the statistics of ``--readout``; with ``--attention_readout scalar|channel`` an ops.AttentionalReadout next to them), and trains
+a per-graph classifier.  Prints ``Time (ms): %.3f`` per epoch as main.py does.
 The label of a graph is a function of its size and its features' mean, so that the loss has something to learn.
 """
 import argparse
@@ -30,6 +31,8 @@ def build_parser():
     p.add_argument("--avg_degree", type=float, default=4.0, help="average degree inside a graph")
     p.add_argument("--batch_graphs", type=int, default=256, help="graphs per mini-batch")
     p.add_argument("--readout", type=str, default="sum", help="comma list of sum, mean, max, min")
+    p.add_argument("--attention_readout", type=str, default="none",
+                   help="none, scalar or channel: an attention readout after the --readout statistics, gated per row or per element")
     p.add_argument("--fused_readout", type=_bool, default=True, help="False: the readout composed from torch ops")
     p.add_argument("--dim", type=int, default=32, help="input feature width")
     p.add_argument("--hidden", type=int, default=64, help="hidden width")
@@ -61,6 +64,8 @@ def _parse(args):
     from .ops import POOL_MODES
     if not modes or [m for m in modes if m not in POOL_MODES] or len(set(modes)) != len(modes):
         raise SystemExit("--readout takes a comma list of sum, mean, max, min, each once (got %r)" % args.readout)
+    if args.attention_readout not in ("none", "scalar", "channel"):
+        raise SystemExit("--attention_readout takes none, scalar or channel (got %r)" % args.attention_readout)
     if args.num_graphs < 1:
         raise SystemExit("--num_graphs must be >= 1")
     if args.batch_graphs < 1:
@@ -75,8 +80,9 @@ def _parse(args):
 def build_model(args, modes):
     from torch.nn import Linear, Module, ModuleList
 
-    from .ops import GCNConv, GINConv, Readout
+    from .ops import AttentionalReadout, GCNConv, GINConv, Readout
     conv = GCNConv if args.model == "gcn" else GINConv
+    attention = args.attention_readout != "none"
 
     class Net(Module):
         def __init__(self):
@@ -84,12 +90,18 @@ def build_model(args, modes):
             dims = [args.dim] + [args.hidden] * args.num_layers
             self.convs = ModuleList(conv(a, b) for a, b in zip(dims[:-1], dims[1:]))
             self.readout = Readout(modes, fused=args.fused_readout)
-            self.lin = Linear(args.hidden * len(modes), args.classes)
+            # the learned readout next to the statistics: its gate scores every row (scalar) or every element (channel)
+            self.attention = AttentionalReadout(Linear(args.hidden, 1 if args.attention_readout == "scalar" else args.hidden),
+                                                fused=args.fused_readout) if attention else None
+            self.lin = Linear(args.hidden * (len(modes) + (1 if attention else 0)), args.classes)
 
         def forward(self, x, batch):
             for layer in self.convs:
                 x = torch.relu(layer(x, batch))
-            return torch.log_softmax(self.lin(self.readout(x, batch)), dim=1)
+            pooled = self.readout(x, batch)
+            if self.attention is not None:
+                pooled = torch.cat((pooled, self.attention(x, batch)), 1)
+            return torch.log_softmax(self.lin(pooled), dim=1)
 
     return Net()
 
@@ -131,6 +143,8 @@ def main(argv=None, capture=None):
         print("# %d graphs, %d nodes, %d edges, %d batches of up to %d graphs, readout %s (%s)" % (
             args.num_graphs, dataset.num_nodes, int(dataset.column_index.numel()), len(batches), B, ",".join(modes),
             "fused" if args.fused_readout else "composed"))
+        if args.attention_readout != "none":
+            print("# attention readout: one score per %s" % ("row" if args.attention_readout == "scalar" else "element"))
 
     def epoch():
         total = torch.zeros((), device=device)

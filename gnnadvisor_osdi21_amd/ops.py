@@ -1616,16 +1616,22 @@ def global_min_pool(X, batch):
     return SegmentPool.apply(X, batch, False, False, True, False)[2]
 
 
+def _batch_vector(batch, device):
+    """(graph_pointers as int64, G, the `batch` vector -- the graph of every row that has one --, the first such row): what the
+    compositions from torch ops index by."""
+    gp = _graph_pointers_of(batch, device).long()
+    G = gp.numel() - 1
+    rows = getattr(batch, "batch", None)
+    if rows is None or rows.device != device:
+        rows = torch.repeat_interleave(torch.arange(G, device=device), gp[1:] - gp[:-1])
+    return gp, G, rows, int(gp[0]) if G else 0
+
+
 def _composed_readout(X, batch, modes):
     """The same statistics from torch ops on the `batch` vector (index_add_, scatter_reduce): the timing baseline and a second
     opinion.  It makes an [N] index tensor (an [N, F] one for the extrema) and fills before it adds."""
-    gp = _graph_pointers_of(batch, X.device).long()
-    G = gp.numel() - 1
-    rows = getattr(batch, "batch", None)
-    if rows is None or rows.device != X.device:
-        rows = torch.repeat_interleave(torch.arange(G, device=X.device), gp[1:] - gp[:-1])
+    gp, G, rows, lo = _batch_vector(batch, X.device)
     counts = (gp[1:] - gp[:-1]).clamp(min=0)
-    lo = int(gp[0]) if G else 0
     Xg = X[lo: lo + rows.numel()]                          # rows of no graph lie before the first and after the last graph
     out = []
     for mode in modes:
@@ -1672,3 +1678,96 @@ class Readout(Module):
             else:
                 parts.append({"sum": s, "mean": s, "max": mx, "min": mn}[mode])
         return parts[0] if len(parts) == 1 else torch.cat(parts, 1)
+
+
+# ---- attention readout: the softmax-weighted sum of the rows of every graph ---------------------------------------------------
+def _gate_2d(X, gate, what):
+    """`gate` as [N, 1] or [N, F]: a score per row ([N] or [N, 1]) or per element ([N, F])."""
+    g2 = gate.unsqueeze(1) if gate.dim() == 1 else gate
+    if g2.dim() != 2 or g2.shape[0] != X.shape[0] or g2.shape[1] not in (1, X.shape[1]):
+        raise ValueError(f"{what}: gate must be [rows], [rows, 1] or [rows, F] for X [rows, F] = {tuple(X.shape)} "
+                         f"(got {tuple(gate.shape)})")
+    return g2
+
+
+class SegmentAttentionPool(Function):
+    """``SegmentAttentionPool.apply(X, gate, batch) -> Y [G, F]``: attention pooling over the rows of every graph of `batch` (a
+    batching.GraphBatch or its graph_pointers), Y[g] = sum over the rows r of graph g of softmax_r(gate[r]) * X[r], from ONE read of
+    X and of the gate (libgnna gnna_segment_attn_pool_ld_f32).  `gate` is [N] or [N, 1] (a score per row) or [N, F] (a score per
+    element, a softmax per column); it may be X itself or a view of it.  A graph without rows gives 0.  Finite scores of any size
+    are safe: exp is only taken of a score minus a running maximum.
+
+    The op saves X, the gate, Y, the log-sum-exp [G, 1 or F] and graph_pointers; no alpha tensor and no [N, F] temporary exists in
+    either pass.  Backward: one pass (libgnna gnna_segment_attn_pool_backward_ld_f32) that writes dX = alpha * dY[g] and
+    d_gate = alpha * dY[g] * (X - Y[g]) (summed over the columns for a score per row), each only if it is needed.  The same bits on
+    every run.  float32 only."""
+
+    @staticmethod
+    def forward(ctx, X, gate, graph_pointers):
+        for t in (X, gate):
+            if t.dtype != torch.float32 or _x16_dtype(t) is not None:
+                raise TypeError("SegmentAttentionPool computes in float32 only: 16-bit features and torch.autocast are not supported "
+                                f"(got {t.dtype}{', inside torch.autocast' if t.dtype == torch.float32 else ''})")
+        if X.dim() != 2:
+            raise ValueError(f"SegmentAttentionPool: X must be [rows, F] (got {tuple(X.shape)})")
+        g2 = _gate_2d(X, gate, "SegmentAttentionPool")
+        ctx.set_materialize_grads(False)
+        gp = _graph_pointers_of(graph_pointers, X.device)
+        Xl, gl = _laid_out(X), _laid_out(g2)
+        Y, lse = GNNA.segment_attn_pool(Xl, gl, gp)
+        ctx.save_for_backward(Xl, gl, Y, lse, gp)
+        ctx.gate_shape = tuple(gate.shape)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        need_x, need_gate = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if dY is None or not (need_x or need_gate):
+            return None, None, None
+        X, gate, Y, lse, gp = ctx.saved_tensors
+        if gp.numel() == 1:                                  # a batch without graphs: every row is a row of no graph
+            return (torch.zeros_like(X) if need_x else None, torch.zeros(ctx.gate_shape, dtype=torch.float32, device=X.device)
+                    if need_gate else None, None)
+        dX, dG = GNNA.segment_attn_pool_backward(X, gate, lse, Y, _laid_out(dY), gp, need_x, need_gate)
+        return dX, None if dG is None else dG.view(ctx.gate_shape), None
+
+
+def global_attention_pool(X, gate, batch):
+    """[G, F]: the rows of every graph of `batch` weighted by the softmax of `gate` ([N], [N, 1] or [N, F]) over the graph's rows;
+    0 for a graph without rows."""
+    return SegmentAttentionPool.apply(X, gate, batch)
+
+
+def _composed_attention_readout(V, gate, batch):
+    """The same readout from torch ops on the `batch` vector (scatter_reduce amax, exp, index_add_, a division, a product,
+    index_add_): the timing baseline and a second opinion.  It makes several [N, F]-sized temporaries."""
+    gp, G, rows, lo = _batch_vector(batch, V.device)
+    g2 = _gate_2d(V, gate, "AttentionalReadout")
+    Vg, sg = V[lo: lo + rows.numel()], g2[lo: lo + rows.numel()]
+    m = torch.full((G, sg.shape[1]), float("-inf"), dtype=V.dtype, device=V.device)
+    m = m.scatter_reduce(0, rows.unsqueeze(1).expand_as(sg), sg.detach(), "amax", include_self=True)
+    e = torch.exp(sg - m[rows])
+    l = torch.zeros(G, sg.shape[1], dtype=V.dtype, device=V.device).index_add_(0, rows, e)
+    return torch.zeros(G, V.shape[1], dtype=V.dtype, device=V.device).index_add_(0, rows, (e / l[rows]) * Vg)
+
+
+class AttentionalReadout(Module):
+    """``AttentionalReadout(gate_nn, nn=None, fused=True)(X, batch) -> [G, F']``: the learned readout of gated graph networks
+    (PyG's GlobalAttention / AttentionalAggregation): gate = gate_nn(X), one score per row ([N, 1]) or per element ([N, F']);
+    V = nn(X) if `nn` is given, else X; Y[g] = sum over the rows r of graph g of softmax_r(gate[r]) * V[r].  fused=True is ONE call
+    of SegmentAttentionPool: one read of V and of the gate, no alpha tensor.  fused=False is the composition from torch ops
+    (scatter_reduce, exp, index_add_), kept as the timing baseline and as a second opinion.  float32 only."""
+
+    def __init__(self, gate_nn, nn=None, fused=True):
+        super().__init__()
+        self.gate_nn, self.nn, self.fused = gate_nn, nn, bool(fused)
+
+    def forward(self, X, batch):
+        if X.dtype != torch.float32 or _x16_dtype(X) is not None:
+            raise TypeError("AttentionalReadout computes in float32 only: 16-bit features and torch.autocast are not supported "
+                            f"(got {X.dtype}{', inside torch.autocast' if X.dtype == torch.float32 else ''})")
+        gate = self.gate_nn(X)
+        V = X if self.nn is None else self.nn(X)
+        if not self.fused:
+            return _composed_attention_readout(V, gate, batch)
+        return SegmentAttentionPool.apply(V, gate, batch)
