@@ -660,7 +660,7 @@ def runtime_counters() -> dict:
     out = (ctypes.c_int64 * 16)()
     n = load().gnna_runtime_counters_ex(out, 16)
     names = ("plan_builds", "launch_syncs", "launch_frees", "launch_mallocs", "backoff_skips", "sweep_launches",
-             "pack_builds", "packed_launches", "full_hashes", "capture_scratch")
+             "pack_builds", "packed_launches", "full_hashes", "capture_scratch", "dense_block_builds", "dense_block_launches")
     return {name: int(out[i]) for i, name in enumerate(names) if i < n}
 
 

@@ -411,6 +411,42 @@ int sweep_auto_phases(const gnna_tuning &t, int mode, int dim, size_t x_bytes, i
     return std::max(2, std::min(std::min(16, 2 * B), std::max(2, part_size / 4)));
 }
 
+// ---- the block rule -----------------------------------------------------------------------------------------------
+// The dense hub-to-hub block (gnna_dense.hip).  Modelled saving of a block of H hubs holding `entries` edges, for rows of
+// 33 .. 64 floats -- two 128-byte requests per gathered row, the only widths the block is taken at (kDenseMinDim):
+//     entries * t_edge  -  t_hub(H)  -  t_launch,      t_hub(H) = rounds * (H_pad / 128) * t_chunk
+// t_edge: what the sweep kernel pays per edge.  t_chunk: what a workgroup of hub_block_kernel takes per 128 source ranks;
+// rounds = workgroups (H_pad / 32) over compute units, rounded up.  On whole rounds that is 2 H^2 64 / r_mfma with r_mfma =
+// 65 TFLOP/s.  All measured on MI355X on the Reddit-like headline (profiles/dense_block/README.md): the sweep kernel fell
+// from 1.3615 to 1.1883 ms for 16.19 M edges taken out (10.7 ps per edge); hub_block_kernel took 131.7 us for 8,192 hubs (64
+// chunks, one round); the step fell by 34 us where 173 - 132 = 41 us of kernel time were saved (t_launch 7 us).
+constexpr double kDenseEdgeSeconds = 10.7e-12;
+constexpr double kDenseChunkSeconds = 2.06e-6;
+constexpr double kDenseLaunchSeconds = 7.0e-6;
+constexpr double kDenseMinSaving = 25.0e-6;     // margin: a saving below the run-to-run spread (1.5 % of the headline) is none
+constexpr double kDenseMinShare = 0.03;         // of the edges
+
+// A workgroup of hub_block_kernel owns 32 ranks and walks all of them: a few ranks beyond a whole round of workgroups (one
+// per compute unit) would double the kernel's time.  The lowest-degree hubs beyond the round stay in the gather.
+int trimmed_hubs(int H, int num_cus)
+{
+    const int round = kDenseTileRanks * std::max(1, num_cus);
+    return (H > round && H % round != 0 && H % round < round / 4) ? H / round * round : H;
+}
+
+// Modelled saving (seconds) of the block of the `hubs` nodes of degree >= theta, which holds `entries` edges.
+double dense_block_saving(double hubs, double entries, int num_cus)
+{
+    if (hubs <= 0.0) return 0.0;
+    const double He = (double)trimmed_hubs((int)hubs, num_cus);
+    const double Hp = std::ceil(He / kDenseChunkRanks) * kDenseChunkRanks;
+    const double rounds = std::ceil(Hp / kDenseTileRanks / (double)std::max(1, num_cus));
+    const double kept = entries * (He / hubs) * (He / hubs);      // (trimmed hubs take their share of the block with them)
+    return kept * kDenseEdgeSeconds - rounds * (Hp / kDenseChunkRanks) * kDenseChunkSeconds - kDenseLaunchSeconds;
+}
+
+bool dense_block_pays(double saving, double entries, double edges) { return saving > kDenseMinSaving && entries >= kDenseMinShare * edges; }
+
 // Phases of the sweep kernel for an unweighted call at this width on a prepared graph (0 or 1: the streaming kernel runs): the
 // sweep's packed copy (Bs phases, 64 groups per chunk) is the one gnna_prepare_graph makes.  MODE_EDGE, which the sweep does
 // not run, takes the streaming kernel on those phases and chunks, so that it reads the same copy.
@@ -796,6 +832,18 @@ int launch_agg(int mode, const float *input, int64_t ld_in, int64_t num_in_rows,
             if (rc != GNNA_OK) return rc;
             if (sw_ids) count_event(CTR_PACKED_LAUNCHES);
         }
+        // dense hub-to-hub block of the prepared graph (gnna_dense.hip): the sweep walks the residual graph and hub_block_kernel
+        // adds the block.  Only where the library chose the sweep itself (a block built under GNNA_DENSE_BLOCK=2: a forced
+        // sweep as well), the packed copy's guard watches the caller's ids, and nothing has to see a finished row (ReLU).
+        DenseBlock db;
+        const int32_t *res_ids = nullptr; const uint32_t *res_off = nullptr;
+        bool dense = false;
+        if (sw_ids && plan.pinned && !relu && dim >= kDenseMinDim && dim <= kDenseMaxDim && num_in_rows == num_nodes && tune.column_phases < 2 &&
+            plan_dense_block(plan.handle, &db) && !db.off && db.res_plan && db.res_cnt && (auto_Bs > 0 || db.forced)) {
+            rc = get_packed_ids(ds, stream, db.res_plan, Bs, kWave, false, false, &res_ids, &res_off);
+            if (rc != GNNA_OK) return rc;
+            dense = true;
+        }
         uint32_t *sync = ds->sweep_sync + (size_t)call_block_of(ds, stream, seq) * kSweepSlotWords;
         static_assert(kXcds * 16 + 2 <= kBlock, "the prologue clears the sweep counters with one block");
         rc = run_prologue(0, sync, kXcds * 16 + 2);       // (dense prologue: it also zeroes the call's step counters and list header)
@@ -812,10 +860,15 @@ int launch_agg(int mode, const float *input, int64_t ld_in, int64_t num_in_rows,
         w.dynamic = tune.xcd_remap != 0;                                          // (experiments: XCD=0 selects the fixed shares per wavefront)
         w.plain_ok = !accumulate_into_out; w.eps = eps;
         w.ids_packed = sw_ids; w.item_off = sw_off; w.packed_stale = stale_flag;
+        if (dense) { w.res_col = db.res_col; w.res_pp = db.res_pp; w.res_cnt = db.res_cnt; w.res_ids_packed = res_ids; w.res_item_off = res_off; }
         t_last_phases = Bs;
         t_last_launches = 1;
         rc = launch_sweep(ds, w, stream);
         if (rc != GNNA_OK) return rc;
+        if (dense) {
+            rc = launch_hub_block(ds, stream, db, X, ldx, out, ldy, dim, mode == MODE_GIN, eps, row_scale, stale_flag, seq);
+            if (rc != GNNA_OK) return rc;
+        }
         profile_record(prof_call, 2, stream);
         return GNNA_OK;
     }
@@ -1125,6 +1178,44 @@ int gnna_prepare_graph(const int32_t *column_index, const int32_t *part_pointers
                 rc = get_packed_ids(ds, stream, plan.handle, B, std::max(1, std::min(kWave, t.groups_per_chunk * B)), true, true, &ids, &off);
             if (rc != GNNA_OK) return rc;
             if (phases_out && Bs >= 2) phases_out[i] = first_of_width ? Bs : std::max(phases_out[i], Bs);
+            // the dense hub-to-hub block and its residual graph (gnna_dense.hip), for a width the library itself sweeps (under
+            // GNNA_DENSE_BLOCK=2: any swept width).  The block is the graph's; the residual's packed copy is per phase count.
+            const int dense_mode = dense_block_mode();
+            const bool self_swept = t.sweep == 0 && t.column_phases < 2;
+            {
+                DenseBlock have;
+                if (plan_dense_block(plan.handle, &have) && have.off != (dense_mode == 0)) {
+                    have.off = dense_mode == 0;
+                    plan_set_dense_block(plan.handle, have);
+                }
+            }
+            if (swept && ids && dense_mode != 0 && dim >= kDenseMinDim && dim <= kDenseMaxDim && num_in_rows == num_out_rows &&
+                (dense_mode == 2 || self_swept)) {
+                DenseBlock db;
+                // (a graph the rule gave no block under this mode is not counted again: not for the next width, not at the next prepare)
+                if (!plan_dense_block(plan.handle, &db) && db.declined_mode != dense_mode) {
+                    rc = build_dense_block(ds, stream, column_index, part_pointers, part2Node, num_parts, num_in_rows,
+                                           (int64_t)plan.stats.edges, dense_mode, &db);
+                    if (rc != GNNA_OK) return rc;
+                    if (db.buf) {
+                        QuietBuilds quiet;
+                        SlicePlan res;
+                        rc = get_slice_plan(ds, stream, db.res_col, db.res_pp, part2Node, num_parts, num_in_rows, true, true, &res);
+                        if (rc == GNNA_OK && res.cnt) { db.res_plan = res.handle; db.res_cnt = res.cnt; }
+                        plan_set_dense_block(plan.handle, db);      // (the plan owns the buffers from here, whatever follows)
+                        if (rc != GNNA_OK) return rc;
+                    } else {
+                        db.declined_mode = dense_mode;
+                        plan_set_dense_block(plan.handle, db);
+                    }
+                }
+                if (db.buf && db.res_plan) {
+                    QuietBuilds quiet;
+                    const int32_t *rids = nullptr; const uint32_t *roff = nullptr;
+                    rc = get_packed_ids(ds, stream, db.res_plan, Bs, kWave, true, true, &rids, &roff);
+                    if (rc != GNNA_OK) return rc;
+                }
+            }
         }
         if (t.deterministic == 1 && dim >= 4) {   // the deterministic schedule parks partial rows in the stream's scratch (slot 2)
             const int G_eff = std::max(1, std::min(kWave, t.groups_per_chunk * std::max(1, B)));

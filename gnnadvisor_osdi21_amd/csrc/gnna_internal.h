@@ -176,8 +176,56 @@ int choose_slices(const SlicePlanStats &st, size_t x_bytes, int S, uint32_t slic
 // Events on the launch path that the contract promises not to happen after gnna_prepare_graph (gnna_runtime_counters).
 enum { CTR_PLAN_BUILDS = 0, CTR_LAUNCH_SYNCS = 1, CTR_LAUNCH_FREES = 2, CTR_LAUNCH_MALLOCS = 3, CTR_BACKOFF_SKIPS = 4,
        CTR_SWEEP_LAUNCHES = 5, CTR_PACK_BUILDS = 6, CTR_PACKED_LAUNCHES = 7, CTR_FULL_HASHES = 8, CTR_CAPTURE_SCRATCH = 9,
-       CTR_COUNT = 10 };
+       CTR_DENSE_BUILDS = 10, CTR_DENSE_LAUNCHES = 11, CTR_COUNT = 12 };
 void count_event(int which);
+// While one lives on this thread, plan and packed-copy builds are not counted: the residual graph of a dense block is made by
+// the caller's ONE gnna_prepare_graph, whose own plan and copies are what plan_builds / pack_builds count.
+struct QuietBuilds {
+    QuietBuilds();
+    ~QuietBuilds();
+    QuietBuilds(const QuietBuilds &) = delete;
+    QuietBuilds &operator=(const QuietBuilds &) = delete;
+};
+
+// ---- dense hub-to-hub block of a prepared graph (gnna_dense.hip) ----------------------------------------------------
+struct DenseBlock {
+    void *buf = nullptr;              // one allocation: r2n, node -> rank map, bm, res_pp
+    const int32_t *r2n = nullptr;     // [H_pad] rank -> node (-1: padding)
+    const void *bm = nullptr;         // [H_pad / 16][H_pad / 4] 64-bit words: 16 destination ranks x 4 source ranks each
+    const int32_t *res_pp = nullptr;  // part_pointers of the residual graph (same part2Node, same group count)
+    int32_t *res_col = nullptr;       // its column ids (an allocation of its own)
+    const uint8_t *res_cnt = nullptr; // its slice counts: those of its slice plan
+    void *res_plan = nullptr;         // the residual graph's (pinned) slice plan
+    int H = 0, H_pad = 0, theta = 0;
+    int64_t entries = 0, res_nnz = 0;
+    bool forced = false;              // built under GNNA_DENSE_BLOCK=2: also taken by a forced sweep
+    bool off = false;                 // the graph's latest gnna_prepare_graph ran under GNNA_DENSE_BLOCK=0
+    int declined_mode = -1;           // buf == null: the GNNA_DENSE_BLOCK mode under which the graph was counted and got no block
+};
+// Geometry of hub_block_kernel that the block rule needs: destination ranks per workgroup, source ranks per chunk (= padding).
+constexpr int kDenseTileRanks = 32, kDenseChunkRanks = 128;
+// Row widths the block is taken at: two 128-byte lines per gathered row, what the rule's constants were measured for.  (A row
+// of <= 32 floats is one request per edge: the sweep saves about half per edge taken out while the block costs the same.)
+constexpr int kDenseMinDim = 33, kDenseMaxDim = 64;
+// The block rule (gnna_agg.hip, beside sweep_auto_phases): hubs a block of `H` nodes keeps (whole rounds of workgroups), its
+// modelled saving in seconds, and whether that is worth a block.
+int trimmed_hubs(int H, int num_cus);
+double dense_block_saving(double hubs, double entries, int num_cus);
+bool dense_block_pays(double saving, double entries, double edges);
+// GNNA_DENSE_BLOCK: 0 never, 1 (default) where the block rule finds a saving, 2 for any prepared graph whose call sweeps.
+int dense_block_mode();
+// Degrees, histograms, the rule's theta, hub ranks, bitmap and residual arrays of the graph, on `stream` (synchronises; only
+// from gnna_prepare_graph).  out->buf stays null when the graph gets no block.
+int build_dense_block(DeviceState *ds, hipStream_t stream, const int32_t *col, const int32_t *pp, const int32_t *p2n, int64_t P,
+                      int64_t N, int64_t nnz, int mode, DenseBlock *out);
+// Y[node(i), :] += scale(i) * sum_j bit(i, j) * X[node(j), :] behind the sweep kernel of the same call; returns at once on
+// the device when *stale_flag == seq.
+int launch_hub_block(DeviceState *ds, hipStream_t stream, const DenseBlock &db, const float *X, int ldx, float *Y, int ldy, int dim,
+                     bool scaled, float eps, const float *row_scale, const int32_t *stale_flag, int32_t seq);
+// The block that hangs on a slice plan (gnna_stream.hip): a copy of it (false: none) / hang `db` on the plan, which owns its
+// buffers and the residual plan from then on.
+bool plan_dense_block(void *plan_handle, DenseBlock *out);
+void plan_set_dense_block(void *plan_handle, const DenseBlock &db);
 
 struct StreamLaunch {
     int mode;                 // MODE_SAG, MODE_GIN (also the pre-scaled GCN form: GIN + row_scale), MODE_GCN (per-edge) or MODE_EDGE
@@ -228,6 +276,10 @@ struct SweepLaunch {
     float eps;
     const int32_t *ids_packed = nullptr; const uint32_t *item_off = nullptr;   // packed ids for (B, 64 groups per chunk)
     const int32_t *packed_stale = nullptr;
+    // the residual graph of a dense block (same p2n and P), or null: the kernel walks it instead of col / pp / cnt / the packed
+    // copy unless *packed_stale == seq
+    const int32_t *res_col = nullptr; const int32_t *res_pp = nullptr; const uint8_t *res_cnt = nullptr;
+    const int32_t *res_ids_packed = nullptr; const uint32_t *res_item_off = nullptr;
 };
 bool sweep_supports(int mode, int dim, size_t x_bytes);
 int sweep_acc_rows(int dim, int wgs_per_cu);   // destination rows a workgroup's LDS accumulators hold at this width

@@ -944,6 +944,8 @@ struct Plan {
     std::vector<Packed> packed;
     uint64_t pack_lookups = 0;
     uint64_t pack_no_memory_until = 0;   // lookups below this do not try to build a copy (the last build's hipMalloc failed)
+    DenseBlock dense;                    // dense hub-to-hub block (gnna_dense.hip; pinned plans only): buf == null: none.  The plan
+                                         // owns its buffers and its residual plan
 };
 constexpr uint64_t kPackedNoMemoryBackoff = 1024;
 constexpr int kMaxPacked = 4;   // copies per plan (a GCN / GIN model aggregates at two or three widths)
@@ -960,6 +962,7 @@ constexpr int kColdStreak = 8;
 int g_cold_evictions = 0;
 int g_skip_builds = 0;
 std::atomic<long long> g_counters[CTR_COUNT];
+thread_local int t_quiet_builds = 0;
 
 // Device buffers of plans that were dropped while freeing them was not safe -- by gnna_forget_graph (a finalizer may run
 // on any thread at any time: hipFree synchronises the device and would invalidate a stream capture in progress), or
@@ -1004,7 +1007,31 @@ StreamKernel pick_stream_lpr(int lpr, bool wide, int u)
 
 }  // namespace
 
-void count_event(int which) { g_counters[which].fetch_add(1, std::memory_order_relaxed); }
+void count_event(int which)
+{
+    if (t_quiet_builds > 0 && (which == CTR_PLAN_BUILDS || which == CTR_PACK_BUILDS)) return;
+    g_counters[which].fetch_add(1, std::memory_order_relaxed);
+}
+QuietBuilds::QuietBuilds() { t_quiet_builds++; }
+QuietBuilds::~QuietBuilds() { t_quiet_builds--; }
+
+bool plan_dense_block(void *plan_handle, DenseBlock *out)
+{
+    std::lock_guard<std::mutex> lock(g_plan_mutex);
+    for (Plan *q : g_plans)
+        if (q == plan_handle) {
+            *out = q->dense;
+            return q->dense.buf != nullptr;
+        }
+    return false;
+}
+
+void plan_set_dense_block(void *plan_handle, const DenseBlock &db)
+{
+    std::lock_guard<std::mutex> lock(g_plan_mutex);
+    for (Plan *q : g_plans)
+        if (q == plan_handle) { q->dense = db; return; }
+}
 
 // Looks up / builds the slice counts of (column_index, part_pointers) for gathers from num_in_rows source
 // rows.  A miss runs slice_count_kernel on `stream`; with want_stats the first use also synchronises the stream
@@ -1137,9 +1164,21 @@ int release_slice_plans(const void *column_index, bool deferred)
     std::lock_guard<std::mutex> lock(g_plan_mutex);
     int dropped = 0;
     if (!column_index) { g_cold_evictions = 0; g_skip_builds = 0; }
+    std::vector<const void *> also;      // residual graphs of the dense blocks that go: their plans go too
+    auto wanted = [&](const Plan *pl) {
+        if (!column_index || pl->col == column_index) return true;
+        return std::find(also.begin(), also.end(), pl->col) != also.end();
+    };
     for (size_t i = 0; i < g_plans.size();) {
         Plan *pl = g_plans[i];
-        if (column_index && pl->col != column_index) { i++; continue; }
+        if (!wanted(pl)) { i++; continue; }
+        if (pl->dense.buf) {
+            g_dead.push_back(pl->dense.buf);
+            if (pl->dense.res_col) { g_dead.push_back(pl->dense.res_col); also.push_back(pl->dense.res_col); }
+            i = 0;                       // (the residual plan may sit before this one)
+            pl->dense = DenseBlock();
+            continue;
+        }
         if (pl->cnt) g_dead.push_back(pl->cnt);
         if (pl->ready) (void)hipEventDestroy(pl->ready);
         for (auto &pk : pl->packed) {

@@ -111,6 +111,13 @@ struct SweepParams {
     const uint32_t *item_off;
     const int32_t *packed_stale;   // *packed_stale == seq: column_index changed since the copy was made, read column_index
     int64_t num_chunks;        // ceil(P / 64)
+    // the residual graph of a dense hub-to-hub block (gnna_dense.hip; same p2n and P) or null: walked instead of col / pp / cnt
+    // and the packed copy unless the ids are stale -- then the call is the caller's whole graph and the hub kernel does nothing
+    const int32_t *res_col;
+    const int32_t *res_pp;
+    const uint8_t *res_cnt;
+    const int32_t *res_ids_packed;
+    const uint32_t *res_item_off;
 };
 
 // First index g in [0, P] with pp[g] >= target (pp non-decreasing, pp[P] >= target), searched 64 ways per round
@@ -197,7 +204,14 @@ sweep_kernel(const SweepParams p)
     const int c = lane % LPR;
     const int D = p.D;
     const bool canonical = p.trust || (*p.flag != p.seq);
-    const bool stale_ids = p.ids_packed != nullptr && *p.packed_stale == p.seq;
+    // (uniform, once: which graph this launch walks)
+    const bool use_res = p.res_pp != nullptr && *p.packed_stale != p.seq;
+    const int32_t *g_col = use_res ? p.res_col : p.col;
+    const int32_t *g_pp = use_res ? p.res_pp : p.pp;
+    const uint8_t *g_cnt = use_res ? p.res_cnt : p.cnt;
+    const int32_t *g_packed = use_res ? p.res_ids_packed : p.ids_packed;
+    const uint32_t *g_item_off = use_res ? p.res_item_off : p.item_off;
+    const bool stale_ids = !use_res && p.ids_packed != nullptr && *p.packed_stale == p.seq;
     const char *xbase = reinterpret_cast<const char *>(p.X);
     const uint32_t row_bytes32 = (uint32_t)p.ldx * 4u;
     uint32_t *offs = s_off[wib];
@@ -222,7 +236,7 @@ sweep_kernel(const SweepParams p)
     uint32_t *ctr = p.sync + xcd * 16;
     const bool syncing = p.slack < 1000 && nbx > 1;
     const int B = p.B, R = p.rounds;
-    const int64_t nnz = (int64_t)p.pp[p.P];
+    const int64_t nnz = (int64_t)g_pp[p.P];
     const int64_t num_sets = (int64_t)gridDim.x * R;
 
     if (threadIdx.x == 0) { s_ctl[2] = 0; s_ctl[3] = 0; }
@@ -231,7 +245,7 @@ sweep_kernel(const SweepParams p)
         // ---- the set: an equal share of the edges, XCD-major, then workgroup, then round -------------------
         const int64_t set = ((int64_t)xcd * nbx + bx) * R + r;
         if (wib < 2) {
-            const int64_t g = sweep_set_start(set + wib, num_sets, nnz, p.pp, p.P, canonical, p.ids_packed != nullptr, lane);
+            const int64_t g = sweep_set_start(set + wib, num_sets, nnz, g_pp, p.P, canonical, g_packed != nullptr, lane);
             if (lane == 0) s_g[wib] = g;
         }
         if (threadIdx.x == 0) { s_ctl[0] = 0; s_ctl[1] = 0; }
@@ -340,16 +354,16 @@ sweep_kernel(const SweepParams p)
                 // ---- 1. descriptors (all loads in flight together) -------------------------------------
                 const bool gl = lane < ng;
                 const int my_row = gl ? p.p2n[g0 + lane] : -1;
-                const int pa = gl ? p.pp[g0 + lane] : 0;
-                const int pb = gl ? p.pp[g0 + lane + 1] : 0;
+                const int pa = gl ? g_pp[g0 + lane] : 0;
+                const int pb = gl ? g_pp[g0 + lane + 1] : 0;
                 int cum_lo = 0, cum_hi = 0x7fffffff;
                 if (gl) {
-                    if (f_lo > 0) cum_lo = p.cnt[(size_t)(f_lo - 1) * (size_t)p.P + (size_t)(g0 + lane)];
-                    if (f_hi < p.S) cum_hi = p.cnt[(size_t)(f_hi - 1) * (size_t)p.P + (size_t)(g0 + lane)];
+                    if (f_lo > 0) cum_lo = g_cnt[(size_t)(f_lo - 1) * (size_t)p.P + (size_t)(g0 + lane)];
+                    if (f_hi < p.S) cum_hi = g_cnt[(size_t)(f_hi - 1) * (size_t)p.P + (size_t)(g0 + lane)];
                 }
-                const bool packed = dyn && p.ids_packed != nullptr && !stale_ids;
-                const uint32_t item_base = packed ? p.item_off[(size_t)t * (size_t)p.num_chunks + (size_t)(g0 >> 6)] : 0u;
-                const int32_t *__restrict__ ids = packed ? p.ids_packed : p.col;
+                const bool packed = dyn && g_packed != nullptr && !stale_ids;
+                const uint32_t item_base = packed ? g_item_off[(size_t)t * (size_t)p.num_chunks + (size_t)(g0 >> 6)] : 0u;
+                const int32_t *__restrict__ ids = packed ? g_packed : g_col;
                 const int len = pb > pa ? pb - pa : 0;
                 const int beg = cum_lo < len ? cum_lo : len;
                 int end = cum_hi < len ? cum_hi : len;
@@ -637,6 +651,9 @@ int launch_sweep(DeviceState *ds, const SweepLaunch &a, hipStream_t stream)
     p.slack = a.slack > 0 ? a.slack : 2;
     p.ids_packed = a.packed_stale ? a.ids_packed : nullptr; p.item_off = a.item_off; p.packed_stale = a.packed_stale;
     p.num_chunks = (a.P + kWave - 1) / kWave;
+    const bool res = a.packed_stale && a.res_pp && a.res_col && a.res_cnt;
+    p.res_col = res ? a.res_col : nullptr; p.res_pp = res ? a.res_pp : nullptr; p.res_cnt = res ? a.res_cnt : nullptr;
+    p.res_ids_packed = res ? a.res_ids_packed : nullptr; p.res_item_off = res ? a.res_item_off : nullptr;
     p.dynamic = a.dynamic ? 1 : 0;
     int lpr = 4;
     const int pieces = (a.D + 3) / 4;
