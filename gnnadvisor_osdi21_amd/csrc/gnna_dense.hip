@@ -221,25 +221,31 @@ struct HubParams {
     float eps;
 };
 
-// A workgroup owns 32 destination ranks (two MFMA tiles) and walks ALL source ranks, 128 at a time: the 128 source rows are
-// staged in LDS (zero beyond D and for padding ranks); the loads of the two chunks after the one being multiplied are in
-// flight meanwhile.  Its 8 wavefronts split the 32 four-rank steps of a chunk: wavefront w takes steps 4 w .. 4 w + 3 of both
-// tiles.  Per step lane (k, j) = (lane / 16, lane % 16) reads X[rank k0 + k][16 q + j] for q = 0 .. 3: the B operands of four
-// MFMAs, MFMA q covering the columns 16 q .. 16 q + 15.  The A operand is the tile's bitmap word.  Accumulator register r of
-// MFMA q holds Y[rank 4 (lane / 16) + r][16 q + lane % 16].  At the end the 8 partial tiles are summed in LDS in wavefront
-// order and the workgroup -- the only writer of its 32 rows in this launch, behind the sweep kernel of the same call -- adds
-// the tile to Y with plain loads and stores: no atomics, and a result that does not depend on timing.
-// (Measured on the headline's block of 8,193 hubs: a first version split the source ranks over workgroups and added partial
-// tiles with float atomics -- 183 us, all of it memory-side atomics at ~10 G 64-byte requests/s; this form with 64-rank chunks
-// and one chunk in flight -- 367 us: one L2 round trip per chunk, and 258 workgroups of 86 KB LDS on 256 compute units.)
+// A workgroup owns 32 destination ranks (two MFMA tiles) and walks ALL source ranks, 128 at a time.  The 128 source rows of a
+// chunk are staged in one of TWO LDS images (zero beyond D and for padding ranks): while chunk c is multiplied out of one
+// image, the rows of chunk c + 1 are written into the other, and the loads of chunks c + 2 and c + 3 are in flight -- one
+// barrier per chunk, and a load has two chunks' time to arrive.  Its 8 wavefronts split the 32 four-rank steps of a chunk:
+// wavefront w takes steps 4 w .. 4 w + 3 of both tiles.  Per step lane (k, j) = (lane / 16, lane % 16) reads
+// X[rank k0 + k][16 q + j] for q = 0 .. NT - 1: the B operands of NT MFMAs, MFMA q covering the columns 16 q .. 16 q + 15
+// (NT = 3 for D <= 48, 4 beyond).  A wavefront issues the B reads of all its four steps first; its 8 NT MFMAs then follow with
+// no branch between them, and the LDS writes of the next chunk and the loads of the chunk after the next two sit one by one
+// between the half steps, in the shadow of the matrix unit.  The A operand is the tile's bitmap word.  Accumulator register r of MFMA q
+// holds Y[rank 4 (lane / 16) + r][16 q + lane % 16].  At the end the 8 partial tiles are laid side by side in LDS (over the
+// images) and summed in wavefront order, and the workgroup -- the only writer of its 32 rows in this launch, behind the sweep
+// kernel of the same call -- adds the tile to Y with plain loads and stores: no atomics, and a result that does not depend
+// on timing.  FULL: D and ldx are multiples of 4, so every staged 16-byte piece is whole.
+// (Measured on the headline's block of 8,192 hubs, profiles/dense_block and profiles/hub_block_rate: partial tiles of a
+// split over source ranks added with float atomics -- 183 us; 64-rank chunks, one chunk in flight -- 367 us; one image, two
+// barriers per chunk, an LDS read waited for before every pair of MFMAs -- 130 us.)
+template <int NT, bool FULL>
 __global__ void __launch_bounds__(kHubThreads)
 hub_block_kernel(const HubParams p)
 {
     typedef typename VecOf<4>::T VT;
     typedef typename VecOf<4>::M MT;
     if (*p.stale == p.seq) return;       // the ids changed since the block was made: the sweep kernel does the whole call
-    __shared__ __attribute__((aligned(16))) float s_x[kHubKC * kHubRowStride];
-    __shared__ float s_red[kHubTileM][64];
+    __shared__ __attribute__((aligned(16))) float s_x[2][kHubKC * kHubRowStride];
+    static_assert(kHubWaves * kHubTileM * 64 <= 2 * kHubKC * kHubRowStride, "the partial tiles fit over the images");
     const int tid = (int)threadIdx.x;
     const int lane = tid & (kWave - 1);
     const int wib = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -248,112 +254,163 @@ hub_block_kernel(const HubParams p)
     const int tile0 = (int)blockIdx.x * (kHubTileM / 16);  // the workgroup's first 16-rank tile
     const int D = p.D;
 
-    // staging: thread t fetches piece t % 16 of the chunk's rows t / 16 + 32 i
-    const int srow = tid >> 4, spiece = (tid & 15) * 4;
+    // staging: thread t fetches piece t % 16 of the chunk's rows 4 (t / 16) .. 4 (t / 16) + 3 (their four ids are one 16-byte
+    // load).  No branch on the way: a padding rank reads row 0 and a piece beyond D reads piece 0; what they fetched is masked
+    // away when the piece goes to LDS (not before: touching a loaded value where it is loaded would wait for it there)
+    typedef int IT __attribute__((ext_vector_type(4)));
+    const int srow = (tid >> 4) * kHubStage, spiece = (tid & 15) * 4;
+    const bool live = spiece < D;
+    const int scol = live ? spiece : 0;
     auto load_piece = [&](int node) -> VT {
-        VT v = vzero<4>();
-        if (node >= 0 && spiece < D) {
-            const float *src = p.X + (size_t)node * (size_t)p.ldx + spiece;
-            if (spiece + 4 <= D) {
-                v = *reinterpret_cast<const MT *>(src);
-            } else {
+        const float *src = p.X + (size_t)(node < 0 ? 0 : node) * (size_t)p.ldx + scol;
+        VT v;
+        if constexpr (FULL) {
+            v = *reinterpret_cast<const MT *>(src);
+        } else if (spiece + 4 <= D) {
+            v = *reinterpret_cast<const MT *>(src);
+        } else {
+            v = vzero<4>();
 #pragma unroll
-                for (int q = 0; q < 4; q++)
-                    if (spiece + q < D) v[q] = src[q];
-            }
+            for (int q = 0; q < 4; q++)
+                if (spiece + q < D) v[q] = src[q];
         }
         return v;
     };
-    // Two stages take the chunks in turn, so that a stage's loads have two chunks' time to arrive; the node ids of a stage's
-    // NEXT chunk are fetched with the rows of the current one (the row addresses never wait for an id)
+    // Two stages take the chunks in turn (s0 the even ones, s1 the odd ones); the node ids of a stage's NEXT chunk are
+    // fetched behind the rows of the current one, so a row address never waits for an id that is younger than the rows the
+    // same wait is for.  A chunk beyond the last is the last one again: fetched, never multiplied.
     struct Stage {
         VT r[kHubStage];
-        int node[kHubStage];
-        unsigned long long w;            // lanes 0 .. 31: the chunk's 32 words of the first tile, lanes 32 .. 63: of the second
+        IT node;
+        uint32_t keep[kHubStage];        // all ones, or zero for a padding rank and for a piece beyond D
     };
     auto fetch_ids = [&](int c, Stage &st) {
-#pragma unroll
-        for (int i = 0; i < kHubStage; i++) st.node[i] = c < chunks ? p.r2n[c * kHubKC + 32 * i + srow] : -1;
+        const int cc = c < chunks ? c : chunks - 1;
+        st.node = *reinterpret_cast<const IT *>(&p.r2n[cc * kHubKC + srow]);
     };
-    auto fetch = [&](int c, Stage &st) {   // rows and words of chunk c (its ids are in st.node), then the ids of chunk c + 2
-        if (c >= chunks) return;
+    auto fetch_row = [&](int i, Stage &st) {                 // piece i of the chunk whose ids are in st.node
+        st.r[i] = load_piece(st.node[i]);
+        st.keep[i] = (st.node[i] >= 0 && live) ? 0xffffffffu : 0u;
+    };
+    // the bitmap words of chunk c: lanes 0 .. 31 the 32 words of the first tile, lanes 32 .. 63 of the second
+    auto fetch_words = [&](int c) -> unsigned long long {
+        const int cc = c < chunks ? c : chunks - 1;
+        return p.bm[(size_t)(tile0 + (lane >> 5)) * (size_t)words_per_tile_row + (size_t)(cc * (kHubKC / 4) + (lane & 31))];
+    };
+    // rows of chunk c (its ids are in st.node), the words of chunk cw, the ids of chunk c + 2: the order of a turn's loads
+    auto fetch = [&](int c, Stage &st, unsigned long long &w, int cw) {
 #pragma unroll
-        for (int i = 0; i < kHubStage; i++) st.r[i] = load_piece(st.node[i]);
-        st.w = p.bm[(size_t)(tile0 + (lane >> 5)) * (size_t)words_per_tile_row + (size_t)(c * (kHubKC / 4) + (lane & 31))];
+        for (int i = 0; i < kHubStage; i++) fetch_row(i, st);
+        w = fetch_words(cw);
         fetch_ids(c + 2, st);
     };
+    auto stage_out = [&](int i, const Stage &st, float *image) {
+        VT v = st.r[i];
+#pragma unroll
+        for (int q = 0; q < 4; q++) v[q] = __uint_as_float(__float_as_uint(v[q]) & st.keep[i]);
+        *reinterpret_cast<VT *>(&image[(srow + i) * kHubRowStride + spiece]) = v;
+    };
 
-    VT acc[2][4];
+    VT acc[2][NT];
 #pragma unroll
     for (int t = 0; t < 2; t++)
 #pragma unroll
-        for (int q = 0; q < 4; q++) acc[t][q] = vzero<4>();
+        for (int q = 0; q < NT; q++) acc[t][q] = vzero<4>();
 
-    auto multiply = [&](unsigned long long w) {
+    // Chunk c out of `cur` with the words w, which then become those of chunk c + 2 (a wavefront moves its eight words to
+    // scalar registers first: no copy of a loaded register, which would wait for the load where the copy stands); st holds
+    // chunk c + 1, which goes into `nxt`, and then starts on chunk c + 3.  The ten memory
+    // operations of a turn (4 LDS writes, 6 loads) are spread over the gaps between the eight half steps of MFMAs and
+    // pinned there: issued in one burst by all eight wavefronts they fill the queue of the compute unit's address unit (a
+    // chunk's 32 KB keep it busy for about half of a chunk's MFMA time), a wavefront stands at its next load until the
+    // queue has room, and no MFMA is issued meanwhile (stamped: 600 - 1,100 cycles per chunk for the nine loads of a burst).
+    auto turn = [&](int c, Stage &st, unsigned long long &w, const float *cur, float *nxt) {
+        constexpr int kSteps = kHubKC / 4 / kHubWaves;
+        static_assert(kSteps == 4 && kHubStage == 4, "the places of the memory operations between the half steps");
+        float b[kSteps][NT];
+#pragma unroll
+        for (int j = 0; j < kSteps; j++) {
+            const float *xs = &cur[((wib * kSteps + j) * 4 + (lane >> 4)) * kHubRowStride + (lane & 15)];
+#pragma unroll
+            for (int q = 0; q < NT; q++) b[j][q] = xs[q * 16];
+        }
+        __builtin_amdgcn_sched_barrier(0);                   // every B read is issued before the first MFMA
         const int w_lo = (int)(uint32_t)w, w_hi = (int)(uint32_t)(w >> 32);
+        unsigned long long m[2][kSteps];
 #pragma unroll
-        for (int j = 0; j < kHubKC / 4 / kHubWaves; j++) {
-            const int s = wib * (kHubKC / 4 / kHubWaves) + j;
-            const unsigned long long m0 = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane(w_hi, s) << 32) |
-                                          (uint32_t)__builtin_amdgcn_readlane(w_lo, s);
-            const unsigned long long m1 = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane(w_hi, 32 + s) << 32) |
-                                          (uint32_t)__builtin_amdgcn_readlane(w_lo, 32 + s);
-            if ((m0 | m1) == 0ull) continue;                 // (wave-uniform) no edge among these 32 x 4 pairs
-            const float *xs = &s_x[(s * 4 + (lane >> 4)) * kHubRowStride + (lane & 15)];
-            const float a0 = ((m0 >> lane) & 1ull) ? 1.f : 0.f;
-            const float a1 = ((m1 >> lane) & 1ull) ? 1.f : 0.f;
+        for (int t = 0; t < 2; t++)
 #pragma unroll
-            for (int q = 0; q < 4; q++) {
-                if (q * 16 >= D) continue;                   // (uniform) a 16-column tile beyond the row: nothing to multiply
-                const float b = xs[q * 16];
-                acc[0][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b, acc[0][q], 0, 0, 0);
-                acc[1][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b, acc[1][q], 0, 0, 0);
+            for (int j = 0; j < kSteps; j++) {
+                const int s = 32 * t + wib * kSteps + j;
+                m[t][j] = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane(w_hi, s) << 32) | (uint32_t)__builtin_amdgcn_readlane(w_lo, s);
+            }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < kSteps; j++) {
+            const float a0 = __builtin_amdgcn_inverse_ballot_w64(m[0][j]) ? 1.f : 0.f;   // (one v_cndmask on the scalar word)
+            const float a1 = __builtin_amdgcn_inverse_ballot_w64(m[1][j]) ? 1.f : 0.f;
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+#pragma unroll
+                for (int q = 2 * h; q < 2 * h + 2 && q < NT; q++) {
+                    acc[0][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b[j][q], acc[0][q], 0, 0, 0);
+                    acc[1][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b[j][q], acc[1][q], 0, 0, 0);
+                }
+                const int k = 2 * j + h;
+                if (k < 2) {
+                    stage_out(2 * k, st, nxt);
+                    stage_out(2 * k + 1, st, nxt);
+                } else if (k < 6) {
+                    fetch_row(k - 2, st);
+                } else if (k == 6) {
+                    w = fetch_words(c + 2);
+                    fetch_ids(c + 5, st);
+                }
+                __builtin_amdgcn_sched_barrier(0);
             }
         }
-    };
-    auto turn = [&](int c, Stage &st) {    // chunk c from stage st; the stage then starts on chunk c + 2
-        if (c >= chunks) return;
-        __syncthreads();                                     // the rows before these have been read by every wavefront
-#pragma unroll
-        for (int i = 0; i < kHubStage; i++) *reinterpret_cast<VT *>(&s_x[(srow + 32 * i) * kHubRowStride + spiece]) = st.r[i];
-        const unsigned long long w = st.w;
-        __syncthreads();
-        fetch(c + 2, st);
-        multiply(w);
+        __syncthreads();                                     // `nxt` is whole, and `cur` has been read by every wavefront
     };
     Stage s0, s1;
     fetch_ids(0, s0);
     fetch_ids(1, s1);
-    fetch(0, s0);
-    fetch(1, s1);
-    for (int c = 0; c < chunks; c += 2) {
-        turn(c, s0);
-        turn(c + 1, s1);
+    unsigned long long w0, w1;           // the words of the even and of the odd chunks
+    fetch(0, s0, w0, 0);
+    fetch(1, s1, w0, 0);
+#pragma unroll
+    for (int i = 0; i < kHubStage; i++) stage_out(i, s0, s_x[0]);
+    fetch(2, s0, w1, 1);
+    __syncthreads();
+    // (two turns per trip and the odd last chunk outside: a branch inside the loop would make the waits of the trip after it
+    // cover the loads of both stages)
+    for (int c = 0; c + 1 < chunks; c += 2) {
+        turn(c, s1, w0, s_x[0], s_x[1]);
+        turn(c + 1, s0, w1, s_x[1], s_x[0]);
     }
+    if (chunks & 1) turn(chunks - 1, s1, w0, s_x[0], s_x[1]);
 
-    // the 8 partial tiles of the workgroup's 32 rows, summed in wavefront order
-    for (int w = 0; w < kHubWaves; w++) {
-        if (wib == w) {
+    // the 8 partial tiles of the workgroup's 32 rows, side by side, then summed in wavefront order
+    // (the last turn ended with a barrier: nobody reads the images any more)
+    float *part = &s_x[0][0];            // [wavefront][32 ranks][64 columns]; the columns from 16 NT on stay unwritten and unread
 #pragma unroll
-            for (int t = 0; t < 2; t++)
+    for (int t = 0; t < 2; t++)
 #pragma unroll
-                for (int q = 0; q < 4; q++)
+        for (int q = 0; q < NT; q++)
 #pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        float *d = &s_red[t * 16 + (lane >> 4) * 4 + r][q * 16 + (lane & 15)];
-                        *d = w == 0 ? acc[t][q][r] : *d + acc[t][q][r];
-                    }
-        }
-        __syncthreads();
-    }
+            for (int r = 0; r < 4; r++)
+                part[(wib * kHubTileM + t * 16 + (lane >> 4) * 4 + r) * 64 + q * 16 + (lane & 15)] = acc[t][q][r];
+    __syncthreads();
     // one plain read-add-write of Y per element
 #pragma unroll
     for (int i = 0; i < kHubTileM * 64 / kHubThreads; i++) {
         const int idx = i * kHubThreads + tid;
         const int row = idx >> 6, col = idx & 63;
-        const float sum = s_red[row][col];
+        if (col >= D) continue;
+        float sum = part[idx];
+#pragma unroll
+        for (int w = 1; w < kHubWaves; w++) sum += part[w * kHubTileM * 64 + idx];
         const int node = p.r2n[tile0 * 16 + row];
-        if (node < 0 || col >= D || sum == 0.f) continue;
+        if (node < 0 || sum == 0.f) continue;
         float scale = 1.f;
         if (p.scaled) {
             scale = p.eps;
@@ -527,7 +584,16 @@ int launch_hub_block(DeviceState *ds, hipStream_t stream, const DenseBlock &db, 
     p.stale = stale_flag; p.seq = seq; p.H_pad = db.H_pad; p.D = dim; p.ldx = ldx; p.ldy = ldy;
     p.scaled = scaled ? 1 : 0; p.eps = eps;
     (void)ds;
-    hipLaunchKernelGGL(hub_block_kernel, dim3((unsigned)(db.H_pad / kHubTileM)), dim3(kHubThreads), 0, stream, p);
+    if (dim < kDenseMinDim || dim > kDenseMaxDim) return fail(GNNA_ERR_INVALID_ARGUMENT, "hub block: width %d", dim);
+    const bool full = dim % 4 == 0 && ldx % 4 == 0;
+    const dim3 grid((unsigned)(db.H_pad / kHubTileM)), block(kHubThreads);
+    if (dim <= 48) {
+        if (full) hipLaunchKernelGGL((hub_block_kernel<3, true>), grid, block, 0, stream, p);
+        else hipLaunchKernelGGL((hub_block_kernel<3, false>), grid, block, 0, stream, p);
+    } else {
+        if (full) hipLaunchKernelGGL((hub_block_kernel<4, true>), grid, block, 0, stream, p);
+        else hipLaunchKernelGGL((hub_block_kernel<4, false>), grid, block, 0, stream, p);
+    }
     const int rc = launch_ok("hub block launch");
     if (rc == GNNA_OK) count_event(CTR_DENSE_LAUNCHES);
     return rc;
