@@ -161,6 +161,18 @@ ATTNPOOL_SIGNATURES = {
     # input, ld_in, gate, ld_gate, gate_dim, (lse, ld) (Y, ld) (dY, ld), graph_pointers, num_segments, (d_input, ld) (d_gate, ld), num_rows, dim, flags, stream
     "gnna_segment_attn_pool_backward_ld_f32": (i, [p, i64, p, i64, i] + [p, i64] * 3 + [p, i64] + [p, i64] * 2 + [i64, i, u, p]),
 }
+# hierarchical pooling on graph batches (include/gnna_topk.h): a tenth table
+TOPK_SIGNATURES = {
+    # n, ratio, k_fixed
+    "gnna_topk_keep_count": (i64, [i64, ctypes.c_double, i64]),
+    # score, num_rows, graph_pointers, num_segments, ratio, k_fixed, row_pointers, column_index, nnz, partSize, new_id, perm, new_graph_pointers,
+    # new_row_pointers, new_column_index, edge_ids, partPtr, part2Node, row_capacity, edge_capacity, part_capacity, counts, stream
+    "gnna_segment_topk_i32": (i, [p, i64, p, i64, ctypes.c_double, i64, p, p, i64, i] + [p] * 8 + [i64, i64, i64, pi64, p]),
+    # input, ld_in, num_in_rows, perm, scale, out, ld_out, num_out_rows, dim, stream
+    "gnna_gather_rows_scale_ld_f32": (i, [p, i64, i64, p, p, p, i64, i64, i, p]),
+    # d_out, ld_dout, num_out_rows, new_id, input, ld_in, scale, d_input, ld_din, d_scale, num_in_rows, dim, stream
+    "gnna_gather_rows_scale_backward_ld_f32": (i, [p, i64, i64, p, p, i64, p, p, i64, p, i64, i, p]),
+}
 del p, i, i64, u, u64, f, s, pd, pi, pi64
 EXPORTS = tuple(SIGNATURES)
 EXT_EXPORTS = tuple(EXT_SIGNATURES)
@@ -181,6 +193,9 @@ POOL_SIGNATURE_TABLES = (POOL_SIGNATURES,)
 # the table of the header after gnna_pool.h, which load() applies after all of those (the four tuples above stay as their tests pin them)
 ATTNPOOL_EXPORTS = tuple(ATTNPOOL_SIGNATURES)
 ATTNPOOL_SIGNATURE_TABLES = (ATTNPOOL_SIGNATURES,)
+# the table of the header after gnna_attnpool.h, which load() applies last (the five tuples above stay as their tests pin them)
+TOPK_EXPORTS = tuple(TOPK_SIGNATURES)
+TOPK_SIGNATURE_TABLES = (TOPK_SIGNATURES,)
 
 
 def load() -> ctypes.CDLL:
@@ -193,7 +208,8 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -m gnnadvisor_osdi21_amd.build`). There is no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    for table in SIGNATURE_TABLES + LATER_SIGNATURE_TABLES + NEWER_SIGNATURE_TABLES + POOL_SIGNATURE_TABLES + ATTNPOOL_SIGNATURE_TABLES:
+    for table in SIGNATURE_TABLES + LATER_SIGNATURE_TABLES + NEWER_SIGNATURE_TABLES + POOL_SIGNATURE_TABLES + ATTNPOOL_SIGNATURE_TABLES + \
+            TOPK_SIGNATURE_TABLES:
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype = restype
@@ -1520,6 +1536,148 @@ def sample_neighbors(row_pointers, column_index, seeds, fanout, rng_seed, partSi
     return {"row_pointers": blk_rp, "column_index": blk_ci[:nnz], "edge_ids": eid[:nnz] if want_edge_ids else None,
             "src_nodes": src[:num_src], "partPtr": pp[:P + 1] if want_part else None,
             "part2Node": p2n[:P] if want_part else None, "num_dst": S, "num_src": num_src}
+
+
+# ---- hierarchical pooling on graph batches (gnna_topk.hip) -------------------------------------------------------------------
+TOPK_WAVE_ROWS = 256            # GNNA_TOPK_WAVE_ROWS: a segment of up to this many rows is selected by one wavefront
+
+
+def topk_keep_count(n: int, ratio=None, k=None) -> int:
+    """gnna_topk_keep_count: the rows a segment of `n` rows keeps under `ratio` (min(n, ceil(ratio * n)) in double) or under a
+    fixed `k` (min(n, k)); -1 for arguments segment_topk refuses."""
+    return int(load().gnna_topk_keep_count(int(n), 0.0 if ratio is None else float(ratio), 0 if k is None else int(k)))
+
+
+def segment_topk(score, graph_pointers, ratio=None, k=None, row_pointers=None, column_index=None, partSize=None, want_edge_ids=False, *,
+                 row_capacity=None, edge_capacity=None, part_capacity=None):
+    """gnna_segment_topk_i32 (device): for every graph g of a batch -- the rows [graph_pointers[g], graph_pointers[g + 1]) -- the
+    min(n, ceil(ratio * n)) (or min(n, k)) rows with the largest `score` (float32 [N]) in the library's total order, ties to the
+    smaller row, kept in increasing row order; with row_pointers / column_index the induced CSR, with partSize its neighbor-group
+    partition (the rule is spelled out in include/gnna_topk.h).  Exactly one of `ratio` (in (0, 1]) and `k` (>= 1) is given.
+    -> dict: new_id [N] (the new row of a kept row, -1 otherwise), perm [N'] (the old row of every new row), graph_pointers
+    [G + 1], num_rows; row_pointers [N' + 1], column_index [nnz'] (relabelled) and edge_ids [nnz'] (positions in the old
+    column_index; None without want_edge_ids) or None without a CSR; partPtr [P + 1] / part2Node [P] or None without partSize.
+    The arrays are trimmed views of buffers sized here (N rows, nnz edges).  One stream synchronisation; refuses to run inside a
+    stream capture; the same bits on every run.  row_capacity / edge_capacity / part_capacity override the sizes chosen here; a
+    GnnaError raised for a capacity that is too small carries the needed (rows, edges, parts) as ``.counts``."""
+    if not (isinstance(score, torch.Tensor) and score.is_cuda):
+        raise GnnaError("segment_topk needs device tensors: there is no CPU path in libgnna")
+    assert score.dtype == torch.float32 and score.dim() == 1 and score.is_contiguous(), "score must be a contiguous float32 tensor [N]"
+    dev = score.device
+    gp, G = _graph_pointers_arg(graph_pointers, dev)
+    if (row_pointers is None) != (column_index is None):
+        raise ValueError("row_pointers and column_index come together")
+    csr = row_pointers is not None
+    want_part = partSize is not None
+    if want_part and not csr:
+        raise ValueError("a partition needs row_pointers and column_index")
+    if want_part and int(partSize) <= 0:
+        raise GnnaError(f"partSize must be positive (got {partSize})")
+    n = score.numel()
+    nnz = 0
+    if csr:
+        rp, ci = _device_i32(row_pointers, "row_pointers"), _device_i32(column_index, "column_index")
+        assert rp.numel() == n + 1 and rp.device == dev and ci.device == dev, "row_pointers must be [N + 1]; it and column_index live on score's device"
+        nnz = ci.numel()
+    row_cap = n if row_capacity is None else int(row_capacity)
+    edge_cap = nnz if edge_capacity is None else int(edge_capacity)
+    part_cap = (edge_cap if part_capacity is None else int(part_capacity)) if want_part else 0
+    if row_cap < 0 or edge_cap < 0 or part_cap < 0:
+        raise GnnaError("capacities must not be negative")
+    with torch.cuda.device(dev):
+        i32 = dict(dtype=torch.int32, device=dev)
+        new_id, perm, new_gp = torch.empty(n, **i32), torch.empty(row_cap, **i32), torch.empty(G + 1, **i32)
+        new_rp = torch.empty(row_cap + 1, **i32) if csr else None
+        new_ci = torch.empty(edge_cap, **i32) if csr else None
+        eid = torch.empty(edge_cap, **i32) if csr and want_edge_ids else None
+        pp = torch.empty(part_cap + 1, **i32) if want_part else None
+        p2n = torch.empty(part_cap, **i32) if want_part else None
+        counts = (ctypes.c_int64 * 3)()
+        rc = load().gnna_segment_topk_i32(_ptr(score) if n > 0 else None, n, gp, G, 0.0 if ratio is None else float(ratio),
+                                          0 if k is None else int(k), _ptr(rp) if csr else None,
+                                          (_ptr(ci) if nnz > 0 else None) if csr else None, nnz, int(partSize) if want_part else 0,
+                                          _ptr(new_id) if n > 0 else None, _ptr(perm) if row_cap > 0 else None, new_gp.data_ptr(),
+                                          _ptr(new_rp), _ptr(new_ci) if csr and edge_cap > 0 else None,
+                                          _ptr(eid) if eid is not None and edge_cap > 0 else None, _ptr(pp),
+                                          _ptr(p2n) if want_part and part_cap > 0 else None, row_cap, edge_cap, part_cap, counts,
+                                          _stream(dev))
+    if rc != GNNA_OK:
+        err = GnnaError(f"libgnna error {rc}: {load().gnna_last_error().decode()}")
+        err.counts = tuple(int(c) for c in counts)
+        raise err
+    rows, edges, P = int(counts[0]), int(counts[1]), int(counts[2])
+    return {"new_id": new_id, "perm": perm[:rows], "graph_pointers": new_gp, "num_rows": rows,
+            "row_pointers": new_rp[:rows + 1] if csr else None, "column_index": new_ci[:edges] if csr else None,
+            "edge_ids": eid[:edges] if eid is not None else None, "partPtr": pp[:P + 1] if want_part else None,
+            "part2Node": p2n[:P] if want_part else None}
+
+
+def _row_ids_arg(t, n, device, what):
+    assert t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous() and t.numel() == n and t.device == device, \
+        f"{what} must be a contiguous int32 tensor [{n}] on {device}"
+    return t.data_ptr() if n > 0 else None
+
+
+def _scale_arg(scale, n, device):
+    if scale is None:
+        return None
+    assert scale.dtype == torch.float32 and scale.dim() == 1 and scale.is_contiguous() and scale.numel() == n and scale.device == device, \
+        f"scale must be a contiguous float32 tensor [{n}] on {device}"
+    return scale.data_ptr() if n > 0 else None
+
+
+def gather_rows_scale(X, perm, scale=None, out=None):
+    """gnna_gather_rows_scale_ld_f32 (include/gnna_topk.h): out[i, :] = scale[perm[i]] * X[perm[i], :], one fp32 multiplication
+    per element; scale=None is a plain gather; a perm[i] outside [0, rows of X) gives a row of zeros.  perm: int32 [M] on X's
+    device, scale: float32 [N].  -> out [M, dim].  `X` and `out` may be row-strided views (stride(1) == 1).  Capturable; the same
+    bits on every run; accepted under set_tuning(deterministic=1)."""
+    _need_device(X, "gather_rows_scale")
+    xp, n, dim, ld_in = _rows_view(X, "X")
+    m = perm.numel()
+    pp = _row_ids_arg(perm, m, X.device, "perm")
+    sp = _scale_arg(scale, n, X.device)
+    out, op_, ld_out = _out_rows(out, m, dim, X.device)
+    if m > 0:
+        _call(X.device, "gnna_gather_rows_scale_ld_f32", xp if n > 0 else None, ld_in, n, pp, sp, op_, ld_out, m, dim)
+    return out
+
+
+def gather_rows_scale_backward(dY, new_id, X=None, scale=None, need_input=True, need_scale=True, out=None):
+    """gnna_gather_rows_scale_backward_ld_f32: with j = new_id[r] (kept: 0 <= j < rows of dY), d_input[r, :] = scale[r] * dY[j, :]
+    and d_scale[r] = <dY[j, :], X[r, :]> for a kept row, 0 for every other.  One pass that writes every element once, nothing is
+    cleared first.  -> (d_input [N, dim] | None, d_scale [N] | None): need_input / need_scale (not both False) choose what is
+    computed; need_scale needs X; `out` may supply "d_input" / "d_scale".  With scale=None and need_scale=False this is the
+    unpooling of a Graph U-Net: the rows of dY placed back at their old rows, zeros elsewhere.  Strided views as in
+    gather_rows_scale."""
+    if not need_input and not need_scale:
+        raise ValueError("gather_rows_scale_backward needs need_input or need_scale")
+    if need_scale and X is None:
+        raise ValueError("gather_rows_scale_backward: need_scale needs X")
+    _need_device(dY, "gather_rows_scale_backward")
+    dp, m, dim, ld_dout = _rows_view(dY, "dY")
+    n = new_id.numel()
+    ip = _row_ids_arg(new_id, n, dY.device, "new_id")
+    xp, ld_in = None, dim
+    if need_scale:
+        xp, xn, xw, ld_in = _rows_view(X, "X")
+        assert (xn, xw) == (n, dim) and X.device == dY.device, f"X must be [{n}, {dim}] on {dY.device}"
+    sp = _scale_arg(scale, n, dY.device)
+    given = dict(out or {})
+    d_input = d_scale = dip = dsp = None
+    ld_din = dim
+    if need_input:
+        d_input, dip, ld_din = _out_rows(given.get("d_input"), n, dim, dY.device)
+    if need_scale:
+        d_scale = given.get("d_scale")
+        if d_scale is None:
+            d_scale = _fresh_output((n,), dY.device)
+        assert d_scale.dtype == torch.float32 and d_scale.dim() == 1 and d_scale.is_contiguous() and d_scale.numel() == n and \
+            d_scale.device == dY.device, f"d_scale must be a contiguous float32 tensor [{n}] on {dY.device}"
+        dsp = d_scale.data_ptr() if n > 0 else None
+    if n > 0:
+        _call(dY.device, "gnna_gather_rows_scale_backward_ld_f32", dp if m > 0 else None, ld_dout, m, ip, xp, ld_in, sp, dip, ld_din,
+              dsp, n, dim)
+    return d_input, d_scale
 
 
 # ---- relation-typed aggregation (gnna_typed.hip) ---------------------------------------------------------------------------

@@ -20,12 +20,21 @@ from .decider import WAVES_PER_BLOCK, inputProperty, lanes_per_row
 from .graph import degrees_from_rowptr
 
 
+class TopKSelection(object):
+    """What ``GraphBatch.coarsen`` kept: ``perm`` int32 [N'] (the old row of every new row, increasing), ``new_id`` int32 [N] (the
+    new row of a kept row, -1 otherwise), ``edge_ids`` int32 [nnz'] or None (the old position of every surviving edge) and
+    ``num_nodes`` (the old N)."""
+
+    def __init__(self, perm, new_id, edge_ids, num_nodes):
+        self.perm, self.new_id, self.edge_ids, self.num_nodes = perm, new_id, edge_ids, int(num_nodes)
+
+
 class GraphBatch(object):
     """A block-diagonal CSR of ``num_graphs`` graphs and ``graph_pointers``.  ``batch`` (int64 [N]: the graph of every row) and
     ``inv_counts`` (float32 [G]: 1 / max(rows of the graph, 1)) are built at their first use; the fused readout needs neither."""
 
     def __init__(self, row_pointers, column_index, graph_pointers, degrees=None, partSize=32, dimWorker=None, warpPerBlock=None,
-                 hiddenDim=64, directed=False, x=None, y=None):
+                 hiddenDim=64, directed=False, x=None, y=None, partPtr=None, part2Node=None):
         for name, t in (("row_pointers", row_pointers), ("column_index", column_index), ("graph_pointers", graph_pointers)):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1:
                 raise TypeError(f"{name} must be a 1-D int32 tensor")
@@ -41,7 +50,11 @@ class GraphBatch(object):
         self.warpPerBlock = int(warpPerBlock) if warpPerBlock is not None else WAVES_PER_BLOCK
         self.directed = bool(directed)
         self.x, self.y = x, y
-        if self.row_pointers.is_cuda:
+        if (partPtr is None) != (part2Node is None):
+            raise ValueError("partPtr and part2Node come together")
+        if partPtr is not None:                                    # the partition of these row pointers at partSize, already built
+            self.partPtr, self.part2Node = partPtr, part2Node
+        elif self.row_pointers.is_cuda:
             self.partPtr, self.part2Node = _lib.build_part_device(self.partSize, self.row_pointers)
         else:
             self.partPtr, self.part2Node = _lib.build_part(self.partSize, self.row_pointers)
@@ -80,6 +93,27 @@ class GraphBatch(object):
             gp = self.graph_pointers.long()
             self._inv_counts = 1.0 / (gp[1:] - gp[:-1]).clamp(min=1).float()
         return self._inv_counts
+
+    def coarsen(self, score, ratio=None, k=None, want_edge_ids=False):
+        """``(GraphBatch, selection)``: every graph keeps its min(n, ceil(ratio * n)) -- or min(n, k) -- rows with the largest
+        `score` (float32 [N] on the batch's device; its values decide, no gradient flows through the choice), and the induced
+        sub-batch is cut out on the device in ONE call (libgnna gnna_segment_topk_i32: rows, graph_pointers, CSR and partition; one
+        read-back).  The kept rows stay in row order, so the rows of a graph stay contiguous.  The new batch carries `directed`,
+        `partSize` and the launch knobs of this one, its degrees come from the new row pointers, and `x` / `y` are not moved: gather
+        the rows with ops.SelectRows.  `selection` is a TopKSelection: perm [N'] (the old row of every new row), new_id [N] (-1 for
+        a dropped row), edge_ids [nnz'] (the old position of every edge; None unless asked for) and num_nodes (the old N)."""
+        if not self.row_pointers.is_cuda:
+            raise _lib.GnnaError("GraphBatch.coarsen needs a batch on the device: there is no CPU path in libgnna")
+        if (ratio is None) == (k is None):
+            raise ValueError("coarsen takes exactly one of ratio and k")
+        score = score.detach().reshape(-1)
+        if score.dtype != torch.float32 or score.numel() != self.num_nodes or score.device != self.row_pointers.device:
+            raise TypeError(f"score must be float32 [{self.num_nodes}] on {self.row_pointers.device}")
+        r = _lib.segment_topk(score.contiguous(), self.graph_pointers, ratio=ratio, k=k, row_pointers=self.row_pointers,
+                              column_index=self.column_index, partSize=self.partSize, want_edge_ids=want_edge_ids)
+        small = GraphBatch(r["row_pointers"], r["column_index"], r["graph_pointers"], partSize=self.partSize, dimWorker=self.dimWorker,
+                           warpPerBlock=self.warpPerBlock, directed=self.directed, partPtr=r["partPtr"], part2Node=r["part2Node"])
+        return small, TopKSelection(r["perm"], r["new_id"], r["edge_ids"], self.num_nodes)
 
     def to(self, device):
         move = lambda t: None if t is None else t.to(device)                                       # noqa: E731

@@ -40,6 +40,7 @@
 #include "gnna_softagg.h"
 #include "gnna_pool.h"
 #include "gnna_attnpool.h"
+#include "gnna_topk.h"
 
 #define CHECK_CUDA(x) TORCH_CHECK(x.is_cuda(), #x " must be a CUDA tensor")
 #define CHECK_CONTIGUOUS(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -1432,6 +1433,117 @@ std::vector<torch::Tensor> build_part_device(int partSize, const torch::Tensor &
     return {partPtr, part2Node};
 }
 
+// ---- hierarchical pooling on graph batches (gnna_topk.hip) ------------------------------------------------------------------
+
+// Top-k selection per graph and the induced sub-batch (gnna_segment_topk_i32) -> (new_id [N], perm [N'], new_graph_pointers
+// [G + 1], new_row_pointers [N' + 1], new_column_index [nnz'], edge_ids [nnz'], partPtr [P + 1], part2Node [P]); None for what was
+// not asked for (the CSR without row_pointers / column_index, edge_ids without want_edge_ids, the partition with partSize = 0).
+// ratio = 0 or k = 0 says which of the two is given.  The arrays are trimmed views of buffers of N rows and nnz edges.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>,
+           c10::optional<torch::Tensor>, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>>
+segment_topk(const torch::Tensor &score, const torch::Tensor &graph_pointers, double ratio, int64_t k,
+             const c10::optional<torch::Tensor> &row_pointers, const c10::optional<torch::Tensor> &column_index, int64_t partSize,
+             bool want_edge_ids)
+{
+    check_floats(score, "score");
+    TORCH_CHECK(score.dim() == 1, "score must be 1-D [num_nodes]");
+    check_device_ids(graph_pointers, "graph_pointers");
+    TORCH_CHECK(graph_pointers.numel() >= 1 && graph_pointers.device() == score.device(),
+                "graph_pointers must be [num_graphs + 1], on score's device");
+    TORCH_CHECK(row_pointers.has_value() == column_index.has_value(), "row_pointers and column_index come together");
+    TORCH_CHECK(partSize >= 0 && partSize <= std::numeric_limits<int>::max(), "partSize must not be negative");
+    const bool csr = row_pointers.has_value(), parts = partSize > 0;
+    TORCH_CHECK(csr || !parts, "a partition needs row_pointers and column_index");
+    const int64_t n = score.numel(), g = graph_pointers.numel() - 1;
+    int64_t nnz = 0;
+    if (csr) {
+        check_device_ids(*row_pointers, "row_pointers");
+        check_device_ids(*column_index, "column_index");
+        TORCH_CHECK(row_pointers->numel() == n + 1 && row_pointers->device() == score.device() && column_index->device() == score.device(),
+                    "row_pointers must be [num_nodes + 1]; it and column_index live on score's device");
+        nnz = column_index->numel();
+    }
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(score.device());
+    const auto ids = graph_pointers.options();
+    const torch::Tensor new_id = torch::empty({n}, ids), perm = torch::empty({n}, ids), new_gp = torch::empty({g + 1}, ids);
+    torch::Tensor new_rp, new_ci, eid, pp, p2n;
+    if (csr) { new_rp = torch::empty({n + 1}, ids); new_ci = torch::empty({nnz}, ids); }
+    if (csr && want_edge_ids) eid = torch::empty({nnz}, ids);
+    if (parts) { pp = torch::empty({nnz + 1}, ids); p2n = torch::empty({nnz}, ids); }
+    auto ip = [](const torch::Tensor &t) { return t.defined() && t.numel() > 0 ? t.data_ptr<int32_t>() : nullptr; };
+    int64_t counts[3] = {0, 0, 0};
+    check_rc(gnna_segment_topk_i32(n > 0 ? score.data_ptr<float>() : nullptr, n, graph_pointers.data_ptr<int32_t>(), g, ratio, k,
+                                   csr ? row_pointers->data_ptr<int32_t>() : nullptr, csr ? ip(*column_index) : nullptr, nnz, (int)partSize,
+                                   ip(new_id), ip(perm), new_gp.data_ptr<int32_t>(), ip(new_rp), ip(new_ci), ip(eid), ip(pp), ip(p2n), n,
+                                   nnz, parts ? nnz : 0, counts, current_stream()));
+    auto opt = [](const torch::Tensor &t, int64_t len) { return t.defined() ? c10::optional<torch::Tensor>(t.narrow(0, 0, len)) : c10::nullopt; };
+    return std::make_tuple(new_id, perm.narrow(0, 0, counts[0]), new_gp, opt(new_rp, counts[0] + 1), opt(new_ci, counts[1]),
+                           opt(eid, counts[1]), opt(pp, counts[2] + 1), opt(p2n, counts[2]));
+}
+
+// what both row gathers check of their features, row ids and scale
+static void gather_rows_check(const torch::Tensor &rows, const char *rows_name, const torch::Tensor &ids, const char *ids_name,
+                              const c10::optional<torch::Tensor> &scale, int64_t scale_len)
+{
+    TORCH_CHECK(rows.is_cuda(), rows_name, " must be a CUDA tensor");
+    TORCH_CHECK(rows.dim() == 2 && rows.size(1) >= 1, rows_name, " must be 2-D [rows, dim] with at least one column");
+    check_f32(rows, rows_name);
+    check_rows(rows, rows_name);
+    check_device_ids(ids, ids_name);
+    TORCH_CHECK(ids.device() == rows.device(), rows_name, " and ", ids_name, " must be on one device");
+    if (scale.has_value()) {
+        check_floats(*scale, "scale");
+        TORCH_CHECK(scale->dim() == 1 && scale->numel() == scale_len && scale->device() == rows.device(),
+                    "scale must be [num_nodes = ", scale_len, "] on ", rows_name, "'s device");
+    }
+}
+
+// Scaled gather of rows (gnna_gather_rows_scale_ld_f32) -> out [perm.numel(), dim]: out[i] = scale[perm[i]] * input[perm[i]]; a
+// plain gather without scale; a perm[i] outside the rows of input gives zeros.  Strided input as aggregate_ld.
+torch::Tensor gather_rows_scale(const torch::Tensor &input, const torch::Tensor &perm, const c10::optional<torch::Tensor> &scale)
+{
+    gather_rows_check(input, "input", perm, "perm", scale, input.dim() == 2 ? input.size(0) : 0);
+    const int64_t n = input.size(0), dim = input.size(1), m = perm.numel();
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(input.device());
+    const torch::Tensor out = fresh({m, dim}, input.options());
+    if (m == 0) return out;
+    check_rc(gnna_gather_rows_scale_ld_f32(n > 0 ? input.data_ptr<float>() : nullptr, ld_of(input), n, perm.data_ptr<int32_t>(),
+                                           scale.has_value() && n > 0 ? scale->data_ptr<float>() : nullptr, out.data_ptr<float>(), dim, m,
+                                           (int)dim, current_stream()));
+    return out;
+}
+
+// Backward of gather_rows_scale (gnna_gather_rows_scale_backward_ld_f32) -> (d_input [num_nodes, dim], d_scale [num_nodes]), None
+// for the one that is not needed: a kept row r (0 <= new_id[r] < rows of d_out) gets scale[r] * d_out[new_id[r]] and
+// <d_out[new_id[r]], input[r]>, every other row 0.  Without scale and d_scale: the unpooling of the rows of d_out.
+std::tuple<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>>
+gather_rows_scale_backward(const torch::Tensor &d_out, const torch::Tensor &new_id, const c10::optional<torch::Tensor> &input,
+                           const c10::optional<torch::Tensor> &scale, bool need_input, bool need_scale)
+{
+    gather_rows_check(d_out, "d_out", new_id, "new_id", scale, new_id.numel());
+    TORCH_CHECK(need_input || need_scale, "neither d_input nor d_scale asked for");
+    TORCH_CHECK(!need_scale || input.has_value(), "d_scale needs input");
+    const int64_t m = d_out.size(0), dim = d_out.size(1), n = new_id.numel();
+    if (need_scale) {
+        CHECK_CUDA((*input));
+        CHECK_F32((*input));
+        TORCH_CHECK(input->dim() == 2 && input->size(0) == n && input->size(1) == dim && input->device() == d_out.device(),
+                    "input must be [num_nodes, dim] on d_out's device");
+        check_rows(*input, "input");
+    }
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(d_out.device());
+    c10::optional<torch::Tensor> d_input, d_scale;
+    if (need_input) d_input = fresh({n, dim}, d_out.options());
+    if (need_scale) d_scale = fresh({n}, d_out.options());
+    if (n == 0) return std::make_tuple(d_input, d_scale);
+    check_rc(gnna_gather_rows_scale_backward_ld_f32(m > 0 ? d_out.data_ptr<float>() : nullptr, ld_of(d_out), m, new_id.data_ptr<int32_t>(),
+                                                    need_scale ? input->data_ptr<float>() : nullptr, need_scale ? ld_of(*input) : dim,
+                                                    scale.has_value() ? scale->data_ptr<float>() : nullptr,
+                                                    need_input ? d_input->data_ptr<float>() : nullptr, dim,
+                                                    need_scale ? d_scale->data_ptr<float>() : nullptr, n, (int)dim, current_stream()));
+    return std::make_tuple(d_input, d_scale);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
 {
     m.def("SAG", &SAG, "GNNAdvisor base Scatter-and-Gather Kernel (HIP, gfx950)");
@@ -1503,6 +1615,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           "per row; one pass that writes every row, 0 for a row of no graph",
           pybind11::arg("X"), pybind11::arg("gate"), pybind11::arg("lse"), pybind11::arg("Y"), pybind11::arg("dY"),
           pybind11::arg("graph_pointers"), pybind11::arg("need_input") = true, pybind11::arg("need_gate") = true);
+    m.def("segment_topk", &segment_topk,
+          "top-k rows per graph of a batch and the induced sub-batch (extension) -> (new_id [N], perm [N'], new_graph_pointers [G + 1], "
+          "new_row_pointers, new_column_index, edge_ids, partPtr, part2Node): every graph keeps its min(n, ceil(ratio * n)) -- or "
+          "min(n, k) -- best-scoring rows in the library's total order, ties to the smaller row, in increasing row order; None for what "
+          "was not asked for.  One stream synchronisation; not capturable",
+          pybind11::arg("score"), pybind11::arg("graph_pointers"), pybind11::arg("ratio") = 0.0, pybind11::arg("k") = 0,
+          pybind11::arg("row_pointers") = pybind11::none(), pybind11::arg("column_index") = pybind11::none(),
+          pybind11::arg("partSize") = 0, pybind11::arg("want_edge_ids") = false);
+    m.def("gather_rows_scale", &gather_rows_scale,
+          "out[i] = scale[perm[i]] * input[perm[i]] (extension) -> out [perm.numel(), dim]; a plain gather without scale; a perm[i] "
+          "outside the rows of input gives a row of zeros",
+          pybind11::arg("input"), pybind11::arg("perm"), pybind11::arg("scale") = pybind11::none());
+    m.def("gather_rows_scale_backward", &gather_rows_scale_backward,
+          "backward of gather_rows_scale (extension) -> (d_input, d_scale), None for the one not needed: a kept row r gets "
+          "scale[r] * d_out[new_id[r]] and <d_out[new_id[r]], input[r]>, every other row 0; without scale and d_scale it is the "
+          "unpooling of the rows of d_out",
+          pybind11::arg("d_out"), pybind11::arg("new_id"), pybind11::arg("input") = pybind11::none(),
+          pybind11::arg("scale") = pybind11::none(), pybind11::arg("need_input") = true, pybind11::arg("need_scale") = true);
     m.def("scatter_arg", &scatter_arg,
           "backward of aggregate_reduce (extension): grad_in[column_index[arg[i, f]], f] += grad_out[i, f] for arg >= 0",
           pybind11::arg("grad_out"), pybind11::arg("arg"), pybind11::arg("column_index"), pybind11::arg("num_in_rows"));

@@ -5,7 +5,9 @@
 The reference evaluates half of its inputs ("Type II": collections of small graphs) with node-level drivers only; this driver
 finishes such a model inside the library.  A seeded synthetic collection (graph.small_graphs) is kept on the device as a
 batching.GraphDataset; every step cuts a mini-batch of ``--batch_graphs`` graphs out of it (GraphDataset.batch), runs two or more
-GCN / GIN layers on the block-diagonal CSR, reduces the node rows of every graph to one row (ops.Readout, one fused call for all
+GCN / GIN layers on the block-diagonal CSR (with ``--pool topk|sag`` a pooling layer after every conv layer but the last keeps
+the best-scoring ``--pool_ratio`` of the nodes of every graph and the next layer runs on the coarsened batch), reduces the node
+rows of every graph to one row (ops.Readout, one fused call for all
 the statistics of ``--readout``; with ``--attention_readout scalar|channel`` an ops.AttentionalReadout next to them), and trains
 a per-graph classifier.  Prints ``Time (ms): %.3f`` per epoch as main.py does.
 The label of a graph is a function of its size and its features' mean, so that the loss has something to learn.
@@ -33,6 +35,11 @@ def build_parser():
     p.add_argument("--readout", type=str, default="sum", help="comma list of sum, mean, max, min")
     p.add_argument("--attention_readout", type=str, default="none",
                    help="none, scalar or channel: an attention readout after the --readout statistics, gated per row or per element")
+    p.add_argument("--pool", type=str, default="none",
+                   help="none, topk or sag: a pooling layer (ops.TopKPooling / ops.SAGPooling) after every conv layer but the last; "
+                        "the readout is taken on the last level")
+    p.add_argument("--pool_ratio", type=float, default=0.5, help="the share of its nodes every graph keeps at a pooling layer")
+    p.add_argument("--fused_pool", type=_bool, default=True, help="False: the pooling composed from torch ops")
     p.add_argument("--fused_readout", type=_bool, default=True, help="False: the readout composed from torch ops")
     p.add_argument("--dim", type=int, default=32, help="input feature width")
     p.add_argument("--hidden", type=int, default=64, help="hidden width")
@@ -66,6 +73,10 @@ def _parse(args):
         raise SystemExit("--readout takes a comma list of sum, mean, max, min, each once (got %r)" % args.readout)
     if args.attention_readout not in ("none", "scalar", "channel"):
         raise SystemExit("--attention_readout takes none, scalar or channel (got %r)" % args.attention_readout)
+    if args.pool not in ("none", "topk", "sag"):
+        raise SystemExit("--pool takes none, topk or sag (got %r)" % args.pool)
+    if not 0.0 < args.pool_ratio <= 1.0:
+        raise SystemExit("--pool_ratio must be in (0, 1] (got %r)" % args.pool_ratio)
     if args.num_graphs < 1:
         raise SystemExit("--num_graphs must be >= 1")
     if args.batch_graphs < 1:
@@ -80,7 +91,7 @@ def _parse(args):
 def build_model(args, modes):
     from torch.nn import Linear, Module, ModuleList
 
-    from .ops import AttentionalReadout, GCNConv, GINConv, Readout
+    from .ops import AttentionalReadout, GCNConv, GINConv, Readout, SAGPooling, TopKPooling
     conv = GCNConv if args.model == "gcn" else GINConv
     attention = args.attention_readout != "none"
 
@@ -94,10 +105,22 @@ def build_model(args, modes):
             self.attention = AttentionalReadout(Linear(args.hidden, 1 if args.attention_readout == "scalar" else args.hidden),
                                                 fused=args.fused_readout) if attention else None
             self.lin = Linear(args.hidden * (len(modes) + (1 if attention else 0)), args.classes)
+            # hierarchical pooling: every conv layer but the last hands a coarsened batch to the next one
+            self.pools = None
+            if args.pool != "none":
+                pool = (lambda: TopKPooling(args.hidden, ratio=args.pool_ratio, fused=args.fused_pool)) if args.pool == "topk" else \
+                    (lambda: SAGPooling(args.hidden, ratio=args.pool_ratio, GNN=conv, fused=args.fused_pool))
+                self.pools = ModuleList(pool() for _ in range(args.num_layers - 1))
+            self.levels = []           # (rows, edges) of every level of the latest forward pass
 
         def forward(self, x, batch):
-            for layer in self.convs:
+            levels = [(batch.num_nodes, int(batch.column_index.numel()))]
+            for k, layer in enumerate(self.convs):
                 x = torch.relu(layer(x, batch))
+                if self.pools is not None and k < len(self.pools):
+                    x, batch, _selection, _gate = self.pools[k](x, batch)
+                    levels.append((batch.num_nodes, int(batch.column_index.numel())))
+            self.levels = levels
             pooled = self.readout(x, batch)
             if self.attention is not None:
                 pooled = torch.cat((pooled, self.attention(x, batch)), 1)
@@ -162,6 +185,10 @@ def main(argv=None, capture=None):
         capture.update(first_loss=float(first))
     if args.verbose_mode:
         print("# loss after 1 epoch: {:.6f}".format(float(first)))
+        if args.pool != "none":
+            print("# pooling %s at ratio %g (%s); the last batch, level by level: %s" % (
+                args.pool, args.pool_ratio, "fused" if args.fused_pool else "composed",
+                ", ".join("%d rows %d edges" % level for level in model.levels)))
     torch.cuda.synchronize()
     start = time.perf_counter()
     for _ in range(args.num_epoches):

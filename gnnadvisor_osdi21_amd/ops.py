@@ -1771,3 +1771,194 @@ class AttentionalReadout(Module):
         if not self.fused:
             return _composed_attention_readout(V, gate, batch)
         return SegmentAttentionPool.apply(V, gate, batch)
+
+
+# ---- hierarchical pooling: the best-scoring rows of every graph, the induced sub-batch, and the way back ----------------------
+def _f32_only(t, who):
+    if t.dtype != torch.float32 or _x16_dtype(t) is not None:
+        raise TypeError(f"{who} computes in float32 only: 16-bit features and torch.autocast are not supported "
+                        f"(got {t.dtype}{', inside torch.autocast' if t.dtype == torch.float32 else ''})")
+
+
+class SelectRows(Function):
+    """``SelectRows.apply(X, scale, selection) -> X' [N', F]``: the rows a ``GraphBatch.coarsen`` kept, X'[i] = scale[perm[i]] *
+    X[perm[i]] (libgnna gnna_gather_rows_scale_ld_f32, one pass, one multiplication per element); `scale` is a float32 [N] or
+    None (a plain gather), `selection` the TopKSelection of coarsen.
+
+    Backward: one pass over the rows of X (libgnna gnna_gather_rows_scale_backward_ld_f32) that writes every element of dX =
+    scale * dX'[new_id] and of d_scale = <dX'[new_id], X> once, zeros for the rows that were dropped -- no zero-fill, no
+    index_add_.  The op saves new_id [N], X only when scale needs a gradient and scale only when X does: nothing of the size of X
+    beyond X itself.  The same bits on every run.  float32 only."""
+
+    @staticmethod
+    def forward(ctx, X, scale, selection):
+        _f32_only(X, "SelectRows")
+        if X.dim() != 2 or X.shape[0] != selection.num_nodes:
+            raise ValueError(f"SelectRows: X must be [{selection.num_nodes}, F] (got {tuple(X.shape)})")
+        if scale is not None:
+            _f32_only(scale, "SelectRows")
+            if scale.numel() != X.shape[0]:
+                raise ValueError(f"SelectRows: scale must hold one factor per row of X ({X.shape[0]}; got {tuple(scale.shape)})")
+        ctx.scale_shape = None if scale is None else tuple(scale.shape)
+        if scale is not None:
+            scale = scale.reshape(-1).contiguous()
+        ctx.set_materialize_grads(False)
+        Xl = _laid_out(X)
+        need_x, need_scale = ctx.needs_input_grad[0], scale is not None and ctx.needs_input_grad[1]
+        ctx.save_for_backward(selection.new_id, Xl if need_scale else None, scale if need_x else None)
+        return GNNA.gather_rows_scale(Xl, selection.perm, scale)
+
+    @staticmethod
+    def backward(ctx, dY):
+        need_x, need_scale = ctx.needs_input_grad[0], ctx.scale_shape is not None and ctx.needs_input_grad[1]
+        if dY is None or not (need_x or need_scale):
+            return None, None, None
+        new_id, X, scale = ctx.saved_tensors
+        dX, dS = GNNA.gather_rows_scale_backward(_laid_out(dY), new_id, X, scale, need_x, need_scale)
+        return dX, None if dS is None else dS.view(ctx.scale_shape), None
+
+
+class UnpoolRows(Function):
+    """``UnpoolRows.apply(X_small, selection) -> [N, F]``: the rows of X_small back at the rows they were selected from, zeros
+    elsewhere (the unpooling of a Graph U-Net), in the one pass of gnna_gather_rows_scale_backward_ld_f32 without a zero-fill;
+    the backward is the plain gather."""
+
+    @staticmethod
+    def forward(ctx, X_small, selection):
+        _f32_only(X_small, "unpool")
+        if X_small.dim() != 2 or X_small.shape[0] != selection.perm.numel():
+            raise ValueError(f"unpool: X_small must be [{selection.perm.numel()}, F] (got {tuple(X_small.shape)})")
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(selection.perm)
+        return GNNA.gather_rows_scale_backward(_laid_out(X_small), selection.new_id, None, None, True, False)[0]
+
+    @staticmethod
+    def backward(ctx, dY):
+        if dY is None or not ctx.needs_input_grad[0]:
+            return None, None
+        perm, = ctx.saved_tensors
+        return GNNA.gather_rows_scale(_laid_out(dY), perm, None), None
+
+
+def unpool(X_small, selection):
+    """[N, F]: the rows of `X_small` [N', F] placed back at the rows `selection` (GraphBatch.coarsen) took them from, zeros for
+    the rows that were dropped."""
+    return UnpoolRows.apply(X_small, selection)
+
+
+def _order_key(score):
+    """int64 [N]: keys that order like the float32 `score` in the library's total order (-0 below +0, a NaN with a clear sign bit
+    above +inf, one with the sign bit set below -inf) -- gnna_keys.h from torch ops."""
+    b = score.contiguous().view(torch.int32).long() & 0xFFFFFFFF
+    return torch.where(b >= 0x80000000, 0xFFFFFFFF - b, b + 0x80000000)
+
+
+def _composed_coarsen(batch, score, ratio=None, k=None):
+    """``GraphBatch.coarsen`` from torch ops, the same rows under the same tie rule: two stable sorts over the whole batch (by
+    key, then by graph), boolean masks over the rows and the edges, cumulative sums for the new ids and row pointers, and the
+    partition built again from the new row pointers.  The timing baseline and a second opinion; graph_pointers must ascend."""
+    from .batching import GraphBatch, TopKSelection
+    if (ratio is None) == (k is None):
+        raise ValueError("coarsen takes exactly one of ratio and k")
+    dev, N = score.device, batch.num_nodes
+    gp, G, rows, lo = _batch_vector(batch, dev)
+    sizes = (gp[1:] - gp[:-1]).clamp(min=0)
+    if k is not None:
+        keep_n = sizes.clamp(max=int(k))
+    else:
+        keep_n = torch.minimum(sizes, torch.ceil(float(ratio) * sizes.double()).long())
+    key = _order_key(score.detach().reshape(-1))[lo: lo + rows.numel()]
+    by_key = torch.sort(key, descending=True, stable=True).indices            # equal keys stay in row order
+    by_graph = torch.sort(rows[by_key], stable=True).indices                   # then graph by graph, best first
+    order = by_key[by_graph]
+    g_sorted = rows[order]
+    rank = torch.arange(order.numel(), device=dev) - (gp[:-1] - lo)[g_sorted]
+    mask = torch.zeros(N, dtype=torch.bool, device=dev)
+    mask[lo + order[rank < keep_n[g_sorted]]] = True
+    perm = mask.nonzero().reshape(-1)
+    new_id = torch.where(mask, torch.cumsum(mask, 0) - 1, torch.full((N,), -1, dtype=torch.int64, device=dev))
+    new_gp = torch.zeros(G + 1, dtype=torch.int64, device=dev)
+    new_gp[1:] = torch.cumsum(keep_n, 0)
+    e_rows, ci = batch.edge_rows().long(), batch.column_index.long()
+    inside = (ci >= 0) & (ci < N)
+    alive = mask[e_rows] & inside & mask[ci.clamp(0, max(N - 1, 0))] if N > 0 else torch.zeros_like(inside)
+    edge_ids = alive.nonzero().reshape(-1)
+    new_ci = new_id[ci[edge_ids]]
+    counts = torch.zeros(perm.numel(), dtype=torch.int64, device=dev).index_add_(0, new_id[e_rows[edge_ids]], torch.ones_like(edge_ids))
+    new_rp = torch.zeros(perm.numel() + 1, dtype=torch.int64, device=dev)
+    new_rp[1:] = torch.cumsum(counts, 0)
+    small = GraphBatch(new_rp.to(torch.int32), new_ci.to(torch.int32), new_gp.to(torch.int32), partSize=batch.partSize,
+                       dimWorker=batch.dimWorker, warpPerBlock=batch.warpPerBlock, directed=batch.directed)
+    return small, TopKSelection(perm.to(torch.int32), new_id.to(torch.int32), edge_ids.to(torch.int32), N)
+
+
+_GATES = {"tanh": torch.tanh, "sigmoid": torch.sigmoid, None: None}
+
+
+class _ScorePooling(Module):
+    """What TopKPooling and SAGPooling share: the gate, the selection and the scaled gather, fused or composed."""
+
+    def __init__(self, ratio, k, multiplier, nonlinearity, fused):
+        super().__init__()
+        if nonlinearity not in _GATES:
+            raise ValueError(f"nonlinearity must be \"tanh\", \"sigmoid\" or None (got {nonlinearity!r})")
+        if k is None and not 0.0 < float(ratio) <= 1.0:
+            raise ValueError(f"ratio must be in (0, 1] (got {ratio!r})")
+        if k is not None and int(k) < 1:
+            raise ValueError(f"k must be >= 1 (got {k!r})")
+        self.ratio, self.k = (None if k is not None else float(ratio)), (None if k is None else int(k))
+        self.multiplier, self.nonlinearity, self.fused = float(multiplier), nonlinearity, bool(fused)
+
+    def _pool(self, X, score, batch):
+        gate = score if self.nonlinearity is None else _GATES[self.nonlinearity](score)
+        scale = gate if self.multiplier == 1.0 else self.multiplier * gate
+        if self.fused:
+            small, sel = batch.coarsen(score, ratio=self.ratio, k=self.k)
+            perm = sel.perm.long()
+            return SelectRows.apply(X, scale, sel), small, sel, gate[perm]
+        small, sel = _composed_coarsen(batch, score, ratio=self.ratio, k=self.k)
+        perm = sel.perm.long()
+        return scale[perm].unsqueeze(1) * X[perm], small, sel, gate[perm]
+
+
+class TopKPooling(_ScorePooling):
+    """``TopKPooling(in_channels, ratio=0.5, k=None, multiplier=1.0, nonlinearity="tanh", fused=True)(X, batch) -> (X', new_batch,
+    selection, gate[perm])``: the top-k pooling of Graph U-Nets on a batching.GraphBatch.  score = (X @ w) / ||w|| with a learned
+    w [in_channels]; every graph keeps its min(n, ceil(ratio * n)) -- or min(n, k) -- best-scoring rows (the library's total order,
+    ties to the smaller row, rows kept in row order); gate = nonlinearity(score) ("tanh", "sigmoid" or None) and X' = multiplier *
+    gate[perm] * X[perm].  The rows are chosen by the score itself, which a monotone gate orders alike but for the ties its
+    saturation makes.  The score and the gate are node-sized torch arithmetic.  fused=True: ONE library call builds the coarsened
+    batch on the device (GraphBatch.coarsen) and SelectRows gathers and scales in one pass, with a one-pass backward.  fused=False
+    is the same function composed from torch ops (sorts, masks, index_add_, a partition built again), kept as the timing baseline
+    and as a second opinion; it selects the same rows.  float32 only."""
+
+    def __init__(self, in_channels, ratio=0.5, k=None, multiplier=1.0, nonlinearity="tanh", fused=True):
+        super().__init__(ratio, k, multiplier, nonlinearity, fused)
+        self.weight = Parameter(torch.empty(int(in_channels)))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        bound = 1.0 / math.sqrt(self.weight.numel())
+        with torch.no_grad():
+            self.weight.uniform_(-bound, bound)
+
+    def forward(self, X, batch):
+        _f32_only(X, "TopKPooling")
+        # (a one-row linear map, not torch.mv: rocBLAS's gemv takes 25 ms for the weight gradient of 2.6 M rows of 64 floats where
+        # the GEMM path takes 2.5 -- profiles/topk_pool/README.md)
+        score = torch.nn.functional.linear(X, self.weight.unsqueeze(0)).reshape(-1) / self.weight.norm(p=2)
+        return self._pool(X, score, batch)
+
+
+class SAGPooling(_ScorePooling):
+    """``SAGPooling(in_channels, ratio=0.5, k=None, GNN=GCNConv, nonlinearity="tanh", fused=True)(X, batch) -> (X', new_batch,
+    selection, gate[perm])``: self-attention graph pooling -- TopKPooling whose score comes from one conv layer of the library at
+    output width 1 on the batch, ``GNN(in_channels, 1)(X, batch)``; X' = gate[perm] * X[perm].  fused as in TopKPooling."""
+
+    def __init__(self, in_channels, ratio=0.5, k=None, GNN=GCNConv, nonlinearity="tanh", fused=True):
+        super().__init__(ratio, k, 1.0, nonlinearity, fused)
+        self.gnn = GNN(int(in_channels), 1)
+
+    def forward(self, X, batch):
+        _f32_only(X, "SAGPooling")
+        return self._pool(X, self.gnn(X, batch).reshape(-1), batch)
