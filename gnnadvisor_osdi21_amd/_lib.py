@@ -35,7 +35,9 @@ class Tuning(ctypes.Structure):
 
 _lib = None
 
-# ---- the C ABI as ctypes sees it: entry -> (restype, argtypes; None: never assigned).  load() applies it, EXPORTS is its keys ----
+# ---- the C ABI as ctypes sees it, one table per public header of include/, in the order the headers were added:
+# HEADERS[header] = {entry: (restype, argtypes; None: never assigned)}.  load() applies every table; a new header adds its key here,
+# its name to build.PUBLIC_HEADERS and its record to tests/test_binding_table_host.py ----
 p, i, i64, u, u64, f, s = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint, ctypes.c_uint64, ctypes.c_float, ctypes.c_char_p
 pd, pi, pi64 = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64)
 _REF_TAIL = [p, p, p, i64, i, i64, i, i, i, p]       # part_pointers, part2Node, out, num_nodes, dim, num_parts, partSize, dimWorker, warpPerBlock, stream
@@ -45,7 +47,8 @@ _GAT_FWD = [p, i64, p, p, p, p, p, p, f, p, i64, p]  # H, ld_h, el, er, the grap
 _GAT_BWD = [p, i64, p, p, p, p, i64, p, i64]         # H, ld_h, el, er, lse, Y, ld_y, dY, ld_dy
 _GAT_BOTH = ([p] * 4 + [i64]) * 2 + [f, p, i64, p, p]   # the graph and its transpose with their num_parts, slope, dH, ld_dh, d_el, d_er
 _TYPED = [p, i64, i64, p, p, p, p, i, i, p, p, p] + _SIZES
-SIGNATURES = {
+HEADERS = {}
+HEADERS["gnna.h"] = {                # the pinned 601 surface
     "gnna_version": (i, None), "gnna_build_id": (s, None), "gnna_last_error": (s, None), "gnna_device_cus": (i, None),
     "gnna_host_threads": (i, None), "gnna_last_num_phases": (i, None), "gnna_last_num_launches": (i, None),
     "gnna_count_parts": (i64, [i, p, i64]),
@@ -103,30 +106,30 @@ SIGNATURES = {
     "gnna_agg_typed_contract_ld_f32": (i, _TYPED),
     "gnna_typed_coef_grad_ld_f32": (i, [p, i64, i64, p, i64, i64, p, p, p, p, p, p, i, i, i, i64, i, u, p]),
 }
-# entries added after the pinned 601 surface (include/gnna_ext.h): a second table, applied by load() the same way
-EXT_SIGNATURES = {
+# entries added after the pinned 601 surface
+HEADERS["gnna_ext.h"] = {
     "gnna_gat_forward_drop_f32": (i, _GAT_FWD[:9] + [f, u64] + _GAT_FWD[9:] + [i64, i64, i, i, i64, i, u, p]),     # attn_drop, rng_seed after the slope
     "gnna_gat_backward_drop_f32": (i, _GAT_BWD + _GAT_BOTH[:11] + [f, u64] + _GAT_BOTH[11:] + [i64, i64, i, i, i, u, p]),
 }
-# fused GATv2 attention (include/gnna_gatv2.h): a third table
+# fused GATv2 attention
 _GRAPH_T = ([p] * 4 + [i64]) * 2                         # the graph and its transpose, each with its num_parts
-GATV2_SIGNATURES = {
+HEADERS["gnna_gatv2.h"] = {
     # Hs, ld_hs, Hd, ld_hd, att, the graph, slope, attn_drop, rng_seed, out, ld_out, lse, sizes
     "gnna_gatv2_forward_f32": (i, [p, i64, p, i64, p] + [p] * 4 + [f, f, u64, p, i64, p, i64, i64, i, i, i64, i, u, p]),
     # Hs, ld_hs, Hd, ld_hd, att, lse, Y, ld_y, dY, ld_dy, both structures, slope, attn_drop, rng_seed, dHs, ld_dhs, dHd, ld_dhd, d_att, sizes
     "gnna_gatv2_backward_f32": (i, [p, i64, p, i64, p, p, p, i64, p, i64] + _GRAPH_T + [f, f, u64, p, i64, p, i64, p,
                                                                                        i64, i64, i, i, i, u, p]),
 }
-# fused dot-product attention (include/gnna_dotattn.h): a fourth table
-DOTATTN_SIGNATURES = {
+# fused dot-product attention
+HEADERS["gnna_dotattn.h"] = {
     # Q, ld_q, K, ld_k, V, ld_v, the graph, scale, attn_drop, rng_seed, out, ld_out, lse, sizes
     "gnna_dot_attn_forward_f32": (i, [p, i64] * 3 + [p] * 4 + [f, f, u64, p, i64, p, i64, i64, i, i, i64, i, u, p]),
     # Q, ld_q, K, ld_k, V, ld_v, lse, Y, ld_y, dY, ld_dy, both structures, scale, attn_drop, rng_seed, dQ, ld_dq, dK, ld_dk, dV, ld_dv, sizes
     "gnna_dot_attn_backward_f32": (i, [p, i64] * 3 + [p, p, i64, p, i64] + _GRAPH_T + [f, f, u64] + [p, i64] * 3 +
                                    [i64, i64, i, i, i, u, p]),
 }
-# fused GAT attention with a per-edge score term (include/gnna_gat_edge.h): a fifth table
-GATEDGE_SIGNATURES = {
+# fused GAT attention with a per-edge score term
+HEADERS["gnna_gat_edge.h"] = {
     # gnna_gat_forward_drop_f32 with ee after er and num_edges after the row counts
     "gnna_gat_edge_forward_f32": (i, _GAT_FWD[:4] + [p] + _GAT_FWD[4:9] + [f, u64] + _GAT_FWD[9:] + [i64, i64, i64, i, i, i64, i, u, p]),
     # gnna_gat_backward_drop_f32 with ee after er, t_edge_pos after the transposed structure, d_ee after d_er, num_edges after the row counts
@@ -135,34 +138,34 @@ GATEDGE_SIGNATURES = {
     # el, er, ee, lse, row_pointers, column_index, slope, alpha, num_out_rows, num_in_rows, num_edges, heads, stream
     "gnna_gat_alpha_f32": (i, [p] * 6 + [f, p, i64, i64, i64, i, p]),
 }
-# neighbor statistics from one gather (include/gnna_stats.h): a sixth table
-STATS_SIGNATURES = {
+# neighbor statistics from one gather
+HEADERS["gnna_stats.h"] = {
     # input, ld_in, num_in_rows, the partition, (sum, ld) (sumsq, ld), (max, ld, argmax, ld) (min, ld, argmin, ld), num_out_rows, dim, num_parts, partSize, flags, stream
     "gnna_agg_stats_ld_f32": (i, [p, i64, i64, p, p, p] + [p, i64] * 6 + [i64, i, i64, i, u, p]),
 }
-# softmax neighbor aggregation (include/gnna_softagg.h): a seventh table
-SOFTAGG_SIGNATURES = {
+# softmax neighbor aggregation
+HEADERS["gnna_softagg.h"] = {
     # input, ld_in, num_in_rows, temp, temp_len, row_pointers, column_index, (out, ld) (lse, ld) (sq, ld), num_out_rows, dim, flags, stream
     "gnna_agg_softmax_ld_f32": (i, [p, i64, i64, p, i, p, p] + [p, i64] * 3 + [i64, i, u, p]),
     # input, ld_in, num_in_rows, temp, temp_len, (lse, ld) (Y, ld) (dY, ld), the transposed structure, d_input, ld_din, num_out_rows, dim, flags, stream
     "gnna_agg_softmax_backward_ld_f32": (i, [p, i64, i64, p, i] + [p, i64] * 3 + [p, p, p, i64, i64, i, u, p]),
 }
-# graph-level readout over the rows of every graph of a batch (include/gnna_pool.h): an eighth table
-POOL_SIGNATURES = {
+# graph-level readout over the rows of every graph of a batch
+HEADERS["gnna_pool.h"] = {
     # input, ld_in, num_rows, graph_pointers, num_segments, (sum, ld), (max, ld, argmax, ld) (min, ld, argmin, ld), dim, flags, stream
     "gnna_segment_pool_ld_f32": (i, [p, i64, i64, p, i64] + [p, i64] * 5 + [i, u, p]),
     # (d_sum, ld), (d_max, ld, argmax, ld) (d_min, ld, argmin, ld), graph_pointers, num_segments, d_input, ld_din, num_rows, dim, flags, stream
     "gnna_segment_pool_backward_ld_f32": (i, [p, i64] * 5 + [p, i64, p, i64, i64, i, u, p]),
 }
-# attention readout over the rows of every graph of a batch (include/gnna_attnpool.h): a ninth table
-ATTNPOOL_SIGNATURES = {
+# attention readout over the rows of every graph of a batch
+HEADERS["gnna_attnpool.h"] = {
     # input, ld_in, num_rows, gate, ld_gate, gate_dim, graph_pointers, num_segments, (out, ld) (lse, ld), dim, flags, stream
     "gnna_segment_attn_pool_ld_f32": (i, [p, i64, i64, p, i64, i, p, i64] + [p, i64] * 2 + [i, u, p]),
     # input, ld_in, gate, ld_gate, gate_dim, (lse, ld) (Y, ld) (dY, ld), graph_pointers, num_segments, (d_input, ld) (d_gate, ld), num_rows, dim, flags, stream
     "gnna_segment_attn_pool_backward_ld_f32": (i, [p, i64, p, i64, i] + [p, i64] * 3 + [p, i64] + [p, i64] * 2 + [i64, i, u, p]),
 }
-# hierarchical pooling on graph batches (include/gnna_topk.h): a tenth table
-TOPK_SIGNATURES = {
+# hierarchical pooling on graph batches
+HEADERS["gnna_topk.h"] = {
     # n, ratio, k_fixed
     "gnna_topk_keep_count": (i64, [i64, ctypes.c_double, i64]),
     # score, num_rows, graph_pointers, num_segments, ratio, k_fixed, row_pointers, column_index, nnz, partSize, new_id, perm, new_graph_pointers,
@@ -174,28 +177,7 @@ TOPK_SIGNATURES = {
     "gnna_gather_rows_scale_backward_ld_f32": (i, [p, i64, i64, p, p, i64, p, p, i64, p, i64, i, p]),
 }
 del p, i, i64, u, u64, f, s, pd, pi, pi64
-EXPORTS = tuple(SIGNATURES)
-EXT_EXPORTS = tuple(EXT_SIGNATURES)
-GATV2_EXPORTS = tuple(GATV2_SIGNATURES)
-DOTATTN_EXPORTS = tuple(DOTATTN_SIGNATURES)
-# every table load() applies (an extension of the surface adds its table here)
-SIGNATURE_TABLES = (SIGNATURES, EXT_SIGNATURES, GATV2_SIGNATURES, DOTATTN_SIGNATURES)
-# the tables of later headers, which load() applies after those (SIGNATURE_TABLES restates the four headers before them and stays)
-GATEDGE_EXPORTS = tuple(GATEDGE_SIGNATURES)
-STATS_EXPORTS = tuple(STATS_SIGNATURES)
-LATER_SIGNATURE_TABLES = (GATEDGE_SIGNATURES, STATS_SIGNATURES)
-# the tables of the headers after gnna_stats.h, which load() applies last (the two tuples above stay as their tests pin them)
-SOFTAGG_EXPORTS = tuple(SOFTAGG_SIGNATURES)
-NEWER_SIGNATURE_TABLES = (SOFTAGG_SIGNATURES,)
-# the tables of the headers after gnna_softagg.h, which load() applies last of all (the three tuples above stay as their tests pin them)
-POOL_EXPORTS = tuple(POOL_SIGNATURES)
-POOL_SIGNATURE_TABLES = (POOL_SIGNATURES,)
-# the table of the header after gnna_pool.h, which load() applies after all of those (the four tuples above stay as their tests pin them)
-ATTNPOOL_EXPORTS = tuple(ATTNPOOL_SIGNATURES)
-ATTNPOOL_SIGNATURE_TABLES = (ATTNPOOL_SIGNATURES,)
-# the table of the header after gnna_attnpool.h, which load() applies last (the five tuples above stay as their tests pin them)
-TOPK_EXPORTS = tuple(TOPK_SIGNATURES)
-TOPK_SIGNATURE_TABLES = (TOPK_SIGNATURES,)
+EXPORTS = tuple(HEADERS["gnna.h"])     # users: the build's check of the library, tests/test_host.py
 
 
 def load() -> ctypes.CDLL:
@@ -208,9 +190,11 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} is missing: the HIP extension has not been built "
             "(run `python -m gnnadvisor_osdi21_amd.build`). There is no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    for table in SIGNATURE_TABLES + LATER_SIGNATURE_TABLES + NEWER_SIGNATURE_TABLES + POOL_SIGNATURE_TABLES + ATTNPOOL_SIGNATURE_TABLES + \
-            TOPK_SIGNATURE_TABLES:
+    bound = {}
+    for header, table in HEADERS.items():
         for name, (restype, argtypes) in table.items():
+            if bound.setdefault(name, header) != header:
+                raise ImportError(f"{name} is bound under two headers of _lib.HEADERS: {bound[name]} and {header}")
             fn = getattr(L, name)
             fn.restype = restype
             if argtypes is not None:
@@ -816,6 +800,30 @@ def scatter_arg_ld(grad_out, arg, column_index, num_in_rows, out=None, accumulat
 STATS = ("sum", "sumsq", "max", "min")
 
 
+def _stat_outputs(names, want, out, rows, dim, device):
+    """(results, argument run) of the statistics `names` of agg_stats_ld / segment_pool: (value, ld) for each and (arg, ld_arg),
+    the int32 positions, after "max" and "min".  One not in `want` is handed over as (None, dim).  A tensor of the dict `out` is
+    used where it supplies one; the positions are not computed when `out` holds the value but not them."""
+    out = dict(out or {})
+    res, args = {}, []
+    for name in names:
+        vp, ld = None, dim
+        if name in want:
+            res[name], vp, ld = _out_rows(out.get(name), rows, dim, device)
+        args += [vp, ld]
+        if name in ("max", "min"):
+            ap, ld_arg = None, dim
+            if name in want and ("arg" + name in out or name not in out):
+                arg = out.get("arg" + name)
+                if arg is None:
+                    arg = _fresh_output((rows, dim), device, torch.int32)
+                assert arg.device == device
+                ap, ld_arg = _arg_view(arg, rows, dim, "arg" + name)
+                res["arg" + name] = arg
+            args += [ap, ld_arg]
+    return res, args
+
+
 def agg_stats_ld(X, column_index, part_pointers, part2Node, num_out_rows=None, partSize=32, want=STATS, out=None):
     """gnna_agg_stats_ld_f32 (include/gnna_stats.h): the statistics named in `want` over the edges e of every row i of
     x = X[column_index[e], f], from one walk over the ids and one load of every source row -- "sum", "sumsq" (sum of x * x), "max"
@@ -830,25 +838,7 @@ def agg_stats_ld(X, column_index, part_pointers, part2Node, num_out_rows=None, p
         raise ValueError(f"want must name some of {STATS} (got {want!r})")
     xp, n_in, dim, ld_in = _rows_view(X, "X")
     n_out = n_in if num_out_rows is None else int(num_out_rows)
-    out = dict(out or {})
-    res, args = {}, []
-    for name in STATS:
-        wanted = name in want
-        val = None
-        if wanted:
-            val, vp, ld = _out_rows(out.get(name), n_out, dim, X.device)
-            res[name] = val
-        args += [vp if wanted else None, ld if wanted else dim]
-        if name in ("max", "min"):
-            arg = None
-            if wanted and ("arg" + name in out or name not in out):
-                arg = out.get("arg" + name)
-                if arg is None:
-                    arg = _fresh_output((n_out, dim), X.device, torch.int32)
-                assert arg.device == X.device
-                ap, ld_arg = _arg_view(arg, n_out, dim, "arg" + name)
-                res["arg" + name] = arg
-            args += [ap if arg is not None else None, ld_arg if arg is not None else dim]
+    res, args = _stat_outputs(STATS, want, out, n_out, dim, X.device)
     _call(X.device, "gnna_agg_stats_ld_f32", xp, ld_in, n_in, column_index.data_ptr(), part_pointers.data_ptr(), part2Node.data_ptr(),
           *args, n_out, dim, part2Node.numel(), int(partSize), 0)
     return res
@@ -936,24 +926,7 @@ def segment_pool(X, graph_pointers, want=("sum",), mean=False, out=None):
     _need_device(X, "segment_pool")
     xp, n, dim, ld_in = _rows_view(X, "X")
     gp, G = _graph_pointers_arg(graph_pointers, X.device)
-    out = dict(out or {})
-    res, args = {}, []
-    for name in POOL_STATS:
-        wanted = name in want
-        if wanted:
-            val, vp, ld = _out_rows(out.get(name), G, dim, X.device)
-            res[name] = val
-        args += [vp if wanted else None, ld if wanted else dim]
-        if name != "sum":
-            arg = None
-            if wanted and ("arg" + name in out or name not in out):
-                arg = out.get("arg" + name)
-                if arg is None:
-                    arg = _fresh_output((G, dim), X.device, torch.int32)
-                assert arg.device == X.device
-                ap, ld_arg = _arg_view(arg, G, dim, "arg" + name)
-                res["arg" + name] = arg
-            args += [ap if arg is not None else None, ld_arg if arg is not None else dim]
+    res, args = _stat_outputs(POOL_STATS, want, out, G, dim, X.device)
     if G > 0:           # (the outputs of a batch without graphs are empty and have no address)
         _call(X.device, "gnna_segment_pool_ld_f32", xp if n > 0 else None, ld_in, n, gp, G, *args, dim, POOL_MEAN if mean else 0)
     return res

@@ -28,17 +28,14 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 LIB_SOURCES = [os.path.join(CSRC, f) for f in ("gnna_agg.hip", "gnna_stream.hip", "gnna_sweep.hip", "gnna_dense.hip", "gnna_x16.hip", "gnna_reduce.hip", "gnna_stats.hip", "gnna_softagg.hip", "gnna_pool.hip", "gnna_attnpool.hip", "gnna_topk.hip", "gnna_sddmm.hip", "gnna_edge.hip", "gnna_gat.hip", "gnna_gatv2.hip", "gnna_dotattn.hip", "gnna_typed.hip", "gnna_transpose.hip", "gnna_sample.hip",
                                                 "gnna_gemm.hip", "gnna_runtime.hip", "gnna_host.cpp", "gnna_reorder.cpp")]
-LIB_DEPS = LIB_SOURCES + [os.path.join(CSRC, "gnna_internal.h"), os.path.join(CSRC, "gnna_device.h"), os.path.join(CSRC, "gnna_launch.h"),
-                           os.path.join(CSRC, "gnna_gat_common.h"), os.path.join(CSRC, "gnna_keys.h"), os.path.join(CSRC, "gnna_segments.h"), os.path.join(INCLUDE, "gnna.h"), os.path.join(INCLUDE, "gnna_ext.h"),
-                           os.path.join(INCLUDE, "gnna_gatv2.h"), os.path.join(INCLUDE, "gnna_dotattn.h"),
-                           os.path.join(INCLUDE, "gnna_gat_edge.h"), os.path.join(INCLUDE, "gnna_stats.h"),
-                           os.path.join(INCLUDE, "gnna_softagg.h"), os.path.join(INCLUDE, "gnna_pool.h"),
-                           os.path.join(INCLUDE, "gnna_attnpool.h"), os.path.join(INCLUDE, "gnna_topk.h")]
+# the headers of include/, in the order they were added: each is a key of _lib.HEADERS (named here, not derived: no torch import)
+PUBLIC_HEADERS = ("gnna.h", "gnna_ext.h", "gnna_gatv2.h", "gnna_dotattn.h", "gnna_gat_edge.h", "gnna_stats.h", "gnna_softagg.h",
+                  "gnna_pool.h", "gnna_attnpool.h", "gnna_topk.h")
+INTERNAL_HEADERS = ("gnna_internal.h", "gnna_device.h", "gnna_launch.h", "gnna_gat_common.h", "gnna_keys.h", "gnna_segments.h")
+_PUBLIC = [os.path.join(INCLUDE, f) for f in PUBLIC_HEADERS]
+LIB_DEPS = LIB_SOURCES + [os.path.join(CSRC, f) for f in INTERNAL_HEADERS] + _PUBLIC
 EXT_SOURCES = [os.path.join(CSRC, "gnna_torch.cpp")]
-EXT_DEPS = EXT_SOURCES + [os.path.join(INCLUDE, "gnna.h"), os.path.join(INCLUDE, "gnna_ext.h"), os.path.join(INCLUDE, "gnna_gatv2.h"),
-                          os.path.join(INCLUDE, "gnna_dotattn.h"), os.path.join(INCLUDE, "gnna_gat_edge.h"),
-                          os.path.join(INCLUDE, "gnna_stats.h"), os.path.join(INCLUDE, "gnna_softagg.h"), os.path.join(INCLUDE, "gnna_pool.h"),
-                          os.path.join(INCLUDE, "gnna_attnpool.h"), os.path.join(INCLUDE, "gnna_topk.h")]
+EXT_DEPS = EXT_SOURCES + _PUBLIC
 
 
 def source_hash() -> str:

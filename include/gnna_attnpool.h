@@ -3,7 +3,7 @@
  * per element, from ONE read of the feature matrix, and the backward pass (gnna_attnpool.hip).
  *
  * Entries of libgnna.so added after gnna_pool.h; gnna.h, the headers before this one and GNNA_VERSION stay as they are.  Bound
- * through a ninth pair of tables (_lib.ATTNPOOL_EXPORTS / _lib.ATTNPOOL_SIGNATURES).  Conventions (status codes,
+ * through this header's table in _lib.HEADERS.  Conventions (status codes,
  * gnna_last_error, streams, scratch) are those of gnna.h; the segments are those of gnna_pool.h: graph_pointers, int32
  * [num_segments + 1] in DEVICE memory, the rows of graph g are [graph_pointers[g], graph_pointers[g + 1]).  The pointers must not
  * descend; that is not checked on the device.  A segment with p[g + 1] < p[g] is taken as empty, every pointer is clamped to

@@ -2,8 +2,8 @@
  * gnna_dotattn.h -- fused scaled dot-product graph attention of libgnna.so (gnna_dotattn.hip).
  *
  * gnna.h (the pinned 601 surface), gnna_ext.h and gnna_gatv2.h are compared entry for entry by the test suite and stay as they
- * are; these entries are declared here and bound through a fourth pair of tables (_lib.DOTATTN_EXPORTS /
- * _lib.DOTATTN_SIGNATURES), which the loader applies the same way.  Conventions (status codes, gnna_last_error, streams,
+ * are; these entries are declared here and bound through this header's table in _lib.HEADERS, which the loader applies the
+ * same way.  Conventions (status codes, gnna_last_error, streams,
  * scratch) are those of gnna.h; gnna_version() stays 601.
  *
  * The function is the attention of graph transformers (TransformerConv / UniMP, DotGatConv, the inner step of HGT and GPS

@@ -1,10 +1,9 @@
 /*
  * gnna_ext.h -- entries of libgnna.so added after the pinned 601 surface of gnna.h.
  *
- * gnna.h, GNNA_VERSION (601) and the binding tables that restate it are compared entry for entry by the test suite and stay as
- * they are; an entry added since is declared here and bound through a second pair of tables (_lib.EXT_EXPORTS /
- * _lib.EXT_SIGNATURES), which the loader applies the same way.  Conventions (status codes, gnna_last_error, streams, scratch) are
- * those of gnna.h.
+ * gnna.h, GNNA_VERSION (601) and the binding table that restates it are compared entry for entry by the test suite and stay as
+ * they are; an entry added since is declared here and bound through this header's table in _lib.HEADERS, which the loader
+ * applies the same way.  Conventions (status codes, gnna_last_error, streams, scratch) are those of gnna.h.
  */
 #ifndef GNNA_EXT_H_
 #define GNNA_EXT_H_

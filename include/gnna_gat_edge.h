@@ -2,7 +2,7 @@
  * gnna_gat_edge.h -- fused GAT attention with a per-edge score term (gnna_gat.hip), and the attention coefficients edge for edge.
  *
  * Entries of libgnna.so added after gnna_dotattn.h; gnna.h, gnna_ext.h, gnna_gatv2.h, gnna_dotattn.h and GNNA_VERSION stay as
- * they are.  Bound through a fifth pair of tables (_lib.GATEDGE_EXPORTS / _lib.GATEDGE_SIGNATURES).  Conventions (status codes,
+ * they are.  Bound through this header's table in _lib.HEADERS.  Conventions (status codes,
  * gnna_last_error, streams, scratch) are those of gnna.h.
  *
  * The function.  For the edge at position e of column_index, in destination row i (row_pointers[i] <= e < row_pointers[i + 1]),

@@ -2,8 +2,8 @@
  * gnna_gatv2.h -- fused GATv2 ("dynamic") attention of libgnna.so (gnna_gatv2.hip).
  *
  * gnna.h (the pinned 601 surface) and gnna_ext.h are compared entry for entry by the test suite and stay as they are; these
- * entries are declared here and bound through a third pair of tables (_lib.GATV2_EXPORTS / _lib.GATV2_SIGNATURES), which the
- * loader applies the same way.  Conventions (status codes, gnna_last_error, streams, scratch) are those of gnna.h;
+ * entries are declared here and bound through this header's table in _lib.HEADERS, which the loader applies the same way.
+ * Conventions (status codes, gnna_last_error, streams, scratch) are those of gnna.h;
  * gnna_version() stays 601.
  *
  * The function (Brody et al., "How Attentive are Graph Attention Networks?").  Hs [num_in_rows, heads * dim] is the source side

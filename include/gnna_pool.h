@@ -3,7 +3,7 @@
  * winning elements, from ONE read of the feature matrix, and the backward pass (gnna_pool.hip).
  *
  * Entries of libgnna.so added after gnna_softagg.h; gnna.h, the headers before this one and GNNA_VERSION stay as they are.
- * Bound through an eighth pair of tables (_lib.POOL_EXPORTS / _lib.POOL_SIGNATURES).  Conventions (status codes,
+ * Bound through this header's table in _lib.HEADERS.  Conventions (status codes,
  * gnna_last_error, streams, scratch) are those of gnna.h.
  *
  * A batch of graphs is a block-diagonal CSR plus graph_pointers, int32 [num_segments + 1] in DEVICE memory: the rows of graph g

@@ -3,7 +3,7 @@
  * backward pass (gnna_softagg.hip): the learnable aggregator of DeeperGCN's GENConv (PyG's aggr.SoftmaxAggregation).
  *
  * Entries of libgnna.so added after gnna_stats.h; gnna.h, the headers before this one and GNNA_VERSION stay as they are.
- * Bound through a seventh pair of tables (_lib.SOFTAGG_EXPORTS / _lib.SOFTAGG_SIGNATURES).  Conventions (status codes,
+ * Bound through this header's table in _lib.HEADERS.  Conventions (status codes,
  * gnna_last_error, streams, scratch) are those of gnna.h.
  *
  * The function.  Over the edges i <- j of destination row i (a duplicate edge counts twice), per channel f, with

@@ -3,7 +3,7 @@
  * source row (gnna_stats.hip): what a layer with several aggregators (PNA: mean, max, min, std) needs of the same X.
  *
  * An entry of libgnna.so added after gnna_gat_edge.h; gnna.h, the headers before this one and GNNA_VERSION stay as they are.
- * Bound through a sixth pair of tables (_lib.STATS_EXPORTS / _lib.STATS_SIGNATURES).  Conventions (status codes,
+ * Bound through this header's table in _lib.HEADERS.  Conventions (status codes,
  * gnna_last_error, streams, scratch, the neighbor-group partition) are those of gnna.h.
  *
  * The function.  Over the edges e of row i, with x = input[column_index[e], f]:

@@ -5,7 +5,7 @@
  * also the unpooling of a Graph U-Net (gnna_gather_rows_scale_ld_f32, gnna_gather_rows_scale_backward_ld_f32).  gnna_topk.hip.
  *
  * Entries of libgnna.so added after gnna_attnpool.h; gnna.h, the headers before this one and GNNA_VERSION stay as they are.
- * Bound through a tenth pair of tables (_lib.TOPK_EXPORTS / _lib.TOPK_SIGNATURES).  Conventions (status codes, gnna_last_error,
+ * Bound through this header's table in _lib.HEADERS.  Conventions (status codes, gnna_last_error,
  * streams, scratch) are those of gnna.h.
  *
  * ---- gnna_segment_topk_i32 -------------------------------------------------------------------------------------------------

@@ -1,67 +1,15 @@
-"""The attention readout, the parts that need no GPU: the ninth header and binding table (include/gnna_attnpool.h,
-_lib.ATTNPOOL_EXPORTS / ATTNPOOL_SIGNATURES in a tuple of its own; the older headers and tuples stay pinned by their own tests), the
-refusals both entries make before any device work, the build lists, the wrappers, the ops' refusals and the driver's new flag."""
+"""The attention readout, the parts that need no GPU (the binding surface of include/gnna_attnpool.h and the build lists are pinned
+by test_binding_table_host.py): the refusals both entries make before any device work, the wrappers, the ops' refusals and the
+driver's new flag."""
 import ctypes
 import inspect
-import os
 
 import pytest
 import torch
 
-from gnnadvisor_osdi21_amd import _lib, build
-from test_binding_table_host import _codes
-from util import declared_entries
+from gnnadvisor_osdi21_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-# name: (restype, argtypes), one letter per ctypes type as in test_binding_table_host.py -- written from the declarations in
-# gnna_attnpool.h
-RECORDED = {
-    "gnna_segment_attn_pool_ld_f32": ("i", "pll" "pli" "pl" "pl" "pl" "iup"),
-    "gnna_segment_attn_pool_backward_ld_f32": ("i", "pl" "pli" "pl" "pl" "pl" "pl" "pl" "pl" "liup"),
-}
-OLDER_HEADERS = ("gnna.h", "gnna_ext.h", "gnna_gatv2.h", "gnna_dotattn.h", "gnna_gat_edge.h", "gnna_stats.h", "gnna_softagg.h", "gnna_pool.h")
 FWD, BWD = "gnna_segment_attn_pool_ld_f32", "gnna_segment_attn_pool_backward_ld_f32"
-
-
-def test_the_header_declares_exactly_the_two_entries():
-    header = open(os.path.join(ROOT, "include", "gnna_attnpool.h")).read()
-    declared = declared_entries(header)
-    assert declared == set(RECORDED)
-    assert isinstance(_lib.ATTNPOOL_EXPORTS, tuple) and set(_lib.ATTNPOOL_EXPORTS) == set(_lib.ATTNPOOL_SIGNATURES) == declared
-    assert '#include "gnna.h"' in header and "#define GNNA_VERSION" not in header
-    assert _lib.load().gnna_version() == 601
-
-
-def test_the_table_is_disjoint_from_the_older_ones_and_is_applied_last():
-    older_exports = (_lib.EXPORTS, _lib.EXT_EXPORTS, _lib.GATV2_EXPORTS, _lib.DOTATTN_EXPORTS, _lib.GATEDGE_EXPORTS, _lib.STATS_EXPORTS,
-                     _lib.SOFTAGG_EXPORTS, _lib.POOL_EXPORTS)
-    assert len(older_exports) == len(OLDER_HEADERS) == 8
-    for older in older_exports:
-        assert not set(_lib.ATTNPOOL_EXPORTS) & set(older)
-    assert isinstance(_lib.ATTNPOOL_SIGNATURE_TABLES, tuple) and len(_lib.ATTNPOOL_SIGNATURE_TABLES) == 1
-    assert _lib.ATTNPOOL_SIGNATURE_TABLES[0] is _lib.ATTNPOOL_SIGNATURES
-    assert _lib.POOL_SIGNATURE_TABLES == (_lib.POOL_SIGNATURES,)
-    source = inspect.getsource(_lib.load)
-    assert source.index(" POOL_SIGNATURE_TABLES") < source.index("ATTNPOOL_SIGNATURE_TABLES")        # applied after the eighth
-    for older in OLDER_HEADERS:
-        assert not declared_entries(open(os.path.join(ROOT, "include", older)).read()) & set(RECORDED)
-
-
-def test_load_applies_the_table_with_the_recorded_signature():
-    lib = _lib.load()
-    assert {name: _codes(restype, argtypes) for name, (restype, argtypes) in _lib.ATTNPOOL_SIGNATURES.items()} == RECORDED
-    assert {name: _codes(getattr(lib, name).restype, getattr(lib, name).argtypes) for name in _lib.ATTNPOOL_EXPORTS} == RECORDED
-
-
-def test_the_sources_are_built_and_hashed():
-    assert any(p.endswith("gnna_attnpool.hip") for p in build.LIB_SOURCES)
-    for name in ("gnna_attnpool.h", "gnna_segments.h"):
-        assert any(p.endswith(name) for p in build.LIB_DEPS), name            # so source_hash covers it
-    assert any(p.endswith("gnna_attnpool.h") for p in build.EXT_DEPS)
-    makefile = open(os.path.join(ROOT, "gnnadvisor_osdi21_amd", "csrc", "Makefile")).read()
-    assert "gnna_attnpool.hip" in makefile and "gnna_attnpool.h" in makefile and "gnna_segments.h" in makefile
-    assert _lib.build_id() == "0.6.1+" + build.source_hash()
 
 
 _B = [(ctypes.c_float * 64)() for _ in range(12)]

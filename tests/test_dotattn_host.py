@@ -1,6 +1,6 @@
-"""Fused dot-product graph attention, the parts that need no GPU: the fourth header and binding table (include/gnna_dotattn.h,
-_lib.DOTATTN_EXPORTS / DOTATTN_SIGNATURES; gnna.h, gnna_ext.h and gnna_gatv2.h stay pinned by their own tests), the refusals the
-two entries make before any device work, the build lists, the driver's flags and the layer's arguments."""
+"""Fused dot-product graph attention, the parts that need no GPU (the binding surface of include/gnna_dotattn.h and the build lists
+are pinned by test_binding_table_host.py): what the header states, the refusals the two entries make before any device work, the
+driver's flags and the layer's arguments."""
 import ctypes
 import inspect
 import os
@@ -8,51 +8,13 @@ import re
 
 import pytest
 
-from gnnadvisor_osdi21_amd import _lib, build
-from test_binding_table_host import _codes
-from util import declared_entries
+from gnnadvisor_osdi21_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-# name: (restype, argtypes), one letter per ctypes type as in test_binding_table_host.py -- written from the declarations of
-# gnna_dotattn.h
-RECORDED = {
-    "gnna_dot_attn_forward_f32": ("i", "plplpl" "pppp" "ffQ" "plp" "lliiliup"),
-    "gnna_dot_attn_backward_f32": ("i", "plplpl" "p" "plpl" "ppppl" "ppppl" "ffQ" "plplpl" "lliiiup"),
-}
 
 
 def _header():
     return open(os.path.join(ROOT, "include", "gnna_dotattn.h")).read()
-
-
-def test_the_fourth_header_and_the_fourth_table_name_the_same_entries():
-    header = _header()
-    declared = declared_entries(header)
-    assert declared == set(RECORDED)
-    assert isinstance(_lib.DOTATTN_EXPORTS, tuple) and len(set(_lib.DOTATTN_EXPORTS)) == len(_lib.DOTATTN_EXPORTS)
-    assert set(_lib.DOTATTN_EXPORTS) == set(_lib.DOTATTN_SIGNATURES) == declared
-    assert '#include "gnna.h"' in header and "#define GNNA_VERSION" not in header
-    assert _lib.load().gnna_version() == 601
-
-
-def test_the_tables_are_disjoint_and_the_fourth_is_appended():
-    for older in (_lib.EXPORTS, _lib.EXT_EXPORTS, _lib.GATV2_EXPORTS):
-        assert not set(_lib.DOTATTN_EXPORTS) & set(older)
-    assert isinstance(_lib.SIGNATURE_TABLES, tuple) and len(_lib.SIGNATURE_TABLES) == 4
-    assert [t is u for t, u in zip(_lib.SIGNATURE_TABLES, (_lib.SIGNATURES, _lib.EXT_SIGNATURES, _lib.GATV2_SIGNATURES,
-                                                           _lib.DOTATTN_SIGNATURES))] == [True] * 4
-    # the three older headers declare none of the new entries
-    for older in ("gnna.h", "gnna_ext.h", "gnna_gatv2.h"):
-        assert not declared_entries(open(os.path.join(ROOT, "include", older)).read()) & set(RECORDED)
-
-
-def test_load_applies_the_fourth_table_with_the_recorded_signatures():
-    lib = _lib.load()
-    table = {name: _codes(restype, argtypes) for name, (restype, argtypes) in _lib.DOTATTN_SIGNATURES.items()}
-    assert table == RECORDED
-    got = {name: _codes(getattr(lib, name).restype, getattr(lib, name).argtypes) for name in _lib.DOTATTN_EXPORTS}
-    assert got == RECORDED
 
 
 def test_the_header_states_the_function():
@@ -63,16 +25,6 @@ def test_the_header_states_the_function():
                   "dK[j,h,:] = scale sum_i dz Q[i,h,:]", "dV[j,h,:] = sum_i alpha k dY[i,h,:]", "MAY overlap",
                   "heads <= 64, dim <= 256", "GNNA_ERR_INVALID_ARGUMENT before any device work", "a scale that is NaN or infinite"):
         assert piece in flat, piece
-
-
-def test_the_sources_are_built_and_hashed():
-    assert any(p.endswith("gnna_dotattn.hip") for p in build.LIB_SOURCES)
-    for name in ("gnna_dotattn.hip", "gnna_gat_common.h", "gnna_dotattn.h"):
-        assert any(p.endswith(name) for p in build.LIB_DEPS), name          # so source_hash covers it
-    assert any(p.endswith("gnna_dotattn.h") for p in build.EXT_DEPS)
-    makefile = open(os.path.join(ROOT, "gnnadvisor_osdi21_amd", "csrc", "Makefile")).read()
-    assert "gnna_dotattn.hip" in makefile and "gnna_dotattn.h" in makefile
-    assert _lib.build_id() == "0.6.1+" + build.source_hash()
 
 
 _B = [(ctypes.c_float * 64)() for _ in range(10)]

@@ -1,7 +1,7 @@
-"""Attention dropout of the fused GAT attention, the parts that need no GPU: the second header and binding table
-(include/gnna_ext.h, _lib.EXT_EXPORTS / EXT_SIGNATURES: the 601 surface of gnna.h stays pinned by test_binding_table_host.py), the
-text of the mask rule, the restated mask (tests/gat_drop_ref.py), the refusals the entries make before any device work, the
-driver's flag and the layer's argument."""
+"""Attention dropout of the fused GAT attention, the parts that need no GPU (the binding surface of include/gnna_ext.h is pinned
+by test_binding_table_host.py): the drop entries are the rect ones with two more arguments, the text of the mask rule, the
+restated mask (tests/gat_drop_ref.py), the refusals the entries make before any device work, the driver's flag and the layer's
+argument."""
 import ctypes
 import inspect
 import os
@@ -13,42 +13,17 @@ import pytest
 import gat_drop_ref as dref
 from gnnadvisor_osdi21_amd import _lib
 from test_binding_table_host import _codes
-from util import declared_entries
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-# name: (restype, argtypes), one letter per ctypes type as in test_binding_table_host.py -- written from the declarations of
-# gnna_ext.h: the rect entries' letters with "fQ" (attn_drop, rng_seed) after the slope's "f"
-RECORDED = {
-    "gnna_gat_forward_drop_f32": ("i", "plppppppffQplplliiliup"),
-    "gnna_gat_backward_drop_f32": ("i", "plpppplplpppplpppplffQplpplliiiup"),
-}
 
 
 def _header():
     return open(os.path.join(ROOT, "include", "gnna_ext.h")).read()
 
 
-def test_the_second_header_and_the_second_table_name_the_same_entries():
-    header = _header()
-    declared = declared_entries(header)
-    assert declared == set(RECORDED)
-    assert isinstance(_lib.EXT_EXPORTS, tuple) and len(set(_lib.EXT_EXPORTS)) == len(_lib.EXT_EXPORTS)
-    assert set(_lib.EXT_EXPORTS) == set(_lib.EXT_SIGNATURES) == declared
-    assert not set(_lib.EXT_EXPORTS) & set(_lib.EXPORTS)
-    assert '#include "gnna.h"' in header and "#define GNNA_VERSION" not in header
-    assert _lib.load().gnna_version() == 601
-
-
-def test_load_applies_the_second_table_with_the_recorded_signatures():
-    lib = _lib.load()
-    table = {name: _codes(restype, argtypes) for name, (restype, argtypes) in _lib.EXT_SIGNATURES.items()}
-    assert table == RECORDED
-    got = {name: _codes(getattr(lib, name).restype, getattr(lib, name).argtypes) for name in _lib.EXT_EXPORTS}
-    assert got == RECORDED
-    # they are the rect entries with two more arguments
+def test_the_drop_entries_are_the_rect_entries_with_two_more_arguments():
     for drop, rect in (("gnna_gat_forward_drop_f32", "gnna_gat_forward_rect_f32"), ("gnna_gat_backward_drop_f32", "gnna_gat_backward_rect_f32")):
-        assert RECORDED[drop][1].replace("ffQ", "f", 1) == _codes(*_lib.SIGNATURES[rect])[1]
+        assert _codes(*_lib.HEADERS["gnna_ext.h"][drop])[1].replace("ffQ", "f", 1) == _codes(*_lib.HEADERS["gnna.h"][rect])[1]
 
 
 def test_the_header_states_the_rule():

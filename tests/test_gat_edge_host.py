@@ -1,7 +1,6 @@
-"""Fused GAT attention with a per-edge score term, the parts that need no GPU: the fifth header and binding table
-(include/gnna_gat_edge.h, _lib.GATEDGE_EXPORTS / GATEDGE_SIGNATURES, applied through _lib.LATER_SIGNATURE_TABLES; the four older
-headers and tables stay pinned by their own tests), the refusals the three entries make before any device work, the build lists,
-the wrappers, the layer's arguments and errors and the driver's flag."""
+"""Fused GAT attention with a per-edge score term, the parts that need no GPU (the binding surface of include/gnna_gat_edge.h and
+the build lists are pinned by test_binding_table_host.py): what the header states, the refusals the three entries make before any
+device work, the wrappers, the layer's arguments and errors and the driver's flag."""
 import ctypes
 import inspect
 import os
@@ -9,51 +8,13 @@ import re
 
 import pytest
 
-from gnnadvisor_osdi21_amd import _lib, build
-from test_binding_table_host import _codes
-from util import declared_entries
+from gnnadvisor_osdi21_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-# name: (restype, argtypes), one letter per ctypes type as in test_binding_table_host.py -- written from the declarations of
-# gnna_gat_edge.h
-RECORDED = {
-    "gnna_gat_edge_forward_f32": ("i", "plppp" "pppp" "ffQ" "plp" "llliiliup"),
-    "gnna_gat_edge_backward_f32": ("i", "plppp" "p" "plpl" "ppppl" "ppppl" "p" "ffQ" "plppp" "llliiiup"),
-    "gnna_gat_alpha_f32": ("i", "pppp" "pp" "f" "p" "llli" "p"),
-}
 
 
 def _header():
     return open(os.path.join(ROOT, "include", "gnna_gat_edge.h")).read()
-
-
-def test_the_fifth_header_and_the_fifth_table_name_the_same_entries():
-    header = _header()
-    declared = declared_entries(header)
-    assert declared == set(RECORDED)
-    assert isinstance(_lib.GATEDGE_EXPORTS, tuple) and len(set(_lib.GATEDGE_EXPORTS)) == len(_lib.GATEDGE_EXPORTS)
-    assert set(_lib.GATEDGE_EXPORTS) == set(_lib.GATEDGE_SIGNATURES) == declared
-    assert '#include "gnna.h"' in header and "#define GNNA_VERSION" not in header
-    assert _lib.load().gnna_version() == 601
-
-
-def test_the_table_is_disjoint_from_the_older_ones_and_applied_after_them():
-    for older in (_lib.EXPORTS, _lib.EXT_EXPORTS, _lib.GATV2_EXPORTS, _lib.DOTATTN_EXPORTS):
-        assert not set(_lib.GATEDGE_EXPORTS) & set(older)
-    # the four pinned tables stay four; the new one is in the second tuple load() walks
-    assert len(_lib.SIGNATURE_TABLES) == 4 and all(t is not _lib.GATEDGE_SIGNATURES for t in _lib.SIGNATURE_TABLES)
-    assert isinstance(_lib.LATER_SIGNATURE_TABLES, tuple) and _lib.LATER_SIGNATURE_TABLES[0] is _lib.GATEDGE_SIGNATURES
-    for older in ("gnna.h", "gnna_ext.h", "gnna_gatv2.h", "gnna_dotattn.h"):
-        assert not declared_entries(open(os.path.join(ROOT, "include", older)).read()) & set(RECORDED)
-
-
-def test_load_applies_the_fifth_table_with_the_recorded_signatures():
-    lib = _lib.load()
-    table = {name: _codes(restype, argtypes) for name, (restype, argtypes) in _lib.GATEDGE_SIGNATURES.items()}
-    assert table == RECORDED
-    got = {name: _codes(getattr(lib, name).restype, getattr(lib, name).argtypes) for name in _lib.GATEDGE_EXPORTS}
-    assert got == RECORDED
 
 
 def test_the_header_states_the_function_and_the_rules():
@@ -68,15 +29,6 @@ def test_the_header_states_the_function_and_the_rules():
                   "Every element of every output is written", "one writer per element", "num_edges >= 0", "ee may be NULL",
                   "GNNA_ACCUMULATE refused for every gradient, d_ee included"):
         assert piece in flat, piece
-
-
-def test_the_sources_are_built_and_hashed():
-    assert any(p.endswith("gnna_gat.hip") for p in build.LIB_SOURCES)
-    assert any(p.endswith("gnna_gat_edge.h") for p in build.LIB_DEPS)          # so source_hash covers it
-    assert any(p.endswith("gnna_gat_edge.h") for p in build.EXT_DEPS)
-    makefile = open(os.path.join(ROOT, "gnnadvisor_osdi21_amd", "csrc", "Makefile")).read()
-    assert "gnna_gat_edge.h" in makefile
-    assert _lib.build_id() == "0.6.1+" + build.source_hash()
 
 
 _B = [(ctypes.c_float * 64)() for _ in range(12)]

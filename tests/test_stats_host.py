@@ -1,59 +1,12 @@
-"""Neighbor statistics from one gather and PNAConv, the parts that need no GPU: the sixth header and binding table
-(include/gnna_stats.h, _lib.STATS_EXPORTS / STATS_SIGNATURES, the second of _lib.LATER_SIGNATURE_TABLES; the older headers and
-tables stay pinned by their own tests), the refusals the entry makes before any device work, the build lists, the wrappers, the
-layer's constructor errors and the driver's refusals."""
+"""Neighbor statistics from one gather and PNAConv, the parts that need no GPU (the binding surface of include/gnna_stats.h
+and the build lists are pinned by test_binding_table_host.py): the refusals the entry makes before any device work, the wrappers,
+the layer's constructor errors and the driver's refusals."""
 import ctypes
 import inspect
-import os
 
 import pytest
 
-from gnnadvisor_osdi21_amd import _lib, build
-from test_binding_table_host import _codes
-from util import declared_entries
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-# name: (restype, argtypes), one letter per ctypes type as in test_binding_table_host.py -- written from the declaration in
-# gnna_stats.h
-RECORDED = {
-    "gnna_agg_stats_ld_f32": ("i", "pll" "ppp" "pl" "pl" "plpl" "plpl" "liliup"),
-}
-OLDER_HEADERS = ("gnna.h", "gnna_ext.h", "gnna_gatv2.h", "gnna_dotattn.h", "gnna_gat_edge.h")
-
-
-def test_the_header_and_the_table_name_the_same_entry():
-    header = open(os.path.join(ROOT, "include", "gnna_stats.h")).read()
-    declared = declared_entries(header)
-    assert declared == set(RECORDED)
-    assert isinstance(_lib.STATS_EXPORTS, tuple) and set(_lib.STATS_EXPORTS) == set(_lib.STATS_SIGNATURES) == declared
-    assert '#include "gnna.h"' in header and "#define GNNA_VERSION" not in header
-    assert _lib.load().gnna_version() == 601
-
-
-def test_the_table_is_disjoint_from_the_older_ones_and_applied_after_them():
-    for older in (_lib.EXPORTS, _lib.EXT_EXPORTS, _lib.GATV2_EXPORTS, _lib.DOTATTN_EXPORTS, _lib.GATEDGE_EXPORTS):
-        assert not set(_lib.STATS_EXPORTS) & set(older)
-    assert len(_lib.SIGNATURE_TABLES) == 4 and _lib.LATER_SIGNATURE_TABLES[0] is _lib.GATEDGE_SIGNATURES
-    assert _lib.LATER_SIGNATURE_TABLES[1] is _lib.STATS_SIGNATURES and len(_lib.LATER_SIGNATURE_TABLES) == 2
-    for older in OLDER_HEADERS:
-        assert not declared_entries(open(os.path.join(ROOT, "include", older)).read()) & set(RECORDED)
-
-
-def test_load_applies_the_table_with_the_recorded_signature():
-    lib = _lib.load()
-    assert {name: _codes(restype, argtypes) for name, (restype, argtypes) in _lib.STATS_SIGNATURES.items()} == RECORDED
-    assert {name: _codes(getattr(lib, name).restype, getattr(lib, name).argtypes) for name in _lib.STATS_EXPORTS} == RECORDED
-
-
-def test_the_sources_are_built_and_hashed():
-    assert any(p.endswith("gnna_stats.hip") for p in build.LIB_SOURCES)
-    for name in ("gnna_stats.h", "gnna_keys.h"):
-        assert any(p.endswith(name) for p in build.LIB_DEPS), name          # so source_hash covers it
-    assert any(p.endswith("gnna_stats.h") for p in build.EXT_DEPS)
-    makefile = open(os.path.join(ROOT, "gnnadvisor_osdi21_amd", "csrc", "Makefile")).read()
-    assert "gnna_stats.hip" in makefile and "gnna_stats.h" in makefile and "gnna_keys.h" in makefile
-    assert _lib.build_id() == "0.6.1+" + build.source_hash()
+from gnnadvisor_osdi21_amd import _lib
 
 
 _B = [(ctypes.c_float * 64)() for _ in range(8)]

@@ -1,7 +1,7 @@
-"""Hierarchical pooling, the parts that need no GPU: the tenth header and binding table (include/gnna_topk.h, _lib.TOPK_EXPORTS /
-TOPK_SIGNATURES in a tuple of its own; the older headers and tuples stay pinned by their own tests), the refusals the three
-entries make before any device work, the rule for the rows a segment keeps, the numpy reference against a brute-force statement
-of the selection, the build lists, the wrappers, and GraphBatch without the new keywords."""
+"""Hierarchical pooling, the parts that need no GPU (the binding surface of include/gnna_topk.h and the build lists are pinned by
+test_binding_table_host.py): the header's constant, the refusals the three entries make before any device work, the rule for the
+rows a segment keeps, the numpy reference against a brute-force statement of the selection, the wrappers, and GraphBatch without
+the new keywords."""
 import ctypes
 import inspect
 import os
@@ -11,72 +11,16 @@ import pytest
 import torch
 
 import topk_ref
-from gnnadvisor_osdi21_amd import _lib, build
-from test_binding_table_host import CODE
-from util import declared_entries
+from gnnadvisor_osdi21_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CODES = dict(CODE)
-CODES[ctypes.c_double] = "d"
 
-# name: (restype, argtypes), one letter per ctypes type as in test_binding_table_host.py ("d": a double by value) -- written from
-# the declarations in gnna_topk.h
-RECORDED = {
-    "gnna_topk_keep_count": ("l", "ldl"),
-    "gnna_segment_topk_i32": ("i", "plpl" "dl" "ppli" "ppp" "ppp" "pp" "lll" "Lp"),
-    "gnna_gather_rows_scale_ld_f32": ("i", "pll" "pp" "pll" "ip"),
-    "gnna_gather_rows_scale_backward_ld_f32": ("i", "pll" "p" "plp" "plp" "lip"),
-}
-OLDER_HEADERS = ("gnna.h", "gnna_ext.h", "gnna_gatv2.h", "gnna_dotattn.h", "gnna_gat_edge.h", "gnna_stats.h", "gnna_softagg.h", "gnna_pool.h",
-                 "gnna_attnpool.h")
 TOPK, FWD, BWD = "gnna_segment_topk_i32", "gnna_gather_rows_scale_ld_f32", "gnna_gather_rows_scale_backward_ld_f32"
 
 
-def _codes(restype, argtypes):
-    return CODES[restype], "".join(CODES[t] for t in argtypes)
-
-
-def test_the_header_declares_exactly_the_new_table():
+def test_the_header_defines_the_constant_the_binding_restates():
     header = open(os.path.join(ROOT, "include", "gnna_topk.h")).read()
-    declared = declared_entries(header)
-    assert declared == set(RECORDED)
-    assert isinstance(_lib.TOPK_EXPORTS, tuple) and set(_lib.TOPK_EXPORTS) == set(_lib.TOPK_SIGNATURES) == declared
-    assert '#include "gnna.h"' in header and "#define GNNA_VERSION" not in header
     assert "#define GNNA_TOPK_WAVE_ROWS %d\n" % _lib.TOPK_WAVE_ROWS in header
-    assert _lib.load().gnna_version() == 601
-
-
-def test_the_table_is_disjoint_from_the_older_ones_and_is_applied_last():
-    older_exports = (_lib.EXPORTS, _lib.EXT_EXPORTS, _lib.GATV2_EXPORTS, _lib.DOTATTN_EXPORTS, _lib.GATEDGE_EXPORTS, _lib.STATS_EXPORTS,
-                     _lib.SOFTAGG_EXPORTS, _lib.POOL_EXPORTS, _lib.ATTNPOOL_EXPORTS)
-    assert len(older_exports) == len(OLDER_HEADERS) == 9
-    for older in older_exports:
-        assert not set(_lib.TOPK_EXPORTS) & set(older)
-    assert isinstance(_lib.TOPK_SIGNATURE_TABLES, tuple) and len(_lib.TOPK_SIGNATURE_TABLES) == 1
-    assert _lib.TOPK_SIGNATURE_TABLES[0] is _lib.TOPK_SIGNATURES
-    # the older tuples are what their own tests pin
-    assert _lib.SIGNATURE_TABLES == (_lib.SIGNATURES, _lib.EXT_SIGNATURES, _lib.GATV2_SIGNATURES, _lib.DOTATTN_SIGNATURES)
-    assert _lib.LATER_SIGNATURE_TABLES == (_lib.GATEDGE_SIGNATURES, _lib.STATS_SIGNATURES)
-    assert _lib.NEWER_SIGNATURE_TABLES == (_lib.SOFTAGG_SIGNATURES,)
-    assert _lib.POOL_SIGNATURE_TABLES == (_lib.POOL_SIGNATURES,) and _lib.ATTNPOOL_SIGNATURE_TABLES == (_lib.ATTNPOOL_SIGNATURES,)
-    source = inspect.getsource(_lib.load)
-    assert source.index("ATTNPOOL_SIGNATURE_TABLES") < source.index("TOPK_SIGNATURE_TABLES")            # applied after the ninth
-    for older in OLDER_HEADERS:
-        assert not declared_entries(open(os.path.join(ROOT, "include", older)).read()) & set(RECORDED)
-
-
-def test_load_applies_the_table_with_the_recorded_signature():
-    lib = _lib.load()
-    assert {name: _codes(restype, argtypes) for name, (restype, argtypes) in _lib.TOPK_SIGNATURES.items()} == RECORDED
-    assert {name: _codes(getattr(lib, name).restype, getattr(lib, name).argtypes) for name in _lib.TOPK_EXPORTS} == RECORDED
-
-
-def test_the_sources_are_built_and_hashed():
-    assert any(p.endswith("gnna_topk.hip") for p in build.LIB_SOURCES)
-    assert any(p.endswith("gnna_topk.h") for p in build.LIB_DEPS) and any(p.endswith("gnna_topk.h") for p in build.EXT_DEPS)
-    makefile = open(os.path.join(ROOT, "gnnadvisor_osdi21_amd", "csrc", "Makefile")).read()
-    assert "gnna_topk.hip" in makefile and "gnna_topk.h" in makefile
-    assert _lib.build_id() == "0.6.1+" + build.source_hash()
 
 
 _B = [(ctypes.c_float * 64)() for _ in range(8)]
