@@ -176,6 +176,18 @@ HEADERS["gnna_topk.h"] = {
     # d_out, ld_dout, num_out_rows, new_id, input, ld_in, scale, d_input, ld_din, d_scale, num_in_rows, dim, stream
     "gnna_gather_rows_scale_backward_ld_f32": (i, [p, i64, i64, p, p, i64, p, p, i64, p, i64, i, p]),
 }
+# ---- staged headers: written as public headers but kept in csrc/ (named in build.INTERNAL_HEADERS) until the record of the public
+# surface in tests/test_binding_table_host.py is next extended; load() applies these tables after HEADERS, under the same rule ----
+STAGED = {}
+# per-graph normalisation (GraphNorm) over the rows of every graph of a batch
+STAGED["gnna_segnorm.h"] = {
+    # input, ld_in, num_rows, graph_pointers, num_segments, (mean, ld) (m2, ld), dim, flags, stream
+    "gnna_segment_moments_ld_f32": (i, [p, i64, i64, p, i64] + [p, i64] * 2 + [i, u, p]),
+    # input, ld_in, num_rows, graph_pointers, num_segments, weight, bias, alpha, eps, (out, ld) (mean, ld) (rstd, ld), dim, flags, stream
+    "gnna_segment_norm_ld_f32": (i, [p, i64, i64, p, i64, p, p, p, f] + [p, i64] * 3 + [i, u, p]),
+    # (d_out, ld) (input, ld) (mean, ld) (rstd, ld), weight, alpha, graph_pointers, num_segments, (d_input, ld) (seg_a, ld) (seg_b, ld), num_rows, dim, flags, stream
+    "gnna_segment_norm_backward_ld_f32": (i, [p, i64] * 4 + [p, p, p, i64] + [p, i64] * 3 + [i64, i, u, p]),
+}
 del p, i, i64, u, u64, f, s, pd, pi, pi64
 EXPORTS = tuple(HEADERS["gnna.h"])     # users: the build's check of the library, tests/test_host.py
 
@@ -191,7 +203,7 @@ def load() -> ctypes.CDLL:
             "(run `python -m gnnadvisor_osdi21_amd.build`). There is no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
     bound = {}
-    for header, table in HEADERS.items():
+    for header, table in list(HEADERS.items()) + list(STAGED.items()):
         for name, (restype, argtypes) in table.items():
             if bound.setdefault(name, header) != header:
                 raise ImportError(f"{name} is bound under two headers of _lib.HEADERS: {bound[name]} and {header}")
@@ -964,6 +976,84 @@ def segment_pool_backward(graph_pointers, num_rows, d_sum=None, d_max=None, argm
     _call(device, "gnna_segment_pool_backward_ld_f32", *args, gp, G, op_ if int(num_rows) > 0 else None, ld_din, int(num_rows), dim,
           POOL_MEAN if mean else 0)
     return out
+
+
+def _param_arg(t, dim, device, what):
+    """The address of a per-column parameter, a contiguous float32 tensor [dim] on `device`; None stands for the default."""
+    if t is None:
+        return None
+    assert t.dtype == torch.float32 and t.device == device and t.is_contiguous() and tuple(t.shape) == (dim,), \
+        f"{what} must be a contiguous float32 tensor [{dim}] on {device}"
+    return t.data_ptr()
+
+
+def segment_moments(X, graph_pointers, out=None):
+    """gnna_segment_moments_ld_f32 (csrc/gnna_segnorm.h): mean[g, f] and m2[g, f] = sum (x - mean)^2 over the rows
+    [graph_pointers[g], graph_pointers[g + 1]) of X for every graph g, from one read of X; both 0 for a graph without rows.  The
+    moments are centred as they are gathered (pairwise merges of (count, mean, m2)), never made from sums of x and x^2.
+    -> dict(mean=, m2=), each [num_graphs, dim].  `X` may be a row-strided view (stride(1) == 1), and so may the tensors of `out`,
+    a dict that supplies some of the results.  graph_pointers as in segment_pool.  The same bits on every run; accepted under
+    set_tuning(deterministic=1)."""
+    _need_device(X, "segment_moments")
+    xp, n, dim, ld_in = _rows_view(X, "X")
+    gp, G = _graph_pointers_arg(graph_pointers, X.device)
+    given = dict(out or {})
+    mean, mp, ld_mean = _out_rows(given.get("mean"), G, dim, X.device)
+    m2, qp, ld_m2 = _out_rows(given.get("m2"), G, dim, X.device)
+    if G > 0:           # (the outputs of a batch without graphs are empty and have no address)
+        _call(X.device, "gnna_segment_moments_ld_f32", xp if n > 0 else None, ld_in, n, gp, G, mp, ld_mean, qp, ld_m2, dim, 0)
+    return {"mean": mean, "m2": m2}
+
+
+def segment_norm(X, graph_pointers, weight=None, bias=None, alpha=None, eps=1e-5, out=None):
+    """gnna_segment_norm_ld_f32: per-graph normalisation.  With mean and m2 as in segment_moments and n the rows of graph g:
+    var = m2 / n + (1 - alpha)^2 mean^2, rstd = 1 / sqrt(var + eps), out[r, f] = weight * (x - alpha * mean) * rstd + bias for the
+    rows r of graph g; a row of no graph gets 0, a graph without rows mean = rstd = 0.  weight / bias / alpha: float32 [dim] or
+    None for 1 / 0 / 1.  -> dict(out= like X, mean=, rstd= [num_graphs, dim]): two reads of X, one write of `out`.  `X` and the
+    tensors of `out`, a dict that supplies some of the results, may be row-strided views; "out" must not be X.  The same bits on
+    every run; accepted under set_tuning(deterministic=1)."""
+    _need_device(X, "segment_norm")
+    xp, n, dim, ld_in = _rows_view(X, "X")
+    gp, G = _graph_pointers_arg(graph_pointers, X.device)
+    given = dict(out or {})
+    y, yp, ld_out = _out_rows(given.get("out"), n, dim, X.device)
+    mean, mp, ld_mean = _out_rows(given.get("mean"), G, dim, X.device)
+    rstd, rp, ld_rstd = _out_rows(given.get("rstd"), G, dim, X.device)
+    if n > 0 or G > 0:
+        _call(X.device, "gnna_segment_norm_ld_f32", xp if n > 0 else None, ld_in, n, gp, G, _param_arg(weight, dim, X.device, "weight"),
+              _param_arg(bias, dim, X.device, "bias"), _param_arg(alpha, dim, X.device, "alpha"), ctypes.c_float(eps),
+              yp if n > 0 else None, ld_out, mp if G > 0 else None, ld_mean, rp if G > 0 else None, ld_rstd, dim, 0)
+    return {"out": y, "mean": mean, "rstd": rstd}
+
+
+def segment_norm_backward(dY, X, mean, rstd, graph_pointers, weight=None, alpha=None, need_input=True, out=None):
+    """gnna_segment_norm_backward_ld_f32: from segment_norm's `mean` and `rstd` and the gradient dY of its `out`, with
+    xhat = (x - alpha * mean) * rstd: seg_a[g, f] = sum dY and seg_b[g, f] = sum dY * xhat over the rows of graph g (one pass over dY
+    and X), then d_input[r, f] = weight * rstd * (dY - xhat * B / n - alpha * (A / n - (1 - alpha) * mean * rstd * B / n)) in one
+    pass that writes every element once; a row of no graph gets 0.  -> (d_input like X | None with need_input=False, seg_a, seg_b).
+    The parameter gradients are [num_graphs, dim] arithmetic: d_bias = sum_g A, d_weight = sum_g B, d_alpha = -sum_g mean * weight *
+    rstd * (A - (1 - alpha) * mean * rstd * B).  `out` may supply "d_input", "seg_a", "seg_b".  Strided views as in segment_norm."""
+    _need_device(X, "segment_norm_backward")
+    xp, n, dim, ld_in = _rows_view(X, "X")
+    dp, nd, wd, ld_do = _rows_view(dY, "dY")
+    gp, G = _graph_pointers_arg(graph_pointers, X.device)
+    mp, gm, wm, ld_mean = _rows_view(mean, "mean")
+    rp, gr, wr, ld_rstd = _rows_view(rstd, "rstd")
+    assert (nd, wd) == (n, dim) and (gm, gr) == (G, G) and (wm, wr) == (dim, dim) and dY.device == mean.device == rstd.device == X.device, \
+        f"dY must be [{n}, {dim}], mean and rstd [{G}, {dim}] on {X.device}"
+    given = dict(out or {})
+    d_input, dip, ld_din = None, None, dim
+    if need_input:
+        d_input, dip, ld_din = _out_rows(given.get("d_input"), n, dim, X.device)
+    seg_a, ap, ld_a = _out_rows(given.get("seg_a"), G, dim, X.device)
+    seg_b, bp, ld_b = _out_rows(given.get("seg_b"), G, dim, X.device)
+    if G > 0 or (n > 0 and need_input):
+        if G == 0:      # (the tensors of a batch without graphs are empty and have no address; none is read)
+            mp = rp = ap = bp = None
+        _call(X.device, "gnna_segment_norm_backward_ld_f32", dp if n > 0 else None, ld_do, xp if n > 0 else None, ld_in, mp, ld_mean,
+              rp, ld_rstd, _param_arg(weight, dim, X.device, "weight"), _param_arg(alpha, dim, X.device, "alpha"), gp, G,
+              dip if n > 0 else None, ld_din, ap, ld_a, bp, ld_b, n, dim, 0)
+    return d_input, seg_a, seg_b
 
 
 def _gate_view(gate, n, dim, device):

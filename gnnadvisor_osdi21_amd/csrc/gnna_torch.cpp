@@ -41,6 +41,7 @@
 #include "gnna_pool.h"
 #include "gnna_attnpool.h"
 #include "gnna_topk.h"
+#include "gnna_segnorm.h"        // staged beside the sources (its first paragraph)
 
 #define CHECK_CUDA(x) TORCH_CHECK(x.is_cuda(), #x " must be a CUDA tensor")
 #define CHECK_CONTIGUOUS(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -662,6 +663,93 @@ segment_attn_pool_backward(const torch::Tensor &input, const torch::Tensor &gate
                                                     d_gate.has_value() ? d_gate->data_ptr<float>() : nullptr, gd, n, (int)dim, 0u,
                                                     current_stream()));
     return std::make_tuple(d_input, d_gate);
+}
+
+// Per-graph normalisation (gnna_segnorm.h).  What the three functions check alike: input [num_rows, dim] float32 with contiguous
+// rows, graph_pointers int32 [num_graphs + 1] on its device.
+static void segnorm_check(const torch::Tensor &input, const torch::Tensor &graph_pointers)
+{
+    CHECK_CUDA(input);
+    TORCH_CHECK(input.dim() == 2, "input must be 2-D [num_nodes, dim]");
+    CHECK_F32(input);
+    check_ids(graph_pointers, "graph_pointers");
+    TORCH_CHECK(graph_pointers.dim() == 1 && graph_pointers.size(0) >= 1, "graph_pointers must be [num_graphs + 1]");
+    TORCH_CHECK(graph_pointers.device() == input.device(), "input and graph_pointers must be on one device");
+    TORCH_CHECK(input.size(1) >= 1, "input must have at least one column");
+    check_rows(input, "input");
+}
+// the address of a per-column parameter [dim] on input's device; null for None (the default)
+static const float *segnorm_param(const c10::optional<torch::Tensor> &t, const torch::Tensor &input, const char *name)
+{
+    if (!t.has_value()) return nullptr;
+    check_floats(*t, name);
+    TORCH_CHECK(t->dim() == 1 && t->size(0) == input.size(1) && t->device() == input.device(), name, " must be [dim = ", input.size(1),
+                "] on input's device");
+    return t->data_ptr<float>();
+}
+
+// Centred moments of the rows of every graph (gnna_segment_moments_ld_f32) -> (mean, m2), each [num_graphs, dim].
+std::tuple<torch::Tensor, torch::Tensor> segment_moments(const torch::Tensor &input, const torch::Tensor &graph_pointers)
+{
+    segnorm_check(input, graph_pointers);
+    const int64_t n = input.size(0), dim = input.size(1), g = graph_pointers.size(0) - 1;
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(input.device());
+    const torch::Tensor mean = fresh({g, dim}, input.options()), m2 = fresh({g, dim}, input.options());
+    if (g == 0) return std::make_tuple(mean, m2);                  // (empty outputs have no address)
+    check_rc(gnna_segment_moments_ld_f32(n > 0 ? input.data_ptr<float>() : nullptr, ld_of(input), n, graph_pointers.data_ptr<int32_t>(), g,
+                                         mean.data_ptr<float>(), dim, m2.data_ptr<float>(), dim, (int)dim, 0u, current_stream()));
+    return std::make_tuple(mean, m2);
+}
+
+// GraphNorm forward (gnna_segment_norm_ld_f32) -> (out like input, mean, rstd [num_graphs, dim]); weight / bias / alpha: [dim] or
+// None for 1 / 0 / 1.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
+segment_norm(const torch::Tensor &input, const torch::Tensor &graph_pointers, const c10::optional<torch::Tensor> &weight,
+             const c10::optional<torch::Tensor> &bias, const c10::optional<torch::Tensor> &alpha, double eps)
+{
+    segnorm_check(input, graph_pointers);
+    const int64_t n = input.size(0), dim = input.size(1), g = graph_pointers.size(0) - 1;
+    const float *wp = segnorm_param(weight, input, "weight"), *bp = segnorm_param(bias, input, "bias"),
+                *ap = segnorm_param(alpha, input, "alpha");
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(input.device());
+    const torch::Tensor out = fresh({n, dim}, input.options()), mean = fresh({g, dim}, input.options()),
+                        rstd = fresh({g, dim}, input.options());
+    if (n == 0 && g == 0) return std::make_tuple(out, mean, rstd);
+    check_rc(gnna_segment_norm_ld_f32(n > 0 ? input.data_ptr<float>() : nullptr, ld_of(input), n, graph_pointers.data_ptr<int32_t>(), g,
+                                      wp, bp, ap, (float)eps, n > 0 ? out.data_ptr<float>() : nullptr, dim,
+                                      g > 0 ? mean.data_ptr<float>() : nullptr, dim, g > 0 ? rstd.data_ptr<float>() : nullptr, dim,
+                                      (int)dim, 0u, current_stream()));
+    return std::make_tuple(out, mean, rstd);
+}
+
+// GraphNorm backward (gnna_segment_norm_backward_ld_f32) -> (d_input like input | None, seg_a, seg_b [num_graphs, dim]).
+std::tuple<c10::optional<torch::Tensor>, torch::Tensor, torch::Tensor>
+segment_norm_backward(const torch::Tensor &dY, const torch::Tensor &input, const torch::Tensor &mean, const torch::Tensor &rstd,
+                      const torch::Tensor &graph_pointers, const c10::optional<torch::Tensor> &weight,
+                      const c10::optional<torch::Tensor> &alpha, bool need_input)
+{
+    segnorm_check(input, graph_pointers);
+    const int64_t n = input.size(0), dim = input.size(1), g = graph_pointers.size(0) - 1;
+    for (const torch::Tensor *t : {&dY, &mean, &rstd}) {
+        CHECK_CUDA((*t));
+        CHECK_F32((*t));
+        TORCH_CHECK(t->dim() == 2 && t->size(0) == (t == &dY ? n : g) && t->size(1) == dim && t->device() == input.device(),
+                    "dY must be [num_nodes, dim], mean and rstd [num_graphs, dim], on input's device");
+        check_rows(*t, "dY / mean / rstd");
+    }
+    const float *wp = segnorm_param(weight, input, "weight"), *ap = segnorm_param(alpha, input, "alpha");
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(input.device());
+    c10::optional<torch::Tensor> d_input;
+    if (need_input) d_input = fresh({n, dim}, input.options());
+    const torch::Tensor seg_a = fresh({g, dim}, input.options()), seg_b = fresh({g, dim}, input.options());
+    if (g == 0 && (n == 0 || !need_input)) return std::make_tuple(d_input, seg_a, seg_b);
+    auto gptr = [&](const torch::Tensor &t) { return g > 0 ? t.data_ptr<float>() : nullptr; };      // (empty tensors have no address)
+    check_rc(gnna_segment_norm_backward_ld_f32(n > 0 ? dY.data_ptr<float>() : nullptr, ld_of(dY), n > 0 ? input.data_ptr<float>() : nullptr,
+                                               ld_of(input), gptr(mean), ld_of(mean), gptr(rstd), ld_of(rstd), wp, ap,
+                                               graph_pointers.data_ptr<int32_t>(), g,
+                                               d_input.has_value() && n > 0 ? d_input->data_ptr<float>() : nullptr, dim, gptr(seg_a), dim,
+                                               gptr(seg_b), dim, n, (int)dim, 0u, current_stream()));
+    return std::make_tuple(d_input, seg_a, seg_b);
 }
 
 // Backward of aggregate_reduce (gnna_scatter_arg_ld_f32): grad_in[column_index[arg[i, f]], f] += grad_out[i, f], arg >= 0.
@@ -1615,6 +1703,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           "per row; one pass that writes every row, 0 for a row of no graph",
           pybind11::arg("X"), pybind11::arg("gate"), pybind11::arg("lse"), pybind11::arg("Y"), pybind11::arg("dY"),
           pybind11::arg("graph_pointers"), pybind11::arg("need_input") = true, pybind11::arg("need_gate") = true);
+    m.def("segment_moments", &segment_moments,
+          "centred moments per graph (extension) -> (mean, m2), each [num_graphs, dim]: over the rows [graph_pointers[g], "
+          "graph_pointers[g + 1]) of X, mean and sum (x - mean)^2 from one read of X, merged pairwise (never from sums of x^2); 0 for a "
+          "graph without rows",
+          pybind11::arg("X"), pybind11::arg("graph_pointers"));
+    m.def("segment_norm", &segment_norm,
+          "per-graph normalisation, GraphNorm (extension) -> (out like X, mean, rstd [num_graphs, dim]): out[r, f] = weight (x - alpha "
+          "mean) rstd + bias with rstd = 1 / sqrt(m2 / n + (1 - alpha)^2 mean^2 + eps) over the rows of graph g; weight / bias / alpha "
+          "[dim] or None for 1 / 0 / 1; 0 for a row of no graph",
+          pybind11::arg("X"), pybind11::arg("graph_pointers"), pybind11::arg("weight") = pybind11::none(),
+          pybind11::arg("bias") = pybind11::none(), pybind11::arg("alpha") = pybind11::none(), pybind11::arg("eps") = 1e-5);
+    m.def("segment_norm_backward", &segment_norm_backward,
+          "backward of segment_norm (extension) -> (d_input | None, seg_a, seg_b): seg_a = sum dY and seg_b = sum dY xhat over the rows of "
+          "every graph, then d_input in one pass that writes every row, 0 for a row of no graph",
+          pybind11::arg("dY"), pybind11::arg("X"), pybind11::arg("mean"), pybind11::arg("rstd"), pybind11::arg("graph_pointers"),
+          pybind11::arg("weight") = pybind11::none(), pybind11::arg("alpha") = pybind11::none(), pybind11::arg("need_input") = true);
     m.def("segment_topk", &segment_topk,
           "top-k rows per graph of a batch and the induced sub-batch (extension) -> (new_id [N], perm [N'], new_graph_pointers [G + 1], "
           "new_row_pointers, new_column_index, edge_ids, partPtr, part2Node): every graph keeps its min(n, ceil(ratio * n)) -- or "

@@ -5,7 +5,7 @@
 The reference evaluates half of its inputs ("Type II": collections of small graphs) with node-level drivers only; this driver
 finishes such a model inside the library.  A seeded synthetic collection (graph.small_graphs) is kept on the device as a
 batching.GraphDataset; every step cuts a mini-batch of ``--batch_graphs`` graphs out of it (GraphDataset.batch), runs two or more
-GCN / GIN layers on the block-diagonal CSR (with ``--pool topk|sag`` a pooling layer after every conv layer but the last keeps
+GCN / GIN layers on the block-diagonal CSR (with ``--norm graph`` an ops.GraphNorm between every conv layer and its ReLU; with ``--pool topk|sag`` a pooling layer after every conv layer but the last keeps
 the best-scoring ``--pool_ratio`` of the nodes of every graph and the next layer runs on the coarsened batch), reduces the node
 rows of every graph to one row (ops.Readout, one fused call for all
 the statistics of ``--readout``; with ``--attention_readout scalar|channel`` an ops.AttentionalReadout next to them), and trains
@@ -41,6 +41,9 @@ def build_parser():
     p.add_argument("--pool_ratio", type=float, default=0.5, help="the share of its nodes every graph keeps at a pooling layer")
     p.add_argument("--fused_pool", type=_bool, default=True, help="False: the pooling composed from torch ops")
     p.add_argument("--fused_readout", type=_bool, default=True, help="False: the readout composed from torch ops")
+    p.add_argument("--norm", type=str, default="none",
+                   help="none or graph: a per-graph normalisation (ops.GraphNorm) between every conv layer and its ReLU")
+    p.add_argument("--fused_norm", type=_bool, default=True, help="False: the normalisation composed from torch ops")
     p.add_argument("--dim", type=int, default=32, help="input feature width")
     p.add_argument("--hidden", type=int, default=64, help="hidden width")
     p.add_argument("--classes", type=int, default=4, help="graph classes")
@@ -75,6 +78,8 @@ def _parse(args):
         raise SystemExit("--attention_readout takes none, scalar or channel (got %r)" % args.attention_readout)
     if args.pool not in ("none", "topk", "sag"):
         raise SystemExit("--pool takes none, topk or sag (got %r)" % args.pool)
+    if args.norm not in ("none", "graph"):
+        raise SystemExit("--norm takes none or graph (got %r)" % args.norm)
     if not 0.0 < args.pool_ratio <= 1.0:
         raise SystemExit("--pool_ratio must be in (0, 1] (got %r)" % args.pool_ratio)
     if args.num_graphs < 1:
@@ -91,7 +96,7 @@ def _parse(args):
 def build_model(args, modes):
     from torch.nn import Linear, Module, ModuleList
 
-    from .ops import AttentionalReadout, GCNConv, GINConv, Readout, SAGPooling, TopKPooling
+    from .ops import AttentionalReadout, GCNConv, GINConv, GraphNorm, Readout, SAGPooling, TopKPooling
     conv = GCNConv if args.model == "gcn" else GINConv
     attention = args.attention_readout != "none"
 
@@ -100,6 +105,8 @@ def build_model(args, modes):
             super().__init__()
             dims = [args.dim] + [args.hidden] * args.num_layers
             self.convs = ModuleList(conv(a, b) for a, b in zip(dims[:-1], dims[1:]))
+            # per-graph normalisation between every conv layer and its ReLU (its parameters start as constants: no random number)
+            self.norms = ModuleList(GraphNorm(args.hidden, fused=args.fused_norm) for _ in self.convs) if args.norm == "graph" else None
             self.readout = Readout(modes, fused=args.fused_readout)
             # the learned readout next to the statistics: its gate scores every row (scalar) or every element (channel)
             self.attention = AttentionalReadout(Linear(args.hidden, 1 if args.attention_readout == "scalar" else args.hidden),
@@ -116,7 +123,10 @@ def build_model(args, modes):
         def forward(self, x, batch):
             levels = [(batch.num_nodes, int(batch.column_index.numel()))]
             for k, layer in enumerate(self.convs):
-                x = torch.relu(layer(x, batch))
+                x = layer(x, batch)
+                if self.norms is not None:
+                    x = self.norms[k](x, batch)
+                x = torch.relu(x)
                 if self.pools is not None and k < len(self.pools):
                     x, batch, _selection, _gate = self.pools[k](x, batch)
                     levels.append((batch.num_nodes, int(batch.column_index.numel())))
@@ -168,6 +178,8 @@ def main(argv=None, capture=None):
             "fused" if args.fused_readout else "composed"))
         if args.attention_readout != "none":
             print("# attention readout: one score per %s" % ("row" if args.attention_readout == "scalar" else "element"))
+        if args.norm != "none":
+            print("# normalisation: GraphNorm after every conv layer (%s)" % ("fused" if args.fused_norm else "composed"))
 
     def epoch():
         total = torch.zeros((), device=device)

@@ -1962,3 +1962,119 @@ class SAGPooling(_ScorePooling):
     def forward(self, X, batch):
         _f32_only(X, "SAGPooling")
         return self._pool(X, self.gnn(X, batch).reshape(-1), batch)
+
+
+# ---- per-graph normalisation: GraphNorm on a batch of graphs -------------------------------------------------------------------
+def _norm_param(t, F, device, what):
+    """A per-column parameter as the library takes it: float32 [F] on `device`, contiguous; None stays None (the default)."""
+    if t is None:
+        return None
+    if t.dtype != torch.float32 or tuple(t.shape) != (F,) or t.device != device:
+        raise ValueError(f"{what} must be a float32 tensor [{F}] on {device} (got {t.dtype} {tuple(t.shape)} on {t.device})")
+    return t.contiguous()
+
+
+class SegmentNorm(Function):
+    """``SegmentNorm.apply(X, graph_pointers, weight, bias, alpha, eps) -> Y like X``: per-graph normalisation (GraphNorm).  Over
+    the rows of graph g (n rows), per column: mean, var = (1/n) sum (x - alpha mean)^2, Y = weight (x - alpha mean) /
+    sqrt(var + eps) + bias (libgnna gnna_segment_norm_ld_f32: one read of X for the centred moments -- merged pairwise, never from
+    sums of x^2 --, one more for the rows).  weight / bias / alpha are [F] or None for 1 / 0 / 1; a row of no graph gets 0, a
+    one-row graph with alpha = 1 gives bias.  The op saves X, mean and rstd [G, F], the parameters and graph_pointers -- nothing
+    else of the size of X.
+
+    Backward: one pass over dY and X for A = sum dY and B = sum dY xhat per graph, one pass that writes every row of dX once
+    (libgnna gnna_segment_norm_backward_ld_f32; skipped when X needs no gradient); the parameter gradients are [G, F] arithmetic on
+    A, B, mean and rstd.  The same bits on every run.  float32 only."""
+
+    @staticmethod
+    def forward(ctx, X, graph_pointers, weight=None, bias=None, alpha=None, eps=1e-5):
+        _f32_only(X, "SegmentNorm")
+        if X.dim() != 2:
+            raise ValueError(f"SegmentNorm: X must be [rows, F] (got {tuple(X.shape)})")
+        if not (float(eps) > 0.0 and math.isfinite(float(eps))):
+            raise ValueError(f"SegmentNorm: eps must be finite and > 0 (got {eps!r})")
+        gp = _graph_pointers_of(graph_pointers, X.device)
+        F = X.shape[1]
+        w, b, a = (_norm_param(t, F, X.device, name) for t, name in ((weight, "weight"), (bias, "bias"), (alpha, "alpha")))
+        Xl = _laid_out(X)
+        Y, mean, rstd = GNNA.segment_norm(Xl, gp, w, b, a, float(eps))
+        ctx.save_for_backward(Xl, mean, rstd, gp, *(t for t in (w, a) if t is not None))
+        ctx.has_weight, ctx.has_alpha = w is not None, a is not None
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        need_x, need_w, need_b, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3], ctx.needs_input_grad[4]
+        if not (need_x or need_w or need_b or need_a):
+            return (None,) * 6
+        X, mean, rstd, gp = ctx.saved_tensors[:4]
+        rest = list(ctx.saved_tensors[4:])
+        w = rest.pop(0) if ctx.has_weight else None
+        a = rest.pop(0) if ctx.has_alpha else None
+        dX, A, B = GNNA.segment_norm_backward(_laid_out(dY), X, mean, rstd, gp, w, a, bool(need_x))
+        dW = B.sum(0) if need_w else None
+        dB = A.sum(0) if need_b else None
+        dA = None
+        if need_a:
+            mr = mean * rstd
+            t = mr * (A - (1.0 - a) * mr * B)
+            dA = -(t if w is None else t * w).sum(0)
+        return dX, None, dW, dB, dA, None
+
+
+def _composed_graph_norm(X, batch, weight, bias, alpha, eps):
+    """The same function from torch ops on the `batch` vector (index_add_, indexing, a division, a square root): the timing
+    baseline and a second opinion.  It makes several [N, F]-sized temporaries."""
+    gp, G, rows, lo = _batch_vector(batch, X.device)
+    n = rows.numel()
+    Xg = X[lo: lo + n]
+    cnt = (gp[1:] - gp[:-1]).clamp(min=1).to(X.dtype).unsqueeze(1)
+    mean = torch.zeros(G, X.shape[1], dtype=X.dtype, device=X.device).index_add_(0, rows, Xg) / cnt
+    xc = Xg - (mean if alpha is None else alpha * mean)[rows]
+    var = torch.zeros(G, X.shape[1], dtype=X.dtype, device=X.device).index_add_(0, rows, xc * xc) / cnt
+    y = xc / torch.sqrt(var + eps)[rows]
+    if weight is not None:
+        y = y * weight
+    if bias is not None:
+        y = y + bias
+    return torch.nn.functional.pad(y, (0, 0, lo, X.shape[0] - lo - n))          # rows of no graph get 0
+
+
+def graph_norm(x, batch, weight=None, bias=None, mean_scale=None, eps=1e-5):
+    """GraphNorm of the rows of every graph of `batch` (a batching.GraphBatch or its graph_pointers), one fused call:
+    weight * (x - mean_scale * mean) / sqrt(var + eps) + bias with the mean and the variance of (x - mean_scale * mean) per graph and
+    column; weight / bias / mean_scale are [F] or None for 1 / 0 / 1 (mean_scale=None: instance normalisation)."""
+    return SegmentNorm.apply(x, batch, weight, bias, mean_scale, eps)
+
+
+class GraphNorm(Module):
+    """``GraphNorm(channels, eps=1e-5, mean_scale=True, affine=True, fused=True)(x, batch) -> like x``: the normalisation of GraphNorm
+    (Cai et al., ICML 2021; PyG's nn.GraphNorm) on a batching.GraphBatch or its graph_pointers: per graph and column,
+    weight * (x - mean_scale * mean) / sqrt(var + eps) + bias, var the variance of (x - mean_scale * mean).  Parameters `weight`
+    (ones), `bias` (zeros) and `mean_scale` (ones): PyG's names and initial values.  mean_scale=False fixes the scale of the mean at 1
+    (PyG's InstanceNorm on a batch), affine=False leaves weight and bias out.  There are no running statistics: training and
+    evaluation compute the same function.  fused=True is ONE call of SegmentNorm; fused=False composes the same function from
+    torch ops on the `batch` vector, kept as the timing baseline and as a second opinion.  float32 only."""
+
+    def __init__(self, channels, eps=1e-5, mean_scale=True, affine=True, fused=True):
+        super().__init__()
+        if not (float(eps) > 0.0 and math.isfinite(float(eps))):
+            raise ValueError(f"eps must be finite and > 0 (got {eps!r})")
+        self.channels, self.eps, self.fused = int(channels), float(eps), bool(fused)
+        self.weight = Parameter(torch.ones(self.channels)) if affine else None
+        self.bias = Parameter(torch.zeros(self.channels)) if affine else None
+        self.mean_scale = Parameter(torch.ones(self.channels)) if mean_scale else None
+
+    def reset_parameters(self):
+        with torch.no_grad():
+            for t, v in ((self.weight, 1.0), (self.bias, 0.0), (self.mean_scale, 1.0)):
+                if t is not None:
+                    t.fill_(v)
+
+    def forward(self, x, batch):
+        _f32_only(x, "GraphNorm")
+        if x.dim() != 2 or x.shape[1] != self.channels:
+            raise ValueError(f"GraphNorm({self.channels}): x must be [rows, {self.channels}] (got {tuple(x.shape)})")
+        if not self.fused:
+            return _composed_graph_norm(x, batch, self.weight, self.bias, self.mean_scale, self.eps)
+        return SegmentNorm.apply(x, batch, self.weight, self.bias, self.mean_scale, self.eps)
