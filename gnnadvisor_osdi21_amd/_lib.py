@@ -188,6 +188,18 @@ STAGED["gnna_segnorm.h"] = {
     # (d_out, ld) (input, ld) (mean, ld) (rstd, ld), weight, alpha, graph_pointers, num_segments, (d_input, ld) (seg_a, ld) (seg_b, ld), num_rows, dim, flags, stream
     "gnna_segment_norm_backward_ld_f32": (i, [p, i64] * 4 + [p, p, p, i64] + [p, i64] * 3 + [i64, i, u, p]),
 }
+# staged headers added after the record of STAGED was pinned (tests/test_segnorm_host.py pins STAGED to its one header as
+# tests/test_binding_table_host.py pins HEADERS): the same kind of table, applied by load() after STAGED under the same rule; its
+# entries move to STAGED, and from there to HEADERS, when those records are next extended
+STAGED_NEXT = {}
+# subgraph sampling: device random walks and the induced subgraph of a node list
+STAGED_NEXT["gnna_walk.h"] = {
+    # row_pointers, column_index, num_nodes, nnz, roots, num_roots, walk_length, rng_seed, walks, edge_ids, stream
+    "gnna_random_walk_i32": (i, [p, p, i64, i64, p, i64, i, u64, p, p, p]),
+    # row_pointers, column_index, num_nodes, nnz, nodes, num_ids, partSize, sub_nodes, new_id, sub_row_pointers, sub_column_index,
+    # sub_edge_ids, partPtr, part2Node, node_capacity, edge_capacity, counts, stream
+    "gnna_induced_subgraph_i32": (i, [p, p, i64, i64, p, i64, i] + [p] * 7 + [i64, i64, pi64, p]),
+}
 del p, i, i64, u, u64, f, s, pd, pi, pi64
 EXPORTS = tuple(HEADERS["gnna.h"])     # users: the build's check of the library, tests/test_host.py
 
@@ -203,7 +215,7 @@ def load() -> ctypes.CDLL:
             "(run `python -m gnnadvisor_osdi21_amd.build`). There is no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
     bound = {}
-    for header, table in list(HEADERS.items()) + list(STAGED.items()):
+    for header, table in list(HEADERS.items()) + list(STAGED.items()) + list(STAGED_NEXT.items()):
         for name, (restype, argtypes) in table.items():
             if bound.setdefault(name, header) != header:
                 raise ImportError(f"{name} is bound under two headers of _lib.HEADERS: {bound[name]} and {header}")
@@ -1599,6 +1611,89 @@ def sample_neighbors(row_pointers, column_index, seeds, fanout, rng_seed, partSi
     return {"row_pointers": blk_rp, "column_index": blk_ci[:nnz], "edge_ids": eid[:nnz] if want_edge_ids else None,
             "src_nodes": src[:num_src], "partPtr": pp[:P + 1] if want_part else None,
             "part2Node": p2n[:P] if want_part else None, "num_dst": S, "num_src": num_src}
+
+
+# ---- subgraph sampling (gnna_walk.hip) -------------------------------------------------------------------------------------
+def _graph_ids(row_pointers, column_index, ids, what):
+    rp, ci = _device_i32(row_pointers, "row_pointers"), _device_i32(column_index, "column_index")
+    t = _device_i32(ids, what)
+    assert rp.numel() >= 1 and ci.device == rp.device and t.device == rp.device, \
+        f"row_pointers must be [num_nodes + 1]; column_index and {what} live on its device"
+    return rp, ci, t
+
+
+def random_walk(row_pointers, column_index, roots, walk_length, rng_seed, want_edge_ids=False):
+    """gnna_random_walk_i32 (device): one uniform first-order walk of `walk_length` steps from every entry of `roots` (int32
+    [R]) on the device CSR row_pointers [N + 1] / column_index [nnz] -> (walks int32 [R, walk_length + 1], edge_ids int32
+    [R, walk_length] or None).  Step t of walk w takes position lo + floor(key * d / 2^64) of its row, key = the splitmix64 key of
+    u = w * walk_length + t under rng_seed; a row without positions and an edge to an id outside the graph make the walk stay
+    (edge id -1); a root outside the graph gives a row of -1 (the rule is spelled out in csrc/gnna_walk.h).  A function of
+    (rng_seed, w, t) and the graph only.  No synchronisation, no read-back: capturable, accepted under
+    set_tuning(deterministic=1)."""
+    rp, ci, rt = _graph_ids(row_pointers, column_index, roots, "roots")
+    n, R, L = rp.numel() - 1, rt.numel(), int(walk_length)
+    if L < 0:
+        raise GnnaError(f"walk_length must not be negative (got {walk_length})")
+    rng_seed = int(rng_seed) & 0xFFFFFFFFFFFFFFFF
+    dev = rp.device
+    with torch.cuda.device(dev):
+        walks = torch.empty((R, L + 1), dtype=torch.int32, device=dev)
+        eid = torch.empty((R, L), dtype=torch.int32, device=dev) if want_edge_ids else None
+    _call(dev, "gnna_random_walk_i32", rp.data_ptr(), _ptr(ci) if ci.numel() else None, n, ci.numel(), _ptr(rt) if R else None, R, L,
+          rng_seed, _ptr(walks) if R else None, _ptr(eid) if want_edge_ids and R * L else None)
+    return walks, eid
+
+
+def induced_subgraph(row_pointers, column_index, nodes, partSize=None, want_edge_ids=True, want_new_id=False, *,
+                     node_capacity=None, edge_capacity=None):
+    """gnna_induced_subgraph_i32 (device): the subgraph that the node list `nodes` (int32 [num_ids]: duplicates welcome, -1
+    skipped, any other id outside the graph an error) induces in the device CSR row_pointers [N + 1] / column_index [nnz].  The
+    kept set S is the distinct ids in increasing global id; row a holds the positions of row S[a] whose column is in S, in
+    increasing position (the rule is spelled out in csrc/gnna_walk.h).  -> dict: row_pointers [n + 1], column_index [nnz']
+    (ranks in S), edge_ids [nnz'] (positions in column_index; None with want_edge_ids=False), nodes [n] (= S, global ids),
+    new_id [N] (the rank of a kept node, -1 otherwise; None unless want_new_id), partPtr [P + 1] / part2Node [P] (what build_part
+    gives for the new row pointers; None without partSize), num_nodes (= n).  The arrays are trimmed views of buffers sized here:
+    min(num_ids, N) nodes and min(nnz, the degree sum over `nodes`) edges.  One stream synchronisation; refuses to run inside a
+    stream capture; the same bits on every run.  node_capacity / edge_capacity override the sizes chosen here; a GnnaError raised
+    for a capacity that is too small carries the needed (nodes, edges, parts) as ``.counts``."""
+    rp, ci, nd = _graph_ids(row_pointers, column_index, nodes, "nodes")
+    n, K, nnz = rp.numel() - 1, nd.numel(), ci.numel()
+    want_part = partSize is not None
+    if want_part and int(partSize) <= 0:
+        raise GnnaError(f"partSize must be positive (got {partSize})")
+    dev = rp.device
+    with torch.cuda.device(dev):
+        node_cap = min(K, n) if node_capacity is None else int(node_capacity)
+        if edge_capacity is not None:
+            edge_cap = int(edge_capacity)
+        elif K > 0 and n > 0:
+            # the degree sum over the list (ids outside the graph are the library's to report)
+            rows = nd.long().clamp(0, n - 1)
+            edge_cap = min(nnz, int((rp[rows + 1] - rp[rows]).clamp(min=0).sum()))
+        else:
+            edge_cap = 0
+        if node_cap < 0 or edge_cap < 0:
+            raise GnnaError("capacities must not be negative")
+        i32 = dict(dtype=torch.int32, device=dev)
+        sub_nodes, sub_rp = torch.empty(node_cap, **i32), torch.empty(node_cap + 1, **i32)
+        sub_ci = torch.empty(edge_cap, **i32)
+        eid = torch.empty(edge_cap, **i32) if want_edge_ids else None
+        new_id = torch.empty(n, **i32) if want_new_id else None
+        pp = torch.empty(edge_cap + 1, **i32) if want_part else None
+        p2n = torch.empty(edge_cap, **i32) if want_part else None
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() > 0 else None                 # noqa: E731
+        counts = (ctypes.c_int64 * 3)()
+        rc = load().gnna_induced_subgraph_i32(rp.data_ptr(), ptr(ci), n, nnz, ptr(nd), K, int(partSize) if want_part else 0,
+                                              ptr(sub_nodes), ptr(new_id), sub_rp.data_ptr(), ptr(sub_ci), ptr(eid), _ptr(pp),
+                                              ptr(p2n), node_cap, edge_cap, counts, _stream(dev))
+    if rc != GNNA_OK:
+        err = GnnaError(f"libgnna error {rc}: {load().gnna_last_error().decode()}")
+        err.counts = tuple(int(c) for c in counts)
+        raise err
+    m, e, P = int(counts[0]), int(counts[1]), int(counts[2])
+    return {"row_pointers": sub_rp[:m + 1], "column_index": sub_ci[:e], "edge_ids": eid[:e] if want_edge_ids else None,
+            "nodes": sub_nodes[:m], "new_id": new_id, "partPtr": pp[:P + 1] if want_part else None,
+            "part2Node": p2n[:P] if want_part else None, "num_nodes": m}
 
 
 # ---- hierarchical pooling on graph batches (gnna_topk.hip) -------------------------------------------------------------------

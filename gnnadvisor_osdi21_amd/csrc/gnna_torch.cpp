@@ -42,6 +42,7 @@
 #include "gnna_attnpool.h"
 #include "gnna_topk.h"
 #include "gnna_segnorm.h"        // staged beside the sources (its first paragraph)
+#include "gnna_walk.h"           // staged likewise
 
 #define CHECK_CUDA(x) TORCH_CHECK(x.is_cuda(), #x " must be a CUDA tensor")
 #define CHECK_CONTIGUOUS(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -1569,6 +1570,75 @@ segment_topk(const torch::Tensor &score, const torch::Tensor &graph_pointers, do
                            opt(eid, counts[1]), opt(pp, counts[2] + 1), opt(p2n, counts[2]));
 }
 
+// ---- subgraph sampling (gnna_walk.hip) ---------------------------------------------------------------------------------------
+
+// what both entries check of the graph and of their id list
+static void walk_check(const torch::Tensor &row_pointers, const torch::Tensor &column_index, const torch::Tensor &ids, const char *ids_name)
+{
+    check_device_ids(row_pointers, "row_pointers");
+    check_device_ids(column_index, "column_index");
+    check_device_ids(ids, ids_name);
+    TORCH_CHECK(row_pointers.numel() >= 1 && column_index.device() == row_pointers.device() && ids.device() == row_pointers.device(),
+                "row_pointers must be [num_nodes + 1]; column_index and ", ids_name, " live on its device");
+}
+
+// Uniform random walks (gnna_random_walk_i32) -> (walks [R, walk_length + 1], edge_ids [R, walk_length] or None).
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>>
+random_walk(const torch::Tensor &row_pointers, const torch::Tensor &column_index, const torch::Tensor &roots, int64_t walk_length,
+            uint64_t rng_seed, bool want_edge_ids)
+{
+    walk_check(row_pointers, column_index, roots, "roots");
+    TORCH_CHECK(walk_length >= 0 && walk_length < std::numeric_limits<int>::max(), "walk_length must not be negative");
+    const int64_t n = row_pointers.numel() - 1, nnz = column_index.numel(), r = roots.numel();
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(row_pointers.device());
+    const auto ids = row_pointers.options();
+    const torch::Tensor walks = torch::empty({r, walk_length + 1}, ids);
+    torch::Tensor eid;
+    if (want_edge_ids) eid = torch::empty({r, walk_length}, ids);
+    auto ip = [](const torch::Tensor &t) { return t.defined() && t.numel() > 0 ? t.data_ptr<int32_t>() : nullptr; };
+    check_rc(gnna_random_walk_i32(row_pointers.data_ptr<int32_t>(), ip(column_index), n, nnz, ip(roots), r, (int)walk_length, rng_seed,
+                                  ip(walks), ip(eid), current_stream()));
+    return std::make_tuple(walks, want_edge_ids ? c10::optional<torch::Tensor>(eid) : c10::nullopt);
+}
+
+// The subgraph a node list induces (gnna_induced_subgraph_i32) -> (row_pointers [n + 1], column_index [nnz'], edge_ids [nnz'],
+// nodes [n], new_id [N], partPtr [P + 1], part2Node [P]); None for what was not asked for (partSize = 0: no partition).  The
+// arrays are trimmed views of buffers of min(num_ids, N) nodes and min(nnz, the degree sum over the list) edges.
+std::tuple<torch::Tensor, torch::Tensor, c10::optional<torch::Tensor>, torch::Tensor, c10::optional<torch::Tensor>,
+           c10::optional<torch::Tensor>, c10::optional<torch::Tensor>>
+induced_subgraph(const torch::Tensor &row_pointers, const torch::Tensor &column_index, const torch::Tensor &nodes, int64_t partSize,
+                 bool want_edge_ids, bool want_new_id)
+{
+    walk_check(row_pointers, column_index, nodes, "nodes");
+    TORCH_CHECK(partSize >= 0 && partSize <= std::numeric_limits<int>::max(), "partSize must not be negative");
+    const bool parts = partSize > 0;
+    const int64_t n = row_pointers.numel() - 1, nnz = column_index.numel(), k = nodes.numel();
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(row_pointers.device());
+    const auto ids = row_pointers.options();
+    const int64_t node_cap = std::min(k, n);
+    int64_t edge_cap = 0;
+    if (k > 0 && n > 0) {
+        // the degree sum over the list (ids outside the graph are the library's to report)
+        const auto rows = nodes.to(at::kLong).clamp(0, n - 1);
+        const auto rp = row_pointers.to(at::kLong);
+        edge_cap = std::min(nnz, (rp.index_select(0, rows + 1) - rp.index_select(0, rows)).clamp_min(0).sum().item<int64_t>());
+    }
+    const torch::Tensor sub_nodes = torch::empty({node_cap}, ids), sub_rp = torch::empty({node_cap + 1}, ids),
+                        sub_ci = torch::empty({edge_cap}, ids);
+    torch::Tensor eid, new_id, pp, p2n;
+    if (want_edge_ids) eid = torch::empty({edge_cap}, ids);
+    if (want_new_id) new_id = torch::empty({n}, ids);
+    if (parts) { pp = torch::empty({edge_cap + 1}, ids); p2n = torch::empty({edge_cap}, ids); }
+    auto ip = [](const torch::Tensor &t) { return t.defined() && t.numel() > 0 ? t.data_ptr<int32_t>() : nullptr; };
+    int64_t counts[3] = {0, 0, 0};
+    check_rc(gnna_induced_subgraph_i32(row_pointers.data_ptr<int32_t>(), ip(column_index), n, nnz, ip(nodes), k, (int)partSize,
+                                       ip(sub_nodes), ip(new_id), sub_rp.data_ptr<int32_t>(), ip(sub_ci), ip(eid), ip(pp), ip(p2n),
+                                       node_cap, edge_cap, counts, current_stream()));
+    auto opt = [](const torch::Tensor &t, int64_t len) { return t.defined() ? c10::optional<torch::Tensor>(t.narrow(0, 0, len)) : c10::nullopt; };
+    return std::make_tuple(sub_rp.narrow(0, 0, counts[0] + 1), sub_ci.narrow(0, 0, counts[1]), opt(eid, counts[1]),
+                           sub_nodes.narrow(0, 0, counts[0]), opt(new_id, n), opt(pp, counts[2] + 1), opt(p2n, counts[2]));
+}
+
 // what both row gathers check of their features, row ids and scale
 static void gather_rows_check(const torch::Tensor &rows, const char *rows_name, const torch::Tensor &ids, const char *ids_name,
                               const c10::optional<torch::Tensor> &scale, int64_t scale_len)
@@ -1727,6 +1797,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           pybind11::arg("score"), pybind11::arg("graph_pointers"), pybind11::arg("ratio") = 0.0, pybind11::arg("k") = 0,
           pybind11::arg("row_pointers") = pybind11::none(), pybind11::arg("column_index") = pybind11::none(),
           pybind11::arg("partSize") = 0, pybind11::arg("want_edge_ids") = false);
+    m.def("random_walk", &random_walk,
+          "uniform first-order random walks on the device (extension) -> (walks [R, walk_length + 1], edge_ids [R, walk_length] | None): "
+          "step t of walk w takes position lo + floor(key * d / 2^64) of its row, key = the splitmix64 key of w * walk_length + t "
+          "under rng_seed; a row without positions or an edge out of the graph makes the walk stay (edge id -1).  No "
+          "synchronisation; capturable",
+          pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("roots"), pybind11::arg("walk_length"),
+          pybind11::arg("rng_seed"), pybind11::arg("want_edge_ids") = false);
+    m.def("induced_subgraph", &induced_subgraph,
+          "the subgraph a node list induces (extension) -> (row_pointers, column_index, edge_ids, nodes, new_id, partPtr, part2Node): "
+          "the kept nodes are the distinct ids of the list in increasing global id (-1 skipped), every row keeps the positions whose "
+          "column is kept, in increasing position; None for what was not asked for.  One stream synchronisation; not capturable",
+          pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("nodes"), pybind11::arg("partSize") = 0,
+          pybind11::arg("want_edge_ids") = true, pybind11::arg("want_new_id") = false);
     m.def("gather_rows_scale", &gather_rows_scale,
           "out[i] = scale[perm[i]] * input[perm[i]] (extension) -> out [perm.numel(), dim]; a plain gather without scale; a perm[i] "
           "outside the rows of input gives a row of zeros",

@@ -100,6 +100,15 @@ def build_parser():
                         "with one entry per layer, the neighbours sampled per node at that layer (-1: all of them), e.g. 25,10; "
                         "the blocks are drawn on the device (sampling.NeighborSampler, MI355X addition)")
     p.add_argument('--batch_size', type=int, default=1024, help="--fanout: seed nodes per mini-batch")
+    p.add_argument('--saint_roots', type=int, default=None,
+                   help="with --walk_length: train on GraphSAINT random-walk subgraphs -- every step walks --walk_length steps from "
+                        "this many random roots on the device and trains on the subgraph the visited nodes induce, at full depth "
+                        "(sampling.SaintRWSampler, MI355X addition); every model whose layers take a graph batch (all but rgcn)")
+    p.add_argument('--walk_length', type=int, default=None, help="--saint_roots: steps of every walk (GraphSAINT-RW on Reddit: 2)")
+    p.add_argument('--saint_steps', type=int, default=8, help="--saint_roots: subgraphs (optimiser steps) per epoch")
+    p.add_argument('--saint_coverage', type=int, default=0,
+                   help="--saint_roots: T > 0 pre-samples T subgraphs and weighs every node's loss by GraphSAINT's T / (N C_v) "
+                        "(SaintRWSampler.estimate_norms); 0: the plain mean over the subgraph's nodes")
     p.add_argument('--policy', type=str, default='mi355x', choices=['mi355x', 'compat'], help="Decider policy")
     p.add_argument('--force_rabbit', default='False', **tf,
                    help="True: with --enable_rabbit True in auto mode, renumber even when the mi355x cost gate says the run is "
@@ -185,6 +194,33 @@ def main(argv=None, capture=None):
             raise SystemExit("--fanout needs one entry per layer: --model %s has 2 layers (got %d)" % (args.model, len(fanouts)))
         if args.batch_size < 1:
             raise SystemExit("--batch_size must be >= 1")
+    saint = args.saint_roots is not None or args.walk_length is not None
+    if saint:
+        if args.saint_roots is None or args.walk_length is None:
+            raise SystemExit("--saint_roots and --walk_length come together: the roots per step and the steps of every walk")
+        if fanouts is not None:
+            raise SystemExit("--saint_roots does not go with --fanout: one trains on induced subgraphs at full depth, the other "
+                             "on per-layer blocks; pass one of them")
+        if args.model == 'rgcn':
+            raise SystemExit("--saint_roots trains on induced subgraphs, which --model rgcn does not take (its layers run on a "
+                             "relational.RelationalGraph): run it with one of gcn, gin, sage, gat, gatv2, transformer, pna, gen")
+        if flag(args.hip_graph):
+            raise SystemExit("--saint_roots does not support --hip_graph True: every step cuts a new subgraph and reads its sizes "
+                             "back; run it with --hip_graph False")
+        if args.dtype != 'float32':
+            raise SystemExit("--saint_roots: the subgraph steps are float32 only; use --dtype float32")
+        if single_spmm or verify_spmm:
+            raise SystemExit("--saint_roots does not go with --single_spmm / --verify_spmm: they run one full-graph aggregation")
+        if args.saint_roots < 1:
+            raise SystemExit("--saint_roots must be >= 1")
+        if args.walk_length < 0:
+            raise SystemExit("--walk_length must be >= 0")
+        if args.saint_steps < 1:
+            raise SystemExit("--saint_steps must be >= 1")
+        if args.saint_coverage < 0:
+            raise SystemExit("--saint_coverage must be >= 0")
+    elif args.saint_steps != 8 or args.saint_coverage != 0:
+        raise SystemExit("--saint_steps and --saint_coverage belong to --saint_roots: pass --saint_roots R --walk_length L")
     assert torch.cuda.is_available(), "requires an MI355X GPU: there is no CPU path"
     device = torch.device('cuda')
     if flag(args.tune_gemm):
@@ -527,6 +563,61 @@ def main(argv=None, capture=None):
             return loss
 
         for _ in range(max(1, -(-10 // len(batches)))):   # dry run: at least 10 steps
+            loss = train()
+        torch.cuda.synchronize()
+        start_train = time.perf_counter()
+        for _ in range(1, args.num_epoches + 1):
+            loss = train()
+        torch.cuda.synchronize()
+        train_time = time.perf_counter() - start_train
+        if capture is not None:
+            capture.update(first_loss=first_loss[0], final_loss=float(loss.detach()))
+    elif saint:
+        # one epoch = --saint_steps steps; every step walks from fresh roots, cuts the induced subgraph of the visited nodes out on
+        # the device (one walk call, one subgraph call), gathers x and y by its nodes and makes one step on ALL its nodes: the
+        # layers run on the subgraph as on any graph batch, at full depth
+        from .sampling import SaintRWSampler
+        sampler = SaintRWSampler(inputInfo, args.saint_roots, args.walk_length, seed=0x5A17)
+        if args.saint_coverage > 0:
+            sampler.estimate_norms(args.saint_coverage)
+        drawn = [0]
+        first_loss = [None]
+        if capture is not None:
+            capture.update(sampler=sampler)
+
+        def saint_logits(x, sub):
+            if args.model == 'gin':
+                for i, conv in enumerate(model.convs):
+                    x = conv(x, sub, relu=i + 1 < len(model.convs))
+            elif attention:
+                kw = {} if edge_attr is None else dict(edge_attr=edge_attr.index_select(0, sub.edge_ids.long()))
+                x = model.conv2(F.elu(model.conv1(x, sub, **kw)), sub, **kw)
+            else:
+                x = model.conv2(model.conv1(x, sub, relu=True), sub)
+            return F.log_softmax(x.float(), dim=1)
+
+        def train():                                   # noqa: F811  (the subgraph epoch replaces the full-graph step)
+            model.train()
+            loss = None
+            for _ in range(args.saint_steps):
+                sub = sampler.sample(drawn[0])
+                drawn[0] += 1
+                rows = sub.nodes.long()
+                optimizer.zero_grad()
+                log_prob = saint_logits(dataset.x.index_select(0, rows), sub)
+                picked = -log_prob.gather(1, dataset.y.index_select(0, rows).view(-1, 1)).view(-1)
+                weight = sub.node_weight
+                # GraphSAINT's loss normalisation: sum_v L_v / lambda_v over the subgraph, lambda_v = N C_v / T
+                loss = picked.mean() if weight is None else (picked * weight).sum()
+                loss.backward()
+                optimizer.step()
+                if first_loss[0] is None:
+                    first_loss[0] = float(loss.detach())
+                    if verbose_mode:
+                        print("# first loss: {:.6f}".format(first_loss[0]))
+            return loss
+
+        for _ in range(max(1, -(-10 // args.saint_steps))):   # dry run: at least 10 steps
             loss = train()
         torch.cuda.synchronize()
         start_train = time.perf_counter()

@@ -10,12 +10,19 @@ indexing: ``blocks[l-1].num_dst == blocks[l].num_src``.
 libgnna keys its per-graph tables (slice plans, hints) by the device address of ``column_index``, and PyTorch's caching
 allocator hands the address of a dropped block to the next one: a block drops the library's entries together with its
 storage (``_lib._forget_when_freed``) and never calls ``prepare_graph``.
+
+Subgraph sampling is the other family: ``RandomWalkSampler`` walks on the device (libgnna ``gnna_random_walk_i32``),
+``induced_subgraph`` cuts the subgraph of an arbitrary node list out on the device (``gnna_induced_subgraph_i32``: one launch
+sequence and one read-back) and ``SaintRWSampler`` puts the two together as GraphSAINT's random-walk sampler.  A ``Subgraph`` is a
+``batching.GraphBatch`` of one graph -- an ordinary square CSR bundle -- so every layer that takes a graph batch runs on it
+unchanged, at full-graph depth, where a ``SampledBlock`` needs one block per layer.
 """
 from __future__ import annotations
 
 import torch
 
 from . import _lib
+from .batching import GraphBatch
 
 
 class _BlockTranspose(object):
@@ -112,3 +119,141 @@ class NeighborSampler(object):
             dst = blk.src_nodes
         blocks.reverse()
         return blocks, blocks[0].src_nodes
+
+
+# ---- subgraph sampling: walks, induced subgraphs, GraphSAINT-RW ----------------------------------------------------------------
+
+def _device_graph(inputInfo, who):
+    ci = inputInfo.column_index
+    if not getattr(ci, "is_cuda", False):
+        raise ValueError(f"{who} runs on the device: move row_pointers and column_index to the GPU first")
+    return inputInfo.row_pointers.to(ci.device), ci
+
+
+class Subgraph(GraphBatch):
+    """The subgraph a node set induces in a parent graph, as a ``GraphBatch`` of ONE graph (``graph_pointers = [0, n]``): every
+    layer that takes a graph batch takes it.  Beyond the batch it carries ``nodes`` (int32 [n]: the global id of every row,
+    increasing), ``edge_ids`` (int32 [nnz']: the position of every edge in the parent's column_index, or None) and
+    ``parent_num_nodes``.  ``directed``, ``partSize`` and the launch knobs are the parent bundle's; the degrees come from the new
+    row pointers.  ``node_weight`` (float32 [n]) and ``edge_weight`` (float32 [nnz']) are GraphSAINT's normalisation
+    coefficients read through ``nodes`` / ``edge_ids``; None unless the sampler that made the subgraph has estimated them."""
+
+    def __init__(self, result, parent, norms=None):
+        n = int(result["num_nodes"])
+        dev = result["row_pointers"].device
+        super().__init__(result["row_pointers"], result["column_index"], torch.tensor([0, n], dtype=torch.int32, device=dev),
+                         partSize=int(getattr(parent, "partSize", None) or 32), dimWorker=getattr(parent, "dimWorker", None),
+                         warpPerBlock=getattr(parent, "warpPerBlock", None), directed=bool(getattr(parent, "directed", False)),
+                         partPtr=result["partPtr"], part2Node=result["part2Node"])
+        self.nodes, self.edge_ids = result["nodes"], result["edge_ids"]
+        self.parent_num_nodes = int(parent.row_pointers.numel()) - 1
+        self._norms = norms
+        if self.column_index.numel() > 0:
+            _lib._forget_when_freed(self.column_index)
+
+    @property
+    def node_weight(self):
+        return None if self._norms is None else self._norms[0].index_select(0, self.nodes.long())
+
+    @property
+    def edge_weight(self):
+        if self._norms is None:
+            return None
+        if self.edge_ids is None:
+            raise ValueError("edge_weight is read through edge_ids: cut the subgraph with want_edge_ids=True")
+        return self._norms[1].index_select(0, self.edge_ids.long())
+
+
+def induced_subgraph(inputInfo, nodes, want_edge_ids=True, *, edge_capacity=None, _norms=None):
+    """The ``Subgraph`` that `nodes` (ids on the graph's device, or anything ``torch.as_tensor`` takes; duplicates welcome, -1
+    skipped) induces in the graph bundle `inputInfo`: its kept nodes are the distinct ids in increasing global id, every row keeps
+    its edges to kept nodes in their order.  One libgnna call and one read-back; the partition comes with it."""
+    rp, ci = _device_graph(inputInfo, "induced_subgraph")
+    ids = torch.as_tensor(nodes).to(device=ci.device, dtype=torch.int32).reshape(-1).contiguous()
+    partSize = int(getattr(inputInfo, "partSize", None) or 32)
+    r = _lib.induced_subgraph(rp, ci, ids, partSize=partSize, want_edge_ids=want_edge_ids, edge_capacity=edge_capacity)
+    return Subgraph(r, inputInfo, _norms)
+
+
+class RandomWalkSampler(object):
+    """``RandomWalkSampler(inputInfo, walk_length).walk(roots, rng_seed)`` -> (walks int32 [R, walk_length + 1], edge_ids int32
+    [R, walk_length] or None): uniform first-order walks on the device, a function of (rng_seed, walk, step) and the graph only
+    (DeepWalk / node2vec corpora with p = q = 1, PinSAGE visit counts, the GraphSAINT-RW sampler).  No read-back: capturable."""
+
+    def __init__(self, inputInfo, walk_length):
+        self.row_pointers, self.column_index = _device_graph(inputInfo, "the walk sampler")
+        self.walk_length = int(walk_length)
+        if self.walk_length < 0:
+            raise ValueError("walk_length must not be negative")
+
+    def walk(self, roots, rng_seed, want_edge_ids=False):
+        roots = torch.as_tensor(roots).to(device=self.column_index.device, dtype=torch.int32).reshape(-1).contiguous()
+        return _lib.random_walk(self.row_pointers, self.column_index, roots, self.walk_length, rng_seed, want_edge_ids=want_edge_ids)
+
+
+class SaintRWSampler(object):
+    """GraphSAINT's random-walk sampler: ``sample(step)`` draws `num_roots` roots from a device generator seeded with
+    (seed, step), walks `walk_length` steps from each (one call) and returns the ``Subgraph`` that the visited nodes induce (one
+    call on ``walks.reshape(-1)``).  The same (seed, step) gives the same subgraph.  The edge buffer of the next call is sized at
+    1.25x the largest subgraph seen so far; a call it was too small for is repeated once with the size the library reported.
+
+    ``estimate_norms(T)`` is GraphSAINT's pre-sampling: over the subgraphs of the steps -1 .. -T, C_v counts those holding node
+    v and C_e those holding edge position e (``node_count`` / ``edge_count``, int64; integer ``index_add_`` is order-independent);
+    a zero count then counts 0.1.  ``node_weight[v] = T / (N C_v)`` weighs the loss of node v, ``edge_weight[e] =
+    clamp(C_row(e) / C_e, 0, 1e4)`` the aggregation over edge e (``ops.EdgeWeightedAggregate``); every later ``Subgraph`` reads
+    them through its ``nodes`` / ``edge_ids``."""
+
+    def __init__(self, inputInfo, num_roots, walk_length, seed=0):
+        self.inputInfo = inputInfo
+        self.walker = RandomWalkSampler(inputInfo, walk_length)
+        self.num_roots, self.walk_length, self.seed = int(num_roots), int(walk_length), int(seed)
+        if self.num_roots < 1:
+            raise ValueError("num_roots must be >= 1")
+        self.num_nodes = int(self.walker.row_pointers.numel()) - 1
+        self.max_edges = 0                    # the largest nnz' seen
+        self.node_count = self.edge_count = self.node_weight = self.edge_weight = None
+
+    def _step_seed(self, step):
+        return (self.seed * 0x9E3779B97F4A7C15 + int(step)) & 0x7FFFFFFFFFFFFFFF
+
+    def roots(self, step):
+        dev = self.walker.column_index.device
+        gen = torch.Generator(device=dev).manual_seed(self._step_seed(step))
+        return torch.randint(0, max(self.num_nodes, 1), (self.num_roots,), generator=gen, device=dev, dtype=torch.int32)
+
+    def sample(self, step):
+        walks, _ = self.walker.walk(self.roots(step), self._step_seed(step))
+        ids = walks.reshape(-1)
+        norms = None if self.node_weight is None else (self.node_weight, self.edge_weight)
+        capacity = min(int(self.max_edges * 1.25) + 1, int(self.walker.column_index.numel())) if self.max_edges > 0 else None
+        try:
+            sub = induced_subgraph(self.inputInfo, ids, edge_capacity=capacity, _norms=norms)
+        except _lib.GnnaError as err:
+            counts = getattr(err, "counts", None)
+            if capacity is None or counts is None or "capacity too small" not in str(err):
+                raise
+            sub = induced_subgraph(self.inputInfo, ids, edge_capacity=counts[1], _norms=norms)      # once, from what it reported
+        self.max_edges = max(self.max_edges, int(sub.column_index.numel()))
+        return sub
+
+    def estimate_norms(self, num_subgraphs):
+        T = int(num_subgraphs)
+        if T < 1:
+            raise ValueError("num_subgraphs must be >= 1")
+        rp, ci = self.walker.row_pointers, self.walker.column_index
+        dev = ci.device
+        self.node_weight = self.edge_weight = None                      # (the pre-sampled subgraphs carry no weights)
+        node_count = torch.zeros(self.num_nodes, dtype=torch.int64, device=dev)
+        edge_count = torch.zeros(ci.numel(), dtype=torch.int64, device=dev)
+        for i in range(T):
+            sub = self.sample(-(i + 1))
+            node_count.index_add_(0, sub.nodes.long(), torch.ones(sub.nodes.numel(), dtype=torch.int64, device=dev))
+            edge_count.index_add_(0, sub.edge_ids.long(), torch.ones(sub.edge_ids.numel(), dtype=torch.int64, device=dev))
+        self.node_count, self.edge_count = node_count, edge_count
+        c_v = node_count.double().masked_fill(node_count == 0, 0.1)
+        c_e = edge_count.double().masked_fill(edge_count == 0, 0.1)
+        rows = torch.repeat_interleave(torch.arange(self.num_nodes, device=dev), (rp[1:] - rp[:-1]).long().clamp(min=0),
+                                       output_size=ci.numel())
+        self.node_weight = (T / (self.num_nodes * c_v)).float()
+        self.edge_weight = (c_v[rows] / c_e).clamp(0, 1e4).float()
+        return self.node_weight, self.edge_weight
