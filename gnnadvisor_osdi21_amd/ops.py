@@ -29,6 +29,25 @@ def _knobs(info):
     return (info.partSize, info.dimWorker, info.warpPerBlock)
 
 
+# ---- layouts: every float [n, W] operand and every incoming gradient passes one of these two before it reaches a binding ------
+# autograd hands a backward whatever layout the graph downstream produced (the gradient of a sum() is an expanded scalar, that
+# of a sum readout has stride(0) == 0, that of a column slice a leading dimension, a product keeps a column-major operand's
+# layout), and forward operands vary the same way (``emb.expand(n, F)``, a column block, ``lin.weight.t()``).
+
+def _laid_out(t):
+    """`t` for a binding that takes a leading dimension: itself when its rows are contiguous and do not overlap (stride(1) == 1,
+    stride(0) >= width: nothing is copied), a contiguous copy otherwise; None stays None."""
+    if t is None or ((t.shape[1] <= 1 or t.stride(1) == 1) and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])):
+        return t
+    return t.contiguous()
+
+
+def _packed(t):
+    """`t` for a binding that takes contiguous tensors only (the reference-shaped entries: SAG, forward / backward and their GIN
+    forms): itself when contiguous, a contiguous copy otherwise; None stays None."""
+    return t if t is None else t.contiguous()
+
+
 def _is_directed(info):
     return bool(getattr(info, "directed", False))
 
@@ -69,7 +88,7 @@ def _block_features(X, block, what):
         raise TypeError(f"{what} on a SampledBlock: float32 features only (got {X.dtype})")
     if X.dim() != 2 or X.shape[0] != block.num_src:
         raise ValueError(f"{what} on a SampledBlock: X must be [num_src = {block.num_src}, F] (got {tuple(X.shape)})")
-    return X if X.shape[1] <= 1 or X.stride(1) == 1 else X.contiguous()
+    return _laid_out(X)
 
 
 def _block_sum(X, graph, num_out_rows):
@@ -82,7 +101,7 @@ def _block_sum_backward(ctx, dY):
     if not ctx.needs_input_grad[0]:
         return None
     block = ctx.block
-    return _block_sum(dY.contiguous(), block.transposed(), block.num_src)
+    return _block_sum(_laid_out(dY), block.transposed(), block.num_src)
 
 
 # ---- features stored in bfloat16 / float16 (libgnna gnna_agg_ld_x16: fp32 accumulation, one rounding of the result) ------
@@ -102,9 +121,7 @@ def _x16_dtype(X):
 def _aggregate_x16(mode, X, graph, partSize, epsilon=1.0, relu=False):
     """mode 0 sag / 1 gcn / 2 gin over 16-bit X -> the same dtype; the degrees stay fp32."""
     _rp, ci, deg, pp, p2n = graph
-    if X.dim() == 2 and X.shape[1] > 1 and X.stride(1) != 1:
-        X = X.contiguous()
-    return GNNA.aggregate_ld(mode, X, ci, deg if mode == 1 else None, float(epsilon), pp, p2n, partSize, None, False, bool(relu))
+    return GNNA.aggregate_ld(mode, _laid_out(X), ci, deg if mode == 1 else None, float(epsilon), pp, p2n, partSize, None, False, bool(relu))
 
 
 class GNNAFunction_X16(Function):
@@ -140,7 +157,6 @@ class GNNAFunction_X16(Function):
         dY = d_output.to(ctx.dtype)
         if ctx.relu:
             dY = dY * (ctx.saved_tensors[2] > 0)
-        dY = dY.contiguous()
         d_input = None
         bgraph = _backward_graph(ctx)
         if ctx.update_first:
@@ -170,7 +186,7 @@ class ScatterAndGather(Function):
         ctx.knobs = _knobs(inputInfo)
         if X.dtype in _X16:
             return _aggregate_x16(0, X, ctx.graph, ctx.knobs[0])
-        return GNNA.SAG(X, *ctx.graph, *ctx.knobs)
+        return GNNA.SAG(_packed(X), *ctx.graph, *ctx.knobs)
 
     @staticmethod
     def backward(ctx, d_output):
@@ -179,7 +195,7 @@ class ScatterAndGather(Function):
         bgraph = _backward_graph(ctx)
         if d_output.dtype in _X16:
             return _aggregate_x16(0, d_output, bgraph, ctx.knobs[0]), None
-        return GNNA.SAG(d_output.contiguous(), *bgraph, *ctx.knobs), None
+        return GNNA.SAG(_packed(d_output), *bgraph, *ctx.knobs), None
 
 
 class GNNAFunction(Function):
@@ -187,6 +203,7 @@ class GNNAFunction(Function):
 
     @staticmethod
     def forward(ctx, X, weight, inputInfo):
+        X, weight = _packed(X), _packed(weight)
         ctx.save_for_backward(X, weight)
         _remember_graph(ctx, inputInfo)
         ctx.knobs = _knobs(inputInfo)
@@ -195,13 +212,14 @@ class GNNAFunction(Function):
     @staticmethod
     def backward(ctx, d_output):
         X, weight = ctx.saved_tensors
-        return _gcn_backward(ctx, d_output.contiguous(), X, weight)
+        return _gcn_backward(ctx, d_output, X, weight)
 
 
 def _gcn_backward(ctx, d_output, X, weight):
     """(d_input, d_weight, None) of a GCN layer from the gradient of its (pre-activation) output: D A^T D dY, then the two
-    dense products."""
+    dense products.  Whatever layout the three arrive in (d_output may be a product that kept a column-major operand's)."""
     bgraph = _backward_graph(ctx)
+    d_output, X, weight = _packed(d_output), _packed(X), _packed(weight)
     if not ctx.needs_input_grad[0]:
         # first layer: the features need no gradient (the reference computes and drops d_input)
         return None, GNNA.backward_weight(d_output, X, *bgraph, *ctx.knobs)[0], None
@@ -238,7 +256,8 @@ class GNNAFunction_GIN(Function):
         _remember_graph(ctx, inputInfo)
         rp, ci, _deg, pp, p2n = ctx.graph
         ctx.knobs, ctx.eplison = _knobs(inputInfo), eplison
-        X_prime, X_agg = GNNA.forward_gin(X, weight, rp, ci, eplison, pp, p2n, *ctx.knobs)
+        weight = _packed(weight)
+        X_prime, X_agg = GNNA.forward_gin(_packed(X), weight, rp, ci, eplison, pp, p2n, *ctx.knobs)
         ctx.save_for_backward(X_agg, weight)
         return X_prime
 
@@ -248,9 +267,9 @@ class GNNAFunction_GIN(Function):
         if not ctx.needs_input_grad[0]:
             # first layer: d_weight = T^T dY needs no aggregation at all; the reference aggregates
             # dY W^T at the input width (F = 602 on Reddit) and drops the result
-            return None, GNNA.xtg(X_agg, d_output.contiguous()), None, None
+            return None, GNNA.xtg(X_agg, _packed(d_output)), None, None
         rp, ci, _deg, pp, p2n = _backward_graph(ctx)
-        d_input, d_weight = GNNA.backward_gin(d_output.contiguous(), X_agg, weight, rp, ci,
+        d_input, d_weight = GNNA.backward_gin(_packed(d_output), X_agg, weight, rp, ci,
                                               ctx.eplison, pp, p2n, *ctx.knobs)
         return d_input, d_weight, None, None
 
@@ -301,7 +320,7 @@ class GNNAFunction_GIN_UpdateFirst(Function):
         rp, ci, _deg, pp, p2n = _backward_graph(ctx)
         if ctx.relu:
             d_output = d_output * (ctx.saved_tensors[2] > 0)
-        G = GNNA.aggregate_gin(d_output.contiguous(), rp, ci, ctx.eplison, pp, p2n, *ctx.knobs)   # eps A^T dY
+        G = GNNA.aggregate_gin(_packed(d_output), rp, ci, ctx.eplison, pp, p2n, *ctx.knobs)   # eps A^T dY
         d_input = torch.mm(G, weight.t()) if ctx.needs_input_grad[0] else None
         return d_input, GNNA.xtg(X, G), None, None, None
 
@@ -378,7 +397,7 @@ def _extreme_forward(op, ctx, X, inputInfo):
         raise TypeError(f"neighbor max / min: float32 features only (got {X.dtype})")
     ci = inputInfo.column_index
     ctx.num_in_rows = X.shape[0]
-    Y, arg = GNNA.aggregate_reduce(op, X, ci, inputInfo.partPtr, inputInfo.part2Node, inputInfo.partSize)
+    Y, arg = GNNA.aggregate_reduce(op, _laid_out(X), ci, inputInfo.partPtr, inputInfo.part2Node, inputInfo.partSize)
     ctx.save_for_backward(arg, ci)
     return Y
 
@@ -388,8 +407,8 @@ def _extreme_backward(ctx, dY):
     if ctx.block is not None:
         if not ctx.needs_input_grad[0]:
             return None, None
-        return _lib.scatter_arg_ld(dY.contiguous(), arg, ci, ctx.num_in_rows), None
-    return GNNA.scatter_arg(dY.contiguous(), arg, ci, ctx.num_in_rows), None
+        return _lib.scatter_arg_ld(_laid_out(dY), arg, ci, ctx.num_in_rows), None
+    return GNNA.scatter_arg(_laid_out(dY), arg, ci, ctx.num_in_rows), None
 
 
 class NeighborMax(Function):
@@ -433,14 +452,14 @@ class NeighborMean(Function):
         ctx.knobs = _knobs(inputInfo)
         inv = inputInfo.inv_row_counts()
         ctx.save_for_backward(inv)
-        return GNNA.SAG(X.contiguous(), *ctx.graph, *ctx.knobs).mul_(inv.unsqueeze(1))
+        return GNNA.SAG(_packed(X), *ctx.graph, *ctx.knobs).mul_(inv.unsqueeze(1))
 
     @staticmethod
     def backward(ctx, dY):
         inv, = ctx.saved_tensors
         if ctx.block is not None:
             return _block_sum_backward(ctx, dY * inv.unsqueeze(1)), None
-        return GNNA.SAG(dY * inv.unsqueeze(1), *_backward_graph(ctx), *ctx.knobs), None
+        return GNNA.SAG(_packed(dY * inv.unsqueeze(1)), *_backward_graph(ctx), *ctx.knobs), None
 
 
 class SAGEConv(Module):
@@ -532,7 +551,7 @@ class NeighborStats(Function):
         else:
             _remember_graph(ctx, inputInfo)
             ctx.knobs = _knobs(inputInfo)
-            X = X if X.dim() == 2 and (X.shape[1] <= 1 or X.stride(1) == 1) else X.contiguous()
+            X = _laid_out(X)
             n_out = X.shape[0]
         need = {k for w in want for k in _STAT_NEEDS[w]}
         ci = inputInfo.column_index
@@ -566,13 +585,13 @@ class NeighborStats(Function):
                 if g_mean is not None:
                     ab[:, :F].addcmul_(g_mean, inv)
             if ctx.block is not None:
-                T = _block_sum(ab, ctx.block.transposed(), ctx.block.num_src)
+                T = _block_sum(_laid_out(ab), ctx.block.transposed(), ctx.block.num_src)
             else:
-                T = GNNA.SAG(ab, *_backward_graph(ctx), *ctx.knobs)
+                T = GNNA.SAG(_packed(ab), *_backward_graph(ctx), *ctx.knobs)
             dX = T if g_std is None else torch.addcmul(T[:, :F], X, T[:, F:])
         for g, arg in ((g_max, amx), (g_min, amn)):
             if g is not None:
-                dX = _lib.scatter_arg_ld(g.contiguous(), arg, ci, X.shape[0], out=dX, accumulate=dX is not None)
+                dX = _lib.scatter_arg_ld(_laid_out(g), arg, ci, X.shape[0], out=dX, accumulate=dX is not None)
         return dX, None, None, None
 
 
@@ -686,7 +705,7 @@ class NeighborSoftmax(Function):
             X = _block_features(X, inputInfo, "NeighborSoftmax")
         else:
             _remember_graph(ctx, inputInfo)
-            X = X if X.dim() == 2 and (X.shape[1] <= 1 or X.stride(1) == 1) else X.contiguous()
+            X = _laid_out(X)
         t = _temp_vector(temp, X.shape[1], X.device, "NeighborSoftmax")
         ctx.temp_shape = temp.shape
         Y, lse, sq = GNNA.aggregate_softmax(X, t, inputInfo.row_pointers, inputInfo.column_index, bool(ctx.needs_input_grad[1]))
@@ -700,9 +719,7 @@ class NeighborSoftmax(Function):
         X, t, Y, lse, sq = ctx.saved_tensors
         dX = dt = None
         if ctx.needs_input_grad[0]:
-            # (the gradient of a sum() arrives as an expanded scalar: the library takes rows that are laid out)
-            if (dY.shape[1] > 1 and dY.stride(1) != 1) or (dY.shape[0] > 1 and dY.stride(0) < dY.shape[1]):
-                dY = dY.contiguous()
+            dY = _laid_out(dY)
             if ctx.block is not None:
                 bgraph = ctx.block.transposed()
                 rp, ci = bgraph.row_pointers, bgraph.column_index
@@ -827,7 +844,7 @@ def _typed_features(X, rel, what):
                         f"(got {X.dtype}{', inside torch.autocast' if X.dtype == torch.float32 else ''})")
     if X.dim() != 2 or X.shape[0] != rel.num_src:
         raise ValueError(f"{what}: X must be [{rel.num_src}, F] (got {tuple(X.shape)})")
-    return X if X.shape[1] <= 1 or X.stride(1) == 1 else X.contiguous()
+    return _laid_out(X)
 
 
 class TypedAggregate(Function):
@@ -840,7 +857,7 @@ class TypedAggregate(Function):
     @staticmethod
     def forward(ctx, X, coef, rel):
         X = _typed_features(X, rel, "TypedAggregate")
-        coef = coef.detach().float().contiguous()
+        coef = _packed(coef.detach().float())
         ctx.rel = rel
         ctx.save_for_backward(X, coef)
         return rel.expand(X, coef)
@@ -848,8 +865,7 @@ class TypedAggregate(Function):
     @staticmethod
     def backward(ctx, dT):
         X, coef = ctx.saved_tensors
-        if dT.dim() == 2 and dT.shape[1] > 1 and dT.stride(1) != 1:
-            dT = dT.contiguous()
+        dT = _laid_out(dT)
         dX = ctx.rel.contract(dT, coef) if ctx.needs_input_grad[0] else None
         dcoef = ctx.rel.coef_grad(X, dT) if ctx.needs_input_grad[1] else None
         return dX, dcoef, None
@@ -940,7 +956,7 @@ class EdgeWeightedAggregate(Function):
         assert X.dim() == 2 and X.shape[1] % heads == 0, "X must be [num_nodes, heads * F]"
         assert wh.shape[1] == inputInfo.column_index.numel(), "w must be indexed like column_index"
         ctx.info, ctx.w_shape = inputInfo, w.shape
-        wh = wh.contiguous()
+        X, wh = _laid_out(X), _packed(wh)
         ctx.save_for_backward(X, wh)
         return _edge_aggregate(X, wh, inputInfo)
 
@@ -948,7 +964,7 @@ class EdgeWeightedAggregate(Function):
     def backward(ctx, dY):
         X, wh = ctx.saved_tensors
         info = ctx.info
-        dY = dY.contiguous()
+        dY = _laid_out(dY)
         heads, F = wh.shape[0], X.shape[1] // wh.shape[0]
         dX = dw = None
         if ctx.needs_input_grad[0]:
@@ -981,14 +997,14 @@ class EdgeSoftmax(Function):
 
     @staticmethod
     def forward(ctx, scores, row_pointers):
-        p = GNNA.edge_softmax(scores.contiguous(), row_pointers)
+        p = GNNA.edge_softmax(_packed(scores), row_pointers)
         ctx.save_for_backward(p, row_pointers)
         return p
 
     @staticmethod
     def backward(ctx, dp):
         p, rp = ctx.saved_tensors
-        return GNNA.edge_softmax_backward(p, dp.contiguous(), rp), None
+        return GNNA.edge_softmax_backward(p, _packed(dp), rp), None
 
 
 class GATAttention(Function):
@@ -1031,7 +1047,7 @@ class GATAttention(Function):
                                  f"[num_src = {info.num_src}, heads] (got {tuple(el.shape)} and {tuple(er.shape)})")
             if el.dtype != torch.float32 or er.dtype != torch.float32:
                 raise TypeError(f"GATAttention on a SampledBlock: float32 scores only (got {el.dtype}, {er.dtype})")
-        el, er = el.contiguous(), er.contiguous()
+        el, er = _packed(el), _packed(er)
         graph = (info.row_pointers, info.column_index, info.partPtr, info.part2Node, info.partSize, float(negative_slope))
         if attn_drop > 0.0:
             Y, lse = GNNA.gat_forward_drop(H, el, er, *graph, attn_drop, rng_seed)
@@ -1094,7 +1110,7 @@ class GATEdgeAttention(Function):
                              f"(got {tuple(ee.shape)})")
         if any(t.dtype != torch.float32 for t in (H, el, er, ee)):
             raise TypeError(f"GATEdgeAttention: float32 only (got {H.dtype}, {el.dtype}, {er.dtype}, {ee.dtype})")
-        el, er, ee = el.contiguous(), er.contiguous(), ee.contiguous()
+        el, er, ee = _packed(el), _packed(er), _packed(ee)
         graph = (info.row_pointers, info.column_index, info.partPtr, info.part2Node, info.partSize, float(negative_slope))
         Y, lse = GNNA.gat_edge_forward(H, el, er, ee, *graph, attn_drop, rng_seed)
         ctx.info, ctx.negative_slope, ctx.attn_drop, ctx.rng_seed = info, float(negative_slope), attn_drop, rng_seed
@@ -1299,7 +1315,7 @@ class GATv2Attention(Function):
             if Hd.shape[0] != info.num_dst:
                 raise ValueError(f"GATv2Attention on a SampledBlock: Hd must be [num_dst = {info.num_dst}, heads * F] "
                                  f"(got {tuple(Hd.shape)})")
-        att = att.contiguous()
+        att = _packed(att)
         Y, lse = GNNA.gatv2_forward(Hs, Hd, att, info.row_pointers, info.column_index, info.partPtr, info.part2Node, info.partSize,
                                     float(negative_slope), attn_drop, rng_seed)
         ctx.info, ctx.negative_slope, ctx.attn_drop, ctx.rng_seed = info, float(negative_slope), attn_drop, rng_seed
@@ -1551,13 +1567,6 @@ def _graph_pointers_of(batch, device):
     return gp.to(device).contiguous()
 
 
-def _laid_out(t):
-    """`t` with rows the library can stride over (the gradient of a sum() arrives as an expanded scalar)."""
-    if t is None or ((t.shape[1] <= 1 or t.stride(1) == 1) and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])):
-        return t
-    return t.contiguous()
-
-
 class SegmentPool(Function):
     """``SegmentPool.apply(X, graph_pointers, want_sum, want_max, want_min, mean) -> (sum, max, min)``: the statistics over the rows
     [graph_pointers[g], graph_pointers[g + 1]) of X for every graph g, each [G, F], from ONE read of X (libgnna
@@ -1801,7 +1810,7 @@ class SelectRows(Function):
                 raise ValueError(f"SelectRows: scale must hold one factor per row of X ({X.shape[0]}; got {tuple(scale.shape)})")
         ctx.scale_shape = None if scale is None else tuple(scale.shape)
         if scale is not None:
-            scale = scale.reshape(-1).contiguous()
+            scale = _packed(scale.reshape(-1))
         ctx.set_materialize_grads(False)
         Xl = _laid_out(X)
         need_x, need_scale = ctx.needs_input_grad[0], scale is not None and ctx.needs_input_grad[1]

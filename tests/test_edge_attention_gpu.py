@@ -10,16 +10,12 @@ import pytest
 import torch
 
 from gnnadvisor_osdi21_amd import _lib, graph, load_extension
+from edge_softmax_ref import SOFTMAX_RTOL, _rows_of, _softmax64
 from util import assert_close_f64
 
 pytestmark = pytest.mark.gpu
 GNNA = load_extension()
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _rows_of(rp):
-    rp = rp.long()
-    return torch.repeat_interleave(torch.arange(rp.numel() - 1, device=rp.device), rp[1:] - rp[:-1])
 
 
 def _agg64(X, w, rp, ci):
@@ -196,19 +192,6 @@ def test_weighted_call_in_a_captured_graph():
 
 
 # ---- edge softmax -------------------------------------------------------------------------------------------------------
-SOFTMAX_RTOL = 1e-5     # of max(1, |ref|) for the probabilities, of max(1, sum of |terms|) for the gradient (test_bindings_agree_gpu.py too)
-
-def _softmax64(s, rp):
-    """fp64 segment softmax of head-major scores s [H, nnz] over the rows of rp."""
-    rows = _rows_of(rp.to(s.device))
-    n = rp.numel() - 1
-    s = s.double()
-    m = torch.full((s.shape[0], n), -float("inf"), dtype=torch.float64, device=s.device)
-    m = m.scatter_reduce(1, rows.expand_as(s), s, reduce="amax")
-    ex = torch.exp(s - m[:, rows])
-    den = torch.zeros(s.shape[0], n, dtype=torch.float64, device=s.device).index_add_(1, rows, ex)
-    return ex / den[:, rows]
-
 
 def _softmax_graph(seed, hub=120000):
     """Empty rows, degree-1 rows, short and medium rows and one hub row of `hub` edges (unsymmetric: not needed here)."""

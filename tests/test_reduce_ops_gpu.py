@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from gnnadvisor_osdi21_amd import _lib
+from reduce_ref import _agg64, _no_ties, _rows_of
 from util import assert_close_f64, make_case
 
 pytestmark = pytest.mark.gpu
@@ -27,28 +28,6 @@ class _Info:
         self.partPtr, self.part2Node = [t.cuda() for t in _lib.build_part(partSize, row_pointers.cpu())]
         self._edge_arrays = lambda: inputProperty._edge_arrays(self)
         self.inv_row_counts = lambda: inputProperty.inv_row_counts(self)
-
-
-def _rows_of(rp):
-    rp = rp.long()
-    return torch.repeat_interleave(torch.arange(rp.numel() - 1), rp[1:] - rp[:-1])
-
-
-def _agg64(X, rp, ci, how):
-    """fp64 reference on the CPU: scatter_reduce over X[column_index] with include_self=False; rows without edges give 0."""
-    rows = _rows_of(rp)
-    n = rp.numel() - 1
-    src = X[ci.long()]
-    out = torch.zeros(n, X.shape[1], dtype=X.dtype)
-    return out.scatter_reduce(0, rows[:, None].expand_as(src), src, reduce=how, include_self=False)
-
-
-def _no_ties(X, rp, ci, how):
-    """No row of the reference has its extreme twice in a column."""
-    ext = _agg64(X, rp, ci, how)
-    rows = _rows_of(rp)
-    hits = torch.zeros_like(ext).index_add_(0, rows, (X[ci.long()] == ext[rows]).to(X.dtype))
-    return bool((hits <= 1).all())
 
 
 @pytest.mark.parametrize("d", [16, 64])

@@ -15,6 +15,7 @@ from gnnadvisor_osdi21_amd import _lib, graph, ops
 from gnnadvisor_osdi21_amd.decider import inputProperty
 from gnnadvisor_osdi21_amd.relational import RelationalGraph, synthetic_edge_types
 from gnnadvisor_osdi21_amd.sampling import NeighborSampler
+from rgcn_ref import dense_expand, dense_layer, dense_relations
 from util import assert_close_f64
 
 pytestmark = pytest.mark.gpu
@@ -50,25 +51,6 @@ def numpy_norm(rp, ety, R):
         t = ety[rp[i]: rp[i + 1]]
         out[rp[i]: rp[i + 1]] = 1.0 / np.bincount(t, minlength=R)[t]
     return out
-
-
-def dense_relations(rp, ci, ety, nrm, R, n_dst, n_src):
-    """float64 [R, n_dst, n_src] on the GPU."""
-    rp, ci, ety = (torch.as_tensor(a).cpu().long() for a in (rp, ci, ety))
-    rows = torch.repeat_interleave(torch.arange(n_dst), rp[1:] - rp[:-1])
-    w = torch.ones(len(ci), dtype=torch.float64) if nrm is None else torch.as_tensor(nrm).cpu().double()
-    A = torch.zeros(R, n_dst, n_src, dtype=torch.float64)
-    A.index_put_((ety, rows, ci), w, accumulate=True)
-    return A.cuda()
-
-
-def dense_expand(A, X, coef):
-    AX = torch.einsum("rij,jf->rif", A, X)
-    return torch.einsum("rb,rif->ibf", coef, AX).reshape(A.shape[1], -1)
-
-
-def dense_layer(A, X, coef, V, W_self, bias):
-    return dense_expand(A, X, coef) @ V.reshape(-1, V.shape[2]) + X[:A.shape[1]] @ W_self + bias
 
 
 def grads_of(fn, tensors, wgt, needs=None):
