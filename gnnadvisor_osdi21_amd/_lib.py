@@ -232,6 +232,27 @@ def _check(rc: int) -> None:
         raise GnnaError(f"libgnna error {rc}: {load().gnna_last_error().decode()}")
 
 
+def _check_counts(rc: int, counts) -> tuple:
+    """The tail of the entries that report three int64 counts: the counts as a tuple, or the GnnaError of `rc` carrying them as
+    ``.counts`` (what a capacity that was too small has to be)."""
+    got = tuple(int(c) for c in counts)
+    if rc != GNNA_OK:
+        err = GnnaError(f"libgnna error {rc}: {load().gnna_last_error().decode()}")
+        err.counts = got
+        raise err
+    return got
+
+
+def _degree_sum(rp: torch.Tensor, ids: torch.Tensor) -> int:
+    """The sum of the degrees of the rows `ids` of the row pointers `rp`, ids clamped to the graph (ids outside it are the
+    library's to report) and a row whose pointers decrease counted as empty: the edges a list of rows can give at the most."""
+    n = rp.numel() - 1
+    if n <= 0 or ids.numel() == 0:
+        return 0
+    rows = ids.long().clamp(0, n - 1)
+    return int((rp[rows + 1] - rp[rows]).clamp(min=0).sum())
+
+
 def _ptr(t: torch.Tensor | None) -> int | None:
     return None if t is None else t.data_ptr()
 
@@ -1577,15 +1598,7 @@ def sample_neighbors(row_pointers, column_index, seeds, fanout, rng_seed, partSi
         raise GnnaError(f"partSize must be positive (got {partSize})")
     dev = rp.device
     with torch.cuda.device(dev):
-        if fanout >= 1:
-            edge_cap = S * fanout
-        elif S > 0:
-            # every neighbour: the seeds' degrees (ids outside the graph are the library's to report)
-            rows = sd.long().clamp(0, max(n - 1, 0))
-            edge_cap = int((rp[rows + 1] - rp[rows]).clamp(min=0).sum()) if n > 0 else 0
-        else:
-            edge_cap = 0
-        edge_cap = min(edge_cap, ci.numel())
+        edge_cap = min(S * fanout if fanout >= 1 else _degree_sum(rp, sd), ci.numel())      # fanout <= 0: every neighbour
         src_cap = min(S + edge_cap, max(n, S))
         if edge_capacity is not None:
             edge_cap = int(edge_capacity)
@@ -1603,11 +1616,7 @@ def sample_neighbors(row_pointers, column_index, seeds, fanout, rng_seed, partSi
         rc = load().gnna_sample_neighbors_i32(rp.data_ptr(), _ptr(ci), n, _ptr(sd), S, fanout, rng_seed,
                                               int(partSize) if want_part else 0, blk_rp.data_ptr(), _ptr(blk_ci), _ptr(eid),
                                               _ptr(src), _ptr(pp), _ptr(p2n), edge_cap, src_cap, counts, _stream(dev))
-    if rc != GNNA_OK:
-        err = GnnaError(f"libgnna error {rc}: {load().gnna_last_error().decode()}")
-        err.counts = tuple(int(c) for c in counts)
-        raise err
-    nnz, num_src, P = int(counts[0]), int(counts[1]), int(counts[2])
+    nnz, num_src, P = _check_counts(rc, counts)
     return {"row_pointers": blk_rp, "column_index": blk_ci[:nnz], "edge_ids": eid[:nnz] if want_edge_ids else None,
             "src_nodes": src[:num_src], "partPtr": pp[:P + 1] if want_part else None,
             "part2Node": p2n[:P] if want_part else None, "num_dst": S, "num_src": num_src}
@@ -1664,14 +1673,7 @@ def induced_subgraph(row_pointers, column_index, nodes, partSize=None, want_edge
     dev = rp.device
     with torch.cuda.device(dev):
         node_cap = min(K, n) if node_capacity is None else int(node_capacity)
-        if edge_capacity is not None:
-            edge_cap = int(edge_capacity)
-        elif K > 0 and n > 0:
-            # the degree sum over the list (ids outside the graph are the library's to report)
-            rows = nd.long().clamp(0, n - 1)
-            edge_cap = min(nnz, int((rp[rows + 1] - rp[rows]).clamp(min=0).sum()))
-        else:
-            edge_cap = 0
+        edge_cap = min(nnz, _degree_sum(rp, nd)) if edge_capacity is None else int(edge_capacity)
         if node_cap < 0 or edge_cap < 0:
             raise GnnaError("capacities must not be negative")
         i32 = dict(dtype=torch.int32, device=dev)
@@ -1686,11 +1688,7 @@ def induced_subgraph(row_pointers, column_index, nodes, partSize=None, want_edge
         rc = load().gnna_induced_subgraph_i32(rp.data_ptr(), ptr(ci), n, nnz, ptr(nd), K, int(partSize) if want_part else 0,
                                               ptr(sub_nodes), ptr(new_id), sub_rp.data_ptr(), ptr(sub_ci), ptr(eid), _ptr(pp),
                                               ptr(p2n), node_cap, edge_cap, counts, _stream(dev))
-    if rc != GNNA_OK:
-        err = GnnaError(f"libgnna error {rc}: {load().gnna_last_error().decode()}")
-        err.counts = tuple(int(c) for c in counts)
-        raise err
-    m, e, P = int(counts[0]), int(counts[1]), int(counts[2])
+    m, e, P = _check_counts(rc, counts)
     return {"row_pointers": sub_rp[:m + 1], "column_index": sub_ci[:e], "edge_ids": eid[:e] if want_edge_ids else None,
             "nodes": sub_nodes[:m], "new_id": new_id, "partPtr": pp[:P + 1] if want_part else None,
             "part2Node": p2n[:P] if want_part else None, "num_nodes": m}
@@ -1759,11 +1757,7 @@ def segment_topk(score, graph_pointers, ratio=None, k=None, row_pointers=None, c
                                           _ptr(eid) if eid is not None and edge_cap > 0 else None, _ptr(pp),
                                           _ptr(p2n) if want_part and part_cap > 0 else None, row_cap, edge_cap, part_cap, counts,
                                           _stream(dev))
-    if rc != GNNA_OK:
-        err = GnnaError(f"libgnna error {rc}: {load().gnna_last_error().decode()}")
-        err.counts = tuple(int(c) for c in counts)
-        raise err
-    rows, edges, P = int(counts[0]), int(counts[1]), int(counts[2])
+    rows, edges, P = _check_counts(rc, counts)
     return {"new_id": new_id, "perm": perm[:rows], "graph_pointers": new_gp, "num_rows": rows,
             "row_pointers": new_rp[:rows + 1] if csr else None, "column_index": new_ci[:edges] if csr else None,
             "edge_ids": eid[:edges] if eid is not None else None, "partPtr": pp[:P + 1] if want_part else None,

@@ -32,7 +32,7 @@ LIB_SOURCES = [os.path.join(CSRC, f) for f in ("gnna_agg.hip", "gnna_stream.hip"
 PUBLIC_HEADERS = ("gnna.h", "gnna_ext.h", "gnna_gatv2.h", "gnna_dotattn.h", "gnna_gat_edge.h", "gnna_stats.h", "gnna_softagg.h",
                   "gnna_pool.h", "gnna_attnpool.h", "gnna_topk.h")
 INTERNAL_HEADERS = ("gnna_internal.h", "gnna_device.h", "gnna_launch.h", "gnna_gat_common.h", "gnna_keys.h", "gnna_segments.h",
-                    "gnna_segnorm.h", "gnna_walk.h")     # gnna_segnorm.h, gnna_walk.h: staged public headers (their own first paragraphs), bound through _lib.STAGED / _lib.STAGED_NEXT
+                    "gnna_parts.h", "gnna_segnorm.h", "gnna_walk.h")     # gnna_segnorm.h, gnna_walk.h: staged public headers (their own first paragraphs), bound through _lib.STAGED / _lib.STAGED_NEXT
 _PUBLIC = [os.path.join(INCLUDE, f) for f in PUBLIC_HEADERS]
 LIB_DEPS = LIB_SOURCES + [os.path.join(CSRC, f) for f in INTERNAL_HEADERS] + _PUBLIC
 EXT_SOURCES = [os.path.join(CSRC, "gnna_torch.cpp")]

@@ -435,8 +435,6 @@ struct DenseTemp {
     ~DenseTemp() { if (ptr) { (void)hipFree(ptr); count_event(CTR_LAUNCH_FREES); } }
 };
 
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 }  // namespace
 
 int dense_block_mode()

@@ -106,6 +106,15 @@ int get_device_state(DeviceState **out);
 // Scratch buffer `slot` of `stream` for an eager call (grow-only, shared by the eager calls on that stream), or -- while `stream`
 // is being captured -- of that capture on that stream (allocated at capture time, never freed, never handed to another call).
 int get_workspace(DeviceState *ds, hipStream_t stream, int slot, size_t bytes, void **out);
+// The layout of a call's scratch buffer: add() declares a region of b bytes ONCE and gives its 256-byte aligned offset, in the
+// order of the calls; `bytes` is what get_workspace is asked for, at<T>(base, offset) the region's pointer.
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+struct Carver {
+    size_t bytes = 0;
+    size_t add(size_t b) { const size_t offset = bytes; bytes += align256(b); return offset; }
+    template <class T>
+    static T *at(void *base, size_t offset) { return reinterpret_cast<T *>(static_cast<char *>(base) + offset); }
+};
 // Fresh non-zero sequence number of an aggregation call on `stream` and its slot among the flags (the call block's index).
 int32_t next_call_seq(DeviceState *ds, hipStream_t stream, int32_t **flag_slot);
 // Index of the call block (see kCallBlocks) of a call with sequence number `seq` on `stream`.
@@ -312,13 +321,25 @@ int launch_zero_fill(DeviceState *ds, hipStream_t stream, float *out, int64_t ro
 // not fuse it.  Enqueues only: the caller's launch_ok reports a failed launch in the entry's own words (gnna_agg.hip).
 void launch_relu_rows(DeviceState *ds, hipStream_t stream, float *out, int64_t rows, int dim, int64_t ld);
 
-// ---- device structure builders (gnna_transpose.hip; also used by gnna_sample.hip) ------------------------------------
+// ---- device structure builders: what gnna_transpose.hip, gnna_sample.hip, gnna_topk.hip and gnna_walk.hip share ---------
+// (defined in gnna_transpose.hip; the partition rule itself -- groups per row, owner search, fill -- is gnna_parts.h)
 // Tiles of the exclusive scan over n ints: the ints of `partial` that launch_exclusive_scan needs.
 int64_t scan_tiles(int64_t n);
 // data[i] <- sum of data[0 .. i) for i < n, in place (int32 counts whose total fits int32); three launches, no read-back.
 int launch_exclusive_scan(hipStream_t stream, int32_t *data, int64_t n, int32_t *partial);
 // GNNA_ERR_UNSUPPORTED when `stream` is being captured (the prepare-time calls read a count back).
 int refuse_capture(const char *what, hipStream_t stream);
+// words[0 .. n) = 0: one launch (a call's record and the scratch that is cleared together with it).
+void launch_clear_words(DeviceState *ds, hipStream_t stream, int32_t *words, int64_t n);
+// count[i] = the neighbor-groups of row i of `rp` for i < rows, 0 for rows <= i <= n (the scan makes the last one the total):
+// one launch over n + 1 items.  rows = *rows_word, read on the device, or n when rows_word is null.
+void launch_part_count(DeviceState *ds, hipStream_t stream, const int32_t *rp, int64_t n, const long long *rows_word, int partSize,
+                       int32_t *count);
+// The tail of a call that reports through a record of `words` int64: "<what>: launch: ..." for a launch that failed, else
+// host[0 .. words) = rec by one copy and one synchronisation ("<what>: reading the counts back: ...").  The words are the entry's.
+int read_record(const char *what, hipStream_t stream, const long long *rec, long long *host, int words);
+// Lanes per row (a power of two, 4 .. 64) from the edges an average row has: the hint of `column_index`, else fallback_avg.
+int lanes_per_row(const int32_t *column_index, int64_t fallback_avg);
 
 // ---- optional per-call kernel timing (gnna_profile_begin/end) ---------------------------------------
 // Returns the index of this call in the active profile (-1 when not profiling).

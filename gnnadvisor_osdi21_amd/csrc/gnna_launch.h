@@ -86,6 +86,14 @@ inline unsigned elementwise_grid(int64_t items, int num_cus, int blocks_per_cu)
     return (unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)num_cus * blocks_per_cu));
 }
 
+// the smallest power of two >= x (1 for x <= 1)
+inline int pow2_at_least(int64_t x)
+{
+    int p = 1;
+    while (p < x) p <<= 1;
+    return p;
+}
+
 // a row stride that is narrower than the row or does not fit the kernels' 32-bit element offsets
 inline bool bad_ld(int64_t ld, int64_t width) { return ld < width || ld >= ((int64_t)1 << 29); }
 

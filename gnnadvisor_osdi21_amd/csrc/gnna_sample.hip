@@ -5,6 +5,7 @@
 //
 // The rule (include/gnna.h has it word for word): a row with more than `fanout` candidate positions keeps the `fanout`
 // positions whose key = splitmix64(rng_seed, position) is smallest.  Keys are COMPUTED from positions, never loaded or stored.
+//   clear_kernel        (gnna_transpose.hip, like every kernel named so below) the record, seedpos[] and mark[]
 //   seed_kernel         seedpos[seeds[i]] = i + 1 (plain stores: of two equal seeds one loses, which the sampling kernels see),
 //                       blk_row_pointers[i] = min(degree, fanout)
 //   scan_* kernels      (gnna_transpose.hip) exclusive scan of those counts = where every row's picks start
@@ -15,7 +16,8 @@
 //   sample_long_kernel  the same for rows beyond kLongRow positions, a whole block per row (counts through LDS)
 //   scan_* kernels      exclusive scan of mark[] = the rank of every non-seed source in increasing global id
 //   relabel_kernel      src_nodes, global -> local ids in place, counts
-//   part_* kernels      the partition of blk_row_pointers, as gnna_build_part_i32 writes it; its size stays on the device
+//   part_count_kernel   (gnna_transpose.hip), the scan, part_fill_kernel: the partition of blk_row_pointers by the one rule of
+//                       gnna_parts.h, as gnna_build_part_i32 writes it; its size stays on the device
 // The splitmix64 finaliser is a bijection and z = rng_seed + odd * (e + 1) is injective in e, so two positions never share a
 // key: the tie rule of the contract (the smaller position wins) never has to act, and "key <= the fanout-th smallest key" picks
 // exactly `fanout` positions.  No position is handed out by an atomic; the result is the same bits for every launch shape.
@@ -23,6 +25,7 @@
 
 #include "gnna_device.h"
 #include "gnna_internal.h"
+#include "gnna_parts.h"
 
 namespace gnna {
 namespace {
@@ -31,12 +34,6 @@ constexpr int kSlotSample = 8;        // library scratch: the record, seedpos[N]
 constexpr int kLongRow = 2048;        // rows with more candidate positions get a whole block
 // the record that is read back: 8 x int64
 enum { REC_NNZ = 0, REC_SRC = 1, REC_PARTS = 2, REC_BAD_SEED = 3, REC_DUP_SEED = 4, REC_BAD_COLUMN = 5, REC_WORDS = 8 };
-
-__global__ void __launch_bounds__(kBlock)
-clear_kernel(int32_t *__restrict__ words, int64_t n)
-{
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) words[i] = 0;
-}
 
 // candidate positions of a seed row: [*start, *start + d), d = 0 for a row whose pointers decrease
 __device__ __forceinline__ int row_extent(const int32_t *__restrict__ rp, int32_t r, int64_t *start)
@@ -283,44 +280,15 @@ relabel_kernel(const int32_t *__restrict__ seeds, int64_t num_seeds, int64_t num
     }
 }
 
-// count[i] = groups of block row i; count[num_seeds] = 0, which the scan turns into the total
+// The partition of the block's row pointers (gnna_parts.h); the number of groups is read on the device.
 __global__ void __launch_bounds__(kBlock)
-part_count_kernel(const int32_t *__restrict__ blk_rp, int64_t num_seeds, int partSize, int32_t *__restrict__ count)
+part_fill_kernel(const CsrRows rows, const int32_t *__restrict__ first_part, int partSize, int64_t capacity,
+                 int32_t *__restrict__ pp, int32_t *__restrict__ p2n, long long *__restrict__ rec)
 {
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i <= num_seeds; i += (int64_t)gridDim.x * kBlock) {
-        const int64_t deg = i < num_seeds ? (int64_t)blk_rp[i + 1] - (int64_t)blk_rp[i] : 0;
-        count[i] = deg > 0 ? (int32_t)((deg + partSize - 1) / partSize) : 0;
-    }
-}
-
-// As part_fill_kernel of gnna_transpose.hip, with the number of groups read on the device (first_part[num_seeds]).
-__global__ void __launch_bounds__(kBlock)
-part_fill_kernel(const int32_t *__restrict__ blk_rp, const int32_t *__restrict__ first_part, int64_t num_seeds, int partSize,
-                 int64_t capacity, int32_t *__restrict__ pp, int32_t *__restrict__ p2n, long long *__restrict__ rec)
-{
-    const int64_t num_parts = first_part[num_seeds];
-    const int64_t first = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (first == 0) rec[REC_PARTS] = num_parts;
+    const int64_t num_parts = first_part[rows.n];
+    if (blockIdx.x == 0 && threadIdx.x == 0) rec[REC_PARTS] = num_parts;
     if (num_parts > capacity) return;                         // (then the edges do not fit either: the call fails)
-    for (int64_t p = first; p <= num_parts; p += (int64_t)gridDim.x * kBlock) {
-        if (p == num_parts) { pp[p] = num_seeds > 0 ? blk_rp[num_seeds] : 0; continue; }
-        int64_t lo = 0, hi = num_seeds - 1;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi + 1) >> 1;
-            if (first_part[mid] <= p) lo = mid; else hi = mid - 1;
-        }
-        pp[p] = (int32_t)((int64_t)blk_rp[lo] + (p - first_part[lo]) * partSize);
-        p2n[p] = (int32_t)lo;
-    }
-}
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-int pow2_at_least(int64_t x)
-{
-    int p = 1;
-    while (p < x) p <<= 1;
-    return p;
+    fill_parts(rows, first_part, partSize, num_parts, pp, p2n);
 }
 
 }  // namespace
@@ -358,35 +326,27 @@ int gnna_sample_neighbors_i32(const int32_t *row_pointers, const int32_t *column
     src_capacity = std::min<int64_t>(src_capacity, 0x7fffffffLL);
 
     // scratch: [record][seedpos: N][mark: N + 1] (cleared together) [scan partials][parts before every block row: S + 1]
-    const size_t rec_bytes = align256(REC_WORDS * sizeof(long long));
-    const size_t pos_bytes = align256((size_t)num_nodes * 4), mark_bytes = align256((size_t)(num_nodes + 1) * 4);
-    const size_t partial_bytes = align256((size_t)scan_tiles(std::max(num_nodes, num_seeds) + 1) * 4);
-    const size_t parts_bytes = align256((size_t)(num_seeds + 1) * 4);
+    Carver c;
+    const size_t o_rec = c.add(REC_WORDS * sizeof(long long)), o_pos = c.add((size_t)num_nodes * 4);
+    const size_t o_mark = c.add((size_t)(num_nodes + 1) * 4), cleared_bytes = c.bytes;
+    const size_t o_partial = c.add((size_t)scan_tiles(std::max(num_nodes, num_seeds) + 1) * 4);
+    const size_t o_parts = c.add((size_t)(num_seeds + 1) * 4);
     void *ws = nullptr;
-    rc = get_workspace(ds, stream, kSlotSample, rec_bytes + pos_bytes + mark_bytes + partial_bytes + parts_bytes, &ws);
+    rc = get_workspace(ds, stream, kSlotSample, c.bytes, &ws);
     if (rc != GNNA_OK) return rc;
-    char *at = static_cast<char *>(ws);
-    long long *rec = reinterpret_cast<long long *>(at); at += rec_bytes;
-    int32_t *seedpos = reinterpret_cast<int32_t *>(at); at += pos_bytes;
-    int32_t *mark = reinterpret_cast<int32_t *>(at); at += mark_bytes;
-    int32_t *partial = reinterpret_cast<int32_t *>(at); at += partial_bytes;
-    int32_t *first_part = reinterpret_cast<int32_t *>(at);
+    long long *rec = Carver::at<long long>(ws, o_rec);
+    int32_t *seedpos = Carver::at<int32_t>(ws, o_pos), *mark = Carver::at<int32_t>(ws, o_mark);
+    int32_t *partial = Carver::at<int32_t>(ws, o_partial), *first_part = Carver::at<int32_t>(ws, o_parts);
 
     const dim3 block(kBlock);
-    const int64_t clear_words = (int64_t)((rec_bytes + pos_bytes + mark_bytes) / 4);
-    hipLaunchKernelGGL(clear_kernel, dim3(elementwise_grid(clear_words, ds->num_cus, 16)), block, 0, stream,
-                       reinterpret_cast<int32_t *>(ws), clear_words);
+    launch_clear_words(ds, stream, static_cast<int32_t *>(ws), (int64_t)(cleared_bytes / 4));
     hipLaunchKernelGGL(seed_kernel, dim3(elementwise_grid(num_seeds + 1, ds->num_cus, 16)), block, 0, stream, row_pointers,
                        (uint32_t)num_nodes, seeds, num_seeds, fanout, seedpos, blk_row_pointers, rec);
     rc = launch_exclusive_scan(stream, blk_row_pointers, num_seeds + 1, partial);
     if (rc != GNNA_OK) return rc;
     if (num_seeds > 0) {
         // lanes per row from the edges an average row has: the graph's hint, else what the fanout suggests
-        gnna_tuning tune;
-        gnna_get_tuning(&tune);
-        apply_graph_hints(column_index, 0, &tune);
-        const int64_t avg = tune.avg_degree > 0 ? tune.avg_degree : (fanout > 0 ? 2 * (int64_t)fanout : kWave);
-        const int L = std::max(4, std::min(kWave, pow2_at_least(avg)));
+        const int L = lanes_per_row(column_index, fanout > 0 ? 2 * (int64_t)fanout : kWave);
         SampleArgs a{row_pointers, column_index, seeds, (uint32_t)num_nodes, num_seeds, fanout, rng_seed, seedpos, mark,
                      blk_row_pointers, blk_column_index, blk_edge_ids, edge_capacity, rec};
         const int64_t rows_per_block = kBlock / L;
@@ -400,19 +360,15 @@ int gnna_sample_neighbors_i32(const int32_t *row_pointers, const int32_t *column
     hipLaunchKernelGGL(relabel_kernel, dim3(elementwise_grid(relabel_items, ds->num_cus, 16)), block, 0, stream, seeds, num_seeds,
                        num_nodes, seedpos, mark, blk_row_pointers, blk_column_index, src_nodes, edge_capacity, src_capacity, rec);
     if (partPtr) {
-        hipLaunchKernelGGL(part_count_kernel, dim3(elementwise_grid(num_seeds + 1, ds->num_cus, 16)), block, 0, stream,
-                           blk_row_pointers, num_seeds, partSize, first_part);
+        launch_part_count(ds, stream, blk_row_pointers, num_seeds, nullptr, partSize, first_part);
         rc = launch_exclusive_scan(stream, first_part, num_seeds + 1, partial);
         if (rc != GNNA_OK) return rc;
         hipLaunchKernelGGL(part_fill_kernel, dim3(elementwise_grid(edge_capacity + 1, ds->num_cus, 16)), block, 0, stream,
-                           blk_row_pointers, first_part, num_seeds, partSize, edge_capacity, partPtr, part2Node, rec);
+                           CsrRows{blk_row_pointers, num_seeds}, first_part, partSize, edge_capacity, partPtr, part2Node, rec);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "%s: launch: %s", what, hipGetErrorString(e));
     long long host[REC_WORDS] = {0};
-    e = hipMemcpyAsync(host, rec, sizeof(host), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "%s: reading the counts back: %s", what, hipGetErrorString(e));
+    rc = read_record(what, stream, rec, host, REC_WORDS);
+    if (rc != GNNA_OK) return rc;
     counts[0] = host[REC_NNZ];
     counts[1] = host[REC_SRC];
     counts[2] = partPtr ? host[REC_PARTS] : 0;

@@ -5,7 +5,7 @@
 //
 // No counterpart in the reference (its models never change the number of rows).
 //
-//   clear_kernel        keep[0 .. N] = 0 and the record
+//   clear_kernel        (gnna_transpose.hip) keep[0 .. N] = 0 and the record
 //   select_wave_kernel  one wavefront per segment of up to GNNA_TOPK_WAVE_ROWS rows: the order keys (gnna_keys.h) of the segment in
 //                       registers, the k-th largest key bit by bit from the top (per bit: ballots + popcounts of "agrees with the
 //                       prefix and has this bit set"), then keep[] = 1 for the keys above it and for the first rows equal to it, in
@@ -19,7 +19,7 @@
 //   scan_* kernels      flag[] -> where every surviving edge goes
 //   edge_fill_kernel    new_column_index, edge_ids, new_row_pointers, and the neighbor-groups of every kept row
 //   scan_* kernels      -> the first group of every row
-//   part_fill_kernel    partPtr / part2Node as part_fill_kernel of gnna_transpose.hip writes them for new_row_pointers
+//   part_fill_kernel    partPtr / part2Node of new_row_pointers by the one rule of gnna_parts.h, over the OLD rows
 // Only ones are stored into keep[] after the clear, every other position is computed from counts and scans, and no global atomic
 // hands a position out: the same bits on every run and for every launch shape.
 //
@@ -37,6 +37,7 @@
 #include "gnna_gat_common.h"     // gat::load_piece, gat::head_sum, gat::check_alias
 #include "gnna_internal.h"
 #include "gnna_keys.h"
+#include "gnna_parts.h"
 #include "gnna_segments.h"
 
 namespace gnna {
@@ -61,12 +62,6 @@ __host__ __device__ __forceinline__ int64_t keep_count(int64_t n, double ratio, 
     if (k_fixed > 0) return n < k_fixed ? n : k_fixed;
     const int64_t k = (int64_t)ceil(ratio * (double)n);
     return n < k ? n : k;
-}
-
-__global__ void __launch_bounds__(kBlock)
-clear_kernel(int32_t *__restrict__ words, int64_t n)
-{
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) words[i] = 0;
 }
 
 struct SelectArgs {
@@ -291,34 +286,33 @@ edge_fill_kernel(const FillArgs a)
             if (i >= 0) {
                 const int32_t b = a.pos[clamp_to(a.rp[r], a.nnz)], e = a.pos[clamp_to(a.rp[r + 1], a.nnz)];
                 if (i < a.row_capacity) a.new_rp[i] = b;
-                if (a.groups && e > b) count = (int32_t)(((int64_t)(e - b) + a.partSize - 1) / a.partSize);
+                if (a.groups) count = groups_of((int64_t)e - b, a.partSize);
             }
         }
         if (a.groups) a.groups[r] = count;
     }
 }
 
-// As part_fill_kernel of gnna_transpose.hip over the OLD rows, of which only the kept ones have groups: group p belongs to the
-// last row whose first group is <= p.  The number of groups is read on the device (first_part[N]).
+// The OLD rows, of which only the kept ones own groups (a group's owner is then a kept row): old row i starts where its first
+// edge goes (pos: the scanned flag[]) and is called by its new id.
+struct KeptRows {
+    const int32_t *rp, *pos, *new_id;
+    int64_t N, nnz;
+    __device__ int64_t rows() const { return N; }
+    __device__ int32_t start(int64_t i) const { return pos[clamp_to(rp[i], nnz)]; }
+    __device__ int32_t id(int64_t i) const { return new_id[i]; }
+    __device__ int32_t end() const { return pos[nnz]; }
+};
+
+// The partition of new_row_pointers (gnna_parts.h); the number of groups is read on the device.
 __global__ void __launch_bounds__(kBlock)
-part_fill_kernel(const int32_t *__restrict__ rp, const int32_t *__restrict__ pos, const int32_t *__restrict__ first_part,
-                 const int32_t *__restrict__ new_id, int64_t N, int64_t nnz, int partSize, int64_t capacity,
+part_fill_kernel(const KeptRows rows, const int32_t *__restrict__ first_part, int partSize, int64_t capacity,
                  int32_t *__restrict__ pp, int32_t *__restrict__ p2n, long long *__restrict__ rec)
 {
-    const int64_t num_parts = first_part[N];
-    const int64_t first = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (first == 0) rec[REC_PARTS] = num_parts;
+    const int64_t num_parts = first_part[rows.N];
+    if (blockIdx.x == 0 && threadIdx.x == 0) rec[REC_PARTS] = num_parts;
     if (num_parts > capacity) return;                         // (the call fails)
-    for (int64_t p = first; p <= num_parts; p += (int64_t)gridDim.x * kBlock) {
-        if (p == num_parts) { pp[p] = pos[nnz]; continue; }
-        int64_t lo = 0, hi = N - 1;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi + 1) >> 1;
-            if (first_part[mid] <= p) lo = mid; else hi = mid - 1;
-        }
-        pp[p] = (int32_t)((int64_t)pos[clamp_to(rp[lo], nnz)] + (p - first_part[lo]) * partSize);
-        p2n[p] = new_id[lo];
-    }
+    fill_parts(rows, first_part, partSize, num_parts, pp, p2n);
 }
 
 // ---- the gathers ---------------------------------------------------------------------------------------------------------------
@@ -445,8 +439,6 @@ gather_rows_bwd_kernel(const GatherArgs p)
     }
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 int launch_gather(bool backward, DeviceState *ds, hipStream_t stream, const GatherArgs &a)
 {
     const int log_lpr = log2_lanes(a.D, 4);
@@ -547,25 +539,18 @@ int gnna_segment_topk_i32(const float *score, int64_t num_rows, const int32_t *g
     part_capacity = std::min<int64_t>(part_capacity, 0x7fffffffll);
 
     // scratch: [record][keep: N + 1] (cleared together) [groups per row: N + 1][flag: nnz + 1][scan partials]
-    const size_t rec_bytes = align256(REC_WORDS * sizeof(long long));
-    const size_t row_bytes = align256((size_t)(num_rows + 1) * 4);
-    const size_t edge_bytes = csr ? align256((size_t)(nnz + 1) * 4) : 0;
-    const size_t partial_bytes = align256((size_t)scan_tiles(std::max(num_rows, csr ? nnz : 0) + 1) * 4);
+    Carver c;
+    const size_t o_rec = c.add(REC_WORDS * sizeof(long long)), o_keep = c.add((size_t)(num_rows + 1) * 4), cleared_bytes = c.bytes;
+    const size_t o_groups = parts ? c.add((size_t)(num_rows + 1) * 4) : 0, o_flag = csr ? c.add((size_t)(nnz + 1) * 4) : 0;
+    const size_t o_partial = c.add((size_t)scan_tiles(std::max(num_rows, csr ? nnz : 0) + 1) * 4);
     void *ws = nullptr;
-    if ((rc = get_workspace(ds, stream, kSlotTopk, rec_bytes + row_bytes + (parts ? row_bytes : 0) + edge_bytes + partial_bytes, &ws)) != GNNA_OK)
-        return rc;
-    char *at = static_cast<char *>(ws);
-    long long *rec = reinterpret_cast<long long *>(at); at += rec_bytes;
-    int32_t *keep = reinterpret_cast<int32_t *>(at); at += row_bytes;
-    int32_t *groups = nullptr;
-    if (parts) { groups = reinterpret_cast<int32_t *>(at); at += row_bytes; }
-    int32_t *flag = reinterpret_cast<int32_t *>(at); at += edge_bytes;
-    int32_t *partial = reinterpret_cast<int32_t *>(at);
+    if ((rc = get_workspace(ds, stream, kSlotTopk, c.bytes, &ws)) != GNNA_OK) return rc;
+    long long *rec = Carver::at<long long>(ws, o_rec);
+    int32_t *keep = Carver::at<int32_t>(ws, o_keep), *groups = parts ? Carver::at<int32_t>(ws, o_groups) : nullptr;
+    int32_t *flag = csr ? Carver::at<int32_t>(ws, o_flag) : nullptr, *partial = Carver::at<int32_t>(ws, o_partial);
 
     const dim3 block(kBlock);
-    const int64_t clear_words = (int64_t)((rec_bytes + row_bytes) / 4);
-    hipLaunchKernelGGL(clear_kernel, dim3(elementwise_grid(clear_words, ds->num_cus, 16)), block, 0, stream, reinterpret_cast<int32_t *>(ws),
-                       clear_words);
+    launch_clear_words(ds, stream, static_cast<int32_t *>(ws), (int64_t)(cleared_bytes / 4));
     if (num_segments > 0 && num_rows > 0) {
         const SelectArgs sa{score, graph_pointers, num_rows, num_segments, ratio, k_fixed, keep};
         hipLaunchKernelGGL(select_wave_kernel, dim3((unsigned)((num_segments + kWavesPerBlock - 1) / kWavesPerBlock)), block, 0, stream, sa);
@@ -583,16 +568,12 @@ int gnna_segment_topk_i32(const float *score, int64_t num_rows, const int32_t *g
         hipLaunchKernelGGL(edge_fill_kernel, dim3(elementwise_grid(std::max(num_rows, nnz) + 1, ds->num_cus, 16)), block, 0, stream, fa);
         if (parts) {
             if ((rc = launch_exclusive_scan(stream, groups, num_rows + 1, partial)) != GNNA_OK) return rc;
-            hipLaunchKernelGGL(part_fill_kernel, dim3(elementwise_grid(part_capacity + 1, ds->num_cus, 16)), block, 0, stream, row_pointers,
-                               flag, groups, new_id, num_rows, nnz, partSize, part_capacity, partPtr, part2Node, rec);
+            hipLaunchKernelGGL(part_fill_kernel, dim3(elementwise_grid(part_capacity + 1, ds->num_cus, 16)), block, 0, stream,
+                               KeptRows{row_pointers, flag, new_id, num_rows, nnz}, groups, partSize, part_capacity, partPtr, part2Node, rec);
         }
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "%s: launch: %s", what, hipGetErrorString(e));
     long long host[REC_WORDS] = {0};
-    e = hipMemcpyAsync(host, rec, sizeof(host), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "%s: reading the counts back: %s", what, hipGetErrorString(e));
+    if ((rc = read_record(what, stream, rec, host, REC_WORDS)) != GNNA_OK) return rc;
     counts[0] = host[REC_ROWS];
     counts[1] = csr ? host[REC_EDGES] : 0;
     counts[2] = parts ? host[REC_PARTS] : 0;

@@ -15,10 +15,14 @@
 // computed, none is handed out by a global atomic: the result is the same bits on every run and for every launch shape.
 // The passes ping-pong between library scratch and the two output arrays, so the scratch is 8 bytes per edge (12 when the
 // caller wants no t_perm) plus 1 KiB per tile.
+// The partition = part_count_kernel, the scan, a read-back of the total, part_fill_kernel; the rule is gnna_parts.h's.  Here
+// is also what gnna_sample.hip, gnna_topk.hip and gnna_walk.hip take from gnna_internal.h: the scan, refuse_capture, the clear,
+// the group count of row pointers, the read-back of a call's record and the lanes-per-row choice.
 #include <algorithm>
 
 #include "gnna_device.h"
 #include "gnna_internal.h"
+#include "gnna_parts.h"
 
 namespace gnna {
 namespace {
@@ -97,7 +101,7 @@ scan_apply_kernel(int32_t *__restrict__ data, int64_t n, const int32_t *__restri
 
 }  // namespace
 
-// (shared with gnna_sample.hip through gnna_internal.h)
+// (shared through gnna_internal.h)
 int64_t scan_tiles(int64_t n) { return (n + kScanTile - 1) / kScanTile; }
 
 // data[i] <- sum of data[0 .. i) for i < n; `partial` holds scan_tiles(n) ints.
@@ -236,44 +240,35 @@ transpose_finish_kernel(const int32_t *__restrict__ rp, int64_t num_out_rows, ui
 }
 
 __global__ void __launch_bounds__(kBlock)
-fill_i32_kernel(int32_t *__restrict__ out, int64_t n, int32_t value)
+clear_kernel(int32_t *__restrict__ words, int64_t n)
 {
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) out[i] = value;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) words[i] = 0;
 }
 
-// ---- neighbor-group partition -------------------------------------------------------------------------------------------
+// ---- neighbor-group partition (the rule: gnna_parts.h) ------------------------------------------------------------------
 
-// count[i] = groups of row i (0 for a row whose pointers decrease); count[num_nodes] = 0, which the scan turns into the total
+// count[i] = groups of row i for i < rows (0 for a row whose pointers decrease), 0 from there to n, which the scan turns into
+// the total.  rows = *rows_word, or n without one.
 __global__ void __launch_bounds__(kBlock)
-part_count_kernel(const int32_t *__restrict__ rp, int64_t num_nodes, int partSize, int32_t *__restrict__ count)
+part_count_kernel(const int32_t *__restrict__ rp, int64_t n, const long long *__restrict__ rows_word, int partSize,
+                  int32_t *__restrict__ count)
 {
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i <= num_nodes; i += (int64_t)gridDim.x * kBlock) {
-        int64_t deg = 0;
-        if (i < num_nodes) deg = (int64_t)rp[i + 1] - (int64_t)rp[i];
-        count[i] = deg > 0 ? (int32_t)((deg + partSize - 1) / partSize) : 0;
-    }
+    const int64_t rows = rows_word ? (int64_t)*rows_word : n;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i <= n; i += (int64_t)gridDim.x * kBlock)
+        count[i] = groups_of(i < rows ? (int64_t)rp[i + 1] - (int64_t)rp[i] : 0, partSize);
 }
 
-// group p belongs to the last row whose first group is <= p (rows without groups share their start with the next row)
+// the partition of device row pointers; num_parts is the host's (scan_parts read it back)
 __global__ void __launch_bounds__(kBlock)
-part_fill_kernel(const int32_t *__restrict__ rp, const int32_t *__restrict__ first_part, int64_t num_nodes, int partSize,
-                 int64_t num_parts, int32_t *__restrict__ pp, int32_t *__restrict__ p2n)
+part_fill_kernel(const CsrRows rows, const int32_t *__restrict__ first_part, int partSize, int64_t num_parts,
+                 int32_t *__restrict__ pp, int32_t *__restrict__ p2n)
 {
-    for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p <= num_parts; p += (int64_t)gridDim.x * kBlock) {
-        if (p == num_parts) { pp[p] = num_nodes > 0 ? rp[num_nodes] : 0; continue; }
-        int64_t lo = 0, hi = num_nodes - 1;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi + 1) >> 1;
-            if (first_part[mid] <= p) lo = mid; else hi = mid - 1;
-        }
-        pp[p] = (int32_t)((int64_t)rp[lo] + (p - first_part[lo]) * partSize);
-        p2n[p] = (int32_t)lo;
-    }
+    fill_parts(rows, first_part, partSize, num_parts, pp, p2n);
 }
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
+
+// ---- shared with gnna_sample.hip, gnna_topk.hip and gnna_walk.hip through gnna_internal.h ---------------------------------
 
 int refuse_capture(const char *what, hipStream_t stream)
 {
@@ -282,6 +277,36 @@ int refuse_capture(const char *what, hipStream_t stream)
     if (cap != hipStreamCaptureStatusNone)
         return fail(GNNA_ERR_UNSUPPORTED, "%s reads a count back and cannot run inside a stream capture: call it before capturing", what);
     return GNNA_OK;
+}
+
+void launch_clear_words(DeviceState *ds, hipStream_t stream, int32_t *words, int64_t n)
+{
+    hipLaunchKernelGGL(clear_kernel, dim3(elementwise_grid(n, ds->num_cus, 16)), dim3(kBlock), 0, stream, words, n);
+}
+
+void launch_part_count(DeviceState *ds, hipStream_t stream, const int32_t *rp, int64_t n, const long long *rows_word, int partSize,
+                       int32_t *count)
+{
+    hipLaunchKernelGGL(part_count_kernel, dim3(elementwise_grid(n + 1, ds->num_cus, 16)), dim3(kBlock), 0, stream, rp, n, rows_word,
+                       partSize, count);
+}
+
+int read_record(const char *what, hipStream_t stream, const long long *rec, long long *host, int words)
+{
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "%s: launch: %s", what, hipGetErrorString(e));
+    e = hipMemcpyAsync(host, rec, (size_t)words * sizeof(long long), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "%s: reading the counts back: %s", what, hipGetErrorString(e));
+    return GNNA_OK;
+}
+
+int lanes_per_row(const int32_t *column_index, int64_t fallback_avg)
+{
+    gnna_tuning tune;
+    gnna_get_tuning(&tune);
+    apply_graph_hints(column_index, 0, &tune);
+    return std::max(4, std::min(kWave, pow2_at_least(tune.avg_degree > 0 ? tune.avg_degree : fallback_avg)));
 }
 
 namespace {
@@ -299,13 +324,13 @@ int scan_parts(const char *what, DeviceState *ds, hipStream_t stream, int partSi
                int32_t **first_part, int64_t *num_parts)
 {
     const int64_t n = num_nodes + 1;
+    Carver c;
+    const size_t o_count = c.add((size_t)n * 4), o_partial = c.add((size_t)scan_tiles(n) * 4);
     void *ws = nullptr;
-    int rc = get_workspace(ds, stream, kSlotTranspose, align256((size_t)n * 4) + align256((size_t)scan_tiles(n) * 4), &ws);
+    int rc = get_workspace(ds, stream, kSlotTranspose, c.bytes, &ws);
     if (rc != GNNA_OK) return rc;
-    int32_t *count = static_cast<int32_t *>(ws);
-    int32_t *partial = reinterpret_cast<int32_t *>(static_cast<char *>(ws) + align256((size_t)n * 4));
-    hipLaunchKernelGGL(part_count_kernel, dim3(elementwise_grid(n, ds->num_cus, 16)), dim3(kBlock), 0, stream, rp, num_nodes,
-                       partSize, count);
+    int32_t *count = Carver::at<int32_t>(ws, o_count), *partial = Carver::at<int32_t>(ws, o_partial);
+    launch_part_count(ds, stream, rp, num_nodes, nullptr, partSize, count);
     rc = launch_exclusive_scan(stream, count, n, partial);
     if (rc != GNNA_OK) return rc;
     int32_t total = 0;
@@ -356,8 +381,7 @@ int gnna_transpose_csr_i32(const int32_t *row_pointers, const int32_t *column_in
     const int64_t nnz = nnz32;
     if (nnz < 0) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: row_pointers[num_out_rows] = %d", what, nnz32);
     if (nnz == 0) {
-        hipLaunchKernelGGL(fill_i32_kernel, dim3(elementwise_grid(num_in_rows + 1, ds->num_cus, 16)), dim3(kBlock), 0, stream,
-                           t_row_pointers, num_in_rows + 1, 0);
+        launch_clear_words(ds, stream, t_row_pointers, num_in_rows + 1);
         return launch_ok("%s: launch", what);
     }
     if (!column_index || !t_column_index) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null index pointer", what);
@@ -370,19 +394,16 @@ int gnna_transpose_csr_i32(const int32_t *row_pointers, const int32_t *column_in
     while (passes < 4 && ((uint64_t)num_in_rows >> (8 * passes)) != 0) passes++;
     const int64_t tiles = (nnz + kSortTile - 1) / kSortTile;
     const int64_t hist_len = tiles * kDigits;
-    const size_t edge_bytes = align256((size_t)nnz * 4);
-    const size_t hist_bytes = align256((size_t)hist_len * 4), partial_bytes = align256((size_t)scan_tiles(hist_len) * 4);
+    // scratch: [keys][positions] (one side of the ping-pong) [positions of the other side, without a t_perm][hist][scan partials]
+    Carver c;
+    const size_t o_keys = c.add((size_t)nnz * 4), o_vals = c.add((size_t)nnz * 4), o_vals_b = t_perm ? 0 : c.add((size_t)nnz * 4);
+    const size_t o_hist = c.add((size_t)hist_len * 4), o_partial = c.add((size_t)scan_tiles(hist_len) * 4);
     void *ws = nullptr;
-    rc = get_workspace(ds, stream, kSlotTranspose, (t_perm ? 2 : 3) * edge_bytes + hist_bytes + partial_bytes, &ws);
+    rc = get_workspace(ds, stream, kSlotTranspose, c.bytes, &ws);
     if (rc != GNNA_OK) return rc;
-    char *at = static_cast<char *>(ws);
-    int32_t *keys_a = reinterpret_cast<int32_t *>(at); at += edge_bytes;
-    int32_t *vals_a = reinterpret_cast<int32_t *>(at); at += edge_bytes;
-    int32_t *vals_b = t_perm;
-    if (!vals_b) { vals_b = reinterpret_cast<int32_t *>(at); at += edge_bytes; }
-    int32_t *keys_b = t_column_index;
-    int32_t *hist = reinterpret_cast<int32_t *>(at); at += hist_bytes;
-    int32_t *partial = reinterpret_cast<int32_t *>(at);
+    int32_t *keys_a = Carver::at<int32_t>(ws, o_keys), *vals_a = Carver::at<int32_t>(ws, o_vals);
+    int32_t *keys_b = t_column_index, *vals_b = t_perm ? t_perm : Carver::at<int32_t>(ws, o_vals_b);
+    int32_t *hist = Carver::at<int32_t>(ws, o_hist), *partial = Carver::at<int32_t>(ws, o_partial);
 
     const int32_t *keys_in = column_index, *vals_in = nullptr;
     const uint32_t n_in = (uint32_t)num_in_rows;
@@ -451,8 +472,8 @@ int gnna_build_part_device_i32(int partSize, const int32_t *indptr, int64_t num_
     if (expect != num_parts)
         return fail(GNNA_ERR_INVALID_ARGUMENT, "num_parts=%lld but the CSR has %lld groups at partSize=%d", (long long)num_parts,
                     (long long)expect, partSize);
-    hipLaunchKernelGGL(part_fill_kernel, dim3(elementwise_grid(num_parts + 1, ds->num_cus, 16)), dim3(kBlock), 0, stream, indptr,
-                       first_part, num_nodes, partSize, num_parts, partPtr, part2Node);
+    hipLaunchKernelGGL(part_fill_kernel, dim3(elementwise_grid(num_parts + 1, ds->num_cus, 16)), dim3(kBlock), 0, stream,
+                       CsrRows{indptr, num_nodes}, first_part, partSize, num_parts, partPtr, part2Node);
     return launch_ok("%s: launch", what);
 }
 

@@ -4,7 +4,7 @@
 //                               gnna_sample_neighbors_i32: ONE read-back, refuses to run inside a stream capture
 //
 // The cut, in launch order (rank / new_id / kept are library scratch: 8 bytes per node + 4 per id):
-//   clear_kernel        the record and rank[N + 1]
+//   clear_kernel        (gnna_transpose.hip) the record and rank[N + 1]
 //   mark_kernel         rank[nodes[i]] = 1 (plain stores: equal ids write the same value)
 //   scan_* kernels      (gnna_transpose.hip) exclusive scan of the marks = the rank of every kept node in increasing global id
 //   ids_kernel          new_id[N] (the table the passes below look ids up in), kept[a] = S[a], sub_nodes, the caller's new_id
@@ -15,13 +15,15 @@
 //   scan_* kernels      exclusive scan of the counts = the result's row pointers
 //   cut_rows_kernel<1>  fill pass: the same walk, every survivor placed by the ballot's prefix -- position order without a sort.
 //   cut_long_kernel<1>  Both return at once when a capacity is too small: nothing is written beyond one
-//   part_* kernels      the partition of the result's row pointers as gnna_build_part_i32 writes it (groups per row where kept[]
-//                       was), sizes read on the device
+//   part_count_kernel   (gnna_transpose.hip), the scan, part_fill_kernel: the partition of the result's row pointers by the one
+//                       rule of gnna_parts.h, as gnna_build_part_i32 writes it (groups per row where kept[] was), sizes read on
+//                       the device
 // Unlike the edge-parallel cut of gnna_topk.hip (a flag and a binary search per edge of the WHOLE graph) nothing here is O(nnz).
 #include <algorithm>
 
 #include "gnna_device.h"
 #include "gnna_internal.h"
+#include "gnna_parts.h"
 #include "gnna_walk.h"
 
 namespace gnna {
@@ -80,12 +82,6 @@ walk_kernel(const int32_t *__restrict__ rp, const int32_t *__restrict__ ci, uint
 }
 
 // ---- the induced subgraph -----------------------------------------------------------------------------------------------------
-
-__global__ void __launch_bounds__(kBlock)
-clear_kernel(int32_t *__restrict__ words, int64_t n)
-{
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) words[i] = 0;
-}
 
 __global__ void __launch_bounds__(kBlock)
 mark_kernel(const int32_t *__restrict__ nodes, int64_t num_ids, uint32_t num_nodes, int32_t *__restrict__ mark,
@@ -265,47 +261,17 @@ cut_long_kernel(const CutArgs a, int split)
 }
 static_assert(kWavesPerBlock == 4, "cut_long_kernel sums four wavefront counts");
 
-// count[i] = groups of result row i; 0 from |S| to M, which the scan turns into the total
-__global__ void __launch_bounds__(kBlock)
-part_count_kernel(const int32_t *__restrict__ sub_rp, int64_t max_rows, int partSize, int32_t *__restrict__ count,
-                  const long long *__restrict__ rec)
-{
-    const int64_t num_kept = rec[REC_NODES];
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i <= max_rows; i += (int64_t)gridDim.x * kBlock) {
-        const int64_t deg = i < num_kept ? (int64_t)sub_rp[i + 1] - (int64_t)sub_rp[i] : 0;
-        count[i] = deg > 0 ? (int32_t)((deg + partSize - 1) / partSize) : 0;
-    }
-}
-
-// As part_fill_kernel of gnna_transpose.hip, with the number of rows and of groups read on the device.
+// The partition of the result's row pointers (gnna_parts.h), with the number of rows (ids_kernel left it in the record) and of
+// groups read on the device.  sub_rp is a scan: sub_rp[0] = 0, so the closing entry is sub_rp[rows] for no rows as well.
 __global__ void __launch_bounds__(kBlock)
 part_fill_kernel(const int32_t *__restrict__ sub_rp, const int32_t *__restrict__ first_part, int partSize, int64_t node_capacity,
                  int64_t edge_capacity, int32_t *__restrict__ pp, int32_t *__restrict__ p2n, long long *__restrict__ rec)
 {
-    const int64_t num_kept = rec[REC_NODES];
-    const int64_t num_parts = first_part[num_kept];
-    const int64_t first = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (first == 0) rec[REC_PARTS] = num_parts;
-    if (num_kept > node_capacity || (int64_t)sub_rp[num_kept] > edge_capacity) return;       // (groups <= edges: they fit as well)
-    for (int64_t p = first; p <= num_parts; p += (int64_t)gridDim.x * kBlock) {
-        if (p == num_parts) { pp[p] = sub_rp[num_kept]; continue; }
-        int64_t lo = 0, hi = num_kept - 1;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi + 1) >> 1;
-            if (first_part[mid] <= p) lo = mid; else hi = mid - 1;
-        }
-        pp[p] = (int32_t)((int64_t)sub_rp[lo] + (p - first_part[lo]) * partSize);
-        p2n[p] = (int32_t)lo;
-    }
-}
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-int pow2_at_least(int64_t x)
-{
-    int p = 1;
-    while (p < x) p <<= 1;
-    return p;
+    const CsrRows rows{sub_rp, rec[REC_NODES]};
+    const int64_t num_parts = first_part[rows.n];
+    if (blockIdx.x == 0 && threadIdx.x == 0) rec[REC_PARTS] = num_parts;
+    if (rows.n > node_capacity || (int64_t)sub_rp[rows.n] > edge_capacity) return;           // (groups <= edges: they fit as well)
+    fill_parts(rows, first_part, partSize, num_parts, pp, p2n);
 }
 
 }  // namespace
@@ -370,24 +336,21 @@ int gnna_induced_subgraph_i32(const int32_t *row_pointers, const int32_t *column
     const int64_t M = std::min(num_ids, num_nodes);                       // |S| <= M
 
     // scratch: [record][rank: N + 1] (cleared together) [new_id: N][kept: M + 1][scan partials]
-    const size_t rec_bytes = align256(REC_WORDS * sizeof(long long));
-    const size_t rank_bytes = align256((size_t)(num_nodes + 1) * 4), id_bytes = align256((size_t)num_nodes * 4);
-    const size_t kept_bytes = align256((size_t)(M + 1) * 4);
-    const size_t partial_bytes = align256((size_t)scan_tiles(num_nodes + 1) * 4);
+    Carver c;
+    const size_t o_rec = c.add(REC_WORDS * sizeof(long long)), o_rank = c.add((size_t)(num_nodes + 1) * 4), cleared_bytes = c.bytes;
+    const size_t o_id = c.add((size_t)num_nodes * 4), o_kept = c.add((size_t)(M + 1) * 4);
+    const size_t o_partial = c.add((size_t)scan_tiles(num_nodes + 1) * 4);
     void *ws = nullptr;
-    rc = get_workspace(ds, stream, kSlotWalk, rec_bytes + rank_bytes + id_bytes + kept_bytes + partial_bytes, &ws);
+    rc = get_workspace(ds, stream, kSlotWalk, c.bytes, &ws);
     if (rc != GNNA_OK) return rc;
-    char *at = static_cast<char *>(ws);
-    long long *rec = reinterpret_cast<long long *>(at); at += rec_bytes;
-    int32_t *rank = reinterpret_cast<int32_t *>(at); at += rank_bytes;        // marks -> ranks -> the result's row pointers
-    int32_t *table = reinterpret_cast<int32_t *>(at); at += id_bytes;
-    int32_t *kept = reinterpret_cast<int32_t *>(at); at += kept_bytes;        // S -> groups before every result row
-    int32_t *partial = reinterpret_cast<int32_t *>(at);
+    long long *rec = Carver::at<long long>(ws, o_rec);
+    int32_t *rank = Carver::at<int32_t>(ws, o_rank);          // marks -> ranks -> the result's row pointers
+    int32_t *table = Carver::at<int32_t>(ws, o_id);
+    int32_t *kept = Carver::at<int32_t>(ws, o_kept);          // S -> groups before every result row
+    int32_t *partial = Carver::at<int32_t>(ws, o_partial);
 
     const dim3 block(kBlock);
-    const int64_t clear_words = (int64_t)((rec_bytes + rank_bytes) / 4);
-    hipLaunchKernelGGL(clear_kernel, dim3(elementwise_grid(clear_words, ds->num_cus, 16)), block, 0, stream,
-                       reinterpret_cast<int32_t *>(ws), clear_words);
+    launch_clear_words(ds, stream, static_cast<int32_t *>(ws), (int64_t)(cleared_bytes / 4));
     hipLaunchKernelGGL(mark_kernel, dim3(elementwise_grid(num_ids, ds->num_cus, 16)), block, 0, stream, nodes, num_ids,
                        (uint32_t)num_nodes, rank, rec);
     rc = launch_exclusive_scan(stream, rank, num_nodes + 1, partial);
@@ -395,11 +358,7 @@ int gnna_induced_subgraph_i32(const int32_t *row_pointers, const int32_t *column
     hipLaunchKernelGGL(ids_kernel, dim3(elementwise_grid(num_nodes, ds->num_cus, 16)), block, 0, stream, rank, num_nodes, table,
                        new_id, kept, sub_nodes, node_capacity, rec);
     // lanes per row from the edges an average row has: the graph's hint, else nnz / num_nodes
-    gnna_tuning tune;
-    gnna_get_tuning(&tune);
-    apply_graph_hints(column_index, 0, &tune);
-    const int64_t avg = tune.avg_degree > 0 ? tune.avg_degree : (num_nodes > 0 ? nnz / num_nodes : 0);
-    const int L = std::max(4, std::min(kWave, pow2_at_least(avg)));
+    const int L = lanes_per_row(column_index, num_nodes > 0 ? nnz / num_nodes : 0);
     CutArgs a{row_pointers, column_index, (uint32_t)num_nodes, nnz, kept, table, M, rank, sub_row_pointers, sub_column_index,
               sub_edge_ids, node_capacity, edge_capacity, rec};
     const int64_t rows_per_block = kBlock / L;
@@ -415,19 +374,15 @@ int gnna_induced_subgraph_i32(const int32_t *row_pointers, const int32_t *column
     hipLaunchKernelGGL(cut_rows_kernel<true>, row_grid, block, 0, stream, a, L);
     if (M > 0) hipLaunchKernelGGL(cut_long_kernel<true>, long_grid, block, 0, stream, a, split);
     if (partPtr) {
-        hipLaunchKernelGGL(part_count_kernel, dim3(elementwise_grid(M + 1, ds->num_cus, 16)), block, 0, stream, rank, M, partSize,
-                           kept, rec);
+        launch_part_count(ds, stream, rank, M, rec + REC_NODES, partSize, kept);
         rc = launch_exclusive_scan(stream, kept, M + 1, partial);
         if (rc != GNNA_OK) return rc;
         hipLaunchKernelGGL(part_fill_kernel, dim3(elementwise_grid(edge_capacity + 1, ds->num_cus, 16)), block, 0, stream, rank,
                            kept, partSize, node_capacity, edge_capacity, partPtr, part2Node, rec);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "%s: launch: %s", what, hipGetErrorString(e));
     long long host[REC_WORDS] = {0};
-    e = hipMemcpyAsync(host, rec, sizeof(host), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "%s: reading the counts back: %s", what, hipGetErrorString(e));
+    rc = read_record(what, stream, rec, host, REC_WORDS);
+    if (rc != GNNA_OK) return rc;
     counts[0] = host[REC_NODES];
     counts[1] = host[REC_NNZ];
     counts[2] = partPtr ? host[REC_PARTS] : 0;

@@ -305,8 +305,6 @@ void launch_main(int log_lpr, dim3 grid, hipStream_t stream, const X16Args &a)
     });
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 
 // Scratch of the 16-bit path: slot 3 = staged source rows (only layouts that are not 16-byte addressable), slot 4 = fp32 sums of
