@@ -416,20 +416,19 @@ int sweep_auto_phases(const gnna_tuning &t, int mode, int dim, size_t x_bytes, i
 // 33 .. 64 floats -- two 128-byte requests per gathered row, the only widths the block is taken at (kDenseMinDim):
 //     entries * t_edge  -  t_hub(H)  -  t_launch,      t_hub(H) = rounds * (H_pad / 128) * t_chunk
 // t_edge: what the sweep kernel pays per edge.  t_chunk: what a workgroup of hub_block_kernel takes per 128 source ranks;
-// rounds = workgroups (H_pad / 32) over compute units, rounded up.  On whole rounds that is 2 H^2 64 / r_mfma with r_mfma =
-// 89 TFLOP/s.  All measured on MI355X on the Reddit-like headline with tools/probe_hub_block.py, a scan over forced hub
-// counts under a kernel trace (profiles/hub_block_rate/hub_count_scan.log and hub_count_scan_kernels.log):
-//   * t_edge: the sweep kernel fell from 1,329.5 to 1,168.6 us for the 16.19 M edges of 8,192 hubs: 9.9 ps per edge (11.6 at
-//     2,048 hubs, 10.1 at 4,097, 9.3 at 6,144, 9.8 at 10,240, 9.1 at 12,295);
-//   * t_chunk: hub_block_kernel took 96.0 us for 8,192 hubs (64 chunks, one round): 1.50 us per chunk; 1.52 at 6,144 hubs, 1.56
-//     at 4,224 ranks, 1.77 at 2,048 (64 workgroups: the launch and the epilogue weigh more).  Two rounds: 213.7 us at 10,240
-//     hubs and 257.6 us at 12,416 ranks, 1.33 us per chunk and round (the second round is a quarter or half of a round, on a
-//     chip that is otherwise idle), so the model is 12 % on the safe side there -- and the step LOSES 89 and 116 us against
-//     8,192 hubs at those two counts, so trimmed_hubs, kDenseMinSaving and kDenseMinShare stay as they were;
+// rounds = workgroups (H_pad / 32) over compute units, rounded up.  All measured on MI355X on the Reddit-like headline with
+// tools/probe_hub_block.py, a scan over forced hub counts under a kernel trace (profiles/hub_block_bf16/hub_count_scan.log and
+// hub_count_scan_kernels.log; the scans of the f32 forms of the kernel: profiles/hub_block_rate, profiles/dense_block):
+//   * t_edge: the sweep kernel fell from 1,335.4 to 1,172.3 us for the 16.19 M edges of 8,192 hubs: 10.1 ps per edge (11.3 at
+//     4,097 hubs, 9.7 at 12,390); 9.9 in the scan before this one, which stays;
+//   * t_chunk: hub_block_kernel (bf16 MFMA on the three-way split of X) took 62.2 us for 8,192 hubs (64 chunks, one round):
+//     0.97 us per chunk (1.50 with f32 MFMA); 1.04 at 4,224 ranks.  Two rounds: 173.2 us at 12,416 ranks, 0.89 us per chunk
+//     and round, so the model is 9 % on the safe side there -- and the step still LOSES 52 us against 8,192 hubs at that
+//     count (1.3345 against 1.2821 ms), so trimmed_hubs, kDenseMinSaving and kDenseMinShare stay as they were;
 //   * t_launch: 7 us from the scan of the first form of the kernel (profiles/dense_block/README.md); in this scan the step
-//     fell by 0 .. 2 us less than the kernel times did.
+//     fell by 6.5 us less than the kernel times did.
 constexpr double kDenseEdgeSeconds = 9.9e-12;
-constexpr double kDenseChunkSeconds = 1.50e-6;
+constexpr double kDenseChunkSeconds = 0.97e-6;
 constexpr double kDenseLaunchSeconds = 7.0e-6;
 constexpr double kDenseMinSaving = 25.0e-6;     // margin: a saving below the run-to-run spread (1.5 % of the headline) is none
 constexpr double kDenseMinShare = 0.03;         // of the edges

@@ -5,13 +5,20 @@
 // 128-byte requests each (gnna_sweep.hip) and carry one bit of information.  gnna_prepare_graph therefore splits the
 // adjacency of a swept graph as A = A_res + A_hub:
 //
-//   * A_hub is the H x H block of the hubs (the nodes of degree >= theta, ranked by node id) as a BITMAP.  One 64-bit
-//     word holds 16 destination ranks x 4 source ranks -- bit (dst % 16) + 16 * (src % 4) -- which is the lane order of
-//     the A operand of v_mfma_f32_16x16x4_f32: the operand of a wavefront is 1.0f where its lane's bit is set;
+//   * A_hub is the H x H block of the hubs (the nodes of degree >= theta, ranked by node id) as a BITMAP of H_pad^2 / 8 bytes
+//     (8 MB at 8,192 hubs, 32 MB at 16,384).  A 32 x 32 tile of it is 64 16-bit halves, half l = (dst % 16) + 16 * (src % 32 / 8)
+//     holding bit (src % 8) + 8 * (dst % 32 / 16): byte t of half l is what lane l of a wavefront needs of the A operand of
+//     v_mfma_f32_16x16x32_bf16 for the tile's t-th 16 destination ranks (element j of the lane = source rank 8 (l / 16) + j);
 //   * A_res is everything else, as a residual graph with the caller's part2Node and group count: new part_pointers
 //     (groups only shrink; some become empty) and a compacted column_index.  The sweep kernel runs on it;
-//   * hub_block_kernel then adds Y[node(i), :] += scale(i) * sum_j bit(i, j) * X[node(j), :] with f32 MFMA (inputs and
-//     accumulation in fp32: the products are exact, the sums are fp32 sums in another order).
+//   * hub_block_kernel then adds Y[node(i), :] += scale(i) * sum_j bit(i, j) * X[node(j), :] with bf16 MFMA on an EXACT
+//     three-way split of X.  A fp32 value is the sum of three bf16 values: hi = x with its low 16 bits cleared, mid = (x - hi)
+//     with its low 16 bits cleared, lo = x - hi - mid.  Each has 8 significant bits and both subtractions are exact (24 = 8 +
+//     8 + 8 bits; a remainder has its leading bit lower, never more bits).  The bitmap operand is 0 or 1, so every product is
+//     exact, and what is rounded are fp32 sums as before: the hi products in one accumulator (one rounding per 32 source
+//     ranks, however the matrix unit adds inside an instruction), the mid and lo products -- 2^-8 and 2^-16 of them -- in
+//     another, the two added once at the end.  (A lo piece below 2^-126 is a bf16 subnormal and may be dropped: an error
+//     below 2^-126 per term.)
 //
 // Multiplicity: the C ABI accepts rows with repeated ids.  The edge that finds its bit already set (atomicOr) is a repeat
 // and stays in the residual; that decision is recorded once per edge in a bit array, which the count pass and the fill
@@ -29,7 +36,10 @@
 // of their choosing); GNNA_DENSE_BLOCK_LOG = 1 prints the block taken (theta, H, entries, density) to stderr.
 //
 // Non-finite features: 0 * Inf is NaN, so an Inf or NaN in the features of one hub reaches every hub's row through the
-// block, not only its neighbours' (the gather would hand it to the neighbours alone).
+// block, not only its neighbours' (the gather would hand it to the neighbours alone): 1 * Inf at the neighbours, NaN at the
+// others.  The split leaves a non-finite x in hi (its mid and lo are NaN); every source rank is multiplied into every
+// row, so a finite hi sum says that no source was non-finite, an infinite one is the result, and a wavefront adds its mid/lo
+// sum only to a hi sum that is not infinite.  (A NaN whose payload lies in its low 16 bits alone is taken for an infinity.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -54,9 +64,9 @@ constexpr int kHubTileM = kDenseTileRanks;    // destination ranks per workgroup
 constexpr int kHubKC = kDenseChunkRanks;      // source ranks staged in LDS at a time; the ranks are padded to a multiple of it
 static_assert(kHubTileM == 32, "two MFMA tiles per workgroup");
 constexpr int kHubStage = kHubKC / 32;   // 16-byte pieces a thread stages per chunk
-constexpr int kHubRowStride = 80;        // floats between staged rows (16-byte aligned; the 4 rows of a step start 16 banks apart)
-static_assert(kHubKC % kHubTileM == 0 && kHubKC * 16 == kHubThreads * kHubStage && kHubKC / 4 * 2 == kWave, "staging; one bitmap word per lane");
-static_assert((kHubKC / 4) % kHubWaves == 0 && (kHubTileM * 64) % kHubThreads == 0, "steps per wavefront, elements per thread");
+constexpr int kHubZeros = 64;            // zero floats behind the ranks of a block: the row a padding rank reads
+static_assert(kHubKC % kHubTileM == 0 && kHubKC * 16 == kHubThreads * kHubStage && (kHubTileM * 64) % kHubThreads == 0, "staging, elements per thread");
+static_assert(kHubZeros >= kDenseMaxDim, "the zeros are a whole row");
 
 // Half-octave bucket of a degree: 2 k for 2^k <= d < sqrt(2) 2^k, 2 k + 1 for sqrt(2) 2^k <= d < 2^(k + 1); 0 for d <= 1.
 // Monotone in d, so "bucket >= b" is "degree >= theta_b".
@@ -133,7 +143,7 @@ hub_rank_kernel(const int32_t *__restrict__ r2n, int H, int64_t N, int32_t *__re
 // gather (taken[e] = 1), every later edge with the same (dst, src) finds the bit set and stays in the residual.
 __global__ void __launch_bounds__(kBlock)
 hub_bitmap_kernel(const int32_t *__restrict__ col, const int32_t *__restrict__ pp, const int32_t *__restrict__ p2n, int64_t P, int64_t N,
-                  const int32_t *__restrict__ n2r, int words_per_tile_row, unsigned long long *__restrict__ bm,
+                  const int32_t *__restrict__ n2r, int steps, uint32_t *__restrict__ bm,
                   uint32_t *__restrict__ taken, unsigned long long *__restrict__ total)
 {
     const int lane = threadIdx.x & (kWave - 1);
@@ -151,9 +161,9 @@ hub_bitmap_kernel(const int32_t *__restrict__ col, const int32_t *__restrict__ p
             if (s < 0 || s >= N) continue;
             const int rs = n2r[s];
             if (rs < 0) continue;
-            const size_t word = (size_t)(rd >> 4) * (size_t)words_per_tile_row + (size_t)(rs >> 2);
-            const unsigned long long bit = 1ull << ((rd & 15) + 16 * (rs & 3));
-            const unsigned long long old = atomicOr(&bm[word], bit);
+            const size_t half = ((size_t)(rd >> 5) * (size_t)steps + (size_t)(rs >> 5)) * 64 + (size_t)((rd & 15) + 16 * ((rs & 31) >> 3));
+            const uint32_t bit = 1u << (16 * (int)(half & 1) + 8 * ((rd >> 4) & 1) + (rs & 7));
+            const uint32_t old = atomicOr(&bm[half >> 1], bit);
             if (!(old & bit)) {
                 atomicOr(&taken[(uint32_t)e >> 5], 1u << (e & 31));
                 mine++;
@@ -211,8 +221,8 @@ hub_res_fill_kernel(const int32_t *__restrict__ col, const int32_t *__restrict__
 struct HubParams {
     const float *X;
     float *Y;
-    const int32_t *r2n;                  // [H_pad] rank -> node, -1 for the padding ranks
-    const unsigned long long *bm;        // [H_pad / 16][H_pad / 4] words
+    const int32_t *r2n;                  // [H_pad] rank -> node, -1 for the padding ranks; then kHubZeros zero floats
+    const uint16_t *bm;                  // [H_pad / 32][H_pad / 32][64] halves (the header of this file)
     const float *row_scale;
     const int32_t *stale;
     int32_t seq;
@@ -221,184 +231,239 @@ struct HubParams {
     float eps;
 };
 
-// A workgroup owns 32 destination ranks (two MFMA tiles) and walks ALL source ranks, 128 at a time.  The 128 source rows of a
-// chunk are staged in one of TWO LDS images (zero beyond D and for padding ranks): while chunk c is multiplied out of one
-// image, the rows of chunk c + 1 are written into the other, and the loads of chunks c + 2 and c + 3 are in flight -- one
-// barrier per chunk, and a load has two chunks' time to arrive.  Its 8 wavefronts split the 32 four-rank steps of a chunk:
-// wavefront w takes steps 4 w .. 4 w + 3 of both tiles.  Per step lane (k, j) = (lane / 16, lane % 16) reads
-// X[rank k0 + k][16 q + j] for q = 0 .. NT - 1: the B operands of NT MFMAs, MFMA q covering the columns 16 q .. 16 q + 15
-// (NT = 3 for D <= 48, 4 beyond).  A wavefront issues the B reads of all its four steps first; its 8 NT MFMAs then follow with
-// no branch between them, and the LDS writes of the next chunk and the loads of the chunk after the next two sit one by one
-// between the half steps, in the shadow of the matrix unit.  The A operand is the tile's bitmap word.  Accumulator register r of MFMA q
-// holds Y[rank 4 (lane / 16) + r][16 q + lane % 16].  At the end the 8 partial tiles are laid side by side in LDS (over the
-// images) and summed in wavefront order, and the workgroup -- the only writer of its 32 rows in this launch, behind the sweep
-// kernel of the same call -- adds the tile to Y with plain loads and stores: no atomics, and a result that does not depend
-// on timing.  FULL: D and ldx are multiples of 4, so every staged 16-byte piece is whole.
-// (Measured on the headline's block of 8,192 hubs, profiles/dense_block and profiles/hub_block_rate: partial tiles of a
-// split over source ranks added with float atomics -- 183 us; 64-rank chunks, one chunk in flight -- 367 us; one image, two
-// barriers per chunk, an LDS read waited for before every pair of MFMAs -- 130 us.)
+typedef typename VecOf<4>::T HubVT;
+typedef typename VecOf<4>::M HubMT;
+typedef int HubIT __attribute__((ext_vector_type(4)));
+
+constexpr int kHubFrag = 1088;           // bytes between the B fragments of an image: 64 lanes x 16 bytes, and 64 (see the LDS image)
+constexpr int kHubPiece = 16 * kHubFrag; // bytes between the hi, mid and lo images of a chunk (4 steps x 4 column tiles)
+constexpr int kHubImage = 3 * kHubPiece; // 52,224 bytes per chunk
+static_assert(kHubKC == 128 && kHubTileM == 32 && kHubWaves == 8 && kHubStage == 4, "the shape hub_block_kernel is written for");
+
+typedef __bf16 HubFrag __attribute__((ext_vector_type(8)));
+typedef uint32_t HubU4 __attribute__((ext_vector_type(4)));
+typedef uint32_t HubU2 __attribute__((ext_vector_type(2)));
+
+// x = hi + mid + lo exactly, each with 8 significant bits in the upper half of its word (a bf16 value): hi is x truncated, mid
+// the truncated remainder, lo what is left of at most 24 bits; both subtractions are exact.  A non-finite x is in hi, with NaN
+// for mid and lo (the header of this file: the end of hub_block_kernel deals with it).
+// (A lo below 2^-126 is a bf16 subnormal whose low bits, and possibly all of it, are dropped: less than 2^-126 per term.)
+__device__ __forceinline__ void hub_split(uint32_t x, uint32_t &hi, uint32_t &mid, uint32_t &lo)
+{
+    hi = x & 0xffff0000u;
+    const float r = __uint_as_float(x) - __uint_as_float(hi);
+    mid = __float_as_uint(r) & 0xffff0000u;
+    lo = __float_as_uint(r - __uint_as_float(mid));
+}
+
+// the upper halves of two words as one: `first` below `second`
+__device__ __forceinline__ uint32_t hub_pack(uint32_t first, uint32_t second) { return __builtin_amdgcn_perm(second, first, 0x07060302u); }
+
+// 8 bitmap bits -> 8 bf16 of 0 or 1 (0x3f80), element j from bit j
+__device__ __forceinline__ HubFrag hub_ones(uint32_t bits)
+{
+    const uint32_t y = bits | (bits << 15);          // bit j at j and at j + 15: bits 2 i and 2 i + 1 are 16 apart
+    HubU4 v;
+#pragma unroll
+    for (int i = 0; i < 4; i++) v[i] = ((y >> (2 * i)) & 0x10001u) * 0x3f80u;
+    return __builtin_bit_cast(HubFrag, v);
+}
+
+// A workgroup owns 32 destination ranks (two 16-rank MFMA tiles) and walks ALL source ranks, 128 at a time, with
+// v_mfma_f32_16x16x32_bf16: A is 16 destination ranks x 32 source ranks of the bitmap (0 or 1), B is 32 source ranks x 16
+// columns of ONE of the three bf16 pieces of X.  Every product is exact; the hi products are summed in one fp32 accumulator, the
+// mid and lo products in another, and the two are added once at the end.
+//
+// Staging.  Thread t fetches 16 bytes (4 columns) of each of 4 consecutive ranks (their four ids are one 16-byte load), splits
+// the 16 values as they go to LDS and writes, per column and piece, the 4 ranks as 8 bytes.  No branch on the way and nothing
+// to mask: a padding rank reads the zeros behind the ranks, and a piece beyond D reads piece 0 into columns of the image whose
+// products are never written to Y.  Within a wavefront, lanes 8 apart take adjacent rank groups and lanes 16 apart take
+// columns 32 apart (below: why).
+//
+// The LDS image of a chunk: [piece 3][step 4][column tile 4] fragments of 64 x 16 bytes, kHubFrag bytes apart.  A fragment is the B
+// operand of one MFMA: 16 bytes = the 8 ranks 8 kg .. 8 kg + 7 of a step at one column n, in slot 16 kg + 4 (n % 4) + n / 4.
+// Read (ds_read_b128, lane = 16 kg + n): the 16 lanes of a service group fall on 16 different slots modulo 16: no conflict.
+// Written (ds_write_b64; a service group is 16 consecutive lanes = columns 4 i + cc of two adjacent column tiles for i = 0 .. 3,
+// and both halves h of the slots): byte 64 (tile + cc) + 16 i + 8 h modulo 128, the 64 from kHubFrag: all 32 banks once.
+//
+// The 8 wavefronts split a chunk as (step s = w % 4, column half w / 4): a wavefront reads the 3 pieces of its 2 column tiles (1
+// for the upper half when NT = 3) and multiplies each with the bitmap bytes of both destination tiles: 12 MFMAs.  Two images
+// take the chunks in turn: while chunk c is multiplied out of one, chunk c + 1 goes into the other, chunk c + 2 is in
+// registers or on its way and chunk c + 3 is asked for (three register stages); one barrier per chunk.  At the end the
+// four steps' partial tiles are laid side by side in LDS (over the images) and summed in step order, and the workgroup --
+// the only writer of its 32 rows in this launch, behind the sweep kernel of the same call -- adds the tile to Y with plain
+// loads and stores: no atomics, and a result that does not depend on timing.  FULL: D and ldx are multiples of 4, so every
+// staged 16-byte piece is whole.
 template <int NT, bool FULL>
 __global__ void __launch_bounds__(kHubThreads)
 hub_block_kernel(const HubParams p)
 {
-    typedef typename VecOf<4>::T VT;
-    typedef typename VecOf<4>::M MT;
     if (*p.stale == p.seq) return;       // the ids changed since the block was made: the sweep kernel does the whole call
-    __shared__ __attribute__((aligned(16))) float s_x[2][kHubKC * kHubRowStride];
-    static_assert(kHubWaves * kHubTileM * 64 <= 2 * kHubKC * kHubRowStride, "the partial tiles fit over the images");
+    __shared__ __attribute__((aligned(16))) unsigned char s_x[2][kHubImage];
+    static_assert(4 * kHubTileM * 64 * 4 <= kHubImage, "the partial tiles fit over the first image");
+    const uint16_t *bm = p.bm;
     const int tid = (int)threadIdx.x;
     const int lane = tid & (kWave - 1);
     const int wib = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int chunks = p.H_pad / kHubKC;
-    const int words_per_tile_row = p.H_pad >> 2;
-    const int tile0 = (int)blockIdx.x * (kHubTileM / 16);  // the workgroup's first 16-rank tile
+    const int steps = p.H_pad >> 5;      // 32-rank steps of a row of the bitmap
     const int D = p.D;
 
-    // staging: thread t fetches piece t % 16 of the chunk's rows 4 (t / 16) .. 4 (t / 16) + 3 (their four ids are one 16-byte
-    // load).  No branch on the way: a padding rank reads row 0 and a piece beyond D reads piece 0; what they fetched is masked
-    // away when the piece goes to LDS (not before: touching a loaded value where it is loaded would wait for it there)
-    typedef int IT __attribute__((ext_vector_type(4)));
-    const int srow = (tid >> 4) * kHubStage, spiece = (tid & 15) * 4;
-    const bool live = spiece < D;
-    const int scol = live ? spiece : 0;
-    auto load_piece = [&](int node) -> VT {
-        const float *src = p.X + (size_t)(node < 0 ? 0 : node) * (size_t)p.ldx + scol;
-        VT v;
+    // staging: 4 ranks from 4 g, 4 columns from 4 pc
+    const int g = 4 * (tid >> 6) + ((lane >> 3) & 1) + 2 * (lane >> 5), pc = (lane & 7) + 8 * ((lane >> 4) & 1);
+    const int srow = 4 * g, spiece = 4 * pc;
+    const int scol = spiece < D ? spiece : 0;                // (a piece beyond D feeds columns that are never written to Y)
+    const int wbase = ((g >> 3) * 4 + (pc >> 2)) * kHubFrag + (16 * ((g & 7) >> 1) + (pc & 3)) * 16 + 8 * (g & 1);
+    const float *zero_row = reinterpret_cast<const float *>(p.r2n + p.H_pad);    // 64 zeros behind the ranks: what a padding rank reads
+    const uintptr_t zero_at = reinterpret_cast<uintptr_t>(zero_row + scol);
+    auto load_piece = [&](int node) -> HubVT {
+        // (one address, chosen without a branch: a padding rank reads the zeros)
+        const uintptr_t row = reinterpret_cast<uintptr_t>(p.X + (size_t)(node < 0 ? 0 : node) * (size_t)p.ldx + scol);
+        const float *src = reinterpret_cast<const float *>(node < 0 ? zero_at : row);
+        HubVT v;
         if constexpr (FULL) {
-            v = *reinterpret_cast<const MT *>(src);
+            v = *reinterpret_cast<const HubMT *>(src);
         } else if (spiece + 4 <= D) {
-            v = *reinterpret_cast<const MT *>(src);
+            v = *reinterpret_cast<const HubMT *>(src);
         } else {
-            v = vzero<4>();
+            v = (HubVT)(0.f);
 #pragma unroll
             for (int q = 0; q < 4; q++)
                 if (spiece + q < D) v[q] = src[q];
         }
         return v;
     };
-    // Two stages take the chunks in turn (s0 the even ones, s1 the odd ones); the node ids of a stage's NEXT chunk are
-    // fetched behind the rows of the current one, so a row address never waits for an id that is younger than the rows the
-    // same wait is for.  A chunk beyond the last is the last one again: fetched, never multiplied.
+    // Three stages take the chunks in turn (chunk c lives in stage c % 3): rows, bitmap bytes and the node ids of the chunk
+    // that FOLLOWS in the same stage, fetched behind the rows, so a row address never waits for an id that is younger than
+    // the rows the same wait is for.  A chunk beyond the last is the last one again: fetched, never multiplied.
     struct Stage {
-        VT r[kHubStage];
-        IT node;
-        uint32_t keep[kHubStage];        // all ones, or zero for a padding rank and for a piece beyond D
+        HubVT r[kHubStage];
+        HubIT node;
+        uint32_t w;                      // this wavefront's step of the bitmap: byte 0 the first destination tile, byte 1 the second
     };
     auto fetch_ids = [&](int c, Stage &st) {
         const int cc = c < chunks ? c : chunks - 1;
-        st.node = *reinterpret_cast<const IT *>(&p.r2n[cc * kHubKC + srow]);
+        st.node = *reinterpret_cast<const HubIT *>(&p.r2n[cc * kHubKC + srow]);
     };
-    auto fetch_row = [&](int i, Stage &st) {                 // piece i of the chunk whose ids are in st.node
-        st.r[i] = load_piece(st.node[i]);
-        st.keep[i] = (st.node[i] >= 0 && live) ? 0xffffffffu : 0u;
-    };
-    // the bitmap words of chunk c: lanes 0 .. 31 the 32 words of the first tile, lanes 32 .. 63 of the second
-    auto fetch_words = [&](int c) -> unsigned long long {
+    auto fetch_words = [&](int c, Stage &st) {
         const int cc = c < chunks ? c : chunks - 1;
-        return p.bm[(size_t)(tile0 + (lane >> 5)) * (size_t)words_per_tile_row + (size_t)(cc * (kHubKC / 4) + (lane & 31))];
+        st.w = bm[((size_t)blockIdx.x * (size_t)steps + (size_t)(cc * 4 + (wib & 3))) * 64 + (size_t)lane];
     };
-    // rows of chunk c (its ids are in st.node), the words of chunk cw, the ids of chunk c + 2: the order of a turn's loads
-    auto fetch = [&](int c, Stage &st, unsigned long long &w, int cw) {
-#pragma unroll
-        for (int i = 0; i < kHubStage; i++) fetch_row(i, st);
-        w = fetch_words(cw);
-        fetch_ids(c + 2, st);
+    auto fetch_row = [&](int i, Stage &st) {                 // row i of the chunk whose ids are in st.node
+        st.r[i] = load_piece(st.node[i]);
     };
-    auto stage_out = [&](int i, const Stage &st, float *image) {
-        VT v = st.r[i];
+    // column cc of the thread's 4 x 4 values: split, packed by rank pairs, 8 bytes per piece
+    auto stage_out = [&](int cc, const Stage &st, unsigned char *image) {
+        uint32_t pk[3][2];
 #pragma unroll
-        for (int q = 0; q < 4; q++) v[q] = __uint_as_float(__float_as_uint(v[q]) & st.keep[i]);
-        *reinterpret_cast<VT *>(&image[(srow + i) * kHubRowStride + spiece]) = v;
+        for (int h = 0; h < 2; h++) {
+            uint32_t a[3], b[3];
+            hub_split(__float_as_uint(st.r[2 * h][cc]), a[0], a[1], a[2]);
+            hub_split(__float_as_uint(st.r[2 * h + 1][cc]), b[0], b[1], b[2]);
+#pragma unroll
+            for (int i = 0; i < 3; i++) pk[i][h] = hub_pack(a[i], b[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            HubU2 v;
+            v[0] = pk[i][0];
+            v[1] = pk[i][1];
+            *reinterpret_cast<HubU2 *>(&image[wbase + i * kHubPiece + cc * 64]) = v;
+        }
     };
 
-    VT acc[2][NT];
+    const int cs = wib & 3, ch = wib >> 2;                  // this wavefront's step of a chunk and its half of the columns
+    const int rbase = (cs * 4 + 2 * ch) * kHubFrag + (16 * (lane >> 4) + 4 * (lane & 3) + ((lane & 15) >> 2)) * 16;
+    HubVT acc_hi[2][2], acc_lo[2][2];                           // [destination tile][column tile of the half]
 #pragma unroll
     for (int t = 0; t < 2; t++)
 #pragma unroll
-        for (int q = 0; q < NT; q++) acc[t][q] = vzero<4>();
+        for (int q = 0; q < 2; q++) acc_hi[t][q] = acc_lo[t][q] = (HubVT)(0.f);
 
-    // Chunk c out of `cur` with the words w, which then become those of chunk c + 2 (a wavefront moves its eight words to
-    // scalar registers first: no copy of a loaded register, which would wait for the load where the copy stands); st holds
-    // chunk c + 1, which goes into `nxt`, and then starts on chunk c + 3.  The ten memory
-    // operations of a turn (4 LDS writes, 6 loads) are spread over the gaps between the eight half steps of MFMAs and
-    // pinned there: issued in one burst by all eight wavefronts they fill the queue of the compute unit's address unit (a
-    // chunk's 32 KB keep it busy for about half of a chunk's MFMA time), a wavefront stands at its next load until the
-    // queue has room, and no MFMA is issued meanwhile (stamped: 600 - 1,100 cycles per chunk for the nine loads of a burst).
-    auto turn = [&](int c, Stage &st, unsigned long long &w, const float *cur, float *nxt) {
-        constexpr int kSteps = kHubKC / 4 / kHubWaves;
-        static_assert(kSteps == 4 && kHubStage == 4, "the places of the memory operations between the half steps");
-        float b[kSteps][NT];
+    // Chunk c out of image c % 2 with the bitmap bytes of stage L, which then starts on chunk c + 3; stage S holds chunk c + 1,
+    // which goes into the other image.  A turn is four parts, pinned in this order: a load of L, the MFMAs of one piece (hi, mid,
+    // lo, none), one column of S split and written.  The loads are spread like this because the compute unit's address unit
+    // takes about as long for a chunk's 32 KB as the rest of the turn does: issued in one burst by all eight wavefronts they
+    // fill its queue, a wavefront stands at its next load until the queue has room, and nothing else is issued meanwhile.
+    auto turn = [&](int c, Stage &L, const Stage &S) {
+        const unsigned char *cur = s_x[c & 1];
+        unsigned char *nxt = s_x[(c & 1) ^ 1];
+        __builtin_amdgcn_sched_barrier(0);
+        HubFrag b[2][3];
 #pragma unroll
-        for (int j = 0; j < kSteps; j++) {
-            const float *xs = &cur[((wib * kSteps + j) * 4 + (lane >> 4)) * kHubRowStride + (lane & 15)];
+        for (int i = 0; i < 3; i++)
 #pragma unroll
-            for (int q = 0; q < NT; q++) b[j][q] = xs[q * 16];
-        }
-        __builtin_amdgcn_sched_barrier(0);                   // every B read is issued before the first MFMA
-        const int w_lo = (int)(uint32_t)w, w_hi = (int)(uint32_t)(w >> 32);
-        unsigned long long m[2][kSteps];
-#pragma unroll
-        for (int t = 0; t < 2; t++)
-#pragma unroll
-            for (int j = 0; j < kSteps; j++) {
-                const int s = 32 * t + wib * kSteps + j;
-                m[t][j] = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane(w_hi, s) << 32) | (uint32_t)__builtin_amdgcn_readlane(w_lo, s);
-            }
+            for (int q = 0; q < 2; q++)
+                if (NT == 4 || q == 0 || ch == 0) b[q][i] = *reinterpret_cast<const HubFrag *>(&cur[rbase + q * kHubFrag + i * kHubPiece]);
+        HubFrag a[2];
+        a[0] = hub_ones(L.w & 0xffu);
+        a[1] = hub_ones((L.w >> 8) & 0xffu);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int j = 0; j < kSteps; j++) {
-            const float a0 = __builtin_amdgcn_inverse_ballot_w64(m[0][j]) ? 1.f : 0.f;   // (one v_cndmask on the scalar word)
-            const float a1 = __builtin_amdgcn_inverse_ballot_w64(m[1][j]) ? 1.f : 0.f;
+        for (int k = 0; k < 4; k++) {
+            fetch_row(k, L);
+            if (k < 3) {
 #pragma unroll
-            for (int h = 0; h < 2; h++) {
+                for (int q = 0; q < 2; q++)
+                    if (NT == 4 || q == 0 || ch == 0) {
 #pragma unroll
-                for (int q = 2 * h; q < 2 * h + 2 && q < NT; q++) {
-                    acc[0][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b[j][q], acc[0][q], 0, 0, 0);
-                    acc[1][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b[j][q], acc[1][q], 0, 0, 0);
-                }
-                const int k = 2 * j + h;
-                if (k < 2) {
-                    stage_out(2 * k, st, nxt);
-                    stage_out(2 * k + 1, st, nxt);
-                } else if (k < 6) {
-                    fetch_row(k - 2, st);
-                } else if (k == 6) {
-                    w = fetch_words(c + 2);
-                    fetch_ids(c + 5, st);
-                }
-                __builtin_amdgcn_sched_barrier(0);
+                        for (int t = 0; t < 2; t++) {
+                            if (k == 0) acc_hi[t][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], b[q][0], acc_hi[t][q], 0, 0, 0);
+                            else acc_lo[t][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], b[q][k], acc_lo[t][q], 0, 0, 0);
+                        }
+                    }
             }
+            stage_out(k, S, nxt);
+            __builtin_amdgcn_sched_barrier(0);
         }
+        fetch_words(c + 3, L);
+        fetch_ids(c + 6, L);
+        __builtin_amdgcn_sched_barrier(0);
         __syncthreads();                                     // `nxt` is whole, and `cur` has been read by every wavefront
     };
-    Stage s0, s1;
+    Stage s0, s1, s2;
     fetch_ids(0, s0);
     fetch_ids(1, s1);
-    unsigned long long w0, w1;           // the words of the even and of the odd chunks
-    fetch(0, s0, w0, 0);
-    fetch(1, s1, w0, 0);
+    fetch_ids(2, s2);
+    // (the order of the loads is that of the turns, and pinned: the counted waits of the loop are those of its entry as well)
+    auto fetch = [&](int c, Stage &st) {
 #pragma unroll
-    for (int i = 0; i < kHubStage; i++) stage_out(i, s0, s_x[0]);
-    fetch(2, s0, w1, 1);
+        for (int i = 0; i < kHubStage; i++) fetch_row(i, st);
+        fetch_words(c, st);
+        fetch_ids(c + 3, st);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    fetch(0, s0);
+    fetch(1, s1);
+    fetch(2, s2);
+#pragma unroll
+    for (int cc = 0; cc < 4; cc++) stage_out(cc, s0, s_x[0]);
+    __builtin_amdgcn_sched_barrier(0);
     __syncthreads();
-    // (two turns per trip and the odd last chunk outside: a branch inside the loop would make the waits of the trip after it
-    // cover the loads of both stages)
-    for (int c = 0; c + 1 < chunks; c += 2) {
-        turn(c, s1, w0, s_x[0], s_x[1]);
-        turn(c + 1, s0, w1, s_x[1], s_x[0]);
+    int c = 0;
+    for (; c + 3 <= chunks; c += 3) {
+        turn(c, s0, s1);
+        turn(c + 1, s1, s2);
+        turn(c + 2, s2, s0);
     }
-    if (chunks & 1) turn(chunks - 1, s1, w0, s_x[0], s_x[1]);
+    if (c < chunks) {
+        turn(c, s0, s1);
+        if (c + 1 < chunks) turn(c + 1, s1, s2);
+    }
 
-    // the 8 partial tiles of the workgroup's 32 rows, side by side, then summed in wavefront order
+    // the 4 partial tiles of the workgroup's 32 rows, side by side, then summed in step order
     // (the last turn ended with a barrier: nobody reads the images any more)
-    float *part = &s_x[0][0];            // [wavefront][32 ranks][64 columns]; the columns from 16 NT on stay unwritten and unread
+    float *part = reinterpret_cast<float *>(&s_x[0][0]);     // [step][32 ranks][64 columns]; the columns from 16 NT on stay unwritten and unread
 #pragma unroll
     for (int t = 0; t < 2; t++)
 #pragma unroll
-        for (int q = 0; q < NT; q++)
+        for (int q = 0; q < 2; q++)
+            if (NT == 4 || q == 0 || ch == 0) {
 #pragma unroll
-            for (int r = 0; r < 4; r++)
-                part[(wib * kHubTileM + t * 16 + (lane >> 4) * 4 + r) * 64 + q * 16 + (lane & 15)] = acc[t][q][r];
+                for (int r = 0; r < 4; r++)
+                    part[(cs * kHubTileM + t * 16 + (lane >> 4) * 4 + r) * 64 + (2 * ch + q) * 16 + (lane & 15)] =
+                        __builtin_isinf(acc_hi[t][q][r]) ? acc_hi[t][q][r] : acc_hi[t][q][r] + acc_lo[t][q][r];
+            }
     __syncthreads();
     // one plain read-add-write of Y per element
 #pragma unroll
@@ -408,8 +473,8 @@ hub_block_kernel(const HubParams p)
         if (col >= D) continue;
         float sum = part[idx];
 #pragma unroll
-        for (int w = 1; w < kHubWaves; w++) sum += part[w * kHubTileM * 64 + idx];
-        const int node = p.r2n[tile0 * 16 + row];
+        for (int s = 1; s < 4; s++) sum += part[s * kHubTileM * 64 + idx];
+        const int node = p.r2n[(int)blockIdx.x * kHubTileM + row];
         if (node < 0 || sum == 0.f) continue;
         float scale = 1.f;
         if (p.scaled) {
@@ -528,24 +593,25 @@ int build_dense_block(DeviceState *ds, hipStream_t stream, const int32_t *col, c
     std::copy(ids.begin(), ids.end(), ranks.begin());
     std::sort(ranks.begin(), ranks.begin() + H);
 
-    const size_t r2n_b = align256((size_t)H_pad * 4);
-    const size_t bm_b = align256((size_t)(H_pad / 16) * (size_t)(H_pad / 4) * 8), rpp_b = align256((size_t)(P + 1) * 4);
+    const size_t r2n_b = align256((size_t)H_pad * 4 + kHubZeros * 4);
+    const size_t bm_b = align256((size_t)H_pad * (size_t)H_pad / 8), rpp_b = align256((size_t)(P + 1) * 4);
     void *blk = nullptr;
     e = hipMalloc(&blk, r2n_b + bm_b + rpp_b);
     count_event(CTR_LAUNCH_MALLOCS);
     if (e != hipSuccess) { (void)hipGetLastError(); return GNNA_OK; }
     char *bb = static_cast<char *>(blk);
     int32_t *r2n = reinterpret_cast<int32_t *>(bb);
-    unsigned long long *bm = reinterpret_cast<unsigned long long *>(bb + r2n_b);
+    uint32_t *bm = reinterpret_cast<uint32_t *>(bb + r2n_b);
     int32_t *res_pp = reinterpret_cast<int32_t *>(bb + r2n_b + bm_b);
     int32_t *res_col = nullptr;
     auto give_up = [&](int rc) { (void)hipStreamSynchronize(stream); (void)hipFree(blk); if (res_col) (void)hipFree(res_col); return rc; };
     e = hipMemcpy(r2n, ranks.data(), (size_t)H_pad * 4, hipMemcpyHostToDevice);
     if (e != hipSuccess) return give_up(fail(GNNA_ERR_HIP, "dense block (ranks): %s", hipGetErrorString(e)));
     (void)hipMemsetAsync(n2r, 0xff, n2r_b, stream);
+    (void)hipMemsetAsync(r2n + H_pad, 0, kHubZeros * 4, stream);
     (void)hipMemsetAsync(bm, 0, bm_b, stream);
     hipLaunchKernelGGL(hub_rank_kernel, dim3((unsigned)((H + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, r2n, (int)H, N, n2r);
-    hipLaunchKernelGGL(hub_bitmap_kernel, dim3(wblocks), dim3(kBlock), 0, stream, col, pp, p2n, P, N, n2r, H_pad / 4, bm, taken, taken_total);
+    hipLaunchKernelGGL(hub_bitmap_kernel, dim3(wblocks), dim3(kBlock), 0, stream, col, pp, p2n, P, N, n2r, H_pad / 32, bm, taken, taken_total);
     hipLaunchKernelGGL(hub_res_count_kernel, dim3(elementwise_grid(P + 1, ds->num_cus, 8)), dim3(kBlock), 0, stream, pp, P, taken, res_pp);
     int rc = launch_exclusive_scan(stream, res_pp, P + 1, partial);
     if (rc != GNNA_OK) return give_up(rc);
@@ -578,7 +644,7 @@ int launch_hub_block(DeviceState *ds, hipStream_t stream, const DenseBlock &db, 
                      bool scaled, float eps, const float *row_scale, const int32_t *stale_flag, int32_t seq)
 {
     HubParams p;
-    p.X = X; p.Y = Y; p.r2n = db.r2n; p.bm = static_cast<const unsigned long long *>(db.bm); p.row_scale = row_scale;
+    p.X = X; p.Y = Y; p.r2n = db.r2n; p.bm = static_cast<const uint16_t *>(db.bm); p.row_scale = row_scale;
     p.stale = stale_flag; p.seq = seq; p.H_pad = db.H_pad; p.D = dim; p.ldx = ldx; p.ldy = ldy;
     p.scaled = scaled ? 1 : 0; p.eps = eps;
     (void)ds;

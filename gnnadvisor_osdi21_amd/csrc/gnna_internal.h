@@ -199,8 +199,8 @@ struct QuietBuilds {
 // ---- dense hub-to-hub block of a prepared graph (gnna_dense.hip) ----------------------------------------------------
 struct DenseBlock {
     void *buf = nullptr;              // one allocation: r2n, node -> rank map, bm, res_pp
-    const int32_t *r2n = nullptr;     // [H_pad] rank -> node (-1: padding)
-    const void *bm = nullptr;         // [H_pad / 16][H_pad / 4] 64-bit words: 16 destination ranks x 4 source ranks each
+    const int32_t *r2n = nullptr;     // [H_pad] rank -> node (-1: padding), then 64 zero floats (what a padding rank reads)
+    const void *bm = nullptr;         // [H_pad / 32][H_pad / 32][64] 16-bit halves: 2 x 16 destination ranks x 8 source ranks each
     const int32_t *res_pp = nullptr;  // part_pointers of the residual graph (same part2Node, same group count)
     int32_t *res_col = nullptr;       // its column ids (an allocation of its own)
     const uint8_t *res_cnt = nullptr; // its slice counts: those of its slice plan
