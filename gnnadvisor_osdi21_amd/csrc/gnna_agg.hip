@@ -414,27 +414,37 @@ int sweep_auto_phases(const gnna_tuning &t, int mode, int dim, size_t x_bytes, i
 // ---- the block rule -----------------------------------------------------------------------------------------------
 // The dense hub-to-hub block (gnna_dense.hip).  Modelled saving of a block of H hubs holding `entries` edges, for rows of
 // 33 .. 64 floats -- two 128-byte requests per gathered row, the only widths the block is taken at (kDenseMinDim):
-//     entries * t_edge  -  t_hub(H)  -  t_launch,      t_hub(H) = rounds * (H_pad / 128) * t_chunk
-// t_edge: what the sweep kernel pays per edge.  t_chunk: what a workgroup of hub_block_kernel takes per 128 source ranks;
-// rounds = workgroups (H_pad / 32) over compute units, rounded up.  All measured on MI355X on the Reddit-like headline with
-// tools/probe_hub_block.py, a scan over forced hub counts under a kernel trace (profiles/hub_block_bf16/hub_count_scan.log and
-// hub_count_scan_kernels.log; the scans of the f32 forms of the kernel: profiles/hub_block_rate, profiles/dense_block):
-//   * t_edge: the sweep kernel fell from 1,335.4 to 1,172.3 us for the 16.19 M edges of 8,192 hubs: 10.1 ps per edge (11.3 at
-//     4,097 hubs, 9.7 at 12,390); 9.9 in the scan before this one, which stays;
-//   * t_chunk: hub_block_kernel (bf16 MFMA on the three-way split of X) took 62.2 us for 8,192 hubs (64 chunks, one round):
-//     0.97 us per chunk (1.50 with f32 MFMA); 1.04 at 4,224 ranks.  Two rounds: 173.2 us at 12,416 ranks, 0.89 us per chunk
-//     and round, so the model is 9 % on the safe side there -- and the step still LOSES 52 us against 8,192 hubs at that
-//     count (1.3345 against 1.2821 ms), so trimmed_hubs, kDenseMinSaving and kDenseMinShare stay as they were;
-//   * t_launch: 7 us from the scan of the first form of the kernel (profiles/dense_block/README.md); in this scan the step
-//     fell by 6.5 us less than the kernel times did.
+//     entries * t_edge  -  t_hub(H)  -  t_split  -  t_launch,      t_hub(H) = rounds * (H_pad / 128) * t_chunk(tile)
+// t_edge: what the sweep kernel pays per edge.  t_chunk: what a workgroup of hub_block_kernel takes per 128 source ranks, for
+// the tile height the launch will take (dense_tile_ranks: 32 destination ranks per workgroup while that is one round, 64
+// beyond); rounds = workgroups (H_pad / tile) over compute units, rounded up.  t_split: hub_split_kernel and the gap of its
+// launch.  All measured on MI355X on the Reddit-like headline with tools/probe_hub_block.py, a scan over forced hub counts
+// and tile heights under a kernel trace (profiles/hub_block_presplit/hub_count_scan.log and hub_count_scan_kernels.log; the
+// scans of the earlier forms of the kernel: profiles/hub_block_bf16, profiles/hub_block_rate, profiles/dense_block):
+//   * t_edge: the sweep kernel fell from 1,351.9 to 1,169.4 us (medians; minima 1,326.8 to 1,158.7) for the 16.19 M edges of
+//     8,192 hubs and to 1,126.4 (1,101.7) for the 22.71 M of 12,390: 11.3 / 9.9 ps per edge by the medians, 10.4 / 9.9 by the
+//     minima; 9.9 from the scans before this one stays;
+//   * t_chunk: hub_block_kernel, reading the split image, took 46.6 us for 8,192 hubs with 32-rank tiles (64 chunks, one round
+//     of 256 workgroups): 0.73 us per chunk (0.97 when every workgroup split X itself; 0.79 at 4,224 ranks), and 73.3 us for
+//     12,416 ranks with 64-rank tiles (97 chunks, 194 workgroups): 0.76 us per chunk (0.80 at 8,192 ranks: 51.1 us, which is
+//     why one round of short tiles stays short);
+//   * t_split: hub_split_kernel 5.2 .. 5.5 us, and the step fell by 11.6 (8,192 hubs) and 13.7 us (12,390) less than the
+//     kernel times did, where one launch's 7 us were modelled: 5.5 us of kernel and 5.5 of gap;
+//   * t_launch: 7 us from the scan of the first form of the kernel (profiles/dense_block/README.md).
+// The step at 12,390 hubs is now 14 us below the step at 8,192 (1.2534 against 1.2673 ms; before, with two rounds of short
+// tiles that split X themselves, 52 us above it), so the rule takes that block on the headline.  trimmed_hubs, kDenseMinSaving
+// and kDenseMinShare stay as they were.
 constexpr double kDenseEdgeSeconds = 9.9e-12;
-constexpr double kDenseChunkSeconds = 0.97e-6;
+constexpr double kDenseChunkSeconds = 0.73e-6;      // a 32-rank tile
+constexpr double kDenseTallChunkSeconds = 0.76e-6;  // a 64-rank tile
+constexpr double kDenseSplitSeconds = 11.0e-6;      // hub_split_kernel and its launch
 constexpr double kDenseLaunchSeconds = 7.0e-6;
 constexpr double kDenseMinSaving = 25.0e-6;     // margin: a saving below the run-to-run spread (1.5 % of the headline) is none
 constexpr double kDenseMinShare = 0.03;         // of the edges
 
 // A workgroup of hub_block_kernel owns 32 ranks and walks all of them: a few ranks beyond a whole round of workgroups (one
-// per compute unit) would double the kernel's time.  The lowest-degree hubs beyond the round stay in the gather.
+// per compute unit) would move the launch to half as many workgroups of 64 ranks, on half the compute units.  The
+// lowest-degree hubs beyond the round stay in the gather.
 int trimmed_hubs(int H, int num_cus)
 {
     const int round = kDenseTileRanks * std::max(1, num_cus);
@@ -447,9 +457,11 @@ double dense_block_saving(double hubs, double entries, int num_cus)
     if (hubs <= 0.0) return 0.0;
     const double He = (double)trimmed_hubs((int)hubs, num_cus);
     const double Hp = std::ceil(He / kDenseChunkRanks) * kDenseChunkRanks;
-    const double rounds = std::ceil(Hp / kDenseTileRanks / (double)std::max(1, num_cus));
+    const int tile = dense_tile_ranks((int)Hp, num_cus);          // (the geometry the launch will take)
+    const double rounds = std::ceil(Hp / tile / (double)std::max(1, num_cus));
+    const double t_chunk = tile == kDenseTileRanks ? kDenseChunkSeconds : kDenseTallChunkSeconds;
     const double kept = entries * (He / hubs) * (He / hubs);      // (trimmed hubs take their share of the block with them)
-    return kept * kDenseEdgeSeconds - rounds * (Hp / kDenseChunkRanks) * kDenseChunkSeconds - kDenseLaunchSeconds;
+    return kept * kDenseEdgeSeconds - rounds * (Hp / kDenseChunkRanks) * t_chunk - kDenseSplitSeconds - kDenseLaunchSeconds;
 }
 
 bool dense_block_pays(double saving, double entries, double edges) { return saving > kDenseMinSaving && entries >= kDenseMinShare * edges; }
@@ -870,10 +882,19 @@ int launch_agg(int mode, const float *input, int64_t ld_in, int64_t num_in_rows,
         if (dense) { w.res_col = db.res_col; w.res_pp = db.res_pp; w.res_cnt = db.res_cnt; w.res_ids_packed = res_ids; w.res_item_off = res_off; }
         t_last_phases = Bs;
         t_last_launches = 1;
+        // the block's operand: the hub rows of this call's X, split once into their three bf16 pieces (scratch of the call's
+        // stream: two streams may run one prepared graph on different X at once).  Ahead of the sweep: it reads X alone.
+        void *hub_image = nullptr;
+        if (dense) {
+            rc = get_workspace(ds, stream, kSlotDenseImage, dense_image_bytes(db.H_pad), &hub_image);
+            if (rc != GNNA_OK) return rc;
+            rc = launch_hub_split(stream, db, X, ldx, dim, hub_image, stale_flag, seq);
+            if (rc != GNNA_OK) return rc;
+        }
         rc = launch_sweep(ds, w, stream);
         if (rc != GNNA_OK) return rc;
         if (dense) {
-            rc = launch_hub_block(ds, stream, db, X, ldx, out, ldy, dim, mode == MODE_GIN, eps, row_scale, stale_flag, seq);
+            rc = launch_hub_block(ds, stream, db, hub_image, out, ldy, dim, mode == MODE_GIN, eps, row_scale, stale_flag, seq);
             if (rc != GNNA_OK) return rc;
         }
         profile_record(prof_call, 2, stream);
@@ -1139,7 +1160,7 @@ int gnna_prepare_graph(const int32_t *column_index, const int32_t *part_pointers
     gnna_tuning tune;
     gnna_get_tuning(&tune);
     const bool hot = plan.stats.edges >= 32.0 * (double)num_in_rows;
-    size_t staged = 0, det_bytes = 0;
+    size_t staged = 0, det_bytes = 0, hub_image = 0;
     // a width that will run in column blocks (column_blocks) is prepared as the blocks' widths: (full width, block width) pairs
     std::vector<std::pair<int, int>> widths;     // (index into dims / phases_out, width the kernels will see)
     for (int i = 0; i < num_dims; i++) {
@@ -1191,9 +1212,13 @@ int gnna_prepare_graph(const int32_t *column_index, const int32_t *part_pointers
             const bool self_swept = t.sweep == 0 && t.column_phases < 2;
             {
                 DenseBlock have;
-                if (plan_dense_block(plan.handle, &have) && have.off != (dense_mode == 0)) {
-                    have.off = dense_mode == 0;
-                    plan_set_dense_block(plan.handle, have);
+                if (plan_dense_block(plan.handle, &have)) {
+                    const int tile = dense_block_tile_env(dense_mode);
+                    if (have.off != (dense_mode == 0) || have.tile != tile) {
+                        have.off = dense_mode == 0;
+                        have.tile = tile;
+                        plan_set_dense_block(plan.handle, have);
+                    }
                 }
             }
             if (swept && ids && dense_mode != 0 && dim >= kDenseMinDim && dim <= kDenseMaxDim && num_in_rows == num_out_rows &&
@@ -1221,6 +1246,8 @@ int gnna_prepare_graph(const int32_t *column_index, const int32_t *part_pointers
                     const int32_t *rids = nullptr; const uint32_t *roff = nullptr;
                     rc = get_packed_ids(ds, stream, db.res_plan, Bs, kWave, true, true, &rids, &roff);
                     if (rc != GNNA_OK) return rc;
+                    // (the split image of a call lives in the stream's scratch: sized here, so that no call allocates)
+                    hub_image = std::max(hub_image, dense_image_bytes(db.H_pad));
                 }
             }
         }
@@ -1239,6 +1266,11 @@ int gnna_prepare_graph(const int32_t *column_index, const int32_t *part_pointers
     if (staged) {
         void *ws = nullptr;
         rc = get_workspace(ds, stream, 1, staged, &ws);
+        if (rc != GNNA_OK) return rc;
+    }
+    if (hub_image) {
+        void *ws = nullptr;
+        rc = get_workspace(ds, stream, kSlotDenseImage, hub_image, &ws);
         if (rc != GNNA_OK) return rc;
     }
     return GNNA_OK;

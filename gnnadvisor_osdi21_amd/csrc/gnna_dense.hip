@@ -18,7 +18,9 @@
 //     exact, and what is rounded are fp32 sums as before: the hi products in one accumulator (one rounding per 32 source
 //     ranks, however the matrix unit adds inside an instruction), the mid and lo products -- 2^-8 and 2^-16 of them -- in
 //     another, the two added once at the end.  (A lo piece below 2^-126 is a bf16 subnormal and may be dropped: an error
-//     below 2^-126 per term.)
+//     below 2^-126 per term.)  The split is made ONCE per call by hub_split_kernel, ahead of the sweep kernel: the three
+//     pieces of the hub rows of that call's X, in the order of the MFMA's B operand, in the scratch of the call's stream
+//     (3 MB at 8,192 hubs, 6 MB at 16,384).  hub_block_kernel loads its operands from that image and does no arithmetic on X.
 //
 // Multiplicity: the C ABI accepts rows with repeated ids.  The edge that finds its bit already set (atomicOr) is a repeat
 // and stays in the residual; that decision is recorded once per edge in a bit array, which the count pass and the fill
@@ -29,11 +31,13 @@
 // swept phase count are made by the code that makes them for any graph.
 //
 // Stale ids: the guard of the packed copy keeps watching the caller's arrays.  On a call that finds them changed the sweep
-// kernel reads the caller's arrays and hub_block_kernel returns at once.
+// kernel reads the caller's arrays and hub_split_kernel and hub_block_kernel return at once.
 //
 // Environment, read at every gnna_prepare_graph: GNNA_DENSE_BLOCK = 0 never / 1 (default) the rule of gnna_agg.hip / 2 any
 // prepared graph whose call sweeps (tests); GNNA_DENSE_BLOCK_THETA = the degree threshold, under mode 2 only (tests: a hub count
-// of their choosing); GNNA_DENSE_BLOCK_LOG = 1 prints the block taken (theta, H, entries, density) to stderr.
+// of their choosing); GNNA_DENSE_BLOCK_TILE = 32 | 64, under mode 2 only: the destination ranks per workgroup of
+// hub_block_kernel (tests and scans; otherwise dense_tile_ranks decides); GNNA_DENSE_BLOCK_LOG = 1 prints the block taken
+// (theta, H, entries, density) to stderr.
 //
 // Non-finite features: 0 * Inf is NaN, so an Inf or NaN in the features of one hub reaches every hub's row through the
 // block, not only its neighbours' (the gather would hand it to the neighbours alone): 1 * Inf at the neighbours, NaN at the
@@ -60,13 +64,12 @@ constexpr int kHubBuckets = 64;          // half-octave degree buckets
 constexpr int kHubMax = 16384;           // most hubs of a block
 constexpr int kHubThreads = 512;         // hub_block_kernel: 8 wavefronts
 constexpr int kHubWaves = kHubThreads / kWave;
-constexpr int kHubTileM = kDenseTileRanks;    // destination ranks per workgroup (two 16-rank MFMA tiles)
-constexpr int kHubKC = kDenseChunkRanks;      // source ranks staged in LDS at a time; the ranks are padded to a multiple of it
-static_assert(kHubTileM == 32, "two MFMA tiles per workgroup");
-constexpr int kHubStage = kHubKC / 32;   // 16-byte pieces a thread stages per chunk
-constexpr int kHubZeros = 64;            // zero floats behind the ranks of a block: the row a padding rank reads
-static_assert(kHubKC % kHubTileM == 0 && kHubKC * 16 == kHubThreads * kHubStage && (kHubTileM * 64) % kHubThreads == 0, "staging, elements per thread");
-static_assert(kHubZeros >= kDenseMaxDim, "the zeros are a whole row");
+constexpr int kHubTileM = kDenseTileRanks;    // destination ranks per workgroup of the short tile (two 16-rank MFMA tiles); the tall one: twice
+constexpr int kHubKC = kDenseChunkRanks;      // source ranks of a chunk (one step per wavefront of a column half); the ranks are padded to a multiple of it
+static_assert(kHubTileM == 32, "a tile row of the bitmap per 32 destination ranks");
+constexpr int kSplitThreads = 128;       // hub_split_kernel: the threads of one 32-rank step
+static_assert(kHubKC % (2 * kHubTileM) == 0 && (kHubTileM * 64) % kHubThreads == 0, "whole tiles per chunk, elements per thread");
+static_assert(kDenseMaxDim <= 64, "the split image holds 64 columns");
 
 // Half-octave bucket of a degree: 2 k for 2^k <= d < sqrt(2) 2^k, 2 k + 1 for sqrt(2) 2^k <= d < 2^(k + 1); 0 for d <= 1.
 // Monotone in d, so "bucket >= b" is "degree >= theta_b".
@@ -219,26 +222,37 @@ hub_res_fill_kernel(const int32_t *__restrict__ col, const int32_t *__restrict__
 
 // ---- the block itself ---------------------------------------------------------------------------------------------
 struct HubParams {
-    const float *X;
     float *Y;
-    const int32_t *r2n;                  // [H_pad] rank -> node, -1 for the padding ranks; then kHubZeros zero floats
+    const int32_t *r2n;                  // [H_pad] rank -> node, -1 for the padding ranks
     const uint16_t *bm;                  // [H_pad / 32][H_pad / 32][64] halves (the header of this file)
+    const unsigned char *img;            // the call's split image (hub_split_kernel)
     const float *row_scale;
     const int32_t *stale;
     int32_t seq;
-    int H_pad, D, ldx, ldy;
+    int H_pad, D, ldy;
     int scaled;                          // MODE_GIN: rows are multiplied by eps (* row_scale[row])
     float eps;
 };
 
+struct SplitParams {
+    const float *X;
+    const int32_t *r2n;
+    unsigned char *img;
+    const int32_t *stale;
+    int32_t seq;
+    int D, ldx;
+};
+
 typedef typename VecOf<4>::T HubVT;
-typedef typename VecOf<4>::M HubMT;
 typedef int HubIT __attribute__((ext_vector_type(4)));
 
-constexpr int kHubFrag = 1088;           // bytes between the B fragments of an image: 64 lanes x 16 bytes, and 64 (see the LDS image)
-constexpr int kHubPiece = 16 * kHubFrag; // bytes between the hi, mid and lo images of a chunk (4 steps x 4 column tiles)
-constexpr int kHubImage = 3 * kHubPiece; // 52,224 bytes per chunk
-static_assert(kHubKC == 128 && kHubTileM == 32 && kHubWaves == 8 && kHubStage == 4, "the shape hub_block_kernel is written for");
+// The split image of a call: per 128-rank chunk [piece 3][32-rank step 4][column tile 4] fragments.  A fragment is the B operand
+// of one MFMA, 64 lanes x 16 bytes, lane-linear: lane 16 kg + n holds the 8 ranks 8 kg .. 8 kg + 7 of the step at column n of
+// the tile.  48 KB per chunk, H_pad * 384 bytes in all (dense_image_bytes).
+constexpr int kHubFrag = 1024;
+constexpr int kHubPiece = 16 * kHubFrag; // bytes between the hi, mid and lo pieces of a chunk (4 steps x 4 column tiles)
+constexpr int kHubImage = 3 * kHubPiece; // 49,152 bytes per chunk
+static_assert(kHubKC == 128 && kHubTileM == 32 && kHubWaves == 8, "the shape hub_block_kernel is written for");
 
 typedef __bf16 HubFrag __attribute__((ext_vector_type(8)));
 typedef uint32_t HubU4 __attribute__((ext_vector_type(4)));
@@ -269,212 +283,197 @@ __device__ __forceinline__ HubFrag hub_ones(uint32_t bits)
     return __builtin_bit_cast(HubFrag, v);
 }
 
-// A workgroup owns 32 destination ranks (two 16-rank MFMA tiles) and walks ALL source ranks, 128 at a time, with
-// v_mfma_f32_16x16x32_bf16: A is 16 destination ranks x 32 source ranks of the bitmap (0 or 1), B is 32 source ranks x 16
-// columns of ONE of the three bf16 pieces of X.  Every product is exact; the hi products are summed in one fp32 accumulator, the
-// mid and lo products in another, and the two are added once at the end.
+// The three bf16 pieces of the hub rows of the call's X, ONCE per call (before, each of the block's workgroups split every row
+// on its way to LDS: 256 times per value).  A workgroup of 128 threads takes a 32-rank step: thread (g, pc) fetches 4 columns of
+// the 4 consecutive ranks 4 g .. 4 g + 3 (their ids are one 16-byte load), splits the 16 values and writes, per column and
+// piece, the 4 ranks as 8 bytes into an LDS image of the step; behind a barrier the image goes out 16 bytes per lane, 4 KB per
+// piece.  A padding rank and the columns from D on are zeros.  FULL: D and ldx are multiples of 4 and X is 16-byte aligned, so
+// every 16-byte piece of a row is whole and aligned; otherwise the elements are fetched one by one.
+template <bool FULL>
+__global__ void __launch_bounds__(kSplitThreads)
+hub_split_kernel(const SplitParams p)
+{
+    if (*p.stale == p.seq) return;       // the ids changed since the block was made: hub_block_kernel returns at once as well
+    __shared__ __attribute__((aligned(16))) unsigned char s_img[3 * 4 * kHubFrag];
+    const int t = (int)threadIdx.x;
+    const int g = t >> 4, pc = t & 15;
+    const int step = (int)blockIdx.x;
+    const int D = p.D;
+    const HubIT node = *reinterpret_cast<const HubIT *>(&p.r2n[step * 32 + 4 * g]);
+    HubVT v[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int nd = node[k];
+        const float *src = p.X + (size_t)(nd < 0 ? 0 : nd) * (size_t)p.ldx + 4 * pc;
+        HubVT x = (HubVT)(0.f);
+        if (nd >= 0) {
+            if constexpr (FULL) {
+                if (4 * pc < D) x = *reinterpret_cast<const HubVT *>(src);
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; q++)
+                    if (4 * pc + q < D) x[q] = src[q];
+            }
+        }
+        v[k] = x;
+    }
+    const int wbase = (pc >> 2) * kHubFrag + (16 * (g >> 1) + 4 * (pc & 3)) * 16 + 8 * (g & 1);
+#pragma unroll
+    for (int cc = 0; cc < 4; cc++) {
+        // column cc of the thread's 4 x 4 values: split, packed by rank pairs, 8 bytes per piece
+        uint32_t pk[3][2];
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            uint32_t a[3], b[3];
+            hub_split(__float_as_uint(v[2 * h][cc]), a[0], a[1], a[2]);
+            hub_split(__float_as_uint(v[2 * h + 1][cc]), b[0], b[1], b[2]);
+#pragma unroll
+            for (int i = 0; i < 3; i++) pk[i][h] = hub_pack(a[i], b[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            HubU2 o;
+            o[0] = pk[i][0];
+            o[1] = pk[i][1];
+            *reinterpret_cast<HubU2 *>(&s_img[wbase + i * 4 * kHubFrag + cc * 16]) = o;
+        }
+    }
+    __syncthreads();
+    unsigned char *out = p.img + (size_t)(step >> 2) * kHubImage + (size_t)(step & 3) * 4 * kHubFrag;
+#pragma unroll
+    for (int u = 0; u < 3 * 4 * kHubFrag / 16 / kSplitThreads; u++) {
+        const int idx = u * kSplitThreads + t;
+        const int i = idx >> 8, off = (idx & 255) * 16;
+        *reinterpret_cast<HubU4 *>(&out[i * kHubPiece + off]) = *reinterpret_cast<const HubU4 *>(&s_img[i * 4 * kHubFrag + off]);
+    }
+}
+
+// A workgroup owns TM destination ranks (TM / 16 MFMA tiles, TM / 32 tile rows of the bitmap) and walks ALL source ranks, 128
+// at a time, with v_mfma_f32_16x16x32_bf16: A is 16 destination ranks x 32 source ranks of the bitmap (0 or 1), B is 32 source
+// ranks x 16 columns of ONE of the three bf16 pieces of X.  Every product is exact; the hi products are summed in one fp32
+// accumulator, the mid and lo products in another, and the two are added once at the end.
 //
-// Staging.  Thread t fetches 16 bytes (4 columns) of each of 4 consecutive ranks (their four ids are one 16-byte load), splits
-// the 16 values as they go to LDS and writes, per column and piece, the 4 ranks as 8 bytes.  No branch on the way and nothing
-// to mask: a padding rank reads the zeros behind the ranks, and a piece beyond D reads piece 0 into columns of the image whose
-// products are never written to Y.  Within a wavefront, lanes 8 apart take adjacent rank groups and lanes 16 apart take
-// columns 32 apart (below: why).
+// The kernel does no arithmetic on X and keeps no image of it in LDS.  The 8 wavefronts split a chunk as (step s = w % 4, column
+// half w / 4), and a fragment of the split image IS the B operand of one MFMA: the 3 pieces of a wavefront's 2 column tiles (1
+// for the upper half when NT = 3: column tile 3 is never read) are 6 wave-wide 16-byte loads straight into its registers, the
+// 8 wavefronts read the chunk's 48 fragments once between them, and nothing is shared before the end -- no barrier in the
+// loop.  Each fragment is multiplied with the bitmap bytes of all TM / 16 destination tiles: 12 MFMAs per chunk for TM = 32, 24
+// for TM = 64, which halves the bytes of the image a destination rank pulls through the L2.  Three register stages take the
+// chunks in turn (chunk c lives in stage c % 3): a piece's fragments are asked for again, three chunks ahead, as soon as its
+// MFMAs are issued, so about two chunks (12 KB per wavefront) are on their way at any time.
 //
-// The LDS image of a chunk: [piece 3][step 4][column tile 4] fragments of 64 x 16 bytes, kHubFrag bytes apart.  A fragment is the B
-// operand of one MFMA: 16 bytes = the 8 ranks 8 kg .. 8 kg + 7 of a step at one column n, in slot 16 kg + 4 (n % 4) + n / 4.
-// Read (ds_read_b128, lane = 16 kg + n): the 16 lanes of a service group fall on 16 different slots modulo 16: no conflict.
-// Written (ds_write_b64; a service group is 16 consecutive lanes = columns 4 i + cc of two adjacent column tiles for i = 0 .. 3,
-// and both halves h of the slots): byte 64 (tile + cc) + 16 i + 8 h modulo 128, the 64 from kHubFrag: all 32 banks once.
-//
-// The 8 wavefronts split a chunk as (step s = w % 4, column half w / 4): a wavefront reads the 3 pieces of its 2 column tiles (1
-// for the upper half when NT = 3) and multiplies each with the bitmap bytes of both destination tiles: 12 MFMAs.  Two images
-// take the chunks in turn: while chunk c is multiplied out of one, chunk c + 1 goes into the other, chunk c + 2 is in
-// registers or on its way and chunk c + 3 is asked for (three register stages); one barrier per chunk.  At the end the
-// four steps' partial tiles are laid side by side in LDS (over the images) and summed in step order, and the workgroup --
-// the only writer of its 32 rows in this launch, behind the sweep kernel of the same call -- adds the tile to Y with plain
-// loads and stores: no atomics, and a result that does not depend on timing.  FULL: D and ldx are multiples of 4, so every
-// staged 16-byte piece is whole.
-template <int NT, bool FULL>
+// At the end the four steps' partial tiles are laid side by side in LDS and summed in step order, and the workgroup -- the
+// only writer of its TM rows in this launch, behind the sweep kernel of the same call -- adds the tile to Y with plain loads
+// and stores: no atomics, and a result that does not depend on timing.  The order in which a destination element's products
+// are added is the same for both tile heights.
+template <int NT, int TM>
 __global__ void __launch_bounds__(kHubThreads)
 hub_block_kernel(const HubParams p)
 {
     if (*p.stale == p.seq) return;       // the ids changed since the block was made: the sweep kernel does the whole call
-    __shared__ __attribute__((aligned(16))) unsigned char s_x[2][kHubImage];
-    static_assert(4 * kHubTileM * 64 * 4 <= kHubImage, "the partial tiles fit over the first image");
-    const uint16_t *bm = p.bm;
+    constexpr int TR = TM / 32;          // tile rows of the bitmap
+    static_assert((TM == kHubTileM || TM == 2 * kHubTileM) && (NT == 3 || NT == 4), "tile shapes");
+    __shared__ __attribute__((aligned(16))) float s_part[4 * TM * 64];
     const int tid = (int)threadIdx.x;
     const int lane = tid & (kWave - 1);
     const int wib = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int chunks = p.H_pad / kHubKC;
     const int steps = p.H_pad >> 5;      // 32-rank steps of a row of the bitmap
     const int D = p.D;
-
-    // staging: 4 ranks from 4 g, 4 columns from 4 pc
-    const int g = 4 * (tid >> 6) + ((lane >> 3) & 1) + 2 * (lane >> 5), pc = (lane & 7) + 8 * ((lane >> 4) & 1);
-    const int srow = 4 * g, spiece = 4 * pc;
-    const int scol = spiece < D ? spiece : 0;                // (a piece beyond D feeds columns that are never written to Y)
-    const int wbase = ((g >> 3) * 4 + (pc >> 2)) * kHubFrag + (16 * ((g & 7) >> 1) + (pc & 3)) * 16 + 8 * (g & 1);
-    const float *zero_row = reinterpret_cast<const float *>(p.r2n + p.H_pad);    // 64 zeros behind the ranks: what a padding rank reads
-    const uintptr_t zero_at = reinterpret_cast<uintptr_t>(zero_row + scol);
-    auto load_piece = [&](int node) -> HubVT {
-        // (one address, chosen without a branch: a padding rank reads the zeros)
-        const uintptr_t row = reinterpret_cast<uintptr_t>(p.X + (size_t)(node < 0 ? 0 : node) * (size_t)p.ldx + scol);
-        const float *src = reinterpret_cast<const float *>(node < 0 ? zero_at : row);
-        HubVT v;
-        if constexpr (FULL) {
-            v = *reinterpret_cast<const HubMT *>(src);
-        } else if (spiece + 4 <= D) {
-            v = *reinterpret_cast<const HubMT *>(src);
-        } else {
-            v = (HubVT)(0.f);
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-                if (spiece + q < D) v[q] = src[q];
-        }
-        return v;
-    };
-    // Three stages take the chunks in turn (chunk c lives in stage c % 3): rows, bitmap bytes and the node ids of the chunk
-    // that FOLLOWS in the same stage, fetched behind the rows, so a row address never waits for an id that is younger than
-    // the rows the same wait is for.  A chunk beyond the last is the last one again: fetched, never multiplied.
+    const int cs = wib & 3, ch = wib >> 2;                  // this wavefront's step of a chunk and its half of the columns
+    const bool two = NT == 4 || ch == 0;                    // (wave-uniform) the half has a second column tile
+    const unsigned char *frag0 = p.img + (size_t)(cs * 4 + 2 * ch) * kHubFrag + (size_t)lane * 16;
+    const uint16_t *word0 = p.bm + ((size_t)blockIdx.x * TR * (size_t)steps + (size_t)cs) * 64 + (size_t)lane;
     struct Stage {
-        HubVT r[kHubStage];
-        HubIT node;
-        uint32_t w;                      // this wavefront's step of the bitmap: byte 0 the first destination tile, byte 1 the second
+        HubFrag b[2][3];                 // [column tile of the half][piece]
+        uint32_t w[TR];                  // this wavefront's step of the bitmap per tile row: byte 0 the first destination tile, byte 1 the second
     };
-    auto fetch_ids = [&](int c, Stage &st) {
-        const int cc = c < chunks ? c : chunks - 1;
-        st.node = *reinterpret_cast<const HubIT *>(&p.r2n[cc * kHubKC + srow]);
+    // (a chunk beyond the last is the last one again: fetched, never multiplied)
+    auto fetch_piece = [&](int c, int i, Stage &st) {
+        const unsigned char *src = frag0 + (size_t)(c < chunks ? c : chunks - 1) * kHubImage + i * kHubPiece;
+        st.b[0][i] = *reinterpret_cast<const HubFrag *>(src);
+        if (two) st.b[1][i] = *reinterpret_cast<const HubFrag *>(src + kHubFrag);
     };
     auto fetch_words = [&](int c, Stage &st) {
         const int cc = c < chunks ? c : chunks - 1;
-        st.w = bm[((size_t)blockIdx.x * (size_t)steps + (size_t)(cc * 4 + (wib & 3))) * 64 + (size_t)lane];
+#pragma unroll
+        for (int tr = 0; tr < TR; tr++) st.w[tr] = word0[((size_t)tr * (size_t)steps + (size_t)(cc * 4)) * 64];
     };
-    auto fetch_row = [&](int i, Stage &st) {                 // row i of the chunk whose ids are in st.node
-        st.r[i] = load_piece(st.node[i]);
-    };
-    // column cc of the thread's 4 x 4 values: split, packed by rank pairs, 8 bytes per piece
-    auto stage_out = [&](int cc, const Stage &st, unsigned char *image) {
-        uint32_t pk[3][2];
+    HubVT acc_hi[2 * TR][2], acc_lo[2 * TR][2];             // [destination tile][column tile of the half]
 #pragma unroll
-        for (int h = 0; h < 2; h++) {
-            uint32_t a[3], b[3];
-            hub_split(__float_as_uint(st.r[2 * h][cc]), a[0], a[1], a[2]);
-            hub_split(__float_as_uint(st.r[2 * h + 1][cc]), b[0], b[1], b[2]);
-#pragma unroll
-            for (int i = 0; i < 3; i++) pk[i][h] = hub_pack(a[i], b[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            HubU2 v;
-            v[0] = pk[i][0];
-            v[1] = pk[i][1];
-            *reinterpret_cast<HubU2 *>(&image[wbase + i * kHubPiece + cc * 64]) = v;
-        }
-    };
-
-    const int cs = wib & 3, ch = wib >> 2;                  // this wavefront's step of a chunk and its half of the columns
-    const int rbase = (cs * 4 + 2 * ch) * kHubFrag + (16 * (lane >> 4) + 4 * (lane & 3) + ((lane & 15) >> 2)) * 16;
-    HubVT acc_hi[2][2], acc_lo[2][2];                           // [destination tile][column tile of the half]
-#pragma unroll
-    for (int t = 0; t < 2; t++)
+    for (int t = 0; t < 2 * TR; t++)
 #pragma unroll
         for (int q = 0; q < 2; q++) acc_hi[t][q] = acc_lo[t][q] = (HubVT)(0.f);
 
-    // Chunk c out of image c % 2 with the bitmap bytes of stage L, which then starts on chunk c + 3; stage S holds chunk c + 1,
-    // which goes into the other image.  A turn is four parts, pinned in this order: a load of L, the MFMAs of one piece (hi, mid,
-    // lo, none), one column of S split and written.  The loads are spread like this because the compute unit's address unit
-    // takes about as long for a chunk's 32 KB as the rest of the turn does: issued in one burst by all eight wavefronts they
-    // fill its queue, a wavefront stands at its next load until the queue has room, and nothing else is issued meanwhile.
-    auto turn = [&](int c, Stage &L, const Stage &S) {
-        const unsigned char *cur = s_x[c & 1];
-        unsigned char *nxt = s_x[(c & 1) ^ 1];
-        __builtin_amdgcn_sched_barrier(0);
-        HubFrag b[2][3];
+    // Chunk c out of stage st, which then starts on chunk c + 3.  A turn is three parts, pinned in this order: the MFMAs of one
+    // piece (hi, mid, lo), then the loads that fill that piece's registers again.
+    auto turn = [&](int c, Stage &st) {
+        HubFrag a[2 * TR];
 #pragma unroll
-        for (int i = 0; i < 3; i++)
+        for (int t = 0; t < 2 * TR; t++) a[t] = hub_ones((st.w[t >> 1] >> (8 * (t & 1))) & 0xffu);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
 #pragma unroll
             for (int q = 0; q < 2; q++)
-                if (NT == 4 || q == 0 || ch == 0) b[q][i] = *reinterpret_cast<const HubFrag *>(&cur[rbase + q * kHubFrag + i * kHubPiece]);
-        HubFrag a[2];
-        a[0] = hub_ones(L.w & 0xffu);
-        a[1] = hub_ones((L.w >> 8) & 0xffu);
-        __builtin_amdgcn_sched_barrier(0);
+                if (q == 0 || two) {
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            fetch_row(k, L);
-            if (k < 3) {
-#pragma unroll
-                for (int q = 0; q < 2; q++)
-                    if (NT == 4 || q == 0 || ch == 0) {
-#pragma unroll
-                        for (int t = 0; t < 2; t++) {
-                            if (k == 0) acc_hi[t][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], b[q][0], acc_hi[t][q], 0, 0, 0);
-                            else acc_lo[t][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], b[q][k], acc_lo[t][q], 0, 0, 0);
-                        }
+                    for (int t = 0; t < 2 * TR; t++) {
+                        if (k == 0) acc_hi[t][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], st.b[q][0], acc_hi[t][q], 0, 0, 0);
+                        else acc_lo[t][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], st.b[q][k], acc_lo[t][q], 0, 0, 0);
                     }
-            }
-            stage_out(k, S, nxt);
+                }
+            fetch_piece(c + 3, k, st);
             __builtin_amdgcn_sched_barrier(0);
         }
-        fetch_words(c + 3, L);
-        fetch_ids(c + 6, L);
+        fetch_words(c + 3, st);
         __builtin_amdgcn_sched_barrier(0);
-        __syncthreads();                                     // `nxt` is whole, and `cur` has been read by every wavefront
     };
     Stage s0, s1, s2;
-    fetch_ids(0, s0);
-    fetch_ids(1, s1);
-    fetch_ids(2, s2);
     // (the order of the loads is that of the turns, and pinned: the counted waits of the loop are those of its entry as well)
     auto fetch = [&](int c, Stage &st) {
 #pragma unroll
-        for (int i = 0; i < kHubStage; i++) fetch_row(i, st);
+        for (int i = 0; i < 3; i++) fetch_piece(c, i, st);
         fetch_words(c, st);
-        fetch_ids(c + 3, st);
         __builtin_amdgcn_sched_barrier(0);
     };
     fetch(0, s0);
     fetch(1, s1);
     fetch(2, s2);
-#pragma unroll
-    for (int cc = 0; cc < 4; cc++) stage_out(cc, s0, s_x[0]);
-    __builtin_amdgcn_sched_barrier(0);
-    __syncthreads();
     int c = 0;
     for (; c + 3 <= chunks; c += 3) {
-        turn(c, s0, s1);
-        turn(c + 1, s1, s2);
-        turn(c + 2, s2, s0);
+        turn(c, s0);
+        turn(c + 1, s1);
+        turn(c + 2, s2);
     }
     if (c < chunks) {
-        turn(c, s0, s1);
-        if (c + 1 < chunks) turn(c + 1, s1, s2);
+        turn(c, s0);
+        if (c + 1 < chunks) turn(c + 1, s1);
     }
 
-    // the 4 partial tiles of the workgroup's 32 rows, side by side, then summed in step order
-    // (the last turn ended with a barrier: nobody reads the images any more)
-    float *part = reinterpret_cast<float *>(&s_x[0][0]);     // [step][32 ranks][64 columns]; the columns from 16 NT on stay unwritten and unread
+    // the 4 partial tiles of the workgroup's TM rows, side by side, then summed in step order
+    float *part = s_part;                // [step][TM ranks][64 columns]; the columns from 16 NT on stay unwritten and unread
 #pragma unroll
-    for (int t = 0; t < 2; t++)
+    for (int t = 0; t < 2 * TR; t++)
 #pragma unroll
         for (int q = 0; q < 2; q++)
-            if (NT == 4 || q == 0 || ch == 0) {
+            if (q == 0 || two) {
 #pragma unroll
                 for (int r = 0; r < 4; r++)
-                    part[(cs * kHubTileM + t * 16 + (lane >> 4) * 4 + r) * 64 + (2 * ch + q) * 16 + (lane & 15)] =
+                    part[(cs * TM + t * 16 + (lane >> 4) * 4 + r) * 64 + (2 * ch + q) * 16 + (lane & 15)] =
                         __builtin_isinf(acc_hi[t][q][r]) ? acc_hi[t][q][r] : acc_hi[t][q][r] + acc_lo[t][q][r];
             }
     __syncthreads();
     // one plain read-add-write of Y per element
 #pragma unroll
-    for (int i = 0; i < kHubTileM * 64 / kHubThreads; i++) {
+    for (int i = 0; i < TM * 64 / kHubThreads; i++) {
         const int idx = i * kHubThreads + tid;
         const int row = idx >> 6, col = idx & 63;
         if (col >= D) continue;
         float sum = part[idx];
 #pragma unroll
-        for (int s = 1; s < 4; s++) sum += part[s * kHubTileM * 64 + idx];
-        const int node = p.r2n[(int)blockIdx.x * kHubTileM + row];
+        for (int s = 1; s < 4; s++) sum += part[s * TM * 64 + idx];
+        const int node = p.r2n[(int)blockIdx.x * TM + row];
         if (node < 0 || sum == 0.f) continue;
         float scale = 1.f;
         if (p.scaled) {
@@ -593,7 +592,7 @@ int build_dense_block(DeviceState *ds, hipStream_t stream, const int32_t *col, c
     std::copy(ids.begin(), ids.end(), ranks.begin());
     std::sort(ranks.begin(), ranks.begin() + H);
 
-    const size_t r2n_b = align256((size_t)H_pad * 4 + kHubZeros * 4);
+    const size_t r2n_b = align256((size_t)H_pad * 4);
     const size_t bm_b = align256((size_t)H_pad * (size_t)H_pad / 8), rpp_b = align256((size_t)(P + 1) * 4);
     void *blk = nullptr;
     e = hipMalloc(&blk, r2n_b + bm_b + rpp_b);
@@ -608,7 +607,6 @@ int build_dense_block(DeviceState *ds, hipStream_t stream, const int32_t *col, c
     e = hipMemcpy(r2n, ranks.data(), (size_t)H_pad * 4, hipMemcpyHostToDevice);
     if (e != hipSuccess) return give_up(fail(GNNA_ERR_HIP, "dense block (ranks): %s", hipGetErrorString(e)));
     (void)hipMemsetAsync(n2r, 0xff, n2r_b, stream);
-    (void)hipMemsetAsync(r2n + H_pad, 0, kHubZeros * 4, stream);
     (void)hipMemsetAsync(bm, 0, bm_b, stream);
     hipLaunchKernelGGL(hub_rank_kernel, dim3((unsigned)((H + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, r2n, (int)H, N, n2r);
     hipLaunchKernelGGL(hub_bitmap_kernel, dim3(wblocks), dim3(kBlock), 0, stream, col, pp, p2n, P, N, n2r, H_pad / 32, bm, taken, taken_total);
@@ -632,6 +630,7 @@ int build_dense_block(DeviceState *ds, hipStream_t stream, const int32_t *col, c
     out->buf = blk; out->r2n = r2n; out->bm = bm; out->res_pp = res_pp; out->res_col = res_col;
     out->H = H; out->H_pad = H_pad; out->theta = theta; out->entries = (int64_t)entries; out->res_nnz = res_nnz;
     out->forced = mode == 2;
+    out->tile = dense_block_tile_env(mode);
     const char *log = std::getenv("GNNA_DENSE_BLOCK_LOG");
     if (log && *log && *log != '0')
         std::fprintf(stderr, "gnna dense block: theta %d, H %d (padded %d), entries %lld of %lld edges, density %.3f\n", theta, (int)H,
@@ -640,26 +639,45 @@ int build_dense_block(DeviceState *ds, hipStream_t stream, const int32_t *col, c
     return GNNA_OK;
 }
 
-int launch_hub_block(DeviceState *ds, hipStream_t stream, const DenseBlock &db, const float *X, int ldx, float *Y, int ldy, int dim,
+int dense_block_tile_env(int mode)
+{
+    const char *s = mode == 2 ? std::getenv("GNNA_DENSE_BLOCK_TILE") : nullptr;
+    const int v = s && *s ? std::atoi(s) : 0;
+    return v == kHubTileM || v == 2 * kHubTileM ? v : 0;
+}
+
+int launch_hub_split(hipStream_t stream, const DenseBlock &db, const float *X, int ldx, int dim, void *image, const int32_t *stale_flag,
+                     int32_t seq)
+{
+    if (dim < kDenseMinDim || dim > kDenseMaxDim) return fail(GNNA_ERR_INVALID_ARGUMENT, "hub block: width %d", dim);
+    SplitParams p;
+    p.X = X; p.r2n = db.r2n; p.img = static_cast<unsigned char *>(image); p.stale = stale_flag; p.seq = seq; p.D = dim; p.ldx = ldx;
+    const bool full = dim % 4 == 0 && ldx % 4 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+    const dim3 grid((unsigned)(db.H_pad / 32)), block(kSplitThreads);
+    if (full) hipLaunchKernelGGL((hub_split_kernel<true>), grid, block, 0, stream, p);
+    else hipLaunchKernelGGL((hub_split_kernel<false>), grid, block, 0, stream, p);
+    return launch_ok("hub split launch");
+}
+
+int launch_hub_block(DeviceState *ds, hipStream_t stream, const DenseBlock &db, const void *image, float *Y, int ldy, int dim,
                      bool scaled, float eps, const float *row_scale, const int32_t *stale_flag, int32_t seq)
 {
     HubParams p;
-    p.X = X; p.Y = Y; p.r2n = db.r2n; p.bm = static_cast<const uint16_t *>(db.bm); p.row_scale = row_scale;
-    p.stale = stale_flag; p.seq = seq; p.H_pad = db.H_pad; p.D = dim; p.ldx = ldx; p.ldy = ldy;
+    p.Y = Y; p.r2n = db.r2n; p.bm = static_cast<const uint16_t *>(db.bm); p.img = static_cast<const unsigned char *>(image);
+    p.row_scale = row_scale; p.stale = stale_flag; p.seq = seq; p.H_pad = db.H_pad; p.D = dim; p.ldy = ldy;
     p.scaled = scaled ? 1 : 0; p.eps = eps;
-    (void)ds;
     if (dim < kDenseMinDim || dim > kDenseMaxDim) return fail(GNNA_ERR_INVALID_ARGUMENT, "hub block: width %d", dim);
-    const bool full = dim % 4 == 0 && ldx % 4 == 0;
-    const dim3 grid((unsigned)(db.H_pad / kHubTileM)), block(kHubThreads);
-    if (dim <= 48) {
-        if (full) hipLaunchKernelGGL((hub_block_kernel<3, true>), grid, block, 0, stream, p);
-        else hipLaunchKernelGGL((hub_block_kernel<3, false>), grid, block, 0, stream, p);
+    const int tile = dense_tile_ranks(db.H_pad, ds->num_cus, db.tile);
+    const dim3 grid((unsigned)(db.H_pad / tile)), block(kHubThreads);
+    if (tile == kHubTileM) {
+        if (dim <= 48) hipLaunchKernelGGL((hub_block_kernel<3, kHubTileM>), grid, block, 0, stream, p);
+        else hipLaunchKernelGGL((hub_block_kernel<4, kHubTileM>), grid, block, 0, stream, p);
     } else {
-        if (full) hipLaunchKernelGGL((hub_block_kernel<4, true>), grid, block, 0, stream, p);
-        else hipLaunchKernelGGL((hub_block_kernel<4, false>), grid, block, 0, stream, p);
+        if (dim <= 48) hipLaunchKernelGGL((hub_block_kernel<3, 2 * kHubTileM>), grid, block, 0, stream, p);
+        else hipLaunchKernelGGL((hub_block_kernel<4, 2 * kHubTileM>), grid, block, 0, stream, p);
     }
     const int rc = launch_ok("hub block launch");
-    if (rc == GNNA_OK) count_event(CTR_DENSE_LAUNCHES);
+    if (rc == GNNA_OK) count_event(CTR_DENSE_LAUNCHES);      // (one per call: the split pass is counted with it)
     return rc;
 }
 

@@ -199,7 +199,7 @@ struct QuietBuilds {
 // ---- dense hub-to-hub block of a prepared graph (gnna_dense.hip) ----------------------------------------------------
 struct DenseBlock {
     void *buf = nullptr;              // one allocation: r2n, node -> rank map, bm, res_pp
-    const int32_t *r2n = nullptr;     // [H_pad] rank -> node (-1: padding), then 64 zero floats (what a padding rank reads)
+    const int32_t *r2n = nullptr;     // [H_pad] rank -> node (-1: padding)
     const void *bm = nullptr;         // [H_pad / 32][H_pad / 32][64] 16-bit halves: 2 x 16 destination ranks x 8 source ranks each
     const int32_t *res_pp = nullptr;  // part_pointers of the residual graph (same part2Node, same group count)
     int32_t *res_col = nullptr;       // its column ids (an allocation of its own)
@@ -209,10 +209,26 @@ struct DenseBlock {
     int64_t entries = 0, res_nnz = 0;
     bool forced = false;              // built under GNNA_DENSE_BLOCK=2: also taken by a forced sweep
     bool off = false;                 // the graph's latest gnna_prepare_graph ran under GNNA_DENSE_BLOCK=0
+    int tile = 0;                     // destination ranks per workgroup forced by GNNA_DENSE_BLOCK_TILE (32 | 64); 0: dense_tile_ranks
     int declined_mode = -1;           // buf == null: the GNNA_DENSE_BLOCK mode under which the graph was counted and got no block
 };
-// Geometry of hub_block_kernel that the block rule needs: destination ranks per workgroup, source ranks per chunk (= padding).
+// Geometry of hub_block_kernel that the block rule needs: destination ranks per workgroup (the short tile; the tall one is
+// twice that), source ranks per chunk (= padding).
 constexpr int kDenseTileRanks = 32, kDenseChunkRanks = 128;
+// Destination ranks per workgroup that a launch on H_pad ranks takes: the short tile while its workgroups are one round (one per
+// compute unit), the tall one beyond -- half the workgroups, and half the bytes of the split image through the L2 per
+// destination rank.  (Behind the sweep kernel of the headline, at 8,192 ranks on 256 compute units: short 46.6 us, tall 51.1;
+// back to back in the stand-alone probe, with a warm L2, the tall tile is already ahead there: profiles/hub_block_presplit.)
+// `forced`: DenseBlock::tile.
+inline int dense_tile_ranks(int H_pad, int num_cus, int forced = 0)
+{
+    if (forced == kDenseTileRanks || forced == 2 * kDenseTileRanks) return forced;
+    return H_pad / kDenseTileRanks <= (num_cus > 1 ? num_cus : 1) ? kDenseTileRanks : 2 * kDenseTileRanks;
+}
+// The split image of a call (hub_split_kernel): the three bf16 pieces of the H_pad hub rows at 64 columns, in the stream's
+// scratch slot kSlotDenseImage -- per call and per stream, never on the plan.
+constexpr int kSlotDenseImage = 18;
+inline size_t dense_image_bytes(int H_pad) { return (size_t)H_pad * 3 * 64 * 2; }
 // Row widths the block is taken at: two 128-byte lines per gathered row, what the rule's constants were measured for.  (A row
 // of <= 32 floats is one request per edge: the sweep saves about half per edge taken out while the block costs the same.)
 constexpr int kDenseMinDim = 33, kDenseMaxDim = 64;
@@ -227,9 +243,15 @@ int dense_block_mode();
 // from gnna_prepare_graph).  out->buf stays null when the graph gets no block.
 int build_dense_block(DeviceState *ds, hipStream_t stream, const int32_t *col, const int32_t *pp, const int32_t *p2n, int64_t P,
                       int64_t N, int64_t nnz, int mode, DenseBlock *out);
-// Y[node(i), :] += scale(i) * sum_j bit(i, j) * X[node(j), :] behind the sweep kernel of the same call; returns at once on
-// the device when *stale_flag == seq.
-int launch_hub_block(DeviceState *ds, hipStream_t stream, const DenseBlock &db, const float *X, int ldx, float *Y, int ldy, int dim,
+// GNNA_DENSE_BLOCK_TILE under GNNA_DENSE_BLOCK=2 (tests and scans): 32 or 64, anything else 0.
+int dense_block_tile_env(int mode);
+// image = the three bf16 pieces of X[node(j), :] for every rank j, in hub_block_kernel's operand order (dense_image_bytes(H_pad)
+// bytes of the call's scratch), ahead of the sweep kernel of the same call; returns at once on the device when *stale_flag == seq.
+int launch_hub_split(hipStream_t stream, const DenseBlock &db, const float *X, int ldx, int dim, void *image, const int32_t *stale_flag,
+                     int32_t seq);
+// Y[node(i), :] += scale(i) * sum_j bit(i, j) * X[node(j), :] from that image, behind the sweep kernel of the same call; returns
+// at once on the device when *stale_flag == seq.
+int launch_hub_block(DeviceState *ds, hipStream_t stream, const DenseBlock &db, const void *image, float *Y, int ldy, int dim,
                      bool scaled, float eps, const float *row_scale, const int32_t *stale_flag, int32_t seq);
 // The block that hangs on a slice plan (gnna_stream.hip): a copy of it (false: none) / hang `db` on the plan, which owns its
 // buffers and the residual plan from then on.

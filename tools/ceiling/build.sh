@@ -10,3 +10,4 @@ for r in 72 64; do /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPI
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared push_probe4.hip -o libpush4.so
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared l1_policy_probe.hip -o libl1policy.so
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 hub_block_bf16_probe.hip -o hub_block_bf16_probe
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 hub_block_presplit_probe.hip -o hub_block_presplit_probe
