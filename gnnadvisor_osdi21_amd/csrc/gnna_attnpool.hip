@@ -28,7 +28,6 @@
 #include <cstdint>
 
 #include "gnna_attnpool.h"
-#include "gnna_pool.h"           // GNNA_POOL_TILE_ROWS, GNNA_POOL_LONG_STEPS: the geometry is the pool kernels'
 #include "gnna_device.h"
 #include "gnna_gat_common.h"     // gat::load_piece, gat::head_sum, gat::check_alias
 #include "gnna_internal.h"
@@ -39,15 +38,14 @@ namespace {
 
 using gat::VT;
 using gat::load_piece;
+using seg::kTile;
+using seg::kRowsInFlight;            // (two 16-byte loads per row in flight with CH)
+using seg::kLongSteps;
 using seg::seg_ptr;
 using seg::first_segment;
 using seg::uniform64;
 using seg::store_piece;
 using seg::exp_nonpos;
-
-constexpr int kTile = GNNA_POOL_TILE_ROWS;
-constexpr int kRowsInFlight = 4;     // rows per slot and step of the row walk: 16-byte loads in flight per lane (twice that with CH)
-constexpr int kLongSteps = GNNA_POOL_LONG_STEPS;
 
 struct FwdArgs {
     const float *X;             // the rows
@@ -402,48 +400,26 @@ attnpool_bwd_kernel(const BwdArgs p)
     }
 }
 
-// Scratch of the forward entry: slot 14 = the pieces of the tiles (a, m, l).  Eager calls of a stream share it (grow-only), a
-// captured call gets its capture's own.
+// Scratch of the forward entry: slot 14 = the pieces of the tiles (a, m, l; seg::get_pieces).
 constexpr int kSlotAttnPoolPieces = 14;
-
-// a stride that is checked against its width only where something is strided by it
-bool bad_ld_of(const void *ptr, int64_t ld, int width) { return ptr ? bad_ld(ld, width) : ld >= ((int64_t)1 << 29); }
 
 // what both entries check alike, before any device work
 int check_sizes(const char *what, int64_t num_rows, int64_t num_segments, int dim, int gate_dim, unsigned flags)
 {
     if (flags != 0u) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s takes no flags (got 0x%x)", what, flags);
-    if (dim < 1) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: dim must be >= 1 (got %d)", what, dim);
+    const int rc = seg::check_dim(what, dim);
+    if (rc != GNNA_OK) return rc;
     if (gate_dim != 1 && gate_dim != dim)
         return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: gate_dim must be 1 or dim = %d (got %d)", what, dim, gate_dim);
-    if (num_rows < 0 || num_segments < 0)
-        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: negative size (num_rows=%lld num_segments=%lld)", what, (long long)num_rows,
-                    (long long)num_segments);
-    if (num_segments >= ((int64_t)1 << 29))
-        return fail(GNNA_ERR_UNSUPPORTED, "%s: %lld segments in one call (at most 536870911): shard the batch", what,
-                    (long long)num_segments);
-    if (num_rows > 0x7fffffffll)
-        return fail(GNNA_ERR_UNSUPPORTED, "%s: %lld rows in one call (at most 2147483647: graph_pointers is int32)", what,
-                    (long long)num_rows);
-    return GNNA_OK;
+    return seg::check_counts(what, num_rows, num_segments);
 }
 
 template <bool CH>
 int launch_forward(int log_lpr, hipStream_t stream, const FwdArgs &a)
 {
-    const int64_t tiles = (a.N + kTile - 1) / kTile;
-    int rc = GNNA_OK;
-    dispatch_lpr(log_lpr, [&](auto L) {
-        if (tiles > 0) {
-            hipLaunchKernelGGL((attnpool_tile_kernel<CH, decltype(L)::value>), dim3((unsigned)((tiles + kWavesPerBlock - 1) / kWavesPerBlock)),
-                               dim3(kBlock), 0, stream, a);
-            if ((rc = launch_ok("attention pooling: tile launch")) != GNNA_OK) return;
-        }
-        hipLaunchKernelGGL((attnpool_finish_kernel<CH, decltype(L)::value>), dim3((unsigned)((a.G + kWavesPerBlock - 1) / kWavesPerBlock)),
-                           dim3(kBlock), 0, stream, a);
-        rc = launch_ok("attention pooling: finish launch");
+    return seg::launch_tiles_then_finish("attention pooling", log_lpr, stream, a, [](auto L) {
+        return std::make_pair(attnpool_tile_kernel<CH, decltype(L)::value>, attnpool_finish_kernel<CH, decltype(L)::value>);
     });
-    return rc;
 }
 
 }  // namespace
@@ -483,19 +459,11 @@ int gnna_segment_attn_pool_ld_f32(const float *input, int64_t ld_in, int64_t num
     FwdArgs a;
     a.X = input; a.ldx = (size_t)ld_in; a.gate = gate; a.ldg = (size_t)ld_gate; a.gp = graph_pointers; a.N = num_rows; a.G = num_segments;
     a.out = out; a.lse = lse; a.ldo = (size_t)ld_out; a.ldl = (size_t)ld_lse;
-    a.Pa = a.Pm = a.Pl = nullptr;
     a.D = dim;
-    const int64_t tiles = (num_rows + kTile - 1) / kTile;
-    if (tiles > 0) {
-        // two pieces per tile: a [dim], then m and l [gate_dim]
-        const size_t pieces = (size_t)tiles * 2;
-        const size_t bytes = pieces * ((size_t)dim + 2 * (size_t)gate_dim) * sizeof(float);
-        void *ws = nullptr;
-        if ((rc = get_workspace(ds, stream, kSlotAttnPoolPieces, (bytes + 255) & ~(size_t)255, &ws)) != GNNA_OK) return rc;
-        a.Pa = static_cast<float *>(ws);
-        a.Pm = a.Pa + pieces * (size_t)dim;
-        a.Pl = a.Pm + pieces * (size_t)gate_dim;
-    }
+    const size_t piece_bytes[3] = {(size_t)dim * sizeof(float), (size_t)gate_dim * sizeof(float), (size_t)gate_dim * sizeof(float)};
+    void *pieces[3];
+    if ((rc = seg::get_pieces(ds, stream, kSlotAttnPoolPieces, num_rows, piece_bytes, pieces)) != GNNA_OK) return rc;
+    a.Pa = static_cast<float *>(pieces[0]); a.Pm = static_cast<float *>(pieces[1]); a.Pl = static_cast<float *>(pieces[2]);
     const int log_lpr = log2_lanes(dim, 4);
     // (dim == 1: a score per element is a score per row)
     return gate_dim == 1 ? launch_forward<false>(log_lpr, stream, a) : launch_forward<true>(log_lpr, stream, a);

@@ -96,6 +96,8 @@ inline int pow2_at_least(int64_t x)
 
 // a row stride that is narrower than the row or does not fit the kernels' 32-bit element offsets
 inline bool bad_ld(int64_t ld, int64_t width) { return ld < width || ld >= ((int64_t)1 << 29); }
+// the stride of an operand that may be null: checked against its width only where something is strided by it
+inline bool bad_ld_of(const void *ptr, int64_t ld, int64_t width) { return ptr ? bad_ld(ld, width) : ld >= ((int64_t)1 << 29); }
 
 }  // namespace gnna
 

@@ -35,11 +35,13 @@ namespace {
 
 using gat::VT;
 using gat::load_piece;
-
-constexpr int kTile = GNNA_POOL_TILE_ROWS;
-constexpr int kRowsInFlight = 4;     // 16-byte loads in flight per lane in the row walk
-// A segment whose pieces would keep its wavefront for more than kLongSteps steps of the join goes to the whole block.
-constexpr int kLongSteps = GNNA_POOL_LONG_STEPS;
+using seg::kTile;
+using seg::kRowsInFlight;
+using seg::kLongSteps;
+using seg::seg_ptr;
+using seg::first_segment;
+using seg::uniform64;
+using seg::store_piece;
 
 struct PoolArgs {
     const float *X;             // forward: the rows
@@ -54,12 +56,6 @@ struct PoolArgs {
     u64 *Pmax, *Pmin;
     int D, mean;
 };
-
-// (the clamped pointers, the search for a tile's first segment and the partial store: gnna_segments.h)
-using seg::seg_ptr;
-using seg::first_segment;
-using seg::uniform64;
-using seg::store_piece;
 
 // what a lane holds of a piece or a segment: four columns
 struct Acc {
@@ -362,47 +358,24 @@ pool_bwd_kernel(const BwdArgs p)
     }
 }
 
-// Scratch of the forward entry: slot 13 = the pieces of the tiles (max keys, min keys, sums).  Eager calls of a stream share it
-// (grow-only), a captured call gets its capture's own.
+// Scratch of the forward entry: slot 13 = the pieces of the tiles (max keys, min keys, sums; seg::get_pieces).
 constexpr int kSlotPoolPieces = 13;
-
-// a stride that is checked against `dim` only where something is strided by it
-bool bad_ld_of(const void *ptr, int64_t ld, int dim) { return ptr ? bad_ld(ld, dim) : ld >= ((int64_t)1 << 29); }
 
 // what both entries check alike, before any device work
 int check_sizes(const char *what, int64_t num_rows, int64_t num_segments, int dim, unsigned flags)
 {
     if (flags & ~GNNA_POOL_MEAN)
         return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x (GNNA_POOL_MEAN is the only flag)", what, flags & ~GNNA_POOL_MEAN);
-    if (dim < 1) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: dim must be >= 1 (got %d)", what, dim);
-    if (num_rows < 0 || num_segments < 0)
-        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: negative size (num_rows=%lld num_segments=%lld)", what, (long long)num_rows,
-                    (long long)num_segments);
-    if (num_segments >= ((int64_t)1 << 29))
-        return fail(GNNA_ERR_UNSUPPORTED, "%s: %lld segments in one call (at most 536870911): shard the batch", what,
-                    (long long)num_segments);
-    if (num_rows > 0x7fffffffll)
-        return fail(GNNA_ERR_UNSUPPORTED, "%s: %lld rows in one call (at most 2147483647: graph_pointers is int32)", what,
-                    (long long)num_rows);
-    return GNNA_OK;
+    const int rc = seg::check_dim(what, dim);
+    return rc != GNNA_OK ? rc : seg::check_counts(what, num_rows, num_segments);
 }
 
 template <bool SUM, bool EXT>
 int launch_forward(int log_lpr, hipStream_t stream, const PoolArgs &a)
 {
-    const int64_t tiles = (a.N + kTile - 1) / kTile;
-    int rc = GNNA_OK;
-    dispatch_lpr(log_lpr, [&](auto L) {
-        if (tiles > 0) {
-            hipLaunchKernelGGL((pool_tile_kernel<SUM, EXT, decltype(L)::value>), dim3((unsigned)((tiles + kWavesPerBlock - 1) / kWavesPerBlock)),
-                               dim3(kBlock), 0, stream, a);
-            if ((rc = launch_ok("segment pooling: tile launch")) != GNNA_OK) return;
-        }
-        hipLaunchKernelGGL((pool_finish_kernel<SUM, EXT, decltype(L)::value>), dim3((unsigned)((a.G + kWavesPerBlock - 1) / kWavesPerBlock)),
-                           dim3(kBlock), 0, stream, a);
-        rc = launch_ok("segment pooling: finish launch");
+    return seg::launch_tiles_then_finish("segment pooling", log_lpr, stream, a, [](auto L) {
+        return std::make_pair(pool_tile_kernel<SUM, EXT, decltype(L)::value>, pool_finish_kernel<SUM, EXT, decltype(L)::value>);
     });
-    return rc;
 }
 
 }  // namespace
@@ -448,23 +421,13 @@ int gnna_segment_pool_ld_f32(const float *input, int64_t ld_in, int64_t num_rows
     a.X = input; a.ldx = (size_t)ld_in; a.gp = graph_pointers; a.N = num_rows; a.G = num_segments;
     a.sum = sum; a.mx = max_out; a.mn = min_out; a.amx = argmax; a.amn = argmin;
     a.lds = (size_t)ld_sum; a.ldmx = (size_t)ld_max; a.ldamx = (size_t)ld_argmax; a.ldmn = (size_t)ld_min; a.ldamn = (size_t)ld_argmin;
-    a.Ps = nullptr; a.Pmax = a.Pmin = nullptr;
     a.D = dim; a.mean = (flags & GNNA_POOL_MEAN) ? 1 : 0;
-    const int64_t tiles = (num_rows + kTile - 1) / kTile;
-    if (tiles > 0) {
-        // two pieces per tile; the keys first, so that they are 8-byte aligned
-        const size_t cells = (size_t)tiles * 2 * (size_t)dim;
-        const size_t bytes = cells * ((extrema ? 2 * sizeof(u64) : 0) + (want_sum ? sizeof(float) : 0));
-        void *ws = nullptr;
-        if ((rc = get_workspace(ds, stream, kSlotPoolPieces, (bytes + 255) & ~(size_t)255, &ws)) != GNNA_OK) return rc;
-        char *at = static_cast<char *>(ws);
-        if (extrema) {
-            a.Pmax = reinterpret_cast<u64 *>(at);
-            a.Pmin = a.Pmax + cells;
-            at += 2 * cells * sizeof(u64);
-        }
-        if (want_sum) a.Ps = reinterpret_cast<float *>(at);
-    }
+    // the keys first, so that they are 8-byte aligned
+    const size_t key_bytes = extrema ? (size_t)dim * sizeof(u64) : 0;
+    const size_t piece_bytes[3] = {key_bytes, key_bytes, want_sum ? (size_t)dim * sizeof(float) : 0};
+    void *pieces[3];
+    if ((rc = seg::get_pieces(ds, stream, kSlotPoolPieces, num_rows, piece_bytes, pieces)) != GNNA_OK) return rc;
+    a.Pmax = static_cast<u64 *>(pieces[0]); a.Pmin = static_cast<u64 *>(pieces[1]); a.Ps = static_cast<float *>(pieces[2]);
     const int log_lpr = log2_lanes(dim, 4);
     if (want_sum && extrema) return launch_forward<true, true>(log_lpr, stream, a);
     if (want_sum) return launch_forward<true, false>(log_lpr, stream, a);

@@ -27,7 +27,6 @@
 #include <cstdint>
 
 #include "gnna_segnorm.h"
-#include "gnna_pool.h"           // GNNA_POOL_TILE_ROWS, GNNA_POOL_LONG_STEPS
 #include "gnna_device.h"
 #include "gnna_gat_common.h"     // gat::load_piece, gat::check_alias
 #include "gnna_internal.h"
@@ -38,14 +37,13 @@ namespace {
 
 using gat::VT;
 using gat::load_piece;
+using seg::kTile;
+using seg::kRowsInFlight;
+using seg::kLongSteps;
 using seg::seg_ptr;
 using seg::first_segment;
 using seg::uniform64;
 using seg::store_piece;
-
-constexpr int kTile = GNNA_POOL_TILE_ROWS;
-constexpr int kRowsInFlight = 4;
-constexpr int kLongSteps = GNNA_POOL_LONG_STEPS;
 
 enum Mode { MOMENTS = 0, NORM = 1, SUMS = 2 };
 
@@ -382,25 +380,15 @@ seg_apply_kernel(const SegArgs p)
     }
 }
 
-// Scratch of the moments and of the backward sums: slot 16 = the pieces of the tiles, (a, b) per column.  Eager calls of a stream
-// share it (grow-only), a captured call gets its capture's own.
+// Scratch of the moments and of the backward sums: slot 16 = the pieces of the tiles, (a, b) per column (seg::get_pieces).
 constexpr int kSlotSegnormPieces = 16;
 
 // what the three entries check alike, before any device work
 int check_sizes(const char *what, int64_t num_rows, int64_t num_segments, int dim, unsigned flags)
 {
     if (flags) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x (the entry has no flags)", what, flags);
-    if (dim < 1) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: dim must be >= 1 (got %d)", what, dim);
-    if (num_rows < 0 || num_segments < 0)
-        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: negative size (num_rows=%lld num_segments=%lld)", what, (long long)num_rows,
-                    (long long)num_segments);
-    if (num_segments >= ((int64_t)1 << 29))
-        return fail(GNNA_ERR_UNSUPPORTED, "%s: %lld segments in one call (at most 536870911): shard the batch", what,
-                    (long long)num_segments);
-    if (num_rows > 0x7fffffffll)
-        return fail(GNNA_ERR_UNSUPPORTED, "%s: %lld rows in one call (at most 2147483647: graph_pointers is int32)", what,
-                    (long long)num_rows);
-    return GNNA_OK;
+    const int rc = seg::check_dim(what, dim);
+    return rc != GNNA_OK ? rc : seg::check_counts(what, num_rows, num_segments);
 }
 
 template <size_t K>
@@ -414,35 +402,21 @@ bool misaligned(const void *const (&ptrs)[K])
 // the pieces of a call's tiles in library scratch
 int get_pieces(DeviceState *ds, hipStream_t stream, SegArgs *a)
 {
-    const int64_t tiles = (a->N + kTile - 1) / kTile;
-    a->P1 = a->P2 = nullptr;
-    if (tiles == 0) return GNNA_OK;
-    const size_t cells = (size_t)tiles * 2 * (size_t)a->D;
-    void *ws = nullptr;
-    const int rc = get_workspace(ds, stream, kSlotSegnormPieces, (2 * cells * sizeof(float) + 255) & ~(size_t)255, &ws);
-    if (rc != GNNA_OK) return rc;
-    a->P1 = static_cast<float *>(ws);
-    a->P2 = a->P1 + cells;
-    return GNNA_OK;
+    const size_t piece_bytes[2] = {(size_t)a->D * sizeof(float), (size_t)a->D * sizeof(float)};
+    void *pieces[2];
+    const int rc = seg::get_pieces(ds, stream, kSlotSegnormPieces, a->N, piece_bytes, pieces);
+    a->P1 = static_cast<float *>(pieces[0]);
+    a->P2 = static_cast<float *>(pieces[1]);
+    return rc;
 }
 
 // the tile and finish kernels of a call with G > 0: every element of o1 and o2 [G, D] is written
 template <int MODE>
 int launch_segments(const char *noun, int log_lpr, hipStream_t stream, const SegArgs &a)
 {
-    const int64_t tiles = (a.N + kTile - 1) / kTile;
-    int rc = GNNA_OK;
-    dispatch_lpr(log_lpr, [&](auto L) {
-        if (tiles > 0) {
-            hipLaunchKernelGGL((seg_tile_kernel<MODE, decltype(L)::value>), dim3((unsigned)((tiles + kWavesPerBlock - 1) / kWavesPerBlock)),
-                               dim3(kBlock), 0, stream, a);
-            if ((rc = launch_ok("%s: tile launch", noun)) != GNNA_OK) return;
-        }
-        hipLaunchKernelGGL((seg_finish_kernel<MODE, decltype(L)::value>), dim3((unsigned)((a.G + kWavesPerBlock - 1) / kWavesPerBlock)),
-                           dim3(kBlock), 0, stream, a);
-        rc = launch_ok("%s: finish launch", noun);
+    return seg::launch_tiles_then_finish(noun, log_lpr, stream, a, [](auto L) {
+        return std::make_pair(seg_tile_kernel<MODE, decltype(L)::value>, seg_finish_kernel<MODE, decltype(L)::value>);
     });
-    return rc;
 }
 
 // the pass over the rows of a call with N > 0: every element of a.out [N, D] is written

@@ -221,9 +221,6 @@ void launch_main(int log_lpr, dim3 grid, hipStream_t stream, const StatsArgs &a)
 // (grow-only), a captured call gets its capture's own.
 constexpr int kSlotStatsKeys = 11;
 
-// a stride that is checked against `dim` only where something is strided by it
-bool bad_ld_of(const void *ptr, int64_t ld, int dim) { return ptr ? bad_ld(ld, dim) : ld >= ((int64_t)1 << 29); }
-
 }  // namespace
 }  // namespace gnna
 
