@@ -200,6 +200,14 @@ STAGED_NEXT["gnna_walk.h"] = {
     # sub_edge_ids, partPtr, part2Node, node_capacity, edge_capacity, counts, stream
     "gnna_induced_subgraph_i32": (i, [p, p, i64, i64, p, i64, i] + [p] * 7 + [i64, i64, pi64, p]),
 }
+# message passing with a feature row per edge (GINE, SchNet's continuous-filter convolution)
+STAGED_NEXT["gnna_edgefeat.h"] = {
+    # input, ld_in, num_in_rows, edge_feat, ld_e, num_edges, row_pointers, column_index, out, ld_out, num_out_rows, dim, combine, act, flags, stream
+    "gnna_agg_edge_feat_ld_f32": (i, [p, i64, i64, p, i64, i64, p, p, p, i64, i64, i, i, i, u, p]),
+    # input, ld_in, num_in_rows, edge_feat, ld_e, num_edges, (dY, ld), the structure, the transposed structure, t_edge_pos, (d_input, ld)
+    # (d_edge, ld), num_out_rows, dim, combine, act, flags, stream
+    "gnna_agg_edge_feat_backward_ld_f32": (i, [p, i64, i64, p, i64, i64, p, i64] + [p] * 5 + [p, i64] * 2 + [i64, i, i, i, u, p]),
+}
 del p, i, i64, u, u64, f, s, pd, pi, pi64
 EXPORTS = tuple(HEADERS["gnna.h"])     # users: the build's check of the library, tests/test_host.py
 
@@ -941,6 +949,71 @@ def agg_softmax_backward(X, temp, lse, Y, dY, t_row_pointers, t_column_index, ou
     _call(X.device, "gnna_agg_softmax_backward_ld_f32", xp, ld_in, n_in, tp, tl, lp, ld_lse, yp, ld_y, gp, ld_dy,
           t_row_pointers.data_ptr(), _ids_ptr(t_column_index, t_row_pointers), op_, ld_din, n_out, dim, 0)
     return out
+
+
+EDGE_ADD, EDGE_MUL = 0, 1               # GNNA_EDGE_ADD / GNNA_EDGE_MUL
+EDGE_ACT_NONE, EDGE_ACT_RELU = 0, 1     # GNNA_EDGE_ACT_NONE / GNNA_EDGE_ACT_RELU
+
+
+def _edge_rows(E, nnz, dim, device, what):
+    """(pointer, leading dimension) of an edge-major float32 [nnz, dim] device tensor with contiguous rows."""
+    assert E.dim() == 2 and tuple(E.shape) == (nnz, dim) and E.device == device, \
+        f"{what} must be [nnz = {nnz}, dim = {dim}] on {device} (got {tuple(E.shape)})"
+    if nnz == 0:                            # no row: nothing is strided, whatever strides an empty tensor carries
+        assert E.dtype == torch.float32, f"{what} must be a float32 tensor"
+        return None, dim
+    ep, _, _, ld_e = _rows_view(E, what)
+    return ep, ld_e
+
+
+def agg_edge_feat(X, E, row_pointers, column_index, num_out_rows=None, combine=EDGE_ADD, act=EDGE_ACT_NONE, out=None):
+    """gnna_agg_edge_feat_ld_f32 (csrc/gnna_edgefeat.h): out[i, f] = sum over the positions e of row i of the CSR (row_pointers,
+    column_index) of act(X[column_index[e], f] (+ | *) E[e, f]) -- combine EDGE_ADD | EDGE_MUL, act EDGE_ACT_NONE | EDGE_ACT_RELU --
+    in one gather that streams E once.  E: [nnz, dim], edge-major in the order of column_index.  -> out [num_out_rows, dim]
+    (num_out_rows: row_pointers.numel() - 1 when not given); rows without edges get 0.  `X`, `E` and a caller's `out` may be
+    row-strided views (stride(1) == 1).  The same bits on every run; accepted under set_tuning(deterministic=1)."""
+    _need_device(X, "aggregation")
+    xp, n_in, dim, ld_in = _rows_view(X, "X")
+    n_out = row_pointers.numel() - 1 if num_out_rows is None else int(num_out_rows)
+    assert row_pointers.numel() == n_out + 1, f"row_pointers must be [num_out_rows + 1 = {n_out + 1}] (got {row_pointers.numel()} entries)"
+    nnz = column_index.numel()
+    ep, ld_e = _edge_rows(E, nnz, dim, X.device, "E")
+    out, op_, ld_out = _out_rows(out, n_out, dim, X.device)
+    _call(X.device, "gnna_agg_edge_feat_ld_f32", xp, ld_in, n_in, ep, ld_e, nnz, row_pointers.data_ptr(), _ids_ptr(column_index, row_pointers),
+          op_, ld_out, n_out, dim, int(combine), int(act), 0)
+    return out
+
+
+def agg_edge_feat_backward(X, E, dY, row_pointers, column_index, t_row_pointers=None, t_column_index=None, t_edge_pos=None,
+                           combine=EDGE_ADD, act=EDGE_ACT_NONE, want_dx=True, want_de=True, dX=None, dE=None):
+    """gnna_agg_edge_feat_backward_ld_f32: the gradients of agg_edge_feat from its inputs and dY [num_out_rows, dim] -> (dX | None,
+    dE | None).  dE [nnz, dim] is made over the rows of the structure itself.  dX (like X) is made over A^T (t_row_pointers,
+    t_column_index: X.shape[0] rows whose ids are destination rows) with t_edge_pos[p] = the position in column_index of the edge
+    that transposed position p stands for (transpose_csr's perm, or reverse_edges of a symmetric structure); the three are needed
+    only with want_dx.  The relu mask is recomputed from X and E: nothing was saved.  Strided views as in agg_edge_feat."""
+    _need_device(X, "aggregation")
+    xp, n_in, dim, ld_in = _rows_view(X, "X")
+    gp, n_out, wg, ld_dy = _rows_view(dY, "dY")
+    assert wg == dim and row_pointers.numel() == n_out + 1, "dY must be [num_out_rows, dim] and row_pointers [num_out_rows + 1]"
+    nnz = column_index.numel()
+    ep, ld_e = _edge_rows(E, nnz, dim, X.device, "E")
+    dxp, ld_din, dep, ld_de, t_args = None, dim, None, dim, (None, None, None)
+    if want_dx:
+        assert t_row_pointers is not None and t_column_index is not None and t_edge_pos is not None, \
+            "want_dx needs the transposed structure and t_edge_pos"
+        assert t_row_pointers.numel() == n_in + 1 and t_column_index.numel() == nnz and t_edge_pos.numel() == nnz and \
+            t_edge_pos.dtype == torch.int32, "t_row_pointers must be [num_in_rows + 1], t_column_index and t_edge_pos int32 [nnz]"
+        dX, dxp, ld_din = _out_rows(dX, n_in, dim, X.device)
+        t_args = (t_row_pointers.data_ptr(), _ids_ptr(t_column_index, t_row_pointers), _ids_ptr(t_edge_pos, t_row_pointers))
+    else:
+        dX = None
+    if want_de:
+        dE, dep, ld_de = _out_rows(dE, nnz, dim, X.device)
+    else:
+        dE = None
+    _call(X.device, "gnna_agg_edge_feat_backward_ld_f32", xp, ld_in, n_in, ep, ld_e, nnz, gp, ld_dy, row_pointers.data_ptr(),
+          _ids_ptr(column_index, row_pointers), *t_args, dxp, ld_din, dep, ld_de, n_out, dim, int(combine), int(act), 0)
+    return dX, dE
 
 
 POOL_TILE_ROWS = 256            # GNNA_POOL_TILE_ROWS: the rows a wavefront walks; segments that cross a multiple of it are joined from pieces

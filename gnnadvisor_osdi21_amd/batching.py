@@ -34,7 +34,7 @@ class GraphBatch(object):
     ``inv_counts`` (float32 [G]: 1 / max(rows of the graph, 1)) are built at their first use; the fused readout needs neither."""
 
     def __init__(self, row_pointers, column_index, graph_pointers, degrees=None, partSize=32, dimWorker=None, warpPerBlock=None,
-                 hiddenDim=64, directed=False, x=None, y=None, partPtr=None, part2Node=None):
+                 hiddenDim=64, directed=False, x=None, y=None, edge_attr=None, partPtr=None, part2Node=None):
         for name, t in (("row_pointers", row_pointers), ("column_index", column_index), ("graph_pointers", graph_pointers)):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1:
                 raise TypeError(f"{name} must be a 1-D int32 tensor")
@@ -50,6 +50,10 @@ class GraphBatch(object):
         self.warpPerBlock = int(warpPerBlock) if warpPerBlock is not None else WAVES_PER_BLOCK
         self.directed = bool(directed)
         self.x, self.y = x, y
+        if edge_attr is not None and (edge_attr.dim() != 2 or edge_attr.shape[0] != column_index.numel()):
+            raise ValueError(f"edge_attr must be [nnz = {column_index.numel()}, K] in the order of column_index "
+                             f"(got {tuple(edge_attr.shape)})")
+        self.edge_attr = edge_attr                                 # [nnz, K] or None: one row per position of column_index
         if (partPtr is None) != (part2Node is None):
             raise ValueError("partPtr and part2Node come together")
         if partPtr is not None:                                    # the partition of these row pointers at partSize, already built
@@ -115,17 +119,23 @@ class GraphBatch(object):
                            warpPerBlock=self.warpPerBlock, directed=self.directed, partPtr=r["partPtr"], part2Node=r["part2Node"])
         return small, TopKSelection(r["perm"], r["new_id"], r["edge_ids"], self.num_nodes)
 
+    def carry_edge_attr(self, small, selection):
+        """Gives the coarsened batch `small` the edge_attr rows of its surviving edges (``coarsen(..., want_edge_ids=True)``);
+        nothing when this batch has none.  -> small."""
+        small.edge_attr = None if self.edge_attr is None else self.edge_attr[selection.edge_ids.long()]
+        return small
+
     def to(self, device):
         move = lambda t: None if t is None else t.to(device)                                       # noqa: E731
         return GraphBatch(self.row_pointers.to(device), self.column_index.to(device), self.graph_pointers.to(device),
                           self.degrees.to(device), self.partSize, self.dimWorker, self.warpPerBlock, directed=self.directed,
-                          x=move(self.x), y=move(self.y))
+                          x=move(self.x), y=move(self.y), edge_attr=move(self.edge_attr))
 
     @staticmethod
-    def from_graphs(graphs, partSize=32, x=None, y=None, **kw):
+    def from_graphs(graphs, partSize=32, x=None, y=None, edge_attr=None, **kw):
         """Collates a list of ``graph.CSRGraph`` (or of (row_pointers, column_index) pairs) on the host: the rows and the column
         ids of graph g are shifted by the rows before it.  A graph without nodes is an empty segment.  Refuses row pointers that
-        do not ascend."""
+        do not ascend.  `edge_attr` [nnz, K]: the edge rows of the graphs one after the other, which is the batch's edge order."""
         rps, cis, sizes = [], [], []
         for k, g in enumerate(graphs):
             rp, ci = (g.row_pointers, g.column_index) if hasattr(g, "row_pointers") else g
@@ -151,27 +161,33 @@ class GraphBatch(object):
             raise ValueError("a batch holds fewer than 2^31 nodes and edges (int32 CSR)")
         column_index = torch.cat(column_index) if column_index else torch.zeros(0, dtype=torch.int64)
         return GraphBatch(torch.cat(row_pointers).to(torch.int32), column_index.to(torch.int32), gp.to(torch.int32),
-                          partSize=partSize, x=x, y=y, **kw)
+                          partSize=partSize, x=x, y=y, edge_attr=edge_attr, **kw)
 
 
 class GraphDataset(object):
     """Many graphs as one concatenated CSR on a device: ``row_pointers`` [N + 1] and ``column_index`` with ids LOCAL to their
-    graph, ``graph_pointers`` [G + 1], node features ``x`` [N, F] and one label ``y`` per graph."""
+    graph, ``graph_pointers`` [G + 1], node features ``x`` [N, F], one label ``y`` per graph and, optionally, edge features
+    ``edge_attr`` [nnz, K] in the order of ``column_index``."""
 
-    def __init__(self, row_pointers, column_index, graph_pointers, x=None, y=None):
+    def __init__(self, row_pointers, column_index, graph_pointers, x=None, y=None, edge_attr=None):
         self.row_pointers, self.column_index, self.graph_pointers = row_pointers, column_index, graph_pointers
         self.x, self.y = x, y
+        if edge_attr is not None and (edge_attr.dim() != 2 or edge_attr.shape[0] != column_index.numel()):
+            raise ValueError(f"edge_attr must be [nnz = {column_index.numel()}, K] in the order of column_index "
+                             f"(got {tuple(edge_attr.shape)})")
+        self.edge_attr = edge_attr
         self.num_graphs = int(graph_pointers.numel()) - 1
         self.num_nodes = int(row_pointers.numel()) - 1
 
     @staticmethod
-    def from_graphs(graphs, x=None, y=None, device="cpu"):
+    def from_graphs(graphs, x=None, y=None, device="cpu", edge_attr=None):
         """From a list of ``graph.CSRGraph``: the arrays of ``GraphBatch.from_graphs`` with the column ids left local."""
         b = GraphBatch.from_graphs(graphs)
         local = b.column_index.long() - b.graph_pointers.long()[:-1][b.batch[b.edge_rows().long()]] if b.column_index.numel() \
             else b.column_index.long()
         move = lambda t: None if t is None else t.to(device)                                       # noqa: E731
-        return GraphDataset(b.row_pointers.to(device), local.to(torch.int32).to(device), b.graph_pointers.to(device), move(x), move(y))
+        return GraphDataset(b.row_pointers.to(device), local.to(torch.int32).to(device), b.graph_pointers.to(device), move(x), move(y),
+                            move(edge_attr))
 
     def __len__(self):
         return self.num_graphs
@@ -201,4 +217,6 @@ class GraphDataset(object):
         y = None if self.y is None else self.y[ids]
         b = GraphBatch(new_rp.to(torch.int32), ci.to(torch.int32), new_gp.to(torch.int32), partSize=partSize, x=x, y=y, **kw)
         b._batch = which
+        if self.edge_attr is not None:
+            b.edge_attr = self.edge_attr[edges]
         return b

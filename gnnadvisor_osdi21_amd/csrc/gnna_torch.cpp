@@ -43,6 +43,7 @@
 #include "gnna_topk.h"
 #include "gnna_segnorm.h"        // staged beside the sources (its first paragraph)
 #include "gnna_walk.h"           // staged likewise
+#include "gnna_edgefeat.h"       // staged likewise
 
 #define CHECK_CUDA(x) TORCH_CHECK(x.is_cuda(), #x " must be a CUDA tensor")
 #define CHECK_CONTIGUOUS(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -521,6 +522,84 @@ torch::Tensor aggregate_softmax_backward(const torch::Tensor &input, const torch
                                               ld_of(dY), t_row_pointers.data_ptr<int32_t>(), softagg_ids(t_column_index, t_row_pointers),
                                               out.data_ptr<float>(), dim, n, (int)dim, 0u, current_stream()));
     return out;
+}
+
+// Message passing with a feature row per edge (gnna_agg_edge_feat_ld_f32, csrc/gnna_edgefeat.h) -> out [num_out_rows, dim] with
+// num_out_rows = row_pointers.size(0) - 1: the sum over a row's positions e of act(X[column_index[e]] (+ | *) E[e]).  E: [nnz, dim],
+// edge-major.  Strided X and E as aggregate_ld.
+static void edgefeat_check(const torch::Tensor &input, const torch::Tensor &edge_feat, const torch::Tensor &row_pointers,
+                           const torch::Tensor &column_index)
+{
+    CHECK_CUDA(input);
+    TORCH_CHECK(input.dim() == 2, "input must be 2-D [num_nodes, dim]");
+    CHECK_F32(input);
+    CHECK_CUDA(edge_feat);
+    CHECK_F32(edge_feat);
+    check_ids(row_pointers, "row_pointers");
+    check_ids(column_index, "column_index");
+    TORCH_CHECK(input.size(1) >= 1, "input must have at least one column");
+    TORCH_CHECK(edge_feat.dim() == 2 && edge_feat.size(0) == column_index.numel() && edge_feat.size(1) == input.size(1),
+                "edge_feat must be [nnz = ", column_index.numel(), ", dim = ", input.size(1), "] in the order of column_index");
+    TORCH_CHECK(row_pointers.dim() == 1 && row_pointers.size(0) >= 1, "row_pointers must be [rows + 1]");
+    TORCH_CHECK(edge_feat.device() == input.device() && row_pointers.device() == input.device() &&
+                column_index.device() == input.device(), "input, edge_feat, row_pointers and column_index must be on one device");
+    check_rows(input, "input");
+    if (edge_feat.size(0) > 0) check_rows(edge_feat, "edge_feat");       // (no row: nothing is strided by whatever an empty tensor carries)
+}
+torch::Tensor aggregate_edge_feat(const torch::Tensor &input, const torch::Tensor &edge_feat, const torch::Tensor &row_pointers,
+                                  const torch::Tensor &column_index, int combine, int act)
+{
+    edgefeat_check(input, edge_feat, row_pointers, column_index);
+    const int64_t n_in = input.size(0), dim = input.size(1), n = row_pointers.size(0) - 1, nnz = column_index.numel();
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(input.device());
+    const torch::Tensor out = fresh({n, dim}, input.options());
+    check_rc(gnna_agg_edge_feat_ld_f32(input.data_ptr<float>(), ld_of(input), n_in, edge_feat.data_ptr<float>(), ld_of(edge_feat), nnz,
+                                       row_pointers.data_ptr<int32_t>(), softagg_ids(column_index, row_pointers), out.data_ptr<float>(), dim,
+                                       n, (int)dim, combine, act, 0u, current_stream()));
+    return out;
+}
+
+// Backward of aggregate_edge_feat (gnna_agg_edge_feat_backward_ld_f32) -> (d_input | None, d_edge | None).  The transposed structure
+// and t_edge_pos (transpose_csr's perm, or the reverse-edge map of a symmetric structure) are needed only with want_dx.
+std::tuple<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>>
+aggregate_edge_feat_backward(const torch::Tensor &input, const torch::Tensor &edge_feat, const torch::Tensor &dY,
+                             const torch::Tensor &row_pointers, const torch::Tensor &column_index,
+                             const c10::optional<torch::Tensor> &t_row_pointers, const c10::optional<torch::Tensor> &t_column_index,
+                             const c10::optional<torch::Tensor> &t_edge_pos, int combine, int act, bool want_dx, bool want_de)
+{
+    edgefeat_check(input, edge_feat, row_pointers, column_index);
+    const int64_t n_in = input.size(0), dim = input.size(1), n = row_pointers.size(0) - 1, nnz = column_index.numel();
+    CHECK_CUDA(dY);
+    CHECK_F32(dY);
+    TORCH_CHECK(dY.dim() == 2 && dY.size(0) == n && dY.size(1) == dim && dY.device() == input.device(),
+                "dY must be [num_out_rows, dim] on input's device");
+    check_rows(dY, "dY");
+    const int32_t *trp = nullptr, *tci = nullptr, *tpos = nullptr;
+    if (want_dx) {
+        TORCH_CHECK(t_row_pointers.has_value() && t_column_index.has_value() && t_edge_pos.has_value(),
+                    "want_dx needs t_row_pointers, t_column_index and t_edge_pos");
+        check_ids(*t_row_pointers, "t_row_pointers");
+        check_ids(*t_column_index, "t_column_index");
+        check_ids(*t_edge_pos, "t_edge_pos");
+        TORCH_CHECK(t_row_pointers->numel() == n_in + 1 && t_column_index->numel() == nnz && t_edge_pos->numel() == nnz,
+                    "t_row_pointers must be [num_in_rows + 1], t_column_index and t_edge_pos [nnz]");
+        TORCH_CHECK(t_row_pointers->device() == input.device() && t_column_index->device() == input.device() &&
+                    t_edge_pos->device() == input.device(), "the transposed structure must be on input's device");
+        trp = t_row_pointers->data_ptr<int32_t>();
+        tci = softagg_ids(*t_column_index, *t_row_pointers);
+        tpos = softagg_ids(*t_edge_pos, *t_row_pointers);
+    }
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(input.device());
+    c10::optional<torch::Tensor> dX, dE;
+    if (want_dx) dX = fresh({n_in, dim}, input.options());
+    if (want_de) dE = fresh({nnz, dim}, input.options());
+    check_rc(gnna_agg_edge_feat_backward_ld_f32(input.data_ptr<float>(), ld_of(input), n_in, edge_feat.data_ptr<float>(), ld_of(edge_feat),
+                                                nnz, dY.data_ptr<float>(), ld_of(dY), row_pointers.data_ptr<int32_t>(),
+                                                softagg_ids(column_index, row_pointers), trp, tci, tpos,
+                                                dX.has_value() ? dX->data_ptr<float>() : nullptr, dim,
+                                                dE.has_value() ? dE->data_ptr<float>() : nullptr, dim, n, (int)dim, combine, act, 0u,
+                                                current_stream()));
+    return std::make_tuple(dX, dE);
 }
 
 // Graph-level readout (gnna_segment_pool_ld_f32) -> (sum, max, argmax, min, argmin), each [num_graphs, dim] with num_graphs =
@@ -1750,6 +1829,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           "dY[i, f] (1 + temp[f] (X[j, f] - Y[i, f]))",
           pybind11::arg("X"), pybind11::arg("temp"), pybind11::arg("lse"), pybind11::arg("Y"), pybind11::arg("dY"),
           pybind11::arg("t_row_pointers"), pybind11::arg("t_column_index"));
+    m.def("aggregate_edge_feat", &aggregate_edge_feat,
+          "message passing with a feature row per edge, in one gather (extension) -> out: out[i, f] = sum over the positions e of row i "
+          "of act(X[column_index[e], f] (+ | *) E[e, f]); combine 0 add, 1 multiply; act 0 none, 1 relu; E is [nnz, dim], edge-major",
+          pybind11::arg("X"), pybind11::arg("E"), pybind11::arg("row_pointers"), pybind11::arg("column_index"),
+          pybind11::arg("combine") = 0, pybind11::arg("act") = 0);
+    m.def("aggregate_edge_feat_backward", &aggregate_edge_feat_backward,
+          "backward of aggregate_edge_feat (extension) -> (dX | None, dE | None); the relu mask is recomputed from X and E; dX runs over "
+          "the transposed structure with t_edge_pos (transpose_csr's perm, or the reverse-edge map of a symmetric structure)",
+          pybind11::arg("X"), pybind11::arg("E"), pybind11::arg("dY"), pybind11::arg("row_pointers"), pybind11::arg("column_index"),
+          pybind11::arg("t_row_pointers") = pybind11::none(), pybind11::arg("t_column_index") = pybind11::none(),
+          pybind11::arg("t_edge_pos") = pybind11::none(), pybind11::arg("combine") = 0, pybind11::arg("act") = 0,
+          pybind11::arg("want_dx") = true, pybind11::arg("want_de") = true);
     m.def("segment_pool", &segment_pool,
           "graph-level readout (extension) -> (sum, max, argmax, min, argmin), each [num_graphs, dim]: over the rows "
           "[graph_pointers[g], graph_pointers[g + 1]) of X, from one read of X; argmax / argmin are the winning rows (-1 and the value 0 "

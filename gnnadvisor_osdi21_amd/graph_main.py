@@ -1,6 +1,7 @@
 """Graph classification on batches of small graphs: conv layers, a readout, a linear layer.
 
     python -m gnnadvisor_osdi21_amd.graph_main --model gin --num_graphs 4096 --graph_nodes 8,72 --batch_graphs 256 --readout sum
+    python -m gnnadvisor_osdi21_amd.graph_main --model gine --edge_dim 4 --num_graphs 4096 --batch_graphs 256
 
 The reference evaluates half of its inputs ("Type II": collections of small graphs) with node-level drivers only; this driver
 finishes such a model inside the library.  A seeded synthetic collection (graph.small_graphs) is kept on the device as a
@@ -11,6 +12,9 @@ rows of every graph to one row (ops.Readout, one fused call for all
 the statistics of ``--readout``; with ``--attention_readout scalar|channel`` an ops.AttentionalReadout next to them), and trains
 a per-graph classifier.  Prints ``Time (ms): %.3f`` per epoch as main.py does.
 The label of a graph is a function of its size and its features' mean, so that the loss has something to learn.
+``--model gine --edge_dim K`` draws K features per edge (not symmetrised: e_ij != e_ji), lets the label depend on them too, and
+trains edgeconv.GINEConv layers on mini-batches built as ``directed`` ones, so that the backward finds an edge's features through
+the device-built ``perm`` of the transposed batch; with ``--pool`` the edge features follow the coarsening.
 """
 import argparse
 import sys
@@ -27,7 +31,9 @@ def _bool(text):
 
 def build_parser():
     p = argparse.ArgumentParser(description="graph classification on batches of small graphs")
-    p.add_argument("--model", type=str, default="gin", help="gcn or gin")
+    p.add_argument("--model", type=str, default="gin", help="gcn, gin, or gine (GIN with edge features: needs --edge_dim)")
+    p.add_argument("--edge_dim", type=int, default=0, help="--model gine: features per edge of the synthetic collection")
+    p.add_argument("--fused_edge", type=_bool, default=True, help="False: the edge-feature aggregation composed from torch ops")
     p.add_argument("--num_graphs", type=int, default=4096, help="graphs in the synthetic collection")
     p.add_argument("--graph_nodes", type=str, default="8,72", help="MIN,MAX nodes per graph")
     p.add_argument("--avg_degree", type=float, default=4.0, help="average degree inside a graph")
@@ -58,9 +64,13 @@ def build_parser():
 
 
 def _parse(args):
-    if args.model not in ("gcn", "gin"):
-        raise SystemExit("--model %s: graph_main trains gcn or gin (the other layers take a GraphBatch too: build the model with ops)"
-                         % args.model)
+    if args.model not in ("gcn", "gin", "gine"):
+        raise SystemExit("--model %s: graph_main trains gcn or gin (the other layers take a GraphBatch too: build the model with ops), "
+                         "or gine with --edge_dim K" % args.model)
+    if args.model == "gine" and args.edge_dim < 1:
+        raise SystemExit("--model gine needs --edge_dim K with K >= 1: the features per edge (got %d)" % args.edge_dim)
+    if args.model != "gine" and args.edge_dim != 0:
+        raise SystemExit("--edge_dim %d: only --model gine takes edge features (got --model %s)" % (args.edge_dim, args.model))
     if args.dtype != "float32":
         raise SystemExit("--dtype %s: the readout (sum / mean / max / min over the rows of a graph) is float32 only; "
                          "run graph_main with --dtype float32" % args.dtype)
@@ -94,17 +104,23 @@ def _parse(args):
 
 
 def build_model(args, modes):
-    from torch.nn import Linear, Module, ModuleList
+    from torch.nn import Linear, Module, ModuleList, ReLU, Sequential
 
     from .ops import AttentionalReadout, GCNConv, GINConv, GraphNorm, Readout, SAGPooling, TopKPooling
     conv = GCNConv if args.model == "gcn" else GINConv
+    gine = args.model == "gine"
+    if gine:
+        from .edgeconv import GINEConv
+
+        def edge_conv(a, b):
+            return GINEConv(Sequential(Linear(a, b), ReLU(), Linear(b, b)), edge_dim=args.edge_dim, fused=args.fused_edge)
     attention = args.attention_readout != "none"
 
     class Net(Module):
         def __init__(self):
             super().__init__()
             dims = [args.dim] + [args.hidden] * args.num_layers
-            self.convs = ModuleList(conv(a, b) for a, b in zip(dims[:-1], dims[1:]))
+            self.convs = ModuleList((edge_conv if gine else conv)(a, b) for a, b in zip(dims[:-1], dims[1:]))
             # per-graph normalisation between every conv layer and its ReLU (its parameters start as constants: no random number)
             self.norms = ModuleList(GraphNorm(args.hidden, fused=args.fused_norm) for _ in self.convs) if args.norm == "graph" else None
             self.readout = Readout(modes, fused=args.fused_readout)
@@ -123,7 +139,7 @@ def build_model(args, modes):
         def forward(self, x, batch):
             levels = [(batch.num_nodes, int(batch.column_index.numel()))]
             for k, layer in enumerate(self.convs):
-                x = layer(x, batch)
+                x = layer(x, batch, batch.edge_attr) if gine else layer(x, batch)
                 if self.norms is not None:
                     x = self.norms[k](x, batch)
                 x = torch.relu(x)
@@ -155,7 +171,19 @@ def make_dataset(args, lo, hi, device):
     order = score.argsort()
     y = torch.empty(args.num_graphs, dtype=torch.int64)
     y[order] = torch.arange(args.num_graphs) * args.classes // args.num_graphs
-    return GraphDataset(rp, ci, gp, x.to(device), y.to(device))
+    if args.model != "gine":
+        return GraphDataset(rp, ci, gp, x.to(device), y.to(device))
+    # one row of K features per edge, each direction of an undirected edge on its own (e_ij != e_ji); the label moves with the mean
+    # of their first column, which only a layer that reads the edge features can see
+    rp_h = rp.cpu().long()
+    nnz = int(rp_h[-1])
+    edge_attr = torch.randn(nnz, args.edge_dim, generator=g)
+    edge_graph = which[torch.repeat_interleave(torch.arange(n), rp_h[1:] - rp_h[:-1])]
+    edges = torch.zeros(args.num_graphs).index_add_(0, edge_graph, torch.ones(nnz))
+    emean0 = torch.zeros(args.num_graphs).index_add_(0, edge_graph, edge_attr[:, 0]) / edges.clamp(min=1)
+    order = (score + 4.0 * emean0).argsort()
+    y[order] = torch.arange(args.num_graphs) * args.classes // args.num_graphs
+    return GraphDataset(rp, ci, gp, x.to(device), y.to(device), edge_attr=edge_attr.to(device))
 
 
 def main(argv=None, capture=None):
@@ -171,13 +199,18 @@ def main(argv=None, capture=None):
     B = min(args.batch_graphs, args.num_graphs)
     # the mini-batches are the same every epoch: cut them out once (each is a few arrays on the device)
     ids = torch.arange(args.num_graphs, device=device)
-    batches = [dataset.batch(ids[k: k + B], partSize=args.partSize, hiddenDim=args.hidden) for k in range(0, args.num_graphs, B)]
+    # (gine: a directed batch finds an edge's features in the backward through the perm of its device-built transpose; the
+    # reverse-edge map of a symmetric one is made on the host)
+    kw = {"directed": True} if args.model == "gine" else {}
+    batches = [dataset.batch(ids[k: k + B], partSize=args.partSize, hiddenDim=args.hidden, **kw) for k in range(0, args.num_graphs, B)]
     if args.verbose_mode:
         print("# %d graphs, %d nodes, %d edges, %d batches of up to %d graphs, readout %s (%s)" % (
             args.num_graphs, dataset.num_nodes, int(dataset.column_index.numel()), len(batches), B, ",".join(modes),
             "fused" if args.fused_readout else "composed"))
         if args.attention_readout != "none":
             print("# attention readout: one score per %s" % ("row" if args.attention_readout == "scalar" else "element"))
+        if args.model == "gine":
+            print("# edge features: %d per edge, GINEConv (%s)" % (args.edge_dim, "fused" if args.fused_edge else "composed"))
         if args.norm != "none":
             print("# normalisation: GraphNorm after every conv layer (%s)" % ("fused" if args.fused_norm else "composed"))
 

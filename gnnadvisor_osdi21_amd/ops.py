@@ -1921,11 +1921,16 @@ class _ScorePooling(Module):
     def _pool(self, X, score, batch):
         gate = score if self.nonlinearity is None else _GATES[self.nonlinearity](score)
         scale = gate if self.multiplier == 1.0 else self.multiplier * gate
+        carries = getattr(batch, "edge_attr", None) is not None        # edge features follow the coarsening (edgeconv.GINEConv, CFConv)
         if self.fused:
-            small, sel = batch.coarsen(score, ratio=self.ratio, k=self.k)
+            small, sel = batch.coarsen(score, ratio=self.ratio, k=self.k, want_edge_ids=carries)
+            if carries:
+                batch.carry_edge_attr(small, sel)
             perm = sel.perm.long()
             return SelectRows.apply(X, scale, sel), small, sel, gate[perm]
         small, sel = _composed_coarsen(batch, score, ratio=self.ratio, k=self.k)
+        if carries:
+            batch.carry_edge_attr(small, sel)
         perm = sel.perm.long()
         return scale[perm].unsqueeze(1) * X[perm], small, sel, gate[perm]
 
