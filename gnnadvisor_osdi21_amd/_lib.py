@@ -36,8 +36,9 @@ class Tuning(ctypes.Structure):
 _lib = None
 
 # ---- the C ABI as ctypes sees it, one table per public header of include/, in the order the headers were added:
-# HEADERS[header] = {entry: (restype, argtypes; None: never assigned)}.  load() applies every table; a new header adds its key here,
-# its name to build.PUBLIC_HEADERS and its record to tests/test_binding_table_host.py ----
+# HEADERS[header] = {entry: (restype, argtypes; None: never assigned)}.  load() applies every table.  A new header is four additions
+# and no edit of an existing test: the header in include/, its key at the end here, its name at the end of build.PUBLIC_HEADERS and
+# its record tests/abi/<header>.json (read by tests/test_binding_table_host.py, which then checks it like every other) ----
 p, i, i64, u, u64, f, s = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint, ctypes.c_uint64, ctypes.c_float, ctypes.c_char_p
 pd, pi, pi64 = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64)
 _REF_TAIL = [p, p, p, i64, i, i64, i, i, i, p]       # part_pointers, part2Node, out, num_nodes, dim, num_parts, partSize, dimWorker, warpPerBlock, stream
@@ -176,11 +177,8 @@ HEADERS["gnna_topk.h"] = {
     # d_out, ld_dout, num_out_rows, new_id, input, ld_in, scale, d_input, ld_din, d_scale, num_in_rows, dim, stream
     "gnna_gather_rows_scale_backward_ld_f32": (i, [p, i64, i64, p, p, i64, p, p, i64, p, i64, i, p]),
 }
-# ---- staged headers: written as public headers but kept in csrc/ (named in build.INTERNAL_HEADERS) until the record of the public
-# surface in tests/test_binding_table_host.py is next extended; load() applies these tables after HEADERS, under the same rule ----
-STAGED = {}
 # per-graph normalisation (GraphNorm) over the rows of every graph of a batch
-STAGED["gnna_segnorm.h"] = {
+HEADERS["gnna_segnorm.h"] = {
     # input, ld_in, num_rows, graph_pointers, num_segments, (mean, ld) (m2, ld), dim, flags, stream
     "gnna_segment_moments_ld_f32": (i, [p, i64, i64, p, i64] + [p, i64] * 2 + [i, u, p]),
     # input, ld_in, num_rows, graph_pointers, num_segments, weight, bias, alpha, eps, (out, ld) (mean, ld) (rstd, ld), dim, flags, stream
@@ -188,12 +186,8 @@ STAGED["gnna_segnorm.h"] = {
     # (d_out, ld) (input, ld) (mean, ld) (rstd, ld), weight, alpha, graph_pointers, num_segments, (d_input, ld) (seg_a, ld) (seg_b, ld), num_rows, dim, flags, stream
     "gnna_segment_norm_backward_ld_f32": (i, [p, i64] * 4 + [p, p, p, i64] + [p, i64] * 3 + [i64, i, u, p]),
 }
-# staged headers added after the record of STAGED was pinned (tests/test_segnorm_host.py pins STAGED to its one header as
-# tests/test_binding_table_host.py pins HEADERS): the same kind of table, applied by load() after STAGED under the same rule; its
-# entries move to STAGED, and from there to HEADERS, when those records are next extended
-STAGED_NEXT = {}
 # subgraph sampling: device random walks and the induced subgraph of a node list
-STAGED_NEXT["gnna_walk.h"] = {
+HEADERS["gnna_walk.h"] = {
     # row_pointers, column_index, num_nodes, nnz, roots, num_roots, walk_length, rng_seed, walks, edge_ids, stream
     "gnna_random_walk_i32": (i, [p, p, i64, i64, p, i64, i, u64, p, p, p]),
     # row_pointers, column_index, num_nodes, nnz, nodes, num_ids, partSize, sub_nodes, new_id, sub_row_pointers, sub_column_index,
@@ -201,7 +195,7 @@ STAGED_NEXT["gnna_walk.h"] = {
     "gnna_induced_subgraph_i32": (i, [p, p, i64, i64, p, i64, i] + [p] * 7 + [i64, i64, pi64, p]),
 }
 # message passing with a feature row per edge (GINE, SchNet's continuous-filter convolution)
-STAGED_NEXT["gnna_edgefeat.h"] = {
+HEADERS["gnna_edgefeat.h"] = {
     # input, ld_in, num_in_rows, edge_feat, ld_e, num_edges, row_pointers, column_index, out, ld_out, num_out_rows, dim, combine, act, flags, stream
     "gnna_agg_edge_feat_ld_f32": (i, [p, i64, i64, p, i64, i64, p, p, p, i64, i64, i, i, i, u, p]),
     # input, ld_in, num_in_rows, edge_feat, ld_e, num_edges, (dY, ld), the structure, the transposed structure, t_edge_pos, (d_input, ld)
@@ -223,7 +217,7 @@ def load() -> ctypes.CDLL:
             "(run `python -m gnnadvisor_osdi21_amd.build`). There is no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
     bound = {}
-    for header, table in list(HEADERS.items()) + list(STAGED.items()) + list(STAGED_NEXT.items()):
+    for header, table in HEADERS.items():
         for name, (restype, argtypes) in table.items():
             if bound.setdefault(name, header) != header:
                 raise ImportError(f"{name} is bound under two headers of _lib.HEADERS: {bound[name]} and {header}")
@@ -967,7 +961,7 @@ def _edge_rows(E, nnz, dim, device, what):
 
 
 def agg_edge_feat(X, E, row_pointers, column_index, num_out_rows=None, combine=EDGE_ADD, act=EDGE_ACT_NONE, out=None):
-    """gnna_agg_edge_feat_ld_f32 (csrc/gnna_edgefeat.h): out[i, f] = sum over the positions e of row i of the CSR (row_pointers,
+    """gnna_agg_edge_feat_ld_f32 (include/gnna_edgefeat.h): out[i, f] = sum over the positions e of row i of the CSR (row_pointers,
     column_index) of act(X[column_index[e], f] (+ | *) E[e, f]) -- combine EDGE_ADD | EDGE_MUL, act EDGE_ACT_NONE | EDGE_ACT_RELU --
     in one gather that streams E once.  E: [nnz, dim], edge-major in the order of column_index.  -> out [num_out_rows, dim]
     (num_out_rows: row_pointers.numel() - 1 when not given); rows without edges get 0.  `X`, `E` and a caller's `out` may be
@@ -1094,7 +1088,7 @@ def _param_arg(t, dim, device, what):
 
 
 def segment_moments(X, graph_pointers, out=None):
-    """gnna_segment_moments_ld_f32 (csrc/gnna_segnorm.h): mean[g, f] and m2[g, f] = sum (x - mean)^2 over the rows
+    """gnna_segment_moments_ld_f32 (include/gnna_segnorm.h): mean[g, f] and m2[g, f] = sum (x - mean)^2 over the rows
     [graph_pointers[g], graph_pointers[g + 1]) of X for every graph g, from one read of X; both 0 for a graph without rows.  The
     moments are centred as they are gathered (pairwise merges of (count, mean, m2)), never made from sums of x and x^2.
     -> dict(mean=, m2=), each [num_graphs, dim].  `X` may be a row-strided view (stride(1) == 1), and so may the tensors of `out`,
@@ -1709,7 +1703,7 @@ def random_walk(row_pointers, column_index, roots, walk_length, rng_seed, want_e
     [R]) on the device CSR row_pointers [N + 1] / column_index [nnz] -> (walks int32 [R, walk_length + 1], edge_ids int32
     [R, walk_length] or None).  Step t of walk w takes position lo + floor(key * d / 2^64) of its row, key = the splitmix64 key of
     u = w * walk_length + t under rng_seed; a row without positions and an edge to an id outside the graph make the walk stay
-    (edge id -1); a root outside the graph gives a row of -1 (the rule is spelled out in csrc/gnna_walk.h).  A function of
+    (edge id -1); a root outside the graph gives a row of -1 (the rule is spelled out in include/gnna_walk.h).  A function of
     (rng_seed, w, t) and the graph only.  No synchronisation, no read-back: capturable, accepted under
     set_tuning(deterministic=1)."""
     rp, ci, rt = _graph_ids(row_pointers, column_index, roots, "roots")
@@ -1731,7 +1725,7 @@ def induced_subgraph(row_pointers, column_index, nodes, partSize=None, want_edge
     """gnna_induced_subgraph_i32 (device): the subgraph that the node list `nodes` (int32 [num_ids]: duplicates welcome, -1
     skipped, any other id outside the graph an error) induces in the device CSR row_pointers [N + 1] / column_index [nnz].  The
     kept set S is the distinct ids in increasing global id; row a holds the positions of row S[a] whose column is in S, in
-    increasing position (the rule is spelled out in csrc/gnna_walk.h).  -> dict: row_pointers [n + 1], column_index [nnz']
+    increasing position (the rule is spelled out in include/gnna_walk.h).  -> dict: row_pointers [n + 1], column_index [nnz']
     (ranks in S), edge_ids [nnz'] (positions in column_index; None with want_edge_ids=False), nodes [n] (= S, global ids),
     new_id [N] (the rank of a kept node, -1 otherwise; None unless want_new_id), partPtr [P + 1] / part2Node [P] (what build_part
     gives for the new row pointers; None without partSize), num_nodes (= n).  The arrays are trimmed views of buffers sized here:

@@ -30,9 +30,9 @@ LIB_SOURCES = [os.path.join(CSRC, f) for f in ("gnna_agg.hip", "gnna_stream.hip"
                                                 "gnna_gemm.hip", "gnna_runtime.hip", "gnna_host.cpp", "gnna_reorder.cpp")]
 # the headers of include/, in the order they were added: each is a key of _lib.HEADERS (named here, not derived: no torch import)
 PUBLIC_HEADERS = ("gnna.h", "gnna_ext.h", "gnna_gatv2.h", "gnna_dotattn.h", "gnna_gat_edge.h", "gnna_stats.h", "gnna_softagg.h",
-                  "gnna_pool.h", "gnna_attnpool.h", "gnna_topk.h")
+                  "gnna_pool.h", "gnna_attnpool.h", "gnna_topk.h", "gnna_segnorm.h", "gnna_walk.h", "gnna_edgefeat.h")
 INTERNAL_HEADERS = ("gnna_internal.h", "gnna_device.h", "gnna_launch.h", "gnna_gat_common.h", "gnna_keys.h", "gnna_segments.h",
-                    "gnna_parts.h", "gnna_segnorm.h", "gnna_walk.h", "gnna_edgefeat.h")     # gnna_segnorm.h, gnna_walk.h, gnna_edgefeat.h: staged public headers (their own first paragraphs), bound through _lib.STAGED / _lib.STAGED_NEXT
+                    "gnna_parts.h")
 _PUBLIC = [os.path.join(INCLUDE, f) for f in PUBLIC_HEADERS]
 LIB_DEPS = LIB_SOURCES + [os.path.join(CSRC, f) for f in INTERNAL_HEADERS] + _PUBLIC
 EXT_SOURCES = [os.path.join(CSRC, "gnna_torch.cpp")]
@@ -112,7 +112,7 @@ def build_ext(force: bool = False, verbose: bool = False) -> str:
                "-DTORCH_EXTENSION_NAME=GNNAdvisor", "-DTORCH_API_INCLUDE_EXTENSION_H", f'-DGNNA_SOURCE_HASH="{digest}"',
                "-DUSE_ROCM", "-D__HIP_PLATFORM_AMD__",
                f"-D_GLIBCXX_USE_CXX11_ABI={int(torch._C._GLIBCXX_USE_CXX11_ABI)}",
-               "-I" + INCLUDE, "-I" + CSRC,
+               "-I" + INCLUDE,
                "-I" + os.path.join(tdir, "include"),
                "-I" + os.path.join(tdir, "include", "torch", "csrc", "api", "include"),
                "-I" + sysconfig.get_paths()["include"], "-I" + pybind11.get_include(),

@@ -41,9 +41,9 @@
 #include "gnna_pool.h"
 #include "gnna_attnpool.h"
 #include "gnna_topk.h"
-#include "gnna_segnorm.h"        // staged beside the sources (its first paragraph)
-#include "gnna_walk.h"           // staged likewise
-#include "gnna_edgefeat.h"       // staged likewise
+#include "gnna_segnorm.h"
+#include "gnna_walk.h"
+#include "gnna_edgefeat.h"
 
 #define CHECK_CUDA(x) TORCH_CHECK(x.is_cuda(), #x " must be a CUDA tensor")
 #define CHECK_CONTIGUOUS(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -524,7 +524,7 @@ torch::Tensor aggregate_softmax_backward(const torch::Tensor &input, const torch
     return out;
 }
 
-// Message passing with a feature row per edge (gnna_agg_edge_feat_ld_f32, csrc/gnna_edgefeat.h) -> out [num_out_rows, dim] with
+// Message passing with a feature row per edge (gnna_agg_edge_feat_ld_f32, include/gnna_edgefeat.h) -> out [num_out_rows, dim] with
 // num_out_rows = row_pointers.size(0) - 1: the sum over a row's positions e of act(X[column_index[e]] (+ | *) E[e]).  E: [nnz, dim],
 // edge-major.  Strided X and E as aggregate_ld.
 static void edgefeat_check(const torch::Tensor &input, const torch::Tensor &edge_feat, const torch::Tensor &row_pointers,

@@ -1,4 +1,4 @@
-"""Message passing with a feature vector per edge: the autograd op over libgnna's fused gather (csrc/gnna_edgefeat.h) and the two
+"""Message passing with a feature vector per edge: the autograd op over libgnna's fused gather (include/gnna_edgefeat.h) and the two
 layers everybody runs on molecular and material graphs.
 
 * ``EdgeFeatureSum`` -- ``Y[i] = sum over the edges e = (i <- j) of act(X[j] (+ | *) E[e])`` with E [nnz, F], one row per position of

@@ -3,11 +3,9 @@
  * ONE gather that streams the edge rows, and its two backward passes (gnna_edgefeat.hip).  It is the aggregation of GINE
  * (relu(x_j + e_ij), Hu et al.) and of SchNet's continuous-filter convolution (x_j * W(e_ij)).
  *
- * STAGED.  This header is written as a public header of libgnna.so and lives beside the sources for now: the record of the public
- * surface (ten headers in include/, ten tables in _lib.HEADERS) is pinned as a whole, and this header moves to include/ -- with
- * its table from _lib.STAGED_NEXT to _lib.HEADERS and its name to build.PUBLIC_HEADERS -- when that record is next extended.  Until
- * then it is bound through its table in _lib.STAGED_NEXT; gnna.h, the headers of include/ and GNNA_VERSION stay as they are.
- * Conventions (status codes, gnna_last_error, streams, scratch) are those of gnna.h.
+ * Entries of libgnna.so added after gnna_walk.h; gnna.h, the headers before this one and GNNA_VERSION stay as they are.
+ * Bound through this header's table in _lib.HEADERS.  Conventions (status codes, gnna_last_error,
+ * streams, scratch) are those of gnna.h.
  *
  * The function.  For position e of column_index in destination row i (row_pointers[i] <= e < row_pointers[i + 1]), with source
  * j = column_index[e] and column f:

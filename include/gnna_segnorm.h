@@ -3,11 +3,9 @@
  * normalisation): the centred moments of the rows of every graph from ONE read of the feature matrix, the normalising pass, and
  * the backward pass (gnna_segnorm.hip).
  *
- * STAGED.  This header is written as a public header of libgnna.so and lives beside the sources for now: the record of the public
- * surface (ten headers in include/, ten tables in _lib.HEADERS) is pinned as a whole, and this header moves to include/ -- with
- * its table from _lib.STAGED to _lib.HEADERS and its name to build.PUBLIC_HEADERS -- when that record is next extended.  Until
- * then it is bound through its table in _lib.STAGED; gnna.h, the headers of include/ and GNNA_VERSION stay as they are.
- * Conventions (status codes, gnna_last_error, streams, scratch) are those of gnna.h.
+ * Entries of libgnna.so added after gnna_topk.h; gnna.h, the headers before this one and GNNA_VERSION stay as they are.
+ * Bound through this header's table in _lib.HEADERS.  Conventions (status codes, gnna_last_error,
+ * streams, scratch) are those of gnna.h.
  *
  * The segments are those of gnna_pool.h: graph_pointers, int32 [num_segments + 1] in DEVICE memory, the rows of graph g are
  * [graph_pointers[g], graph_pointers[g + 1]).  The pointers must not descend; that is not checked on the device.  A segment with

@@ -3,11 +3,9 @@
  * node set, cut out on the device as a square CSR with its neighbor-group partition (gnna_walk.hip).  Together they are the
  * GraphSAINT random-walk sampler; the second alone takes the node lists of Cluster-GCN partitions and k-hop ego nets.
  *
- * STAGED.  This header is written as a public header of libgnna.so and lives beside the sources for now: the record of the public
- * surface (ten headers in include/, ten tables in _lib.HEADERS) is pinned as a whole, and this header moves to include/ -- with
- * its table from _lib.STAGED_NEXT to _lib.HEADERS and its name to build.PUBLIC_HEADERS -- when that record is next extended.  Until
- * then it is bound through its table in _lib.STAGED_NEXT; gnna.h, the headers of include/ and GNNA_VERSION stay as they are.
- * Conventions (status codes, gnna_last_error, streams, scratch) are those of gnna.h.
+ * Entries of libgnna.so added after gnna_segnorm.h; gnna.h, the headers before this one and GNNA_VERSION stay as they are.
+ * Bound through this header's table in _lib.HEADERS.  Conventions (status codes, gnna_last_error,
+ * streams, scratch) are those of gnna.h.
  *
  * The graph is a CSR in DEVICE memory: row_pointers int32 [num_nodes + 1], column_index int32 [nnz].  Neither entry trusts it: a
  * row whose pointers decrease or leave [0, nnz] has no positions, and a column id outside [0, num_nodes) is never followed and

@@ -1,4 +1,4 @@
-"""fp64 numpy restatement of csrc/gnna_edgefeat.h (forward, d_input, d_edge, each with its sum-of-|terms| scale) and the case
+"""fp64 numpy restatement of include/gnna_edgefeat.h (forward, d_input, d_edge, each with its sum-of-|terms| scale) and the case
 builders of the edge-feature tests.  The relu mask is taken from the fp32 `pre`, as the header states."""
 import numpy as np
 import torch

@@ -1,5 +1,5 @@
 """An fp32 numpy restatement of how ``csrc/gnna_segnorm.hip`` gathers the centred moments of a segment, and the fp64 reference of
-the whole function: what the accuracy contract of ``csrc/gnna_segnorm.h`` is checked against on a machine without a GPU
+the whole function: what the accuracy contract of ``include/gnna_segnorm.h`` is checked against on a machine without a GPU
 (test_segnorm_host.py), and what the GPU tests compare the kernels with (test_segnorm_gpu.py).
 
 The restatement follows the kernels' order of operations, every one rounded to fp32: a slot of a wavefront takes the rows

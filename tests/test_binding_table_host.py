@@ -1,11 +1,17 @@
 """The binding surface of ``_lib`` (no GPU), in one place: for every public header of ``include/``, the entries it declares, its
-table in ``_lib.HEADERS`` and the record below name the same entries, and restype and argtypes of every entry -- in the table and as
-``load()`` leaves them on the loaded library -- are the recorded ones.  A wrong argtype does not fail loudly -- a 64-bit count passed
-as c_int is truncated, a float passed as an integer is garbage -- so every table is pinned as a whole.  The gnna.h record was taken
-from the hand-written assignments that ``load()`` held before the table replaced them; the others were written from the
-declarations of their headers.  One letter per ctypes type (``CODE``; "d": a double by value); None: ``argtypes`` was never
-assigned.  Then the surface as a whole (the headers, disjoint names, the version) and the build lists that must name every file."""
+table in ``_lib.HEADERS`` and its record ``tests/abi/<header>.json`` name the same entries, and restype and argtypes of every entry
+-- in the table and as ``load()`` leaves them on the loaded library -- are the recorded ones.  A wrong argtype does not fail loudly
+-- a 64-bit count passed as c_int is truncated, a float passed as an integer is garbage -- so every table is pinned as a whole.  The
+gnna.h record was taken from the hand-written assignments that ``load()`` held before the table replaced them; the others were
+written from the declarations of their headers.  One letter per ctypes type (``CODE``; "d": a double by value); null: ``argtypes``
+was never assigned; spaces in a record only group the letters.  Then the surface as a whole (the headers, disjoint names, the
+version) and the build lists that must name every file.
+
+Adding a header is four additions and no edit of this file or any other existing test: the header in ``include/``, its key at the
+end of ``_lib.HEADERS``, its name at the end of ``build.PUBLIC_HEADERS`` and its record ``tests/abi/<header>.json``.  Every test
+below then covers it; one of the four without the others fails ``test_every_header_has_a_table_and_every_table_a_header``."""
 import ctypes
+import json
 import os
 import re
 
@@ -16,117 +22,21 @@ from util import declared_entries
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gnnadvisor_osdi21_amd", "csrc")
+ABI = os.path.join(ROOT, "tests", "abi")
 
 CODE = {None: "-", ctypes.c_void_p: "p", ctypes.c_int: "i", ctypes.c_int64: "l", ctypes.c_float: "f", ctypes.c_uint: "u",
         ctypes.c_uint64: "Q", ctypes.c_char_p: "s", ctypes.POINTER(ctypes.c_double): "D", ctypes.POINTER(ctypes.c_int): "I",
         ctypes.POINTER(ctypes.c_int64): "L", ctypes.POINTER(_lib.Tuning): "T", ctypes.c_double: "d"}
 
+
+def _record(file):
+    """{name: (restype, argtypes)} of a file of tests/abi = {name: [restype letter, argtype letters or null]}."""
+    with open(os.path.join(ABI, file)) as f:
+        return {name: (restype, argtypes and argtypes.replace(" ", "")) for name, (restype, argtypes) in json.load(f).items()}
+
+
 # header: {name: (restype, argtypes)}
-RECORDED = {}
-RECORDED["gnna.h"] = {
-    'gnna_agg_edge_ld_f32': ('i', 'pllppppplliliup'),
-    'gnna_agg_gcn_f32': ('i', 'pppppppliliiip'),
-    'gnna_agg_gin_f32': ('i', 'pppfpppliliiip'),
-    'gnna_agg_ld_f32': ('i', 'ipllpppfppplliliup'),
-    'gnna_agg_ld_x16': ('i', 'iipllpppfpppilliliup'),
-    'gnna_agg_rect_f32': ('i', 'iplpppfpppliliip'),
-    'gnna_agg_rect_windows_f32': ('i', 'iplpppfpppliliiiiip'),
-    'gnna_agg_reduce_ld_f32': ('i', 'ipllpppplplliliup'),
-    'gnna_agg_typed_contract_ld_f32': ('i', 'pllppppiippplliliup'),
-    'gnna_agg_typed_expand_ld_f32': ('i', 'pllppppiippplliliup'),
-    'gnna_build_id': ('s', None),
-    'gnna_build_part_device_i32': ('i', 'iplpplp'),
-    'gnna_build_part_i32': ('i', 'iplppl'),
-    'gnna_count_parts': ('l', 'ipl'),
-    'gnna_count_parts_device_i32': ('l', 'iplp'),
-    'gnna_csr_from_edges_i32': ('l', 'ppllpp'),
-    'gnna_csr_from_edges_range_i32': ('l', 'ppllllppl'),
-    'gnna_debug_untrusted_copies': ('i', 'p'),
-    'gnna_degrees_f32': ('i', 'plp'),
-    'gnna_device_cus': ('i', None),
-    'gnna_edge_softmax_backward_f32': ('i', 'pppllipp'),
-    'gnna_edge_softmax_f32': ('i', 'ppllipp'),
-    'gnna_edge_span': ('i', 'pplD'),
-    'gnna_forget_graph': ('i', 'p'),
-    'gnna_forget_plans': ('i', 'p'),
-    'gnna_gat_backward_dir_f32': ('i', 'plpppplplpppplpppplfplppliiiup'),
-    'gnna_gat_backward_f32': ('i', 'plpppplplppppfplppliiliup'),
-    'gnna_gat_backward_rect_f32': ('i', 'plpppplplpppplpppplfplpplliiiup'),
-    'gnna_gat_forward_f32': ('i', 'plppppppfplpliiliup'),
-    'gnna_gat_forward_rect_f32': ('i', 'plppppppfplplliiliup'),
-    'gnna_get_tuning': ('-', 'T'),
-    'gnna_host_threads': ('i', None),
-    'gnna_last_error': ('s', None),
-    'gnna_last_num_launches': ('i', None),
-    'gnna_last_num_phases': ('i', None),
-    'gnna_preferred_ld': ('l', 'ill'),
-    'gnna_prepare_graph': ('i', 'pppllliIiIp'),
-    'gnna_prepare_x16': ('i', 'llpip'),
-    'gnna_profile_begin': ('i', 'i'),
-    'gnna_profile_end': ('i', 'DDI'),
-    'gnna_relabel_csr_i32': ('i', 'pplppp'),
-    'gnna_relabel_edges_i32': ('i', 'pplplD'),
-    'gnna_release_graph': ('i', 'p'),
-    'gnna_reorder_community_csr_i32': ('i', 'pplp'),
-    'gnna_reorder_community_i32': ('i', 'ppllp'),
-    'gnna_reorder_rcm_i32': ('i', 'ppllp'),
-    'gnna_reverse_edges_i32': ('i', 'pplp'),
-    'gnna_row_counts_i64': ('i', 'pllp'),
-    'gnna_row_splits_i64': ('i', 'plipp'),
-    'gnna_runtime_counters': ('-', 'L'),
-    'gnna_runtime_counters_ex': ('i', 'Li'),
-    'gnna_sag_f32': ('i', 'pppppppliliiip'),
-    'gnna_sample_neighbors_i32': ('i', 'pplpliQippppppllLp'),
-    'gnna_scatter_arg_ld_f32': ('i', 'plplplplliup'),
-    'gnna_sddmm_f32': ('i', 'ppppppllilip'),
-    'gnna_sddmm_ld_f32': ('i', 'plplppppllilip'),
-    'gnna_set_graph_hints': ('i', 'pii'),
-    'gnna_set_graph_phases': ('i', 'pii'),
-    'gnna_set_tuning': ('i', 'T'),
-    'gnna_transpose_csr_i32': ('i', 'ppllpppp'),
-    'gnna_typed_coef_grad_ld_f32': ('i', 'pllpllppppppiiiliup'),
-    'gnna_version': ('i', None),
-    'gnna_xtg_f32': ('i', 'pppliip'),
-}
-# the rect entries' letters with "fQ" (attn_drop, rng_seed) after the slope's "f"
-RECORDED["gnna_ext.h"] = {
-    "gnna_gat_forward_drop_f32": ("i", "plppppppffQplplliiliup"),
-    "gnna_gat_backward_drop_f32": ("i", "plpppplplpppplpppplffQplpplliiiup"),
-}
-RECORDED["gnna_gatv2.h"] = {
-    "gnna_gatv2_forward_f32": ("i", "plplp" "pppp" "ffQ" "plp" "lliiliup"),
-    "gnna_gatv2_backward_f32": ("i", "plplp" "p" "plpl" "ppppl" "ppppl" "ffQ" "plplp" "lliiiup"),
-}
-RECORDED["gnna_dotattn.h"] = {
-    "gnna_dot_attn_forward_f32": ("i", "plplpl" "pppp" "ffQ" "plp" "lliiliup"),
-    "gnna_dot_attn_backward_f32": ("i", "plplpl" "p" "plpl" "ppppl" "ppppl" "ffQ" "plplpl" "lliiiup"),
-}
-RECORDED["gnna_gat_edge.h"] = {
-    "gnna_gat_edge_forward_f32": ("i", "plppp" "pppp" "ffQ" "plp" "llliiliup"),
-    "gnna_gat_edge_backward_f32": ("i", "plppp" "p" "plpl" "ppppl" "ppppl" "p" "ffQ" "plppp" "llliiiup"),
-    "gnna_gat_alpha_f32": ("i", "pppp" "pp" "f" "p" "llli" "p"),
-}
-RECORDED["gnna_stats.h"] = {
-    "gnna_agg_stats_ld_f32": ("i", "pll" "ppp" "pl" "pl" "plpl" "plpl" "liliup"),
-}
-RECORDED["gnna_softagg.h"] = {
-    "gnna_agg_softmax_ld_f32": ("i", "pll" "pi" "pp" "pl" "pl" "pl" "liup"),
-    "gnna_agg_softmax_backward_ld_f32": ("i", "pll" "pi" "pl" "pl" "pl" "pp" "pl" "liup"),
-}
-RECORDED["gnna_pool.h"] = {
-    "gnna_segment_pool_ld_f32": ("i", "pll" "pl" "pl" "plpl" "plpl" "iup"),
-    "gnna_segment_pool_backward_ld_f32": ("i", "pl" "plpl" "plpl" "pl" "pl" "liup"),
-}
-RECORDED["gnna_attnpool.h"] = {
-    "gnna_segment_attn_pool_ld_f32": ("i", "pll" "pli" "pl" "pl" "pl" "iup"),
-    "gnna_segment_attn_pool_backward_ld_f32": ("i", "pl" "pli" "pl" "pl" "pl" "pl" "pl" "pl" "liup"),
-}
-RECORDED["gnna_topk.h"] = {
-    "gnna_topk_keep_count": ("l", "ldl"),
-    "gnna_segment_topk_i32": ("i", "plpl" "dl" "ppli" "ppp" "ppp" "pp" "lll" "Lp"),
-    "gnna_gather_rows_scale_ld_f32": ("i", "pll" "pp" "pll" "ip"),
-    "gnna_gather_rows_scale_backward_ld_f32": ("i", "pll" "p" "plp" "plp" "lip"),
-}
+RECORDED = {file[:-len(".json")]: _record(file) for file in sorted(os.listdir(ABI)) if file.endswith(".json")}
 every_header = pytest.mark.parametrize("header", list(RECORDED))
 
 
@@ -170,12 +80,13 @@ def test_every_header_has_a_table_and_every_table_a_header():
     assert tuple(_lib.HEADERS) == build.PUBLIC_HEADERS and build.PUBLIC_HEADERS[0] == "gnna.h"          # in the order they were added
 
 
-def test_the_entry_names_are_disjoint_and_83():
-    assert [len(table) for table in _lib.HEADERS.values()] == [63, 2, 2, 2, 3, 1, 2, 2, 2, 4]
+def test_the_entry_names_are_disjoint_and_as_many_as_recorded():
+    assert [len(table) for table in _lib.HEADERS.values()][:13] == [63, 2, 2, 2, 3, 1, 2, 2, 2, 4, 3, 2, 2]     # 90 names in all
+    recorded = sum(len(record) for record in RECORDED.values())
     names = [name for table in _lib.HEADERS.values() for name in table]
-    assert len(names) == len(set(names)) == 83
+    assert len(names) == len(set(names)) == recorded
     declared = [name for header in _lib.HEADERS for name in sorted(declared_entries(_header(header)))]
-    assert len(declared) == len(set(declared)) == 83                      # no header declares an entry of another
+    assert len(declared) == len(set(declared)) == recorded                # no header declares an entry of another
 
 
 def test_load_refuses_an_entry_bound_under_two_headers(monkeypatch):

@@ -1,4 +1,4 @@
-"""Edge-feature message passing on the GPU through the C ABI (csrc/gnna_edgefeat.h, ``_lib.agg_edge_feat`` /
+"""Edge-feature message passing on the GPU through the C ABI (include/gnna_edgefeat.h, ``_lib.agg_edge_feat`` /
 ``_lib.agg_edge_feat_backward``): every case runs both combines and both activations against the fp64 restatement
 (edgefeat_ref.py) within the project's bound 1e-4 * max(1, sum |terms|) and prints the worst ratio to the bound."""
 import numpy as np

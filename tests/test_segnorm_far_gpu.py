@@ -1,4 +1,4 @@
-"""The three entries of csrc/gnna_segnorm.h with their row-strided operands 2^31 bytes, 2^32 bytes, 2^31 elements and 2^32
+"""The three entries of include/gnna_segnorm.h with their row-strided operands 2^31 bytes, 2^32 bytes, 2^31 elements and 2^32
 elements past their base pointers, built from tests/far_offsets.py as test_far_offsets_gpu.py builds its cases: node-sized operands
 (X, dY, out, d_input) are 272 rows 64 MiB apart, segment-sized ones (mean, m2, rstd, seg_a, seg_b) 18 rows 1 GiB apart, each in its
 own column window of an 18 GiB arena of this module, aligned and shifted by one float; NaN beside every input, a sentinel that must

@@ -1,7 +1,7 @@
 """gnna_segment_moments_ld_f32 / gnna_segment_norm_ld_f32 / gnna_segment_norm_backward_ld_f32 on the GPU, through the C ABI
 (_lib), against tests/segnorm_ref.py.
 
-The statistics are held to the contract of csrc/gnna_segnorm.h, per segment with u = 2^-24 max|x|: |mean - mean64| <= 4 u and
+The statistics are held to the contract of include/gnna_segnorm.h, per segment with u = 2^-24 max|x|: |mean - mean64| <= 4 u and
 |m2 / n - var64| <= 1e-5 var64 + 4 u sqrt(var64) -- the bounds the fp32 restatement is shown to keep in test_segnorm_host.py and a
 sum of x^2 is shown to miss.  rstd is held to what those two bounds allow: var_t = m2 / n + (1 - alpha)^2 mean^2 may be off by
 b = bound_var + (1 - alpha)^2 (2 |mean64| bound_mean + bound_mean^2) + 2^-22 var_t64 (the two statistics' bounds carried through the

@@ -1,69 +1,23 @@
-"""Per-graph normalisation (csrc/gnna_segnorm.h), the part that needs no GPU: the staged header, its table in ``_lib.STAGED`` and
-the record below name the same entries with the same signatures; the build lists name the header and the source; every argument
-check answers through gnna_last_error before any device work; the fp32 restatement of the moments pass (segnorm_ref.py) stays
-inside the accuracy contract of the header, which a sum of x^2 does not; and the driver's flags."""
+"""Per-graph normalisation (include/gnna_segnorm.h), the part that needs no GPU: every argument check answers through
+gnna_last_error before any device work; the fp32 restatement of the moments pass (segnorm_ref.py) stays inside the accuracy contract
+of the header, which a sum of x^2 does not; and the driver's flags.  The header's entries, table and signatures are checked with
+every other header's in test_binding_table_host.py."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 
 import segnorm_ref
-from gnnadvisor_osdi21_amd import _lib, build, graph_main
-from util import declared_entries
+from gnnadvisor_osdi21_amd import _lib, graph_main
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gnnadvisor_osdi21_amd", "csrc")
 HEADER = "gnna_segnorm.h"
 
-CODE = {None: "-", ctypes.c_void_p: "p", ctypes.c_int: "i", ctypes.c_int64: "l", ctypes.c_float: "f", ctypes.c_uint: "u"}
-RECORDED = {
-    "gnna_segment_moments_ld_f32": ("i", "pll" "pl" "pl" "pl" "iup"),
-    "gnna_segment_norm_ld_f32": ("i", "pll" "pl" "ppp" "f" "pl" "pl" "pl" "iup"),
-    "gnna_segment_norm_backward_ld_f32": ("i", "pl" "pl" "pl" "pl" "pp" "pl" "pl" "pl" "pl" "liup"),
-}
 
-
-def _codes(restype, argtypes):
-    return CODE[restype], "".join(CODE[t] for t in argtypes)
-
-
-# ---- the staged header and its table ----
-
-def test_header_table_and_record_name_the_same_entries():
-    text = open(os.path.join(CSRC, HEADER)).read()
-    assert declared_entries(text) == set(_lib.STAGED[HEADER]) == set(RECORDED) and list(_lib.STAGED) == [HEADER]
-    assert '#include "gnna.h"' in text and 'extern "C"' in text and "#define GNNA_VERSION" not in text
-    first_paragraph = text.split("\n *\n")[1]
-    assert "STAGED" in first_paragraph and "include/" in first_paragraph
-
-
-def test_the_table_is_the_record_and_load_leaves_it_on_the_library():
-    assert {name: _codes(*sig) for name, sig in _lib.STAGED[HEADER].items()} == RECORDED
-    lib = _lib.load()
-    assert {name: _codes(getattr(lib, name).restype, getattr(lib, name).argtypes) for name in RECORDED} == RECORDED
-
-
-def test_the_staged_names_are_disjoint_from_the_public_ones():
-    public = {name for table in _lib.HEADERS.values() for name in table}
-    assert not public & set(RECORDED) and HEADER not in _lib.HEADERS and HEADER not in build.PUBLIC_HEADERS
-    assert not os.path.exists(os.path.join(ROOT, "include", HEADER))
-
-
-def test_load_refuses_a_staged_entry_that_a_public_header_binds(monkeypatch):
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setitem(_lib.STAGED, "gnna_twice.h", {"gnna_version": _lib.HEADERS["gnna.h"]["gnna_version"]})
-    with pytest.raises(ImportError, match="gnna_version is bound under two headers of _lib.HEADERS: gnna.h and gnna_twice.h"):
-        _lib.load()
-
-
-def test_the_build_lists_name_the_header_and_the_source():
-    makefile = open(os.path.join(CSRC, "Makefile")).read()
-    listed = lambda name: re.search(r"^%s\s*=(.*)$" % name, makefile, re.M).group(1).split()
-    assert HEADER in build.INTERNAL_HEADERS and HEADER in listed("HEADERS")
-    assert os.path.join(CSRC, "gnna_segnorm.hip") in build.LIB_SOURCES and "gnna_segnorm.hip" in listed("SOURCES")
-    assert os.path.join(CSRC, HEADER) in build.LIB_DEPS            # so source_hash covers it
+def test_the_header_is_extern_c_and_the_module_includes_it():
+    assert 'extern "C"' in open(os.path.join(ROOT, "include", HEADER)).read()
     assert '#include "gnna_segnorm.h"' in open(os.path.join(CSRC, "gnna_torch.cpp")).read()
 
 

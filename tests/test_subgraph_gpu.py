@@ -1,5 +1,5 @@
 """gnna_induced_subgraph_i32 on the GPU, exact against the numpy restatement of the subgraph rule (tests/walk_ref.py), and the
-agreement of the ctypes binding and the GNNAdvisor module for both entries of csrc/gnna_walk.h."""
+agreement of the ctypes binding and the GNNAdvisor module for both entries of include/gnna_walk.h."""
 import ctypes
 import functools
 

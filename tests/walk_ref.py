@@ -1,4 +1,4 @@
-"""numpy restatements of the two rules of csrc/gnna_walk.h -- the walk rule of gnna_random_walk_i32 and the subgraph rule of
+"""numpy restatements of the two rules of include/gnna_walk.h -- the walk rule of gnna_random_walk_i32 and the subgraph rule of
 gnna_induced_subgraph_i32 -- and the inputs their tests share (checker side only).  Nothing here reads the library."""
 import functools
 

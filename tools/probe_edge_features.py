@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times edge-feature message passing -- edgeconv.EdgeFeatureSum forward and forward + backward, fused against the same function
-composed from torch ops, in GINE's mode (add, relu) and CFConv's (mul, none) -- and each kernel pass of csrc/gnna_edgefeat.h
+composed from torch ops, in GINE's mode (add, relu) and CFConv's (mul, none) -- and each kernel pass of include/gnna_edgefeat.h
 against torch.clone of the bytes the pass must move; then graph_main.py --model gine epochs, fused and composed.
 
     python tools/probe_edge_features.py [--shapes small,amazon] [--dims 64,128] [--reps 7] [--driver 1] [--kernels_only 0]
