@@ -3,8 +3,8 @@ as it stands, plus ``graph_pointers`` (int32 [G + 1]: the rows of graph g are [g
 the readout (ops.Readout, ops.global_*_pool; libgnna gnna_segment_pool_ld_f32) reduces over.
 
 * ``GraphBatch`` -- one batch.  It carries the attributes a layer reads from a graph bundle (``row_pointers column_index degrees
-  partPtr part2Node partSize dimWorker warpPerBlock directed``, ``set_input() / set_hidden()``, ``transposed()``), so every layer
-  takes it where it takes a ``decider.inputProperty``.
+  partPtr part2Node partSize dimWorker warpPerBlock directed``, ``set_input() / set_hidden()``) and is a
+  ``structure.GraphStructure``, so every layer takes it where it takes a ``decider.inputProperty``.
 * ``GraphBatch.from_graphs`` collates a list of ``graph.CSRGraph`` on the host.
 * ``GraphDataset`` keeps many graphs as one concatenated CSR on the device; ``GraphDataset.batch(ids)`` cuts the batch of the chosen
   graphs out of it with torch arithmetic on the device (one read-back: the batch's sizes).
@@ -16,8 +16,9 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .decider import WAVES_PER_BLOCK, inputProperty, lanes_per_row
+from .decider import WAVES_PER_BLOCK, lanes_per_row
 from .graph import degrees_from_rowptr
+from .structure import GraphStructure
 
 
 class TopKSelection(object):
@@ -29,7 +30,7 @@ class TopKSelection(object):
         self.perm, self.new_id, self.edge_ids, self.num_nodes = perm, new_id, edge_ids, int(num_nodes)
 
 
-class GraphBatch(object):
+class GraphBatch(GraphStructure):
     """A block-diagonal CSR of ``num_graphs`` graphs and ``graph_pointers``.  ``batch`` (int64 [N]: the graph of every row) and
     ``inv_counts`` (float32 [G]: 1 / max(rows of the graph, 1)) are built at their first use; the fused readout needs neither."""
 
@@ -71,14 +72,6 @@ class GraphBatch(object):
 
     def set_hidden(self):
         return self
-
-    _edge_arrays = inputProperty._edge_arrays
-    reverse_edges = inputProperty.reverse_edges
-    require_symmetric = inputProperty.require_symmetric
-    transposed = inputProperty.transposed
-    backward_graph = inputProperty.backward_graph
-    edge_rows = inputProperty.edge_rows
-    inv_row_counts = inputProperty.inv_row_counts
 
     # ---- the batch ------------------------------------------------------------------------------------------------------------
     @property

@@ -16,7 +16,8 @@ from torch.autograd import Function
 from torch.nn import Linear, Module, Parameter
 
 from . import _lib
-from .ops import GNNA, _block_features, _is_block, _is_directed, _laid_out
+from .ops import GNNA, _block_features, _is_block, _laid_out
+from .structure import backward_structure
 
 _COMBINE = {"add": _lib.EDGE_ADD, "mul": _lib.EDGE_MUL}
 _ACT = {"none": _lib.EDGE_ACT_NONE, "relu": _lib.EDGE_ACT_RELU}
@@ -79,13 +80,8 @@ class EdgeFeatureSum(Function):
             return None, None, None, None, None
         transposed = (None, None, None)
         if want_dx:
-            if _is_block(info) or _is_directed(info):
-                t = info.transposed()
-                transposed = (t.row_pointers, t.column_index, t.perm)
-            else:
-                from .decider import inputProperty
-                inputProperty.require_symmetric(info)
-                transposed = (info.row_pointers, info.column_index, info.reverse_edges())
+            t, edge_pos = backward_structure(info, require_symmetric=True, edge_pos=True)
+            transposed = (t.row_pointers, t.column_index, edge_pos)
         dX, dE = GNNA.aggregate_edge_feat_backward(X, E, _laid_out(dY), info.row_pointers, info.column_index, *transposed,
                                                    ctx.combine, ctx.act, bool(want_dx), bool(want_de))
         return dX, dE, None, None, None

@@ -236,6 +236,7 @@ def main(argv=None, capture=None):
     from .decider import inputProperty
     from .loader import custom_dataset
     from .ops import GATConv, GATv2Conv, GCNConv, GENConv, GINConv, PNAConv, RGCNConv, SAGEConv, TransformerConv
+    from .structure import backward_structure
     GNNA = load_extension()
 
     # ---- loading data --------------------------------------------------------------------
@@ -305,9 +306,9 @@ def main(argv=None, capture=None):
     if inputInfo.directed:
         # the backward passes' structure: built (and prepared like the forward graph) here, never inside a captured epoch
         start = time.perf_counter()
-        t_graph = inputInfo.transposed()
-        if attention and not flag(args.fused_attention):
-            t_graph.perm                  # (edge-valued backward: the weights are read through the permutation)
+        # (composed attention is edge-valued: its backward reads the weights through the position map, so that is built too)
+        edge_valued = attention and not flag(args.fused_attention)
+        t_graph = backward_structure(inputInfo, edge_pos=True)[0] if edge_valued else backward_structure(inputInfo)
         torch.cuda.synchronize()
         if verbose_mode:
             print("# Build transposed graph on the device (s): {:.3f}".format(time.perf_counter() - start))
@@ -326,10 +327,10 @@ def main(argv=None, capture=None):
         # synthetic edge features in the order of the column_index the Decider has settled on (a renumbering is behind us)
         gen = torch.Generator(device='cpu').manual_seed(0xED6E)
         edge_attr = torch.randn(inputInfo.column_index.numel(), args.edge_dim, generator=gen).to(device)
-        if inputInfo.directed:
-            inputInfo.transposed().perm           # (the source-side pass reads the edge term through the permutation)
-        elif flag(args.fused_attention) and args.fanout is None:
-            inputInfo.reverse_edges()             # (... through the reverse-edge map: built here, not inside the first step)
+        if inputInfo.directed or (flag(args.fused_attention) and args.fanout is None):
+            # the source-side pass reads the edge term through the position map of the backward structure (the permutation, or
+            # the reverse-edge map, which also settles the symmetry question): built here, not inside the first step
+            backward_structure(inputInfo, edge_pos=True)
     if capture is not None:
         capture.update(dataset=dataset, inputInfo=inputInfo, args=args, edge_attr=edge_attr)
 

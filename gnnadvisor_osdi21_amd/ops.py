@@ -16,6 +16,7 @@ from torch.nn import Module, Parameter
 
 from . import _lib, load_extension
 from .sampling import SampledBlock
+from .structure import backward_structure
 
 GNNA = load_extension()
 
@@ -48,29 +49,13 @@ def _packed(t):
     return t if t is None else t.contiguous()
 
 
-def _is_directed(info):
-    return bool(getattr(info, "directed", False))
-
-
-def _remember_graph(ctx, info):
-    """Forward: the graph the layer ran on, and the profile its backward pass may have to ask for the transposed one."""
-    ctx.graph, ctx.info, ctx.directed = _graph_args(info), info, _is_directed(info)
-
-
-def _backward_graph(ctx):
-    """Backward: (row_pointers, column_index, degrees, partPtr, part2Node) to aggregate the gradient over.  A sum over the
-    edges i <- j sends row i's gradient to row j, i.e. it aggregates over A^T: the transposed structure of a directed graph
-    (decider.inputProperty.transposed, built on the device and cached), the forward graph itself when the structure is
-    symmetric (``directed`` false: the reference's assumption and this package's default)."""
-    return _graph_args(ctx.info.transposed()) if ctx.directed else ctx.graph
-
-
 # ---- sampled blocks (sampling.SampledBlock): rectangular, [num_src, F] -> [num_dst, F] ------------------------------------
 # The GraphSAGE operators take a block where they take an inputProperty.  Forward and backward go through the rectangular
 # entries of libgnna (gnna_agg_ld_f32, gnna_agg_reduce_ld_f32, gnna_scatter_arg_ld_f32); the backward of a sum aggregates dY over
-# block.transposed(), which is only built when the layer's input needs a gradient (the first layer's does not).
+# the transposed block, which is only built when the layer's input needs a gradient (the first layer's does not).
 # The fused attention (GATAttention, GATConv(fused=True)) takes a block too, through gnna_gat_forward_rect_f32 /
-# gnna_gat_backward_rect_f32; its backward always runs on block.transposed() (the gradient of the layer's own weight needs dH).
+# gnna_gat_backward_rect_f32; its backward always runs on the transposed block (the gradient of the layer's own weight needs dH).
+# Which structure a backward walks is structure.backward_structure's decision for every operator here, blocks included.
 
 def _is_block(info):
     return isinstance(info, SampledBlock)
@@ -96,12 +81,14 @@ def _block_sum(X, graph, num_out_rows):
     return _lib.agg_ld(_lib.MODE_SAG, X, graph.column_index, graph.partPtr, graph.part2Node, num_out_rows, graph.partSize)
 
 
-def _block_sum_backward(ctx, dY):
-    """A^T dY over the transposed block, or nothing when the layer's input needs no gradient."""
+def _sum_backward(ctx, dY):
+    """A^T dY of a float32 neighbor sum over ``backward_structure(ctx.info)``; a block's through the rectangular entry, and not
+    at all when its input needs no gradient (the first layer's: no transposed block is built for it)."""
+    if ctx.block is None:
+        return GNNA.SAG(_packed(dY), *_graph_args(backward_structure(ctx.info)), *ctx.knobs)
     if not ctx.needs_input_grad[0]:
         return None
-    block = ctx.block
-    return _block_sum(_laid_out(dY), block.transposed(), block.num_src)
+    return _block_sum(_laid_out(dY), backward_structure(ctx.info), ctx.block.num_src)
 
 
 # ---- features stored in bfloat16 / float16 (libgnna gnna_agg_ld_x16: fp32 accumulation, one rounding of the result) ------
@@ -134,16 +121,16 @@ class GNNAFunction_X16(Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda")
     def forward(ctx, X, weight, inputInfo, mode, epsilon, update_first, relu, dtype):
-        _remember_graph(ctx, inputInfo)
-        ctx.partSize = inputInfo.partSize
+        ctx.info, ctx.partSize = inputInfo, inputInfo.partSize
+        graph = _graph_args(inputInfo)
         ctx.mode, ctx.eps, ctx.update_first, ctx.relu, ctx.dtype = int(mode), float(epsilon), bool(update_first), bool(relu), dtype
         ctx.in_dtypes = (X.dtype, weight.dtype)
         Xh, Wh = X.to(dtype), weight.to(dtype)
         if ctx.update_first:
-            Y = _aggregate_x16(ctx.mode, torch.mm(Xh, Wh), ctx.graph, ctx.partSize, ctx.eps, ctx.relu)
+            Y = _aggregate_x16(ctx.mode, torch.mm(Xh, Wh), graph, ctx.partSize, ctx.eps, ctx.relu)
             ctx.save_for_backward(Xh, Wh, *((Y,) if ctx.relu else ()))
         else:
-            T = _aggregate_x16(ctx.mode, Xh, ctx.graph, ctx.partSize, ctx.eps)
+            T = _aggregate_x16(ctx.mode, Xh, graph, ctx.partSize, ctx.eps)
             Y = torch.mm(T, Wh)
             if ctx.relu:
                 Y = torch.relu(Y)
@@ -158,7 +145,7 @@ class GNNAFunction_X16(Function):
         if ctx.relu:
             dY = dY * (ctx.saved_tensors[2] > 0)
         d_input = None
-        bgraph = _backward_graph(ctx)
+        bgraph = _graph_args(backward_structure(ctx.info))
         if ctx.update_first:
             G = _aggregate_x16(ctx.mode, dY, bgraph, ctx.partSize, ctx.eps)
             d_weight = torch.mm(saved.t(), G)
@@ -179,23 +166,19 @@ class ScatterAndGather(Function):
 
     @staticmethod
     def forward(ctx, X, inputInfo):
-        ctx.block = inputInfo if _is_block(inputInfo) else None
+        ctx.info, ctx.block = inputInfo, inputInfo if _is_block(inputInfo) else None
         if ctx.block is not None:
             return _block_sum(_block_features(X, inputInfo, "ScatterAndGather"), inputInfo, inputInfo.num_dst)
-        _remember_graph(ctx, inputInfo)
         ctx.knobs = _knobs(inputInfo)
         if X.dtype in _X16:
-            return _aggregate_x16(0, X, ctx.graph, ctx.knobs[0])
-        return GNNA.SAG(_packed(X), *ctx.graph, *ctx.knobs)
+            return _aggregate_x16(0, X, _graph_args(inputInfo), ctx.knobs[0])
+        return GNNA.SAG(_packed(X), *_graph_args(inputInfo), *ctx.knobs)
 
     @staticmethod
     def backward(ctx, d_output):
-        if ctx.block is not None:
-            return _block_sum_backward(ctx, d_output), None
-        bgraph = _backward_graph(ctx)
-        if d_output.dtype in _X16:
-            return _aggregate_x16(0, d_output, bgraph, ctx.knobs[0]), None
-        return GNNA.SAG(_packed(d_output), *bgraph, *ctx.knobs), None
+        if ctx.block is None and d_output.dtype in _X16:
+            return _aggregate_x16(0, d_output, _graph_args(backward_structure(ctx.info)), ctx.knobs[0]), None
+        return _sum_backward(ctx, d_output), None
 
 
 class GNNAFunction(Function):
@@ -205,9 +188,8 @@ class GNNAFunction(Function):
     def forward(ctx, X, weight, inputInfo):
         X, weight = _packed(X), _packed(weight)
         ctx.save_for_backward(X, weight)
-        _remember_graph(ctx, inputInfo)
-        ctx.knobs = _knobs(inputInfo)
-        return GNNA.forward(X, weight, *ctx.graph, *ctx.knobs)[0]
+        ctx.info, ctx.knobs = inputInfo, _knobs(inputInfo)
+        return GNNA.forward(X, weight, *_graph_args(inputInfo), *ctx.knobs)[0]
 
     @staticmethod
     def backward(ctx, d_output):
@@ -218,7 +200,7 @@ class GNNAFunction(Function):
 def _gcn_backward(ctx, d_output, X, weight):
     """(d_input, d_weight, None) of a GCN layer from the gradient of its (pre-activation) output: D A^T D dY, then the two
     dense products.  Whatever layout the three arrive in (d_output may be a product that kept a column-major operand's)."""
-    bgraph = _backward_graph(ctx)
+    bgraph = _graph_args(backward_structure(ctx.info))
     d_output, X, weight = _packed(d_output), _packed(X), _packed(weight)
     if not ctx.needs_input_grad[0]:
         # first layer: the features need no gradient (the reference computes and drops d_input)
@@ -234,9 +216,8 @@ class GNNAFunction_ReLU(Function):
 
     @staticmethod
     def forward(ctx, X, weight, inputInfo):
-        _remember_graph(ctx, inputInfo)
-        rp, ci, deg, pp, p2n = ctx.graph
-        ctx.knobs = _knobs(inputInfo)
+        rp, ci, deg, pp, p2n = _graph_args(inputInfo)
+        ctx.info, ctx.knobs = inputInfo, _knobs(inputInfo)
         Y = GNNA.aggregate_ld(1, torch.mm(X, weight), ci, deg, 1.0, pp, p2n, inputInfo.partSize, None, False, True)
         ctx.save_for_backward(X, weight, Y)
         return Y
@@ -253,9 +234,8 @@ class GNNAFunction_GIN(Function):
 
     @staticmethod
     def forward(ctx, X, weight, inputInfo, eplison):
-        _remember_graph(ctx, inputInfo)
-        rp, ci, _deg, pp, p2n = ctx.graph
-        ctx.knobs, ctx.eplison = _knobs(inputInfo), eplison
+        rp, ci, _deg, pp, p2n = _graph_args(inputInfo)
+        ctx.info, ctx.knobs, ctx.eplison = inputInfo, _knobs(inputInfo), eplison
         weight = _packed(weight)
         X_prime, X_agg = GNNA.forward_gin(_packed(X), weight, rp, ci, eplison, pp, p2n, *ctx.knobs)
         ctx.save_for_backward(X_agg, weight)
@@ -268,7 +248,7 @@ class GNNAFunction_GIN(Function):
             # first layer: d_weight = T^T dY needs no aggregation at all; the reference aggregates
             # dY W^T at the input width (F = 602 on Reddit) and drops the result
             return None, GNNA.xtg(X_agg, _packed(d_output)), None, None
-        rp, ci, _deg, pp, p2n = _backward_graph(ctx)
+        rp, ci, _deg, pp, p2n = _graph_args(backward_structure(ctx.info))
         d_input, d_weight = GNNA.backward_gin(_packed(d_output), X_agg, weight, rp, ci,
                                               ctx.eplison, pp, p2n, *ctx.knobs)
         return d_input, d_weight, None, None
@@ -301,9 +281,8 @@ class GNNAFunction_GIN_UpdateFirst(Function):
 
     @staticmethod
     def forward(ctx, X, weight, inputInfo, eplison, relu=False):
-        _remember_graph(ctx, inputInfo)
-        rp, ci, _deg, pp, p2n = ctx.graph
-        ctx.knobs, ctx.eplison = _knobs(inputInfo), eplison
+        rp, ci, _deg, pp, p2n = _graph_args(inputInfo)
+        ctx.info, ctx.knobs, ctx.eplison = inputInfo, _knobs(inputInfo), eplison
         ctx.relu = bool(relu)
         with torch.no_grad():
             XW = _mm_for_gather(X, weight, ci)
@@ -317,7 +296,7 @@ class GNNAFunction_GIN_UpdateFirst(Function):
     @staticmethod
     def backward(ctx, d_output):
         X, weight = ctx.saved_tensors[:2]
-        rp, ci, _deg, pp, p2n = _backward_graph(ctx)
+        rp, ci, _deg, pp, p2n = _graph_args(backward_structure(ctx.info))
         if ctx.relu:
             d_output = d_output * (ctx.saved_tensors[2] > 0)
         G = GNNA.aggregate_gin(_packed(d_output), rp, ci, ctx.eplison, pp, p2n, *ctx.knobs)   # eps A^T dY
@@ -441,25 +420,22 @@ class NeighborMean(Function):
 
     @staticmethod
     def forward(ctx, X, inputInfo):
-        ctx.block = inputInfo if _is_block(inputInfo) else None
+        ctx.info, ctx.block = inputInfo, inputInfo if _is_block(inputInfo) else None
         if ctx.block is not None:
             inv = inputInfo.inv_row_counts()
             ctx.save_for_backward(inv)
             return _block_sum(_block_features(X, inputInfo, "NeighborMean"), inputInfo, inputInfo.num_dst).mul_(inv.unsqueeze(1))
         if X.dtype != torch.float32:
             raise TypeError(f"NeighborMean: float32 features only (got {X.dtype})")
-        _remember_graph(ctx, inputInfo)
         ctx.knobs = _knobs(inputInfo)
         inv = inputInfo.inv_row_counts()
         ctx.save_for_backward(inv)
-        return GNNA.SAG(_packed(X), *ctx.graph, *ctx.knobs).mul_(inv.unsqueeze(1))
+        return GNNA.SAG(_packed(X), *_graph_args(inputInfo), *ctx.knobs).mul_(inv.unsqueeze(1))
 
     @staticmethod
     def backward(ctx, dY):
         inv, = ctx.saved_tensors
-        if ctx.block is not None:
-            return _block_sum_backward(ctx, dY * inv.unsqueeze(1)), None
-        return GNNA.SAG(_packed(dY * inv.unsqueeze(1)), *_backward_graph(ctx), *ctx.knobs), None
+        return _sum_backward(ctx, dY * inv.unsqueeze(1)), None
 
 
 class SAGEConv(Module):
@@ -544,12 +520,11 @@ class NeighborStats(Function):
             raise TypeError("NeighborStats computes in float32 only: 16-bit features and torch.autocast are not supported "
                             f"(got {X.dtype}{', inside torch.autocast' if X.dtype == torch.float32 else ''})")
         ctx.set_materialize_grads(False)
-        ctx.block = inputInfo if _is_block(inputInfo) else None
+        ctx.info, ctx.block = inputInfo, inputInfo if _is_block(inputInfo) else None
         if ctx.block is not None:
             X = _block_features(X, inputInfo, "NeighborStats")
             n_out = inputInfo.num_dst
         else:
-            _remember_graph(ctx, inputInfo)
             ctx.knobs = _knobs(inputInfo)
             X = _laid_out(X)
             n_out = X.shape[0]
@@ -584,10 +559,7 @@ class NeighborStats(Function):
                 torch.mul(b, mean, out=ab[:, :F]).neg_()
                 if g_mean is not None:
                     ab[:, :F].addcmul_(g_mean, inv)
-            if ctx.block is not None:
-                T = _block_sum(_laid_out(ab), ctx.block.transposed(), ctx.block.num_src)
-            else:
-                T = GNNA.SAG(_packed(ab), *_backward_graph(ctx), *ctx.knobs)
+            T = _sum_backward(ctx, ab)
             dX = T if g_std is None else torch.addcmul(T[:, :F], X, T[:, F:])
         for g, arg in ((g_max, amx), (g_min, amn)):
             if g is not None:
@@ -700,12 +672,8 @@ class NeighborSoftmax(Function):
             raise TypeError("NeighborSoftmax computes in float32 only: 16-bit features and torch.autocast are not supported "
                             f"(got {X.dtype}{', inside torch.autocast' if X.dtype == torch.float32 else ''})")
         ctx.set_materialize_grads(False)
-        ctx.block = inputInfo if _is_block(inputInfo) else None
-        if ctx.block is not None:
-            X = _block_features(X, inputInfo, "NeighborSoftmax")
-        else:
-            _remember_graph(ctx, inputInfo)
-            X = _laid_out(X)
+        ctx.info = inputInfo
+        X = _block_features(X, inputInfo, "NeighborSoftmax") if _is_block(inputInfo) else _laid_out(X)
         t = _temp_vector(temp, X.shape[1], X.device, "NeighborSoftmax")
         ctx.temp_shape = temp.shape
         Y, lse, sq = GNNA.aggregate_softmax(X, t, inputInfo.row_pointers, inputInfo.column_index, bool(ctx.needs_input_grad[1]))
@@ -720,12 +688,8 @@ class NeighborSoftmax(Function):
         dX = dt = None
         if ctx.needs_input_grad[0]:
             dY = _laid_out(dY)
-            if ctx.block is not None:
-                bgraph = ctx.block.transposed()
-                rp, ci = bgraph.row_pointers, bgraph.column_index
-            else:
-                rp, ci = _backward_graph(ctx)[:2]
-            dX = GNNA.aggregate_softmax_backward(X, t, lse, Y, dY, rp, ci)
+            bgraph = backward_structure(ctx.info)
+            dX = GNNA.aggregate_softmax_backward(X, t, lse, Y, dY, bgraph.row_pointers, bgraph.column_index)
         if ctx.needs_input_grad[1]:
             per_channel = torch.addcmul(sq, Y, Y, value=-1.0).mul_(dY).sum(0)
             dt = (per_channel if t.numel() > 1 else per_channel.sum()).reshape(ctx.temp_shape)
@@ -968,11 +932,8 @@ class EdgeWeightedAggregate(Function):
         heads, F = wh.shape[0], X.shape[1] // wh.shape[0]
         dX = dw = None
         if ctx.needs_input_grad[0]:
-            if _is_directed(info):
-                t = info.transposed()
-                dX = _edge_aggregate(dY, wh.index_select(1, t.perm).contiguous(), t)
-            else:
-                dX = _edge_aggregate(dY, wh.index_select(1, info.reverse_edges()).contiguous(), info)
+            bgraph, edge_pos = backward_structure(info, edge_pos=True)
+            dX = _edge_aggregate(dY, wh.index_select(1, edge_pos).contiguous(), bgraph)
         if ctx.needs_input_grad[1]:
             dw = torch.stack([_sddmm_at_least_4(dY[:, h * F:(h + 1) * F], X[:, h * F:(h + 1) * F], info.column_index,
                                                 info.partPtr, info.part2Node, info.partSize) for h in range(heads)])
@@ -1007,6 +968,38 @@ class EdgeSoftmax(Function):
         return GNNA.edge_softmax_backward(p, _packed(dp), rp), None
 
 
+# ---- the frame the fused attention Functions share ------------------------------------------------------------------------
+
+def _drop_args(who, attn_drop, rng_seed):
+    """(attn_drop as a float in [0, 1), rng_seed mod 2^64 -- the key arithmetic is mod 2^64) of the Function `who`."""
+    attn_drop, rng_seed = float(attn_drop), int(rng_seed) & (2 ** 64 - 1)
+    if not 0.0 <= attn_drop < 1.0:
+        raise ValueError(f"{who}: attn_drop must be in [0, 1) (got {attn_drop})")
+    return attn_drop, rng_seed
+
+
+def _grads(ctx, grads=()):
+    """What a backward returns: `grads` for the forward's leading tensor arguments, each kept only where ``needs_input_grad``
+    asks for it, then None for every other argument (inputInfo, negative_slope, ... whichever the call gave)."""
+    need = ctx.needs_input_grad
+    return tuple(g if n else None for g, n in zip(grads, need)) + (None,) * (len(need) - len(grads))
+
+
+def _transposed_args(info, t):
+    """The `transposed` argument of an attention backward entry: None when the backward walks the forward structure itself (a
+    symmetric graph: the binding then passes its structure as the transposed one)."""
+    return None if t is info else [t.row_pointers, t.column_index, t.partPtr, t.part2Node]
+
+
+def _step_seed(module, rng_seed):
+    """The seed of this forward of a layer with attention dropout: the caller's, else 63 bits from torch's CPU default generator
+    (a CPU tensor: no device synchronisation); kept as ``module.last_rng_seed``."""
+    if rng_seed is None:
+        rng_seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
+    module.last_rng_seed = int(rng_seed)
+    return module.last_rng_seed
+
+
 class GATAttention(Function):
     """The attention of a GAT layer in one fused call per direction (libgnna gnna_gat_forward_f32 / gnna_gat_backward_f32):
     ``GATAttention.apply(H, el, er, inputInfo, negative_slope) -> Y`` with H [N, heads * F], el / er [N, heads] and
@@ -1036,9 +1029,7 @@ class GATAttention(Function):
     @staticmethod
     def forward(ctx, H, el, er, inputInfo, negative_slope, attn_drop=0.0, rng_seed=0):
         info = inputInfo
-        attn_drop, rng_seed = float(attn_drop), int(rng_seed) & (2 ** 64 - 1)      # (the key arithmetic is mod 2^64)
-        if not 0.0 <= attn_drop < 1.0:
-            raise ValueError(f"GATAttention: attn_drop must be in [0, 1) (got {attn_drop})")
+        attn_drop, rng_seed = _drop_args("GATAttention", attn_drop, rng_seed)
         if _is_block(info):
             H = _block_features(H, info, "GATAttention")
             if er.dim() != 2 or er.shape[0] != info.num_src or el.dim() != 2 or el.shape[0] != info.num_dst or \
@@ -1061,23 +1052,13 @@ class GATAttention(Function):
     def backward(ctx, dY):
         H, el, er, lse, Y = ctx.saved_tensors
         info = ctx.info
-        rest = (None,) * (len(ctx.needs_input_grad) - 3)       # inputInfo, negative_slope (, attn_drop (, rng_seed))
         if not any(ctx.needs_input_grad[:3]):
-            return (None, None, None) + rest
-        transposed = None
-        if _is_block(info) or _is_directed(info):      # (a block is never symmetric: require_symmetric is not for it)
-            t = info.transposed()
-            transposed = [t.row_pointers, t.column_index, t.partPtr, t.part2Node]
-        else:
-            from .decider import inputProperty
-            inputProperty.require_symmetric(info)    # raises on a structure that is not symmetric (answer cached per column_index)
+            return _grads(ctx)
+        transposed = _transposed_args(info, backward_structure(info, require_symmetric=True))
         graph = (info.row_pointers, info.column_index, info.partPtr, info.part2Node, info.partSize, ctx.negative_slope)
-        if ctx.attn_drop > 0.0:     # (a symmetric graph: the binding passes its structure as the transposed one)
-            dH, d_el, d_er = GNNA.gat_backward_drop(H, el, er, lse, Y, dY, *graph, ctx.attn_drop, ctx.rng_seed, transposed)
-        else:
-            dH, d_el, d_er = GNNA.gat_backward(H, el, er, lse, Y, dY, *graph, transposed)
-        need = ctx.needs_input_grad
-        return (dH if need[0] else None, d_el if need[1] else None, d_er if need[2] else None) + rest
+        if ctx.attn_drop > 0.0:
+            return _grads(ctx, GNNA.gat_backward_drop(H, el, er, lse, Y, dY, *graph, ctx.attn_drop, ctx.rng_seed, transposed))
+        return _grads(ctx, GNNA.gat_backward(H, el, er, lse, Y, dY, *graph, transposed))
 
 
 class GATEdgeAttention(Function):
@@ -1095,9 +1076,7 @@ class GATEdgeAttention(Function):
     @staticmethod
     def forward(ctx, H, el, er, ee, inputInfo, negative_slope, attn_drop=0.0, rng_seed=0):
         info = inputInfo
-        attn_drop, rng_seed = float(attn_drop), int(rng_seed) & (2 ** 64 - 1)
-        if not 0.0 <= attn_drop < 1.0:
-            raise ValueError(f"GATEdgeAttention: attn_drop must be in [0, 1) (got {attn_drop})")
+        attn_drop, rng_seed = _drop_args("GATEdgeAttention", attn_drop, rng_seed)
         if _is_block(info):
             H = _block_features(H, info, "GATEdgeAttention")
             if er.dim() != 2 or er.shape[0] != info.num_src or el.dim() != 2 or el.shape[0] != info.num_dst or \
@@ -1121,22 +1100,12 @@ class GATEdgeAttention(Function):
     def backward(ctx, dY):
         H, el, er, ee, lse, Y = ctx.saved_tensors
         info = ctx.info
-        rest = (None,) * (len(ctx.needs_input_grad) - 4)
         if not any(ctx.needs_input_grad[:4]):
-            return (None, None, None, None) + rest
-        transposed = None
-        if _is_block(info) or _is_directed(info):
-            t = info.transposed()
-            transposed, t_edge_pos = [t.row_pointers, t.column_index, t.partPtr, t.part2Node], t.perm
-        else:
-            from .decider import inputProperty
-            inputProperty.require_symmetric(info)
-            t_edge_pos = info.reverse_edges()
-        dH, d_el, d_er, d_ee = GNNA.gat_edge_backward(H, el, er, ee, lse, Y, dY, info.row_pointers, info.column_index, info.partPtr,
-                                                      info.part2Node, t_edge_pos, info.partSize, ctx.negative_slope, ctx.attn_drop,
-                                                      ctx.rng_seed, transposed)
-        need = ctx.needs_input_grad
-        return (dH if need[0] else None, d_el if need[1] else None, d_er if need[2] else None, d_ee if need[3] else None) + rest
+            return _grads(ctx)
+        t, t_edge_pos = backward_structure(info, require_symmetric=True, edge_pos=True)
+        return _grads(ctx, GNNA.gat_edge_backward(H, el, er, ee, lse, Y, dY, info.row_pointers, info.column_index, info.partPtr,
+                                                  info.part2Node, t_edge_pos, info.partSize, ctx.negative_slope, ctx.attn_drop,
+                                                  ctx.rng_seed, _transposed_args(info, t)))
 
 
 class GATConv(Module):
@@ -1237,13 +1206,11 @@ class GATConv(Module):
         er = (Hh * self.att_r).sum(-1)          # [N, heads] ([num_src, heads]): source side
         weights = None
         if self.fused and drop:
-            if rng_seed is None:
-                rng_seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())       # (a CPU tensor: no device synchronisation)
-            self.last_rng_seed = int(rng_seed)
+            seed = _step_seed(self, rng_seed)
             if ee is not None:
-                Y = GATEdgeAttention.apply(H, el, er, ee, inputInfo, self.negative_slope, self.attn_drop, self.last_rng_seed)
+                Y = GATEdgeAttention.apply(H, el, er, ee, inputInfo, self.negative_slope, self.attn_drop, seed)
             else:
-                Y = GATAttention.apply(H, el, er, inputInfo, self.negative_slope, self.attn_drop, self.last_rng_seed)
+                Y = GATAttention.apply(H, el, er, inputInfo, self.negative_slope, self.attn_drop, seed)
         elif self.fused:
             if ee is not None:
                 Y = GATEdgeAttention.apply(H, el, er, ee, inputInfo, self.negative_slope)
@@ -1301,9 +1268,7 @@ class GATv2Attention(Function):
     @staticmethod
     def forward(ctx, Hs, Hd, att, inputInfo, negative_slope, attn_drop=0.0, rng_seed=0):
         info = inputInfo
-        attn_drop, rng_seed = float(attn_drop), int(rng_seed) & (2 ** 64 - 1)      # (the key arithmetic is mod 2^64)
-        if not 0.0 <= attn_drop < 1.0:
-            raise ValueError(f"GATv2Attention: attn_drop must be in [0, 1) (got {attn_drop})")
+        attn_drop, rng_seed = _drop_args("GATv2Attention", attn_drop, rng_seed)
         for t, name in ((Hs, "Hs"), (Hd, "Hd"), (att, "att")):
             if t.dtype != torch.float32:
                 raise TypeError(f"GATv2Attention: float32 only (got {name}: {t.dtype})")
@@ -1326,21 +1291,12 @@ class GATv2Attention(Function):
     def backward(ctx, dY):
         Hs, Hd, att, lse, Y = ctx.saved_tensors
         info = ctx.info
-        rest = (None,) * (len(ctx.needs_input_grad) - 3)       # inputInfo, negative_slope (, attn_drop (, rng_seed))
         if not any(ctx.needs_input_grad[:3]):
-            return (None, None, None) + rest
-        transposed = None
-        if _is_block(info) or _is_directed(info):      # (a block is never symmetric: require_symmetric is not for it)
-            t = info.transposed()
-            transposed = [t.row_pointers, t.column_index, t.partPtr, t.part2Node]
-        else:
-            from .decider import inputProperty
-            inputProperty.require_symmetric(info)    # raises on a structure that is not symmetric (answer cached per column_index)
-        dHs, dHd, d_att = GNNA.gatv2_backward(Hs, Hd, att, lse, Y, dY, info.row_pointers, info.column_index, info.partPtr,
-                                              info.part2Node, info.partSize, ctx.negative_slope, ctx.attn_drop, ctx.rng_seed,
-                                              transposed)
-        need = ctx.needs_input_grad
-        return (dHs if need[0] else None, dHd if need[1] else None, d_att if need[2] else None) + rest
+            return _grads(ctx)
+        transposed = _transposed_args(info, backward_structure(info, require_symmetric=True))
+        return _grads(ctx, GNNA.gatv2_backward(Hs, Hd, att, lse, Y, dY, info.row_pointers, info.column_index, info.partPtr,
+                                               info.part2Node, info.partSize, ctx.negative_slope, ctx.attn_drop, ctx.rng_seed,
+                                               transposed))
 
 
 class GATv2Conv(Module):
@@ -1399,10 +1355,8 @@ class GATv2Conv(Module):
             Hd = torch.mm(X[:n] if block else X, self.W_r)
         if self.fused:
             if drop:
-                if rng_seed is None:
-                    rng_seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())       # (a CPU tensor: no device synchronisation)
-                self.last_rng_seed = int(rng_seed)
-                Y = GATv2Attention.apply(Hs, Hd, self.att, inputInfo, self.negative_slope, self.attn_drop, self.last_rng_seed)
+                Y = GATv2Attention.apply(Hs, Hd, self.att, inputInfo, self.negative_slope, self.attn_drop,
+                                         _step_seed(self, rng_seed))
             else:
                 Y = GATv2Attention.apply(Hs, Hd, self.att, inputInfo, self.negative_slope)
         else:
@@ -1437,9 +1391,7 @@ class DotAttention(Function):
     def forward(ctx, Q, K, V, inputInfo, heads, scale=None, attn_drop=0.0, rng_seed=0):
         info = inputInfo
         heads = int(heads)
-        attn_drop, rng_seed = float(attn_drop), int(rng_seed) & (2 ** 64 - 1)      # (the key arithmetic is mod 2^64)
-        if not 0.0 <= attn_drop < 1.0:
-            raise ValueError(f"DotAttention: attn_drop must be in [0, 1) (got {attn_drop})")
+        attn_drop, rng_seed = _drop_args("DotAttention", attn_drop, rng_seed)
         for t, name in ((Q, "Q"), (K, "K"), (V, "V")):
             if t.dtype != torch.float32:
                 raise TypeError(f"DotAttention: float32 only (got {name}: {t.dtype})")
@@ -1465,20 +1417,11 @@ class DotAttention(Function):
     def backward(ctx, dY):
         Q, K, V, lse, Y = ctx.saved_tensors
         info = ctx.info
-        rest = (None,) * (len(ctx.needs_input_grad) - 3)       # inputInfo, heads (, scale (, attn_drop (, rng_seed)))
         if not any(ctx.needs_input_grad[:3]):
-            return (None, None, None) + rest
-        transposed = None
-        if _is_block(info) or _is_directed(info):      # (a block is never symmetric: require_symmetric is not for it)
-            t = info.transposed()
-            transposed = [t.row_pointers, t.column_index, t.partPtr, t.part2Node]
-        else:
-            from .decider import inputProperty
-            inputProperty.require_symmetric(info)    # raises on a structure that is not symmetric (answer cached per column_index)
-        dQ, dK, dV = GNNA.dot_attn_backward(Q, K, V, ctx.heads, lse, Y, dY, info.row_pointers, info.column_index, info.partPtr,
-                                            info.part2Node, info.partSize, ctx.scale, ctx.attn_drop, ctx.rng_seed, transposed)
-        need = ctx.needs_input_grad
-        return (dQ if need[0] else None, dK if need[1] else None, dV if need[2] else None) + rest
+            return _grads(ctx)
+        transposed = _transposed_args(info, backward_structure(info, require_symmetric=True))
+        return _grads(ctx, GNNA.dot_attn_backward(Q, K, V, ctx.heads, lse, Y, dY, info.row_pointers, info.column_index, info.partPtr,
+                                                  info.part2Node, info.partSize, ctx.scale, ctx.attn_drop, ctx.rng_seed, transposed))
 
 
 class TransformerConv(Module):
@@ -1533,10 +1476,7 @@ class TransformerConv(Module):
         Q, K, V = P[:n, :W], P[:, W:2 * W], P[:, 2 * W:]
         if self.fused:
             if drop:
-                if rng_seed is None:
-                    rng_seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())       # (a CPU tensor: no device synchronisation)
-                self.last_rng_seed = int(rng_seed)
-                Y = DotAttention.apply(Q, K, V, inputInfo, self.heads, None, self.attn_drop, self.last_rng_seed)
+                Y = DotAttention.apply(Q, K, V, inputInfo, self.heads, None, self.attn_drop, _step_seed(self, rng_seed))
             else:
                 Y = DotAttention.apply(Q, K, V, inputInfo, self.heads)
         else:

@@ -103,14 +103,8 @@ class RelationalGraph(object):
     def transposed(self):
         """The transposed structure with its permuted edge arrays (built once; synchronises; not inside a stream capture)."""
         if self._transposed is None:
-            info = self.info
-            t = info.transposed()
-            perm = getattr(t, "perm", None)
-            if perm is None:
-                # (the builder gives the same bits on every run: this pass orders the edges exactly as the block's own did)
-                rp = info.row_pointers.to(self.edge_type.device)
-                perm = _lib.transpose_csr(rp, info.column_index, num_in_rows=self.num_src)[2].clamp_(min=0)
-            self._transposed = _TypedTranspose(t, perm, self.edge_type, self.edge_norm)
+            t = self.info.transposed()
+            self._transposed = _TypedTranspose(t, t.perm, self.edge_type, self.edge_norm)
         return self._transposed
 
     # ---- the three passes ---------------------------------------------------------------------------------------------------

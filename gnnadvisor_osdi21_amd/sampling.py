@@ -23,28 +23,19 @@ import torch
 
 from . import _lib
 from .batching import GraphBatch
+from .structure import Transpose
 
 
-class _BlockTranspose(object):
+class _BlockTranspose(Transpose):
     """A^T of a block with its partition: [num_src] rows gathering from [num_dst] rows (what the backward of a sum runs on).
-    ``perm`` (int32 [nnz]: position in the block's column_index of every transposed edge) is built at its first use, which only
-    the attention with an edge term makes."""
+    ``perm`` is the base's: built at its first use, which only the operators with a per-edge operand make."""
 
     def __init__(self, block):
-        self._source, self._num_src, self._perm = (block.row_pointers, block.column_index), block.num_src, None
-        self.row_pointers, self.column_index, _ = _lib.transpose_csr(block.row_pointers, block.column_index,
-                                                                     num_in_rows=block.num_src, want_perm=False)
-        self.partSize = block.partSize
-        self.partPtr, self.part2Node = _lib.build_part_device(self.partSize, self.row_pointers)
+        source = (block.row_pointers, block.column_index)
+        t_rp, t_ci, _ = _lib.transpose_csr(*source, num_in_rows=block.num_src, want_perm=False)
+        super().__init__(t_rp, t_ci, block.partSize, source)
         if self.column_index.numel() > 0:
             _lib._forget_when_freed(self.column_index)
-
-    @property
-    def perm(self):
-        if self._perm is None:
-            # (the builder gives the same bits on every run; an edge dropped for an id outside the block sits behind every row)
-            self._perm = _lib.transpose_csr(*self._source, num_in_rows=self._num_src)[2].clamp_(min=0)
-        return self._perm
 
 
 class SampledBlock(object):

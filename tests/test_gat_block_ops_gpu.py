@@ -65,7 +65,7 @@ def test_fused_gatconv_on_a_block_matches_the_fp64_layer(fin, fout, heads, conca
 
 
 def test_the_transpose_is_built_by_the_first_backward_that_needs_it_and_by_nothing_else():
-    """What a sum operator's rule (`_block_sum_backward`: no transpose when X needs no gradient) becomes for attention.  The
+    """What a sum operator's rule (`ops._sum_backward`: no transpose when X needs no gradient) becomes for attention.  The
     gradient of the layer's own weight is X^T dH with dH[j] = sum_i alpha(i, j) dY[i], a sum over the edges that leave source j:
     the source-side pass, which walks block.transposed().  So unlike SAGEConv a first GAT layer with a trainable weight does
     build the transpose even though X needs no gradient.  What holds, and is checked: the forward builds none; a backward that
