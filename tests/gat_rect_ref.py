@@ -133,6 +133,62 @@ def wide_short_structure(n_out=700, n_in=300, hub_row=17, hub_edges=5000, empty=
     return rp.astype(np.int32), ci.astype(np.int32)
 
 
+THRESHOLDS = (32, 64, 128, 256, 512, 1024, 2048)
+THRESHOLD_N_IN = 150
+
+
+def threshold_lengths():
+    """The row lengths threshold_structure() must contain: the shortest rows and t - 1, t, t + 1 around every power of two t at
+    which a pass changes its path (sorted)."""
+    return sorted({0, 1, 2, 3, 5} | {t + d for t in THRESHOLDS for d in (-1, 0, 1)})
+
+
+def threshold_structure(extra=36, unreached=10, seed=31):
+    """A [62 x 150] structure whose destination rows have every length of threshold_lengths() once -- a row is `long` for GAT's lse
+    pass above seg * 32 edges (seg = 4 .. 64 lanes) and for the shared lse pass of GATv2 / dot above (64 / LPR) * 32, and a pull
+    kernel loads 64 ids per step, so each of those switches sits between two rows -- and `extra` rows of 1 .. 11 edges, in a seeded
+    random order.  Random unsorted ids with duplicates (the long rows have far more edges than there are sources); the last
+    `unreached` source rows are named by no edge.  About 12,400 edges.  -> (rp, ci) int32 numpy; THRESHOLD_N_IN source rows."""
+    rng = np.random.default_rng(seed)
+    deg = np.concatenate([np.array(threshold_lengths()), rng.integers(1, 12, size=extra)])
+    deg = deg[rng.permutation(len(deg))]
+    rp = np.zeros(len(deg) + 1, dtype=np.int64)
+    rp[1:] = np.cumsum(deg)
+    ci = rng.integers(0, THRESHOLD_N_IN - unreached, size=rp[-1])
+    return rp.astype(np.int32), ci.astype(np.int32)
+
+
+def multi_run_structure(num_groups, partSize, unreached=10, seed=41):
+    """A structure with exactly `num_groups` neighbor-groups at `partSize` (1 or 100) whose rows are runs of several groups, for the
+    launches that give a wavefront more than one group.  partSize 1: rows of 0 .. 12 edges, so a row of k edges is a run of k
+    groups.  partSize 100: rows of 1 .. 8 edges (one group) and every 50th row 250 edges (three groups).  The source side has a
+    third of the rows (the transposed structure has longer rows, and enough groups for G >= 2 there too), random unsorted ids
+    with duplicates, the last `unreached` sources named by no edge.  -> (rp, ci, num_in_rows), int32 numpy."""
+    assert partSize in (1, 100) and num_groups >= 64
+    rng = np.random.default_rng(seed + partSize)
+    if partSize == 1:
+        deg = rng.integers(0, 13, size=num_groups // 5)                 # mean 6: more rows than needed
+        cut = int(np.searchsorted(np.cumsum(deg), num_groups, side="left"))
+        deg = deg[:cut + 1]
+        deg[-1] -= deg.sum() - num_groups                               # (the last row is shortened to the count; never below 1)
+    else:
+        n = num_groups                                                  # an upper bound of the rows
+        deg = rng.integers(1, 9, size=n)
+        deg[26::50] = 250
+        groups = np.cumsum(-(-deg // partSize))
+        cut = int(np.searchsorted(groups, num_groups, side="left"))
+        deg = deg[:cut + 1]
+        if groups[cut] != num_groups:                                   # a three-group row overshoots: one group in its place
+            deg[-1] = 7
+            deg = np.concatenate([deg, np.full(num_groups - int(groups[cut - 1]) - 1, 3)])
+    assert int((-(-deg // partSize)).sum()) == num_groups
+    rp = np.zeros(len(deg) + 1, dtype=np.int64)
+    rp[1:] = np.cumsum(deg)
+    n_in = max(64, len(deg) // 3) + unreached
+    ci = rng.integers(0, n_in - unreached, size=rp[-1])
+    return rp.astype(np.int32), ci.astype(np.int32), n_in
+
+
 def plant_out_of_range(ci, n_in, every=9):
     """A copy of ci with every `every`-th id replaced by one outside [0, n_in): n_in itself, n_in + 7, 2^31 - 1 and -1 in turn."""
     out = np.array(ci, dtype=np.int64)

@@ -6,8 +6,8 @@ run that spans several 64-id loads), duplicate edges, 40 rows without edges and 
 ids outside the source rows planted; a small symmetric square graph passed as its own transpose with Q, K and V as column slices
 of one [N, 3 W] matrix; a directed square graph with the device-built transpose.  partSize 3 and 32: a row's groups straddle the
 wavefronts of a workgroup and workgroups.
-Shapes: every lane layout -- LPH = 1 (64 x 1) to 64 (1 x 256), dim % 4 != 0, rows wider than one wave-wide load (8 x 40: column
-blocks of whole heads).  Inputs: randn Q, K, V, dY with scale = 1 / sqrt(dim).
+Shapes: 8 of the 28 lane layouts -- LPH = 1 (64 x 1) to 64 (1 x 256), dim % 4 != 0, rows wider than one wave-wide load (8 x 40:
+column blocks of whole heads); tests/test_attn_layouts_gpu.py runs every layout.  Inputs: randn Q, K, V, dY with scale = 1 / sqrt(dim).
 Bounds: 1e-5 * max(1, sum of |terms|) * max(1, S) (dotattn_ref's docstring); the function is smooth, so no element is excluded.
 Every call pre-fills its outputs with NaN, so an element the library does not write fails the comparison.  S is printed per
 shape."""

@@ -5,8 +5,8 @@ Structures: gat_rect_ref.wide_short_structure() -- 700 x 300 with a 5,000-edge h
 run that spans several 64-id loads), duplicate edges, 40 rows without edges and 20 sources no edge reaches -- as it is and with
 ids outside the source rows planted; a small symmetric square graph passed as its own transpose; a directed square graph with
 the device-built transpose.  partSize 3 and 32: a row's groups straddle the wavefronts of a workgroup and workgroups.
-Shapes: every lane layout -- LPH = 1 (64 x 1) to 64 (1 x 256), dim % 4 != 0, rows wider than one wave-wide load (8 x 40: column
-blocks of whole heads).
+Shapes: 8 of the 28 lane layouts -- LPH = 1 (64 x 1) to 64 (1 x 256), dim % 4 != 0, rows wider than one wave-wide load (8 x 40:
+column blocks of whole heads); tests/test_attn_layouts_gpu.py runs every layout.
 Bounds: 1e-5 * max(1, sum of |terms|) * max(1, S) (gatv2_ref's docstring); elements of dHs / dHd with an edge at the kink of the
 leaky ReLU are excluded, nothing of d_att or the forward is.  Every call pre-fills its outputs with NaN, so an element the
 library does not write fails the comparison.  The seeds: gatv2_ref.inputs under seeds 5 .. 12 was checked on the CPU in fp64

@@ -5,11 +5,15 @@ The expected values were worked out by hand from the formula every launcher carr
 2048 / partSize)), halved while ceil(P / G) < 16 * num_cus; blocks = ceil(ceil(P / G) / 4).  A slip here costs speed, not
 correctness, so no parity test would see it.  attn_layout is the lane layout of the fused attention kernels: log_lph =
 log2_lanes(dim, 4), then log_lpr raised from log_lph while log_lpr < 6 and 2^(log_lpr - log_lph) < heads; the values were worked
-out by hand from that rule."""
+out by hand from that rule.  The shape table of tests/attn_cases.py (what the GPU tests of the attention kernels run) is put to
+the same program: its base set must hit each of the 28 layouts exactly once and its column-block set must need more than one
+wave-wide load per row, by the header's own answer."""
 import os
 import subprocess
 
 import pytest
+
+import attn_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gnnadvisor_osdi21_amd", "csrc")
@@ -82,6 +86,7 @@ def answers(tmp_path_factory):
                            "-o", exe])
     asked = [("g",) + k for k, _ in CHUNK_GRID] + [("l", d_, 4, 0) for d_ in LANES_4] + [("l", d_, 8, 0) for d_ in LANES_8]
     asked += [("a",) + k + (0,) for k, _ in ATTN_LAYOUT]
+    asked += [("a",) + k + (0,) for k in attn_cases.ALL_SHAPES if ("a",) + k + (0,) not in asked]
     out = subprocess.check_output([exe] + [str(x) for q in asked for x in q], text=True).splitlines()
     assert len(out) == len(asked)
     return {q: tuple(int(x) for x in line.split()) for q, line in zip(asked, out)}
@@ -100,3 +105,23 @@ def test_log2_lanes(answers):
 @pytest.mark.parametrize("args, want", ATTN_LAYOUT, ids=["%dx%d" % k for k, _ in ATTN_LAYOUT])
 def test_attn_layout(answers, args, want):
     assert answers[("a",) + args + (0,)] == want
+
+
+def test_the_shape_table_hits_each_of_the_28_layouts_once(answers):
+    got = [answers[("a",) + k + (0,)] for k in attn_cases.BASE_SHAPES]
+    every = [(lph, lpr) for lph in range(7) for lpr in range(lph, 7)]
+    assert len(every) == 28 and sorted(got) == every, sorted(set(every) - set(got))
+    for lph, shapes in attn_cases.BASE.items():                       # and the table files each shape under its own log_lph
+        assert [answers[("a",) + k + (0,)] for k in shapes] == [(lph, lpr) for lpr in range(lph, 7)], lph
+    assert all(h <= 64 and d <= 256 for h, d in attn_cases.ALL_SHAPES)  # (what the entries accept)
+
+
+def test_the_column_block_shapes_need_several_blocks(answers):
+    """One per log_lph = 1 .. 6: log_lpr = 6 and more heads than the 2^(6 - log_lph) a wave-wide load holds; the first five end
+    in a partial block (log_lph = 0 has no such shape: 64 heads of at most 4 floats fit one load, and 64 heads is the most)."""
+    assert len(attn_cases.COLUMN_BLOCKS) == 6
+    for k, (heads, dim) in enumerate(attn_cases.COLUMN_BLOCKS):
+        log_lph, log_lpr = answers[("a", heads, dim, 0)]
+        per_block = 1 << (log_lpr - log_lph)
+        assert (log_lph, log_lpr) == (k + 1, 6) and heads > per_block, (heads, dim)
+        assert (heads % per_block != 0) == (k < 5), (heads, dim)
