@@ -202,6 +202,12 @@ HEADERS["gnna_edgefeat.h"] = {
     # (d_edge, ld), num_out_rows, dim, combine, act, flags, stream
     "gnna_agg_edge_feat_backward_ld_f32": (i, [p, i64, i64, p, i64, i64, p, i64] + [p] * 5 + [p, i64] * 2 + [i64, i, i, i, u, p]),
 }
+# graph construction from coordinates: the radius / k-nearest-neighbour graph of every point set of a batch
+HEADERS["gnna_spatial.h"] = {
+    # pos, ld_pos, num_rows, dim, graph_pointers, num_segments, radius, max_neighbors, loop, partSize, row_pointers, column_index,
+    # dist2, partPtr, part2Node, edge_capacity, counts, stream
+    "gnna_radius_graph_f32": (i, [p, i64, i64, i, p, i64, f, i, i, i] + [p] * 5 + [i64, pi64, p]),
+}
 del p, i, i64, u, u64, f, s, pd, pi, pi64
 EXPORTS = tuple(HEADERS["gnna.h"])     # users: the build's check of the library, tests/test_host.py
 
@@ -1761,8 +1767,84 @@ def induced_subgraph(row_pointers, column_index, nodes, partSize=None, want_edge
             "part2Node": p2n[:P] if want_part else None, "num_nodes": m}
 
 
+# ---- graph construction from coordinates (gnna_spatial.hip) ------------------------------------------------------------------
+SPATIAL_LONG_ROWS = 256         # GNNA_SPATIAL_LONG_ROWS: a segment of more rows is taken by the tile kernel (a row per lane, LDS tiles)
+SPATIAL_SOURCE_TILE = 8192      # GNNA_SPATIAL_SOURCE_TILE: floats of a staged source tile (SPATIAL_SOURCE_TILE // dim rows, 256 at most)
+SPATIAL_REGISTER_DIM = 4        # GNNA_SPATIAL_REGISTER_DIM: the tile kernel keeps a destination row of up to this many columns in registers
+SPATIAL_MAX_DIM = 64            # GNNA_SPATIAL_MAX_DIM
+SPATIAL_MAX_NEIGHBORS = 64      # GNNA_SPATIAL_MAX_NEIGHBORS
+SPATIAL_DEFAULT_EDGES = 1 << 22  # edges the default capacity of radius_graph holds at least (or 64 per row), before the one retry
+
+
+def radius_graph(pos, graph_pointers, radius, max_neighbors=None, loop=False, partSize=None, want_dist2=True, *, edge_capacity=None):
+    """gnna_radius_graph_f32 (device): for every point set g of a batch -- the rows [graph_pointers[g], graph_pointers[g + 1]) of
+    `pos` (float32 [N, dim], 1 <= dim <= 64; a column slice is fine) -- the graph that joins row i to the rows j of its set with
+    d2(i, j) = sum_c (pos[j, c] - pos[i, c])^2 <= radius * radius, every operation rounded to fp32, columns in order; j == i only
+    with loop=True.  max_neighbors (1 .. 64) keeps the that many candidates with the smallest (d2, j) per row; radius = inf with a
+    cap is the k-nearest-neighbour graph (the rule is spelled out in include/gnna_spatial.h).  -> dict: row_pointers [N + 1],
+    column_index [nnz'] (global row ids, increasing within a row), dist2 [nnz'] (None with want_dist2=False), partPtr [P + 1] /
+    part2Node [P] (what build_part gives for the row pointers; None without partSize), num_edges.  The arrays are trimmed views of
+    buffers sized here: min(U, max(2^22, 64 N)) edges, U = sum_g n_g * min(n_g - 1 + loop, max_neighbors or n_g) from a host copy of
+    graph_pointers; when that is too small the call is repeated once at the size it reported.  One stream synchronisation per
+    call; refuses to run inside a stream capture; the same bits on every run; accepted under set_tuning(deterministic=1).
+    edge_capacity overrides the size chosen here (no retry then); a GnnaError raised for a capacity that is too small carries the
+    needed (rows, edges, parts) as ``.counts``."""
+    radius = float(radius)
+    if not radius >= 0.0:
+        raise GnnaError(f"radius must be >= 0 or inf (got {radius})")
+    cap = 0 if max_neighbors is None else int(max_neighbors)
+    if max_neighbors is not None and not 1 <= cap <= SPATIAL_MAX_NEIGHBORS:
+        raise GnnaError(f"max_neighbors must be in [1, {SPATIAL_MAX_NEIGHBORS}] or None (got {max_neighbors})")
+    want_part = partSize is not None
+    if want_part and int(partSize) <= 0:
+        raise GnnaError(f"partSize must be positive (got {partSize})")
+    if edge_capacity is not None and int(edge_capacity) < 0:
+        raise GnnaError("capacities must not be negative")
+    if not (isinstance(pos, torch.Tensor) and pos.dim() == 2 and pos.dtype == torch.float32):
+        raise GnnaError("pos must be a float32 tensor [N, dim]")
+    if not 1 <= pos.shape[1] <= SPATIAL_MAX_DIM:
+        raise GnnaError(f"pos must have 1 .. {SPATIAL_MAX_DIM} columns (got {pos.shape[1]})")
+    _need_device(pos, "radius_graph")
+    # (a tensor without rows has no strides worth checking)
+    xp, n, dim, ld = _rows_view(pos, "pos") if pos.shape[0] > 0 else (None, 0, pos.shape[1], pos.shape[1])
+    dev = pos.device
+    gp, G = _graph_pointers_arg(graph_pointers, dev)
+    loop = bool(loop)
+    if edge_capacity is None:
+        sizes = graph_pointers.cpu().long().clamp(0, n).diff().clamp(min=0)
+        per_row = (sizes - 1 + int(loop)).clamp(min=0)
+        upper = int((sizes * (per_row.clamp(max=cap) if cap else per_row)).sum())
+        edge_cap = min(upper, max(SPATIAL_DEFAULT_EDGES, 64 * n))
+    else:
+        edge_cap = int(edge_capacity)
+
+    def call(edge_cap):
+        with torch.cuda.device(dev):
+            i32 = dict(dtype=torch.int32, device=dev)
+            rp, ci = torch.empty(n + 1, **i32), torch.empty(edge_cap, **i32)
+            d2 = torch.empty(edge_cap, dtype=torch.float32, device=dev) if want_dist2 else None
+            pp = torch.empty(edge_cap + 1, **i32) if want_part else None
+            p2n = torch.empty(edge_cap, **i32) if want_part else None
+            ptr = lambda t: t.data_ptr() if t is not None and t.numel() > 0 else None                 # noqa: E731
+            counts = (ctypes.c_int64 * 3)()
+            rc = load().gnna_radius_graph_f32(xp if n > 0 else None, ld, n, dim, gp, G, radius, cap, int(loop),
+                                              int(partSize) if want_part else 0, rp.data_ptr(), ptr(ci), ptr(d2), _ptr(pp), ptr(p2n),
+                                              edge_cap, counts, _stream(dev))
+        _, e, P = _check_counts(rc, counts)
+        return {"row_pointers": rp, "column_index": ci[:e], "dist2": d2[:e] if want_dist2 else None,
+                "partPtr": pp[:P + 1] if want_part else None, "part2Node": p2n[:P] if want_part else None, "num_edges": e}
+
+    try:
+        return call(edge_cap)
+    except GnnaError as err:
+        needed = getattr(err, "counts", (0, 0, 0))[1]
+        if edge_capacity is not None or not edge_cap < needed < 2 ** 31:
+            raise
+    return call(needed)                                    # once, from what it reported
+
+
 # ---- hierarchical pooling on graph batches (gnna_topk.hip) -------------------------------------------------------------------
-TOPK_WAVE_ROWS = 256            # GNNA_TOPK_WAVE_ROWS: a segment of up to this many rows is selected by one wavefront
+TOPK_WAVE_ROWS = 256           # GNNA_TOPK_WAVE_ROWS: a segment of up to this many rows is selected by one wavefront
 
 
 def topk_keep_count(n: int, ratio=None, k=None) -> int:

@@ -26,11 +26,12 @@ EXT = os.path.join(PKG, "GNNAdvisor.so")
 ARCH = "gfx950"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-LIB_SOURCES = [os.path.join(CSRC, f) for f in ("gnna_agg.hip", "gnna_stream.hip", "gnna_sweep.hip", "gnna_dense.hip", "gnna_x16.hip", "gnna_reduce.hip", "gnna_stats.hip", "gnna_softagg.hip", "gnna_pool.hip", "gnna_segnorm.hip", "gnna_attnpool.hip", "gnna_topk.hip", "gnna_sddmm.hip", "gnna_edge.hip", "gnna_gat.hip", "gnna_gatv2.hip", "gnna_dotattn.hip", "gnna_typed.hip", "gnna_transpose.hip", "gnna_sample.hip", "gnna_walk.hip", "gnna_edgefeat.hip",
+LIB_SOURCES = [os.path.join(CSRC, f) for f in ("gnna_agg.hip", "gnna_stream.hip", "gnna_sweep.hip", "gnna_dense.hip", "gnna_x16.hip", "gnna_reduce.hip", "gnna_stats.hip", "gnna_softagg.hip", "gnna_pool.hip", "gnna_segnorm.hip", "gnna_attnpool.hip", "gnna_topk.hip", "gnna_sddmm.hip", "gnna_edge.hip", "gnna_gat.hip", "gnna_gatv2.hip", "gnna_dotattn.hip", "gnna_typed.hip", "gnna_transpose.hip", "gnna_sample.hip", "gnna_walk.hip", "gnna_edgefeat.hip", "gnna_spatial.hip",
                                                 "gnna_gemm.hip", "gnna_runtime.hip", "gnna_host.cpp", "gnna_reorder.cpp")]
 # the headers of include/, in the order they were added: each is a key of _lib.HEADERS (named here, not derived: no torch import)
 PUBLIC_HEADERS = ("gnna.h", "gnna_ext.h", "gnna_gatv2.h", "gnna_dotattn.h", "gnna_gat_edge.h", "gnna_stats.h", "gnna_softagg.h",
-                  "gnna_pool.h", "gnna_attnpool.h", "gnna_topk.h", "gnna_segnorm.h", "gnna_walk.h", "gnna_edgefeat.h")
+                  "gnna_pool.h", "gnna_attnpool.h", "gnna_topk.h", "gnna_segnorm.h", "gnna_walk.h", "gnna_edgefeat.h",
+                  "gnna_spatial.h")
 INTERNAL_HEADERS = ("gnna_internal.h", "gnna_device.h", "gnna_launch.h", "gnna_gat_common.h", "gnna_keys.h", "gnna_segments.h",
                     "gnna_parts.h")
 _PUBLIC = [os.path.join(INCLUDE, f) for f in PUBLIC_HEADERS]

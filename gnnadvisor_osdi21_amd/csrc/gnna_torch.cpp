@@ -43,6 +43,7 @@
 #include "gnna_topk.h"
 #include "gnna_segnorm.h"
 #include "gnna_walk.h"
+#include "gnna_spatial.h"
 #include "gnna_edgefeat.h"
 
 #define CHECK_CUDA(x) TORCH_CHECK(x.is_cuda(), #x " must be a CUDA tensor")
@@ -1718,6 +1719,63 @@ induced_subgraph(const torch::Tensor &row_pointers, const torch::Tensor &column_
                            sub_nodes.narrow(0, 0, counts[0]), opt(new_id, n), opt(pp, counts[2] + 1), opt(p2n, counts[2]));
 }
 
+// ---- graph construction from coordinates (gnna_spatial.hip) --------------------------------------------------------------------
+
+// The radius / k-nearest-neighbour graph of every point set of a batch (gnna_radius_graph_f32) -> (row_pointers [N + 1],
+// column_index [nnz'], dist2 [nnz'], partPtr [P + 1], part2Node [P]); None for what was not asked for (partSize = 0: no partition,
+// max_neighbors = 0: no cap).  The arrays are trimmed views of buffers of min(U, max(2^22, 64 N)) edges, U = sum_g n_g *
+// min(n_g - 1 + loop, max_neighbors or n_g); when that is too small the call is repeated once at the size it reported.
+std::tuple<torch::Tensor, torch::Tensor, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>>
+radius_graph(const torch::Tensor &pos, const torch::Tensor &graph_pointers, double radius, int64_t max_neighbors, bool loop,
+             int64_t partSize, bool want_dist2)
+{
+    TORCH_CHECK(pos.is_cuda(), "pos must be a CUDA tensor (the builder runs on the device)");
+    TORCH_CHECK(pos.dim() == 2 && pos.size(1) >= 1 && pos.size(1) <= GNNA_SPATIAL_MAX_DIM, "pos must be 2-D [N, dim] with 1 .. ",
+                GNNA_SPATIAL_MAX_DIM, " columns");
+    check_f32(pos, "pos");
+    check_rows(pos, "pos");
+    check_device_ids(graph_pointers, "graph_pointers");
+    TORCH_CHECK(graph_pointers.numel() >= 1 && graph_pointers.device() == pos.device(),
+                "graph_pointers must be [num_graphs + 1] on pos's device");
+    TORCH_CHECK(radius >= 0.0, "radius must be >= 0 or inf");
+    TORCH_CHECK(max_neighbors >= 0 && max_neighbors <= GNNA_SPATIAL_MAX_NEIGHBORS, "max_neighbors must be in [0, ",
+                GNNA_SPATIAL_MAX_NEIGHBORS, "] (0: no cap)");
+    TORCH_CHECK(partSize >= 0 && partSize <= std::numeric_limits<int>::max(), "partSize must not be negative");
+    const bool parts = partSize > 0;
+    const int64_t n = pos.size(0), g = graph_pointers.numel() - 1;
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(pos.device());
+    const auto ids = graph_pointers.options();
+    int64_t edge_cap = 0;
+    {
+        const auto sizes = graph_pointers.to(at::kCPU).to(at::kLong).clamp(0, n).diff().clamp_min(0);
+        auto per_row = (sizes - 1 + (loop ? 1 : 0)).clamp_min(0);
+        if (max_neighbors > 0) per_row = per_row.clamp_max(max_neighbors);
+        edge_cap = std::min<int64_t>((sizes * per_row).sum().item<int64_t>(), std::max<int64_t>((int64_t)1 << 22, 64 * n));
+    }
+    const torch::Tensor rp = torch::empty({n + 1}, ids);
+    auto ip = [](const torch::Tensor &t) { return t.defined() && t.numel() > 0 ? t.data_ptr<int32_t>() : nullptr; };
+    torch::Tensor ci, d2, pp, p2n;
+    int64_t counts[3] = {0, 0, 0};
+    for (int attempt = 0;; attempt++) {
+        ci = torch::empty({edge_cap}, ids);
+        if (want_dist2) d2 = torch::empty({edge_cap}, pos.options());
+        if (parts) { pp = torch::empty({edge_cap + 1}, ids); p2n = torch::empty({edge_cap}, ids); }
+        const int rc = gnna_radius_graph_f32(n > 0 ? pos.data_ptr<float>() : nullptr, ld_of(pos), n, (int)pos.size(1),
+                                             graph_pointers.data_ptr<int32_t>(), g, (float)radius, (int)max_neighbors, loop ? 1 : 0,
+                                             (int)partSize, rp.data_ptr<int32_t>(), ip(ci),
+                                             want_dist2 && edge_cap > 0 ? d2.data_ptr<float>() : nullptr, ip(pp), ip(p2n), edge_cap,
+                                             counts, current_stream());
+        if (rc != GNNA_OK && attempt == 0 && counts[1] > edge_cap && counts[1] < ((int64_t)1 << 31)) {
+            edge_cap = counts[1];                                          // once, from what it reported
+            continue;
+        }
+        check_rc(rc);
+        break;
+    }
+    auto opt = [](const torch::Tensor &t, int64_t len) { return t.defined() ? c10::optional<torch::Tensor>(t.narrow(0, 0, len)) : c10::nullopt; };
+    return std::make_tuple(rp, ci.narrow(0, 0, counts[1]), opt(d2, counts[1]), opt(pp, counts[2] + 1), opt(p2n, counts[2]));
+}
+
 // what both row gathers check of their features, row ids and scale
 static void gather_rows_check(const torch::Tensor &rows, const char *rows_name, const torch::Tensor &ids, const char *ids_name,
                               const c10::optional<torch::Tensor> &scale, int64_t scale_len)
@@ -1901,6 +1959,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           "column is kept, in increasing position; None for what was not asked for.  One stream synchronisation; not capturable",
           pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("nodes"), pybind11::arg("partSize") = 0,
           pybind11::arg("want_edge_ids") = true, pybind11::arg("want_new_id") = false);
+    m.def("radius_graph", &radius_graph,
+          "the radius / k-nearest-neighbour graph of every point set of a batch (extension) -> (row_pointers, column_index, dist2, "
+          "partPtr, part2Node): row i keeps the rows j of its set with sum_c (pos[j, c] - pos[i, c])^2 <= radius^2 in fp32, under "
+          "max_neighbors > 0 the that many with the smallest (d2, j), in increasing j; None for what was not asked for.  One stream "
+          "synchronisation; not capturable",
+          pybind11::arg("pos"), pybind11::arg("graph_pointers"), pybind11::arg("radius"), pybind11::arg("max_neighbors") = 0,
+          pybind11::arg("loop") = false, pybind11::arg("partSize") = 0, pybind11::arg("want_dist2") = true);
     m.def("gather_rows_scale", &gather_rows_scale,
           "out[i] = scale[perm[i]] * input[perm[i]] (extension) -> out [perm.numel(), dim]; a plain gather without scale; a perm[i] "
           "outside the rows of input gives a row of zeros",

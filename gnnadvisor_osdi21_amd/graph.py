@@ -284,6 +284,46 @@ def small_graphs(num_graphs: int, min_nodes: int, max_nodes: int, avg_degree: fl
     return rp.to(torch.int32).to(device), cols.to(torch.int32).to(device), gp.to(torch.int32).to(device)
 
 
+def small_point_clouds(num_graphs: int, min_nodes: int, max_nodes: int, dim: int = 3, density: float = 1.0, seed: int = 0,
+                       classes: int = 4, device="cpu"):
+    """Seeded point sets shaped like small molecules: `num_graphs` sets whose sizes are drawn uniformly from [min_nodes,
+    max_nodes]; set g is uniform in a cube whose side is s_g * (n_g / density)^(1 / dim), with a per-set stretch s_g drawn from
+    [0.7, 1.4] -- so `density` is about the points per unit volume, a cutoff r sees about density * volume of the r-ball
+    neighbours, and the sets differ in how spread out they are.  The label is the class (by quantiles over the collection) of
+    the set's mean pairwise distance, which only a model that reads the geometry can learn.
+    -> (pos float32 [N, dim], graph_pointers int32 [G + 1], y int64 [G]) on `device`.  The same arguments give the same arrays."""
+    if num_graphs < 0 or min_nodes < 0 or max_nodes < min_nodes or dim < 1 or not density > 0:
+        raise ValueError(f"small_point_clouds: need num_graphs >= 0, 0 <= min_nodes <= max_nodes, dim >= 1 and density > 0 "
+                         f"(got {num_graphs}, {min_nodes}, {max_nodes}, {dim}, {density})")
+    g = torch.Generator()
+    g.manual_seed(int(seed))
+    sizes = torch.randint(min_nodes, max_nodes + 1, (num_graphs,), generator=g, dtype=torch.int64)
+    gp = torch.zeros(num_graphs + 1, dtype=torch.int64)
+    gp[1:] = torch.cumsum(sizes, 0)
+    n = int(gp[-1])
+    if n >= 2 ** 31:
+        raise ValueError("small_point_clouds: fewer than 2^31 points in all (int32 pointers)")
+    stretch = 0.7 + 0.7 * torch.rand(num_graphs, generator=g, dtype=torch.float64)
+    side = stretch * (sizes.double().clamp(min=1) / float(density)) ** (1.0 / dim)
+    which = torch.repeat_interleave(torch.arange(num_graphs), sizes)
+    pos = torch.rand(n, dim, generator=g, dtype=torch.float64) * side[which, None]
+    # the mean pairwise distance of every set, from padded coordinates (host, once)
+    mean_dist = torch.zeros(num_graphs, dtype=torch.float64)
+    n_max = int(sizes.max()) if num_graphs else 0
+    chunk = max(1, (1 << 24) // max(1, n_max * n_max))
+    for lo in range(0, num_graphs if n > 0 else 0, chunk):
+        hi = min(num_graphs, lo + chunk)
+        local = torch.arange(n_max)
+        valid = local[None, :] < sizes[lo:hi, None]
+        P = pos[(gp[lo:hi, None] + local[None, :]).clamp(max=max(n - 1, 0))]
+        d = torch.cdist(P, P) * (valid[:, :, None] & valid[:, None, :])
+        pairs = (sizes[lo:hi] * (sizes[lo:hi] - 1)).clamp(min=1).double()
+        mean_dist[lo:hi] = d.sum((1, 2)) / pairs
+    y = torch.empty(num_graphs, dtype=torch.int64)
+    y[mean_dist.argsort()] = torch.arange(num_graphs) * int(classes) // max(num_graphs, 1)
+    return pos.float().to(device), gp.to(torch.int32).to(device), y.to(device)
+
+
 # Named synthetic stand-ins for BASELINE.json's configs (SURVEY.md 8d).  Shapes follow the
 # public dataset cards; the graphs themselves are seeded power-law graphs.
 CONFIGS = {

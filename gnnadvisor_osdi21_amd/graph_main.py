@@ -2,6 +2,7 @@
 
     python -m gnnadvisor_osdi21_amd.graph_main --model gin --num_graphs 4096 --graph_nodes 8,72 --batch_graphs 256 --readout sum
     python -m gnnadvisor_osdi21_amd.graph_main --model gine --edge_dim 4 --num_graphs 4096 --batch_graphs 256
+    python -m gnnadvisor_osdi21_amd.graph_main --model schnet --cutoff 1.5 --num_graphs 4096 --batch_graphs 256
 
 The reference evaluates half of its inputs ("Type II": collections of small graphs) with node-level drivers only; this driver
 finishes such a model inside the library.  A seeded synthetic collection (graph.small_graphs) is kept on the device as a
@@ -15,6 +16,10 @@ The label of a graph is a function of its size and its features' mean, so that t
 ``--model gine --edge_dim K`` draws K features per edge (not symmetrised: e_ij != e_ji), lets the label depend on them too, and
 trains edgeconv.GINEConv layers on mini-batches built as ``directed`` ones, so that the backward finds an edge's features through
 the device-built ``perm`` of the transposed batch; with ``--pool`` the edge features follow the coarsening.
+``--model schnet --cutoff R [--max_neighbors K]`` draws point sets instead (graph.small_point_clouds: the label is the class of a
+set's mean pairwise distance) and builds the graph of every mini-batch on the device from the batch's positions at every step
+(spatial.radius_graph: libgnna gnna_radius_graph_f32; ``--fused_graph False`` composes it from torch ops), runs
+spatial.SchNetInteraction layers on it and the same readout.
 """
 import argparse
 import sys
@@ -34,6 +39,11 @@ def build_parser():
     p.add_argument("--model", type=str, default="gin", help="gcn, gin, or gine (GIN with edge features: needs --edge_dim)")
     p.add_argument("--edge_dim", type=int, default=0, help="--model gine: features per edge of the synthetic collection")
     p.add_argument("--fused_edge", type=_bool, default=True, help="False: the edge-feature aggregation composed from torch ops")
+    p.add_argument("--cutoff", type=float, default=None, help="--model schnet: the radius of the graph built from the positions")
+    p.add_argument("--max_neighbors", type=int, default=None, help="--model schnet: keep the nearest K (1 .. 64) within the cutoff")
+    p.add_argument("--num_gaussians", type=int, default=32, help="--model schnet: centres of the distance expansion")
+    p.add_argument("--fused_graph", type=_bool, default=True, help="False: the radius graph composed from torch ops")
+    p.add_argument("--density", type=float, default=1.0, help="--model schnet: points per unit volume of the synthetic point sets")
     p.add_argument("--num_graphs", type=int, default=4096, help="graphs in the synthetic collection")
     p.add_argument("--graph_nodes", type=str, default="8,72", help="MIN,MAX nodes per graph")
     p.add_argument("--avg_degree", type=float, default=4.0, help="average degree inside a graph")
@@ -64,11 +74,22 @@ def build_parser():
 
 
 def _parse(args):
-    if args.model not in ("gcn", "gin", "gine"):
+    if args.model not in ("gcn", "gin", "gine", "schnet"):
         raise SystemExit("--model %s: graph_main trains gcn or gin (the other layers take a GraphBatch too: build the model with ops), "
                          "or gine with --edge_dim K" % args.model)
     if args.model == "gine" and args.edge_dim < 1:
         raise SystemExit("--model gine needs --edge_dim K with K >= 1: the features per edge (got %d)" % args.edge_dim)
+    if args.model == "schnet":
+        if args.cutoff is None or not 0.0 < args.cutoff < float("inf"):
+            raise SystemExit("--model schnet needs --cutoff R with 0 < R < inf: the radius of the graph (got %r)" % args.cutoff)
+        if args.max_neighbors is not None and not 1 <= args.max_neighbors <= 64:
+            raise SystemExit("--max_neighbors must be in [1, 64] (got %d)" % args.max_neighbors)
+        if args.num_gaussians < 2:
+            raise SystemExit("--num_gaussians must be >= 2 (got %d)" % args.num_gaussians)
+        if args.pool != "none" or args.norm != "none":
+            raise SystemExit("--model schnet runs without --pool and --norm: a coarsened batch would need its graph rebuilt from the kept positions")
+    elif args.cutoff is not None or args.max_neighbors is not None:
+        raise SystemExit("--cutoff / --max_neighbors: only --model schnet builds its graph from positions (got --model %s)" % args.model)
     if args.model != "gine" and args.edge_dim != 0:
         raise SystemExit("--edge_dim %d: only --model gine takes edge features (got --model %s)" % (args.edge_dim, args.model))
     if args.dtype != "float32":
@@ -107,6 +128,30 @@ def build_model(args, modes):
     from torch.nn import Linear, Module, ModuleList, ReLU, Sequential
 
     from .ops import AttentionalReadout, GCNConv, GINConv, GraphNorm, Readout, SAGPooling, TopKPooling
+    if args.model == "schnet":
+        from .spatial import SchNetInteraction
+
+        class SchNet(Module):
+            def __init__(self):
+                super().__init__()
+                self.embed = Linear(args.dim, args.hidden)
+                self.layers = ModuleList(SchNetInteraction(args.hidden, args.hidden, args.num_gaussians, args.cutoff, fused=args.fused_edge)
+                                         for _ in range(args.num_layers))
+                self.readout = Readout(modes, fused=args.fused_readout)
+                self.attention = AttentionalReadout(Linear(args.hidden, 1 if args.attention_readout == "scalar" else args.hidden),
+                                                    fused=args.fused_readout) if args.attention_readout != "none" else None
+                self.lin = Linear(args.hidden * (len(modes) + (1 if self.attention is not None else 0)), args.classes)
+
+            def forward(self, x, batch):
+                x = self.embed(x)
+                for layer in self.layers:
+                    x = layer(x, batch)
+                pooled = self.readout(x, batch)
+                if self.attention is not None:
+                    pooled = torch.cat((pooled, self.attention(x, batch)), 1)
+                return torch.log_softmax(self.lin(pooled), dim=1)
+
+        return SchNet()
     conv = GCNConv if args.model == "gcn" else GINConv
     gine = args.model == "gine"
     if gine:
@@ -186,6 +231,27 @@ def make_dataset(args, lo, hi, device):
     return GraphDataset(rp, ci, gp, x.to(device), y.to(device), edge_attr=edge_attr.to(device))
 
 
+class PointBatch(object):
+    """The graphs [first, last) of a point-set collection: positions, pointers, features and labels; its graph is built per step."""
+
+    def __init__(self, pos, gp, x, y, first, last):
+        lo, hi = int(gp[first]), int(gp[last])
+        self.pos, self.x, self.y = pos[lo:hi], x[lo:hi], y[first:last]
+        self.graph_pointers = (gp[first:last + 1] - lo).to(torch.int32).to(pos.device)
+        self.num_graphs = last - first
+
+
+def make_point_batches(args, lo, hi, device, B):
+    """(the PointBatch list of --model schnet, nodes in all): graph.small_point_clouds, node features as make_dataset draws them."""
+    from .graph import small_point_clouds
+    pos, gp, y = small_point_clouds(args.num_graphs, lo, hi, dim=3, density=args.density, seed=args.seed, classes=args.classes)
+    g = torch.Generator()
+    g.manual_seed(args.seed + 1)
+    x = torch.randn(int(gp[-1]), args.dim, generator=g)
+    pos, x, y = pos.to(device), x.to(device), y.to(device)
+    return [PointBatch(pos, gp, x, y, k, min(k + B, args.num_graphs)) for k in range(0, args.num_graphs, B)], int(gp[-1])
+
+
 def main(argv=None, capture=None):
     args = build_parser().parse_args(argv)
     lo, hi, modes = _parse(args)
@@ -193,10 +259,13 @@ def main(argv=None, capture=None):
         raise SystemExit("graph_main needs a GPU: there is no CPU path in libgnna")
     device = torch.device("cuda")
     torch.manual_seed(args.seed)
+    schnet = args.model == "schnet"
+    B = min(args.batch_graphs, args.num_graphs)
+    if schnet:
+        return train_schnet(args, lo, hi, modes, device, B, capture)
     dataset = make_dataset(args, lo, hi, device)
     model = build_model(args, modes).to(device)
     optimizer = torch.optim.Adam(model.parameters(), lr=args.lr)
-    B = min(args.batch_graphs, args.num_graphs)
     # the mini-batches are the same every epoch: cut them out once (each is a few arrays on the device)
     ids = torch.arange(args.num_graphs, device=device)
     # (gine: a directed batch finds an edge's features in the backward through the perm of its device-built transpose; the
@@ -243,6 +312,68 @@ def main(argv=None, capture=None):
     if capture is not None:
         capture.update(final_loss=float(loss), epoch_ms=train_time * 1e3 / args.num_epoches)
     if args.verbose_mode:
+        print("# final loss: {:.6f}".format(float(loss)))
+    print('Time (ms): {:.3f}'.format(train_time * 1e3 / args.num_epoches))
+    print()
+    return 0
+
+
+def train_schnet(args, lo, hi, modes, device, B, capture):
+    """--model schnet: every step builds its mini-batch's graph on the device from the batch's positions."""
+    from . import spatial
+    batches, nodes = make_point_batches(args, lo, hi, device, B)
+    model = build_model(args, modes).to(device)
+    optimizer = torch.optim.Adam(model.parameters(), lr=args.lr)
+    seen = {"edges": 0, "graph_ms": 0.0}
+
+    def graph_of(b):
+        batch = spatial.radius_graph(b.pos, args.cutoff, b.graph_pointers, max_num_neighbors=args.max_neighbors, partSize=args.partSize,
+                                     fused=args.fused_graph, hiddenDim=args.hidden)
+        seen["edges"] += int(batch.column_index.numel())
+        return batch
+
+    def epoch(timed=False):
+        total = torch.zeros((), device=device)
+        seen["edges"] = 0
+        for b in batches:
+            if timed:
+                torch.cuda.synchronize()
+                start = time.perf_counter()
+            batch = graph_of(b)
+            if timed:
+                torch.cuda.synchronize()
+                seen["graph_ms"] += (time.perf_counter() - start) * 1e3
+            optimizer.zero_grad(set_to_none=True)
+            loss = torch.nn.functional.nll_loss(model(b.x, batch), b.y)
+            loss.backward()
+            optimizer.step()
+            total += loss.detach() * b.num_graphs
+        return total / args.num_graphs
+
+    model.train()
+    first = epoch()                                   # dry run; also the loss after one epoch
+    if capture is not None:
+        capture.update(first_loss=float(first), num_edges=seen["edges"], num_nodes=nodes)
+    if args.verbose_mode:
+        print("# %d point sets, %d nodes, %d batches of up to %d graphs, readout %s (%s)" % (
+            args.num_graphs, nodes, len(batches), B, ",".join(modes), "fused" if args.fused_readout else "composed"))
+        print("# radius graph: cutoff %g, %s, built per step (%s): %d nodes %d edges per epoch" % (
+            args.cutoff, "no cap" if args.max_neighbors is None else "at most %d neighbours" % args.max_neighbors,
+            "fused" if args.fused_graph else "composed", nodes, seen["edges"]))
+        print("# loss after 1 epoch: {:.6f}".format(float(first)))
+    torch.cuda.synchronize()
+    start = time.perf_counter()
+    for _ in range(args.num_epoches):
+        loss = epoch()
+    torch.cuda.synchronize()
+    train_time = time.perf_counter() - start
+    if capture is not None:
+        capture.update(final_loss=float(loss), epoch_ms=train_time * 1e3 / args.num_epoches)
+    if args.verbose_mode:
+        epoch(timed=True)                             # one more epoch with a synchronisation around every graph build
+        print("# graph construction: {:.3f} ms of an epoch (synchronised around every build)".format(seen["graph_ms"]))
+        if capture is not None:
+            capture.update(graph_ms=seen["graph_ms"])
         print("# final loss: {:.6f}".format(float(loss)))
     print('Time (ms): {:.3f}'.format(train_time * 1e3 / args.num_epoches))
     print()
