@@ -33,7 +33,7 @@ PUBLIC_HEADERS = ("gnna.h", "gnna_ext.h", "gnna_gatv2.h", "gnna_dotattn.h", "gnn
                   "gnna_pool.h", "gnna_attnpool.h", "gnna_topk.h", "gnna_segnorm.h", "gnna_walk.h", "gnna_edgefeat.h",
                   "gnna_spatial.h")
 INTERNAL_HEADERS = ("gnna_internal.h", "gnna_device.h", "gnna_launch.h", "gnna_gat_common.h", "gnna_keys.h", "gnna_segments.h",
-                    "gnna_parts.h")
+                    "gnna_parts.h", "gnna_prepass.h")
 _PUBLIC = [os.path.join(INCLUDE, f) for f in PUBLIC_HEADERS]
 LIB_DEPS = LIB_SOURCES + [os.path.join(CSRC, f) for f in INTERNAL_HEADERS] + _PUBLIC
 EXT_SOURCES = [os.path.join(CSRC, "gnna_torch.cpp")]

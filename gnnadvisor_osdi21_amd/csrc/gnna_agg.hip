@@ -22,10 +22,12 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 
 #include "gnna.h"
 #include "gnna_device.h"
 #include "gnna_internal.h"
+#include "gnna_prepass.h"
 
 namespace gnna {
 namespace {
@@ -38,58 +40,14 @@ prologue_kernel(float *__restrict__ Y, size_t n_floats, int D, int ldy, const in
                 const int32_t *__restrict__ chk_ids, int64_t chk_n, const unsigned long long *__restrict__ chk_sum,
                 int32_t *stale_flag, uint32_t *__restrict__ clear_words, int n_clear)
 {
-    // the step counters of the sweep kernel behind this launch (<= kBlock words): cleared here instead of by a launch of their own
-    if (blockIdx.x == 0 && (int)threadIdx.x < n_clear) clear_words[threadIdx.x] = 0u;
-    // packed ids of a prepared graph: does column_index still look like the array the copy was made from?  (1024 samples:
-    // catches a buffer that was rewritten, which is what happens when a promise of immutability is broken by accident.)
-    // The launcher adds one block for it, so that the zero-fill does not wait behind the sampled loads.
+    // the launcher adds one block for the packed-id sample check (gnna_prepass.h: check_packed_ids), the last of the grid
     const unsigned fill_blocks = chk_ids ? gridDim.x - 1 : gridDim.x;
     if (blockIdx.x >= fill_blocks) {
-        if (threadIdx.x < kWave) {
-            const unsigned long long then = chk_sum[0], distrusted = chk_sum[4];   // [4]: a full hash differed earlier (gnna_stream.hip)
-            const unsigned long long now = graph_checksum(chk_ids, chk_n, pp, P, (int)threadIdx.x);
-            if (threadIdx.x == 0 && (now != then || distrusted != 0ull)) *stale_flag = seq;
-        }
+        check_packed_ids(chk_ids, chk_n, pp, P, chk_sum, stale_flag, seq);
         return;
     }
-    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t nthreads = (size_t)fill_blocks * blockDim.x;
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    if (!zero_fill) {
-        // accumulate mode: Y keeps its contents
-    } else if (ldy != D) {
-        // rows `ldy` floats apart (the caller's leading dimension): only the D floats of every row are the library's
-        if ((D & 3) == 0 && (ldy & 3) == 0 && (reinterpret_cast<uintptr_t>(Y) & 15) == 0) {
-            const size_t n4 = n_floats >> 2;
-            const unsigned d4 = (unsigned)D >> 2, ld4 = (unsigned)ldy >> 2;
-            const f32x4 z = (f32x4)(0.f);
-            for (size_t i = tid; i < n4; i += nthreads) {
-                const size_t r = i / d4;
-                reinterpret_cast<f32x4 *>(Y)[r * ld4 + (i - r * d4)] = z;
-            }
-        } else {
-            for (size_t i = tid; i < n_floats; i += nthreads) {
-                const size_t r = i / (unsigned)D;
-                Y[r * (size_t)ldy + (i - r * (unsigned)D)] = 0.f;
-            }
-        }
-    } else if ((reinterpret_cast<uintptr_t>(Y) & 15) == 0) {
-        const size_t n4 = n_floats >> 2;
-        f32x4 *Y4 = reinterpret_cast<f32x4 *>(Y);
-        const f32x4 z = (f32x4)(0.f);
-        for (size_t i = tid; i < n4; i += nthreads) Y4[i] = z;
-        for (size_t i = (n4 << 2) + tid; i < n_floats; i += nthreads) Y[i] = 0.f;
-    } else {
-        for (size_t i = tid; i < n_floats; i += nthreads) Y[i] = 0.f;
-    }
-    if (validate) {
-        bool bad = false;
-        for (int64_t g = (int64_t)tid; g < P; g += (int64_t)nthreads) {
-            if (pp[g + 1] < pp[g]) bad = true;
-            if (g + 1 < P && p2n[g + 1] < p2n[g]) bad = true;
-        }
-        if (bad) *flag = seq;  // every writer stores the same value
-    }
+    fill_and_validate(Y, n_floats, D, ldy, p2n, pp, P, flag, seq, validate, zero_fill, clear_words, n_clear, blockIdx.x, fill_blocks,
+                      blockDim.x);
 }
 
 // ---- sparse prologue: zero only the rows nobody overwrites --------------------------------------
@@ -209,45 +167,54 @@ post_prologue_kernel(float *__restrict__ Y, size_t n_floats, int D, int ldy, con
     }
 }
 
-// ---- GCN pre-scaling: Xs[j, :] = deg[j] * X[j, :] -------------------------------------------
-// Lets the degree-weighted aggregation run as an unweighted gather of Xs with one multiply by
-// deg[i] at the flush (deg_i * sum_j deg_j x_j), instead of one extra 4-byte gather plus a
-// broadcast and a multiply per edge.
+// ---- staging copy / GCN pre-scaling on its own: Xs[j, :] = deg[j] * X[j, :] (gnna_prepass.h: stage_rows) ---------------------
 __global__ void __launch_bounds__(kBlock)
 scale_rows_kernel(const float *__restrict__ X, int64_t ld_in, const float *__restrict__ deg, float *__restrict__ Xs,
                   int64_t rows, int D, int ld_out)
 {
-    // Xs[r, 0:D] = (deg ? deg[r] : 1) * X[r, 0:D]; rows of X `ld_in`, rows of Xs `ld_out` floats apart (pads never read,
-    // except by the 4-float loads of rows narrower than 4 floats, whose padding lanes are never stored)
-    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t nthreads = (size_t)gridDim.x * blockDim.x;
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    const bool aligned = ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Xs)) & 15) == 0;
-    if (ld_out == D && ld_in == D && (D & 3) == 0 && aligned) {
-        const size_t n4 = ((size_t)rows * (size_t)D) >> 2;
-        const int d4 = D >> 2;
-        for (size_t i = tid; i < n4; i += nthreads) {
-            const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(X) + i);
-            reinterpret_cast<f32x4 *>(Xs)[i] = deg ? v * deg[i / d4] : v;
-        }
-    } else if ((D & 3) == 0 && (ld_out & 3) == 0 && (ld_in & 3) == 0 && aligned) {
-        // padded / gapped layouts of rows whose width is a whole number of 16-byte pieces: one vector per thread
-        const size_t n4 = ((size_t)rows * (size_t)D) >> 2;
-        const unsigned d4 = (unsigned)D >> 2;
-        const size_t ldo4 = (size_t)ld_out >> 2, ldi4 = (size_t)ld_in >> 2;
-        for (size_t i = tid; i < n4; i += nthreads) {
-            const size_t r = i / d4, c4 = i - r * d4;
-            const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(X) + r * ldi4 + c4);
-            reinterpret_cast<f32x4 *>(Xs)[r * ldo4 + c4] = deg ? v * deg[r] : v;
-        }
-    } else {
-        const size_t total = (size_t)rows * (size_t)D;
-        for (size_t i = tid; i < total; i += nthreads) {
-            const size_t r = i / (unsigned)D, cc = i - r * (unsigned)D;
-            const float v = __builtin_nontemporal_load(X + r * (size_t)ld_in + cc);
-            Xs[r * (size_t)ld_out + cc] = deg ? v * deg[r] : v;
+    stage_rows(X, ld_in, deg, Xs, rows, D, ld_out, blockIdx.x, gridDim.x, blockDim.x);
+}
+
+// ---- the pre-pass: the passes in front of the aggregation kernel as block ranges of one launch -------------------------------
+// None reads what another writes: the staging copy touches X and the scratch, the fill `out` (and the partition and the call's
+// sync words), the check the ids, the split X and the image.  So the call pays one launch for them, not three one behind the
+// other, and the copy's loads overlap the fill's stores.  The split reads the hub rows from the caller's X (the staged copy is
+// being written by this very launch) and runs whatever the check finds: it cannot see the stale flag of its own launch, its
+// inputs (r2n, the image scratch) belong to the plan and the stream, and hub_block_kernel -- the image's only reader -- returns
+// at once when the ids are stale.  A block of the split is one 32-rank step on the block's first 128 threads (the other two
+// wavefronts only meet the barrier): 12 KB of LDS per block, so eight blocks still fit a compute unit (96 of 160 KB) and the
+// copy and fill blocks lose no occupancy, which two steps per block (24 KB) would cost them.
+struct PrepassStage { const float *X; int64_t ld_in; const float *deg; float *Xs; int64_t rows; int D; int ld_out; };
+struct PrepassFill {
+    float *Y; size_t n_floats; int D, ldy; const int32_t *p2n; const int32_t *pp; int64_t P; int32_t *flag; int32_t seq;
+    int validate, zero_fill; uint32_t *clear_words; int n_clear;
+};
+struct PrepassCheck { const int32_t *ids; int64_t n; const unsigned long long *sum; int32_t *stale_flag; };
+struct PrepassSplit { const float *X; const float *deg; const int32_t *r2n; unsigned char *img; int ldx, full; };
+
+template <bool SPLIT>
+__global__ void __launch_bounds__(kBlock)
+prepass_kernel(const PrepassGrid grid, const PrepassStage st, const PrepassFill fl, const PrepassCheck ck, const PrepassSplit sp)
+{
+    const PrepassRole r = prepass_role_of(grid, blockIdx.x);       // (block-uniform)
+    if constexpr (SPLIT) {
+        __shared__ __attribute__((aligned(16))) unsigned char s_img[kSplitLdsBytes];
+        if (r.role == PREPASS_SPLIT) {
+            const int t = (int)threadIdx.x;
+            if (t < kSplitThreads) {
+                if (sp.full) split_step_to_lds<true>(sp.X, sp.ldx, sp.deg, sp.r2n, fl.D, s_img, (int)r.index, t);
+                else split_step_to_lds<false>(sp.X, sp.ldx, sp.deg, sp.r2n, fl.D, s_img, (int)r.index, t);
+            }
+            __syncthreads();
+            if (t < kSplitThreads) split_step_from_lds(sp.img, s_img, (int)r.index, t);
+            return;
         }
     }
+    if (r.role == PREPASS_STAGE) stage_rows(st.X, st.ld_in, st.deg, st.Xs, st.rows, st.D, st.ld_out, r.index, r.count, blockDim.x);
+    else if (r.role == PREPASS_FILL)
+        fill_and_validate(fl.Y, fl.n_floats, fl.D, fl.ldy, fl.p2n, fl.pp, fl.P, fl.flag, fl.seq, fl.validate, fl.zero_fill, fl.clear_words,
+                          fl.n_clear, r.index, r.count, blockDim.x);
+    else if (r.role == PREPASS_CHECK) check_packed_ids(ck.ids, ck.n, fl.pp, fl.P, ck.sum, ck.stale_flag, fl.seq);
 }
 
 // ---- host side ------------------------------------------------------------------------------
@@ -417,10 +384,12 @@ int sweep_auto_phases(const gnna_tuning &t, int mode, int dim, size_t x_bytes, i
 //     entries * t_edge  -  t_hub(H)  -  t_split  -  t_launch,      t_hub(H) = rounds * (H_pad / 128) * t_chunk(tile)
 // t_edge: what the sweep kernel pays per edge.  t_chunk: what a workgroup of hub_block_kernel takes per 128 source ranks, for
 // the tile height the launch will take (dense_tile_ranks: 32 destination ranks per workgroup while that is one round, 64
-// beyond); rounds = workgroups (H_pad / tile) over compute units, rounded up.  t_split: hub_split_kernel and the gap of its
-// launch.  All measured on MI355X on the Reddit-like headline with tools/probe_hub_block.py, a scan over forced hub counts
-// and tile heights under a kernel trace (profiles/hub_block_presplit/hub_count_scan.log and hub_count_scan_kernels.log; the
-// scans of the earlier forms of the kernel: profiles/hub_block_bf16, profiles/hub_block_rate, profiles/dense_block):
+// beyond); rounds = workgroups (H_pad / tile) over compute units, rounded up.  t_split: what the split of the hub rows adds
+// to the call -- since the pre-pass launch (prepass_kernel) a block range of a launch the call makes anyway, so neither a
+// launch nor a gap of its own.  All measured on MI355X on the Reddit-like headline with tools/probe_hub_block.py, a scan over
+// forced hub counts and tile heights under a kernel trace (t_edge, t_chunk: profiles/hub_block_presplit/hub_count_scan.log and
+// hub_count_scan_kernels.log; t_split: profiles/prepass/hub_count_scan_*.log; the scans of the earlier forms of the kernel:
+// profiles/hub_block_bf16, profiles/hub_block_rate, profiles/dense_block):
 //   * t_edge: the sweep kernel fell from 1,351.9 to 1,169.4 us (medians; minima 1,326.8 to 1,158.7) for the 16.19 M edges of
 //     8,192 hubs and to 1,126.4 (1,101.7) for the 22.71 M of 12,390: 11.3 / 9.9 ps per edge by the medians, 10.4 / 9.9 by the
 //     minima; 9.9 from the scans before this one stays;
@@ -428,16 +397,19 @@ int sweep_auto_phases(const gnna_tuning &t, int mode, int dim, size_t x_bytes, i
 //     of 256 workgroups): 0.73 us per chunk (0.97 when every workgroup split X itself; 0.79 at 4,224 ranks), and 73.3 us for
 //     12,416 ranks with 64-rank tiles (97 chunks, 194 workgroups): 0.76 us per chunk (0.80 at 8,192 ranks: 51.1 us, which is
 //     why one round of short tiles stays short);
-//   * t_split: hub_split_kernel 5.2 .. 5.5 us, and the step fell by 11.6 (8,192 hubs) and 13.7 us (12,390) less than the
-//     kernel times did, where one launch's 7 us were modelled: 5.5 us of kernel and 5.5 of gap;
+//   * t_split: prepass_kernel took 32.8 us without a block, 33.5 with the split of 8,192 hubs and 33.3 with that of 12,416
+//     ranks (medians of 20 .. 44 launches), with no gap behind it in any leg: 0.7 us.  (As a launch of its own,
+//     hub_split_kernel took 5.2 .. 5.5 us and as much again of gap: 11 us, the constant until the pre-pass.)  The step by
+//     events cannot resolve the term: over three scans it fell by 107.0 .. 122.8 us at 8,192 hubs and by 136.0 .. 161.4 at the
+//     rule's own 12,352 against no block, where the model says 105.9 and 142.9;
 //   * t_launch: 7 us from the scan of the first form of the kernel (profiles/dense_block/README.md).
-// The step at 12,390 hubs is now 14 us below the step at 8,192 (1.2534 against 1.2673 ms; before, with two rounds of short
-// tiles that split X themselves, 52 us above it), so the rule takes that block on the headline.  trimmed_hubs, kDenseMinSaving
-// and kDenseMinShare stay as they were.
+// The term is the same for every hub count, so the block the rule takes on the headline is the one it took before: 12,352 hubs
+// (theta 1,449, 22.66 M entries), whose step is 29 .. 50 us below the step at 8,192.  What moves is the margin: a block now
+// pays from a modelled 25 us of saving that used to need 35.  trimmed_hubs, kDenseMinSaving and kDenseMinShare stay as they were.
 constexpr double kDenseEdgeSeconds = 9.9e-12;
 constexpr double kDenseChunkSeconds = 0.73e-6;      // a 32-rank tile
 constexpr double kDenseTallChunkSeconds = 0.76e-6;  // a 64-rank tile
-constexpr double kDenseSplitSeconds = 11.0e-6;      // hub_split_kernel and its launch
+constexpr double kDenseSplitSeconds = 0.7e-6;       // the split's blocks inside the pre-pass launch
 constexpr double kDenseLaunchSeconds = 7.0e-6;
 constexpr double kDenseMinSaving = 25.0e-6;     // margin: a saving below the run-to-run spread (1.5 % of the headline) is none
 constexpr double kDenseMinShare = 0.03;         // of the edges
@@ -573,6 +545,56 @@ void launch_relu_rows(DeviceState *ds, hipStream_t stream, float *out, int64_t r
 
 namespace {
 
+// GNNA_PREPASS, read at every call: 0 = every pass in front of the aggregation kernel is a launch of its own (A/B runs, tests),
+// unset or anything else = the pre-pass launch.
+bool prepass_enabled()
+{
+    const char *s = std::getenv("GNNA_PREPASS");
+    return !(s && *s && std::atoi(s) == 0);
+}
+
+// The pre-pass launch of a call (prepass_kernel): the staging copy (`stage`, or null: the rows are gathered from where they
+// are), the dense prologue, the packed-id check (chk_ids, or null) and the hub-row split of `split_db` (or null) from the
+// caller's X.  GNNA_PREPASS_ORDER, read at every call: 0 = the stage range ahead of the fill range, unset or 1 = stage and fill
+// blocks alternate (profiles/prepass: the order that measured faster).  GNNA_PREPASS_LOG=1 prints the roles and their blocks.
+int launch_prepass(DeviceState *ds, hipStream_t stream, const PrepassStage *stage, float *out, size_t n_floats, int dim, int ldy,
+                   const int32_t *part2Node, const int32_t *part_pointers, int64_t num_parts, int32_t *flag, int32_t seq, int validate,
+                   int zero_fill, uint32_t *clear_words, int n_clear, const int32_t *chk_ids, int64_t chk_n,
+                   const unsigned long long *chk_sum, int32_t *stale_flag, const DenseBlock *split_db, const float *input, int ld_in,
+                   const float *split_deg, void *split_image)
+{
+    PrepassStage st{};
+    if (stage) st = *stage;
+    PrepassFill fl;
+    fl.Y = out; fl.n_floats = n_floats; fl.D = dim; fl.ldy = ldy; fl.p2n = part2Node; fl.pp = part_pointers; fl.P = num_parts;
+    fl.flag = flag; fl.seq = seq; fl.validate = validate; fl.zero_fill = zero_fill; fl.clear_words = clear_words; fl.n_clear = n_clear;
+    PrepassCheck ck;
+    ck.ids = chk_ids; ck.n = chk_n; ck.sum = chk_sum; ck.stale_flag = stale_flag;
+    PrepassSplit sp{};
+    if (split_db) {
+        if (dim < kDenseMinDim || dim > kDenseMaxDim) return fail(GNNA_ERR_INVALID_ARGUMENT, "hub block: width %d", dim);
+        sp.X = input; sp.deg = split_deg; sp.r2n = split_db->r2n; sp.img = static_cast<unsigned char *>(split_image); sp.ldx = ld_in;
+        sp.full = (dim % 4 == 0 && ld_in % 4 == 0 && (reinterpret_cast<uintptr_t>(input) & 15) == 0) ? 1 : 0;
+    }
+    const char *order = std::getenv("GNNA_PREPASS_ORDER");
+    const bool interleave = !(order && *order && std::atoi(order) == 0);
+    const uint64_t stage_items = stage ? (uint64_t)stage->rows * (uint64_t)dim * sizeof(float) / 16 : 0;
+    // (a copy of fewer than 16 bytes is still a copy; the fill always has the call's sync words and the validation)
+    const PrepassGrid grid = prepass_grid(stage ? std::max<uint64_t>(1, stage_items) : 0,
+                                          std::max<uint64_t>(1, std::max<uint64_t>(n_floats / 4, (uint64_t)num_parts)), chk_ids != nullptr,
+                                          split_db ? (unsigned)(split_db->H_pad / 32) : 0u, ds->num_cus, interleave);
+    if (split_db) hipLaunchKernelGGL((prepass_kernel<true>), dim3(grid.total), dim3(kBlock), 0, stream, grid, st, fl, ck, sp);
+    else hipLaunchKernelGGL((prepass_kernel<false>), dim3(grid.total), dim3(kBlock), 0, stream, grid, st, fl, ck, sp);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GNNA_ERR_HIP, "pre-pass launch: %s", hipGetErrorString(e));
+    const char *log = std::getenv("GNNA_PREPASS_LOG");
+    if (log && *log && *log != '0')
+        std::fprintf(stderr, "gnna prepass: stage %u, fill %u (zero-fill %d, validate %d), check %u, split %u blocks, %s\n",
+                     grid.count[PREPASS_STAGE], grid.count[PREPASS_FILL], zero_fill, validate, grid.count[PREPASS_CHECK],
+                     grid.count[PREPASS_SPLIT], interleave ? "stage and fill alternate" : "stage ahead of fill");
+    return GNNA_OK;
+}
+
 // One aggregation call.  ld_in / ld_out: row strides of `input` / `out` in floats (>= dim).  flags: GNNA_ACCUMULATE,
 // GNNA_EPILOGUE_RELU.  num_windows > 1: the call is one of a windowed sequence and covers source windows [win_begin, win_end).
 // (MODE_EDGE: `degrees_in` carries the caller's edge weights, indexed like column_index; `degrees` is unused)
@@ -697,10 +719,41 @@ int launch_agg(int mode, const float *input, int64_t ld_in, int64_t num_in_rows,
     const unsigned long long *chk_sum = nullptr;
     int64_t chk_n = 0;
     int32_t *stale_flag = flag + kFlagSlots;          // the second ring, same slot
-    auto run_prologue = [&](int sparse_G, uint32_t *clear_words = nullptr, int n_clear = 0) -> int {
+    // The staging copy of this call (set where the rows' source is decided, below) and the hub-row split of its dense block:
+    // enqueued by run_prologue, as block ranges of the pre-pass launch where that applies -- the dense prologue of a whole,
+    // non-deterministic call that has a copy or a split to make (GNNA_PREPASS, read per call: 0 = every pass its own launch) --
+    // and as launches of their own otherwise: the copy ahead of the prologue, the split behind it (hub_split_kernel reads the
+    // stale flag the prologue raises).
+    PrepassStage stage{};
+    bool need_stage = false, split_done = false;
+    auto run_staging = [&]() -> int {
+        const size_t s_bytes = (size_t)stage.rows * (size_t)dim * sizeof(float);
+        hipLaunchKernelGGL(scale_rows_kernel, dim3(std::max(1u, prepass_pass_blocks(s_bytes / 16, ds->num_cus))), dim3(kBlock), 0, stream,
+                           stage.X, stage.ld_in, stage.deg, stage.Xs, stage.rows, stage.D, stage.ld_out);
+        hipError_t es = hipGetLastError();
+        if (es != hipSuccess) return fail(GNNA_ERR_HIP, "staging launch: %s", hipGetErrorString(es));
+        return GNNA_OK;
+    };
+    auto run_prologue = [&](int sparse_G, uint32_t *clear_words = nullptr, int n_clear = 0, const DenseBlock *split_db = nullptr,
+                            void *split_image = nullptr) -> int {
         const int validate = (num_parts > 0 && !tune.trust_canonical) ? 1 : 0;
         const int zero_fill = (accumulate_into_out || win_begin > 0) ? 0 : 1;
-        if (sparse_G > 0 && zero_fill && num_parts > 0) {
+        const bool sparse_path = sparse_G > 0 && zero_fill && num_parts > 0;
+        if (!sparse_path && num_parts > 0 && num_windows == 1 && tune.deterministic != 1 && (need_stage || split_db) && prepass_enabled()) {
+            const int rc_pre = launch_prepass(ds, stream, need_stage ? &stage : nullptr, out, n_floats, dim, ldy, part2Node, part_pointers,
+                                              num_parts, flag, seq, validate, zero_fill, clear_words, n_clear,
+                                              chk_sum ? column_index : nullptr, chk_n, chk_sum, stale_flag, split_db, input, (int)ld_in,
+                                              stage.deg, split_image);
+            if (rc_pre != GNNA_OK) return rc_pre;
+            split_done = split_db != nullptr;
+            profile_record(prof_call, 1, stream);
+            return GNNA_OK;
+        }
+        if (need_stage) {
+            const int rc_stage = run_staging();
+            if (rc_stage != GNNA_OK) return rc_stage;
+        }
+        if (sparse_path) {
             int64_t blocks = (num_parts + kBlock - 1) / kBlock;
             blocks = std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)ds->num_cus * 8));
             unsigned long long *gaps = ds->gap_lists + (size_t)call_block_of(ds, stream, seq) * kGapWords;
@@ -774,14 +827,10 @@ int launch_agg(int mode, const float *input, int64_t ld_in, int64_t num_in_rows,
         // (windowed calls stage the rows of their own windows only: later windows may not have arrived)
         const int64_t r0 = std::min<int64_t>((int64_t)win_begin * window_rows, num_in_rows);
         const int64_t r1 = std::min<int64_t>((int64_t)win_end * window_rows, num_in_rows);
-        const size_t s_bytes = (size_t)(r1 - r0) * (size_t)dim * sizeof(float);
-        int64_t sblocks = (int64_t)((s_bytes / 16 + kBlock - 1) / kBlock);
-        sblocks = std::max<int64_t>(1, std::min<int64_t>(sblocks, (int64_t)ds->num_cus * 8));
-        hipLaunchKernelGGL(scale_rows_kernel, dim3((unsigned)sblocks), dim3(kBlock), 0, stream,
-                           input + (size_t)r0 * (size_t)ld_in, ld_in, prescale ? degrees_in + r0 : nullptr,
-                           static_cast<float *>(xs) + (size_t)r0 * ldx, r1 - r0, dim, ldx);
-        hipError_t es = hipGetLastError();
-        if (es != hipSuccess) return fail(GNNA_ERR_HIP, "staging launch: %s", hipGetErrorString(es));
+        // (the copy itself is enqueued where the prologue is, run_prologue: as blocks of the pre-pass or as a launch of its own)
+        stage.X = input + (size_t)r0 * (size_t)ld_in; stage.ld_in = ld_in; stage.deg = prescale ? degrees_in + r0 : nullptr;
+        stage.Xs = static_cast<float *>(xs) + (size_t)r0 * ldx; stage.rows = r1 - r0; stage.D = dim; stage.ld_out = ldx;
+        need_stage = true;
         X = static_cast<const float *>(xs);
         if (prescale) {
             row_scale = degrees;
@@ -865,7 +914,15 @@ int launch_agg(int mode, const float *input, int64_t ld_in, int64_t num_in_rows,
         }
         uint32_t *sync = ds->sweep_sync + (size_t)call_block_of(ds, stream, seq) * kSweepSlotWords;
         static_assert(kXcds * 16 + 2 <= kBlock, "the prologue clears the sweep counters with one block");
-        rc = run_prologue(0, sync, kXcds * 16 + 2);       // (dense prologue: it also zeroes the call's step counters and list header)
+        // the block's operand: the hub rows of this call's X, split once into their three bf16 pieces (scratch of the call's
+        // stream: two streams may run one prepared graph on different X at once).  Ahead of the sweep: it reads X alone.
+        void *hub_image = nullptr;
+        if (dense) {
+            rc = get_workspace(ds, stream, kSlotDenseImage, dense_image_bytes(db.H_pad), &hub_image);
+            if (rc != GNNA_OK) return rc;
+        }
+        // (dense prologue: it also zeroes the call's step counters and list header; with the copy and the split: the pre-pass)
+        rc = run_prologue(0, sync, kXcds * 16 + 2, dense ? &db : nullptr, hub_image);
         if (rc != GNNA_OK) return rc;
         SweepLaunch w;
         w.mode = mode; w.X = X; w.col = column_index; w.pp = part_pointers; w.p2n = part2Node; w.Y = out;
@@ -882,12 +939,7 @@ int launch_agg(int mode, const float *input, int64_t ld_in, int64_t num_in_rows,
         if (dense) { w.res_col = db.res_col; w.res_pp = db.res_pp; w.res_cnt = db.res_cnt; w.res_ids_packed = res_ids; w.res_item_off = res_off; }
         t_last_phases = Bs;
         t_last_launches = 1;
-        // the block's operand: the hub rows of this call's X, split once into their three bf16 pieces (scratch of the call's
-        // stream: two streams may run one prepared graph on different X at once).  Ahead of the sweep: it reads X alone.
-        void *hub_image = nullptr;
-        if (dense) {
-            rc = get_workspace(ds, stream, kSlotDenseImage, dense_image_bytes(db.H_pad), &hub_image);
-            if (rc != GNNA_OK) return rc;
+        if (dense && !split_done) {                       // (GNNA_PREPASS=0: the split as a launch of its own, from the gathered rows)
             rc = launch_hub_split(stream, db, X, ldx, dim, hub_image, stale_flag, seq);
             if (rc != GNNA_OK) return rc;
         }

@@ -18,7 +18,8 @@
 //     exact, and what is rounded are fp32 sums as before: the hi products in one accumulator (one rounding per 32 source
 //     ranks, however the matrix unit adds inside an instruction), the mid and lo products -- 2^-8 and 2^-16 of them -- in
 //     another, the two added once at the end.  (A lo piece below 2^-126 is a bf16 subnormal and may be dropped: an error
-//     below 2^-126 per term.)  The split is made ONCE per call by hub_split_kernel, ahead of the sweep kernel: the three
+//     below 2^-126 per term.)  The split is made ONCE per call, ahead of the sweep kernel, by the split role of the pre-pass
+//     launch (prepass_kernel, gnna_agg.hip; hub_split_kernel where the pass is a launch of its own: GNNA_PREPASS=0): the three
 //     pieces of the hub rows of that call's X, in the order of the MFMA's B operand, in the scratch of the call's stream
 //     (3 MB at 8,192 hubs, 6 MB at 16,384).  hub_block_kernel loads its operands from that image and does no arithmetic on X.
 //
@@ -31,7 +32,8 @@
 // swept phase count are made by the code that makes them for any graph.
 //
 // Stale ids: the guard of the packed copy keeps watching the caller's arrays.  On a call that finds them changed the sweep
-// kernel reads the caller's arrays and hub_split_kernel and hub_block_kernel return at once.
+// kernel reads the caller's arrays and hub_block_kernel returns at once (and so does hub_split_kernel; the split role of the
+// pre-pass cannot see the flag its own launch raises and writes an image that nobody reads).
 //
 // Environment, read at every gnna_prepare_graph: GNNA_DENSE_BLOCK = 0 never / 1 (default) the rule of gnna_agg.hip / 2 any
 // prepared graph whose call sweeps (tests); GNNA_DENSE_BLOCK_THETA = the degree threshold, under mode 2 only (tests: a hub count
@@ -56,6 +58,7 @@
 #include "gnna.h"
 #include "gnna_device.h"
 #include "gnna_internal.h"
+#include "gnna_prepass.h"
 
 namespace gnna {
 namespace {
@@ -67,7 +70,6 @@ constexpr int kHubWaves = kHubThreads / kWave;
 constexpr int kHubTileM = kDenseTileRanks;    // destination ranks per workgroup of the short tile (two 16-rank MFMA tiles); the tall one: twice
 constexpr int kHubKC = kDenseChunkRanks;      // source ranks of a chunk (one step per wavefront of a column half); the ranks are padded to a multiple of it
 static_assert(kHubTileM == 32, "a tile row of the bitmap per 32 destination ranks");
-constexpr int kSplitThreads = 128;       // hub_split_kernel: the threads of one 32-rank step
 static_assert(kHubKC % (2 * kHubTileM) == 0 && (kHubTileM * 64) % kHubThreads == 0, "whole tiles per chunk, elements per thread");
 static_assert(kDenseMaxDim <= 64, "the split image holds 64 columns");
 
@@ -243,35 +245,10 @@ struct SplitParams {
     int D, ldx;
 };
 
-typedef typename VecOf<4>::T HubVT;
-typedef int HubIT __attribute__((ext_vector_type(4)));
-
-// The split image of a call: per 128-rank chunk [piece 3][32-rank step 4][column tile 4] fragments.  A fragment is the B operand
-// of one MFMA, 64 lanes x 16 bytes, lane-linear: lane 16 kg + n holds the 8 ranks 8 kg .. 8 kg + 7 of the step at column n of
-// the tile.  48 KB per chunk, H_pad * 384 bytes in all (dense_image_bytes).
-constexpr int kHubFrag = 1024;
-constexpr int kHubPiece = 16 * kHubFrag; // bytes between the hi, mid and lo pieces of a chunk (4 steps x 4 column tiles)
-constexpr int kHubImage = 3 * kHubPiece; // 49,152 bytes per chunk
-static_assert(kHubKC == 128 && kHubTileM == 32 && kHubWaves == 8, "the shape hub_block_kernel is written for");
-
 typedef __bf16 HubFrag __attribute__((ext_vector_type(8)));
-typedef uint32_t HubU4 __attribute__((ext_vector_type(4)));
-typedef uint32_t HubU2 __attribute__((ext_vector_type(2)));
-
-// x = hi + mid + lo exactly, each with 8 significant bits in the upper half of its word (a bf16 value): hi is x truncated, mid
-// the truncated remainder, lo what is left of at most 24 bits; both subtractions are exact.  A non-finite x is in hi, with NaN
-// for mid and lo (the header of this file: the end of hub_block_kernel deals with it).
-// (A lo below 2^-126 is a bf16 subnormal whose low bits, and possibly all of it, are dropped: less than 2^-126 per term.)
-__device__ __forceinline__ void hub_split(uint32_t x, uint32_t &hi, uint32_t &mid, uint32_t &lo)
-{
-    hi = x & 0xffff0000u;
-    const float r = __uint_as_float(x) - __uint_as_float(hi);
-    mid = __float_as_uint(r) & 0xffff0000u;
-    lo = __float_as_uint(r - __uint_as_float(mid));
-}
-
-// the upper halves of two words as one: `first` below `second`
-__device__ __forceinline__ uint32_t hub_pack(uint32_t first, uint32_t second) { return __builtin_amdgcn_perm(second, first, 0x07060302u); }
+static_assert(kHubKC == 128 && kHubTileM == 32 && kHubWaves == 8, "the shape hub_block_kernel is written for");
+// (HubVT, HubIT, HubU4, HubU2, the geometry of the split image -- kHubFrag, kHubPiece, kHubImage -- and hub_split / hub_pack:
+// gnna_prepass.h, beside the split's body)
 
 // 8 bitmap bits -> 8 bf16 of 0 or 1 (0x3f80), element j from bit j
 __device__ __forceinline__ HubFrag hub_ones(uint32_t bits)
@@ -283,69 +260,19 @@ __device__ __forceinline__ HubFrag hub_ones(uint32_t bits)
     return __builtin_bit_cast(HubFrag, v);
 }
 
-// The three bf16 pieces of the hub rows of the call's X, ONCE per call (before, each of the block's workgroups split every row
-// on its way to LDS: 256 times per value).  A workgroup of 128 threads takes a 32-rank step: thread (g, pc) fetches 4 columns of
-// the 4 consecutive ranks 4 g .. 4 g + 3 (their ids are one 16-byte load), splits the 16 values and writes, per column and
-// piece, the 4 ranks as 8 bytes into an LDS image of the step; behind a barrier the image goes out 16 bytes per lane, 4 KB per
-// piece.  A padding rank and the columns from D on are zeros.  FULL: D and ldx are multiples of 4 and X is 16-byte aligned, so
-// every 16-byte piece of a row is whole and aligned; otherwise the elements are fetched one by one.
+// The split pass on its own (a caller's gapped layout under GNNA_PREPASS=0; otherwise the split is a block range of
+// prepass_kernel, gnna_agg.hip): one workgroup of 128 threads per 32-rank step, the body of gnna_prepass.h.
 template <bool FULL>
 __global__ void __launch_bounds__(kSplitThreads)
 hub_split_kernel(const SplitParams p)
 {
     if (*p.stale == p.seq) return;       // the ids changed since the block was made: hub_block_kernel returns at once as well
-    __shared__ __attribute__((aligned(16))) unsigned char s_img[3 * 4 * kHubFrag];
+    __shared__ __attribute__((aligned(16))) unsigned char s_img[kSplitLdsBytes];
     const int t = (int)threadIdx.x;
-    const int g = t >> 4, pc = t & 15;
     const int step = (int)blockIdx.x;
-    const int D = p.D;
-    const HubIT node = *reinterpret_cast<const HubIT *>(&p.r2n[step * 32 + 4 * g]);
-    HubVT v[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int nd = node[k];
-        const float *src = p.X + (size_t)(nd < 0 ? 0 : nd) * (size_t)p.ldx + 4 * pc;
-        HubVT x = (HubVT)(0.f);
-        if (nd >= 0) {
-            if constexpr (FULL) {
-                if (4 * pc < D) x = *reinterpret_cast<const HubVT *>(src);
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4; q++)
-                    if (4 * pc + q < D) x[q] = src[q];
-            }
-        }
-        v[k] = x;
-    }
-    const int wbase = (pc >> 2) * kHubFrag + (16 * (g >> 1) + 4 * (pc & 3)) * 16 + 8 * (g & 1);
-#pragma unroll
-    for (int cc = 0; cc < 4; cc++) {
-        // column cc of the thread's 4 x 4 values: split, packed by rank pairs, 8 bytes per piece
-        uint32_t pk[3][2];
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            uint32_t a[3], b[3];
-            hub_split(__float_as_uint(v[2 * h][cc]), a[0], a[1], a[2]);
-            hub_split(__float_as_uint(v[2 * h + 1][cc]), b[0], b[1], b[2]);
-#pragma unroll
-            for (int i = 0; i < 3; i++) pk[i][h] = hub_pack(a[i], b[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            HubU2 o;
-            o[0] = pk[i][0];
-            o[1] = pk[i][1];
-            *reinterpret_cast<HubU2 *>(&s_img[wbase + i * 4 * kHubFrag + cc * 16]) = o;
-        }
-    }
+    split_step_to_lds<FULL>(p.X, p.ldx, nullptr, p.r2n, p.D, s_img, step, t);
     __syncthreads();
-    unsigned char *out = p.img + (size_t)(step >> 2) * kHubImage + (size_t)(step & 3) * 4 * kHubFrag;
-#pragma unroll
-    for (int u = 0; u < 3 * 4 * kHubFrag / 16 / kSplitThreads; u++) {
-        const int idx = u * kSplitThreads + t;
-        const int i = idx >> 8, off = (idx & 255) * 16;
-        *reinterpret_cast<HubU4 *>(&out[i * kHubPiece + off]) = *reinterpret_cast<const HubU4 *>(&s_img[i * 4 * kHubFrag + off]);
-    }
+    split_step_from_lds(p.img, s_img, step, t);
 }
 
 // A workgroup owns TM destination ranks (TM / 16 MFMA tiles, TM / 32 tile rows of the bitmap) and walks ALL source ranks, 128

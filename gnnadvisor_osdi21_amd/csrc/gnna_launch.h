@@ -86,6 +86,67 @@ inline unsigned elementwise_grid(int64_t items, int num_cus, int blocks_per_cu)
     return (unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)num_cus * blocks_per_cu));
 }
 
+// ---- the pre-pass launch of an aggregation call (prepass_kernel, gnna_agg.hip) ----------------------------------------------
+// One grid whose blocks are divided among up to four roles: staging copy, output fill (+ partition validation), packed-id check
+// and hub-row split.  A role without work has no blocks.  The grid begins with the split blocks (short blocks with a barrier:
+// first, so that they are not the tail), then the check block, then the stage and fill blocks -- alternating block by block
+// while both roles have blocks left (`interleave`), else the stage range ahead of the fill range.  Plain arithmetic: the launcher
+// fills a PrepassGrid and the kernel asks prepass_role_of for its block; a host program asks both (tests/test_prepass_grid.py).
+#if defined(__HIPCC__)
+#define GNNA_HOST_DEVICE __host__ __device__
+#else
+#define GNNA_HOST_DEVICE
+#endif
+enum { PREPASS_STAGE = 0, PREPASS_FILL = 1, PREPASS_CHECK = 2, PREPASS_SPLIT = 3, PREPASS_ROLES = 4 };
+struct PrepassGrid {
+    unsigned count[PREPASS_ROLES];   // blocks of each role
+    unsigned check_begin;            // = count[PREPASS_SPLIT]
+    unsigned pass_begin;             // the first stage / fill block
+    unsigned pairs;                  // stage and fill blocks that alternate: min(stage, fill) when interleaved, else 0
+    unsigned total;
+};
+struct PrepassRole {
+    int role;
+    unsigned index, count;           // the block's index among the blocks of its role, and how many those are
+};
+// Blocks of a grid-stride pass over `items` work items, one thread each: none for no items, at most 8 per compute unit.
+inline unsigned prepass_pass_blocks(uint64_t items, int num_cus)
+{
+    if (items == 0) return 0u;
+    const uint64_t blocks = items / (uint64_t)kBlock + (items % (uint64_t)kBlock != 0 ? 1 : 0);    // (no sum that could wrap)
+    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)std::max(1, num_cus) * 8));
+}
+// stage_items: 16-byte pieces of the rows to copy; fill_items: max(16-byte pieces of the output, neighbor-groups to validate);
+// check: the packed-id sample check runs (one block); split_steps: 32-rank steps of the hub-row split (one block each).
+inline PrepassGrid prepass_grid(uint64_t stage_items, uint64_t fill_items, bool check, unsigned split_steps, int num_cus, bool interleave)
+{
+    PrepassGrid g;
+    g.count[PREPASS_STAGE] = prepass_pass_blocks(stage_items, num_cus);
+    g.count[PREPASS_FILL] = prepass_pass_blocks(fill_items, num_cus);
+    g.count[PREPASS_CHECK] = check ? 1u : 0u;
+    g.count[PREPASS_SPLIT] = split_steps;
+    g.check_begin = g.count[PREPASS_SPLIT];
+    g.pass_begin = g.check_begin + g.count[PREPASS_CHECK];
+    g.pairs = interleave ? std::min(g.count[PREPASS_STAGE], g.count[PREPASS_FILL]) : 0u;
+    g.total = g.pass_begin + g.count[PREPASS_STAGE] + g.count[PREPASS_FILL];
+    return g;
+}
+// The role of block `block` < g.total.
+GNNA_HOST_DEVICE inline PrepassRole prepass_role_of(const PrepassGrid &g, unsigned block)
+{
+    if (block < g.check_begin) return {PREPASS_SPLIT, block, g.count[PREPASS_SPLIT]};
+    if (block < g.pass_begin) return {PREPASS_CHECK, block - g.check_begin, g.count[PREPASS_CHECK]};
+    unsigned j = block - g.pass_begin;
+    if (j < 2u * g.pairs) {
+        const int role = (j & 1u) ? PREPASS_FILL : PREPASS_STAGE;
+        return {role, j >> 1, g.count[role]};
+    }
+    j -= 2u * g.pairs;                // what is left of the two ranges, stage first
+    const unsigned stage_left = g.count[PREPASS_STAGE] - g.pairs;
+    if (j < stage_left) return {PREPASS_STAGE, g.pairs + j, g.count[PREPASS_STAGE]};
+    return {PREPASS_FILL, g.pairs + (j - stage_left), g.count[PREPASS_FILL]};
+}
+
 // the smallest power of two >= x (1 for x <= 1)
 inline int pow2_at_least(int64_t x)
 {
