@@ -351,6 +351,9 @@ int64_t scan_tiles(int64_t n);
 int launch_exclusive_scan(hipStream_t stream, int32_t *data, int64_t n, int32_t *partial);
 // GNNA_ERR_UNSUPPORTED when `stream` is being captured (the prepare-time calls read a count back).
 int refuse_capture(const char *what, hipStream_t stream);
+// GNNA_ERR_INVALID_ARGUMENT for the optional partition outputs of a builder when one of partPtr / part2Node comes without the
+// other (a null part2Node is fine where edge_capacity = 0 leaves it no entry), or when they come with a partSize <= 0.
+int check_part_outputs(const char *what, const int32_t *partPtr, const int32_t *part2Node, int partSize, int64_t edge_capacity);
 // words[0 .. n) = 0: one launch (a call's record and the scratch that is cleared together with it).
 void launch_clear_words(DeviceState *ds, hipStream_t stream, int32_t *words, int64_t n);
 // count[i] = the neighbor-groups of row i of `rp` for i < rows, 0 for rows <= i <= n (the scan makes the last one the total):

@@ -9,11 +9,13 @@
 //   seed_kernel         seedpos[seeds[i]] = i + 1 (plain stores: of two equal seeds one loses, which the sampling kernels see),
 //                       blk_row_pointers[i] = min(degree, fanout)
 //   scan_* kernels      (gnna_transpose.hip) exclusive scan of those counts = where every row's picks start
-//   sample_rows_kernel  one segment of L = 4 .. 64 lanes per row: the fanout-th smallest key by a most-significant-bit-first
-//                       search (per bit: ballot + popcount of "agrees with the prefix and has this bit clear", keys recomputed),
-//                       then the picks in position order by a ballot prefix; only the picks read column_index.  Marks the
-//                       picked global ids that are not seeds in mark[].
-//   sample_long_kernel  the same for rows beyond kLongRow positions, a whole block per row (counts through LDS)
+//   sample_rows_kernel  one group of L = 4 .. 64 lanes per row, by the walks of gnna_rowwalk.h: the fanout-th smallest key by a
+//                       most-significant-bit-first search (select_kth: per bit a ballot + popcount of "agrees with the prefix and
+//                       has this bit clear", keys recomputed), then the picks in position order by a ballot prefix
+//                       (place_by_ballot); only the picks read column_index.  Marks the picked global ids that are not seeds
+//                       in mark[].
+//   sample_long_kernel  the same for rows beyond kLongRow positions, a whole block per row (gnna_rowwalk.h's long-row walk: a
+//                       quarter of the row per wavefront, counts through LDS)
 //   scan_* kernels      exclusive scan of mark[] = the rank of every non-seed source in increasing global id
 //   relabel_kernel      src_nodes, global -> local ids in place, counts
 //   part_count_kernel   (gnna_transpose.hip), the scan, part_fill_kernel: the partition of blk_row_pointers by the one rule of
@@ -26,6 +28,7 @@
 #include "gnna_device.h"
 #include "gnna_internal.h"
 #include "gnna_parts.h"
+#include "gnna_rowwalk.h"
 
 namespace gnna {
 namespace {
@@ -93,162 +96,74 @@ __device__ __forceinline__ void emit_pick(const SampleArgs &a, int64_t pos, int6
     }
 }
 
-__device__ __forceinline__ int wave_max(int v)
-{
-    for (int d = 32; d > 0; d >>= 1) v = max(v, __shfl_xor(v, d));
-    return v;
-}
-
-// L lanes per row (a power of two, 4 .. 64), 256 / L rows per block.  Every loop bound is uniform over the wavefront: all 64
-// lanes reach every ballot.
+// L lanes per row (gnna_rowwalk.h), 256 / L rows per block: the fanout-th smallest key of a row with more than `fanout`
+// positions, then the picks in position order.
 __global__ void __launch_bounds__(kBlock)
 sample_rows_kernel(const SampleArgs a, int L)
 {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int lis = lane & (L - 1);
-    const unsigned long long segmask = (L == kWave ? ~0ull : ((1ull << L) - 1ull)) << (lane & ~(L - 1));
-    const unsigned long long below = segmask & ((1ull << lane) - 1ull);
-    const int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / L;
+    const LaneGroup g(L);
+    const int64_t i = g.row;
     int64_t start = 0, out0 = 0;
     int d = 0;
     if (i < a.num_seeds) {
         const int32_t r = a.seeds[i];
         if ((uint32_t)r < a.num_nodes) {
-            if (lis == 0 && a.seedpos[r] != (int32_t)(i + 1)) a.rec[REC_DUP_SEED] = i + 1;
+            if (g.lis == 0 && a.seedpos[r] != (int32_t)(i + 1)) a.rec[REC_DUP_SEED] = i + 1;
             d = row_extent(a.rp, r, &start);
             out0 = a.blk_rp[i];
             if (d > kLongRow) d = 0;                          // sample_long_kernel's
         }
     }
     const bool select = a.fanout > 0 && d > a.fanout;
-    // the fanout-th smallest key of the row: after bit b, `m` keys agree with `prefix` on bits 63 .. b and the wanted key is
-    // the k-th smallest of them; m == 1: it is found, and the picks are the keys with (key >> b) <= (prefix >> b)
-    uint64_t prefix = 0;
-    int k = a.fanout, m = select ? d : 0, sh = 0;
-    const int rounds_sel = wave_max(select ? (d + L - 1) / L : 0);
-    for (int b = 63; b >= 0; b--) {
-        const bool act = m > 1;
-        if (!__any(act)) break;
-        int c0 = 0;
-        for (int j = 0; j < rounds_sel; j++) {
-            const int t = j * L + lis;
-            bool p = false;
-            if (act && t < d) p = ((key_of_position(a.rng_seed, start + t) ^ prefix) >> b) == 0;
-            c0 += __popcll(__ballot(p) & segmask);
-        }
-        if (act) {
-            if (k <= c0) {
-                m = c0;
-            } else {
-                k -= c0;
-                m -= c0;
-                prefix |= 1ull << b;
-            }
-            sh = b;
-        }
-    }
-    const int rounds = wave_max((d + L - 1) / L);
-    int written = 0;
-    for (int j = 0; j < rounds; j++) {
-        const int t = j * L + lis;
-        bool p = false;
-        if (t < d) p = !select || (key_of_position(a.rng_seed, start + t) >> sh) <= (prefix >> sh);
-        const unsigned long long picks = __ballot(p) & segmask;
-        if (p) emit_pick(a, out0 + written + __popcll(picks & below), start + t);
-        written += __popcll(picks);
-    }
+    const Selection sel = select_kth(g, d, a.fanout, select ? d : 0, [&](int t, uint64_t *key) {
+        *key = key_of_position(a.rng_seed, start + t);
+        return true;
+    });
+    place_by_ballot(
+        g, d, out0, [&](int t) { return !select || sel.keeps(key_of_position(a.rng_seed, start + t)); },
+        [&](int64_t pos, int t) { emit_pick(a, pos, start + t); });
 }
 
 // Block b looks at seeds [256 b, 256 b + 256) and samples the rows among them that have more than kLongRow positions, one
-// after another with all 256 threads.
+// after another with all 256 threads: every wavefront counts and compacts one contiguous quarter of the row.
 __global__ void __launch_bounds__(kBlock)
 sample_long_kernel(const SampleArgs a)
 {
-    __shared__ unsigned long long s_long[kWavesPerBlock];
-    __shared__ int s_cnt[kWavesPerBlock];
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    {
-        const int64_t i = (int64_t)blockIdx.x * kBlock + tid;
-        bool is_long = false;
-        if (i < a.num_seeds) {
-            const int32_t r = a.seeds[i];
-            if ((uint32_t)r < a.num_nodes) {
-                int64_t start;
-                is_long = row_extent(a.rp, r, &start) > kLongRow;
-            }
-        }
-        const unsigned long long mine = __ballot(is_long);
-        if (lane == 0) s_long[wave] = mine;
-    }
-    __syncthreads();
-    for (int w = 0; w < kWavesPerBlock; w++) {
-        unsigned long long todo = s_long[w];
-        while (todo) {
-            const int bitpos = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            const int64_t i = (int64_t)blockIdx.x * kBlock + w * kWave + bitpos;
-            const int32_t r = a.seeds[i];
-            if (tid == 0 && a.seedpos[r] != (int32_t)(i + 1)) a.rec[REC_DUP_SEED] = i + 1;
+    __shared__ LongRowLds lds;
+    const LaneGroup g(kWave);
+    const int64_t mine_i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    bool is_long = false;
+    if (mine_i < a.num_seeds) {
+        const int32_t r = a.seeds[mine_i];
+        if ((uint32_t)r < a.num_nodes) {
             int64_t start;
-            const int d = row_extent(a.rp, r, &start);
-            const int64_t out0 = a.blk_rp[i];
-            const bool select = a.fanout > 0 && d > a.fanout;
-            uint64_t prefix = 0;
-            int sh = 0;
-            if (select) {
-                int k = a.fanout, m = d;
-                for (int b = 63; b >= 0 && m > 1; b--) {
-                    int c = 0;
-                    for (int base = 0; base < d; base += kBlock) {
-                        const int t = base + tid;
-                        const bool p = t < d && ((key_of_position(a.rng_seed, start + t) ^ prefix) >> b) == 0;
-                        c += __popcll(__ballot(p));
-                    }
-                    __syncthreads();                           // (the previous readers of s_cnt are done)
-                    if (lane == 0) s_cnt[wave] = c;
-                    __syncthreads();
-                    int c0 = 0;
-#pragma unroll
-                    for (int v = 0; v < kWavesPerBlock; v++) c0 += s_cnt[v];
-                    if (k <= c0) {
-                        m = c0;
-                    } else {
-                        k -= c0;
-                        m -= c0;
-                        prefix |= 1ull << b;
-                    }
-                    sh = b;
-                }
-            }
-            // every wavefront compacts one contiguous quarter of the row: count, exchange, write
-            const int chunk = ((d + kBlock - 1) / kBlock) * kWave;
-            const int lo = min(d, wave * chunk), hi = min(d, lo + chunk);
-            int mine = hi - lo;
-            if (select) {
-                mine = 0;
-                for (int base = lo; base < hi; base += kWave) {
-                    const int t = base + lane;
-                    const bool p = t < hi && (key_of_position(a.rng_seed, start + t) >> sh) <= (prefix >> sh);
-                    mine += __popcll(__ballot(p));
-                }
-            }
-            __syncthreads();
-            if (lane == 0) s_cnt[wave] = mine;
-            __syncthreads();
-            int64_t pos = out0;
-#pragma unroll
-            for (int v = 0; v < kWavesPerBlock; v++)
-                if (v < wave) pos += s_cnt[v];
-            for (int base = lo; base < hi; base += kWave) {
-                const int t = base + lane;
-                const bool p = t < hi && (!select || (key_of_position(a.rng_seed, start + t) >> sh) <= (prefix >> sh));
-                const unsigned long long picks = __ballot(p);
-                if (p) emit_pick(a, pos + __popcll(picks & below), start + t);
-                pos += __popcll(picks);
-            }
+            is_long = row_extent(a.rp, r, &start) > kLongRow;
         }
     }
+    for_each_flagged(lds, is_long, [&](int slot, int) {
+        const int64_t i = (int64_t)blockIdx.x * kBlock + slot;
+        const int32_t r = a.seeds[i];
+        if (threadIdx.x == 0 && a.seedpos[r] != (int32_t)(i + 1)) a.rec[REC_DUP_SEED] = i + 1;
+        int64_t start;
+        const int d = row_extent(a.rp, r, &start);
+        const Quarter q = my_quarter(d);
+        const int64_t first = start + q.lo;
+        const bool select = a.fanout > 0 && d > a.fanout;
+        Selection sel{0, 0};
+        int mine = q.hi - q.lo;
+        if (select) {
+            int k = a.fanout, m = d;
+            for (int b = 63; b >= 0 && m > 1; b--) {
+                const int c = count_by_ballot(g, q.hi - q.lo, [&](int t) { return sel.agrees(key_of_position(a.rng_seed, first + t), b); });
+                select_step(b, exchange_counts(lds, c).total, &k, &m, &sel);
+            }
+            mine = count_by_ballot(g, q.hi - q.lo, [&](int t) { return sel.keeps(key_of_position(a.rng_seed, first + t)); });
+        }
+        const int64_t pos = a.blk_rp[i] + exchange_counts(lds, mine).before;
+        place_by_ballot(
+            g, q.hi - q.lo, pos, [&](int t) { return !select || sel.keeps(key_of_position(a.rng_seed, first + t)); },
+            [&](int64_t at, int t) { emit_pick(a, at, first + t); });
+    });
 }
 
 // rank[v] (the scanned mark[]) = picked non-seed ids below v; rank[v + 1] > rank[v]: v is one of them.
@@ -311,13 +226,11 @@ int gnna_sample_neighbors_i32(const int32_t *row_pointers, const int32_t *column
     if (!counts || !blk_row_pointers || (num_seeds > 0 && (!seeds || !row_pointers)) || (edge_capacity > 0 && !blk_column_index) ||
         (src_capacity > 0 && !src_nodes))
         return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
-    if ((part2Node && !partPtr) || (partPtr && !part2Node && edge_capacity > 0))
-        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: partPtr and part2Node come together", what);
-    if (partPtr && partSize <= 0)
-        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: partSize must be positive when a partition is asked for (got %d)", what, partSize);
+    int rc = check_part_outputs(what, partPtr, part2Node, partSize, edge_capacity);
+    if (rc != GNNA_OK) return rc;
     if (num_nodes >= 0x7fffffffLL || num_seeds >= 0x7fffffffLL) return fail(GNNA_ERR_UNSUPPORTED, "%s: more than 2^31 - 2 rows", what);
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    int rc = refuse_capture(what, stream);
+    rc = refuse_capture(what, stream);
     if (rc != GNNA_OK) return rc;
     DeviceState *ds = nullptr;
     rc = get_device_state(&ds);

@@ -7,13 +7,14 @@
 //   clear_kernel            (gnna_transpose.hip) the record and counts[N + 1]
 //   check_segments_kernel   the first segment whose clamped pointers decrease, into the record
 //   radius_rows_kernel<0>   count pass over the rows of segments of up to kLongRows rows, L = 4 .. 64 lanes per row: the
-//                           candidates of a lane group's row counted by ballot + popcount
+//                           candidates of a lane group's row counted by ballot + popcount (the lane groups of gnna_rowwalk.h)
 //   radius_tiles_kernel<0>  count pass over the rows of longer segments: a workgroup per tile of 256 destination rows, a row per
 //                           lane, source tiles staged in LDS as structure-of-arrays (returns at once when no segment is long)
 //   total_kernel            nnz' in 64 bits (an integer sum: the same whatever the order)
 //   scan_* kernels          (gnna_transpose.hip) exclusive scan of the counts = the row pointers
 //   radius_rows_kernel<1>   fill pass: the same walks; under a cap a row with more candidates than the cap first finds its
-//   radius_tiles_kernel<1>  cap-th smallest key most-significant-bit first over recomputed keys; every kept neighbour is placed by
+//   radius_tiles_kernel<1>  cap-th smallest key most-significant-bit first over recomputed keys (both kernels search with
+//                           gnna_rowwalk.h's Selection and select_step, each over its own layout of a row); every kept neighbour is placed by
 //                           the ballot's prefix (rows kernel) or the lane's own counter (tiles kernel): increasing j, no sort.
 //                           Both write nothing but row_pointers when the capacity is too small
 //   part_count_kernel       (gnna_transpose.hip), the scan, part_fill_kernel: the partition by the one rule of gnna_parts.h
@@ -26,6 +27,7 @@
 #include "gnna_gat_common.h"     // gat::check_alias
 #include "gnna_internal.h"
 #include "gnna_parts.h"
+#include "gnna_rowwalk.h"
 #include "gnna_segments.h"
 #include "gnna_spatial.h"
 
@@ -88,25 +90,6 @@ __device__ __forceinline__ void emit_neighbor(const SpatialArgs &a, int64_t at, 
     }
 }
 
-__device__ __forceinline__ int wave_max(int v)
-{
-    for (int d = 32; d > 0; d >>= 1) v = max(v, __shfl_xor(v, d));
-    return v;
-}
-
-// One step of the most-significant-bit-first search for the k-th smallest of m keys that agree with `prefix` above bit b, c0 of
-// them with bit b clear (sample_rows_kernel's step).
-__device__ __forceinline__ void select_step(int b, int c0, int *k, int *m, uint64_t *prefix)
-{
-    if (*k <= c0) {
-        *m = c0;
-    } else {
-        *k -= c0;
-        *m -= c0;
-        *prefix |= 1ull << b;
-    }
-}
-
 __global__ void __launch_bounds__(kBlock)
 check_segments_kernel(const int32_t *__restrict__ gp, int64_t G, int64_t N, long long *__restrict__ rec)
 {
@@ -128,18 +111,16 @@ total_kernel(const int32_t *__restrict__ cnt, int64_t N, long long *__restrict__
 
 // ---- short segments: L lanes per row ------------------------------------------------------------------------------------------
 
-// L lanes per row (a power of two, 4 .. 64), 256 / L rows per block, rows 0 .. N: many segments share a workgroup.  Every loop
-// bound is uniform over the wavefront: all 64 lanes reach every ballot.  FILL = false: cnt[i] = the neighbours row i keeps (0 for
-// row N; a row of a long segment is radius_tiles_kernel's).  FILL = true: the neighbours, and the caller's row pointers.
+// L lanes per row (gnna_rowwalk.h), 256 / L rows per block, rows 0 .. N: many segments share a workgroup.  FILL = false:
+// cnt[i] = the neighbours row i keeps (0 for row N; a row of a long segment is radius_tiles_kernel's).  FILL = true: the
+// neighbours, and the caller's row pointers.
 template <bool FILL>
 __global__ void __launch_bounds__(kBlock)
 radius_rows_kernel(const SpatialArgs a, int L)
 {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int lis = lane & (L - 1);
-    const unsigned long long segmask = (L == kWave ? ~0ull : ((1ull << L) - 1ull)) << (lane & ~(L - 1));
-    const unsigned long long below = segmask & ((1ull << lane) - 1ull);
-    const int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / L;
+    const LaneGroup g(L);
+    const int lis = g.lis;
+    const int64_t i = g.row;
     int64_t out0 = 0;
     if (FILL) {
         if (i <= a.N) {
@@ -165,8 +146,11 @@ radius_rows_kernel(const SpatialArgs a, int L)
         }
     }
     if (!FILL && is_long && lis == 0) a.rec[REC_LONG] = 1;      // (plain stores of one value)
+    // This kernel walks its rounds itself and not through place_by_ballot / select_kth: with a cap those were 4 % slower per call
+    // (profiles/rowwalk/README.md).  It keeps the first round's key in a register, found by the round and not by the position: a
+    // segment of up to L rows computes every distance once per pass.  Every loop bound is a wave_max: all 64 lanes reach every
+    // ballot.
     const int rounds = wave_max((d + L - 1) / L);
-    // the first round's key stays in a register: a segment of up to L rows computes every distance once per pass
     const uint64_t key0 = lis < d ? candidate_key(a, i, s + lis) : kNoKey;
     auto key_at = [&](int j) -> uint64_t {
         if (j == 0) return key0;
@@ -175,16 +159,15 @@ radius_rows_kernel(const SpatialArgs a, int L)
     };
     int cnt = 0;
     if (!FILL || a.cap > 0)
-        for (int j = 0; j < rounds; j++) cnt += __popcll(__ballot(key_at(j) != kNoKey) & segmask);
+        for (int j = 0; j < rounds; j++) cnt += __popcll(__ballot(key_at(j) != kNoKey) & g.segmask);
     if (!FILL) {
         if (lis == 0 && i <= a.N && !is_long) a.cnt[i] = a.cap > 0 ? min(cnt, a.cap) : cnt;
         return;
     }
-    // the cap-th smallest key of the row: after bit b, `m` keys agree with `prefix` on bits 63 .. b and the wanted key is the
-    // k-th smallest of them; m == 1: it is found, and the kept keys are those with (key >> b) <= (prefix >> b)
+    // a row with more candidates than the cap keeps the keys up to its cap-th smallest
     const bool select = a.cap > 0 && cnt > a.cap;
-    uint64_t prefix = 0;
-    int k = a.cap, m = select ? cnt : 0, sh = 0;
+    Selection sel{0, 0};
+    int k = a.cap, m = select ? cnt : 0;
     const int rounds_sel = wave_max(select ? (d + L - 1) / L : 0);
     for (int b = 63; b >= 0; b--) {
         const bool act = m > 1;
@@ -192,19 +175,16 @@ radius_rows_kernel(const SpatialArgs a, int L)
         int c0 = 0;
         for (int j = 0; j < rounds_sel; j++) {
             const uint64_t key = act ? key_at(j) : kNoKey;
-            c0 += __popcll(__ballot(key != kNoKey && ((key ^ prefix) >> b) == 0) & segmask);
+            c0 += __popcll(__ballot(key != kNoKey && sel.agrees(key, b)) & g.segmask);
         }
-        if (act) {
-            select_step(b, c0, &k, &m, &prefix);
-            sh = b;
-        }
+        if (act) select_step(b, c0, &k, &m, &sel);
     }
     int written = 0;
     for (int j = 0; j < rounds; j++) {
         const uint64_t key = key_at(j);
-        const bool p = key != kNoKey && (!select || (key >> sh) <= (prefix >> sh));
-        const unsigned long long picks = __ballot(p) & segmask;
-        if (p) emit_neighbor(a, out0 + written + __popcll(picks & below), key);
+        const bool p = key != kNoKey && (!select || sel.keeps(key));
+        const unsigned long long picks = __ballot(p) & g.segmask;
+        if (p) emit_neighbor(a, out0 + written + __popcll(picks & g.below), key);
         written += __popcll(picks);
     }
 }
@@ -287,21 +267,18 @@ radius_tiles_kernel(const SpatialArgs a)
             continue;
         }
         const bool select = mine && a.cap > 0 && cnt > a.cap;
-        uint64_t prefix = 0;
-        int k = a.cap, m = select ? cnt : 0, sh = 0;
+        Selection sel{0, 0};
+        int k = a.cap, m = select ? cnt : 0;
         for (int b = 63; b >= 0; b--) {
             const bool act = m > 1;
             if (!__syncthreads_or(act)) break;
             int c0 = 0;
-            sweep_segment(a, s_pos, s, e, i, act, [&](uint64_t key) { c0 += ((key ^ prefix) >> b) == 0; });
-            if (act) {
-                select_step(b, c0, &k, &m, &prefix);
-                sh = b;
-            }
+            sweep_segment(a, s_pos, s, e, i, act, [&](uint64_t key) { c0 += sel.agrees(key, b); });
+            if (act) select_step(b, c0, &k, &m, &sel);
         }
         int64_t at = mine ? (int64_t)a.cnt[i] : 0;
         sweep_segment(a, s_pos, s, e, i, mine, [&](uint64_t key) {
-            if (!select || (key >> sh) <= (prefix >> sh)) emit_neighbor(a, at++, key);
+            if (!select || sel.keeps(key)) emit_neighbor(a, at++, key);
         });
     }
 }
@@ -347,10 +324,7 @@ int gnna_radius_graph_f32(const float *pos, int64_t ld_pos, int64_t num_rows, in
                     max_neighbors);
     if (!row_pointers || !graph_pointers || (num_rows > 0 && !pos) || (edge_capacity > 0 && !column_index))
         return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
-    if ((part2Node && !partPtr) || (partPtr && !part2Node && edge_capacity > 0))
-        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: partPtr and part2Node come together", what);
-    if (partPtr && partSize <= 0)
-        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: partSize must be positive when a partition is asked for (got %d)", what, partSize);
+    if ((rc = check_part_outputs(what, partPtr, part2Node, partSize, edge_capacity)) != GNNA_OK) return rc;
     {
         const void *const ins[2] = {pos, graph_pointers};
         const void *const outs[5] = {row_pointers, column_index, dist2, partPtr, part2Node};

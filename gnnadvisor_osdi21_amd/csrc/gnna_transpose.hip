@@ -16,8 +16,9 @@
 // The passes ping-pong between library scratch and the two output arrays, so the scratch is 8 bytes per edge (12 when the
 // caller wants no t_perm) plus 1 KiB per tile.
 // The partition = part_count_kernel, the scan, a read-back of the total, part_fill_kernel; the rule is gnna_parts.h's.  Here
-// is also what gnna_sample.hip, gnna_topk.hip and gnna_walk.hip take from gnna_internal.h: the scan, refuse_capture, the clear,
-// the group count of row pointers, the read-back of a call's record and the lanes-per-row choice.
+// is also what gnna_sample.hip, gnna_topk.hip, gnna_walk.hip and gnna_spatial.hip take from gnna_internal.h: the scan,
+// refuse_capture, the check of the optional partition outputs, the clear, the group count of row pointers, the read-back of a
+// call's record and the lanes-per-row choice.
 #include <algorithm>
 
 #include "gnna_device.h"
@@ -276,6 +277,15 @@ int refuse_capture(const char *what, hipStream_t stream)
     if (hipStreamIsCapturing(stream, &cap) != hipSuccess) (void)hipGetLastError();
     if (cap != hipStreamCaptureStatusNone)
         return fail(GNNA_ERR_UNSUPPORTED, "%s reads a count back and cannot run inside a stream capture: call it before capturing", what);
+    return GNNA_OK;
+}
+
+int check_part_outputs(const char *what, const int32_t *partPtr, const int32_t *part2Node, int partSize, int64_t edge_capacity)
+{
+    if ((part2Node && !partPtr) || (partPtr && !part2Node && edge_capacity > 0))
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: partPtr and part2Node come together", what);
+    if (partPtr && partSize <= 0)
+        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: partSize must be positive when a partition is asked for (got %d)", what, partSize);
     return GNNA_OK;
 }
 

@@ -10,7 +10,8 @@
 //   ids_kernel          new_id[N] (the table the passes below look ids up in), kept[a] = S[a], sub_nodes, the caller's new_id
 //   cut_rows_kernel<0>  count pass over the KEPT rows, L = 4 .. 64 lanes per row: column_index coalesced, every id looked up in
 //   cut_long_kernel<0>  new_id, survivors counted by ballot + popcount (a whole block for a row beyond kLongRow positions, up to
-//                       64 blocks sharing the long rows of 256 kept rows);
+//                       64 blocks sharing the long rows of 256 kept rows); both walks are gnna_rowwalk.h's, the survivor test
+//                       and the emit are cut_positions here;
 //                       the counts go where the marks were (rank[] is free once ids_kernel has run)
 //   scan_* kernels      exclusive scan of the counts = the result's row pointers
 //   cut_rows_kernel<1>  fill pass: the same walk, every survivor placed by the ballot's prefix -- position order without a sort.
@@ -24,6 +25,7 @@
 #include "gnna_device.h"
 #include "gnna_internal.h"
 #include "gnna_parts.h"
+#include "gnna_rowwalk.h"
 #include "gnna_walk.h"
 
 namespace gnna {
@@ -147,24 +149,28 @@ __device__ __forceinline__ void emit_edge(const CutArgs &a, int64_t pos, int32_t
     }
 }
 
-__device__ __forceinline__ int wave_max(int v)
+// The survivors among positions [first, first + n) placed from `pos` on (gnna_rowwalk.h), or only counted without FILL; returns
+// their count.  `local` is the survivor's between the placement's question and its emit.
+template <bool FILL>
+__device__ __forceinline__ int cut_positions(const CutArgs &a, const LaneGroup &g, int64_t first, int n, int64_t pos)
 {
-    for (int d = 32; d > 0; d >>= 1) v = max(v, __shfl_xor(v, d));
-    return v;
+    int32_t local;
+    return place_by_ballot(
+        g, n, pos, [&](int t) { return (local = local_of(a, first + t)) >= 0; },
+        [&](int64_t at, int t) {
+            if (FILL) emit_edge(a, at, local, first + t);
+        });
 }
 
-// L lanes per row (a power of two, 4 .. 64), 256 / L rows per block, rows 0 .. M.  Every loop bound is uniform over the
-// wavefront: all 64 lanes reach every ballot.  FILL = false: sub_rp[i] = survivors of row i (0 from |S| on; a long row is
-// cut_long_kernel's).  FILL = true: the survivors, and the caller's row pointers.
+// L lanes per row (gnna_rowwalk.h), 256 / L rows per block, rows 0 .. M.  FILL = false: sub_rp[i] = survivors of row i (0 from
+// |S| on; a long row is cut_long_kernel's).  FILL = true: the survivors, and the caller's row pointers.
 template <bool FILL>
 __global__ void __launch_bounds__(kBlock)
 cut_rows_kernel(const CutArgs a, int L)
 {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int lis = lane & (L - 1);
-    const unsigned long long segmask = (L == kWave ? ~0ull : ((1ull << L) - 1ull)) << (lane & ~(L - 1));
-    const unsigned long long below = segmask & ((1ull << lane) - 1ull);
-    const int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / L;
+    const LaneGroup g(L);
+    const int lis = g.lis;
+    const int64_t i = g.row;
     const int64_t num_kept = a.rec[REC_NODES];
     if (FILL) {
         if (i == 0 && lis == 0) a.rec[REC_NNZ] = a.sub_rp[num_kept];
@@ -182,15 +188,7 @@ cut_rows_kernel(const CutArgs a, int L)
         out0 = a.sub_rp[i];
         if (lis == 0) a.out_rp[i] = (int32_t)out0;
     }
-    const int rounds = wave_max((d + L - 1) / L);
-    int written = 0;
-    for (int j = 0; j < rounds; j++) {
-        const int t = j * L + lis;
-        const int32_t local = t < d ? local_of(a, start + t) : -1;
-        const unsigned long long picks = __ballot(local >= 0) & segmask;
-        if (FILL && local >= 0) emit_edge(a, out0 + written + __popcll(picks & below), local, start + t);
-        written += __popcll(picks);
-    }
+    const int written = cut_positions<FILL>(a, g, start, d, out0);
     if (!FILL && lis == 0 && i <= a.max_rows && !is_long) a.sub_rp[i] = written;
 }
 
@@ -202,64 +200,32 @@ template <bool FILL>
 __global__ void __launch_bounds__(kBlock)
 cut_long_kernel(const CutArgs a, int split)
 {
-    __shared__ unsigned long long s_long[kWavesPerBlock];
-    __shared__ int s_cnt[kWavesPerBlock];
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    const unsigned long long below = (1ull << lane) - 1ull;
+    __shared__ LongRowLds lds;
+    const LaneGroup g(kWave);
     const int64_t num_kept = a.rec[REC_NODES];
     if (FILL && !cut_fits(a, num_kept)) return;
     const int64_t group = blockIdx.x / split;
     const int share = blockIdx.x % split;
-    {
-        const int64_t i = group * kBlock + tid;
-        bool is_long = false;
-        if (i < num_kept) {
-            int64_t start;
-            is_long = row_extent(a.rp, a.kept[i], a.nnz, &start) > kLongRow;
-        }
-        const unsigned long long mine = __ballot(is_long);
-        if (lane == 0) s_long[wave] = mine;
+    const int64_t mine_i = group * kBlock + threadIdx.x;
+    bool is_long = false;
+    if (mine_i < num_kept) {
+        int64_t start;
+        is_long = row_extent(a.rp, a.kept[mine_i], a.nnz, &start) > kLongRow;
     }
-    __syncthreads();
-    int ordinal = 0;                                           // (uniform over the block, like everything that steers it)
-    for (int w = 0; w < kWavesPerBlock; w++) {
-        unsigned long long todo = s_long[w];
-        while (todo) {
-            const int bitpos = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            if (ordinal++ % split != share) continue;
-            const int64_t i = group * kBlock + w * kWave + bitpos;
-            int64_t start;
-            const int d = row_extent(a.rp, a.kept[i], a.nnz, &start);
-            const int chunk = ((d + kBlock - 1) / kBlock) * kWave;
-            const int lo = min(d, wave * chunk), hi = min(d, lo + chunk);
-            int mine = 0;
-            for (int base = lo; base < hi; base += kWave) {
-                const int t = base + lane;
-                mine += __popcll(__ballot(t < hi && local_of(a, start + t) >= 0));
-            }
-            __syncthreads();                                   // (the previous readers of s_cnt are done)
-            if (lane == 0) s_cnt[wave] = mine;
-            __syncthreads();
-            if (!FILL) {
-                if (tid == 0) a.sub_rp[i] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-                continue;
-            }
-            int64_t pos = a.sub_rp[i];
-#pragma unroll
-            for (int v = 0; v < kWavesPerBlock; v++)
-                if (v < wave) pos += s_cnt[v];
-            for (int base = lo; base < hi; base += kWave) {
-                const int t = base + lane;
-                const int32_t local = t < hi ? local_of(a, start + t) : -1;
-                const unsigned long long picks = __ballot(local >= 0);
-                if (local >= 0) emit_edge(a, pos + __popcll(picks & below), local, start + t);
-                pos += __popcll(picks);
-            }
+    for_each_flagged(lds, is_long, [&](int slot, int ordinal) {
+        if (ordinal % split != share) return;
+        const int64_t i = group * kBlock + slot;
+        int64_t start;
+        const int d = row_extent(a.rp, a.kept[i], a.nnz, &start);
+        const Quarter q = my_quarter(d);
+        const QuarterCounts c = exchange_counts(lds, cut_positions<false>(a, g, start + q.lo, q.hi - q.lo, 0));
+        if (!FILL) {
+            if (threadIdx.x == 0) a.sub_rp[i] = c.total;
+            return;
         }
-    }
+        cut_positions<true>(a, g, start + q.lo, q.hi - q.lo, a.sub_rp[i] + c.before);
+    });
 }
-static_assert(kWavesPerBlock == 4, "cut_long_kernel sums four wavefront counts");
 
 // The partition of the result's row pointers (gnna_parts.h), with the number of rows (ids_kernel left it in the record) and of
 // groups read on the device.  sub_rp is a scan: sub_rp[0] = 0, so the closing entry is sub_rp[rows] for no rows as well.
@@ -319,14 +285,12 @@ int gnna_induced_subgraph_i32(const int32_t *row_pointers, const int32_t *column
     if (!counts || !sub_row_pointers || (num_ids > 0 && !nodes) || (num_nodes > 0 && !row_pointers) || (nnz > 0 && !column_index) ||
         (node_capacity > 0 && !sub_nodes) || (edge_capacity > 0 && !sub_column_index))
         return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
-    if ((part2Node && !partPtr) || (partPtr && !part2Node && edge_capacity > 0))
-        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: partPtr and part2Node come together", what);
-    if (partPtr && partSize <= 0)
-        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: partSize must be positive when a partition is asked for (got %d)", what, partSize);
+    int rc = check_part_outputs(what, partPtr, part2Node, partSize, edge_capacity);
+    if (rc != GNNA_OK) return rc;
     if (num_nodes >= 0x7fffffffLL || nnz > 0x7fffffffLL || num_ids >= 0x7fffffffLL)
         return fail(GNNA_ERR_UNSUPPORTED, "%s: more than 2^31 - 2 rows or ids, or 2^31 - 1 edges", what);
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    int rc = refuse_capture(what, stream);
+    rc = refuse_capture(what, stream);
     if (rc != GNNA_OK) return rc;
     DeviceState *ds = nullptr;
     rc = get_device_state(&ds);
