@@ -208,6 +208,14 @@ HEADERS["gnna_spatial.h"] = {
     # dist2, partPtr, part2Node, edge_capacity, counts, stream
     "gnna_radius_graph_f32": (i, [p, i64, i64, i, p, i64, f, i, i, i] + [p] * 5 + [i64, pi64, p]),
 }
+# fused GAT attention by row-owning kernels: no partition, no atomics, the same bits on every run
+HEADERS["gnna_gat_rows.h"] = {
+    # H, ld_h, num_in_rows, el, er, row_pointers, column_index, slope, out, ld_out, lse, num_out_rows, heads, dim, flags, stream
+    "gnna_gat_forward_rows_f32": (i, [p, i64, i64, p, p, p, p, f, p, i64, p, i64, i, i, u, p]),
+    # H, ld_h, num_in_rows, el, er, lse, (Y, ld) (dY, ld), the structure, the transposed structure, slope, dH, ld_dh, d_el, d_er,
+    # num_out_rows, heads, dim, flags, stream
+    "gnna_gat_backward_rows_f32": (i, [p, i64, i64, p, p, p, p, i64, p, i64, p, p, p, p, f, p, i64, p, p, i64, i, i, u, p]),
+}
 del p, i, i64, u, u64, f, s, pd, pi, pi64
 EXPORTS = tuple(HEADERS["gnna.h"])     # users: the build's check of the library, tests/test_host.py
 
@@ -1352,6 +1360,57 @@ def _gat_backward(drop, H, el, er, lse, Y, dY, row_pointers, column_index, part_
     else:
         _call(H.device, "gnna_gat_backward_f32", *head, *outs, n_out, heads, width // heads, part2Node.numel(), int(partSize), 0)
     return dH, d_el, d_er
+
+
+def gat_forward_rows(H, el, er, row_pointers, column_index, negative_slope=0.2, out=None, lse=None, relu=False):
+    """gnna_gat_forward_rows_f32 (include/gnna_gat_rows.h): the function of gat_forward by kernels that own the rows they write --
+    no partition, no atomics, no zero-fill, ONE pass over column_index (the softmax is online); the same bits on every run and
+    accepted under ``set_tuning(deterministic=1)``.  Shapes as gat_forward (square or rectangular).  -> (out, lse)."""
+    _need_device(H, "GAT attention")
+    hp, n_out, n_in, width, heads, ld_h = _gat_sizes(H, el, er, row_pointers)
+    if out is None:
+        out = _fresh_output((n_out, width), H.device)
+    if lse is None:
+        lse = _fresh_output((n_out, heads), H.device)
+    op_, n_o, width_o, ld_out = _rows_view(out, "out")
+    assert n_o == n_out and width_o == width and _node_heads(lse, n_out, "lse") == heads
+    _call(H.device, "gnna_gat_forward_rows_f32", hp, ld_h, n_in, el.data_ptr(), er.data_ptr(), row_pointers.data_ptr(),
+          column_index.data_ptr(), float(negative_slope), op_, ld_out, lse.data_ptr(), n_out, heads, width // heads, _flags(relu=relu))
+    return out, lse
+
+
+def gat_backward_rows(H, el, er, lse, Y, dY, row_pointers, column_index, t_row_pointers, t_column_index, negative_slope=0.2,
+                      dH=None, d_el=None, d_er=None, want=(True, True, True)):
+    """gnna_gat_backward_rows_f32 (include/gnna_gat_rows.h): (dH, d_el, d_er) of gat_forward_rows for the gradient dY of its output
+    Y, without atomics.  The transposed structure (num_in_rows rows) is always given; a graph whose structure is symmetric gives its
+    own arrays twice.  want: which of the three are made -- the others come back None, and a pass none of whose outputs is wanted
+    is not launched."""
+    _need_device(H, "GAT attention")
+    hp, n_out, n_in, width, heads, ld_h = _gat_sizes(H, el, er, row_pointers)
+    yp, n_y, width_y, ld_y = _rows_view(Y, "Y")
+    gp, n_g, width_g, ld_g = _rows_view(dY, "dY")
+    assert _node_heads(lse, n_out, "lse") == heads
+    assert (n_y, width_y) == (n_out, width) and (n_g, width_g) == (n_out, width), "Y and dY must be [num_out_rows, heads * dim]"
+    for t in (row_pointers, column_index, t_row_pointers, t_column_index):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.device == H.device, \
+            "the graph and its transpose must be contiguous int32 tensors on H's device"
+    assert t_row_pointers.numel() == n_in + 1, "transposed: [num_in_rows + 1] row pointers"
+    dp, ld_d = None, width
+    if want[0]:
+        if dH is None:
+            dH = _fresh_output((n_in, width), H.device)
+        dp, n_d, width_d, ld_d = _rows_view(dH, "dH")
+        assert (n_d, width_d) == (n_in, width), "dH must have the shape of H"
+    if want[1] and d_el is None:
+        d_el = _fresh_output((n_out, heads), H.device)
+    if want[2] and d_er is None:
+        d_er = _fresh_output((n_in, heads), H.device)
+    assert (not want[1] or _node_heads(d_el, n_out, "d_el") == heads) and (not want[2] or _node_heads(d_er, n_in, "d_er") == heads)
+    _call(H.device, "gnna_gat_backward_rows_f32", hp, ld_h, n_in, el.data_ptr(), er.data_ptr(), lse.data_ptr(), yp, ld_y, gp, ld_g,
+          row_pointers.data_ptr(), column_index.data_ptr(), t_row_pointers.data_ptr(), t_column_index.data_ptr(),
+          float(negative_slope), dp, ld_d, _ptr(d_el) if want[1] else None, _ptr(d_er) if want[2] else None, n_out, heads,
+          width // heads, 0)
+    return (dH if want[0] else None), (d_el if want[1] else None), (d_er if want[2] else None)
 
 
 def _edge_heads(t, nnz, heads, what):

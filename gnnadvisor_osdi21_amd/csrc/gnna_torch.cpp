@@ -45,6 +45,7 @@
 #include "gnna_walk.h"
 #include "gnna_spatial.h"
 #include "gnna_edgefeat.h"
+#include "gnna_gat_rows.h"
 
 #define CHECK_CUDA(x) TORCH_CHECK(x.is_cuda(), #x " must be a CUDA tensor")
 #define CHECK_CONTIGUOUS(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -1063,6 +1064,66 @@ gat_backward_drop(const torch::Tensor &H, const torch::Tensor &el, const torch::
                             transposed, &drop);
 }
 
+// The rows form of the fused GAT attention (gnna_gat_rows.h): gat_forward / gat_backward by kernels that own the rows they write.
+// The CSR alone is the graph (no partition), and the backward always takes the transposed CSR.
+static void gat_rows_check_csr(const torch::Tensor &H, int64_t rows, const torch::Tensor &row_pointers, const torch::Tensor &column_index)
+{
+    check_ids(row_pointers, "row_pointers");
+    check_ids(column_index, "column_index");
+    TORCH_CHECK(row_pointers.dim() == 1 && row_pointers.size(0) == rows + 1, "row_pointers must be [num_nodes + 1] (", rows + 1,
+                " entries: one more than the rows of the side it walks)");
+    TORCH_CHECK(row_pointers.device() == H.device() && column_index.device() == H.device(), "H and the graph must be on one device");
+}
+
+std::tuple<torch::Tensor, torch::Tensor>
+gat_forward_rows(const torch::Tensor &H_in, const torch::Tensor &el, const torch::Tensor &er, const torch::Tensor &row_pointers,
+                 const torch::Tensor &column_index, double negative_slope)
+{
+    const int heads = gat_heads(H_in, el, er);
+    const int64_t n_in = H_in.size(0), n_out = el.size(0), width = H_in.size(1);
+    const torch::Tensor H = gat_rows(H_in, "H", n_in, width);
+    gat_rows_check_csr(H, n_out, row_pointers, column_index);
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(H.device());
+    auto Y = fresh({n_out, width}, el.options()), lse = fresh({n_out, (int64_t)heads}, el.options());
+    check_rc(gnna_gat_forward_rows_f32(H.data_ptr<float>(), ld_of(H), n_in, el.data_ptr<float>(), er.data_ptr<float>(),
+                                       row_pointers.data_ptr<int32_t>(), softagg_ids(column_index, row_pointers), (float)negative_slope,
+                                       Y.data_ptr<float>(), width, lse.data_ptr<float>(), n_out, heads, (int)(width / heads), 0u,
+                                       current_stream()));
+    return std::make_tuple(Y, lse);
+}
+
+// need = (dH, d_el, d_er) wanted: an output that is not comes back undefined (None), and its pass may not be launched at all
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
+gat_backward_rows(const torch::Tensor &H_in, const torch::Tensor &el, const torch::Tensor &er, const torch::Tensor &lse,
+                  const torch::Tensor &Y_in, const torch::Tensor &dY_in, const torch::Tensor &row_pointers,
+                  const torch::Tensor &column_index, const torch::Tensor &t_row_pointers, const torch::Tensor &t_column_index,
+                  double negative_slope, const std::vector<bool> &need)
+{
+    const int heads = gat_heads(H_in, el, er);
+    const int64_t n_in = H_in.size(0), n_out = el.size(0), width = H_in.size(1);
+    TORCH_CHECK(need.size() == 3, "need must be (dH, d_el, d_er)");
+    const torch::Tensor H = gat_rows(H_in, "H", n_in, width), Y = gat_rows(Y_in, "Y", n_out, width),
+                        dY = gat_rows(dY_in, "dY", n_out, width);
+    check_floats(lse, "lse");
+    TORCH_CHECK(lse.sizes() == el.sizes() && lse.device() == H.device(), "lse must be [num_nodes, heads] (the shape of el) on H's device");
+    TORCH_CHECK(Y.device() == H.device() && dY.device() == H.device(), "H, Y and dY must be on one device");
+    gat_rows_check_csr(H, n_out, row_pointers, column_index);
+    gat_rows_check_csr(H, n_in, t_row_pointers, t_column_index);
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(H.device());
+    torch::Tensor dH, d_el, d_er;
+    if (need[0]) dH = fresh({n_in, width}, el.options());
+    if (need[1]) d_el = fresh({n_out, (int64_t)heads}, el.options());
+    if (need[2]) d_er = fresh({n_in, (int64_t)heads}, el.options());
+    check_rc(gnna_gat_backward_rows_f32(H.data_ptr<float>(), ld_of(H), n_in, el.data_ptr<float>(), er.data_ptr<float>(),
+                                        lse.data_ptr<float>(), Y.data_ptr<float>(), ld_of(Y), dY.data_ptr<float>(), ld_of(dY),
+                                        row_pointers.data_ptr<int32_t>(), softagg_ids(column_index, row_pointers),
+                                        t_row_pointers.data_ptr<int32_t>(), softagg_ids(t_column_index, t_row_pointers),
+                                        (float)negative_slope, need[0] ? dH.data_ptr<float>() : nullptr, width,
+                                        need[1] ? d_el.data_ptr<float>() : nullptr, need[2] ? d_er.data_ptr<float>() : nullptr, n_out,
+                                        heads, (int)(width / heads), 0u, current_stream()));
+    return std::make_tuple(dH, d_el, d_er);
+}
+
 // Fused GAT attention with a per-edge score term (gnna_gat_edge.h): gat_forward_drop / gat_backward_drop with ee [num_edges,
 // heads] (edge-major, indexed like column_index) in the score, its gradient d_ee, and the coefficients edge for edge.
 static void gat_check_edge_term(const torch::Tensor &t, const char *name, const torch::Tensor &column_index, int heads)
@@ -2009,6 +2070,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("part_pointers"), pybind11::arg("part2Node"),
           pybind11::arg("partSize"), pybind11::arg("negative_slope"), pybind11::arg("attn_drop"), pybind11::arg("rng_seed"),
           pybind11::arg("transposed") = pybind11::none());
+    m.def("gat_forward_rows", &gat_forward_rows,
+          "gat_forward by kernels that own the rows they write (extension; gnna_gat_rows.h): no partition, no atomics, one pass over "
+          "column_index, the same bits on every run -> (Y, lse)",
+          pybind11::arg("H"), pybind11::arg("el"), pybind11::arg("er"), pybind11::arg("row_pointers"), pybind11::arg("column_index"),
+          pybind11::arg("negative_slope") = 0.2);
+    m.def("gat_backward_rows", &gat_backward_rows,
+          "gradient of gat_forward_rows -> (dH, d_el, d_er), without atomics (extension; gnna_gat_rows.h).  The transposed CSR is "
+          "always given (a symmetric structure: its own arrays); need = (dH, d_el, d_er) wanted, the others come back None",
+          pybind11::arg("H"), pybind11::arg("el"), pybind11::arg("er"), pybind11::arg("lse"), pybind11::arg("Y"), pybind11::arg("dY"),
+          pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("t_row_pointers"), pybind11::arg("t_column_index"),
+          pybind11::arg("negative_slope") = 0.2, pybind11::arg("need") = std::vector<bool>{true, true, true});
     m.def("gat_edge_forward", &gat_edge_forward,
           "gat_forward_drop with a per-edge score term (extension; gnna_gat_edge.h): z = el[i, h] + er[col(e), h] + ee[e, h]; "
           "ee [num_edges, heads], edge-major, indexed like column_index -> (Y, lse)",

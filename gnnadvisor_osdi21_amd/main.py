@@ -76,8 +76,10 @@ def build_parser():
     p.add_argument('--tune_gemm', default='False', **tf,
                    help="True: let PyTorch's TunableOp time the rocBLAS / hipBLASLt solutions for the layer GEMMs at "
                         "first use (X W and G W^T run 1.3-2x faster; costs 1-2 minutes of set-up, MI355X addition)")
-    p.add_argument('--fused_attention', default='False', **tf,
-                   help="True: --model gat runs both layers on the fused attention kernels (GATConv(fused=True): alpha is made "
+    p.add_argument('--fused_attention', default='False', choices=['True', 'False', 'rows'],
+                   help="rows: --model gat runs both layers on the fused attention by kernels that own the rows they write "
+                        "(GATConv(fused=\"rows\"): no atomics, the same bits on every run; without --attn_drop and --edge_dim).  "
+                        "True: --model gat runs both layers on the fused attention kernels (GATConv(fused=True): alpha is made "
                         "from node-sized values where the rows are gathered, no per-edge tensor; MI355X addition); --model gatv2 likewise "
                         "(GATv2Conv(fused=...): False is the composed path with [nnz, heads * hidden] tensors) and --model transformer "
                         "(TransformerConv(fused=...))")
@@ -161,6 +163,14 @@ def main(argv=None, capture=None):
         raise SystemExit("--single_spmm / --verify_spmm run the float32 entry: use --dtype float32")
     if args.heads < 1:
         raise SystemExit("--heads must be >= 1")
+    fused_rows = args.fused_attention == 'rows'
+    if fused_rows:
+        if args.model != 'gat':
+            raise SystemExit("--fused_attention rows selects the row-owned GAT attention: run it with --model gat (got --model %s)" % args.model)
+        if args.attn_drop != 0.0 or args.edge_dim > 0:
+            raise SystemExit("--fused_attention rows has no attention dropout and no edge features: run --attn_drop / --edge_dim "
+                             "with --fused_attention True")
+        args.fused_attention = 'True'      # everything below that asks for the fused path holds for it
     if flag(args.fused_attention) and not attention:
         raise SystemExit("--fused_attention True selects the fused GAT attention: run it with --model gat (got --model %s)" % args.model)
     if args.attn_drop != 0.0 and not attention:
@@ -362,7 +372,7 @@ def main(argv=None, capture=None):
                 x = self.conv2(x, inputInfo.set_hidden())
                 return F.log_softmax(x.float(), dim=1)
     elif args.model == 'gat':
-        fused = flag(args.fused_attention)
+        fused = "rows" if fused_rows else flag(args.fused_attention)
 
         edge_dim = args.edge_dim if args.edge_dim > 0 else None
 

@@ -1116,6 +1116,9 @@ class GATConv(Module):
     ``directed`` (then it gathers over the transposed structure).
     fused=True: the attention runs on GATAttention instead -- the same function, with alpha made from node-sized values inside
     the gathers: no per-edge tensor, one call for all heads.
+    fused="rows": the fused attention on GATAttentionRows -- kernels that own the rows they write, no atomics, the same bits on
+    every run (reproducible training; accepted under ``_lib.set_tuning(deterministic=1)``).  Everything said of fused=True below
+    holds for it, except that attn_drop > 0 and edge_dim are refused at construction: those stay on fused=True.
     With fused=True `inputInfo` may be a sampling.SampledBlock: X is [num_src, in], H = X W covers all num_src rows, er comes
     from all of H and el from H[:num_dst] (a block's destination rows are its first source rows); the result is
     [num_dst, heads * out] ([num_dst, out] with concat=False).  float32 only.  fused=False refuses a block: the composed path
@@ -1145,6 +1148,12 @@ class GATConv(Module):
             raise ValueError(f"GATConv: attn_drop must be in [0, 1) (got {attn_drop})")
         self.last_rng_seed = None
         self.heads, self.out_dim, self.concat, self.negative_slope = int(heads), int(output_dim), bool(concat), float(negative_slope)
+        self.rows = isinstance(fused, str)       # fused="rows": the fused attention on GATAttentionRows
+        if self.rows and fused != "rows":
+            raise ValueError(f'GATConv: fused must be True, False or "rows" (got {fused!r})')
+        if self.rows and (self.attn_drop > 0.0 or edge_dim is not None):
+            raise ValueError('GATConv(fused="rows") has no attention dropout and no edge features (attn_drop = 0 and edge_dim = None '
+                             f"only; got attn_drop = {attn_drop}, edge_dim = {edge_dim}): those run on fused=True")
         self.fused = bool(fused)
         self.weights = Parameter(torch.empty(input_dim, self.heads * self.out_dim))
         self.att_l = Parameter(torch.empty(self.heads, self.out_dim))
@@ -1205,7 +1214,9 @@ class GATConv(Module):
         el = ((Hh[:n] if block else Hh) * self.att_l).sum(-1)      # [N, heads] ([num_dst, heads]): destination side
         er = (Hh * self.att_r).sum(-1)          # [N, heads] ([num_src, heads]): source side
         weights = None
-        if self.fused and drop:
+        if self.rows:
+            Y = GATAttentionRows.apply(H, el, er, inputInfo, self.negative_slope)
+        elif self.fused and drop:
             seed = _step_seed(self, rng_seed)
             if ee is not None:
                 Y = GATEdgeAttention.apply(H, el, er, ee, inputInfo, self.negative_slope, self.attn_drop, seed)
@@ -2032,3 +2043,7 @@ class GraphNorm(Module):
         if not self.fused:
             return _composed_graph_norm(x, batch, self.weight, self.bias, self.mean_scale, self.eps)
         return SegmentNorm.apply(x, batch, self.weight, self.bias, self.mean_scale, self.eps)
+
+
+# ops.GATAttentionRows: the fused GAT attention by row-owning kernels lives in a module of its own (which reads this one's helpers)
+from .gat_rows import GATAttentionRows  # noqa: E402,F401

@@ -1,0 +1,87 @@
+"""The rows form of the fused GAT attention against the atomic fused path (profiles/gat_rows/):
+
+    python tools/probe_gat_rows.py [--graphs reddit-like,products-like] [--configs 1x64,4x16] [--reps 5] [--rounds 5]
+
+The attention alone, from (H, el, er): "forward" is the forward call, "step" forward + backward to (dH, d_el, d_er), as
+ops.GATAttention ("atomic") and ops.GATAttentionRows ("rows") run them, in ONE process, the two alternated round by round, ms from
+HIP events, median / smallest / largest round.  Then the peak torch memory of one step of either, and how far the outputs of the
+two are apart (relative to the largest |element|).  One JSON line per figure."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from gnnadvisor_osdi21_amd import graph  # noqa: E402
+from probe_gat_fused import Info, timed  # noqa: E402
+
+
+def variants(info, heads, dim, seed=1):
+    from gnnadvisor_osdi21_amd.ops import GATAttention, GATAttentionRows
+    n = info.row_pointers.numel() - 1
+    gen = torch.Generator(device="cuda").manual_seed(seed)
+    H = torch.randn(n, heads * dim, device="cuda", generator=gen).requires_grad_()
+    el = torch.randn(n, heads, device="cuda", generator=gen).requires_grad_()
+    er = torch.randn(n, heads, device="cuda", generator=gen).requires_grad_()
+    G = torch.randn(n, heads * dim, device="cuda", generator=gen)
+    out = {}
+    for name, op in (("atomic", GATAttention), ("rows", GATAttentionRows)):
+        def forward(op=op):
+            with torch.no_grad():
+                return op.apply(H, el, er, info, 0.2)
+
+        def step(op=op):
+            return torch.autograd.grad(op.apply(H, el, er, info, 0.2), (H, el, er), G)
+        out[name] = {"forward": forward, "step": step}
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--graphs", default="reddit-like,products-like")
+    ap.add_argument("--configs", default="1x64,4x16", help="heads x dim, comma separated")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=5)
+    args = ap.parse_args()
+    for name in args.graphs.split(","):
+        g = graph.make_config_graph(name, device="cuda")
+        info = Info(g, 32)
+        head = dict(graph=name, nodes=g.num_nodes, edges=info.column_index.numel(), reps=args.reps, rounds=args.rounds)
+        for cfg in args.configs.split(","):
+            heads, dim = [int(v) for v in cfg.split("x")]
+            v = variants(info, heads, dim)
+            a, r = [(v[k]["forward"](),) + v[k]["step"]() for k in ("atomic", "rows")]      # (also the warm-up: symmetry check, scratch)
+            apart = [float((x - y).abs().max() / x.abs().max()) for x, y in zip(a, r)]
+            print(json.dumps(dict(head, heads=heads, dim=dim, figure="rows vs atomic, max |difference| / max |element| of (Y, dH, "
+                                  "d_el, d_er)", values=[float("%.3g" % x) for x in apart])), flush=True)
+            del a, r
+            for what in ("forward", "step"):
+                ms = {k: [] for k in v}
+                for _ in range(args.rounds):
+                    for k in v:
+                        ms[k].append(timed(v[k][what], args.reps))
+                for k, t in ms.items():
+                    print(json.dumps(dict(head, heads=heads, dim=dim, what=what, variant=k, ms_median=round(statistics.median(t), 4),
+                                          ms_min=round(min(t), 4), ms_max=round(max(t), 4))), flush=True)
+                print(json.dumps(dict(head, heads=heads, dim=dim, what=what, variant="rows / atomic",
+                                      ratio_of_medians=round(statistics.median(ms["rows"]) / statistics.median(ms["atomic"]), 4))), flush=True)
+            for k in v:
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                before = torch.cuda.memory_allocated()
+                timed(v[k]["step"], 1)
+                print(json.dumps(dict(head, heads=heads, dim=dim, variant=k, figure="peak torch memory of one step, MiB",
+                                      peak_mib=round((torch.cuda.max_memory_allocated() - before) / 2 ** 20, 1))), flush=True)
+            del v
+            torch.cuda.empty_cache()
+        del info, g
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
