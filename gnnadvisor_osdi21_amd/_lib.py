@@ -216,6 +216,16 @@ HEADERS["gnna_gat_rows.h"] = {
     # num_out_rows, heads, dim, flags, stream
     "gnna_gat_backward_rows_f32": (i, [p, i64, i64, p, p, p, p, i64, p, i64, p, p, p, p, f, p, i64, p, p, i64, i, i, u, p]),
 }
+# fused dot-product attention by row-owning kernels: one-pass forward, no partition, no atomics, the same bits on every run
+HEADERS["gnna_dot_rows.h"] = {
+    # Q, ld_q, K, ld_k, V, ld_v, num_in_rows, row_pointers, column_index, scale, attn_drop, rng_seed, out, ld_out, lse, num_out_rows,
+    # heads, dim, flags, stream
+    "gnna_dot_attn_forward_rows_f32": (i, [p, i64] * 3 + [i64, p, p, f, f, u64, p, i64, p, i64, i, i, u, p]),
+    # Q, ld_q, K, ld_k, V, ld_v, num_in_rows, lse, (Y, ld) (dY, ld), the structure, the transposed structure, scale, attn_drop,
+    # rng_seed, (dQ, ld) (dK, ld) (dV, ld), num_out_rows, heads, dim, flags, stream
+    "gnna_dot_attn_backward_rows_f32": (i, [p, i64] * 3 + [i64, p, p, i64, p, i64, p, p, p, p, f, f, u64] + [p, i64] * 3 +
+                                        [i64, i, i, u, p]),
+}
 del p, i, i64, u, u64, f, s, pd, pi, pi64
 EXPORTS = tuple(HEADERS["gnna.h"])     # users: the build's check of the library, tests/test_host.py
 
@@ -1653,6 +1663,64 @@ def dot_attn_backward(Q, K, V, heads, lse, Y, dY, row_pointers, column_index, pa
           float(attn_drop), int(rng_seed), dqp, ld_dq, dkp, ld_dk, dvp, ld_dv, n_out, n_in, heads, width // heads,
           int(partSize), 0)
     return dQ, dK, dV
+
+
+def dot_attn_forward_rows(Q, K, V, heads, row_pointers, column_index, scale=None, attn_drop=0.0, rng_seed=0, out=None, lse=None,
+                          relu=False):
+    """gnna_dot_attn_forward_rows_f32 (include/gnna_dot_rows.h): the function of dot_attn_forward by kernels that own the rows they
+    write -- no partition, no atomics, no zero-fill, ONE pass over column_index in which K[j] and V[j] are gathered once each (the
+    softmax is online); the same bits on every run and accepted under ``set_tuning(deterministic=1)``.  Shapes, strided views,
+    scale and the mask as dot_attn_forward.  -> (out, lse)."""
+    _need_device(Q, "dot-product attention")
+    qp, ld_q, kp, ld_k, vp, ld_v, n_out, n_in, width = _dot_attn_sizes(Q, K, V, heads, row_pointers)
+    heads = int(heads)
+    if scale is None:
+        scale = 1.0 / math.sqrt(width // heads)
+    if out is None:
+        out = _fresh_output((n_out, width), Q.device)
+    if lse is None:
+        lse = _fresh_output((n_out, heads), Q.device)
+    op_, n_o, width_o, ld_out = _rows_view(out, "out")
+    assert n_o == n_out and width_o == width and _node_heads(lse, n_out, "lse") == heads
+    _call(Q.device, "gnna_dot_attn_forward_rows_f32", qp, ld_q, kp, ld_k, vp, ld_v, n_in, row_pointers.data_ptr(),
+          column_index.data_ptr(), float(scale), float(attn_drop), int(rng_seed), op_, ld_out, lse.data_ptr(), n_out, heads,
+          width // heads, _flags(relu=relu))
+    return out, lse
+
+
+def dot_attn_backward_rows(Q, K, V, heads, lse, Y, dY, row_pointers, column_index, t_row_pointers, t_column_index, scale=None,
+                           attn_drop=0.0, rng_seed=0, dQ=None, dK=None, dV=None, want=(True, True, True)):
+    """gnna_dot_attn_backward_rows_f32 (include/gnna_dot_rows.h): (dQ, dK, dV) of dot_attn_forward_rows for the gradient dY of its
+    output Y (same scale, attn_drop and rng_seed), without atomics.  The transposed structure (num_in_rows rows) is always given; a
+    graph whose structure is symmetric gives its own arrays twice.  want: which of the three are made -- the others come back
+    None, and a pass none of whose outputs is wanted is not launched."""
+    _need_device(Q, "dot-product attention")
+    qp, ld_q, kp, ld_k, vp, ld_v, n_out, n_in, width = _dot_attn_sizes(Q, K, V, heads, row_pointers)
+    heads = int(heads)
+    if scale is None:
+        scale = 1.0 / math.sqrt(width // heads)
+    yp, n_y, width_y, ld_y = _rows_view(Y, "Y")
+    gp, n_g, width_g, ld_g = _rows_view(dY, "dY")
+    assert _node_heads(lse, n_out, "lse") == heads
+    assert (n_y, width_y) == (n_out, width) and (n_g, width_g) == (n_out, width), "Y and dY must be [num_out_rows, heads * dim]"
+    for t in (row_pointers, column_index, t_row_pointers, t_column_index):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.device == Q.device, \
+            "the graph and its transpose must be contiguous int32 tensors on Q's device"
+    assert t_row_pointers.numel() == n_in + 1, "transposed: [num_in_rows + 1] row pointers"
+    outs, args = [], []
+    for wanted, t, rows, name in zip(want, (dQ, dK, dV), (n_out, n_in, n_in), ("dQ", "dK", "dV")):
+        ptr, ld = None, width
+        if wanted:
+            if t is None:
+                t = _fresh_output((rows, width), Q.device)
+            ptr, n_t, width_t, ld = _rows_view(t, name)
+            assert (n_t, width_t) == (rows, width), "dQ / dK / dV must have the shapes of Q / K / V"
+        outs.append(t if wanted else None)
+        args += [ptr, ld]
+    _call(Q.device, "gnna_dot_attn_backward_rows_f32", qp, ld_q, kp, ld_k, vp, ld_v, n_in, lse.data_ptr(), yp, ld_y, gp, ld_g,
+          row_pointers.data_ptr(), column_index.data_ptr(), t_row_pointers.data_ptr(), t_column_index.data_ptr(), float(scale),
+          float(attn_drop), int(rng_seed), *args, n_out, heads, width // heads, 0)
+    return tuple(outs)
 
 
 def _device_i32(t, what):

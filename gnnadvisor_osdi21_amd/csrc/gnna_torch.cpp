@@ -46,6 +46,7 @@
 #include "gnna_spatial.h"
 #include "gnna_edgefeat.h"
 #include "gnna_gat_rows.h"
+#include "gnna_dot_rows.h"
 
 #define CHECK_CUDA(x) TORCH_CHECK(x.is_cuda(), #x " must be a CUDA tensor")
 #define CHECK_CONTIGUOUS(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -1362,6 +1363,59 @@ dot_attn_backward(const torch::Tensor &Q_in, const torch::Tensor &K_in, const to
     return std::make_tuple(dQ, dK, dV);
 }
 
+// The rows form of the fused dot-product attention (gnna_dot_rows.h): dot_attn_forward / dot_attn_backward by kernels that own the
+// rows they write.  The CSR alone is the graph (no partition), and the backward always takes the transposed CSR.
+std::tuple<torch::Tensor, torch::Tensor>
+dot_attn_forward_rows(const torch::Tensor &Q_in, const torch::Tensor &K_in, const torch::Tensor &V_in, int64_t heads,
+                      const torch::Tensor &row_pointers, const torch::Tensor &column_index, double scale, double attn_drop,
+                      uint64_t rng_seed)
+{
+    dot_attn_shapes(Q_in, K_in, V_in, heads, scale);
+    const int64_t n_in = K_in.size(0), n_out = Q_in.size(0), width = Q_in.size(1);
+    const torch::Tensor Q = gat_rows(Q_in, "Q", n_out, width), K = gat_rows(K_in, "K", n_in, width), V = gat_rows(V_in, "V", n_in, width);
+    gat_rows_check_csr(Q, n_out, row_pointers, column_index);
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(Q.device());
+    auto Y = fresh({n_out, width}, Q.options()), lse = fresh({n_out, heads}, Q.options());
+    check_rc(gnna_dot_attn_forward_rows_f32(Q.data_ptr<float>(), ld_of(Q), K.data_ptr<float>(), ld_of(K), V.data_ptr<float>(), ld_of(V),
+                                            n_in, row_pointers.data_ptr<int32_t>(), softagg_ids(column_index, row_pointers),
+                                            (float)scale, (float)attn_drop, rng_seed, Y.data_ptr<float>(), width, lse.data_ptr<float>(),
+                                            n_out, (int)heads, (int)(width / heads), 0u, current_stream()));
+    return std::make_tuple(Y, lse);
+}
+
+// need = (dQ, dK, dV) wanted: an output that is not comes back undefined (None), and its pass may not be launched at all
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
+dot_attn_backward_rows(const torch::Tensor &Q_in, const torch::Tensor &K_in, const torch::Tensor &V_in, int64_t heads,
+                       const torch::Tensor &lse, const torch::Tensor &Y_in, const torch::Tensor &dY_in, const torch::Tensor &row_pointers,
+                       const torch::Tensor &column_index, const torch::Tensor &t_row_pointers, const torch::Tensor &t_column_index,
+                       double scale, double attn_drop, uint64_t rng_seed, const std::vector<bool> &need)
+{
+    dot_attn_shapes(Q_in, K_in, V_in, heads, scale);
+    const int64_t n_in = K_in.size(0), n_out = Q_in.size(0), width = Q_in.size(1);
+    TORCH_CHECK(need.size() == 3, "need must be (dQ, dK, dV)");
+    const torch::Tensor Q = gat_rows(Q_in, "Q", n_out, width), K = gat_rows(K_in, "K", n_in, width), V = gat_rows(V_in, "V", n_in, width),
+                        Y = gat_rows(Y_in, "Y", n_out, width), dY = gat_rows(dY_in, "dY", n_out, width);
+    check_floats(lse, "lse");
+    TORCH_CHECK(lse.dim() == 2 && lse.size(0) == n_out && lse.size(1) == heads && lse.device() == Q.device(),
+                "lse must be [num_out_rows, heads] on Q's device");
+    TORCH_CHECK(Y.device() == Q.device() && dY.device() == Q.device(), "Q, Y and dY must be on one device");
+    gat_rows_check_csr(Q, n_out, row_pointers, column_index);
+    gat_rows_check_csr(Q, n_in, t_row_pointers, t_column_index);
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(Q.device());
+    torch::Tensor dQ, dK, dV;
+    if (need[0]) dQ = fresh({n_out, width}, Q.options());
+    if (need[1]) dK = fresh({n_in, width}, Q.options());
+    if (need[2]) dV = fresh({n_in, width}, Q.options());
+    check_rc(gnna_dot_attn_backward_rows_f32(Q.data_ptr<float>(), ld_of(Q), K.data_ptr<float>(), ld_of(K), V.data_ptr<float>(), ld_of(V),
+                                             n_in, lse.data_ptr<float>(), Y.data_ptr<float>(), ld_of(Y), dY.data_ptr<float>(), ld_of(dY),
+                                             row_pointers.data_ptr<int32_t>(), softagg_ids(column_index, row_pointers),
+                                             t_row_pointers.data_ptr<int32_t>(), softagg_ids(t_column_index, t_row_pointers),
+                                             (float)scale, (float)attn_drop, rng_seed, need[0] ? dQ.data_ptr<float>() : nullptr, width,
+                                             need[1] ? dK.data_ptr<float>() : nullptr, width, need[2] ? dV.data_ptr<float>() : nullptr,
+                                             width, n_out, (int)heads, (int)(width / heads), 0u, current_stream()));
+    return std::make_tuple(dQ, dK, dV);
+}
+
 // SDDMM (gnna_sddmm_ld_f32): edge_out[e] = <A[row(e)], B[column_index[e]]>; A and B may be row-strided views.
 torch::Tensor sddmm(const torch::Tensor &A, const torch::Tensor &B, const torch::Tensor &column_index,
                     const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize)
@@ -2129,6 +2183,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           pybind11::arg("dY"), pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("part_pointers"),
           pybind11::arg("part2Node"), pybind11::arg("partSize"), pybind11::arg("scale"), pybind11::arg("attn_drop") = 0.0,
           pybind11::arg("rng_seed") = 0, pybind11::arg("transposed") = pybind11::none());
+    m.def("dot_attn_forward_rows", &dot_attn_forward_rows,
+          "dot_attn_forward by kernels that own the rows they write (extension; gnna_dot_rows.h): no partition, no atomics, one pass "
+          "over column_index (K and V gathered once each), the same bits on every run -> (Y, lse)",
+          pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("heads"), pybind11::arg("row_pointers"),
+          pybind11::arg("column_index"), pybind11::arg("scale"), pybind11::arg("attn_drop") = 0.0, pybind11::arg("rng_seed") = 0);
+    m.def("dot_attn_backward_rows", &dot_attn_backward_rows,
+          "gradient of dot_attn_forward_rows for the same scale, attn_drop and rng_seed -> (dQ, dK, dV), without atomics (extension; "
+          "gnna_dot_rows.h).  The transposed CSR is always given (a symmetric structure: its own arrays); need = (dQ, dK, dV) wanted, "
+          "the others come back None",
+          pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("heads"), pybind11::arg("lse"), pybind11::arg("Y"),
+          pybind11::arg("dY"), pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("t_row_pointers"),
+          pybind11::arg("t_column_index"), pybind11::arg("scale"), pybind11::arg("attn_drop") = 0.0, pybind11::arg("rng_seed") = 0,
+          pybind11::arg("need") = std::vector<bool>{true, true, true});
     m.def("transpose_csr", &transpose_csr,
           "device-built CSR of A^T (extension) -> [t_row_pointers, t_column_index, t_perm]: row j lists the rows i of the edges i <- j in "
           "increasing position e, t_perm[p] = e (a stable argsort of column_index); ids outside [0, num_in_rows) are dropped",

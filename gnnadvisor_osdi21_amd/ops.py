@@ -1445,7 +1445,10 @@ class TransformerConv(Module):
     K[cols] are [nnz, heads * out]-sized torch work (index_select, product, sum), then EdgeSoftmax, torch dropout and
     EdgeWeightedAggregate; it exists to be compared with.  With fused=True `inputInfo` may be a sampling.SampledBlock: X is
     [num_src, in], K and V cover all num_src rows, Q is the first num_dst rows and the skip connection reads X[:num_dst];
-    fused=False refuses a block.  float32 only.  attn_drop, ``forward(..., rng_seed=...)`` and ``last_rng_seed`` are GATConv's."""
+    fused=False refuses a block.  float32 only.  attn_drop, ``forward(..., rng_seed=...)`` and ``last_rng_seed`` are GATConv's.
+    fused="rows": the fused attention on DotAttentionRows -- kernels that own the rows they write, a one-pass forward, no atomics,
+    the same bits on every run (reproducible training; accepted under ``_lib.set_tuning(deterministic=1)``).  Everything said of
+    fused=True holds for it, attn_drop included: the mask rule is the same, so the two drop the same edges for the same seed."""
 
     def __init__(self, input_dim, output_dim, heads=1, concat=True, root_weight=True, attn_drop=0.0, fused=True):
         super().__init__()
@@ -1456,6 +1459,9 @@ class TransformerConv(Module):
             raise ValueError(f"TransformerConv: heads and output_dim must be >= 1 (got {heads}, {output_dim})")
         self.last_rng_seed = None
         self.heads, self.out_dim, self.concat = int(heads), int(output_dim), bool(concat)
+        self.rows = isinstance(fused, str)       # fused="rows": the fused attention on DotAttentionRows
+        if self.rows and fused != "rows":
+            raise ValueError(f'TransformerConv: fused must be True, False or "rows" (got {fused!r})')
         self.root_weight, self.fused = bool(root_weight), bool(fused)
         self.weights = Parameter(torch.empty(input_dim, 3 * self.heads * self.out_dim))
         if self.root_weight:
@@ -1486,10 +1492,11 @@ class TransformerConv(Module):
         P = torch.mm(X, self.weights)                       # [num_src, 3 * heads * out]: Q | K | V
         Q, K, V = P[:n, :W], P[:, W:2 * W], P[:, 2 * W:]
         if self.fused:
+            attention = DotAttentionRows if self.rows else DotAttention
             if drop:
-                Y = DotAttention.apply(Q, K, V, inputInfo, self.heads, None, self.attn_drop, _step_seed(self, rng_seed))
+                Y = attention.apply(Q, K, V, inputInfo, self.heads, None, self.attn_drop, _step_seed(self, rng_seed))
             else:
-                Y = DotAttention.apply(Q, K, V, inputInfo, self.heads)
+                Y = attention.apply(Q, K, V, inputInfo, self.heads)
         else:
             rows, ci = inputInfo.edge_rows(), inputInfo.column_index
             qk = Q.index_select(0, rows) * K.index_select(0, ci)                       # [nnz, heads * out]
@@ -2047,3 +2054,5 @@ class GraphNorm(Module):
 
 # ops.GATAttentionRows: the fused GAT attention by row-owning kernels lives in a module of its own (which reads this one's helpers)
 from .gat_rows import GATAttentionRows  # noqa: E402,F401
+# ops.DotAttentionRows: likewise, the fused dot-product attention by row-owning kernels
+from .dot_rows import DotAttentionRows  # noqa: E402,F401
