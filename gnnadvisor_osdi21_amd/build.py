@@ -33,7 +33,7 @@ PUBLIC_HEADERS = ("gnna.h", "gnna_ext.h", "gnna_gatv2.h", "gnna_dotattn.h", "gnn
                   "gnna_pool.h", "gnna_attnpool.h", "gnna_topk.h", "gnna_segnorm.h", "gnna_walk.h", "gnna_edgefeat.h",
                   "gnna_spatial.h", "gnna_gat_rows.h", "gnna_dot_rows.h")
 INTERNAL_HEADERS = ("gnna_internal.h", "gnna_device.h", "gnna_launch.h", "gnna_gat_common.h", "gnna_keys.h", "gnna_segments.h",
-                    "gnna_parts.h", "gnna_prepass.h", "gnna_rowwalk.h")
+                    "gnna_parts.h", "gnna_prepass.h", "gnna_rowwalk.h", "gnna_ownrows.h")
 # sources compiled with flags of their own, after the common ones: the float4 arithmetic of the rows kernels without packed fp32 ops
 _NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"gnna_gat_rows.hip": _NO_PK, "gnna_dot_rows.hip": _NO_PK}

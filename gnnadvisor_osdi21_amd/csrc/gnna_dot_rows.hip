@@ -2,8 +2,9 @@
 // gnna_dot_attn_backward_rows_f32; include/gnna_dot_rows.h): the function of gnna_dotattn.hip by kernels that own the rows they
 // write.  CDNA4 / gfx950 only.  No counterpart in the reference (it has no attention layer).
 //
-// One kernel body, three passes, with or without the dropout mask.  Ownership is that of gnna_gat_rows.hip, restated here (one
-// shared copy for both rows families is a refactor of its own): R = 64 / LPR consecutive rows per wavefront, a row by its own
+// One kernel body, three passes, with or without the dropout mask.  Ownership is that of gnna_gat_rows.hip, restated here (the
+// limits and the host side are shared, gnna_ownrows.h; one shared kernel skeleton is not yet: profiles/ownrows/README.md):
+// R = 64 / LPR consecutive rows per wavefront, a row by its own
 // slot, by the slots of its wavefront or by the whole workgroup, by its degree alone; ids one step ahead; no neighbor-group
 // partition, no atomics, no zero-fill.  The lane layout is attn_layout's: LPH = next_pow2(ceil(dim / 4)) lanes of 4 floats cover a
 // head, LPR = LPH * (heads of a column block) <= 64 lanes a row, rows wider than one wave-wide load go in column blocks of whole
@@ -43,6 +44,7 @@
 #include "gnna_device.h"
 #include "gnna_gat_common.h"     // the lane-layout folds, load_piece, set_drop, check_drop, check_alias
 #include "gnna_internal.h"
+#include "gnna_ownrows.h"        // the ownership limits, the host side of the rows entries
 #include "gnna_rowwalk.h"        // wave_max
 #include "gnna_segments.h"       // seg::store_piece, seg::exp_nonpos
 
@@ -60,13 +62,8 @@ using seg::store_piece;
 // The larger of {2, 4} at which no instance has a private segment or a spill: at 4 the backward passes spill 4 to 8 SGPRs (with
 // and without the mask) and the source side with the mask drops to 3 waves per SIMD (the table per pass).
 constexpr int kEdges = 2;
-// a row of up to this many edges is walked by its own slot (wavefronts of more than one slot only)
-constexpr int kSlotEdges = 8;
-// a row that would keep its wavefront for more than kLongSteps steps goes to the whole block: more than
-// (slots of a wavefront) * kEdges * kLongSteps = (64 / LPR) * 128 edges
-constexpr int kLongSteps = 128 / kEdges;
-static_assert(kSlotEdges == 8 && kEdges * kLongSteps == 128,
-              "include/gnna_dot_rows.h states the limits as 8 edges for a slot and (64 / LPR) * 128 edges for a wavefront");
+using own::kSlotEdges;                          // the two ownership limits: gnna_ownrows.h
+constexpr int kLongSteps = own::kLongSteps<kEdges>;
 
 constexpr int kSlotDotRowsPack = 21;    // library scratch: (lse, c) per (destination row, head) of a backward call
 
@@ -493,8 +490,7 @@ template <int PASS>
 int launch(const Args &a, hipStream_t stream, const char *noun)
 {
     const AttnLayout layout = attn_layout(a.heads, a.dim);                  // (dim <= kMaxDim: log_lph is never capped)
-    const int64_t rows_per_block = (int64_t)(kWave >> layout.log_lpr) * kWavesPerBlock;
-    const dim3 grid((unsigned)std::max<int64_t>(1, (a.rows + rows_per_block - 1) / rows_per_block));       // (rows < 2^29)
+    const dim3 grid = own::rows_grid(a.rows, layout);
     auto with_mask = [&](auto D) {
         dispatch_layout(layout, [&](auto H, auto L) {
             hipLaunchKernelGGL((dot_rows_kernel<PASS, decltype(H)::value, decltype(L)::value, decltype(D)::value>), grid, dim3(kBlock),
@@ -506,23 +502,14 @@ int launch(const Args &a, hipStream_t stream, const char *noun)
     return launch_ok("%s launch", noun);
 }
 
-// what both entries check alike, before any device work: the checks of gnna_gat_rows.hip's entries (no partition, no refusal
-// under gnna_tuning.deterministic = 1), then attn_drop and scale as the dot entries check them
+// what both entries check alike, before any device work: the checks of every rows entry, then attn_drop and scale as the dot
+// entries check them
 int check_sizes(const char *what, int64_t num_out_rows, int64_t num_in_rows, int heads, int dim, unsigned flags, unsigned allowed_flags,
                 float attn_drop, float scale)
 {
-    if (flags & GNNA_ACCUMULATE) return fail(GNNA_ERR_UNSUPPORTED, "%s: GNNA_ACCUMULATE is not supported", what);
-    if (flags & ~allowed_flags) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", what, flags);
-    if (num_out_rows < 0 || num_in_rows < 0 || heads < 1 || dim < 1)
-        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: bad size (num_out_rows=%lld num_in_rows=%lld heads=%d dim=%d)", what,
-                    (long long)num_out_rows, (long long)num_in_rows, heads, dim);
-    const int64_t most = std::max(num_out_rows, num_in_rows);
-    if (most >= ((int64_t)1 << 29))
-        return fail(GNNA_ERR_UNSUPPORTED, "%s: %lld rows in one call (at most 536870911): shard the rows", what, (long long)most);
-    if (dim > gat::kMaxDim) return fail(GNNA_ERR_UNSUPPORTED, "%s: at most %d floats per head (got %d)", what, gat::kMaxDim, dim);
-    if (heads > 64) return fail(GNNA_ERR_UNSUPPORTED, "%s: at most 64 heads (got %d)", what, heads);
-    const int rc = gat::check_drop(what, attn_drop);
+    int rc = own::check_rows_sizes(what, num_out_rows, num_in_rows, heads, dim, flags, allowed_flags);
     if (rc != GNNA_OK) return rc;
+    if ((rc = gat::check_drop(what, attn_drop)) != GNNA_OK) return rc;
     // (0 is uniform attention, a negative scale is allowed)
     if (!std::isfinite(scale)) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: scale must be finite (got %g)", what, (double)scale);
     return GNNA_OK;
@@ -593,11 +580,8 @@ int gnna_dot_attn_backward_rows_f32(const float *Q, int64_t ld_q, const float *K
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     float2 *pack = nullptr;
     if (!one_side && want_src) {
-        DeviceState *ds = nullptr;
-        if ((rc = get_device_state(&ds)) != GNNA_OK) return rc;
         void *ws = nullptr;
-        if ((rc = get_workspace(ds, stream, kSlotDotRowsPack, align256((size_t)num_out_rows * heads * sizeof(float2)), &ws)) != GNNA_OK)
-            return rc;
+        if ((rc = own::record_scratch(stream, kSlotDotRowsPack, (size_t)num_out_rows * heads * sizeof(float2), &ws)) != GNNA_OK) return rc;
         pack = static_cast<float2 *>(ws);
     }
     Args a{};

@@ -35,6 +35,7 @@
 #include "gnna_device.h"
 #include "gnna_gat_common.h"     // the lane-layout folds, load_piece, leaky, check_alias
 #include "gnna_internal.h"
+#include "gnna_ownrows.h"        // the ownership limits, the host side of the rows entries
 #include "gnna_rowwalk.h"        // wave_max
 #include "gnna_segments.h"       // seg::store_piece, seg::exp_nonpos
 
@@ -52,12 +53,8 @@ using seg::store_piece;
 // edges per slot and step = gathered row pieces in flight per lane (the source side gathers a 16-byte record beside each).  Not
 // tuned: 4 is between gnna_edgefeat.hip's 2 (two row pieces per edge) and the 8 of the atomic gather.
 constexpr int kEdges = 4;
-// a row of up to this many edges is walked by its own slot (wavefronts of more than one slot only): gnna_edgefeat.hip's limit
-constexpr int kSlotEdges = 8;
-// a row that would keep its wavefront for more than kLongSteps steps goes to the whole block: more than
-// (slots of a wavefront) * kEdges * kLongSteps = (64 / LPR) * 128 edges
-constexpr int kLongSteps = 32;
-static_assert(kEdges * kLongSteps == 128, "include/gnna_gat_rows.h states the long-row limit as (64 / LPR) * 128 edges");
+using own::kSlotEdges;                          // the two ownership limits: gnna_ownrows.h
+constexpr int kLongSteps = own::kLongSteps<kEdges>;
 
 constexpr int kSlotGatRowsPack = 20;    // library scratch: (el, lse, c, 0) per (destination row, head) of a backward call
 
@@ -423,29 +420,11 @@ template <int PASS>
 int launch(const Args &a, hipStream_t stream, const char *noun)
 {
     const AttnLayout layout = attn_layout(a.heads, a.dim);                  // (dim <= kMaxDim: log_lph is never capped)
-    const int64_t rows_per_block = (int64_t)(kWave >> layout.log_lpr) * kWavesPerBlock;
-    const dim3 grid((unsigned)std::max<int64_t>(1, (a.rows + rows_per_block - 1) / rows_per_block));       // (rows < 2^29)
+    const dim3 grid = own::rows_grid(a.rows, layout);
     dispatch_layout(layout, [&](auto H, auto L) {
         hipLaunchKernelGGL((gat_rows_kernel<PASS, decltype(H)::value, decltype(L)::value>), grid, dim3(kBlock), 0, stream, a);
     });
     return launch_ok("%s launch", noun);
-}
-
-// what both entries check alike, before any device work: the checks of the rect entries without the partition, and without their
-// refusal under gnna_tuning.deterministic = 1
-int check_sizes(const char *what, int64_t num_out_rows, int64_t num_in_rows, int heads, int dim, unsigned flags, unsigned allowed_flags)
-{
-    if (flags & GNNA_ACCUMULATE) return fail(GNNA_ERR_UNSUPPORTED, "%s: GNNA_ACCUMULATE is not supported", what);
-    if (flags & ~allowed_flags) return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", what, flags);
-    if (num_out_rows < 0 || num_in_rows < 0 || heads < 1 || dim < 1)
-        return fail(GNNA_ERR_INVALID_ARGUMENT, "%s: bad size (num_out_rows=%lld num_in_rows=%lld heads=%d dim=%d)", what,
-                    (long long)num_out_rows, (long long)num_in_rows, heads, dim);
-    const int64_t most = std::max(num_out_rows, num_in_rows);
-    if (most >= ((int64_t)1 << 29))
-        return fail(GNNA_ERR_UNSUPPORTED, "%s: %lld rows in one call (at most 536870911): shard the rows", what, (long long)most);
-    if (dim > gat::kMaxDim) return fail(GNNA_ERR_UNSUPPORTED, "%s: at most %d floats per head (got %d)", what, gat::kMaxDim, dim);
-    if (heads > 64) return fail(GNNA_ERR_UNSUPPORTED, "%s: at most 64 heads (got %d)", what, heads);
-    return GNNA_OK;
 }
 
 }  // namespace
@@ -460,7 +439,7 @@ int gnna_gat_forward_rows_f32(const float *H, int64_t ld_h, int64_t num_in_rows,
                               int64_t ld_out, float *lse, int64_t num_out_rows, int heads, int dim, unsigned flags, void *stream_v)
 {
     static const char what[] = "gnna_gat_forward_rows_f32";
-    const int rc = check_sizes(what, num_out_rows, num_in_rows, heads, dim, flags, GNNA_ACCUMULATE | GNNA_EPILOGUE_RELU);
+    const int rc = own::check_rows_sizes(what, num_out_rows, num_in_rows, heads, dim, flags, GNNA_ACCUMULATE | GNNA_EPILOGUE_RELU);
     if (rc != GNNA_OK) return rc;
     if (num_out_rows == 0) return GNNA_OK;                    // nothing to write
     const int64_t W = (int64_t)heads * dim;
@@ -486,7 +465,7 @@ int gnna_gat_backward_rows_f32(const float *H, int64_t ld_h, int64_t num_in_rows
                                int heads, int dim, unsigned flags, void *stream_v)
 {
     static const char what[] = "gnna_gat_backward_rows_f32";
-    int rc = check_sizes(what, num_out_rows, num_in_rows, heads, dim, flags, GNNA_ACCUMULATE);
+    int rc = own::check_rows_sizes(what, num_out_rows, num_in_rows, heads, dim, flags, GNNA_ACCUMULATE);
     if (rc != GNNA_OK) return rc;
     const int64_t W = (int64_t)heads * dim;
     const bool want_dh = dH && num_in_rows > 0, want_der = d_er && num_in_rows > 0, want_del = d_el && num_out_rows > 0;
@@ -507,10 +486,8 @@ int gnna_gat_backward_rows_f32(const float *H, int64_t ld_h, int64_t num_in_rows
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     VT *pack = nullptr;
     if (!one_side && want_src) {
-        DeviceState *ds = nullptr;
-        if ((rc = get_device_state(&ds)) != GNNA_OK) return rc;
         void *ws = nullptr;
-        if ((rc = get_workspace(ds, stream, kSlotGatRowsPack, align256((size_t)num_out_rows * heads * sizeof(VT)), &ws)) != GNNA_OK) return rc;
+        if ((rc = own::record_scratch(stream, kSlotGatRowsPack, (size_t)num_out_rows * heads * sizeof(VT), &ws)) != GNNA_OK) return rc;
         pack = static_cast<VT *>(ws);
     }
     if (want_del || pack) {

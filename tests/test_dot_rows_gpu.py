@@ -81,12 +81,13 @@ def test_the_five_outputs_against_fp64(which, heads, dim):
 
 
 @pytest.mark.parametrize("heads,dim", [(4, 16), (3, 5)])
-def test_the_mask_is_the_fused_paths_and_leaves_lse_alone(heads, dim):
+@pytest.mark.parametrize("which", ["hub", "limits"])          # limits: the key's row on slot-owned and workgroup-owned rows of A^T
+def test_the_mask_is_the_fused_paths_and_leaves_lse_alone(which, heads, dim):
     seed = 2 ** 63 + 11
-    s, ins, r = _case("hub", heads, dim, 0.5, seed)
+    s, ins, r = _case(which, heads, dim, 0.5, seed)
     got = _run(s, *ins, heads, dim, 0.5, seed)
     assert r.k is not None and bool((r.k == 0).any()) and bool((r.k == 2).any())
-    _within_the_bound(f"hub {heads}x{dim} attn_drop=0.5", got, r)
+    _within_the_bound(f"{which} {heads}x{dim} attn_drop=0.5", got, r)
     assert torch.equal(got[1], _run(s, *ins, heads, dim)[1]), "lse is that of the un-dropped scores"
 
 
