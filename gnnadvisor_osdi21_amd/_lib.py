@@ -226,6 +226,11 @@ HEADERS["gnna_dot_rows.h"] = {
     "gnna_dot_attn_backward_rows_f32": (i, [p, i64] * 3 + [i64, p, p, i64, p, i64, p, p, p, p, f, f, u64] + [p, i64] * 3 +
                                         [i64, i, i, u, p]),
 }
+# the same by kernels over bfloat16 / float16 storage with float32 accumulation: `type` in front, the argument lists of gnna_dot_rows.h
+HEADERS["gnna_dot_rows_x16.h"] = {
+    "gnna_dot_attn_forward_rows_x16": (i, [i] + HEADERS["gnna_dot_rows.h"]["gnna_dot_attn_forward_rows_f32"][1]),
+    "gnna_dot_attn_backward_rows_x16": (i, [i] + HEADERS["gnna_dot_rows.h"]["gnna_dot_attn_backward_rows_f32"][1]),
+}
 del p, i, i64, u, u64, f, s, pd, pi, pi64
 EXPORTS = tuple(HEADERS["gnna.h"])     # users: the build's check of the library, tests/test_host.py
 
@@ -1583,12 +1588,14 @@ def gatv2_backward(Hs, Hd, att, lse, Y, dY, row_pointers, column_index, part_poi
     return dHs, dHd, d_att
 
 
-def _dot_attn_sizes(Q, K, V, heads, row_pointers):
+def _dot_attn_sizes(Q, K, V, heads, row_pointers, view=None):
     """(Q's pointer, ld_q, K's pointer, ld_k, V's pointer, ld_v, num_out_rows, num_in_rows, width) of a dot-product attention call,
-    taken from the tensors: num_out_rows = Q.shape[0] = row_pointers.numel() - 1, num_in_rows = K.shape[0] = V.shape[0]."""
-    qp, n_out, width, ld_q = _rows_view(Q, "Q")
-    kp, n_in, width_k, ld_k = _rows_view(K, "K")
-    vp, n_v, width_v, ld_v = _rows_view(V, "V")
+    taken from the tensors: num_out_rows = Q.shape[0] = row_pointers.numel() - 1, num_in_rows = K.shape[0] = V.shape[0].  view:
+    _rows_view (float32, the default) or _rows_view_any (the 16-bit entries)."""
+    view = view or _rows_view
+    qp, n_out, width, ld_q = view(Q, "Q")
+    kp, n_in, width_k, ld_k = view(K, "K")
+    vp, n_v, width_v, ld_v = view(V, "V")
     assert width_k == width and width_v == width and n_v == n_in and K.device == Q.device and V.device == Q.device, \
         "Q must be [num_out_rows, heads * dim], K and V [num_in_rows, heads * dim]"
     assert int(heads) >= 1 and width % int(heads) == 0, f"heads = {heads} must divide the row width {width}"
@@ -1718,6 +1725,73 @@ def dot_attn_backward_rows(Q, K, V, heads, lse, Y, dY, row_pointers, column_inde
         outs.append(t if wanted else None)
         args += [ptr, ld]
     _call(Q.device, "gnna_dot_attn_backward_rows_f32", qp, ld_q, kp, ld_k, vp, ld_v, n_in, lse.data_ptr(), yp, ld_y, gp, ld_g,
+          row_pointers.data_ptr(), column_index.data_ptr(), t_row_pointers.data_ptr(), t_column_index.data_ptr(), float(scale),
+          float(attn_drop), int(rng_seed), *args, n_out, heads, width // heads, 0)
+    return tuple(outs)
+
+
+def _dot_x16_type(who, *tensors):
+    """GNNA_BF16 / GNNA_F16 of a 16-bit dot-product attention call: every matrix of the call has the one 16-bit dtype."""
+    dt = tensors[0].dtype
+    if dt not in _X16_TYPES or any(t.dtype != dt for t in tensors):
+        raise GnnaError(f"{who} takes matrices that are all bfloat16 or all float16 (got {', '.join(str(t.dtype) for t in tensors)}); "
+                        "float32 goes through the _f32 function")
+    return _X16_TYPES[dt]
+
+
+def dot_attn_forward_rows_x16(Q, K, V, heads, row_pointers, column_index, scale=None, attn_drop=0.0, rng_seed=0, out=None, lse=None,
+                              relu=False):
+    """gnna_dot_attn_forward_rows_x16 (include/gnna_dot_rows_x16.h): dot_attn_forward_rows over bfloat16 / float16 Q, K and V with
+    float32 accumulation -> (out in that dtype, each element rounded once; lse float32).  The same bits on every run; accepted
+    under ``set_tuning(deterministic=1)``.  Views whose base is 16-byte aligned and whose row stride and head width are multiples
+    of 8 move by 16-byte accesses, any others element by element -- with the same bits."""
+    _need_device(Q, "dot-product attention")
+    qp, ld_q, kp, ld_k, vp, ld_v, n_out, n_in, width = _dot_attn_sizes(Q, K, V, heads, row_pointers, _rows_view_any)
+    heads = int(heads)
+    if scale is None:
+        scale = 1.0 / math.sqrt(width // heads)
+    if out is None:
+        out = _fresh_output((n_out, width), Q.device, Q.dtype)
+    if lse is None:
+        lse = _fresh_output((n_out, heads), Q.device)
+    type_ = _dot_x16_type("dot_attn_forward_rows_x16", Q, K, V, out)
+    op_, n_o, width_o, ld_out = _rows_view_any(out, "out")
+    assert n_o == n_out and width_o == width and _node_heads(lse, n_out, "lse") == heads
+    _call(Q.device, "gnna_dot_attn_forward_rows_x16", type_, qp, ld_q, kp, ld_k, vp, ld_v, n_in, row_pointers.data_ptr(),
+          column_index.data_ptr(), float(scale), float(attn_drop), int(rng_seed), op_, ld_out, lse.data_ptr(), n_out, heads,
+          width // heads, _flags(relu=relu))
+    return out, lse
+
+
+def dot_attn_backward_rows_x16(Q, K, V, heads, lse, Y, dY, row_pointers, column_index, t_row_pointers, t_column_index, scale=None,
+                               attn_drop=0.0, rng_seed=0, dQ=None, dK=None, dV=None, want=(True, True, True)):
+    """gnna_dot_attn_backward_rows_x16 (include/gnna_dot_rows_x16.h): dot_attn_backward_rows over bfloat16 / float16 matrices (Q, K,
+    V, Y, dY and the gradients all of one dtype; lse float32) with float32 accumulation.  Y is the rounded output of the forward."""
+    _need_device(Q, "dot-product attention")
+    qp, ld_q, kp, ld_k, vp, ld_v, n_out, n_in, width = _dot_attn_sizes(Q, K, V, heads, row_pointers, _rows_view_any)
+    heads = int(heads)
+    if scale is None:
+        scale = 1.0 / math.sqrt(width // heads)
+    yp, n_y, width_y, ld_y = _rows_view_any(Y, "Y")
+    gp, n_g, width_g, ld_g = _rows_view_any(dY, "dY")
+    assert _node_heads(lse, n_out, "lse") == heads
+    assert (n_y, width_y) == (n_out, width) and (n_g, width_g) == (n_out, width), "Y and dY must be [num_out_rows, heads * dim]"
+    for t in (row_pointers, column_index, t_row_pointers, t_column_index):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.device == Q.device, \
+            "the graph and its transpose must be contiguous int32 tensors on Q's device"
+    assert t_row_pointers.numel() == n_in + 1, "transposed: [num_in_rows + 1] row pointers"
+    outs, args = [], []
+    for wanted, t, rows, name in zip(want, (dQ, dK, dV), (n_out, n_in, n_in), ("dQ", "dK", "dV")):
+        ptr, ld = None, width
+        if wanted:
+            if t is None:
+                t = _fresh_output((rows, width), Q.device, Q.dtype)
+            ptr, n_t, width_t, ld = _rows_view_any(t, name)
+            assert (n_t, width_t) == (rows, width), "dQ / dK / dV must have the shapes of Q / K / V"
+        outs.append(t if wanted else None)
+        args += [ptr, ld]
+    type_ = _dot_x16_type("dot_attn_backward_rows_x16", Q, K, V, Y, dY, *(t for t in outs if t is not None))
+    _call(Q.device, "gnna_dot_attn_backward_rows_x16", type_, qp, ld_q, kp, ld_k, vp, ld_v, n_in, lse.data_ptr(), yp, ld_y, gp, ld_g,
           row_pointers.data_ptr(), column_index.data_ptr(), t_row_pointers.data_ptr(), t_column_index.data_ptr(), float(scale),
           float(attn_drop), int(rng_seed), *args, n_out, heads, width // heads, 0)
     return tuple(outs)

@@ -56,12 +56,13 @@ void dispatch_lpr(int log_lpr, F &&f)
 
 // Lane layout of the fused attention kernels (gnna_gat.hip, gnna_gatv2.hip, gnna_dotattn.hip): 2^log_lph lanes of 4 floats cover
 // a head of `dim` floats, 2^log_lpr lanes a row of a column block -- as many whole heads as fit in a wavefront, `heads` at most.
+// elems_per_lane = 8: the lanes of 8 16-bit elements of gnna_dot_rows_x16.hip.
 struct AttnLayout {
     int log_lph, log_lpr;
 };
-inline AttnLayout attn_layout(int heads, int dim)
+inline AttnLayout attn_layout(int heads, int dim, int elems_per_lane = 4)
 {
-    const int log_lph = log2_lanes(dim, 4);
+    const int log_lph = log2_lanes(dim, elems_per_lane);
     int log_lpr = log_lph;
     while (log_lpr < 6 && (1 << (log_lpr - log_lph)) < heads) log_lpr++;
     return {log_lph, log_lpr};

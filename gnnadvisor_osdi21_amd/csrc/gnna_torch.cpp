@@ -47,6 +47,7 @@
 #include "gnna_edgefeat.h"
 #include "gnna_gat_rows.h"
 #include "gnna_dot_rows.h"
+#include "gnna_dot_rows_x16.h"
 
 #define CHECK_CUDA(x) TORCH_CHECK(x.is_cuda(), #x " must be a CUDA tensor")
 #define CHECK_CONTIGUOUS(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -1416,6 +1417,78 @@ dot_attn_backward_rows(const torch::Tensor &Q_in, const torch::Tensor &K_in, con
     return std::make_tuple(dQ, dK, dV);
 }
 
+// The same over bfloat16 / float16 matrices with float32 accumulation (gnna_dot_rows_x16.h): every matrix of a call has Q's 16-bit
+// dtype, lse stays float32, and the results come back in that dtype, each element rounded once.
+static int dot_x16_type(const torch::Tensor &Q)
+{
+    TORCH_CHECK(Q.scalar_type() == at::kBFloat16 || Q.scalar_type() == at::kHalf, "Q must be bfloat16 or float16 (got ", Q.scalar_type(),
+                "); float32 goes through the function without _x16");
+    return Q.scalar_type() == at::kBFloat16 ? GNNA_BF16 : GNNA_F16;
+}
+
+static torch::Tensor dot_x16_rows(const torch::Tensor &t, const char *what, int64_t n, int64_t width, const torch::Tensor &Q)
+{
+    CHECK_CUDA(t);
+    TORCH_CHECK(t.scalar_type() == Q.scalar_type(), what, " must have Q's dtype ", Q.scalar_type(), " (got ", t.scalar_type(), ")");
+    TORCH_CHECK(t.dim() == 2 && t.size(0) == n && t.size(1) == width, what, " must be [", n, ", heads * dim = ", width, "]");
+    const bool rows_ok = (width <= 1 || t.stride(1) == 1) && (n <= 1 || t.stride(0) >= width);
+    return rows_ok ? t : t.contiguous();
+}
+
+std::tuple<torch::Tensor, torch::Tensor>
+dot_attn_forward_rows_x16(const torch::Tensor &Q_in, const torch::Tensor &K_in, const torch::Tensor &V_in, int64_t heads,
+                          const torch::Tensor &row_pointers, const torch::Tensor &column_index, double scale, double attn_drop,
+                          uint64_t rng_seed)
+{
+    dot_attn_shapes(Q_in, K_in, V_in, heads, scale);
+    const int type = dot_x16_type(Q_in);
+    const int64_t n_in = K_in.size(0), n_out = Q_in.size(0), width = Q_in.size(1);
+    const torch::Tensor Q = dot_x16_rows(Q_in, "Q", n_out, width, Q_in), K = dot_x16_rows(K_in, "K", n_in, width, Q_in),
+                        V = dot_x16_rows(V_in, "V", n_in, width, Q_in);
+    gat_rows_check_csr(Q, n_out, row_pointers, column_index);
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(Q.device());
+    auto Y = fresh({n_out, width}, Q.options()), lse = fresh({n_out, heads}, Q.options().dtype(at::kFloat));
+    check_rc(gnna_dot_attn_forward_rows_x16(type, Q.data_ptr(), ld_of(Q), K.data_ptr(), ld_of(K), V.data_ptr(), ld_of(V), n_in,
+                                            row_pointers.data_ptr<int32_t>(), softagg_ids(column_index, row_pointers), (float)scale,
+                                            (float)attn_drop, rng_seed, Y.data_ptr(), width, lse.data_ptr<float>(), n_out, (int)heads,
+                                            (int)(width / heads), 0u, current_stream()));
+    return std::make_tuple(Y, lse);
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
+dot_attn_backward_rows_x16(const torch::Tensor &Q_in, const torch::Tensor &K_in, const torch::Tensor &V_in, int64_t heads,
+                           const torch::Tensor &lse, const torch::Tensor &Y_in, const torch::Tensor &dY_in, const torch::Tensor &row_pointers,
+                           const torch::Tensor &column_index, const torch::Tensor &t_row_pointers, const torch::Tensor &t_column_index,
+                           double scale, double attn_drop, uint64_t rng_seed, const std::vector<bool> &need)
+{
+    dot_attn_shapes(Q_in, K_in, V_in, heads, scale);
+    const int type = dot_x16_type(Q_in);
+    const int64_t n_in = K_in.size(0), n_out = Q_in.size(0), width = Q_in.size(1);
+    TORCH_CHECK(need.size() == 3, "need must be (dQ, dK, dV)");
+    const torch::Tensor Q = dot_x16_rows(Q_in, "Q", n_out, width, Q_in), K = dot_x16_rows(K_in, "K", n_in, width, Q_in),
+                        V = dot_x16_rows(V_in, "V", n_in, width, Q_in), Y = dot_x16_rows(Y_in, "Y", n_out, width, Q_in),
+                        dY = dot_x16_rows(dY_in, "dY", n_out, width, Q_in);
+    check_floats(lse, "lse");
+    TORCH_CHECK(lse.dim() == 2 && lse.size(0) == n_out && lse.size(1) == heads && lse.device() == Q.device(),
+                "lse must be [num_out_rows, heads] on Q's device");
+    TORCH_CHECK(Y.device() == Q.device() && dY.device() == Q.device(), "Q, Y and dY must be on one device");
+    gat_rows_check_csr(Q, n_out, row_pointers, column_index);
+    gat_rows_check_csr(Q, n_in, t_row_pointers, t_column_index);
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(Q.device());
+    torch::Tensor dQ, dK, dV;
+    if (need[0]) dQ = fresh({n_out, width}, Q.options());
+    if (need[1]) dK = fresh({n_in, width}, Q.options());
+    if (need[2]) dV = fresh({n_in, width}, Q.options());
+    check_rc(gnna_dot_attn_backward_rows_x16(type, Q.data_ptr(), ld_of(Q), K.data_ptr(), ld_of(K), V.data_ptr(), ld_of(V), n_in,
+                                             lse.data_ptr<float>(), Y.data_ptr(), ld_of(Y), dY.data_ptr(), ld_of(dY),
+                                             row_pointers.data_ptr<int32_t>(), softagg_ids(column_index, row_pointers),
+                                             t_row_pointers.data_ptr<int32_t>(), softagg_ids(t_column_index, t_row_pointers),
+                                             (float)scale, (float)attn_drop, rng_seed, need[0] ? dQ.data_ptr() : nullptr, width,
+                                             need[1] ? dK.data_ptr() : nullptr, width, need[2] ? dV.data_ptr() : nullptr, width, n_out,
+                                             (int)heads, (int)(width / heads), 0u, current_stream()));
+    return std::make_tuple(dQ, dK, dV);
+}
+
 // SDDMM (gnna_sddmm_ld_f32): edge_out[e] = <A[row(e)], B[column_index[e]]>; A and B may be row-strided views.
 torch::Tensor sddmm(const torch::Tensor &A, const torch::Tensor &B, const torch::Tensor &column_index,
                     const torch::Tensor &part_pointers, const torch::Tensor &part2Node, int partSize)
@@ -2192,6 +2265,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           "gradient of dot_attn_forward_rows for the same scale, attn_drop and rng_seed -> (dQ, dK, dV), without atomics (extension; "
           "gnna_dot_rows.h).  The transposed CSR is always given (a symmetric structure: its own arrays); need = (dQ, dK, dV) wanted, "
           "the others come back None",
+          pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("heads"), pybind11::arg("lse"), pybind11::arg("Y"),
+          pybind11::arg("dY"), pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("t_row_pointers"),
+          pybind11::arg("t_column_index"), pybind11::arg("scale"), pybind11::arg("attn_drop") = 0.0, pybind11::arg("rng_seed") = 0,
+          pybind11::arg("need") = std::vector<bool>{true, true, true});
+    m.def("dot_attn_forward_rows_x16", &dot_attn_forward_rows_x16,
+          "dot_attn_forward_rows over bfloat16 / float16 Q, K and V, accumulated in float32 (extension; gnna_dot_rows_x16.h) -> (Y in "
+          "that dtype, each element rounded once; lse float32).  The same bits on every run",
+          pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("heads"), pybind11::arg("row_pointers"),
+          pybind11::arg("column_index"), pybind11::arg("scale"), pybind11::arg("attn_drop") = 0.0, pybind11::arg("rng_seed") = 0);
+    m.def("dot_attn_backward_rows_x16", &dot_attn_backward_rows_x16,
+          "gradient of dot_attn_forward_rows_x16 -> (dQ, dK, dV) in the inputs' 16-bit dtype (extension; gnna_dot_rows_x16.h); Y is the "
+          "rounded output of the forward, lse float32; the other arguments as dot_attn_backward_rows",
           pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"), pybind11::arg("heads"), pybind11::arg("lse"), pybind11::arg("Y"),
           pybind11::arg("dY"), pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("t_row_pointers"),
           pybind11::arg("t_column_index"), pybind11::arg("scale"), pybind11::arg("attn_drop") = 0.0, pybind11::arg("rng_seed") = 0,

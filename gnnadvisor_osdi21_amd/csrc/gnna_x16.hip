@@ -30,6 +30,7 @@
 #include <cstdint>
 
 #include "gnna.h"
+#include "gnna_convert16.h"
 #include "gnna_device.h"
 #include "gnna_internal.h"
 
@@ -38,50 +39,10 @@ namespace {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
-// the two 16-bit elements of one 32-bit word, widened (exact in both formats)
-template <int TYPE>
-__device__ __forceinline__ void widen2(uint32_t w, float &lo, float &hi)
-{
-    if constexpr (TYPE == GNNA_BF16) {
-        lo = __uint_as_float(w << 16);
-        hi = __uint_as_float(w & 0xffff0000u);
-    } else {
-        const f16x2 h = __builtin_bit_cast(f16x2, w);
-        lo = (float)h.x;
-        hi = (float)h.y;
-    }
-}
-
-// one fp32 value -> the 16 bits of its round-to-nearest-even bf16 / fp16 (overflow: +-inf, NaN stays NaN)
-template <int TYPE>
-__device__ __forceinline__ uint16_t narrow1(float v)
-{
-    if constexpr (TYPE == GNNA_BF16) {
-        const __hip_bfloat16 r = __float2bfloat16(v);
-        uint16_t u;
-        __builtin_memcpy(&u, &r, sizeof(u));
-        return u;
-    } else {
-        return __builtin_bit_cast(uint16_t, (_Float16)v);
-    }
-}
-template <int TYPE>
-__device__ __forceinline__ uint32_t narrow2(float a, float b)
-{
-    if constexpr (TYPE == GNNA_BF16) {
-        const __hip_bfloat162 r = __float22bfloat162_rn(make_float2(a, b));     // v_cvt_pk_bf16_f32
-        uint32_t u;
-        __builtin_memcpy(&u, &r, sizeof(u));
-        return u;
-    } else {
-        f16x2 r;
-        r.x = (_Float16)a;                                                       // v_cvt_f16_f32 (round-to-nearest-even)
-        r.y = (_Float16)b;
-        return __builtin_bit_cast(uint32_t, r);
-    }
-}
+using cvt16::narrow1;           // the conversions: gnna_convert16.h
+using cvt16::narrow2;
+using cvt16::widen2;
 
 // Reduce-scatter steps over the lane pairs (l, l ^ STRIDE): the lanes whose STRIDE bit is clear get a(l) + a(l ^ STRIDE), the
 // others b(l) + b(l ^ STRIDE).

@@ -133,7 +133,9 @@ def main(argv=None, capture=None):
     if attention and flag(args.hip_graph):
         # (the attention layers build their per-edge arrays and the SDDMM's id copies at first use: not captured yet)
         raise SystemExit("--model %s does not support --hip_graph True: run it with --hip_graph False" % args.model)
-    if args.dtype != 'float32' and attention:
+    # (16-bit storage exists for one attention path: the transformer on the row-owned kernels, gnna_dot_rows_x16.h)
+    x16_rows = args.model == 'transformer' and args.fused_attention == 'rows'
+    if args.dtype != 'float32' and attention and not x16_rows:
         raise SystemExit("--dtype %s: the attention layers (edge-weighted aggregation, SDDMM, edge softmax) are float32 only; "
                          "run --model %s with --dtype float32" % (args.dtype, args.model))
     if args.dtype != 'float32' and args.model == 'sage':
@@ -435,7 +437,7 @@ def main(argv=None, capture=None):
                     return F.log_softmax(x, dim=1)
                 x = F.elu(self.conv1(dataset.x, inputInfo.set_input()))
                 x = self.conv2(x, inputInfo.set_hidden())
-                return F.log_softmax(x, dim=1)
+                return F.log_softmax(x.float(), dim=1)      # (--dtype bfloat16 / float16 with --fused_attention rows: the loss in fp32)
     elif args.model == 'sage':
         inputInfo.inv_row_counts()      # (the mean's row factors: built here, not inside a captured epoch)
 
@@ -525,7 +527,8 @@ def main(argv=None, capture=None):
         # features and parameters stored in 16 bits; every aggregation accumulates in fp32 and rounds its result once
         dataset.x = dataset.x.to(getattr(torch, args.dtype))
         model = model.to(getattr(torch, args.dtype))
-        _gnna_lib.prepare_x16(dataset.num_nodes, dataset.num_nodes, _prep_widths, device=device)
+        if not x16_rows:                # (the rows attention has no scratch to size: its records are made at the first backward)
+            _gnna_lib.prepare_x16(dataset.num_nodes, dataset.num_nodes, _prep_widths, device=device)
     if capture is not None:
         capture.update(dataset=dataset, inputInfo=inputInfo, model=model, args=args)
     if verbose_mode:

@@ -68,8 +68,9 @@ def _refuse_block(info, layer):
                         "(GATAttention, GATConv(fused=True))")
 
 
-def _block_features(X, block, what):
-    if X.dtype != torch.float32:
+def _block_features(X, block, what, x16=False):
+    """x16: bfloat16 / float16 rows are taken too (the callers with a 16-bit kernel behind them)."""
+    if X.dtype != torch.float32 and not (x16 and X.dtype in _X16):
         raise TypeError(f"{what} on a SampledBlock: float32 features only (got {X.dtype})")
     if X.dim() != 2 or X.shape[0] != block.num_src:
         raise ValueError(f"{what} on a SampledBlock: X must be [num_src = {block.num_src}, F] (got {tuple(X.shape)})")
@@ -1448,7 +1449,10 @@ class TransformerConv(Module):
     fused=False refuses a block.  float32 only.  attn_drop, ``forward(..., rng_seed=...)`` and ``last_rng_seed`` are GATConv's.
     fused="rows": the fused attention on DotAttentionRows -- kernels that own the rows they write, a one-pass forward, no atomics,
     the same bits on every run (reproducible training; accepted under ``_lib.set_tuning(deterministic=1)``).  Everything said of
-    fused=True holds for it, attn_drop included: the mask rule is the same, so the two drop the same edges for the same seed."""
+    fused=True holds for it, attn_drop included: the mask rule is the same, so the two drop the same edges for the same seed.
+    fused="rows" also computes in 16 bits -- bfloat16 / float16 X (a cast model) or float32 X inside torch.autocast("cuda",
+    dtype=bfloat16 | float16): both products are torch.mm in that dtype, the attention runs on the x16 entries (float32 sums, one
+    rounding per output element) and stays bit-reproducible; the other two forms stay float32 only."""
 
     def __init__(self, input_dim, output_dim, heads=1, concat=True, root_weight=True, attn_drop=0.0, fused=True):
         super().__init__()
@@ -1482,14 +1486,21 @@ class TransformerConv(Module):
         drop = self.training and self.attn_drop > 0.0
         if block and not self.fused:
             _refuse_block(inputInfo, "TransformerConv(fused=False)")
-        if X.dtype != torch.float32 or _x16_dtype(X) is not None:
+        dt = _x16_dtype(X)                                  # fused="rows" alone computes in 16 bits (gnna_dot_rows_x16.h)
+        if X.dtype not in (torch.float32,) + _X16 or (dt is not None and not self.rows):
             raise TypeError("TransformerConv computes in float32 only: 16-bit features and torch.autocast are not "
                             f"supported (got {X.dtype}{', inside torch.autocast' if X.dtype == torch.float32 else ''})")
         if block:
-            X = _block_features(X, inputInfo, "TransformerConv")
+            X = _block_features(X, inputInfo, "TransformerConv", x16=dt is not None)
         n = inputInfo.num_dst if block else X.shape[0]      # rows of the result
         W = self.heads * self.out_dim
-        P = torch.mm(X, self.weights)                       # [num_src, 3 * heads * out]: Q | K | V
+        weights, W_skip = self.weights, self.W_skip
+        if dt is not None:
+            # a cast model or torch.autocast: both products are torch.mm on 16-bit operands, the attention keeps fp32 sums and
+            # returns that dtype; fp32 parameters and an fp32 X get their gradients in fp32 through the casts
+            X, weights = X.to(dt), weights.to(dt)
+            W_skip = None if W_skip is None else W_skip.to(dt)
+        P = torch.mm(X, weights)                            # [num_src, 3 * heads * out]: Q | K | V
         Q, K, V = P[:n, :W], P[:, W:2 * W], P[:, 2 * W:]
         if self.fused:
             attention = DotAttentionRows if self.rows else DotAttention
@@ -1507,8 +1518,8 @@ class TransformerConv(Module):
             Y = EdgeWeightedAggregate.apply(V.contiguous(), alpha, inputInfo)
         if not (self.concat or self.heads == 1):
             Y = Y.view(n, self.heads, self.out_dim).mean(1)
-        if self.W_skip is not None:
-            Y = Y + torch.mm(X[:n] if block else X, self.W_skip)
+        if W_skip is not None:
+            Y = Y + torch.mm(X[:n] if block else X, W_skip)
         return Y
 
 

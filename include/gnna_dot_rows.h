@@ -58,7 +58,7 @@
  * row beyond that by the four wavefronts of its workgroup, which meet through LDS in the order of the wavefronts.  A row is owned
  * by at most one workgroup: there is no hub splitting.
  *
- * Out of scope: a per-edge score term, GATv2 (gnna_gatv2.h), 16-bit storage.
+ * Out of scope: a per-edge score term, GATv2 (gnna_gatv2.h).  bfloat16 / float16 storage: gnna_dot_rows_x16.h.
  *
  * Checks, before any device work: GNNA_ACCUMULATE, unknown flag bits, sizes >= 0 with heads, dim >= 1, row counts < 2^29,
  * dim <= 256, heads <= 64, attn_drop in [0, 1) and not NaN, a finite scale (0 is uniform attention), row strides >= heads * dim
