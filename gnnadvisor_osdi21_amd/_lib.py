@@ -231,6 +231,16 @@ HEADERS["gnna_dot_rows_x16.h"] = {
     "gnna_dot_attn_forward_rows_x16": (i, [i] + HEADERS["gnna_dot_rows.h"]["gnna_dot_attn_forward_rows_f32"][1]),
     "gnna_dot_attn_backward_rows_x16": (i, [i] + HEADERS["gnna_dot_rows.h"]["gnna_dot_attn_backward_rows_f32"][1]),
 }
+# fused GATv2 attention by row-owning kernels: one-pass forward, no partition, no atomics (d_att included), the same bits on every run
+HEADERS["gnna_gatv2_rows.h"] = {
+    # Hs, ld_hs, Hd, ld_hd, att, num_in_rows, row_pointers, column_index, slope, attn_drop, rng_seed, out, ld_out, lse, num_out_rows,
+    # heads, dim, flags, stream
+    "gnna_gatv2_forward_rows_f32": (i, [p, i64] * 2 + [p, i64, p, p, f, f, u64, p, i64, p, i64, i, i, u, p]),
+    # Hs, ld_hs, Hd, ld_hd, att, num_in_rows, lse, (Y, ld) (dY, ld), the structure, the transposed structure, slope, attn_drop,
+    # rng_seed, (dHs, ld) (dHd, ld), d_att, num_out_rows, heads, dim, flags, stream
+    "gnna_gatv2_backward_rows_f32": (i, [p, i64] * 2 + [p, i64, p, p, i64, p, i64, p, p, p, p, f, f, u64] + [p, i64] * 2 +
+                                     [p, i64, i, i, u, p]),
+}
 del p, i, i64, u, u64, f, s, pd, pi, pi64
 EXPORTS = tuple(HEADERS["gnna.h"])     # users: the build's check of the library, tests/test_host.py
 
@@ -1586,6 +1596,63 @@ def gatv2_backward(Hs, Hd, att, lse, Y, dY, row_pointers, column_index, part_poi
           float(attn_drop), int(rng_seed), sgp, ld_dhs, dgp, ld_dhd, d_att.data_ptr(), n_out, n_in, heads, width // heads,
           int(partSize), 0)
     return dHs, dHd, d_att
+
+
+def gatv2_forward_rows(Hs, Hd, att, row_pointers, column_index, negative_slope=0.2, attn_drop=0.0, rng_seed=0, out=None, lse=None,
+                       relu=False):
+    """gnna_gatv2_forward_rows_f32 (include/gnna_gatv2_rows.h): the function of gatv2_forward by kernels that own the rows they
+    write -- no partition, no atomics, no zero-fill, ONE pass over column_index in which Hs[j] is gathered once (the softmax is
+    online); the same bits on every run and accepted under ``set_tuning(deterministic=1)``.  Shapes, strided views and the mask
+    as gatv2_forward.  -> (out, lse)."""
+    _need_device(Hs, "GATv2 attention")
+    sp, ld_hs, dp, ld_hd, n_out, n_in, width, heads = _gatv2_sizes(Hs, Hd, att, row_pointers)
+    if out is None:
+        out = _fresh_output((n_out, width), Hs.device)
+    if lse is None:
+        lse = _fresh_output((n_out, heads), Hs.device)
+    op_, n_o, width_o, ld_out = _rows_view(out, "out")
+    assert n_o == n_out and width_o == width and _node_heads(lse, n_out, "lse") == heads
+    _call(Hs.device, "gnna_gatv2_forward_rows_f32", sp, ld_hs, dp, ld_hd, att.data_ptr(), n_in, row_pointers.data_ptr(),
+          column_index.data_ptr(), float(negative_slope), float(attn_drop), int(rng_seed), op_, ld_out, lse.data_ptr(), n_out, heads,
+          width // heads, _flags(relu=relu))
+    return out, lse
+
+
+def gatv2_backward_rows(Hs, Hd, att, lse, Y, dY, row_pointers, column_index, t_row_pointers, t_column_index, negative_slope=0.2,
+                        attn_drop=0.0, rng_seed=0, dHs=None, dHd=None, d_att=None, want=(True, True, True)):
+    """gnna_gatv2_backward_rows_f32 (include/gnna_gatv2_rows.h): (dHs, dHd, d_att) of gatv2_forward_rows for the gradient dY of its
+    output Y (same negative_slope, attn_drop and rng_seed), without atomics -- d_att too: one partial per workgroup, summed in a
+    fixed order.  The transposed structure (num_in_rows rows) is always given; a graph whose structure is symmetric gives its own
+    arrays twice.  want: which of the three are made -- the others come back None, and work that serves only those is not done."""
+    _need_device(Hs, "GATv2 attention")
+    sp, ld_hs, dp, ld_hd, n_out, n_in, width, heads = _gatv2_sizes(Hs, Hd, att, row_pointers)
+    yp, n_y, width_y, ld_y = _rows_view(Y, "Y")
+    gp, n_g, width_g, ld_g = _rows_view(dY, "dY")
+    assert _node_heads(lse, n_out, "lse") == heads
+    assert (n_y, width_y) == (n_out, width) and (n_g, width_g) == (n_out, width), "Y and dY must be [num_out_rows, heads * dim]"
+    for t in (row_pointers, column_index, t_row_pointers, t_column_index):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.device == Hs.device, \
+            "the graph and its transpose must be contiguous int32 tensors on Hs's device"
+    assert t_row_pointers.numel() == n_in + 1, "transposed: [num_in_rows + 1] row pointers"
+    outs, args = [], []
+    for wanted, t, rows, name in zip(want, (dHs, dHd), (n_in, n_out), ("dHs", "dHd")):
+        ptr, ld = None, width
+        if wanted:
+            if t is None:
+                t = _fresh_output((rows, width), Hs.device)
+            ptr, n_t, width_t, ld = _rows_view(t, name)
+            assert (n_t, width_t) == (rows, width), "dHs / dHd must have the shapes of Hs / Hd"
+        outs.append(t if wanted else None)
+        args += [ptr, ld]
+    if want[2]:
+        if d_att is None:
+            d_att = _fresh_output(tuple(att.shape), Hs.device)
+        assert d_att.dtype == torch.float32 and d_att.is_contiguous() and d_att.numel() == width and d_att.device == Hs.device
+    outs.append(d_att if want[2] else None)
+    _call(Hs.device, "gnna_gatv2_backward_rows_f32", sp, ld_hs, dp, ld_hd, att.data_ptr(), n_in, lse.data_ptr(), yp, ld_y, gp, ld_g,
+          row_pointers.data_ptr(), column_index.data_ptr(), t_row_pointers.data_ptr(), t_column_index.data_ptr(),
+          float(negative_slope), float(attn_drop), int(rng_seed), *args, _ptr(outs[2]), n_out, heads, width // heads, 0)
+    return tuple(outs)
 
 
 def _dot_attn_sizes(Q, K, V, heads, row_pointers, view=None):

@@ -48,6 +48,7 @@
 #include "gnna_gat_rows.h"
 #include "gnna_dot_rows.h"
 #include "gnna_dot_rows_x16.h"
+#include "gnna_gatv2_rows.h"
 
 #define CHECK_CUDA(x) TORCH_CHECK(x.is_cuda(), #x " must be a CUDA tensor")
 #define CHECK_CONTIGUOUS(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -1295,6 +1296,59 @@ gatv2_backward(const torch::Tensor &Hs_in, const torch::Tensor &Hd_in, const tor
     return std::make_tuple(dHs, dHd, d_att);
 }
 
+// The rows form of the fused GATv2 attention (gnna_gatv2_rows.h): gatv2_forward / gatv2_backward by kernels that own the rows they
+// write.  The CSR alone is the graph (no partition), and the backward always takes the transposed CSR.
+std::tuple<torch::Tensor, torch::Tensor>
+gatv2_forward_rows(const torch::Tensor &Hs_in, const torch::Tensor &Hd_in, const torch::Tensor &att, const torch::Tensor &row_pointers,
+                   const torch::Tensor &column_index, double negative_slope, double attn_drop, uint64_t rng_seed)
+{
+    const int heads = gatv2_heads(Hs_in, Hd_in, att);
+    const int64_t n_in = Hs_in.size(0), n_out = Hd_in.size(0), width = Hs_in.size(1);
+    const torch::Tensor Hs = gat_rows(Hs_in, "Hs", n_in, width), Hd = gat_rows(Hd_in, "Hd", n_out, width);
+    gat_rows_check_csr(Hs, n_out, row_pointers, column_index);
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(Hs.device());
+    auto Y = fresh({n_out, width}, att.options()), lse = fresh({n_out, (int64_t)heads}, att.options());
+    check_rc(gnna_gatv2_forward_rows_f32(Hs.data_ptr<float>(), ld_of(Hs), Hd.data_ptr<float>(), ld_of(Hd), att.data_ptr<float>(), n_in,
+                                         row_pointers.data_ptr<int32_t>(), softagg_ids(column_index, row_pointers),
+                                         (float)negative_slope, (float)attn_drop, rng_seed, Y.data_ptr<float>(), width,
+                                         lse.data_ptr<float>(), n_out, heads, (int)(width / heads), 0u, current_stream()));
+    return std::make_tuple(Y, lse);
+}
+
+// need = (dHs, dHd, d_att) wanted: an output that is not comes back undefined (None), and work that serves only it is not done
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
+gatv2_backward_rows(const torch::Tensor &Hs_in, const torch::Tensor &Hd_in, const torch::Tensor &att, const torch::Tensor &lse,
+                    const torch::Tensor &Y_in, const torch::Tensor &dY_in, const torch::Tensor &row_pointers,
+                    const torch::Tensor &column_index, const torch::Tensor &t_row_pointers, const torch::Tensor &t_column_index,
+                    double negative_slope, double attn_drop, uint64_t rng_seed, const std::vector<bool> &need)
+{
+    const int heads = gatv2_heads(Hs_in, Hd_in, att);
+    const int64_t n_in = Hs_in.size(0), n_out = Hd_in.size(0), width = Hs_in.size(1);
+    TORCH_CHECK(need.size() == 3, "need must be (dHs, dHd, d_att)");
+    const torch::Tensor Hs = gat_rows(Hs_in, "Hs", n_in, width), Hd = gat_rows(Hd_in, "Hd", n_out, width),
+                        Y = gat_rows(Y_in, "Y", n_out, width), dY = gat_rows(dY_in, "dY", n_out, width);
+    check_floats(lse, "lse");
+    TORCH_CHECK(lse.dim() == 2 && lse.size(0) == n_out && lse.size(1) == heads && lse.device() == Hs.device(),
+                "lse must be [num_out_rows, heads] on Hs's device");
+    TORCH_CHECK(Y.device() == Hs.device() && dY.device() == Hs.device(), "Hs, Y and dY must be on one device");
+    gat_rows_check_csr(Hs, n_out, row_pointers, column_index);
+    gat_rows_check_csr(Hs, n_in, t_row_pointers, t_column_index);
+    at::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(Hs.device());
+    torch::Tensor dHs, dHd, d_att;
+    if (need[0]) dHs = fresh({n_in, width}, att.options());
+    if (need[1]) dHd = fresh({n_out, width}, att.options());
+    if (need[2]) d_att = fresh(att.sizes(), att.options());
+    check_rc(gnna_gatv2_backward_rows_f32(Hs.data_ptr<float>(), ld_of(Hs), Hd.data_ptr<float>(), ld_of(Hd), att.data_ptr<float>(), n_in,
+                                          lse.data_ptr<float>(), Y.data_ptr<float>(), ld_of(Y), dY.data_ptr<float>(), ld_of(dY),
+                                          row_pointers.data_ptr<int32_t>(), softagg_ids(column_index, row_pointers),
+                                          t_row_pointers.data_ptr<int32_t>(), softagg_ids(t_column_index, t_row_pointers),
+                                          (float)negative_slope, (float)attn_drop, rng_seed,
+                                          need[0] ? dHs.data_ptr<float>() : nullptr, width, need[1] ? dHd.data_ptr<float>() : nullptr,
+                                          width, need[2] ? d_att.data_ptr<float>() : nullptr, n_out, heads, (int)(width / heads), 0u,
+                                          current_stream()));
+    return std::make_tuple(dHs, dHd, d_att);
+}
+
 // Fused scaled dot-product graph attention (gnna_dot_attn_forward_f32 / gnna_dot_attn_backward_f32, gnna_dotattn.h): Q [num_out_rows,
 // heads * dim] with num_out_rows = row_pointers.numel() - 1, K and V [num_in_rows, heads * dim].  One (rectangular) entry for every
 // structure; attn_drop = 0 is the plain function.  Q, K and V go through their leading dimensions: column slices of one projection
@@ -2241,6 +2295,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("part_pointers"), pybind11::arg("part2Node"),
           pybind11::arg("partSize"), pybind11::arg("negative_slope") = 0.2, pybind11::arg("attn_drop") = 0.0, pybind11::arg("rng_seed") = 0,
           pybind11::arg("transposed") = pybind11::none());
+    m.def("gatv2_forward_rows", &gatv2_forward_rows,
+          "gatv2_forward by kernels that own the rows they write (extension; gnna_gatv2_rows.h): no partition, no atomics, one pass "
+          "over column_index (Hs gathered once per edge), the same bits on every run -> (Y, lse)",
+          pybind11::arg("Hs"), pybind11::arg("Hd"), pybind11::arg("att"), pybind11::arg("row_pointers"), pybind11::arg("column_index"),
+          pybind11::arg("negative_slope") = 0.2, pybind11::arg("attn_drop") = 0.0, pybind11::arg("rng_seed") = 0);
+    m.def("gatv2_backward_rows", &gatv2_backward_rows,
+          "gradient of gatv2_forward_rows for the same negative_slope, attn_drop and rng_seed -> (dHs, dHd, d_att), without atomics "
+          "(extension; gnna_gatv2_rows.h).  The transposed CSR is always given (a symmetric structure: its own arrays); need = (dHs, "
+          "dHd, d_att) wanted, the others come back None",
+          pybind11::arg("Hs"), pybind11::arg("Hd"), pybind11::arg("att"), pybind11::arg("lse"), pybind11::arg("Y"), pybind11::arg("dY"),
+          pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("t_row_pointers"), pybind11::arg("t_column_index"),
+          pybind11::arg("negative_slope") = 0.2, pybind11::arg("attn_drop") = 0.0, pybind11::arg("rng_seed") = 0,
+          pybind11::arg("need") = std::vector<bool>{true, true, true});
     m.def("dot_attn_forward", &dot_attn_forward,
           "fused multi-head scaled dot-product graph attention -> (Y, lse) (extension; gnna_dotattn.h): z = scale * <Q[i, h], K[col(e), h]>, "
           "Y[i, h] = sum_e exp(z - lse[i, h]) * k * V[col(e), h] with the dropout factor k of gat_forward_drop (1 at attn_drop = 0).  "

@@ -79,7 +79,9 @@ def build_parser():
     p.add_argument('--fused_attention', default='False', choices=['True', 'False', 'rows'],
                    help="rows: --model gat runs both layers on the fused attention by kernels that own the rows they write "
                         "(GATConv(fused=\"rows\"): no atomics, the same bits on every run; without --attn_drop and --edge_dim); "
-                        "--model transformer likewise (TransformerConv(fused=\"rows\"): a one-pass forward; --attn_drop is allowed).  "
+                        "--model transformer likewise (TransformerConv(fused=\"rows\"): a one-pass forward; --attn_drop is allowed) "
+                        "and --model gatv2 (GATv2Conv(fused=\"rows\"): a one-pass forward, the gradient of att without atomics; "
+                        "--attn_drop is allowed).  "
                         "True: --model gat runs both layers on the fused attention kernels (GATConv(fused=True): alpha is made "
                         "from node-sized values where the rows are gathered, no per-edge tensor; MI355X addition); --model gatv2 likewise "
                         "(GATv2Conv(fused=...): False is the composed path with [nnz, heads * hidden] tensors) and --model transformer "
@@ -168,9 +170,9 @@ def main(argv=None, capture=None):
         raise SystemExit("--heads must be >= 1")
     fused_rows = args.fused_attention == 'rows'
     if fused_rows:
-        if args.model not in ('gat', 'transformer'):
-            raise SystemExit("--fused_attention rows selects the row-owned attention kernels: run it with --model gat or --model "
-                             "transformer (got --model %s)" % args.model)
+        if args.model not in ('gat', 'gatv2', 'transformer'):
+            raise SystemExit("--fused_attention rows selects the row-owned attention kernels: run it with --model gat, --model gatv2 "
+                             "or --model transformer (got --model %s)" % args.model)
         if args.model == 'gat' and (args.attn_drop != 0.0 or args.edge_dim > 0):
             raise SystemExit("--fused_attention rows has no attention dropout and no edge features: run --attn_drop / --edge_dim "
                              "with --fused_attention True")
@@ -402,7 +404,7 @@ def main(argv=None, capture=None):
                 x = self.conv2(x, inputInfo.set_hidden(), edge_attr=edges_of(None))
                 return F.log_softmax(x, dim=1)
     elif args.model == 'gatv2':
-        fused = flag(args.fused_attention)
+        fused = "rows" if fused_rows else flag(args.fused_attention)
 
         class Net(torch.nn.Module):
             def __init__(self):

@@ -1320,7 +1320,11 @@ class GATv2Conv(Module):
     EdgeSoftmax, torch dropout and EdgeWeightedAggregate; it exists to be compared with, and its memory is why it is not the default.
     With fused=True `inputInfo` may be a sampling.SampledBlock: X is [num_src, in], Hs covers all num_src rows and Hd is
     X[:num_dst] W_r (with share_weights: the first num_dst rows of Hs); fused=False refuses a block.  float32 only.
-    attn_drop, ``forward(..., rng_seed=...)`` and ``last_rng_seed`` are GATConv's."""
+    attn_drop, ``forward(..., rng_seed=...)`` and ``last_rng_seed`` are GATConv's.
+    fused="rows": the fused attention on GATv2AttentionRows -- kernels that own the rows they write, a one-pass forward, no atomics
+    (the gradient of att included), the same bits on every run (reproducible training; accepted under
+    ``_lib.set_tuning(deterministic=1)``).  Everything said of fused=True holds for it, attn_drop, share_weights and blocks
+    included: the mask rule is the same, so the two drop the same edges for the same seed."""
 
     def __init__(self, input_dim, output_dim, heads=1, concat=True, negative_slope=0.2, share_weights=False, attn_drop=0.0,
                  fused=True):
@@ -1332,6 +1336,9 @@ class GATv2Conv(Module):
             raise ValueError(f"GATv2Conv: heads and output_dim must be >= 1 (got {heads}, {output_dim})")
         self.last_rng_seed = None
         self.heads, self.out_dim, self.concat, self.negative_slope = int(heads), int(output_dim), bool(concat), float(negative_slope)
+        self.rows = isinstance(fused, str)       # fused="rows": the fused attention on GATv2AttentionRows
+        if self.rows and fused != "rows":
+            raise ValueError(f'GATv2Conv: fused must be True, False or "rows" (got {fused!r})')
         self.share_weights, self.fused = bool(share_weights), bool(fused)
         self.W_l = Parameter(torch.empty(input_dim, self.heads * self.out_dim))
         if self.share_weights:
@@ -1366,11 +1373,11 @@ class GATv2Conv(Module):
         else:
             Hd = torch.mm(X[:n] if block else X, self.W_r)
         if self.fused:
+            attention = GATv2AttentionRows if self.rows else GATv2Attention
             if drop:
-                Y = GATv2Attention.apply(Hs, Hd, self.att, inputInfo, self.negative_slope, self.attn_drop,
-                                         _step_seed(self, rng_seed))
+                Y = attention.apply(Hs, Hd, self.att, inputInfo, self.negative_slope, self.attn_drop, _step_seed(self, rng_seed))
             else:
-                Y = GATv2Attention.apply(Hs, Hd, self.att, inputInfo, self.negative_slope)
+                Y = attention.apply(Hs, Hd, self.att, inputInfo, self.negative_slope)
         else:
             rows, ci = inputInfo.edge_rows(), inputInfo.column_index
             t = torch.nn.functional.leaky_relu(Hs.index_select(0, ci) + Hd.index_select(0, rows), self.negative_slope)
@@ -2067,3 +2074,5 @@ class GraphNorm(Module):
 from .gat_rows import GATAttentionRows  # noqa: E402,F401
 # ops.DotAttentionRows: likewise, the fused dot-product attention by row-owning kernels
 from .dot_rows import DotAttentionRows  # noqa: E402,F401
+# ops.GATv2AttentionRows: likewise, the fused GATv2 attention by row-owning kernels
+from .gatv2_rows import GATv2AttentionRows  # noqa: E402,F401
